@@ -11,6 +11,13 @@ N > 1) of sv_dgcnn_cls --binary, B=32 per GPU, N=1024, k=20, synthetic clouds re
 
 `--gpus N` without a launcher (WORLD_SIZE unset) starts the N ranks itself: N fresh child processes, one per GPU, before
 this process touches a GPU.  Rank 0 prints ONE JSON line (contract in the task statement).
+
+A plain run sets up, warms up, times the K steps and prints the line: nothing else.  `--full` adds everything measured next to
+the headline figure, each in runs of its own after the timed region: the forward-only leg, the roofline legs, the launch count of
+the captured graph, the collective's own cost (N > 1), and for the default workload the train-loop leg, the other BASELINE
+workloads and the CPU baseline (`--no-extras` / `--no-cpu-baseline` leave those out again).
+`--dump-outputs DIR` writes what the timed step computed in its last replay (train: loss.npy and grads.npy, the flat gradient bucket
+in model.parameters() order; eval: logits.npy) into DIR, so that two builds can be compared output for output on the same seeded inputs.
 """
 import argparse
 import contextlib
@@ -58,12 +65,18 @@ def parse_args():
     ap.add_argument("--workload", choices=tuple(WORKLOADS), default="dgcnn_cls",
                     help="which BASELINE.json config to run (default: the headline one, sv_dgcnn_cls --binary B=32 N=1024 k=20)")
     ap.add_argument("--no-graph", action="store_true", help="launch eagerly instead of replaying a HIP graph")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also run the secondary legs (forward only, roofline, graph launch count, collective "
+                         "cost, train loop, other workloads, CPU baseline); a plain run measures the headline figure only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed step computed in its last step as DIR/<name>.npy (train: loss and the flat gradient bucket; "
+                         "eval: logits)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--no-extras", action="store_true",
-                    help="default workload only: skip the other BASELINE configs' legs (other_workloads) and the train-loop leg")
+                    help="--full, default workload only: skip the other BASELINE configs' legs (other_workloads) and the train-loop leg")
     ap.add_argument("--force-collective", action="store_true",
                     help="--gpus 1 only: run the RCCL all-reduce(avg) of the real gradient bucket inside the timed loop at world size 1 "
-                         "(the collective's fixed cost on this box: collective_us)")
+                         "(with --full, the collective's fixed cost alone: collective_us)")
     ap.add_argument("--selftest-cpu", action="store_true",
                     help="NOT a benchmark: drive this file's rank plumbing (spawn, world-size check, process group, barrier, all_gather of the "
                          "per-rank clocks, max over ranks, rank-0-only JSON line, collective_us) on gloo / CPU with a stand-in step - "
@@ -604,6 +617,38 @@ class _SelftestStep:
         return loss
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def step_outputs(args, work, train):
+    """{name: host array} of what a caller of the timed step receives after its last run: train mode the loss and the flat gradient
+    bucket (every parameter's gradient, in model.parameters() order), eval mode the logits."""
+    import torch
+    if args.mode == "eval":
+        out = {"logits": work.out.detach()}
+    else:
+        out = {"loss": train.loss.detach().reshape(1), "grads": train.bucket.flat.detach()}
+    return {k: v.to(torch.float64 if v.dtype == torch.float64 else torch.float32).cpu().numpy() for k, v in out.items()}
+
+
+def dump_outputs(path, arrays, limit=DUMP_LIMIT_BYTES):
+    """Write {name: array} as path/<name>.npy.  Should the arrays exceed `limit` bytes in all, each one larger than 4096 elements is
+    replaced by a seeded sample of its flattened elements (sorted indices), in proportion to its size, so that all fit."""
+    import numpy as np
+    big = [n for n, a in arrays.items() if a.size > 4096]
+    small_bytes = sum(a.nbytes for n, a in arrays.items() if n not in big)
+    big_bytes = sum(arrays[n].nbytes for n in big)
+    if small_bytes + big_bytes > limit:
+        frac = (limit - small_bytes) / float(big_bytes)
+        for name in big:
+            a = arrays[name]
+            idx = np.sort(np.random.RandomState(0).choice(a.size, max(1, int(a.size * frac)), replace=False))
+            arrays[name] = a.reshape(-1)[idx]
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def rank_main(args):
     """One rank of the job (the whole job at --gpus 1).  The product run talks RCCL ("nccl") from cuda:LOCAL_RANK; --selftest-cpu runs
     the SAME control flow - process group, world-size check, barrier, per-rank clocks, max over ranks, rank-0-only line - on gloo / CPU
@@ -710,8 +755,10 @@ def rank_main(args):
     else:
         run_step = work.run
     elapsed, per_rank = timed(run_step, args.steps, args.warmup)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, step_outputs(args, work, train))
     collective_us = None
-    if collective and args.mode == "train":
+    if collective and args.mode == "train" and args.full:
         # the collective alone: `steps` back-to-back all-reduces of the bucket after the timed region (HIP events on the device)
         for _ in range(3):
             train.bucket.all_reduce_mean(force=True)
@@ -736,7 +783,7 @@ def rank_main(args):
 
     # secondary number: forward-only eval throughput next to the headline one (rank-local graph, after the timed region)
     fwd_only = None
-    if args.mode == "train" and world == 1 and not selftest:
+    if args.full and args.mode == "train" and world == 1 and not selftest:
         fs = ForwardStep(model, inputs)
         try:
             if not args.no_graph:
@@ -752,7 +799,7 @@ def rank_main(args):
     stages = per_launch = primary = None
     launches = None
     bucket_mb = train.bucket.flat.numel() * 4 / 1e6
-    if rank == 0 and not selftest:
+    if args.full and rank == 0 and not selftest:
         if args.workload == "dgcnn_cls":
             per_launch, stages = dgcnn_cls_legs(args, model, x, train, work, torch, _lib)
             primary = per_launch if args.mode == "train" else (stages or {}).get("knn_gather_forward")
@@ -761,8 +808,8 @@ def rank_main(args):
         if graph_ok:
             launches = graph_kernel_nodes(work)
 
-    extras = (args.workload == "dgcnn_cls" and args.mode == "train" and world == 1 and not args.no_extras and not args.no_graph
-              and not selftest)
+    extras = (args.full and args.workload == "dgcnn_cls" and args.mode == "train" and world == 1 and not args.no_extras
+              and not args.no_graph and not selftest)
     others = loop_leg = None
     if rank == 0 and extras:
         try:
@@ -822,7 +869,7 @@ def rank_main(args):
                 out["train_loop_ms_per_step"] = loop_leg["train_loop_ms_per_step"]
         if others:
             out["other_workloads"] = others
-        if world == 1 and not args.no_cpu_baseline and not selftest:
+        if args.full and world == 1 and not args.no_cpu_baseline and not selftest:
             # the headline workload at its own B = 32; the secondary workloads on a bounded sample (--workload runs only)
             out["cpu_baseline"] = cpu_baseline(wl, sample_b=None if args.workload == "dgcnn_cls" else (8 if wl["model"] != "sv_dgcnn_pseg" else 2))
         print(json.dumps(out))

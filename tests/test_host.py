@@ -216,7 +216,7 @@ def test_bench_rank_plumbing_runs_end_to_end_on_two_gloo_ranks(launcher):
     go through spawn (or the driver's `python -m torch.distributed.run` launch), the world-size check on the collective's own group, the
     barrier-bracketed timed region, the all_gather of the per-rank clocks, the max over ranks, the product's GradBucket.all_reduce_mean()
     and the rank-0-only JSON line with `rccl_world` and `collective_us`."""
-    rc, lines, err = _run_bench(["--gpus", "2", "--steps", "4", "--warmup", "1", "--selftest-cpu"], launcher=launcher)
+    rc, lines, err = _run_bench(["--gpus", "2", "--steps", "4", "--warmup", "1", "--selftest-cpu", "--full"], launcher=launcher)
     assert rc == 0, err[-2000:]
     assert len(lines) == 1, (lines, err[-2000:])                      # rank 0 only, ONE line
     out = json.loads(lines[0])
@@ -228,6 +228,41 @@ def test_bench_rank_plumbing_runs_end_to_end_on_two_gloo_ranks(launcher):
     assert abs(out["value"] - 64 * 1e3 / out["ms_per_step"]) < 1e-2 * out["value"]   # whole-job throughput: all ranks' clouds / that time
     assert out["config"]["collective_us"] is not None and out["config"]["collective_us"] > 0
     assert "cpu_baseline" not in out and "other_workloads" not in out                # world-1-only legs stay out of the N > 1 line
+
+
+def test_bench_plain_run_times_the_steps_only_and_dumps_the_last_step(tmp_path):
+    """A plain bench run (no --full) measures the headline figure and nothing else: no collective leg after the timed region.
+    --steps sets the timed steps; --dump-outputs writes the last step's loss and flat gradient bucket as float32 .npy files, the
+    same on every run with the same arguments."""
+    dumps = []
+    for run in range(2):
+        d = tmp_path / ("out%d" % run)
+        rc, lines, err = _run_bench(["--gpus", "2", "--steps", "3", "--warmup", "1", "--selftest-cpu", "--dump-outputs", str(d)])
+        assert rc == 0, err[-2000:]
+        assert len(lines) == 1, (lines, err[-2000:])
+        out = json.loads(lines[0])
+        assert out["steps"] == 3 and out["warmup"] == 1 and out["ms_per_step"] > 0
+        assert out["config"]["collective_us"] is None and "forward_only" not in out and "roofline_stages" not in out
+        files = sorted(os.listdir(d))
+        assert files == ["grads.npy", "loss.npy"], files
+        arrays = {f: np.load(os.path.join(d, f)) for f in files}
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrays.values())
+        n_params = 16 * 32 + 32 + 2 * 32 + 32 * 40 + 40                                # the stand-in step's Linear-BN-ReLU-Linear
+        assert arrays["grads.npy"].shape == (n_params,) and abs(arrays["grads.npy"]).max() > 0
+        assert abs(float(arrays["loss.npy"][0]) - out["loss"]) < 1e-5
+        dumps.append(arrays)
+    assert all(np.array_equal(dumps[0][f], dumps[1][f]) for f in dumps[0])
+
+
+def test_bench_dump_samples_outputs_beyond_the_size_limit(tmp_path):
+    """--dump-outputs stays within its size limit by writing a fixed, seeded sample of each large array."""
+    import bench
+    arrays = {"big": np.arange(100000, dtype=np.float32), "small": np.ones(10, np.float32)}
+    bench.dump_outputs(str(tmp_path), dict(arrays), limit=40000 + 40)
+    big = np.load(os.path.join(tmp_path, "big.npy"))
+    assert big.size == 10000 and np.all(np.diff(big) > 0) and np.array_equal(np.load(os.path.join(tmp_path, "small.npy")), arrays["small"])
+    bench.dump_outputs(str(tmp_path / "again"), dict(arrays), limit=40000 + 40)
+    assert np.array_equal(np.load(os.path.join(tmp_path, "again", "big.npy")), big)          # the same seeded sample every time
 
 
 def test_bench_parent_fails_when_a_rank_fails_and_refuses_a_wrong_world_size():
