@@ -71,7 +71,8 @@ typedef struct svnet_gate_bwd_job {
  * xx_mode: 0 = ||x||^2 summed the way ATen reduces an OUTER dim (contiguous [B,C,N]),
  *          1 = the way ATen reduces the CONTIGUOUS dim (transposed view of [B,N,C])   
  * idx_out: [B,N,k] int64, cloud-local neighbour ids, nearest first (self first), ties -> lowest id.
- * Bit-exact against the reference's torch-CPU result for C <= 384, N <= 4096, k <= 64.           */
+ * Bit-exact against the reference's torch-CPU result for C <= 384, N <= 32768, k <= 128 (k <= N); anything
+ * past those limits returns SVNET_E_UNSUPPORTED.                                                        */
 size_t svnet_knn_workspace_bytes(int64_t B, int64_t N, int64_t C);
 int svnet_knn_f32(const float* x, int64_t B, int64_t N, int64_t C, int64_t sb, int64_t sn, int64_t sc,
                   int xx_mode, int k, int64_t* idx_out, void* workspace, size_t workspace_bytes, void* stream);

@@ -940,6 +940,171 @@ __global__ __launch_bounds__(512, 4) void knn_mf8_kernel(const float* __restrict
     knn_select4<T>(acc, xxb, N, k, lane, rows + wave * (8 * SVNET_KNN_SLOTS), qid, idx_out + (size_t)b * N * k);
 }
 
+// ---- Streamed form: 4096 < N <= 32768 or 64 < k <= 128 (any N, any C <= 384).  A query can no longer hold all its candidate distances
+// in registers, so one wave takes 16 queries (the A operand of v_mfma_f32_16x16x4_f32) and walks the cloud in chunks of 64 candidates:
+//  * distance: the 16 x 64 inner products of a chunk on the matrix cores, four 16-candidate tiles, operands straight from the
+//    channel-major table (L2; every wave reads the whole table, 16 queries per pass over it).  The same bit-exact chain as the MF forms.
+//  * hand-over: through 4 KB of the wave's LDS, so that lane l holds candidate j0 + l of every query.
+//  * selection: each query keeps a running list of its 64 * KR first-ranked composite keys (ord_key(pd) << 32) | ~j in LDS, sorted,
+//    rank r at [r]; its k-th key stays in a register (lane q) as a wave-uniform threshold.  A chunk's candidates are tested against it
+//    (one 64-bit compare per lane); only when some lane beats it are the chunk's survivors sorted across the wave and bitonic-merged into
+//    the list.  A chunk holds at most 64 survivors, one per lane, so there is no overflow to handle, ties included.  The composite is a
+//    total order that agrees with "larger pd first, equal pd: lower index first", so the result depends neither on the chunking nor on
+//    the order in which chunks arrive.
+// One wave per workgroup (LDS per wave: 4.25 KB + 8 KB x KR; no barriers), XCD-aware cloud order as in knn_main_kernel.
+constexpr int KNN_ST_LD = 68;            // hand-over row stride: the four query groups a tile's lanes write lie 16 banks apart
+constexpr int KNN_ST_RING = 3;           // k-steps of operands in flight
+template <int KR>                        // list keys per lane: 1 (k <= 64), 2 (k <= 128: ranks l and 64 + l)
+__global__ __launch_bounds__(64) void knn_stream_kernel(const float* __restrict__ xT, const float* __restrict__ xx, int N, int C,
+                                                        int64_t cloud_rows, int k, int64_t* __restrict__ idx_out, int xcd_blocks_per_cloud) {
+    typedef __attribute__((ext_vector_type(4))) float f32x4;
+    __shared__ float tbuf[16 * KNN_ST_LD];
+    __shared__ uint32_t lhi[16 * 64 * KR], llo[16 * 64 * KR];
+    const int lane = threadIdx.x;
+    int bx = blockIdx.x, b = blockIdx.y;
+    if (gridDim.y == 1 && xcd_blocks_per_cloud > 0) {
+        const int w = blockIdx.x, per = xcd_blocks_per_cloud;
+        b = (w / (per * 8)) * 8 + (w & 7);
+        bx = (w >> 3) % per;
+    }
+    const int q0 = bx * 16;
+    const float* __restrict__ xb = xT + (size_t)b * cloud_rows * N;
+    const float* __restrict__ xxb = xx + (size_t)b * N;
+    const int kl = lane >> 4, jl = lane & 15;
+    for (int i = lane; i < 16 * 64 * KR; i += 64) { lhi[i] = 0u; llo[i] = 0u; }    // empty slots: key 0, below every candidate (~id: out of range)
+    uint32_t th_hi = 0u, th_lo = 0u;                                      // lane q < 16: query q's k-th key
+    const float xxq = xxb[min(q0 + jl, N - 1)];                           // lane q < 16: ||x||^2 of query q
+    const int nq = min(16, N - q0);
+
+    // operand stream over (chunk, k-step), KNN_ST_RING steps ahead; lane l: A[jl][kl] = x[4 s + kl][q0 + jl], B[kl][jl] = x[4 s + kl][j0 + 16 tt + jl].
+    // Channels past C: A is zero (B is read from row C - 1, finite), so the padded products add exact zeros.  Candidates past N: a clamped
+    // column, masked in the selection.
+    const int nks = (C + 3) >> 2;
+    const int qa = min(q0 + jl, N - 1);
+    int ls = 0, lj = 0;                                                  // k-step and chunk of the next load (past the end: the last chunk again)
+    float ar[KNN_ST_RING], br[KNN_ST_RING][4];
+#define SVNET_KNN_ST_LOAD(SLOT)                                                                                   \
+    do {                                                                                                          \
+        const int c_ = 4 * ls + kl;                                                                               \
+        const float* r_ = xb + (size_t)min(c_, C - 1) * N;                                                        \
+        const float a_ = r_[qa];                                                                                  \
+        ar[SLOT] = c_ < C ? a_ : 0.f;                                                                             \
+        _Pragma("unroll") for (int tt = 0; tt < 4; ++tt) br[SLOT][tt] = r_[min(lj + 16 * tt + jl, N - 1)];        \
+        if (++ls == nks) { ls = 0; lj = min(lj + 64, (N - 1) & ~63); }                                            \
+    } while (0)
+#pragma unroll
+    for (int u = 0; u < KNN_ST_RING; ++u) SVNET_KNN_ST_LOAD(u);
+
+    for (int j0 = 0; j0 < N; j0 += 64) {
+        f32x4 dacc[4];
+#pragma unroll
+        for (int tt = 0; tt < 4; ++tt) dacc[tt] = f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int s = 0; s < nks; ++s) {
+            const float a = ar[0];
+            float bv[4];
+#pragma unroll
+            for (int tt = 0; tt < 4; ++tt) bv[tt] = br[0][tt];
+#pragma unroll
+            for (int u = 0; u + 1 < KNN_ST_RING; ++u) {
+                ar[u] = ar[u + 1];
+#pragma unroll
+                for (int tt = 0; tt < 4; ++tt) br[u][tt] = br[u + 1][tt];
+            }
+            SVNET_KNN_ST_LOAD(KNN_ST_RING - 1);
+#pragma unroll
+            for (int tt = 0; tt < 4; ++tt) dacc[tt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bv[tt], dacc[tt], 0, 0, 0);
+        }
+        // D register g of tile tt in lane l: query 4 kl + g, candidate j0 + 16 tt + jl
+#pragma unroll
+        for (int tt = 0; tt < 4; ++tt)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) tbuf[(4 * kl + g) * KNN_ST_LD + 16 * tt + jl] = dacc[tt][g];
+        __syncthreads();                                                  // (one wave: orders the hand-over's LDS writes before its reads)
+        const int j = j0 + lane;
+        const float xxj = xxb[min(j, N - 1)];
+#pragma unroll 1
+        for (int q = 0; q < nq; ++q) {
+            const float inner = -2.0f * tbuf[q * KNN_ST_LD + lane];       // exact
+            const float t1 = __fsub_rn(-xxj, inner);                      // fl(-xx[j] - inner)
+            const float pd = __fsub_rn(t1, __int_as_float(__builtin_amdgcn_readlane(__float_as_int(xxq), q)));   // fl(.. - xx[i])
+            uint32_t hi = j < N ? ord_key(pd) : 0u, lo = j < N ? ~(uint32_t)j : 0u;
+            const uint32_t thh = (uint32_t)__builtin_amdgcn_readlane((int)th_hi, q), thl = (uint32_t)__builtin_amdgcn_readlane((int)th_lo, q);
+            const bool beat = ((((uint64_t)hi) << 32) | lo) > ((((uint64_t)thh) << 32) | thl);
+            if (__ballot(beat) == 0) continue;                            // (wave-uniform: the common case once the list has filled)
+            hi = beat ? hi : 0u;
+            lo = beat ? lo : 0u;
+            // the survivors, sorted descending across the wave (lane 0: first-ranked)
+#define SVNET_X_PAIR(K2) do { const uint32_t m_ = xform<K2>(lane); hi ^= m_; lo ^= m_; } while (0)
+            SVNET_X_PAIR(2); cx_pair<1>(hi, lo, lane);
+            SVNET_X_PAIR(4); cx_pair<2>(hi, lo, lane); cx_pair<1>(hi, lo, lane);
+            SVNET_X_PAIR(8); cx_pair<4>(hi, lo, lane); cx_pair<2>(hi, lo, lane); cx_pair<1>(hi, lo, lane);
+            SVNET_X_PAIR(16); cx_pair<8>(hi, lo, lane); cx_pair<4>(hi, lo, lane); cx_pair<2>(hi, lo, lane); cx_pair<1>(hi, lo, lane);
+            SVNET_X_PAIR(32); cx_pair<16>(hi, lo, lane); cx_pair<8>(hi, lo, lane); cx_pair<4>(hi, lo, lane); cx_pair<2>(hi, lo, lane);
+            cx_pair<1>(hi, lo, lane);
+            SVNET_X_PAIR(64); cx_pair<32>(hi, lo, lane); cx_pair<16>(hi, lo, lane); cx_pair<8>(hi, lo, lane); cx_pair<4>(hi, lo, lane);
+            cx_pair<2>(hi, lo, lane); cx_pair<1>(hi, lo, lane);
+#undef SVNET_X_PAIR
+            // bitonic merge: max(L[i], S[63 - i]) of two descending runs holds the 64 first-ranked of their union as a bitonic sequence
+            // (min(..): the 64 others), which the last six exchanges of the network sort
+#define SVNET_HALF_CLEAN(H, L) do { sort_step_pair<64, 32>(H, L, lane); sort_step_pair<64, 16>(H, L, lane); sort_step_pair<64, 8>(H, L, lane); \
+                                    sort_step_pair<64, 4>(H, L, lane); sort_step_pair<64, 2>(H, L, lane); sort_step_pair<64, 1>(H, L, lane); } while (0)
+            uint32_t* qh = lhi + q * 64 * KR;
+            uint32_t* ql = llo + q * 64 * KR;
+            uint32_t h0 = qh[lane], l0 = ql[lane];
+            uint32_t rh = (uint32_t)__shfl((int)hi, 63 - lane, 64), rl = (uint32_t)__shfl((int)lo, 63 - lane, 64);
+            const bool t0 = ((((uint64_t)rh) << 32) | rl) > ((((uint64_t)h0) << 32) | l0);
+            uint32_t mh = t0 ? h0 : rh, ml = t0 ? l0 : rl;               // (the 64 that rank after: into the second half of the list)
+            h0 = t0 ? rh : h0;
+            l0 = t0 ? rl : l0;
+            SVNET_HALF_CLEAN(h0, l0);
+            qh[lane] = h0;
+            ql[lane] = l0;
+            uint32_t kh, klo;
+            if (KR == 2) {
+                uint32_t h1 = qh[64 + lane], l1 = ql[64 + lane];
+                SVNET_HALF_CLEAN(mh, ml);
+                rh = (uint32_t)__shfl((int)mh, 63 - lane, 64);
+                rl = (uint32_t)__shfl((int)ml, 63 - lane, 64);
+                const bool t1b = ((((uint64_t)rh) << 32) | rl) > ((((uint64_t)h1) << 32) | l1);
+                h1 = t1b ? rh : h1;
+                l1 = t1b ? rl : l1;
+                SVNET_HALF_CLEAN(h1, l1);
+                qh[64 + lane] = h1;
+                ql[64 + lane] = l1;
+                kh = (uint32_t)__builtin_amdgcn_readlane((int)(k <= 64 ? h0 : h1), (k - 1) & 63);
+                klo = (uint32_t)__builtin_amdgcn_readlane((int)(k <= 64 ? l0 : l1), (k - 1) & 63);
+            } else {
+                kh = (uint32_t)__builtin_amdgcn_readlane((int)h0, k - 1);
+                klo = (uint32_t)__builtin_amdgcn_readlane((int)l0, k - 1);
+            }
+#undef SVNET_HALF_CLEAN
+            th_hi = lane == q ? kh : th_hi;
+            th_lo = lane == q ? klo : th_lo;
+        }
+        __syncthreads();                                                  // (the hand-over buffer has been read)
+    }
+#undef SVNET_KNN_ST_LOAD
+    // (NaN distances can leave slots at key 0, whose ~index is out of range: never hand such an id to the gathers)
+    int64_t* __restrict__ out = idx_out + (size_t)b * N * k;
+#pragma unroll 1
+    for (int q = 0; q < nq; ++q) {
+#pragma unroll
+        for (int r = 0; r < KR; ++r) {
+            const int rank = 64 * r + lane;
+            const uint32_t id = ~llo[q * 64 * KR + rank];
+            if (rank < k) out[(size_t)(q0 + q) * k + rank] = id < (uint32_t)N ? (int64_t)id : (int64_t)(q0 + q);
+        }
+    }
+}
+
+void launch_stream(const float* xT, const float* xx, int64_t B, int N, int C, int64_t cloud_rows, int k, int64_t* idx, hipStream_t st) {
+    dim3 grid((unsigned)svnet_cdiv(N, 16), (unsigned)B);
+    int per = 0;
+    if ((B & 7) == 0) { per = (int)grid.x; grid = dim3((unsigned)(grid.x * B), 1u); }   // XCD-aware cloud order
+    if (k <= 64) hipLaunchKernelGGL(knn_stream_kernel<1>, grid, dim3(64), 0, st, xT, xx, N, C, cloud_rows, k, idx, per);
+    else hipLaunchKernelGGL(knn_stream_kernel<2>, grid, dim3(64), 0, st, xT, xx, N, C, cloud_rows, k, idx, per);
+}
+
 template <int T, int Q>
 void launch_main(const float* xT, const float* xx, int64_t B, int N, int C, int k, int64_t* idx, hipStream_t st, bool mf8 = false) {
     dim3 grid((unsigned)svnet_cdiv(N, 4 * Q), (unsigned)B);
@@ -1005,6 +1170,15 @@ bool svnet_knn_table_is_channel_major(int64_t N, int64_t C, int64_t* Cpad) {
 }
 
 static int knn_run_main(const float* xT, const float* xx, int64_t B, int64_t N, int64_t C, int k, int64_t* idx_out, bool mf8, hipStream_t st);
+static int knn_run_stream(const float* xT, const float* xx, int64_t B, int64_t N, int64_t C, int64_t cloud_rows, int k, int64_t* idx_out,
+                          hipStream_t st);
+
+// The range the register-resident forms take (every shape they took before the streamed form existed still takes them) ...
+static bool knn_in_register_range(int64_t N, int k) { return N <= 4096 && k <= 64; }
+// ... and the whole range of the contract: past it the streamed form's limits (ids are 32-bit keys; a list holds 128) and MKL's K blocking
+#define SVNET_KNN_MAX_N 32768
+#define SVNET_KNN_MAX_K 128
+#define SVNET_KNN_MAX_C 384
 
 extern "C" int svnet_knn_table_fusable(int64_t B, int64_t N, int64_t C) {
     return B > 0 && N > 0 && (N % 32) == 0 && C >= 8 && C <= 384 && N <= 4096 && svnet_knn_table_is_channel_major(N, C, nullptr) ? 1 : 0;
@@ -1015,13 +1189,15 @@ extern "C" int svnet_knn_from_table_f32(const void* workspace, size_t workspace_
     SVNET_REQUIRE(workspace && idx_out, SVNET_E_ARG, "svnet_knn_from_table_f32: null pointer");
     SVNET_REQUIRE(B >= 0 && N > 0 && C > 0 && k > 0 && k <= N, SVNET_E_ARG, "svnet_knn_from_table_f32: bad sizes B=%lld N=%lld C=%lld k=%d",
                   (long long)B, (long long)N, (long long)C, k);
-    SVNET_REQUIRE(C <= 384 && N <= 4096 && k <= 64, SVNET_E_UNSUPPORTED, "svnet_knn_from_table_f32: outside C<=384, N<=4096, k<=64");
+    SVNET_REQUIRE(C <= SVNET_KNN_MAX_C && N <= 4096 && k <= SVNET_KNN_MAX_K, SVNET_E_UNSUPPORTED,
+                  "svnet_knn_from_table_f32: N=%lld C=%lld k=%d outside C<=384, N<=4096, k<=128", (long long)N, (long long)C, k);
     SVNET_REQUIRE(workspace_bytes >= svnet_knn_workspace_bytes(B, N, C), SVNET_E_WORKSPACE, "svnet_knn_from_table_f32: workspace too small");
     const KnnLayout lay = knn_layout(N, C);
     SVNET_REQUIRE(!lay.il4, SVNET_E_UNSUPPORTED, "svnet_knn_from_table_f32: this configuration reads an interleaved table (svnet_knn_table_fusable)");
     if (B == 0) return SVNET_OK;
     const float* xT = (const float*)workspace;
     const float* xx = xT + B * N * ((C + 7) / 8 * 8);
+    if (!knn_in_register_range(N, k)) return knn_run_stream(xT, xx, B, N, C, lay.Cpad, k, idx_out, (hipStream_t)stream);   // (clouds Cpad rows apart)
     return knn_run_main(xT, xx, B, N, C, k, idx_out, lay.mf8, (hipStream_t)stream);
 }
 
@@ -1052,15 +1228,17 @@ static int knn_impl(const float* x, const float* x2, int64_t split, int64_t B, i
     SVNET_REQUIRE(B >= 0 && N > 0 && C > 0 && k > 0 && k <= N, SVNET_E_ARG, "svnet_knn_f32: bad sizes B=%lld N=%lld C=%lld k=%d",
                   (long long)B, (long long)N, (long long)C, k);
     SVNET_REQUIRE(xx_mode == 0 || xx_mode == 1, SVNET_E_ARG, "svnet_knn_f32: xx_mode must be 0 or 1");
-    SVNET_REQUIRE(C <= 384, SVNET_E_UNSUPPORTED, "svnet_knn_f32: C=%lld > 384 (bit-exact contract ends where MKL splits K)", (long long)C);
-    SVNET_REQUIRE(N <= 4096 && k <= 64, SVNET_E_UNSUPPORTED, "svnet_knn_f32: N=%lld k=%d outside N<=4096, k<=64", (long long)N, k);
+    SVNET_REQUIRE(C <= SVNET_KNN_MAX_C, SVNET_E_UNSUPPORTED, "svnet_knn_f32: C=%lld > 384 (bit-exact contract ends where MKL splits K)", (long long)C);
+    SVNET_REQUIRE(N <= SVNET_KNN_MAX_N && k <= SVNET_KNN_MAX_K, SVNET_E_UNSUPPORTED, "svnet_knn_f32: N=%lld k=%d outside N<=32768, k<=128",
+                  (long long)N, k);
     SVNET_REQUIRE(workspace_bytes >= svnet_knn_workspace_bytes(B, N, C), SVNET_E_WORKSPACE, "svnet_knn_f32: workspace too small");
     if (B == 0) return SVNET_OK;
     hipStream_t st = (hipStream_t)stream;
     float* xT = (float*)workspace;
     const int64_t C8 = (C + 7) / 8 * 8;
     float* xx = xT + B * N * C8;
-    const KnnLayout lay = knn_layout(N, C);
+    const bool streamed = !knn_in_register_range(N, k);
+    const KnnLayout lay = streamed ? KnnLayout{0, false, C} : knn_layout(N, C);     // (the streamed form reads the plain channel-major table)
     const int il4 = lay.il4;
     const bool mf8 = lay.mf8;
     // one wave per workgroup: a thread walks its point's row, so every load instruction of a wave touches 64 cache lines - the kernel is
@@ -1079,7 +1257,15 @@ static int knn_impl(const float* x, const float* x2, int64_t split, int64_t B, i
 #if SVNET_KNN_ABL == 5   // diagnostic build: the table preparation alone
     return SVNET_OK;
 #endif
+    if (streamed) return knn_run_stream(xT, xx, B, N, C, C, k, idx_out, st);
     return knn_run_main(xT, xx, B, N, C, k, idx_out, mf8, st);
+}
+
+static int knn_run_stream(const float* xT, const float* xx, int64_t B, int64_t N, int64_t C, int64_t cloud_rows, int k, int64_t* idx_out,
+                          hipStream_t st) {
+    launch_stream(xT, xx, B, (int)N, (int)C, cloud_rows, k, idx_out, st);
+    SVNET_CHECK_LAUNCH("knn_stream_kernel");
+    return SVNET_OK;
 }
 
 static int knn_run_main(const float* xT, const float* xx, int64_t B, int64_t N, int64_t C, int k, int64_t* idx_out, bool mf8, hipStream_t st) {
