@@ -254,7 +254,8 @@ int svnet_edgeblock_apply_f32(const int32_t* n_max, const int32_t* n_min, const 
  * launches of latency-bound work per level sat on the forward's critical path; here every workgroup (32 points of one cloud) derives
  * the ~2 (Os + Ov) coefficients from the statistic slices and its cloud's gate itself - the same expressions as the separate kernels,
  * bit-identical outputs - and workgroup 0 alone writes coef, the running statistics and the counters.  Needs N % 32 == 0, Os <= 256,
- * Ov <= 256 (svnet_block_tail_supported); stat1 = the scalar path's sums: int64 slices of (sum n, sum n^2) for the edge block
+ * Ov <= 256 and a dynamic LDS of at most 64 KiB - the coefficients, plus 32 staged rows of Os + 3 Ov floats only with a table
+ * (svnet_block_tail_supported); stat1 = the scalar path's sums: int64 slices of (sum n, sum n^2) for the edge block
  * (scale1 required), fp64 slices of (sum y, sum y^2) for the first level (scale1 NULL); hi / lo = n_max / n_min (int32) or y_max / y_min. */
 typedef struct svnet_block_tail_desc {
     const void* stat1; const double* stat_v; int64_t E, Os, Ov;

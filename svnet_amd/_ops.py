@@ -1518,7 +1518,9 @@ class GlobalMaxMeanPoolBNV(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, y, v_lin, gate, g1, b1, rm1, rv1, g2, b2, rm2, rv2, Wz, scz, training, act, slope, nbt1=None, nbt2=None,
-                eps=BN_EPS, momentum=BN_MOMENTUM):
+                eps=BN_EPS, momentum=BN_MOMENTUM, v_on_side=False):
+        """v_on_side: v_lin was produced on the side stream (SVBlock.vector_path_on_side), so autograd runs linear2's backward - the
+        consumer of dv - there too; False (the single-stream path) = it runs on the main stream."""
         global _FUSED_VSTATS
         _hip(y, v_lin, gate, g1, b1, g2, b2, Wz, scz)
         y, v_lin = _f32c(y), _f32c(v_lin)
@@ -1572,6 +1574,7 @@ class GlobalMaxMeanPoolBNV(torch.autograd.Function):
                 TAP["acts"].append((g1.data_ptr(), ((y2 - mean1) * invstd1 * g1 + b1) > 0))
         ctx.meta = (B, N, Ca, C, act, slope, bool(training), v_lin.shape, None if gate is None else gate.shape,
                     None if scz is None else scz.shape)
+        ctx.v_on_side = bool(v_on_side)
         return out
 
     @staticmethod
@@ -1586,12 +1589,18 @@ class GlobalMaxMeanPoolBNV(torch.autograd.Function):
         dy = torch.empty((B, N, Ca), dtype=F, device=dev) if ctx.needs_input_grad[0] else None
         red1, red2, dgate, gxb = _zeros_pool(dev, ((_sliced_len(2 * Ca),), F), ((_sliced_len(2 * C),), F), ((B, C), F), ((_sliced_len(3 * C),), F))
         main, side = torch.cuda.current_stream(dev), _side_stream(dev)
+        # dv belongs to the pool of the stream that consumes it: linear2's backward, which autograd runs where linear2's forward ran.
+        # On the two-stream path that is the side stream (allocated there below: the allocator may hand the block on as soon as it is
+        # freed; allocated on the main stream, dv's block went back to the MAIN stream's pool while linear2's products were still reading
+        # it).  On the single-stream path (B*N < TWO_STREAM_MIN_ROWS) it is the main stream: a side-stream block freed there would be
+        # handed to the side stream's next allocation while main may still be reading it, so dv comes from main's pool instead - the side
+        # stream writes it before main.wait_stream(side) below, and main frees it only after its own reads.  (g5 is written and read on
+        # the side stream alone, so it stays there.)
+        dv = None if ctx.v_on_side else torch.empty((P, 3, C), dtype=F, device=dev)
         side.wait_stream(main)
         with torch.cuda.stream(side):
-            # (allocated ON the side stream: every kernel that touches them runs there - this pass, VectorBN's apply pass, linear2's backward,
-            #  which autograd runs where its forward ran - so the allocator may hand their blocks on as soon as they are freed; allocated on the
-            #  main stream, dv's block went back to the MAIN stream's pool while linear2's products were still reading it)
-            dv = torch.empty((P, 3, C), dtype=F, device=dev)
+            if dv is None:
+                dv = torch.empty((P, 3, C), dtype=F, device=dev)
             recompute = bool(config.FUSE_VTAIL_APPLY)
             g5 = None if recompute else torch.empty((P, 3, C), dtype=F, device=dev)
             call("svnet_vtail_bwd_f32", _p(v3), _p(mean2), _p(invstd2), _p(g2), _p(b2), _p(gate2), _p(w_eff), _p(g[:, Ca:]), _p(g[:, Ct + Ca:]),
@@ -1616,9 +1625,9 @@ class GlobalMaxMeanPoolBNV(torch.autograd.Function):
         for t in (dWz, dscz):
             if t is not None:
                 t.record_stream(main)
-        # forward args: y, v_lin, gate, g1, b1, rm1, rv1, g2, b2, rm2, rv2, Wz, scz, training, act, slope, nbt1, nbt2, eps, momentum
+        # forward args: y, v_lin, gate, g1, b1, rm1, rv1, g2, b2, rm2, rv2, Wz, scz, training, act, slope, nbt1, nbt2, eps, momentum, v_on_side
         return (dy, dv.view(vshape), dgate.view(gshape) if gate2 is not None else None, red1[Ca:2 * Ca], red1[:Ca], None, None,
-                red2[C:2 * C], red2[:C], None, None, dWz, dscz, None, None, None, None, None, None, None)
+                red2[C:2 * C], red2[:C], None, None, dWz, dscz, None, None, None, None, None, None, None, None)
 
 
 class Act(torch.autograd.Function):

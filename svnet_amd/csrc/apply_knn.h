@@ -98,6 +98,13 @@ constexpr int APPLY_KNN_TP = 32;       // points per tile (knn_prep_rows_kernel'
 
 __host__ inline size_t apply_knn_lds_bytes(int64_t Os, int64_t Ov) { return (size_t)APPLY_KNN_TP * ((size_t)(Os + 3 * Ov) | 1) * sizeof(float); }
 
+// dynamic LDS of a fused level's tail launch (svnet_*_tail_f32): the coefficients (4 Os + 4 Ov, rounded to 4), and the tile's staged rows
+// only when the launch also writes the k-NN table (without one, apply_knn_tiles never touches them)
+__host__ inline size_t block_tail_lds_bytes(int64_t Os, int64_t Ov, bool with_knn_table) {
+    return (size_t)((4 * Os + 4 * Ov + 3) & ~(int64_t)3) * sizeof(float) + (with_knn_table ? apply_knn_lds_bytes(Os, Ov) : 0);
+}
+constexpr size_t BLOCK_TAIL_LDS_MAX = 64 * 1024;     // what a launch gets without an opt-in (the tail launches ask for none)
+
 // what the host entry points check before the fused launch: the table layout, whole tiles per cloud, the workspace
 __host__ inline bool apply_knn_supported(int64_t P, int64_t N, int64_t Os, int64_t Ov, int64_t* Cpad) {
     const int64_t C = Os + 3 * Ov;

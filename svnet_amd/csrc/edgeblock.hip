@@ -912,6 +912,7 @@ extern "C" int svnet_edgeblock_apply_knn_f32(const int32_t* n_max, const int32_t
 
 extern "C" int svnet_block_tail_supported(int64_t P, int64_t N, int64_t Os, int64_t Ov, int with_knn_table) {
     if (!(P > 0 && N > 0 && P % N == 0 && N % APPLY_KNN_TP == 0 && Os > 0 && Os <= 256 && Ov > 0 && Ov <= 256)) return 0;
+    if (block_tail_lds_bytes(Os, Ov, with_knn_table != 0) > BLOCK_TAIL_LDS_MAX) return 0;
     int64_t Cpad = 0;
     return (!with_knn_table || apply_knn_supported(P, N, Os, Ov, &Cpad)) ? 1 : 0;
 }
@@ -935,7 +936,7 @@ static int block_tail_check(const svnet_block_tail_desc& d, const char* who, siz
         *xT = (float*)d.knn_workspace;
         *xx = *xT + d.P * ((d.Os + 3 * d.Ov + 7) / 8 * 8);
     }
-    *lds = (size_t)((4 * d.Os + 4 * d.Ov + 3) & ~(int64_t)3) * sizeof(float) + apply_knn_lds_bytes(d.Os, d.Ov);
+    *lds = block_tail_lds_bytes(d.Os, d.Ov, d.knn_workspace != nullptr);
     return SVNET_OK;
 }
 

@@ -750,7 +750,7 @@ extern "C" int svnet_xyzblock_tail_f32(const svnet_block_tail_desc* desc, void* 
         xT = (float*)d.knn_workspace;
         xx = xT + d.P * ((d.Os + 3 * d.Ov + 7) / 8 * 8);
     }
-    const size_t lds = (size_t)((4 * d.Os + 4 * d.Ov + 3) & ~(int64_t)3) * sizeof(float) + apply_knn_lds_bytes(d.Os, d.Ov);
+    const size_t lds = block_tail_lds_bytes(d.Os, d.Ov, d.knn_workspace != nullptr);
     const XyzCoefArgs ca = {reinterpret_cast<const double*>(d.stat1), d.stat_v, d.E, (int)d.Os, (int)d.Ov, d.gamma1, d.beta1, d.running_mean1,
                             d.running_var1, d.gamma2, d.beta2, d.running_mean2, d.running_var2, d.training, d.eps, d.momentum};
     hipLaunchKernelGGL(xyzblock_tail_kernel, dim3((unsigned)(d.P / APPLY_KNN_TP)), dim3(256), lds, (hipStream_t)stream, ca, d.coef,

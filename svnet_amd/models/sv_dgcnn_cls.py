@@ -71,7 +71,8 @@ class SV_DGCNN_CLS(nn.Module):
                 pooled = _ops.GlobalMaxMeanPoolBNV.apply(
                     y5, v_lin, gate, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn2.weight, bn2.bias, bn2.running_mean,
                     bn2.running_var, fz.weight, fz.scale if fz.bw else None, bn.training, _ACT_LEAKY, self.conv5.relu.negative_slope,
-                    bn.num_batches_tracked if bn.training else None, bn2.num_batches_tracked if bn2.training else None, bn.eps, _bn_momentum(bn))
+                    bn.num_batches_tracked if bn.training else None, bn2.num_batches_tracked if bn2.training else None, bn.eps, _bn_momentum(bn),
+                    self.conv5.vector_path_on_side(x5[0]))
                 h = self.dp1(linear_bn_act(self.linear1, self.bn1, pooled, _ACT_LEAKY, 0.2))
                 h = self.dp2(linear_bn_act(self.linear2, self.bn2, h, _ACT_LEAKY, 0.2))
                 return _ops.FpLinear.apply(h, self.linear3.weight, self.linear3.bias)

@@ -406,10 +406,15 @@ class SVBlock(nn.Module):
             v_out = self.bn2(self.linear2(v, vstats=True), gate=v_scale)
         return (s_out, v_out)
 
+    @staticmethod
+    def vector_path_on_side(s):
+        """True when the rows path on scalars s runs the vector path (linear2, and so its backward) on the side stream."""
+        rows = s.numel() // max(s.shape[-1], 1)
+        return bool(config.TWO_STREAM_BLOCKS and rows >= config.TWO_STREAM_MIN_ROWS and s.is_cuda)
+
     def _forward_rows(self, x, prebn=False, pretail=False):
         s, v = x
-        rows = s.numel() // max(s.shape[-1], 1)
-        if config.TWO_STREAM_BLOCKS and rows >= config.TWO_STREAM_MIN_ROWS and s.is_cuda:
+        if self.vector_path_on_side(s):
             # the two paths only share their inputs: the vector path goes to the side stream (fork / join with events, so the
             # pattern is captured into a HIP graph as two branches); its output is handed to the main stream's allocator view.
             # linear2 needs neither the gate nor s: its product starts at the fork, the gate (a pooling pass + a tiny MLP, ~50 us of

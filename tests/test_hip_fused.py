@@ -669,6 +669,16 @@ def test_models_give_the_same_bits_with_and_without_the_block_tail(model_name, B
         assert float(np.abs(g_ - ref).max()) <= 1e-4 * float(np.abs(ref).max()) + 1e-5 * gmax, n
 
 
+@pytest.mark.parametrize("training", [True, False], ids=["train", "eval"])
+@pytest.mark.parametrize("xyz", [False, True], ids=["edge_level", "first_level"])
+@pytest.mark.parametrize("cfg", [(1, 1024, 256, 128, 256), (2, 256, 256, 256, 64)], ids=["os256_ov128", "os256_ov256"])
+def test_wide_block_tail_without_a_table_is_bit_identical_to_its_three_launches(cfg, xyz, training, hip_device):
+    """The widest levels svnet_block_tail_supported takes without a k-NN table (Os = 256, Ov up to 256): the launch asks for the
+    coefficients' LDS alone there (it used to reserve 32 staged rows it never writes - 139 392 B at Os = Ov = 256, past what a
+    launch without an opt-in gets) and must still match the separate launches bit for bit."""
+    test_block_tail_is_bit_identical_to_its_three_launches(cfg, xyz, training, False, hip_device)
+
+
 # ----------------------------------------------------------------------------- conv5's concatenation with the gate's mean inside
 
 @pytest.mark.parametrize("cfg", [(4, 256, 256, 83, True), (2, 1024, 256, 83, True), (3, 64, 200, 40, False), (2, 48, 256, 83, True)],

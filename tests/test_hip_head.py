@@ -94,32 +94,39 @@ def test_fused_head_layer_matches_layerwise(shape, train, hip_device):
         assert err <= (1e-4 if k == "d:scale" else 2e-5), "%s: %.3e" % (k, err)
 
 
-@pytest.mark.parametrize("shape", [(32, 2044, 512, 1), (32, 512, 256, 2), (9, 200, 33, 1)], ids=["l1", "l2", "ragged"])
-def test_fused_head_layer_matches_oracle(shape, hip_device):
-    """Train-mode forward + backward of the fused layer against the oracle's exact-STE restatement (sv_layers.py:35-51 + BatchNorm +
-    activation), with the HIP path's sign decisions replayed so that knife-edge signs cannot blur an element-wise comparison."""
+def head_vs_oracle(shape, dev, dtype=torch.float32):
+    """(got, ref): train-mode forward + backward of the fused layer and of the oracle's exact-STE restatement (sv_layers.py:35-51 +
+    BatchNorm + activation) in `dtype`, with the HIP path's sign decisions replayed so that knife-edge signs cannot blur an element-wise
+    comparison.  Keys: out, dx, d:weight, d:beta, d:scale, d:bn.weight, d:bn.bias."""
     from tests import decisions as D
     M, K, O, act = shape
-    lin, bn = _layer(K, O, hip_device, 3 * M + K)
+    lin, bn = _layer(K, O, dev, 3 * M + K)
     x = _input(M, K, O)
     with D.tapped() as tap:
-        got = _run(lin, bn, x, act, hip_device, True, True, 9)
+        got = _run(lin, bn, x, act, dev, True, True, 9)
         dec = D.decisions_of(tap)
-    P = {"lin.weight": lin.weight.detach().cpu().clone().requires_grad_(True), "lin.beta": lin.beta.detach().cpu().clone().requires_grad_(True),
-         "lin.scale": lin.scale.detach().cpu().clone().requires_grad_(True), "bn.weight": bn.weight.detach().cpu().clone().requires_grad_(True),
-         "bn.bias": bn.bias.detach().cpu().clone().requires_grad_(True)}
-    xc = x.clone().requires_grad_(True)
+    P = {"lin.weight": lin.weight, "lin.beta": lin.beta, "lin.scale": lin.scale, "bn.weight": bn.weight, "bn.bias": bn.bias}
+    P = {n: t.detach().cpu().to(dtype).clone().requires_grad_(True) for n, t in P.items()}
+    xc = x.to(dtype).clone().requires_grad_(True)
     ctx = sv_ref.Ctx(train=True, exact_ste=True)
     ctx.decisions = dec
     y = sv_ref.linear(xc, P, "lin", True, True, ctx)
     mean, var = y.mean(0), y.var(0, unbiased=False)
     z = (y - mean) / torch.sqrt(var + bn.eps) * P["bn.weight"] + P["bn.bias"]
     out = torch.nn.functional.leaky_relu(z, 0.2) if act == 1 else (torch.relu(z) if act == 2 else z)
-    gout = torch.randn(out.shape, generator=torch.Generator().manual_seed(9))
+    gout = torch.randn(out.shape, generator=torch.Generator().manual_seed(9)).to(dtype)
     out.backward(gout)
     dec.check()                                                             # every replayed sign the oracle would have taken differently is a knife edge
     ref = {"out": out.detach().numpy(), "dx": xc.grad.numpy(), "d:weight": P["lin.weight"].grad.numpy(), "d:beta": P["lin.beta"].grad.numpy(),
            "d:scale": P["lin.scale"].grad.numpy(), "d:bn.weight": P["bn.weight"].grad.numpy(), "d:bn.bias": P["bn.bias"].grad.numpy()}
+    return {k: got[k] for k in ref}, ref
+
+
+@pytest.mark.parametrize("shape", [(32, 2044, 512, 1), (32, 512, 256, 2), (9, 200, 33, 1)], ids=["l1", "l2", "ragged"])
+def test_fused_head_layer_matches_oracle(shape, hip_device):
+    """Train-mode forward + backward of the fused layer against the oracle's exact-STE restatement (sv_layers.py:35-51 + BatchNorm +
+    activation), with the HIP path's sign decisions replayed so that knife-edge signs cannot blur an element-wise comparison."""
+    got, ref = head_vs_oracle(shape, hip_device)
     gmax = max(float(np.abs(ref[k]).max()) for k in ref if k.startswith("d:"))
     for k, r in ref.items():
         floor = gmax if k == "d:scale" else 1e-2 * gmax                     # (the scale feeding a train-mode BatchNorm has a zero true gradient)

@@ -101,12 +101,17 @@ TRAIN_CASES = [c for c in C.MODEL_CASES if c[0].endswith("_small") and c[0] != "
     # STRICT pseg_bin_small (the binary model's per-cloud blocks are well conditioned at two rows; only the fp twin is not): the float64
     # oracle step on E = 163 840 edges of 272 columns is what bounds the size - B = 4 ran past seven minutes on the GPU box's host
     ("pseg_bin_n2048", "sv_dgcnn_pseg", True, 2, 2048, 40),
+    # the classifier's fused tail (_ops.GlobalMaxMeanPoolBNV: N >= 256, C <= 192) on the SINGLE-stream path: 2048 rows < TWO_STREAM_MIN_ROWS,
+    # so linear2's product - and its backward, the consumer of the tail's dv - stays on the main stream (dgcnn_bin_b8 has N = 128 and no
+    # fused tail, dgcnn_bin_n1024 has 8192 rows and takes the two-stream path)
+    ("dgcnn_bin_n256", "sv_dgcnn_cls", True, 8, 256, 20),
 ]
+SINGLE_STREAM_TAIL = ("dgcnn_bin_n256",)        # cases whose train step must run the fused tail with v_lin from the main stream
 # cases held to the north-star tolerance itself (1e-3) on every tensor, whatever the yard-sticks say
 STRICT = ("dgcnn_bin_small", "dgcnn_fp_small", "pseg_bin_small", "dgcnn_bin_b16", "dgcnn_bin_b16b", "dgcnn_bin_b8", "dgcnn_fp_b16",
-          "pseg_bin_b32", "pseg_fp_b32", "dgcnn_bin_n1024", "pseg_bin_n2048")
+          "pseg_bin_b32", "pseg_fp_b32", "dgcnn_bin_n1024", "pseg_bin_n2048", "dgcnn_bin_n256")
 WIDER_CERTIFICATE = ("ppseg_fp_b16",)          # the one case whose decision certificate allows 30 instead of 20 rms of fp32 noise (see below)
-NO_SENSITIVITY_LEG = ("dgcnn_bin_n1024", "pseg_bin_n2048")     # STRICT cases never use the float64 sensitivity (a third oracle step: ~1 min at this size)
+NO_SENSITIVITY_LEG = ("dgcnn_bin_n1024", "pseg_bin_n2048", "dgcnn_bin_n256")     # STRICT cases never use the float64 sensitivity (a third oracle step: ~1 min at this size)
 YARDSTICK = 3.0         # a tensor may be this many times further from the float64 truth than the fp32 oracle is ...
 SENSITIVITY = 10.0      # ... or this many times what the float64 truth itself moves when its input moves by one part in 1e7
 SECOND_DRAW_THREADS = 128   # the certificate's second fp32 draw when torch's default is already the CPU share: the thread count torch
@@ -232,8 +237,20 @@ def _train_step_case(case, hip_device, corrupt=None):
 
 
 @pytest.mark.parametrize("case", TRAIN_CASES, ids=[c[0] for c in TRAIN_CASES])
-def test_train_step_matches_oracle_elementwise(case, hip_device):
+def test_train_step_matches_oracle_elementwise(case, hip_device, monkeypatch):
+    if case[0] not in SINGLE_STREAM_TAIL:
+        _train_step_case(case, hip_device)
+        return
+    from svnet_amd import _ops
+    seen = []
+    real = _ops.GlobalMaxMeanPoolBNV.apply
+
+    def spy(*args):
+        seen.append(args[-1])                   # v_on_side
+        return real(*args)
+    monkeypatch.setattr(_ops.GlobalMaxMeanPoolBNV, "apply", spy)
     _train_step_case(case, hip_device)
+    assert seen == [False], seen                # the fused tail ran once, on the single-stream path
 
 
 test_train_step_matches_oracle_elementwise.__doc__ = _train_step_case.__doc__

@@ -73,6 +73,33 @@ def test_shape_queries_of_the_fused_launches_answer_without_a_gpu():
     assert L.svnet_v2s_cat_sum_supported(32768, 83, 300, 1024) == 0 and L.svnet_v2s_cat_sum_supported(32768, 340, 512, 1024) == 0
 
 
+def test_block_tail_asks_for_at_most_64_kib_of_lds():
+    """The one-launch block tail (svnet_edgeblock_tail_f32 / svnet_xyzblock_tail_f32) takes no LDS opt-in, so every shape
+    svnet_block_tail_supported accepts must fit 64 KiB of dynamic LDS: the coefficients (4 Os + 4 Ov floats, rounded to 4) plus,
+    only when the launch writes the next k-NN's table, 32 staged rows of (Os + 3 Ov) | 1 floats (include/svnet_hip.h).  Without a
+    table the launch used to ask for the staged rows anyway - 139 392 B at Os = Ov = 256 - and fail instead of falling back."""
+    from svnet_amd import _lib
+    L = _lib.lib()
+
+    def lds(Os, Ov, table):
+        return ((4 * Os + 4 * Ov + 3) & ~3) * 4 + (32 * ((Os + 3 * Ov) | 1) * 4 if table else 0)
+    P, N = 2048, 1024
+    # no table: the widest level is taken (8 KiB of coefficients), one channel more on either side is not
+    assert L.svnet_block_tail_supported(P, N, 256, 256, 0) == 1 and lds(256, 256, False) <= 65536 < lds(256, 256, True)
+    assert L.svnet_block_tail_supported(P, N, 257, 256, 0) == 0 and L.svnet_block_tail_supported(P, N, 256, 257, 0) == 0
+    assert L.svnet_block_tail_supported(P, N, 256, 128, 0) == 1
+    # with a table the row width Os + 3 Ov <= 384 bounds the staging: 384 is taken, 385 is not (and Os = Ov = 256 never is)
+    assert L.svnet_block_tail_supported(P, N, 96, 96, 1) == 1 and L.svnet_block_tail_supported(P, N, 256, 42, 1) == 1
+    assert L.svnet_block_tail_supported(P, N, 97, 96, 1) == 0 and L.svnet_block_tail_supported(P, N, 256, 43, 1) == 0
+    assert L.svnet_block_tail_supported(P, N, 256, 256, 1) == 0 and L.svnet_block_tail_supported(P, N, 256, 128, 1) == 0
+    # and over the whole box of widths: whatever is accepted fits
+    for Os in (1, 2, 8, 31, 64, 96, 128, 192, 255, 256, 257, 300):
+        for Ov in (1, 3, 21, 42, 43, 64, 96, 128, 170, 255, 256, 257):
+            for table in (0, 1):
+                if L.svnet_block_tail_supported(P, N, Os, Ov, table):
+                    assert lds(Os, Ov, table) <= 65536, (Os, Ov, table)
+
+
 def test_product_path_has_no_cpu_fallback():
     from svnet_amd.models.utils.sv_util import knn, svpool
     from svnet_amd.models.sv_layers import Linear

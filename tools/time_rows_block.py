@@ -41,7 +41,7 @@ for it in range(3):
         y5, v_lin, gate = blk.forward_pretail((s, v))
         pooled = _ops.GlobalMaxMeanPoolBNV.apply(y5, v_lin, gate, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn2.weight, bn2.bias,
                                                  bn2.running_mean, bn2.running_var, fz.weight, fz.scale, True, 1, 0.2, bn.num_batches_tracked,
-                                                 bn2.num_batches_tracked, bn.eps, 0.1)
+                                                 bn2.num_batches_tracked, bn.eps, 0.1, blk.vector_path_on_side(s))
     mark = len(records)
     pooled.sum().backward()
     torch.cuda.synchronize()
