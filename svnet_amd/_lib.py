@@ -146,6 +146,17 @@ class BinHeadDesc(ctypes.Structure):
     ]
 
 
+# The post-pool stage of a fused level has one entry point per block (edge / xyz) and one argument list for both (csrc/block_post.h):
+#   coeffs: stat1, stat_v, E, Os, Ov, [the edge block's scale1,] gamma1 .. running_var2, training, eps, momentum, coef, nbt1, nbt2, gate job, stream
+#   apply:  hi, lo, mv, mvn, coef, gate, P, N, Os, Ov, slope, s_out, v_out, s_cat, s_ld, v_cat, v_ld  (+ stream / + k-NN workspace, bytes, stream)
+#   tail:   descriptor, stream
+def _block_coeffs(scale1):
+    return [c_p, c_p, c_i64, c_i64, c_i64] + scale1 + [c_p] * 8 + [c_int, c_f, c_f] + [c_p] * 5
+
+
+_BLOCK_APPLY = [c_p] * 6 + [c_i64] * 4 + [c_f, c_p, c_p, c_p, c_i64, c_p, c_i64]
+_BLOCK_TAIL = [c_p, c_p]
+
 # name -> (restype, argtypes); every symbol include/svnet_hip.h declares
 SIGNATURES = {
     "svnet_version": (c_int, []),
@@ -158,8 +169,8 @@ SIGNATURES = {
     "svnet_knn_sv_f32": (c_int, [c_p, c_i64, c_p, c_i64, c_i64, c_i64, c_int, c_p, c_p, c_sz, c_p]),
     "svnet_knn_table_fusable": (c_int, [c_i64, c_i64, c_i64]),
     "svnet_block_tail_supported": (c_int, [c_i64, c_i64, c_i64, c_i64, c_int]),
-    "svnet_edgeblock_tail_f32": (c_int, [c_p, c_p]),
-    "svnet_xyzblock_tail_f32": (c_int, [c_p, c_p]),
+    "svnet_edgeblock_tail_f32": (c_int, _BLOCK_TAIL),
+    "svnet_xyzblock_tail_f32": (c_int, _BLOCK_TAIL),
     "svnet_knn_from_table_f32": (c_int, [c_p, c_sz, c_i64, c_i64, c_i64, c_int, c_p, c_p]),
     "svnet_edge_xyz_f32": (c_int, [c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_int, c_p, c_p]),
     "svnet_edge_diffcat_fwd_f32": (c_int, [c_p, c_p, c_int, c_i64, c_i64, c_i64, c_i64, c_i64, c_p, c_p]),
@@ -176,18 +187,18 @@ SIGNATURES = {
     "svnet_edgeblock_bwd_params_f32": (c_int, [c_p] * 8 + [c_i64] * 4 + [c_p] * 6 + [c_p]),
     "svnet_edgeblock_prepare_f32": (c_int, [c_p, c_p, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_p]),
     "svnet_edgeblock_fwd_f32": (c_int, [ctypes.POINTER(EdgeBlockDesc), c_p]),
-    "svnet_edgeblock_coeffs_f32": (c_int, [c_p, c_p, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_int, c_f, c_f, c_p, c_p, c_p, c_p, c_p]),
-    "svnet_edgeblock_apply_f32": (c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_f, c_p, c_p, c_p, c_i64, c_p, c_i64, c_p]),
-    "svnet_edgeblock_apply_knn_f32": (c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_f, c_p, c_p, c_p, c_i64, c_p, c_i64, c_p, c_sz, c_p]),
+    "svnet_edgeblock_coeffs_f32": (c_int, _block_coeffs([c_p])),
+    "svnet_edgeblock_apply_f32": (c_int, _BLOCK_APPLY + [c_p]),
+    "svnet_edgeblock_apply_knn_f32": (c_int, _BLOCK_APPLY + [c_p, c_sz, c_p]),
     "svnet_edgeblock_wbt_bf16": (c_int, [c_p, c_p, c_i64, c_i64, c_i64, c_p, c_p, c_p]),
     "svnet_edgeblock_bwd_prelude_f32": (c_int, [c_p] * 9 + [c_i64, c_i64, c_i64, c_i64, c_f, c_p, c_p, c_p, c_p, c_p, c_i64, c_p, c_i64, c_p, c_p]),
     "svnet_edgeblock_bwd_coeffs_f32": (c_int, [c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_int, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
     "svnet_edgeblock_bwd_f32": (c_int, [ctypes.POINTER(EdgeBlockBwdDesc), c_p]),
     "svnet_edgeblock_wgrad_f32": (c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_p, ctypes.c_uint32, c_p]),
     "svnet_xyzblock_fwd_f32": (c_int, [ctypes.POINTER(XyzBlockDesc), c_p]),
-    "svnet_xyzblock_coeffs_f32": (c_int, [c_p, c_p, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_int, c_f, c_f, c_p, c_p, c_p, c_p, c_p]),
-    "svnet_xyzblock_apply_f32": (c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_f, c_p, c_p, c_p, c_i64, c_p, c_i64, c_p]),
-    "svnet_xyzblock_apply_knn_f32": (c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_f, c_p, c_p, c_p, c_i64, c_p, c_i64, c_p, c_sz, c_p]),
+    "svnet_xyzblock_coeffs_f32": (c_int, _block_coeffs([])),
+    "svnet_xyzblock_apply_f32": (c_int, _BLOCK_APPLY + [c_p]),
+    "svnet_xyzblock_apply_knn_f32": (c_int, _BLOCK_APPLY + [c_p, c_sz, c_p]),
     "svnet_xyzblock_bwd_prelude_f32": (c_int, [c_p] * 8 + [c_i64, c_i64, c_i64, c_i64, c_f, c_p, c_p, c_p, c_p, c_p, c_i64, c_p, c_i64, c_p, c_p]),
     "svnet_xyzblock_bwd_f32": (c_int, [ctypes.POINTER(XyzBlockBwdDesc), c_p]),
     "svnet_binweight_i8_bytes": (c_sz, [c_i64, c_i64]),

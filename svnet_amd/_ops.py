@@ -117,27 +117,60 @@ def knn(x, k):
     return idx
 
 
-def _block_tail(entry, P, N, E, Os, Ov, stat1, stat_v, sc1, g1, b1, rm1, rv1, g2, b2, rm2, rv2, training, coef, nbt1, nbt2, job, hi, lo, mv, mvn,
-                s_out, v_out, slot, kws):
-    """svnet_{edgeblock,xyzblock}_tail_f32: coefficients + gate MLP + apply (+ the k-NN table kws) of a fused level as ONE launch.
-    False = not taken (switch off / shape not supported): the caller issues the separate launches."""
-    if not config.FUSE_BLOCK_TAIL or not _lib.lib().svnet_block_tail_supported(P, N, Os, Ov, 1 if kws is not None else 0):
-        return False
-    d = _lib.BlockTailDesc()
-    d.stat1, d.stat_v, d.E, d.Os, d.Ov, d.scale1 = _p(stat1), _p(stat_v), E, Os, Ov, _p(sc1)
-    d.gamma1, d.beta1, d.running_mean1, d.running_var1 = _p(g1), _p(b1), _p(rm1), _p(rv1)
-    d.gamma2, d.beta2, d.running_mean2, d.running_var2 = _p(g2), _p(b2), _p(rm2), _p(rv2)
-    d.training, d.eps, d.momentum = int(training), BN_EPS, BN_MOMENTUM
-    d.coef, d.num_batches_tracked1, d.num_batches_tracked2 = _p(coef), _p(nbt1), _p(nbt2)
-    d.gate = job
-    d.hi, d.lo, d.mv, d.mvn, d.P, d.N, d.slope = _p(hi), _p(lo), _p(mv), _p(mvn), P, N, 0.2
-    d.s_out, d.v_out = _p(s_out), _p(v_out)
-    if slot is not None:
-        d.s_cat, d.s_ld, d.v_cat, d.v_ld = slot
+def _block_post(block, B, N, k, Os, Ov, gate_sum, Wg0, Wg0c, Wg2c, hi, lo, slot_max, slot_min, mv, mvn, stat1, stat_v, sc1, g1, b1, rm1, rv1,
+                g2, b2, rm2, rv2, training, nbt1, nbt2):
+    """Everything behind the edge pass of a fused level (block: "edgeblock" / "xyzblock"; csrc/block_post.h): BatchNorm coefficients of
+    both sets with the gate MLP beside them (sv_layers.py:156-161,179-183: one workgroup per cloud, on the mean edge scalar gate_sum),
+    the apply pass on the pooled extrema hi / lo and mv / mvn, its concatenation slices (_SINK) and, inside knn_table_ahead, the table
+    of the next k-NN - ONE launch (svnet_*_tail_f32) where the switch and the shape allow it, else coefficients + apply.
+    sc1: the pre-BN scale of the edge block's integer scalars (None for xyz).  Returns coef, gate, h, gin, s_out, v_out, s_view, v_view."""
+    P, E = B * N, B * N * k
+    dev = mv.device
+    f32 = dict(dtype=torch.float32, device=dev)
+    H, Cin = Wg0.shape[0], gate_sum.shape[1]
+    h = torch.empty((B, H), **f32)
+    gate = torch.empty((B, Ov), **f32)
+    gin = torch.empty((B, Cin), **f32)
+    Wg0c, Wg2c = _f32c(Wg0c), _f32c(Wg2c)
+    # (the MLP runs in extra workgroups of the coefficient launch below: the two only share their inputs)
+    job = _lib.GateFwdJob(None, _p(gate_sum), _p(gin), 1.0 / float(N * k), _p(Wg0c), _p(Wg2c), B, Cin, H, Ov, _p(h), _p(gate))
+
+    coef = torch.empty((4 * Os + 4 * Ov,), **f32)
+    s_out = torch.empty((B, N, Os), **f32)
+    v_out = torch.empty((B, N, 3, Ov), **f32)
+    slot = _SINK.slot(B, N, Os, Ov, dev) if _SINK is not None else None
+    kws = knn_table_ahead.workspace(B, N, Os, Ov, dev)
+    cat = slot if slot is not None else (None, 0, None, 0)
+    if config.FUSE_BLOCK_TAIL and _lib.lib().svnet_block_tail_supported(P, N, Os, Ov, 1 if kws is not None else 0):
+        d = _lib.BlockTailDesc()        # coefficients + gate MLP + apply (+ the next k-NN's table) in one launch
+        d.stat1, d.stat_v, d.E, d.Os, d.Ov, d.scale1 = _p(stat1), _p(stat_v), E, Os, Ov, _p(sc1)
+        d.gamma1, d.beta1, d.running_mean1, d.running_var1 = _p(g1), _p(b1), _p(rm1), _p(rv1)
+        d.gamma2, d.beta2, d.running_mean2, d.running_var2 = _p(g2), _p(b2), _p(rm2), _p(rv2)
+        d.training, d.eps, d.momentum = int(training), BN_EPS, BN_MOMENTUM
+        d.coef, d.num_batches_tracked1, d.num_batches_tracked2 = _p(coef), _p(nbt1), _p(nbt2)
+        d.gate = job
+        d.hi, d.lo, d.mv, d.mvn, d.P, d.N, d.slope = _p(hi), _p(lo), _p(mv), _p(mvn), P, N, 0.2
+        d.s_out, d.v_out = _p(s_out), _p(v_out)
+        d.s_cat, d.s_ld, d.v_cat, d.v_ld = cat
+        if kws is not None:
+            d.knn_workspace, d.knn_workspace_bytes = _p(kws), kws.numel()
+        call("svnet_%s_tail_f32" % block, ctypes.byref(d), _stream())
+    else:
+        scale = () if sc1 is None else (_p(sc1),)
+        call("svnet_%s_coeffs_f32" % block, _p(stat1), _p(stat_v), E, Os, Ov, *scale, _p(g1), _p(b1), _p(rm1), _p(rv1), _p(g2), _p(b2), _p(rm2),
+             _p(rv2), int(training), BN_EPS, BN_MOMENTUM, _p(coef), _p(nbt1), _p(nbt2), ctypes.byref(job), _stream())
+        apply = (_p(hi), _p(lo), _p(mv), _p(mvn), _p(coef), _p(gate), P, N, Os, Ov, 0.2, _p(s_out), _p(v_out), *cat)
+        if kws is not None:
+            call("svnet_%s_apply_knn_f32" % block, *apply, _p(kws), kws.numel(), _stream())
+        else:
+            call("svnet_%s_apply_f32" % block, *apply, _stream())
     if kws is not None:
-        d.knn_workspace, d.knn_workspace_bytes = _p(kws), kws.numel()
-    call(entry, ctypes.byref(d), _stream())
-    return True
+        knn_table_ahead.table = (s_out.data_ptr(), v_out.data_ptr(), kws, B, N, Os + 3 * Ov)
+    _tap_act(Wg0, 2, h)
+    s_view, v_view = _SINK.wrote(s_out, v_out) if slot is not None else (None, None)
+    if TAP is not None:      # the pooled slot: BatchNorm + LeakyReLU is increasing (slope coef[o] >= 0: max_k) or decreasing (min_k)
+        TAP["pools"].append(torch.where(coef[:Os].view(1, Os) >= 0, slot_max, slot_min))
+    return coef, gate, h, gin, s_out, v_out, s_view, v_view
 
 
 class knn_table_ahead:
@@ -1977,41 +2010,13 @@ class EdgeBlock(torch.autograd.Function):
         if TAP is not None:
             TAP["signs"].append(("edges", E, (Cs, Cv), planes))
 
-        # gate MLP on the mean edge scalar (sv_layers.py:156-161,179-183): one workgroup per cloud
-        H = Wg0.shape[0]
-        h = torch.empty((B, H), **f32)
-        gate = torch.empty((B, Ov), **f32)
-        gin = torch.empty((B, 2 * Cs), **f32)
-        # (the MLP runs in extra workgroups of the coefficient launch below: the two only share their inputs)
-        job = _lib.GateFwdJob(None, _p(gate_sum), _p(gin), 1.0 / float(N * k), _p(Wg0c), _p(Wg2c), B, 2 * Cs, H, Ov, _p(h), _p(gate))
-
-        coef = torch.empty((4 * Os + 4 * Ov,), **f32)
-        s_out = torch.empty((B, N, Os), **f32)
-        v_out = torch.empty((B, N, 3, Ov), **f32)
-        slot = _SINK.slot(B, N, Os, Ov, dev) if _SINK is not None else None
-        kws = knn_table_ahead.workspace(B, N, Os, Ov, dev)
-        if _block_tail("svnet_edgeblock_tail_f32", P, N, E, Os, Ov, stat_n, stat_v, sc1, g1, b1, rm1, rv1, g2, b2, rm2, rv2, training, coef,
-                       nbt1, nbt2, job, n_max, n_min, mv, mvn, s_out, v_out, slot, kws):
-            pass        # coefficients + gate MLP + apply (+ the next k-NN's table) in one launch
-        else:
-            call("svnet_edgeblock_coeffs_f32", _p(stat_n), _p(stat_v), E, Os, Ov, _p(sc1), _p(g1), _p(b1), _p(rm1), _p(rv1),
-                 _p(g2), _p(b2), _p(rm2), _p(rv2), int(training), BN_EPS, BN_MOMENTUM, _p(coef), _p(nbt1), _p(nbt2), ctypes.byref(job), _stream())
-            if kws is not None:
-                call("svnet_edgeblock_apply_knn_f32", _p(n_max), _p(n_min), _p(mv), _p(mvn), _p(coef), _p(gate), P, N, Os, Ov, 0.2, _p(s_out),
-                     _p(v_out), *(slot if slot is not None else (None, 0, None, 0)), _p(kws), kws.numel(), _stream())
-            else:
-                call("svnet_edgeblock_apply_f32", _p(n_max), _p(n_min), _p(mv), _p(mvn), _p(coef), _p(gate), P, N, Os, Ov, 0.2, _p(s_out),
-                     _p(v_out), *(slot if slot is not None else (None, 0, None, 0)), _stream())
-        if kws is not None:
-            knn_table_ahead.table = (s_out.data_ptr(), v_out.data_ptr(), kws, B, N, Os + 3 * Ov)
-        _tap_act(Wg0, 2, h)
-        s_view, v_view = _SINK.wrote(s_out, v_out) if slot is not None else (None, None)
-        if TAP is not None:      # the pooled slot: BatchNorm + LeakyReLU is increasing (slope coef[o] >= 0: max_k n) or decreasing (min_k n)
-            TAP["pools"].append(torch.where(coef[:Os].view(1, Os) >= 0, slot_max, slot_min))
-            # ... and the kink decision of bn1 + LeakyReLU on EVERY edge (sv_layers.py:189-190): the layer's pre-activation is
+        coef, gate, h, gin, s_out, v_out, s_view, v_view = _block_post(
+            "edgeblock", B, N, k, Os, Ov, gate_sum, Wg0, Wg0c, Wg2c, n_max, n_min, slot_max, slot_min, mv, mvn, stat_n, stat_v, sc1, g1, b1,
+            rm1, rv1, g2, b2, rm2, rv2, training, nbt1, nbt2)
+        if TAP is not None and "acts" in TAP and n16 is not None:
+            # the kink decision of bn1 + LeakyReLU on EVERY edge (sv_layers.py:189-190): the layer's pre-activation is
             # A1[o] * n + B1[o] with the kept integer n - the expression the apply kernel evaluates at the pooled edge
-            if "acts" in TAP and n16 is not None:
-                TAP["acts"].append((g1.data_ptr(), (coef[:Os].view(1, Os) * n16.float() + coef[Os:2 * Os].view(1, Os)) > 0))
+            TAP["acts"].append((g1.data_ptr(), (coef[:Os].view(1, Os) * n16.float() + coef[Os:2 * Os].view(1, Os)) > 0))
         ctx.save_for_backward(v, idx, zz, ut, w_sign, w_nz, n16, planes, n_max, n_min, slot_max, slot_min, mv, mvn, coef, gate, h,
                               gin, wv, scv, W1c, sc1, W2c, sc2f, Wzc, sczf, g1, g2, Wg0c, Wg2c, wbt)
         ctx.meta = (B, N, k, Cs, Cv, Os, Ov, bool(training), scale1.shape, sc2.shape, scz.shape)
@@ -2140,34 +2145,41 @@ class EdgeBlock(torch.autograd.Function):
                 gemm(320, Os, E, a_planes=(x_sign, x_nz), B=dn_out, b_rs=Os, b_cs=1, C=GXp, ldc=1, c_cs=320, accumulate=True,
                      tern_tile_mask=used)
 
+        def gather():
+            call("svnet_edgeblock_bwd_gather_f32", _p(msg), _p(rev_range), _p(rev_edge), _p(rev_src), _p(ut), _p(ub_tab), _p(ge_tab),
+                 _p(coef), _p(bcoef), Os, _p(dvc), _p(dzc), P, N, Cs, Cv, Ov, _p(acat), Rp, _p(ds_acc), _p(dv_acc), _p(dbeta_perm),
+                 _p(dbeta1), GATHER_CHUNK, _p(ovf_items), _p(ovf_count), _stream())
+
+        def params():
+            """GXp, GXc -> the parameter gradients; returns the backward's result (one entry per forward argument)."""
+            dW1, dW2, dWz = torch.empty((Os, K1), **f32), torch.empty((Ov, 2 * Cv), **f32), torch.empty((3, 2 * Cv), **f32)
+            dsc1, dsc2, dscz = torch.empty((Os,), **f32), torch.empty((Ov,), **f32), torch.empty((3,), **f32)
+            call("svnet_edgeblock_bwd_params_f32", _p(GXp), _p(GXc), _p(W1), _p(sc1), _p(W2), _p(sc2), _p(Wz), _p(scz), Os, Ov, Cs, Cv,
+                 _p(dW1), _p(dsc1), _p(dW2), _p(dsc2), _p(dWz), _p(dscz), _stream())
+            # forward args: s, v, idx, k, training, Wz, scz, W1, beta1, scale1, g1, b1, rm1, rv1, W2, sc2, g2, b2, rm2, rv2, Wg0, Wg2, nbt1, nbt2
+            return (ds_acc.view(B, N, Cs), dv_acc.view(B, N, 3, Cv), None, None, None, dWz, dscz.view(shz), dW1, dbeta1,
+                    dsc1.view(sh1), dg1, db1, None, None, dW2, dsc2.view(sh2), dg2, db2, None, None, dWg0, dWg2, None, None)
+
         if DEFERRED.active and DEFERRED.first_use(W1, W2, Wz, Wg0, Wg2, g1, g2):
             # the step gathers the parameter gradients once, after the whole backward: the weight-gradient chain stays on the side
             # stream, unjoined, and the main stream carries what the NEXT layer's backward waits for (message sums -> dv product)
             with torch.cuda.stream(side):
                 wgrad1()
             main.wait_event(vec_done)
-            call("svnet_edgeblock_bwd_gather_f32", _p(msg), _p(rev_range), _p(rev_edge), _p(rev_src), _p(ut), _p(ub_tab), _p(ge_tab),
-                 _p(coef), _p(bcoef), Os, _p(dvc), _p(dzc), P, N, Cs, Cv, Ov, _p(acat), Rp, _p(ds_acc), _p(dv_acc), _p(dbeta_perm),
-                 _p(dbeta1), GATHER_CHUNK, _p(ovf_items), _p(ovf_count), _stream())
+            gather()
             gathered = main.record_event()
             gemm(3 * P, Cv, R, A=acat, a_rs=Rp, a_cs=1, a_scale=scv, B=wv, b_rs=Cv, b_cs=1, b_exact=True, C=dv_acc, ldc=Cv, accumulate=True)
             with torch.cuda.stream(side):
                 side.wait_event(gathered)
                 gemm(R, Cv, 3 * P, A=acat, a_rs=1, a_cs=Rp, B=v, b_rs=Cv, b_cs=1, C=GXc, ldc=Cv, accumulate=True)
-                dW1, dW2, dWz = torch.empty((Os, K1), **f32), torch.empty((Ov, 2 * Cv), **f32), torch.empty((3, 2 * Cv), **f32)
-                dsc1, dsc2, dscz = torch.empty((Os,), **f32), torch.empty((Ov,), **f32), torch.empty((3,), **f32)
-                call("svnet_edgeblock_bwd_params_f32", _p(GXp), _p(GXc), _p(W1), _p(sc1), _p(W2), _p(sc2), _p(Wz), _p(scz), Os, Ov, Cs, Cv,
-                     _p(dW1), _p(dsc1), _p(dW2), _p(dsc2), _p(dWz), _p(dscz), _stream())
+                grads = params()
             # (NOT the returned gradients: autograd keeps a returned tensor as the parameter's .grad only while nobody else holds it -
             #  with a second reference it clones it, on the main stream, before the side stream has written it; .grad keeps them alive)
             DEFERRED.keep.append((n16, slot_max, slot_min, gy, bcoef, x_sign, x_nz, dn_out, GXp, GXc, acat, v, W1, sc1, W2, sc2, Wz, scz))
-            return (ds_acc.view(B, N, Cs), dv_acc.view(B, N, 3, Cv), None, None, None, dWz, dscz.view(shz), dW1, dbeta1,
-                    dsc1.view(sh1), dg1, db1, None, None, dW2, dsc2.view(sh2), dg2, db2, None, None, dWg0, dWg2, None, None)
+            return grads
         wgrad1()
         with torch.cuda.stream(side):
-            call("svnet_edgeblock_bwd_gather_f32", _p(msg), _p(rev_range), _p(rev_edge), _p(rev_src), _p(ut), _p(ub_tab), _p(ge_tab),
-                 _p(coef), _p(bcoef), Os, _p(dvc), _p(dzc), P, N, Cs, Cv, Ov, _p(acat), Rp, _p(ds_acc), _p(dv_acc), _p(dbeta_perm),
-                 _p(dbeta1), GATHER_CHUNK, _p(ovf_items), _p(ovf_count), _stream())
+            gather()
             gathered = side.record_event()
             # linear2 and the v2s frame: dv += (acat * scv) . wv  (what the next layer waits for: stays behind the gather)
             gemm(3 * P, Cv, R, A=acat, a_rs=Rp, a_cs=1, a_scale=scv, B=wv, b_rs=Cv, b_cs=1, b_exact=True, C=dv_acc, ldc=Cv, accumulate=True)
@@ -2175,14 +2187,7 @@ class EdgeBlock(torch.autograd.Function):
         main.wait_event(gathered)
         gemm(R, Cv, 3 * P, A=acat, a_rs=1, a_cs=Rp, B=v, b_rs=Cv, b_cs=1, C=GXc, ldc=Cv, accumulate=True)
         main.wait_stream(side)
-        dW1, dW2, dWz = torch.empty((Os, K1), **f32), torch.empty((Ov, 2 * Cv), **f32), torch.empty((3, 2 * Cv), **f32)
-        dsc1, dsc2, dscz = torch.empty((Os,), **f32), torch.empty((Ov,), **f32), torch.empty((3,), **f32)
-        call("svnet_edgeblock_bwd_params_f32", _p(GXp), _p(GXc), _p(W1), _p(sc1), _p(W2), _p(sc2), _p(Wz), _p(scz), Os, Ov, Cs, Cv,
-             _p(dW1), _p(dsc1), _p(dW2), _p(dsc2), _p(dWz), _p(dscz), _stream())
-
-        # forward args: s, v, idx, k, training, Wz, scz, W1, beta1, scale1, g1, b1, rm1, rv1, W2, sc2, g2, b2, rm2, rv2, Wg0, Wg2, nbt1, nbt2
-        return (ds_acc.view(B, N, Cs), dv_acc.view(B, N, 3, Cv), None, None, None, dWz, dscz.view(shz), dW1, dbeta1,
-                dsc1.view(sh1), dg1, db1, None, None, dW2, dsc2.view(sh2), dg2, db2, None, None, dWg0, dWg2, None, None)
+        return params()
 
 
 class XyzBlock(torch.autograd.Function):
@@ -2222,36 +2227,9 @@ class XyzBlock(torch.autograd.Function):
         d.nc = NC
         call("svnet_xyzblock_fwd_f32", ctypes.byref(d), _stream())
 
-        H = Wg0.shape[0]
-        h = torch.empty((B, H), **f32)
-        gate = torch.empty((B, Ov), **f32)
-        gin = torch.empty((B, NG), **f32)
-        Wg0c, Wg2c = _f32c(Wg0), _f32c(Wg2)
-        job = _lib.GateFwdJob(None, _p(gate_sum), _p(gin), 1.0 / float(N * k), _p(Wg0c), _p(Wg2c), B, NG, H, Ov, _p(h), _p(gate))   # (beside the coefficients)
-
-        coef = torch.empty((4 * Os + 4 * Ov,), **f32)
-        s_out = torch.empty((B, N, Os), **f32)
-        v_out = torch.empty((B, N, 3, Ov), **f32)
-        slot = _SINK.slot(B, N, Os, Ov, dev) if _SINK is not None else None
-        kws = knn_table_ahead.workspace(B, N, Os, Ov, dev)
-        if _block_tail("svnet_xyzblock_tail_f32", P, N, E, Os, Ov, stat_y, stat_v, None, g1, b1, rm1, rv1, g2, b2, rm2, rv2, training, coef,
-                       nbt1, nbt2, job, y_max, y_min, mv, mvn, s_out, v_out, slot, kws):
-            pass
-        else:
-            call("svnet_xyzblock_coeffs_f32", _p(stat_y), _p(stat_v), E, Os, Ov, _p(g1), _p(b1), _p(rm1), _p(rv1), _p(g2), _p(b2), _p(rm2),
-                 _p(rv2), int(training), BN_EPS, BN_MOMENTUM, _p(coef), _p(nbt1), _p(nbt2), ctypes.byref(job), _stream())
-            if kws is not None:
-                call("svnet_xyzblock_apply_knn_f32", _p(y_max), _p(y_min), _p(mv), _p(mvn), _p(coef), _p(gate), P, N, Os, Ov, 0.2, _p(s_out),
-                     _p(v_out), *(slot if slot is not None else (None, 0, None, 0)), _p(kws), kws.numel(), _stream())
-            else:
-                call("svnet_xyzblock_apply_f32", _p(y_max), _p(y_min), _p(mv), _p(mvn), _p(coef), _p(gate), P, N, Os, Ov, 0.2, _p(s_out), _p(v_out),
-                     *(slot if slot is not None else (None, 0, None, 0)), _stream())
-        if kws is not None:
-            knn_table_ahead.table = (s_out.data_ptr(), v_out.data_ptr(), kws, B, N, Os + 3 * Ov)
-        _tap_act(Wg0, 2, h)
-        s_view, v_view = _SINK.wrote(s_out, v_out) if slot is not None else (None, None)
-        if TAP is not None:
-            TAP["pools"].append(torch.where(coef[:Os].view(1, Os) >= 0, slot_max, slot_min))
+        coef, gate, h, gin, s_out, v_out, s_view, v_view = _block_post(
+            "xyzblock", B, N, k, Os, Ov, gate_sum, Wg0, Wg0, Wg2, y_max, y_min, slot_max, slot_min, mv, mvn, stat_y, stat_v, None, g1, b1, rm1,
+            rv1, g2, b2, rm2, rv2, training, nbt1, nbt2)
         ctx.save_for_backward(x, idx, W0c, Wzc, W1c, W2c, y_max, y_min, slot_max, slot_min, mv, mvn, coef, gate, h, gin, g1, g2, Wg0, Wg2)
         ctx.meta = (B, N, k, Os, Ov, bool(training), NC)
         ctx.set_materialize_grads(False)

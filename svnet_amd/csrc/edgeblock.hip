@@ -14,6 +14,8 @@
 //   * VectorBN is affine in (v', v'/|v'|): mean_k out = gate * (Av * mean_k v' + Bv * mean_k v'/n').
 // One wave per point; lanes are channels.  The five ternary words of an edge row (s_j-s_i | s_i | s_v[:,0..2]) are
 // produced by wave ballots in a lane-friendly bit order; linear1's sign planes are permuted to that order once.
+// Behind the pooling (BatchNorm coefficients + gate MLP, apply pass, k-NN table, the one-launch tail) the kernels and host checks are
+// block_post.h's, shared with xyzblock.hip; this file supplies EdgeCoefArgs / block_coefs_channel and EdgeApplyMath.
 #include <limits.h>
 #include <stdlib.h>
 
@@ -22,6 +24,7 @@
 #include "common.h"
 #include "gate_mlp.h"
 #include "apply_knn.h"
+#include "block_post.h"
 
 namespace {
 
@@ -641,14 +644,14 @@ __global__ __launch_bounds__(256, 4) void edgeblock_fwd2_kernel(FwdArgs fa) {
 //   vector: q(n') = Av + Bv/n' with Av = gamma'*invstd', Bv = beta' - gamma'*mean'*invstd'
 // coef layout: [A1 (Os) | B1 (Os) | mean_y (Os) | invstd_y (Os) | Av (Ov) | Bv (Ov) | mean' (Ov) | invstd' (Ov)]
 struct EdgeCoefArgs {
-    const long long* stat_n; const double* stat_v; int64_t E; int Os, Ov;
+    const long long* stat1; const double* stat_v; int64_t E; int Os, Ov;
     const float* scale1; const float* g1; const float* b1; float* rm1; float* rv1;
     const float* g2; const float* b2; float* rm2; float* rv2;
     int training; float eps, momentum;
 };
 // channel c of both coefficient sets into `out` (the coef layout; global memory or a workgroup's LDS copy).  commit: this caller also
-// updates the running statistics (exactly one workgroup of a launch does).  One body for the coefficient kernel and the tail kernel.
-__device__ __forceinline__ void edge_coefs_channel(const EdgeCoefArgs& a, int c, bool commit, float* out) {
+// updates the running statistics (exactly one workgroup of a launch does).  Called by the kernels of block_post.h.
+__device__ __forceinline__ void block_coefs_channel(const EdgeCoefArgs& a, int c, bool commit, float* out) {
     const int Os = a.Os, Ov = a.Ov;
     const int64_t E = a.E;
     float* A1 = out; float* B1 = out + Os; float* MY = out + 2 * Os; float* IY = out + 3 * Os;
@@ -658,7 +661,7 @@ __device__ __forceinline__ void edge_coefs_channel(const EdgeCoefArgs& a, int c,
         if (a.training) {
             const double sc = (double)a.scale1[c];
             long long sn1 = 0, sn2 = 0;                        // the forward kernel's slices (exact integers: any order)
-            for (int sl = 0; sl < SVNET_RED_SLICES; ++sl) { sn1 += a.stat_n[sl * 2 * Os + c]; sn2 += a.stat_n[sl * 2 * Os + Os + c]; }
+            for (int sl = 0; sl < SVNET_RED_SLICES; ++sl) { sn1 += a.stat1[sl * 2 * Os + c]; sn2 += a.stat1[sl * 2 * Os + Os + c]; }
             const double mn = (double)sn1 / (double)E;
             double var_n = (double)sn2 / (double)E - mn * mn;
             if (var_n < 0.0) var_n = 0.0;
@@ -699,25 +702,14 @@ __device__ __forceinline__ void edge_coefs_channel(const EdgeCoefArgs& a, int c,
     }
 }
 
-__global__ void edgeblock_coeffs_kernel(EdgeCoefArgs a, float* __restrict__ coef, long long* __restrict__ nbt1, long long* __restrict__ nbt2,
-                                        svnet_gate_fwd_job job, int coef_blocks) {
-    if ((int)blockIdx.x >= coef_blocks) { svnet_gate_fwd_block(job, (int)blockIdx.x - coef_blocks); return; }   // the gate MLP beside the coefficients
-    const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c == 0 && a.training) {
-        if (nbt1) *nbt1 += 1;
-        if (nbt2) *nbt2 += 1;
-    }
-    edge_coefs_channel(a, c, true, coef);
-}
-
 // Pooled outputs: s_out = lrelu(A1 * (A1 >= 0 ? n_max : n_min) + B1); v_out = gate * (Av*mv + Bv*mvn).
-// (one functor for both apply kernels below: the same expressions, so the same contraction - their outputs are bit-identical,
-//  tests/test_hip_fused.py)
+// (one functor for the apply, apply + k-NN table and tail kernels of block_post.h: the same expressions, so the same contraction -
+//  their outputs are bit-identical, tests/test_hip_fused.py)
 struct EdgeApplyMath {
     const int32_t* __restrict__ n_max; const int32_t* __restrict__ n_min;
     const float* __restrict__ mv; const float* __restrict__ mvn;
     const float* __restrict__ A1; const float* __restrict__ B1; const float* __restrict__ Av; const float* __restrict__ Bv;
-    const float* __restrict__ gate;
+    const float* gate;                                  // (no __restrict__: the tail kernel passes job.gate, which it has just written)
     int Os, Ov;
     float slope;
     __device__ __forceinline__ float s(int64_t p, int o) const {
@@ -730,75 +722,6 @@ struct EdgeApplyMath {
         return gate[b * Ov + c] * (Av[c] * mv[e] + Bv[c] * mvn[e]);
     }
 };
-
-__global__ __launch_bounds__(256) void edgeblock_apply_kernel(const int32_t* __restrict__ n_max, const int32_t* __restrict__ n_min,
-                                                              const float* __restrict__ mv, const float* __restrict__ mvn,
-                                                              const float* __restrict__ coef, const float* __restrict__ gate,
-                                                              int64_t P, int64_t N, int Os, int Ov, float slope,
-                                                              float* __restrict__ s_out, float* __restrict__ v_out, float* __restrict__ s_cat,
-                                                              int64_t s_ld, float* __restrict__ v_cat, int64_t v_ld) {
-    const EdgeApplyMath m = {n_max, n_min, mv, mvn, coef, coef + Os, coef + 4 * Os, coef + 4 * Os + Ov, gate, Os, Ov, slope};
-    // a wave per point row: lanes over the Os scalar channels, then over the 3*Ov vector entries - no per-element divisions (the flat
-    // e -> (e % Os, q % Ov, q / 3Ov, p / N) form spent four 64-bit divisions on every output)
-    const int lane = threadIdx.x & 63;
-    const int64_t wave0 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6, nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
-    for (int64_t p = wave0; p < P; p += nwaves) {
-        const int64_t b = p / N;
-        for (int o = lane; o < Os; o += 64) {
-            const float z = m.s(p, o);
-            s_out[p * Os + o] = z;
-            if (s_cat) s_cat[p * s_ld + o] = z;            // (the level's column slice of the pyramid's concatenation, written in place)
-        }
-        for (int q = lane; q < 3 * Ov; q += 64) {
-            const int dd = q >= 2 * Ov ? 2 : (q >= Ov ? 1 : 0), c = q - dd * Ov;
-            const float z = m.v(p, b, q, c);
-            v_out[p * 3 * Ov + q] = z;
-            if (v_cat) v_cat[(p * 3 + dd) * v_ld + c] = z;
-        }
-    }
-}
-
-// ... and the same pass preparing the k-NN table of its output (apply_knn.h)
-__global__ __launch_bounds__(256) void edgeblock_apply_knn_kernel(const int32_t* __restrict__ n_max, const int32_t* __restrict__ n_min,
-                                                                  const float* __restrict__ mv, const float* __restrict__ mvn,
-                                                                  const float* __restrict__ coef, const float* __restrict__ gate,
-                                                                  int64_t P, int64_t N, int Os, int Ov, float slope,
-                                                                  float* __restrict__ s_out, float* __restrict__ v_out,
-                                                                  float* __restrict__ s_cat, int64_t s_ld, float* __restrict__ v_cat,
-                                                                  int64_t v_ld, float* __restrict__ xT, float* __restrict__ xx, int64_t Cpad) {
-    extern __shared__ float apply_knn_rows[];
-    const EdgeApplyMath m = {n_max, n_min, mv, mvn, coef, coef + Os, coef + 4 * Os, coef + 4 * Os + Ov, gate, Os, Ov, slope};
-    apply_knn_tiles<APPLY_KNN_TP>(m, P, N, Os, Ov, s_out, v_out, s_cat, s_ld, v_cat, v_ld, xT, xx, Cpad, apply_knn_rows);
-}
-
-// ---- coefficients + gate MLP + apply (+ the next k-NN's table) in one launch (svnet_hip.h: svnet_block_tail_desc).  A workgroup = one
-// tile of APPLY_KNN_TP points of cloud b: its 256 threads derive the coefficients into LDS (thread c: channel c of both sets, as the
-// coefficient kernel's threads do), run cloud b's gate MLP (every workgroup of the cloud writes the same h / gin / gate values), then the
-// apply pass reads both from there.  Workgroup 0 alone commits: coef, running statistics, counters.
-__global__ __launch_bounds__(256) void edgeblock_tail_kernel(EdgeCoefArgs ca, float* __restrict__ coef, long long* __restrict__ nbt1,
-                                                             long long* __restrict__ nbt2, svnet_gate_fwd_job job,
-                                                             const int32_t* __restrict__ n_max, const int32_t* __restrict__ n_min,
-                                                             const float* __restrict__ mv, const float* __restrict__ mvn, int64_t P, int64_t N,
-                                                             float slope, float* __restrict__ s_out, float* __restrict__ v_out,
-                                                             float* __restrict__ s_cat, int64_t s_ld, float* __restrict__ v_cat, int64_t v_ld,
-                                                             float* __restrict__ xT, float* __restrict__ xx, int64_t Cpad) {
-    extern __shared__ float tail_lds[];                                  // [coef: 4 Os + 4 Ov (rounded to 4) | the tile's rows]
-    const int Os = ca.Os, Ov = ca.Ov;
-    const int ncoef = (4 * Os + 4 * Ov + 3) & ~3;
-    const bool first = blockIdx.x == 0;
-    const int64_t b = ((int64_t)blockIdx.x * APPLY_KNN_TP) / N;
-    if (first && threadIdx.x == 0 && ca.training) {
-        if (nbt1) *nbt1 += 1;
-        if (nbt2) *nbt2 += 1;
-    }
-    edge_coefs_channel(ca, (int)threadIdx.x, first, tail_lds);
-    svnet_gate_fwd_block(job, (int)b);
-    __syncthreads();                                                     // the coefficients in LDS, the cloud's gate in global memory
-    if (first)
-        for (int i = threadIdx.x; i < 4 * Os + 4 * Ov; i += blockDim.x) coef[i] = tail_lds[i];
-    const EdgeApplyMath m = {n_max, n_min, mv, mvn, tail_lds, tail_lds + Os, tail_lds + 4 * Os, tail_lds + 4 * Os + Ov, job.gate, Os, Ov, slope};
-    apply_knn_tiles<APPLY_KNN_TP>(m, P, N, Os, Ov, s_out, v_out, s_cat, s_ld, v_cat, v_ld, xT, xx, Cpad, tail_lds + ncoef);
-}
 
 }  // namespace
 
@@ -861,53 +784,28 @@ extern "C" int svnet_edgeblock_coeffs_f32(const int64_t* stat_n, const double* s
                                           float* running_var1, const float* gamma2, const float* beta2, float* running_mean2,
                                           float* running_var2, int training, float eps, float momentum, float* coef,
                                           int64_t* num_batches_tracked1, int64_t* num_batches_tracked2, const svnet_gate_fwd_job* gate_job, void* stream) {
-    SVNET_REQUIRE(scale1 && gamma1 && beta1 && gamma2 && beta2 && coef && E > 0 && Os > 0 && Ov > 0, SVNET_E_ARG, "svnet_edgeblock_coeffs_f32: bad arguments");
-    SVNET_REQUIRE(training ? (stat_n && stat_v) : (running_mean1 && running_var1 && running_mean2 && running_var2), SVNET_E_ARG,
-                  "svnet_edgeblock_coeffs_f32: missing statistics");
-    const int64_t n = Os > Ov ? Os : Ov;
-    SVNET_REQUIRE(!gate_job || svnet_gate_fwd_job_ok(gate_job), SVNET_E_ARG, "svnet_edgeblock_coeffs_f32: bad gate job");
-    const int coef_blocks = (int)svnet_cdiv(n, 256);
-    const svnet_gate_fwd_job job = gate_job ? *gate_job : svnet_gate_fwd_job{};
+    SVNET_REQUIRE(scale1, SVNET_E_ARG, "svnet_edgeblock_coeffs_f32: bad arguments");
     const EdgeCoefArgs ca = {reinterpret_cast<const long long*>(stat_n), stat_v, E, (int)Os, (int)Ov, scale1, gamma1, beta1, running_mean1,
                              running_var1, gamma2, beta2, running_mean2, running_var2, training, eps, momentum};
-    hipLaunchKernelGGL(edgeblock_coeffs_kernel, dim3((unsigned)(coef_blocks + (gate_job ? gate_job->B : 0))), dim3(256), 0, (hipStream_t)stream,
-                       ca, coef, reinterpret_cast<long long*>(num_batches_tracked1), reinterpret_cast<long long*>(num_batches_tracked2), job, coef_blocks);
-    SVNET_CHECK_LAUNCH("edgeblock_coeffs_kernel");
-    return SVNET_OK;
+    return block_coeffs_launch("svnet_edgeblock_coeffs_f32", "edgeblock_coeffs_kernel", ca, Os, Ov, coef, num_batches_tracked1,
+                               num_batches_tracked2, gate_job, stream);
 }
 
 extern "C" int svnet_edgeblock_apply_f32(const int32_t* n_max, const int32_t* n_min, const float* mv, const float* mvn,
                                          const float* coef, const float* gate, int64_t P, int64_t N, int64_t Os, int64_t Ov,
                                          float slope, float* s_out, float* v_out, float* s_cat, int64_t s_ld, float* v_cat, int64_t v_ld,
                                          void* stream) {
-    SVNET_REQUIRE(n_max && n_min && mv && mvn && coef && gate && s_out && v_out && P >= 0 && N > 0, SVNET_E_ARG, "svnet_edgeblock_apply_f32: bad arguments");
-    SVNET_REQUIRE((!s_cat || s_ld >= Os) && (!v_cat || v_ld >= Ov), SVNET_E_ARG, "svnet_edgeblock_apply_f32: concatenation row shorter than the slice");
-    if (P == 0) return SVNET_OK;
-    hipLaunchKernelGGL(edgeblock_apply_kernel, dim3(svnet_grid(P * 64, 256, 256 * 8)), dim3(256), 0, (hipStream_t)stream, n_max, n_min,
-                       mv, mvn, coef, gate, P, N, (int)Os, (int)Ov, slope, s_out, v_out, s_cat, s_ld, v_cat, v_ld);
-    SVNET_CHECK_LAUNCH("edgeblock_apply_kernel");
-    return SVNET_OK;
+    return block_apply_launch<EdgeApplyMath>("svnet_edgeblock_apply_f32", "edgeblock_apply_kernel", n_max, n_min, mv, mvn, coef, gate, P, N, Os,
+                                             Ov, slope, s_out, v_out, s_cat, s_ld, v_cat, v_ld, stream);
 }
 
 extern "C" int svnet_edgeblock_apply_knn_f32(const int32_t* n_max, const int32_t* n_min, const float* mv, const float* mvn,
                                              const float* coef, const float* gate, int64_t P, int64_t N, int64_t Os, int64_t Ov,
                                              float slope, float* s_out, float* v_out, float* s_cat, int64_t s_ld, float* v_cat,
                                              int64_t v_ld, void* knn_workspace, size_t knn_workspace_bytes, void* stream) {
-    SVNET_REQUIRE(n_max && n_min && mv && mvn && coef && gate && s_out && v_out && knn_workspace && P > 0 && N > 0 && P % N == 0, SVNET_E_ARG,
-                  "svnet_edgeblock_apply_knn_f32: bad arguments");
-    SVNET_REQUIRE((!s_cat || s_ld >= Os) && (!v_cat || v_ld >= Ov), SVNET_E_ARG, "svnet_edgeblock_apply_knn_f32: concatenation row shorter than the slice");
-    int64_t Cpad = 0;
-    SVNET_REQUIRE(apply_knn_supported(P, N, Os, Ov, &Cpad), SVNET_E_UNSUPPORTED,
-                  "svnet_edgeblock_apply_knn_f32: N=%lld, Os=%lld, Ov=%lld not supported (ask svnet_knn_table_fusable first)", (long long)N,
-                  (long long)Os, (long long)Ov);
-    SVNET_REQUIRE(knn_workspace_bytes >= svnet_knn_workspace_bytes(P / N, N, Os + 3 * Ov), SVNET_E_WORKSPACE,
-                  "svnet_edgeblock_apply_knn_f32: k-NN workspace too small");
-    float* xT = (float*)knn_workspace;
-    float* xx = xT + P * ((Os + 3 * Ov + 7) / 8 * 8);
-    hipLaunchKernelGGL(edgeblock_apply_knn_kernel, dim3((unsigned)(P / APPLY_KNN_TP)), dim3(256), apply_knn_lds_bytes(Os, Ov), (hipStream_t)stream,
-                       n_max, n_min, mv, mvn, coef, gate, P, N, (int)Os, (int)Ov, slope, s_out, v_out, s_cat, s_ld, v_cat, v_ld, xT, xx, Cpad);
-    SVNET_CHECK_LAUNCH("edgeblock_apply_knn_kernel");
-    return SVNET_OK;
+    return block_apply_knn_launch<EdgeApplyMath>("svnet_edgeblock_apply_knn_f32", "edgeblock_apply_knn_kernel", n_max, n_min, mv, mvn, coef,
+                                                 gate, P, N, Os, Ov, slope, s_out, v_out, s_cat, s_ld, v_cat, v_ld, knn_workspace,
+                                                 knn_workspace_bytes, stream);
 }
 
 extern "C" int svnet_block_tail_supported(int64_t P, int64_t N, int64_t Os, int64_t Ov, int with_knn_table) {
@@ -917,42 +815,11 @@ extern "C" int svnet_block_tail_supported(int64_t P, int64_t N, int64_t Os, int6
     return (!with_knn_table || apply_knn_supported(P, N, Os, Ov, &Cpad)) ? 1 : 0;
 }
 
-// the checks both tail entry points share; returns the launch's dynamic LDS bytes through *lds and the table pointers
-static int block_tail_check(const svnet_block_tail_desc& d, const char* who, size_t* lds, float** xT, float** xx, int64_t* Cpad) {
-    SVNET_REQUIRE(d.hi && d.lo && d.mv && d.mvn && d.coef && d.s_out && d.v_out && d.gamma1 && d.beta1 && d.gamma2 && d.beta2, SVNET_E_ARG,
-                  "%s: null pointer", who);
-    SVNET_REQUIRE(d.training ? (d.stat1 && d.stat_v) : (d.running_mean1 && d.running_var1 && d.running_mean2 && d.running_var2), SVNET_E_ARG,
-                  "%s: missing statistics", who);
-    SVNET_REQUIRE(svnet_gate_fwd_job_ok(&d.gate) && d.gate.Ov == d.Ov && d.gate.B * d.N == d.P, SVNET_E_ARG, "%s: bad gate job", who);
-    SVNET_REQUIRE((!d.s_cat || d.s_ld >= d.Os) && (!d.v_cat || d.v_ld >= d.Ov), SVNET_E_ARG, "%s: concatenation row shorter than the slice", who);
-    SVNET_REQUIRE(svnet_block_tail_supported(d.P, d.N, d.Os, d.Ov, d.knn_workspace != nullptr), SVNET_E_UNSUPPORTED,
-                  "%s: P=%lld N=%lld Os=%lld Ov=%lld not supported (svnet_block_tail_supported)", who, (long long)d.P, (long long)d.N,
-                  (long long)d.Os, (long long)d.Ov);
-    *xT = nullptr; *xx = nullptr; *Cpad = 0;
-    if (d.knn_workspace) {
-        SVNET_REQUIRE(d.knn_workspace_bytes >= svnet_knn_workspace_bytes(d.P / d.N, d.N, d.Os + 3 * d.Ov), SVNET_E_WORKSPACE,
-                      "%s: k-NN workspace too small", who);
-        apply_knn_supported(d.P, d.N, d.Os, d.Ov, Cpad);
-        *xT = (float*)d.knn_workspace;
-        *xx = *xT + d.P * ((d.Os + 3 * d.Ov + 7) / 8 * 8);
-    }
-    *lds = block_tail_lds_bytes(d.Os, d.Ov, d.knn_workspace != nullptr);
-    return SVNET_OK;
-}
-
 extern "C" int svnet_edgeblock_tail_f32(const svnet_block_tail_desc* desc, void* stream) {
     SVNET_REQUIRE(desc, SVNET_E_ARG, "svnet_edgeblock_tail_f32: null descriptor");
+    SVNET_REQUIRE(desc->scale1, SVNET_E_ARG, "svnet_edgeblock_tail_f32: scale1 is required");
     const svnet_block_tail_desc& d = *desc;
-    SVNET_REQUIRE(d.scale1, SVNET_E_ARG, "svnet_edgeblock_tail_f32: scale1 is required");
-    size_t lds; float* xT; float* xx; int64_t Cpad;
-    const int rc = block_tail_check(d, "svnet_edgeblock_tail_f32", &lds, &xT, &xx, &Cpad);
-    if (rc != SVNET_OK) return rc;
     const EdgeCoefArgs ca = {reinterpret_cast<const long long*>(d.stat1), d.stat_v, d.E, (int)d.Os, (int)d.Ov, d.scale1, d.gamma1, d.beta1,
                              d.running_mean1, d.running_var1, d.gamma2, d.beta2, d.running_mean2, d.running_var2, d.training, d.eps, d.momentum};
-    hipLaunchKernelGGL(edgeblock_tail_kernel, dim3((unsigned)(d.P / APPLY_KNN_TP)), dim3(256), lds, (hipStream_t)stream, ca, d.coef,
-                       reinterpret_cast<long long*>(d.num_batches_tracked1), reinterpret_cast<long long*>(d.num_batches_tracked2), d.gate,
-                       (const int32_t*)d.hi, (const int32_t*)d.lo, d.mv, d.mvn, d.P, d.N, d.slope, d.s_out, d.v_out, d.s_cat, d.s_ld, d.v_cat,
-                       d.v_ld, xT, xx, Cpad);
-    SVNET_CHECK_LAUNCH("edgeblock_tail_kernel");
-    return SVNET_OK;
+    return block_tail_launch<EdgeApplyMath, int32_t>("svnet_edgeblock_tail_f32", "edgeblock_tail_kernel", d, ca, stream);
 }

@@ -12,12 +12,15 @@
 // BatchNorm+LeakyReLU (keep max_k y, min_k y and their slots) and VectorBN is affine in (v', v'/|v'|).
 // The input coordinates need no gradient, so the backward is a pure reduction into the (tiny) parameter gradients:
 // per-lane register accumulators, flushed once per wave with float atomics.
+// Behind the pooling (BatchNorm coefficients + gate MLP, apply pass, k-NN table, the one-launch tail) the kernels and host checks are
+// block_post.h's, shared with edgeblock.hip; this file supplies XyzCoefArgs / block_coefs_channel and XyzApplyMath.
 #include <float.h>
 
 #include "common.h"
 #include "prelude.h"
 #include "gate_mlp.h"
 #include "apply_knn.h"
+#include "block_post.h"
 
 namespace {
 
@@ -263,19 +266,19 @@ __global__ __launch_bounds__(256) void xyzblock_fwd_kernel(XyzFwdArgs fa) {
 
 // coef = [A1 | B1 | mean_y | invstd_y (Os each) | Av | Bv | mean_n' | invstd_n' (Ov each)]  (same layout as edgeblock)
 struct XyzCoefArgs {
-    const double* stat_y; const double* stat_v; int64_t E; int Os, Ov;
+    const double* stat1; const double* stat_v; int64_t E; int Os, Ov;
     const float* g1; const float* b1; float* rm1; float* rv1; const float* g2; const float* b2; float* rm2; float* rv2;
     int training; float eps, momentum;
 };
 // channel c of both coefficient sets into `out` (global memory or a workgroup's LDS copy); commit: this caller also updates the running
-// statistics.  One body for the coefficient kernel and the tail kernel.
-__device__ __forceinline__ void xyz_coefs_channel(const XyzCoefArgs& a, int c, bool commit, float* coef) {
+// statistics.  Called by the kernels of block_post.h.
+__device__ __forceinline__ void block_coefs_channel(const XyzCoefArgs& a, int c, bool commit, float* coef) {
     const int Os = a.Os, Ov = a.Ov;
     const int64_t E = a.E;
     for (int part = 0; part < 2; ++part) {
         const int C = part == 0 ? Os : Ov;
         if (c >= C) continue;
-        const double* st = part == 0 ? a.stat_y : a.stat_v;
+        const double* st = part == 0 ? a.stat1 : a.stat_v;
         const float* g = part == 0 ? a.g1 : a.g2;
         const float* bb = part == 0 ? a.b1 : a.b2;
         float* rm = part == 0 ? a.rm1 : a.rm2;
@@ -303,23 +306,12 @@ __device__ __forceinline__ void xyz_coefs_channel(const XyzCoefArgs& a, int c, b
     }
 }
 
-__global__ void xyzblock_coeffs_kernel(XyzCoefArgs a, float* __restrict__ coef, long long* __restrict__ nbt1, long long* __restrict__ nbt2,
-                                       svnet_gate_fwd_job job, int coef_blocks) {
-    if ((int)blockIdx.x >= coef_blocks) { svnet_gate_fwd_block(job, (int)blockIdx.x - coef_blocks); return; }   // the gate MLP beside the coefficients
-    const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c == 0 && a.training) {
-        if (nbt1) *nbt1 += 1;
-        if (nbt2) *nbt2 += 1;
-    }
-    xyz_coefs_channel(a, c, true, coef);
-}
-
-// (one functor for both apply kernels below: bit-identical outputs)
+// (one functor for the apply, apply + k-NN table and tail kernels of block_post.h: bit-identical outputs)
 struct XyzApplyMath {
     const float* __restrict__ y_max; const float* __restrict__ y_min;
     const float* __restrict__ mv; const float* __restrict__ mvn;
     const float* __restrict__ A1; const float* __restrict__ B1; const float* __restrict__ Av; const float* __restrict__ Bv;
-    const float* __restrict__ gate;
+    const float* gate;                                  // (no __restrict__: the tail kernel passes job.gate, which it has just written)
     int Os, Ov;
     float slope;
     __device__ __forceinline__ float s(int64_t p, int o) const {
@@ -335,72 +327,6 @@ struct XyzApplyMath {
         return __fmul_rn(gate[b * Ov + c], __fmaf_rn(Bv[c], mvn[e], __fmul_rn(Av[c], mv[e])));
     }
 };
-
-__global__ __launch_bounds__(256) void xyzblock_apply_kernel(const float* __restrict__ y_max, const float* __restrict__ y_min,
-                                                             const float* __restrict__ mv, const float* __restrict__ mvn,
-                                                             const float* __restrict__ coef, const float* __restrict__ gate,
-                                                             int64_t P, int64_t N, int Os, int Ov, float slope,
-                                                             float* __restrict__ s_out, float* __restrict__ v_out, float* __restrict__ s_cat,
-                                                             int64_t s_ld, float* __restrict__ v_cat, int64_t v_ld) {
-    const XyzApplyMath m = {y_max, y_min, mv, mvn, coef, coef + Os, coef + 4 * Os, coef + 4 * Os + Ov, gate, Os, Ov, slope};
-    // a wave per point row: lanes over the Os scalar channels, then over the 3*Ov vector entries - no per-element divisions (the flat
-    // e -> (e % Os, q % Ov, q / 3Ov, p / N) form spent four 64-bit divisions on every output)
-    const int lane = threadIdx.x & 63;
-    const int64_t wave0 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6, nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
-    for (int64_t p = wave0; p < P; p += nwaves) {
-        const int64_t b = p / N;
-        for (int o = lane; o < Os; o += 64) {
-            const float z = m.s(p, o);
-            s_out[p * Os + o] = z;
-            if (s_cat) s_cat[p * s_ld + o] = z;            // (the level's column slice of the pyramid's concatenation, written in place)
-        }
-        for (int q = lane; q < 3 * Ov; q += 64) {
-            const int dd = q >= 2 * Ov ? 2 : (q >= Ov ? 1 : 0), c = q - dd * Ov;
-            const float z = m.v(p, b, q, c);
-            v_out[p * 3 * Ov + q] = z;
-            if (v_cat) v_cat[(p * 3 + dd) * v_ld + c] = z;
-        }
-    }
-}
-
-// ... and the same pass preparing the k-NN table of its output (apply_knn.h)
-__global__ __launch_bounds__(256) void xyzblock_apply_knn_kernel(const float* __restrict__ y_max, const float* __restrict__ y_min,
-                                                                 const float* __restrict__ mv, const float* __restrict__ mvn,
-                                                                 const float* __restrict__ coef, const float* __restrict__ gate,
-                                                                 int64_t P, int64_t N, int Os, int Ov, float slope,
-                                                                 float* __restrict__ s_out, float* __restrict__ v_out,
-                                                                 float* __restrict__ s_cat, int64_t s_ld, float* __restrict__ v_cat,
-                                                                 int64_t v_ld, float* __restrict__ xT, float* __restrict__ xx, int64_t Cpad) {
-    extern __shared__ float apply_knn_rows[];
-    const XyzApplyMath m = {y_max, y_min, mv, mvn, coef, coef + Os, coef + 4 * Os, coef + 4 * Os + Ov, gate, Os, Ov, slope};
-    apply_knn_tiles<APPLY_KNN_TP>(m, P, N, Os, Ov, s_out, v_out, s_cat, s_ld, v_cat, v_ld, xT, xx, Cpad, apply_knn_rows);
-}
-
-// ---- coefficients + gate MLP + apply (+ the next k-NN's table) in one launch: as edgeblock_tail_kernel (edgeblock.hip)
-__global__ __launch_bounds__(256) void xyzblock_tail_kernel(XyzCoefArgs ca, float* __restrict__ coef, long long* __restrict__ nbt1,
-                                                            long long* __restrict__ nbt2, svnet_gate_fwd_job job,
-                                                            const float* __restrict__ y_max, const float* __restrict__ y_min,
-                                                            const float* __restrict__ mv, const float* __restrict__ mvn, int64_t P, int64_t N,
-                                                            float slope, float* __restrict__ s_out, float* __restrict__ v_out,
-                                                            float* __restrict__ s_cat, int64_t s_ld, float* __restrict__ v_cat, int64_t v_ld,
-                                                            float* __restrict__ xT, float* __restrict__ xx, int64_t Cpad) {
-    extern __shared__ float tail_lds[];                                  // [coef: 4 Os + 4 Ov (rounded to 4) | the tile's rows]
-    const int Os = ca.Os, Ov = ca.Ov;
-    const int ncoef = (4 * Os + 4 * Ov + 3) & ~3;
-    const bool first = blockIdx.x == 0;
-    const int64_t b = ((int64_t)blockIdx.x * APPLY_KNN_TP) / N;
-    if (first && threadIdx.x == 0 && ca.training) {
-        if (nbt1) *nbt1 += 1;
-        if (nbt2) *nbt2 += 1;
-    }
-    xyz_coefs_channel(ca, (int)threadIdx.x, first, tail_lds);
-    svnet_gate_fwd_block(job, (int)b);
-    __syncthreads();                                                     // the coefficients in LDS, the cloud's gate in global memory
-    if (first)
-        for (int i = threadIdx.x; i < 4 * Os + 4 * Ov; i += blockDim.x) coef[i] = tail_lds[i];
-    const XyzApplyMath m = {y_max, y_min, mv, mvn, tail_lds, tail_lds + Os, tail_lds + 4 * Os, tail_lds + 4 * Os + Ov, job.gate, Os, Ov, slope};
-    apply_knn_tiles<APPLY_KNN_TP>(m, P, N, Os, Ov, s_out, v_out, s_cat, s_ld, v_cat, v_ld, xT, xx, Cpad, tail_lds + ncoef);
-}
 
 // ---------------------------------------------------------------------------------------------- backward
 // prelude: gy = Gs*lrelu'(y*), red = [sum gy | sum gy*xhat*], dgate, redv = [sum Gv*gate*mv | sum Gv*gate*mvn]  (prelude.h)
@@ -681,84 +607,34 @@ extern "C" int svnet_xyzblock_coeffs_f32(const double* stat_y, const double* sta
                                          const float* gamma2, const float* beta2, float* running_mean2, float* running_var2,
                                          int training, float eps, float momentum, float* coef, int64_t* num_batches_tracked1,
                                          int64_t* num_batches_tracked2, const svnet_gate_fwd_job* gate_job, void* stream) {
-    SVNET_REQUIRE(gamma1 && beta1 && gamma2 && beta2 && coef && E > 0 && Os > 0 && Ov > 0, SVNET_E_ARG, "svnet_xyzblock_coeffs_f32: bad arguments");
-    SVNET_REQUIRE(training ? (stat_y && stat_v) : (running_mean1 && running_var1 && running_mean2 && running_var2), SVNET_E_ARG,
-                  "svnet_xyzblock_coeffs_f32: missing statistics");
-    const int64_t n = Os > Ov ? Os : Ov;
-    SVNET_REQUIRE(!gate_job || svnet_gate_fwd_job_ok(gate_job), SVNET_E_ARG, "svnet_xyzblock_coeffs_f32: bad gate job");
-    const int coef_blocks = (int)svnet_cdiv(n, 256);
-    const svnet_gate_fwd_job job = gate_job ? *gate_job : svnet_gate_fwd_job{};
     const XyzCoefArgs ca = {stat_y, stat_v, E, (int)Os, (int)Ov, gamma1, beta1, running_mean1, running_var1, gamma2, beta2, running_mean2,
                             running_var2, training, eps, momentum};
-    hipLaunchKernelGGL(xyzblock_coeffs_kernel, dim3((unsigned)(coef_blocks + (gate_job ? gate_job->B : 0))), dim3(256), 0, (hipStream_t)stream, ca,
-                       coef, reinterpret_cast<long long*>(num_batches_tracked1), reinterpret_cast<long long*>(num_batches_tracked2), job, coef_blocks);
-    SVNET_CHECK_LAUNCH("xyzblock_coeffs_kernel");
-    return SVNET_OK;
+    return block_coeffs_launch("svnet_xyzblock_coeffs_f32", "xyzblock_coeffs_kernel", ca, Os, Ov, coef, num_batches_tracked1,
+                               num_batches_tracked2, gate_job, stream);
 }
 
 extern "C" int svnet_xyzblock_apply_f32(const float* y_max, const float* y_min, const float* mv, const float* mvn, const float* coef,
                                         const float* gate, int64_t P, int64_t N, int64_t Os, int64_t Ov, float slope, float* s_out,
                                         float* v_out, float* s_cat, int64_t s_ld, float* v_cat, int64_t v_ld, void* stream) {
-    SVNET_REQUIRE(y_max && y_min && mv && mvn && coef && gate && s_out && v_out && P >= 0 && N > 0, SVNET_E_ARG, "svnet_xyzblock_apply_f32: bad arguments");
-    SVNET_REQUIRE((!s_cat || s_ld >= Os) && (!v_cat || v_ld >= Ov), SVNET_E_ARG, "svnet_xyzblock_apply_f32: concatenation row shorter than the slice");
-    if (P == 0) return SVNET_OK;
-    hipLaunchKernelGGL(xyzblock_apply_kernel, dim3(svnet_grid(P * 64, 256, 256 * 8)), dim3(256), 0, (hipStream_t)stream, y_max, y_min, mv,
-                       mvn, coef, gate, P, N, (int)Os, (int)Ov, slope, s_out, v_out, s_cat, s_ld, v_cat, v_ld);
-    SVNET_CHECK_LAUNCH("xyzblock_apply_kernel");
-    return SVNET_OK;
+    return block_apply_launch<XyzApplyMath>("svnet_xyzblock_apply_f32", "xyzblock_apply_kernel", y_max, y_min, mv, mvn, coef, gate, P, N, Os, Ov,
+                                            slope, s_out, v_out, s_cat, s_ld, v_cat, v_ld, stream);
 }
 
 extern "C" int svnet_xyzblock_apply_knn_f32(const float* y_max, const float* y_min, const float* mv, const float* mvn, const float* coef,
                                             const float* gate, int64_t P, int64_t N, int64_t Os, int64_t Ov, float slope, float* s_out,
                                             float* v_out, float* s_cat, int64_t s_ld, float* v_cat, int64_t v_ld, void* knn_workspace,
                                             size_t knn_workspace_bytes, void* stream) {
-    SVNET_REQUIRE(y_max && y_min && mv && mvn && coef && gate && s_out && v_out && knn_workspace && P > 0 && N > 0 && P % N == 0, SVNET_E_ARG,
-                  "svnet_xyzblock_apply_knn_f32: bad arguments");
-    SVNET_REQUIRE((!s_cat || s_ld >= Os) && (!v_cat || v_ld >= Ov), SVNET_E_ARG, "svnet_xyzblock_apply_knn_f32: concatenation row shorter than the slice");
-    int64_t Cpad = 0;
-    SVNET_REQUIRE(apply_knn_supported(P, N, Os, Ov, &Cpad), SVNET_E_UNSUPPORTED,
-                  "svnet_xyzblock_apply_knn_f32: N=%lld, Os=%lld, Ov=%lld not supported (ask svnet_knn_table_fusable first)", (long long)N,
-                  (long long)Os, (long long)Ov);
-    SVNET_REQUIRE(knn_workspace_bytes >= svnet_knn_workspace_bytes(P / N, N, Os + 3 * Ov), SVNET_E_WORKSPACE,
-                  "svnet_xyzblock_apply_knn_f32: k-NN workspace too small");
-    float* xT = (float*)knn_workspace;
-    float* xx = xT + P * ((Os + 3 * Ov + 7) / 8 * 8);
-    hipLaunchKernelGGL(xyzblock_apply_knn_kernel, dim3((unsigned)(P / APPLY_KNN_TP)), dim3(256), apply_knn_lds_bytes(Os, Ov), (hipStream_t)stream,
-                       y_max, y_min, mv, mvn, coef, gate, P, N, (int)Os, (int)Ov, slope, s_out, v_out, s_cat, s_ld, v_cat, v_ld, xT, xx, Cpad);
-    SVNET_CHECK_LAUNCH("xyzblock_apply_knn_kernel");
-    return SVNET_OK;
+    return block_apply_knn_launch<XyzApplyMath>("svnet_xyzblock_apply_knn_f32", "xyzblock_apply_knn_kernel", y_max, y_min, mv, mvn, coef, gate, P,
+                                                N, Os, Ov, slope, s_out, v_out, s_cat, s_ld, v_cat, v_ld, knn_workspace, knn_workspace_bytes,
+                                                stream);
 }
 
 extern "C" int svnet_xyzblock_tail_f32(const svnet_block_tail_desc* desc, void* stream) {
     SVNET_REQUIRE(desc, SVNET_E_ARG, "svnet_xyzblock_tail_f32: null descriptor");
     const svnet_block_tail_desc& d = *desc;
-    const char* who = "svnet_xyzblock_tail_f32";
-    SVNET_REQUIRE(d.hi && d.lo && d.mv && d.mvn && d.coef && d.s_out && d.v_out && d.gamma1 && d.beta1 && d.gamma2 && d.beta2, SVNET_E_ARG,
-                  "%s: null pointer", who);
-    SVNET_REQUIRE(d.training ? (d.stat1 && d.stat_v) : (d.running_mean1 && d.running_var1 && d.running_mean2 && d.running_var2), SVNET_E_ARG,
-                  "%s: missing statistics", who);
-    SVNET_REQUIRE(svnet_gate_fwd_job_ok(&d.gate) && d.gate.Ov == d.Ov && d.gate.B * d.N == d.P, SVNET_E_ARG, "%s: bad gate job", who);
-    SVNET_REQUIRE((!d.s_cat || d.s_ld >= d.Os) && (!d.v_cat || d.v_ld >= d.Ov), SVNET_E_ARG, "%s: concatenation row shorter than the slice", who);
-    SVNET_REQUIRE(svnet_block_tail_supported(d.P, d.N, d.Os, d.Ov, d.knn_workspace != nullptr), SVNET_E_UNSUPPORTED,
-                  "%s: P=%lld N=%lld Os=%lld Ov=%lld not supported (svnet_block_tail_supported)", who, (long long)d.P, (long long)d.N,
-                  (long long)d.Os, (long long)d.Ov);
-    float* xT = nullptr; float* xx = nullptr; int64_t Cpad = 0;
-    if (d.knn_workspace) {
-        SVNET_REQUIRE(d.knn_workspace_bytes >= svnet_knn_workspace_bytes(d.P / d.N, d.N, d.Os + 3 * d.Ov), SVNET_E_WORKSPACE,
-                      "%s: k-NN workspace too small", who);
-        apply_knn_supported(d.P, d.N, d.Os, d.Ov, &Cpad);
-        xT = (float*)d.knn_workspace;
-        xx = xT + d.P * ((d.Os + 3 * d.Ov + 7) / 8 * 8);
-    }
-    const size_t lds = block_tail_lds_bytes(d.Os, d.Ov, d.knn_workspace != nullptr);
     const XyzCoefArgs ca = {reinterpret_cast<const double*>(d.stat1), d.stat_v, d.E, (int)d.Os, (int)d.Ov, d.gamma1, d.beta1, d.running_mean1,
                             d.running_var1, d.gamma2, d.beta2, d.running_mean2, d.running_var2, d.training, d.eps, d.momentum};
-    hipLaunchKernelGGL(xyzblock_tail_kernel, dim3((unsigned)(d.P / APPLY_KNN_TP)), dim3(256), lds, (hipStream_t)stream, ca, d.coef,
-                       reinterpret_cast<long long*>(d.num_batches_tracked1), reinterpret_cast<long long*>(d.num_batches_tracked2), d.gate,
-                       (const float*)d.hi, (const float*)d.lo, d.mv, d.mvn, d.P, d.N, d.slope, d.s_out, d.v_out, d.s_cat, d.s_ld, d.v_cat,
-                       d.v_ld, xT, xx, Cpad);
-    SVNET_CHECK_LAUNCH("xyzblock_tail_kernel");
-    return SVNET_OK;
+    return block_tail_launch<XyzApplyMath, float>("svnet_xyzblock_tail_f32", "xyzblock_tail_kernel", d, ca, stream);
 }
 
 extern "C" int svnet_xyzblock_bwd_prelude_f32(const float* gs, const float* gv, const float* y_max, const float* y_min, const float* mv,
