@@ -47,7 +47,7 @@ int svnet_slices_sum_f64(double* buf, int64_t L, void* stream);
  * changes its required length (200: sliced accumulators, SVNET_SLICED_LEN; 400: this header; 401: the totals of a sliced accumulator are
  * written by its consumer, svnet_slices_sum_*; 402: GX of svnet_v2s_bwd_*, gw of svnet_xyzblock_bwd_f32 and col_sum of svnet_gemm_f32 are sliced accumulators; 403: svnet_binweight_grad_f32 takes sliced inputs).  svnet_version() returns the value the
  * library was BUILT with: a caller compiled against another header must refuse to run (svnet_amd/_lib.py does).                   */
-#define SVNET_ABI_VERSION 417
+#define SVNET_ABI_VERSION 418
 int svnet_version(void);
 const char* svnet_last_error(void);
 
@@ -667,6 +667,42 @@ int svnet_sgd_step_f32(float* p, const float* g, float* buf, int64_t n, float lr
  * sgd hyper = [lr, momentum, weight_decay, first_step (0 / 1)].                                                                    */
 int svnet_adam_step_dev_f32(float* p, const float* g, float* m, float* v, int64_t n, const float* hyper, void* stream);
 int svnet_sgd_step_dev_f32(float* p, const float* g, float* buf, int64_t n, const float* hyper, void* stream);
+
+/* ------------------------------------------------------------------ batch assembly from a device-resident pool
+ * What the reference's loaders do per sample on the host (data.py:165-170 translate_pointcloud; :192-198 ModelNet40, :284-294
+ * ShapeNetPart, :327-337 ScanObjectNN), the collate, the per-batch rotation (main_cls_dgcnn.py:168-178) and the permute to [B,3,N]
+ * (:179) as ONE launch, one workgroup per cloud, into fixed caller-owned buffers.  Everything slot b receives is a pure function of
+ * (seed, epoch, g = first + b) - counter-based splitmix64, the derivation is fixed in svnet_amd/data.py's docstring - so batch size,
+ * rank count, graph replay and a resume cannot change a sample.  Slots count .. B-1 repeat slot 0 (a short final batch stays finite).
+ * The sorted modes put 8 bytes per key into LDS (keys: N for FIRST_SHUFFLED, P for SUBSET; at most 8192 = 64 KiB, no opt-in). */
+#define SVNET_BATCH_FIRST_SHUFFLED 0 /* the first N points of the cloud, in random order */
+#define SVNET_BATCH_SUBSET 1         /* N of all P points, in random order */
+#define SVNET_BATCH_FIRST_ORDERED 2  /* the first N points as stored */
+#define SVNET_BATCH_ROTATE_NONE 0
+#define SVNET_BATCH_ROTATE_Z 1       /* uniform angle about z */
+#define SVNET_BATCH_ROTATE_SO3 2     /* uniform rotation */
+typedef struct svnet_batch_desc {
+    const float* data;    /* [M,P,3] pool, point-major */
+    const int64_t* label; /* [M] */
+    const int64_t* seg;   /* [M,P] or NULL */
+    const int64_t* order; /* [L] pool indices in epoch order; an entry outside 0 .. M-1 poisons its slot (NaN, -1) and reads nothing */
+    int64_t M, P, L;
+    int64_t B, N;         /* the output buffers' batch size and points per cloud, N <= P */
+    int64_t first, count; /* slot b < count holds position first + b of `order`; 1 <= count <= B, first + count <= L */
+    int64_t seed, epoch;
+    int select_mode;      /* SVNET_BATCH_FIRST_SHUFFLED / _SUBSET / _FIRST_ORDERED */
+    int scale_shift;      /* 0 / 1: x * scale + shift per axis, scale ~ U(2/3, 3/2), shift ~ U(-0.2, 0.2) per cloud */
+    int rotate;           /* SVNET_BATCH_ROTATE_*: R x, applied after scale and shift */
+    int64_t num_cat;      /* columns of onehot */
+    float* x;             /* [B,3,N] */
+    int64_t* y;           /* [B] */
+    int64_t* seg_out;     /* [B,N] in x's point order, or NULL */
+    float* onehot;        /* [B,num_cat] one-hot of the label, or NULL */
+    float* params;        /* [B,16]: 3 scales, 3 shifts, 9 rotation entries (row-major), 0 */
+} svnet_batch_desc;
+/* 1 when svnet_batch_assemble_f32 takes the shape, else 0: a pure host function. */
+int svnet_batch_supported(int64_t P, int64_t N, int select_mode);
+int svnet_batch_assemble_f32(const svnet_batch_desc* d, void* stream);
 
 /* ------------------------------------------------------------------ diagnostics (no reference counterpart)
  * One thread writes the constant-rate device clock (s_memrealtime: 100 MHz ticks) to *slot when the stream reaches it: the start

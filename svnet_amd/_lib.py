@@ -10,7 +10,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SVNET_DIAG_LIB") or os.path.join(_HERE, "libsvnet_hip.so")    # (SVNET_DIAG_LIB: an ablation build, tools/ only)
 _lib = None
-ABI_VERSION = 417       # include/svnet_hip.h SVNET_ABI_VERSION: argument lists / buffer-length contracts this binding was written against
+ABI_VERSION = 418       # include/svnet_hip.h SVNET_ABI_VERSION: argument lists / buffer-length contracts this binding was written against
 
 c_p = ctypes.c_void_p
 c_i64 = ctypes.c_int64
@@ -146,6 +146,20 @@ class BinHeadDesc(ctypes.Structure):
     ]
 
 
+class BatchDesc(ctypes.Structure):
+    """struct svnet_batch_desc (include/svnet_hip.h)."""
+    _fields_ = [
+        ("data", c_p), ("label", c_p), ("seg", c_p), ("order", c_p),
+        ("M", c_i64), ("P", c_i64), ("L", c_i64),
+        ("B", c_i64), ("N", c_i64),
+        ("first", c_i64), ("count", c_i64),
+        ("seed", c_i64), ("epoch", c_i64),
+        ("select_mode", c_int), ("scale_shift", c_int), ("rotate", c_int),
+        ("num_cat", c_i64),
+        ("x", c_p), ("y", c_p), ("seg_out", c_p), ("onehot", c_p), ("params", c_p),
+    ]
+
+
 # The post-pool stage of a fused level has one entry point per block (edge / xyz) and one argument list for both (csrc/block_post.h):
 #   coeffs: stat1, stat_v, E, Os, Ov, [the edge block's scale1,] gamma1 .. running_var2, training, eps, momentum, coef, nbt1, nbt2, gate job, stream
 #   apply:  hi, lo, mv, mvn, coef, gate, P, N, Os, Ov, slope, s_out, v_out, s_cat, s_ld, v_cat, v_ld  (+ stream / + k-NN workspace, bytes, stream)
@@ -249,6 +263,8 @@ SIGNATURES = {
     "svnet_binhead_fwd_f32": (c_int, [ctypes.POINTER(BinHeadDesc), c_p]),
     "svnet_binhead_bwd_f32": (c_int, [ctypes.POINTER(BinHeadDesc), c_p]),
     "svnet_fplinear_small_bwd_f32": (c_int, [c_p, c_p, c_p, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_p]),
+    "svnet_batch_supported": (c_int, [c_i64, c_i64, c_int]),
+    "svnet_batch_assemble_f32": (c_int, [ctypes.POINTER(BatchDesc), c_p]),
 }
 
 

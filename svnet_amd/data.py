@@ -1,0 +1,209 @@
+"""Device-resident data sets and on-device batch assembly (svnet_amd/csrc/batch.hip).
+
+What the reference does per sample on the host - `translate_pointcloud` and the point shuffle of its loaders (data.py:165-170,
+192-198 ModelNet40, 284-294 ShapeNetPart, 327-337 ScanObjectNN), collate, copy to the device, rotate, permute
+(main_cls_dgcnn.py:167-179) - is here ONE launch per batch: the whole pool lives on the device (ModelNet40 train is 242 MB) and a
+batch is gathered and transformed straight into the fixed buffers a TrainStep / ForwardStep runs on.
+
+    pool = DevicePool(data, label, device="cuda:0")                # data [M,P,3] float32 = np.asarray(h5['data']), label [M] or [M,1]
+    loader = BatchLoader(pool, 32, 1024, select="first_shuffled", scale_shift=True, rotate="none", seed=1)
+    step = TrainStep(model, inputs=(loader.x,), target=loader.y).capture()
+    for epoch in range(E):
+        loader.set_epoch(epoch)
+        mean_loss = train_epoch(step, loader, optimizer)
+
+Randomness is counter-based (splitmix64 `sm`, the one of svnet_amd/synth.py; all arithmetic on uint64, wrapping), never a stateful
+generator: everything a cloud receives is a pure function of (seed, epoch, g), g = the cloud's position in the epoch order.  Batch
+size, rank count, eager or replayed launches and a resume in mid-run cannot change what a sample looks like in an epoch, and the
+host can restate a batch exactly (tests/loader_ref.py does).  The derivation:
+
+    epoch_key = sm(sm(seed) ^ epoch)
+    epoch order (shuffle=True): ascending order of the keys ((sm(order_key + i) >> 32) << 32) | i, i = 0..M-1,
+                                order_key = sm(epoch_key ^ (2^64 - 1));  shuffle=False: 0..M-1
+    cloud_key = sm(epoch_key ^ g)                                     = sm(sm(sm(seed) ^ epoch) ^ g)
+    point order: ascending order of the keys ((sm(cloud_key + p) >> 16) << 16) | p, p = 0..S-1 (unique by construction: no tie
+                 rule); S = N for "first_shuffled", S = P for "subset"; the first N of that order are taken, output slot n holds
+                 pool point p_n.  "first_ordered": p_n = n.
+    uniform u_j = (sm(cloud_key + 2^32 + j) >> 40) * 2^-24, exact in fp32, in [0, 1);  j = 0..2 scales, 3..5 shifts, 6..8 rotation
+    scale_c = fl(LO + fl(SPAN * u_c)),     LO = fp32(2/3), SPAN = fp32(3/2 - 2/3)       (data.py:166)
+    shift_c = fl(SLO + fl(SSPAN * u_3+c)), SLO = fp32(-0.2), SSPAN = fp32(0.4)          (data.py:167)
+    coordinates: v_c = fl(fl(x_c * scale_c) + shift_c)                                  (only when scale_shift is on)
+    rotation (only when rotate is "z" / "so3"), all in fp32, sinpi / cospi of the exact argument 2u:
+        "z":   s, c = sin, cos(2 pi u_6);  R = [[c, -s, 0], [s, c, 0], [0, 0, 1]]
+        "so3": a = sqrt(1 - u_6), b = sqrt(u_6); unit quaternion (w, i, j, k) = (b cos 2 pi u_8, a sin 2 pi u_7, a cos 2 pi u_7,
+               b sin 2 pi u_8) - uniform on S^3 (Shoemake), hence R uniform on SO(3); R = the matrix of train.rotate_clouds:
+               [[1-2(jj+kk), 2(ij-kw), 2(ik+jw)], [2(ij+kw), 1-2(ii+kk), 2(jk-iw)], [2(ik-jw), 2(jk+iw), 1-2(ii+jj)]]
+        out_r = fl(fl(fl(R_r0 * v_0) + fl(R_r1 * v_1)) + fl(R_r2 * v_2))                (R x, as train.rotate_clouds' bmm)
+    Every operation is a single-rounded fp32 operation, never contracted into an fma.  The kernel writes the 3 scales, 3 shifts and
+    9 rotation entries it used into `params` [B,16] (no augmentation: 1, 0, identity; those operations are then skipped, not
+    multiplied through).
+
+There is no CPU fallback: a pool that is not on a HIP device raises.
+"""
+import ctypes
+
+import numpy as np
+import torch
+
+from . import _lib, _ops, synth
+
+SELECT_MODES = {"first_shuffled": 0, "subset": 1, "first_ordered": 2}      # SVNET_BATCH_* (include/svnet_hip.h)
+ROTATE_MODES = {"none": 0, None: 0, "z": 1, "so3": 2}                      # SVNET_BATCH_ROTATE_*
+
+_U64 = np.uint64
+
+
+def _sm(x):
+    return synth._splitmix64(np.asarray(x, dtype=np.uint64))
+
+
+def _epoch_key(seed, epoch):
+    return _sm(_sm(_U64(int(seed) & 0xFFFFFFFFFFFFFFFF)) ^ _U64(int(epoch) & 0xFFFFFFFFFFFFFFFF))
+
+
+def epoch_order(seed, epoch, M):
+    """The epoch's sample order: a permutation of 0..M-1 as int64 numpy (host side, once per epoch; see the module docstring)."""
+    M = int(M)
+    if not 0 < M < (1 << 32):
+        raise ValueError("epoch_order: M = %d outside 1 .. 2^32 - 1" % M)
+    order_key = _sm(_epoch_key(seed, epoch) ^ _U64(0xFFFFFFFFFFFFFFFF))
+    i = np.arange(M, dtype=np.uint64)
+    with np.errstate(over="ignore"):
+        keys = ((_sm(order_key + i) >> _U64(32)) << _U64(32)) | i
+    return np.argsort(keys, kind="stable").astype(np.int64)
+
+
+def _as_tensor(a, dtype, name):
+    t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))
+    if t.dtype != dtype:
+        raise TypeError("DevicePool: %s must be %s, got %s" % (name, dtype, t.dtype))
+    return t
+
+
+class DevicePool:
+    """A whole data set on the device: data [M,P,3] float32 (point-major, as the HDF5 files hold it: `np.asarray(h5['data'])` is what
+    goes in), label [M] or [M,1] int64, optional seg [M,P] int64.  numpy arrays or tensors; moved to `device` once."""
+
+    def __init__(self, data, label, seg=None, device="cuda:0"):
+        data = _as_tensor(data, torch.float32, "data")
+        label = _as_tensor(label, torch.int64, "label")
+        if data.dim() != 3 or data.shape[2] != 3 or data.shape[0] < 1 or data.shape[1] < 1:
+            raise ValueError("DevicePool: data must be [M,P,3], got %s" % (tuple(data.shape),))
+        M, P = int(data.shape[0]), int(data.shape[1])
+        if tuple(label.shape) not in ((M,), (M, 1)):
+            raise ValueError("DevicePool: label must be [M] or [M,1] with M = %d, got %s" % (M, tuple(label.shape)))
+        if seg is not None:
+            seg = _as_tensor(seg, torch.int64, "seg")
+            if tuple(seg.shape) != (M, P):
+                raise ValueError("DevicePool: seg must be [M,P] = %s, got %s" % ((M, P), tuple(seg.shape)))
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError("svnet_amd: DevicePool needs a HIP (cuda) device, got %s — the product path has no CPU fallback" % device)
+        self.M, self.P, self.device = M, P, device
+        self.data = data.to(device).contiguous()
+        self.label = label.reshape(M).to(device).contiguous()
+        self.seg = None if seg is None else seg.to(device).contiguous()
+
+    @staticmethod
+    def synthetic_arrays(seed, M, P, num_class, num_part=None):
+        """(data, label, seg or None) of a synthetic pool as numpy: the clouds of synth.cloud_batch, point-major."""
+        data = np.ascontiguousarray(synth.cloud_batch(seed, 0, 0, M, P).transpose(0, 2, 1))
+        label = synth.class_labels(seed, 0, 0, M, num_class)
+        seg = None if num_part is None else synth.seg_labels(seed, 0, 0, M, P, num_part)
+        return data, label, seg
+
+    @classmethod
+    def synthetic(cls, seed, M, P, num_class, num_part=None, device="cuda:0"):
+        """A pool of M synthetic clouds of P points (tests and tools): labels < num_class, per-point labels < num_part if given."""
+        return cls(*cls.synthetic_arrays(seed, M, P, num_class, num_part), device=device)
+
+
+def steps_per_epoch(M, batch_size, world=1, drop_last=True):
+    """Steps every rank takes per epoch: rank r fills its batch of step s from positions (s * world + r) * B + b of the epoch order."""
+    per_step = int(batch_size) * int(world)
+    return int(M) // per_step if drop_last else -(-int(M) // per_step)
+
+
+def batch_span(M, batch_size, step, rank=0, world=1):
+    """(first, count) of `rank`'s batch at `step`: positions first .. first + count - 1 of the epoch order (count 0: nothing left)."""
+    first = (int(step) * int(world) + int(rank)) * int(batch_size)
+    return first, max(0, min(int(batch_size), int(M) - first))
+
+
+class BatchLoader:
+    """Fills fixed device buffers with one batch per `load(step)`, one launch each (see the module docstring).
+
+    .x [B,3,N] float32 (the models' input), .y [B] int64, .seg [B,N] int64 (pools with seg), .onehot [B,num_cat] float32 (when
+    num_cat is given: the one-hot of the label, the part-seg models' second input), .params [B,16] float32 (the augmentation used).
+    select: "first_shuffled" (ModelNet40 / ShapeNetPart training), "subset" (ScanObjectNN), "first_ordered" (every test partition).
+    """
+
+    def __init__(self, pool, batch_size, num_points, *, select, scale_shift, rotate, shuffle=True, drop_last=True, seed,
+                 rank=0, world=1, num_cat=None):
+        if not isinstance(pool, DevicePool):
+            raise TypeError("BatchLoader: pool must be a DevicePool")
+        _ops._hip(pool.data, pool.label, pool.seg)
+        if select not in SELECT_MODES:
+            raise ValueError("BatchLoader: select must be one of %r" % sorted(SELECT_MODES))
+        if rotate not in ROTATE_MODES:
+            raise ValueError("BatchLoader: rotate must be 'none', 'z' or 'so3'")
+        B, N = int(batch_size), int(num_points)
+        if B < 1 or not 0 <= int(rank) < int(world):
+            raise ValueError("BatchLoader: batch_size %d, rank %d of %d" % (B, rank, world))
+        if N < 1 or N > pool.P:
+            raise ValueError("BatchLoader: num_points %d outside 1 .. P = %d" % (N, pool.P))
+        if not 0 <= int(seed) < (1 << 63):
+            raise ValueError("BatchLoader: seed must be in 0 .. 2^63 - 1")
+        self.select_mode = SELECT_MODES[select]
+        if not _lib.lib().svnet_batch_supported(pool.P, N, self.select_mode):
+            raise _lib.SvnetHipError("BatchLoader: P = %d, N = %d, select = %r is not supported (the point keys of a cloud must fit "
+                                     "64 KiB of LDS: at most 8192)" % (pool.P, N, select))
+        self.pool, self.B, self.N = pool, B, N
+        self.scale_shift, self.rotate = int(bool(scale_shift)), ROTATE_MODES[rotate]
+        self.shuffle, self.drop_last, self.seed = bool(shuffle), bool(drop_last), int(seed)
+        self.rank, self.world = int(rank), int(world)
+        dev = pool.device
+        self.x = torch.zeros(B, 3, N, dtype=torch.float32, device=dev)
+        self.y = torch.zeros(B, dtype=torch.int64, device=dev)
+        self.seg = None if pool.seg is None else torch.zeros(B, N, dtype=torch.int64, device=dev)
+        self.num_cat = None if num_cat is None else int(num_cat)
+        self.onehot = None if num_cat is None else torch.zeros(B, self.num_cat, dtype=torch.float32, device=dev)
+        self.params = torch.zeros(B, 16, dtype=torch.float32, device=dev)
+        self.order = torch.empty(pool.M, dtype=torch.int64, device=dev)
+        self.epoch = None
+        self._desc = _lib.BatchDesc()
+        d = self._desc
+        d.data, d.label, d.seg, d.order = _ops._p(pool.data), _ops._p(pool.label), _ops._p(pool.seg), _ops._p(self.order)
+        d.M, d.P, d.L, d.B, d.N = pool.M, pool.P, pool.M, B, N
+        d.seed = self.seed
+        d.select_mode, d.scale_shift, d.rotate = self.select_mode, self.scale_shift, self.rotate
+        d.num_cat = self.num_cat or 0
+        d.x, d.y, d.seg_out, d.onehot, d.params = _ops._p(self.x), _ops._p(self.y), _ops._p(self.seg), _ops._p(self.onehot), _ops._p(self.params)
+        self.set_epoch(0)
+
+    def set_epoch(self, epoch):
+        """Fix the epoch: its sample order (one host argsort of M keys, one small copy to the device) and its augmentation stream."""
+        if not 0 <= int(epoch) < (1 << 63):
+            raise ValueError("BatchLoader.set_epoch: epoch must be in 0 .. 2^63 - 1")
+        self.epoch = int(epoch)
+        order = epoch_order(self.seed, self.epoch, self.pool.M) if self.shuffle else np.arange(self.pool.M, dtype=np.int64)
+        self.order.copy_(torch.from_numpy(order))       # (stream-ordered on the current stream: behind the previous epoch's launches)
+        self._desc.epoch = self.epoch
+
+    def __len__(self):
+        return steps_per_epoch(self.pool.M, self.B, self.world, self.drop_last)
+
+    def span(self, step):
+        return batch_span(self.pool.M, self.B, step, self.rank, self.world)
+
+    def load(self, step):
+        """Enqueue the assembly of this rank's batch of `step` on the current stream; returns the number of valid clouds (slots past
+        it repeat slot 0; 0 = this rank has no cloud left at this step and nothing was launched)."""
+        if not 0 <= int(step) < len(self):
+            raise IndexError("BatchLoader.load: step %d outside 0 .. %d" % (step, len(self) - 1))
+        first, count = self.span(step)
+        if count == 0:
+            return 0
+        self._desc.first, self._desc.count = first, count
+        _lib.call("svnet_batch_assemble_f32", ctypes.byref(self._desc), _ops._stream())
+        return count

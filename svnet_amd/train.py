@@ -7,6 +7,8 @@ CosineAnnealingLR.step (:128-135,187).  Here:
   cal_loss          utils.py:33-50 as one HIP kernel (label-smoothed cross entropy)
   TrainStep         fwd + cal_loss + bwd (+ the data-parallel gradient all-reduce) on fixed device buffers, launched eagerly or
                     replayed as ONE captured HIP graph (the step is ~200 short kernels: launch-bound when launched one by one)
+  train_epoch       one epoch over a device-resident pool (svnet_amd/data.py: one batch-assembly launch in front of every step);
+  eval_epoch        the evaluation pass over such a pool (main_cls_dgcnn.py:218-251): logits of the valid clouds
   rotate_clouds     the per-batch augmentation (main_cls_dgcnn.py:168-178) without pytorch3d
   FlatAdam/FlatSGD  torch.optim.Adam / SGD semantics (main_cls_dgcnn.py:128-133) as ONE kernel over the flat parameter /
                     gradient buffers (svnet_amd/csrc/optim.hip) instead of one small kernel chain per parameter tensor
@@ -160,6 +162,35 @@ class ForwardStep:
         else:
             self.out = self.forward()
         return self.out
+
+
+# ----------------------------------------------------------------------------- epochs over a device-resident pool (svnet_amd/data.py)
+
+def train_epoch(step, loader, optimizer):
+    """One epoch of `step` (a TrainStep built on `loader`'s buffers: inputs=(loader.x, ...), target=loader.y): per step the batch
+    assembly launch, the (replayed) step, the optimizer.  The assembly stays outside a captured graph - its step index is an ordinary
+    kernel argument - and stream order puts it in front of the replay.  Returns the mean loss as a float: a running sum on the device,
+    read by the host once at the end."""
+    total = None
+    steps = len(loader)
+    for i in range(steps):
+        loader.load(i)
+        loss = step.run()
+        total = loss.detach().clone() if total is None else total.add_(loss.detach())     # (a captured step's loss lives in a fixed buffer)
+        optimizer.step()
+    return float(total) / steps if steps else float("nan")
+
+
+def eval_epoch(fwd_step, loader):
+    """One pass of a ForwardStep built on `loader`'s buffers over the loader's epoch (an evaluation loader: drop_last=False, no
+    shuffle, "first_ordered").  Returns (logits, predictions) of the VALID clouds, concatenated in loader order, on the device."""
+    outs = []
+    for i in range(len(loader)):
+        count = loader.load(i)
+        if count:
+            outs.append(fwd_step.run()[:count].clone())
+    logits = torch.cat(outs, dim=0)
+    return logits, logits.argmax(dim=1)
 
 
 # ----------------------------------------------------------------------------- augmentation
