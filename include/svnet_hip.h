@@ -47,7 +47,7 @@ int svnet_slices_sum_f64(double* buf, int64_t L, void* stream);
  * changes its required length (200: sliced accumulators, SVNET_SLICED_LEN; 400: this header; 401: the totals of a sliced accumulator are
  * written by its consumer, svnet_slices_sum_*; 402: GX of svnet_v2s_bwd_*, gw of svnet_xyzblock_bwd_f32 and col_sum of svnet_gemm_f32 are sliced accumulators; 403: svnet_binweight_grad_f32 takes sliced inputs).  svnet_version() returns the value the
  * library was BUILT with: a caller compiled against another header must refuse to run (svnet_amd/_lib.py does).                   */
-#define SVNET_ABI_VERSION 418
+#define SVNET_ABI_VERSION 419
 int svnet_version(void);
 const char* svnet_last_error(void);
 
@@ -703,6 +703,38 @@ typedef struct svnet_batch_desc {
 /* 1 when svnet_batch_assemble_f32 takes the shape, else 0: a pure host function. */
 int svnet_batch_supported(int64_t P, int64_t N, int select_mode);
 int svnet_batch_assemble_f32(const svnet_batch_desc* d, void* stream);
+
+/* ------------------------------------------------------------------ epoch metrics (main_cls_dgcnn.py:187-251, main_partseg_dgcnn.py:185-279,
+ * utils.py:68-91 calculate_shape_IoU; the accuracy scores of sklearn.metrics are functions of the confusion matrix)
+ * Both forms ACCUMULATE into a caller-owned device state and hand nothing to the host:
+ *     state, as int64 words: conf[C*C] (row = true class, column = predicted class) | rows | invalid | loss_sum (a float64)
+ * svnet_metrics_state_bytes gives its size; svnet_metrics_reset zero-fills it and marks all `capacity` shape slots empty (one launch).
+ * Per valid row: the prediction is the LOWEST index among the row's maxima, a NaN counting as the maximum (torch.max over a dim on the
+ * CPU), and loss_sum grows by the row's cal_loss term in the fp32 arithmetic of svnet_smooth_ce_f32.  A row whose target lies outside
+ * 0 .. C-1 (the batch assembly's -1 poison included) indexes nothing: it is counted in `invalid` and otherwise skipped.  Integer counts
+ * are integer atomics; loss_sum is added in a fixed order by a finishing launch of the same call (no float atomics): two identical
+ * passes give identical bits.  `count`: the valid leading rows / clouds (0: nothing is launched).  `workspace`: scratch of
+ * svnet_metrics_workspace_bytes for B rows (N = 0, the cls form) or B clouds of N points (the seg form); contents need not survive.
+ *
+ * cls: logits [R,C], target [R].
+ * seg: logits [B,num_part,N] (the part-segmentation models' layout; rows = points, C = num_part), seg [B,N], label [B];
+ *      part_start / part_num [num_cat] (device): the parts of category c are part_start[c] .. part_start[c] + part_num[c] - 1.
+ *      Per valid cloud b, over ALL its points with the prediction taken over all num_part channels: for each part p of the cloud's
+ *      category I = #(pred == p and seg == p), U = #(pred == p or seg == p), part IoU = 1 when U == 0, else I / U in float64;
+ *      shape_iou[first + b] = (sum over p ascending) / part_num, shape_cat[first + b] = label[b].  A label outside 0 .. num_cat-1 (or
+ *      a part range outside 0 .. num_part-1): shape_iou = NaN, shape_cat = SVNET_METRICS_CAT_INVALID.  first + count > capacity is
+ *      refused with SVNET_E_UNSUPPORTED, as are num_part > 4096 and B > 65535.                                                      */
+#define SVNET_METRICS_CAT_EMPTY (-1)   /* shape_cat of a slot no call has filled since the reset */
+#define SVNET_METRICS_CAT_INVALID (-2) /* shape_cat of a cloud whose label was out of range */
+size_t svnet_metrics_state_bytes(int64_t C);
+size_t svnet_metrics_workspace_bytes(int64_t B, int64_t C, int64_t N);
+int svnet_metrics_reset(void* state, int64_t C, double* shape_iou, int64_t* shape_cat, int64_t capacity, void* stream);
+int svnet_metrics_cls_f32(const float* logits, const int64_t* target, int64_t R, int64_t C, int64_t count, float eps, void* state,
+                          void* workspace, size_t workspace_bytes, void* stream);
+int svnet_metrics_seg_f32(const float* logits, const int64_t* seg, const int64_t* label, int64_t B, int64_t num_part, int64_t N,
+                          const int64_t* part_start, const int64_t* part_num, int64_t num_cat, int64_t count, int64_t first, float eps,
+                          void* state, double* shape_iou, int64_t* shape_cat, int64_t capacity, void* workspace, size_t workspace_bytes,
+                          void* stream);
 
 /* ------------------------------------------------------------------ diagnostics (no reference counterpart)
  * One thread writes the constant-rate device clock (s_memrealtime: 100 MHz ticks) to *slot when the stream reaches it: the start

@@ -9,6 +9,7 @@ CosineAnnealingLR.step (:128-135,187).  Here:
                     replayed as ONE captured HIP graph (the step is ~200 short kernels: launch-bound when launched one by one)
   train_epoch       one epoch over a device-resident pool (svnet_amd/data.py: one batch-assembly launch in front of every step);
   eval_epoch        the evaluation pass over such a pool (main_cls_dgcnn.py:218-251): logits of the valid clouds
+  evaluate          the same pass, reduced on the device to the epoch's metrics (svnet_amd/metrics.py): no logits are kept
   rotate_clouds     the per-batch augmentation (main_cls_dgcnn.py:168-178) without pytorch3d
   FlatAdam/FlatSGD  torch.optim.Adam / SGD semantics (main_cls_dgcnn.py:128-133) as ONE kernel over the flat parameter /
                     gradient buffers (svnet_amd/csrc/optim.hip) instead of one small kernel chain per parameter tensor
@@ -41,10 +42,13 @@ class TrainStep:
         loss = step.run()                                      # replay (or eager launch) + gradient all-reduce
 
     The loss tensor returned by run() lives in a fixed buffer when the step is captured (read it before the next run()).
+    keep_output=True: `self.out` holds the detached model output of the last run() (captured: a fixed buffer, like the loss) - what
+    train_epoch(..., metrics=) reads.
     """
 
-    def __init__(self, model, inputs, target, loss_fn=cal_loss):
+    def __init__(self, model, inputs, target, loss_fn=cal_loss, keep_output=False):
         self.model, self.inputs, self.target, self.loss_fn = model, tuple(inputs), target, loss_fn
+        self.keep_output, self.out = bool(keep_output), None
         self.bucket = GradBucket(model.parameters())
         self.graph = None
         self.loss = None
@@ -72,7 +76,11 @@ class TrainStep:
         _ops.begin_step(self.bucket.flat.device, planes_external, self._arena)   # one zero fill for the step's accumulators; stale packed weights rebuilt on the side stream
         try:
             self.bucket.begin()
-            loss = self.loss_fn(self.model(*self.inputs), self.target)
+            out = self.model(*self.inputs)
+            if self.keep_output:
+                self.out = out.detach()
+            loss = self.loss_fn(out, self.target)
+            del out
             # nothing reads a parameter gradient before pack() (checked: _deferral_is_safe): see _ops._Deferred
             _ops.DEFERRED.active = bool(config.DEFER_WGRAD) and self._deferral_is_safe()
             if loss.dim() == 0 and loss.is_cuda and loss.dtype == torch.float32:
@@ -166,17 +174,29 @@ class ForwardStep:
 
 # ----------------------------------------------------------------------------- epochs over a device-resident pool (svnet_amd/data.py)
 
-def train_epoch(step, loader, optimizer):
+def _update_metrics(metrics, out, loader, step_index, count):
+    """One metrics launch for the batch `loader` holds: per-point labels where the pool has them (part segmentation), else the class."""
+    first, _ = loader.span(step_index)
+    metrics.update(out, loader.y if loader.seg is None else loader.seg, count, label=loader.y, first=first)
+
+
+def train_epoch(step, loader, optimizer, metrics=None):
     """One epoch of `step` (a TrainStep built on `loader`'s buffers: inputs=(loader.x, ...), target=loader.y): per step the batch
     assembly launch, the (replayed) step, the optimizer.  The assembly stays outside a captured graph - its step index is an ordinary
     kernel argument - and stream order puts it in front of the replay.  Returns the mean loss as a float: a running sum on the device,
-    read by the host once at the end."""
+    read by the host once at the end.
+    metrics: an EpochMetrics (svnet_amd/metrics.py) that receives every step's output (`step` built with keep_output=True) - one more
+    launch behind the replay, outside the graph like the assembly; nothing is read by the host."""
     total = None
     steps = len(loader)
     for i in range(steps):
-        loader.load(i)
+        count = loader.load(i)
         loss = step.run()
         total = loss.detach().clone() if total is None else total.add_(loss.detach())     # (a captured step's loss lives in a fixed buffer)
+        if metrics is not None:
+            if step.out is None:
+                raise RuntimeError("train_epoch(metrics=...): build the TrainStep with keep_output=True")
+            _update_metrics(metrics, step.out, loader, i, count)
         optimizer.step()
     return float(total) / steps if steps else float("nan")
 
@@ -191,6 +211,17 @@ def eval_epoch(fwd_step, loader):
             outs.append(fwd_step.run()[:count].clone())
     logits = torch.cat(outs, dim=0)
     return logits, logits.argmax(dim=1)
+
+
+def evaluate(fwd_step, loader, metrics):
+    """eval_epoch's pass with every batch reduced on the device: resets `metrics`, adds each batch's valid clouds, keeps no logits and
+    returns metrics.result() (the pass's one host read)."""
+    metrics.reset()
+    for i in range(len(loader)):
+        count = loader.load(i)
+        if count:
+            _update_metrics(metrics, fwd_step.run(), loader, i, count)
+    return metrics.result()
 
 
 # ----------------------------------------------------------------------------- augmentation
