@@ -47,7 +47,7 @@ int svnet_slices_sum_f64(double* buf, int64_t L, void* stream);
  * changes its required length (200: sliced accumulators, SVNET_SLICED_LEN; 400: this header; 401: the totals of a sliced accumulator are
  * written by its consumer, svnet_slices_sum_*; 402: GX of svnet_v2s_bwd_*, gw of svnet_xyzblock_bwd_f32 and col_sum of svnet_gemm_f32 are sliced accumulators; 403: svnet_binweight_grad_f32 takes sliced inputs).  svnet_version() returns the value the
  * library was BUILT with: a caller compiled against another header must refuse to run (svnet_amd/_lib.py does).                   */
-#define SVNET_ABI_VERSION 419
+#define SVNET_ABI_VERSION 420
 int svnet_version(void);
 const char* svnet_last_error(void);
 
@@ -703,6 +703,25 @@ typedef struct svnet_batch_desc {
 /* 1 when svnet_batch_assemble_f32 takes the shape, else 0: a pure host function. */
 int svnet_batch_supported(int64_t P, int64_t N, int select_mode);
 int svnet_batch_assemble_f32(const svnet_batch_desc* d, void* stream);
+
+/* ------------------------------------------------------------------ farthest point sampling and the resampled pool
+ * (models/utils/pointnet_util.py:63-84 farthest_point_sample; data.py:203-256 ModelNet40_v2(uniform=True) with data.py:15-20 pc_normalize)
+ * svnet_fps_f32: xyz [M,P,3], start [M] (the reference draws it with torch.randint; here it is an input), idx [M,npoint]:
+ *     mind[p] = fp32(1e10), f = start[m];  npoint times: idx[i] = f, d_c = fl(x[p,c] - x[f,c]),
+ *     dist = fl(fl(fl(d_0 d_0) + fl(d_1 d_1)) + fl(d_2 d_2)), mind[p] = dist < mind[p] ? dist : mind[p], f = the SMALLEST p among the
+ *     maxima of mind.  Single-rounded fp32, never an fma: given the start, bit-identical to the reference's CPU result.  Coordinates
+ *     must be finite (NaN / Inf: undefined order, never an out-of-range index).  A start outside 0 .. P-1 is clamped into the cloud.
+ *     One workgroup per cloud; 1 <= npoint <= P <= 16384 (SVNET_E_UNSUPPORTED past it).  svnet_fps_tier: which kernel form a P takes
+ *     (0 .. 4: P <= 64, 1024, 4096, 10240, 16384), -1 = unsupported; svnet_fps_supported: 1 / 0.  Both are pure host functions.
+ * svnet_pool_gather_f32: out[m,n,:] = data[m, idx[m,n], :] (data [M,P,3], idx [M,N]) and, when seg_out is given, seg_out[m,n] =
+ *     seg[m, idx[m,n]] (seg [M,P]); one launch, one workgroup per cloud.  normalize != 0 applies pc_normalize to every selection:
+ *     c = the float64 mean of its N points rounded once to fp32 (summed in a fixed order: bit-reproducible), d = fl(p - c),
+ *     m = max_n sqrt(fl(fl(d_0 d_0 + d_1 d_1) + d_2 d_2)), out = fl(d / m).  An index outside 0 .. P-1 reads nothing: NaN row, seg -1. */
+int svnet_fps_supported(int64_t P, int64_t npoint);
+int svnet_fps_tier(int64_t P);
+int svnet_fps_f32(const float* xyz, int64_t M, int64_t P, int64_t npoint, const int64_t* start, int64_t* idx, void* stream);
+int svnet_pool_gather_f32(const float* data, const int64_t* seg, const int64_t* idx, int64_t M, int64_t P, int64_t N, int normalize,
+                          float* out, int64_t* seg_out, void* stream);
 
 /* ------------------------------------------------------------------ epoch metrics (main_cls_dgcnn.py:187-251, main_partseg_dgcnn.py:185-279,
  * utils.py:68-91 calculate_shape_IoU; the accuracy scores of sklearn.metrics are functions of the confusion matrix)

@@ -38,6 +38,23 @@ host can restate a batch exactly (tests/loader_ref.py does).  The derivation:
     9 rotation entries it used into `params` [B,16] (no augmentation: 1, 0, identity; those operations are then skipped, not
     multiplied through).
 
+Uniformly resampled pools (the reference's ModelNet40_v2(uniform=True), data.py:203-256: ~10 000-point clouds reduced to num_points
+by `farthest_point_sample`, models/utils/pointnet_util.py:63-84, then `pc_normalize`, data.py:15-20) are made once, on the device
+(svnet_amd/csrc/fps.hip), and the result is an ordinary pool:
+
+    big = DevicePool(data10k, label, device="cuda:0")                   # [M,10000,3]: past the loader's 8192-point limit
+    pool = big.resample_fps(1024, seed=0, normalize=True)               # [M,1024,3]; pool.fps_index [M,1024] says which points
+
+    for one cloud xyz [P,3], a start index s and npoint <= P (all fp32, each operation rounded once, never an fma):
+        mind[p] = fp32(1e10);  f = s
+        for i in 0 .. npoint-1:  idx[i] = f;  d_c = fl(xyz[p,c] - xyz[f,c]);  dist = fl(fl(fl(d_0 d_0) + fl(d_1 d_1)) + fl(d_2 d_2))
+                                 mind[p] = dist < mind[p] ? dist : mind[p];  f = the smallest p with mind[p] == max_p mind[p]
+    which is the reference's loop with its `torch.randint` start made an input (default: fps_start, counter-based like everything
+    above): given the start, the index list equals the reference's CPU result bit for bit.  Coordinates must be finite.
+    normalize: c = the float64 mean of the N selected points (fixed summation order) rounded once to fp32, d = fl(p - c),
+        m = max_n sqrt(fl(fl(d_0 d_0 + d_1 d_1) + d_2 d_2)), out = fl(d / m): single-rounded fp32, the same bits on every run (numpy's
+        float32 mean rounds differently: close to the reference's output, not bit-identical to it).
+
 There is no CPU fallback: a pool that is not on a HIP device raises.
 """
 import ctypes
@@ -73,6 +90,46 @@ def epoch_order(seed, epoch, M):
     return np.argsort(keys, kind="stable").astype(np.int64)
 
 
+def fps_start(seed, M, P):
+    """The default start index of cloud m = 0..M-1 for farthest point sampling: sm(sm(seed) ^ m) mod P as int64 numpy; a pure function
+    of (seed, m) (the reference draws it with torch.randint, pointnet_util.py:75)."""
+    M, P = int(M), int(P)
+    if M < 1 or P < 1:
+        raise ValueError("fps_start: M = %d, P = %d must be positive" % (M, P))
+    m = np.arange(M, dtype=np.uint64)
+    return (_sm(_sm(_U64(int(seed) & 0xFFFFFFFFFFFFFFFF)) ^ m) % _U64(P)).astype(np.int64)
+
+
+def farthest_point_sample(xyz, npoint, start):
+    """Farthest point sampling (models/utils/pointnet_util.py:63 farthest_point_sample, same return convention): xyz [B,P,3] float32
+    on a HIP device, start [B] int64 (the first centroid of every cloud, which the reference draws at random) -> [B,npoint] int64.
+    Given the start the result equals the reference's CPU result bit for bit (module docstring).  A preparation-time call: the start
+    range is checked with one device reduction and one synchronisation before the launch."""
+    if not isinstance(xyz, torch.Tensor) or not isinstance(start, torch.Tensor):
+        raise TypeError("farthest_point_sample: xyz and start must be tensors")
+    _ops._hip(xyz, start)
+    if xyz.dtype != torch.float32 or start.dtype != torch.int64:
+        raise TypeError("farthest_point_sample: xyz must be float32 and start int64, got %s and %s" % (xyz.dtype, start.dtype))
+    if xyz.dim() != 3 or xyz.shape[2] != 3 or xyz.shape[0] < 1:
+        raise ValueError("farthest_point_sample: xyz must be [B,P,3], got %s" % (tuple(xyz.shape),))
+    B, P, npoint = int(xyz.shape[0]), int(xyz.shape[1]), int(npoint)
+    if tuple(start.shape) != (B,):
+        raise ValueError("farthest_point_sample: start must be [B] = [%d], got %s" % (B, tuple(start.shape)))
+    if not xyz.is_contiguous() or not start.is_contiguous():
+        raise ValueError("farthest_point_sample: xyz and start must be contiguous")
+    if start.device != xyz.device:
+        raise ValueError("farthest_point_sample: xyz on %s, start on %s" % (xyz.device, start.device))
+    if not _lib.lib().svnet_fps_supported(P, npoint):
+        raise _lib.SvnetHipError("farthest_point_sample: P = %d, npoint = %d is not supported (1 <= npoint <= P <= 16384)" % (P, npoint))
+    lo, hi = (int(v) for v in torch.aminmax(start))
+    if lo < 0 or hi >= P:
+        raise ValueError("farthest_point_sample: start outside 0 .. P-1 = %d (min %d, max %d)" % (P - 1, lo, hi))
+    idx = torch.empty(B, npoint, dtype=torch.int64, device=xyz.device)
+    with torch.cuda.device(xyz.device):
+        _lib.call("svnet_fps_f32", _ops._p(xyz), B, P, npoint, _ops._p(start), _ops._p(idx), _ops._stream())
+    return idx
+
+
 def _as_tensor(a, dtype, name):
     t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))
     if t.dtype != dtype:
@@ -103,6 +160,27 @@ class DevicePool:
         self.data = data.to(device).contiguous()
         self.label = label.reshape(M).to(device).contiguous()
         self.seg = None if seg is None else seg.to(device).contiguous()
+
+    def resample_fps(self, num_points, *, start=None, seed=0, normalize=False):
+        """A new pool [M,num_points,3] on the same device: every cloud reduced to `num_points` by farthest point sampling, optionally
+        followed by pc_normalize (module docstring) - how a pool of more than 8192 points per cloud gets under the BatchLoader's limit.
+        `start` [M] int64 (numpy or tensor) is the first centroid of every cloud; None: fps_start(seed, M, P).  `label` is shared,
+        `seg` is gathered, and `.fps_index` [M,num_points] keeps which point of the source every point is."""
+        N = int(num_points)
+        if start is None:
+            start = fps_start(seed, self.M, self.P)
+        start = _as_tensor(start, torch.int64, "start").to(self.device).contiguous()
+        idx = farthest_point_sample(self.data, N, start)
+        new = object.__new__(DevicePool)
+        new.M, new.P, new.device = self.M, N, self.device
+        new.data = torch.empty(self.M, N, 3, dtype=torch.float32, device=self.device)
+        new.label = self.label
+        new.seg = None if self.seg is None else torch.empty(self.M, N, dtype=torch.int64, device=self.device)
+        new.fps_index = idx
+        with torch.cuda.device(self.device):
+            _lib.call("svnet_pool_gather_f32", _ops._p(self.data), _ops._p(self.seg), _ops._p(idx), self.M, self.P, N,
+                      int(bool(normalize)), _ops._p(new.data), _ops._p(new.seg), _ops._stream())
+        return new
 
     @staticmethod
     def synthetic_arrays(seed, M, P, num_class, num_part=None):
