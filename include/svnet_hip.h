@@ -654,6 +654,34 @@ int svnet_fplinear_small_bwd_f32(const float* g, const float* x, const float* W,
 int svnet_smooth_ce_f32(const float* logits, const int64_t* target, int64_t R, int64_t C, float eps, float* loss,
                         float* dlogits, float* workspace, int64_t workspace_floats, void* stream);
 
+/* ------------------------------------------------------------------ knowledge distillation fused with cal_loss (csrc/kdloss.hip)
+ * The reference publishes distilled binary models (README, scripts.sh: *_binary_kd_*) without the loss's source; this is Hinton et al.'s:
+ *     ce_r = -(soft_r . log_softmax(s_r))   (utils.py:33-50, soft = 1 - eps at the target, eps / (C - 1) elsewhere)
+ *     kl_r = sum_c p_rc (logp_rc - logq_rc),  logp = log_softmax(t_r / T), logq = log_softmax(s_r / T), p = exp(logp)
+ *     L = (1 - alpha) mean_r ce_r + alpha T^2 mean_r kl_r
+ *     dlogits = dL/ds = [(1 - alpha)(softmax(s_r) - soft_r) + alpha T (exp(logq_r) - p_r)] / rows     (may be NULL; the teacher gets none)
+ * student / teacher / dlogits share ONE layout:
+ *     SVNET_KD_ROWS           [R,C] contiguous: pass B = R, N = 1; target [R]
+ *     SVNET_KD_CHANNEL_MAJOR  [B,C,N] contiguous (the part-segmentation models' output: rows = points, classes at stride N); target
+ *                             [B,N].  Read and written where it lies, consecutive lanes along N: no transposed copy of anything.
+ * result: 3 floats {L, CE, KL}, CE and KL the unweighted means.  T > 0 and 0 <= alpha <= 1 (else SVNET_E_ARG).  Targets are compared
+ * with the class index, never used as one.  logp / logq are formed as (x - max) / T - log(sum exp): an underflowed p contributes 0.
+ * workspace: >= SVNET_KD_WORKSPACE_FLOATS floats (one (ce, kl) pair per workgroup, added in a fixed order by a finishing launch of the
+ * same call: no float atomics, results and gradient are bit-reproducible).
+ * svnet_kd_supported / svnet_kd_tier are pure host functions over the same (layout, B, C, N): supported = 2 <= C <= 65536, 1 <= rows
+ * (R, or B * N) <= 2^31 - 1, N = 1 in the rows layout; anything else makes the call return SVNET_E_UNSUPPORTED.  tier: -1 = unsupported,
+ * else bit 0 = the classes do not fit one pass (rows layout: C > 64, a lane walks several classes; channel-major: C > 64, the logits
+ * are re-read from memory instead of kept in registers), bit 1 = more rows than one grid (rows layout: > 4096 rows, channel-major:
+ * > 262144 points) - the workgroups stride.  At alpha = 0 the rows layout's dlogits are svnet_smooth_ce_f32's, bit for bit.          */
+#define SVNET_KD_ROWS 0
+#define SVNET_KD_CHANNEL_MAJOR 1
+#define SVNET_KD_WORKSPACE_FLOATS 8192
+int svnet_kd_supported(int layout, int64_t B, int64_t C, int64_t N);
+int svnet_kd_tier(int layout, int64_t B, int64_t C, int64_t N);
+int svnet_kd_loss_f32(int layout, const float* student, const float* teacher, const int64_t* target, int64_t B, int64_t C, int64_t N,
+                      float eps, float alpha, float T, float* result, float* dlogits, float* workspace, int64_t workspace_floats,
+                      void* stream);
+
 /* ------------------------------------------------------------------ optimizer steps on flat buffers (main_cls_dgcnn.py:128-133)
  * p, g, m, v, buf: n floats each (all parameters / gradients of the model, flattened in model.parameters() order).
  * Adam = torch.optim.Adam(lr, betas, eps, weight_decay) at 1-based `step` (bias correction); SGD = torch.optim.SGD(lr,

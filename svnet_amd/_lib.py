@@ -259,6 +259,9 @@ SIGNATURES = {
     "svnet_adam_step_dev_f32": (c_int, [c_p, c_p, c_p, c_p, c_i64, c_p, c_p]),
     "svnet_sgd_step_dev_f32": (c_int, [c_p, c_p, c_p, c_i64, c_p, c_p]),
     "svnet_smooth_ce_f32": (c_int, [c_p, c_p, c_i64, c_i64, c_f, c_p, c_p, c_p, c_i64, c_p]),
+    "svnet_kd_supported": (c_int, [c_int, c_i64, c_i64, c_i64]),
+    "svnet_kd_tier": (c_int, [c_int, c_i64, c_i64, c_i64]),
+    "svnet_kd_loss_f32": (c_int, [c_int, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_f, c_f, c_f, c_p, c_p, c_p, c_i64, c_p]),
     "svnet_binhead_pack_f32": (c_int, [c_p, c_p, c_i64, c_i64, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
     "svnet_binhead_fwd_f32": (c_int, [ctypes.POINTER(BinHeadDesc), c_p]),
     "svnet_binhead_bwd_f32": (c_int, [ctypes.POINTER(BinHeadDesc), c_p]),
@@ -275,6 +278,10 @@ SIGNATURES = {
     "svnet_metrics_cls_f32": (c_int, [c_p, c_p, c_i64, c_i64, c_i64, c_f, c_p, c_p, c_sz, c_p]),
     "svnet_metrics_seg_f32": (c_int, [c_p, c_p, c_p, c_i64, c_i64, c_i64, c_p, c_p, c_i64, c_i64, c_i64, c_f, c_p, c_p, c_p, c_i64, c_p, c_sz, c_p]),
 }
+
+
+KD_ROWS, KD_CHANNEL_MAJOR = 0, 1     # SVNET_KD_ROWS / SVNET_KD_CHANNEL_MAJOR
+KD_WORKSPACE_FLOATS = 8192           # SVNET_KD_WORKSPACE_FLOATS
 
 
 class SvnetHipError(RuntimeError):

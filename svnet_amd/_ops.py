@@ -1795,6 +1795,43 @@ class SmoothCE(torch.autograd.Function):
         return dlog * g, None, None
 
 
+class KDLoss(torch.autograd.Function):
+    """Knowledge distillation fused with cal_loss (include/svnet_hip.h svnet_kd_loss_f32, csrc/kdloss.hip):
+    L = (1 - alpha) * smoothed CE(student, target) + alpha * T^2 * KL(softmax(teacher / T) || softmax(student / T)), means over rows.
+    layout _lib.KD_ROWS: student / teacher [R,C], target [R]; _lib.KD_CHANNEL_MAJOR: [B,C,N] (rows = points), target [B,N] - read and
+    written where it lies.  Returns (L, parts): parts = the detached [3] tensor {L, CE, KL} (CE, KL unweighted, for logging).  The
+    gradient is computed by the forward launch and saved; teacher, target and the scalars get none."""
+
+    @staticmethod
+    def forward(ctx, student, teacher, target, eps, alpha, T, layout):
+        _hip(student, teacher, target)
+        st, te = _f32c(student), _f32c(teacher.detach())
+        if layout == _lib.KD_ROWS:
+            (B, C), N = st.shape, 1
+        else:
+            B, C, N = st.shape
+        if not _lib.lib().svnet_kd_supported(layout, B, C, N):
+            raise _lib.SvnetHipError("KDLoss: layout %d, logits %s are not supported (2 <= C <= 65536, at most 2^31 - 1 rows)" % (layout, tuple(st.shape)))
+        tg = target.contiguous().view(-1)
+        parts = torch.empty((3,), dtype=torch.float32, device=st.device)
+        dlog = torch.empty_like(st)
+        ws = torch.empty((_lib.KD_WORKSPACE_FLOATS,), dtype=torch.float32, device=st.device)
+        call("svnet_kd_loss_f32", layout, _p(st), _p(te), _p(tg), B, C, N, eps, alpha, T, _p(parts), _p(dlog), _p(ws), _lib.KD_WORKSPACE_FLOATS, _stream())
+        ctx.save_for_backward(dlog)
+        ctx.mark_non_differentiable(parts)
+        ctx.set_materialize_grads(False)
+        return parts[0], parts
+
+    @staticmethod
+    def backward(ctx, g, _g_parts):
+        (dlog,) = ctx.saved_tensors
+        if g is None:
+            return (None,) * 7
+        if g is UNIT_GRAD.get(dlog.device):      # the step's own seed (train.TrainStep: a cached 1.0): dL/dstudent is dlog itself
+            return dlog, None, None, None, None, None, None
+        return dlog * g, None, None, None, None, None, None
+
+
 # ----------------------------------------------------------------------------- fused edge block (tier 2)
 
 def _act_raw(x, kind):

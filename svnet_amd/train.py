@@ -5,6 +5,9 @@ clouds, permute to [B,3,N], zero_grad, forward, utils.cal_loss, backward, optimi
 CosineAnnealingLR.step (:128-135,187).  Here:
 
   cal_loss          utils.py:33-50 as one HIP kernel (label-smoothed cross entropy)
+  kd_loss           cal_loss blended with the distillation term against a teacher's logits, loss and gradient in ONE HIP kernel
+  kd_seg_loss       (svnet_amd/csrc/kdloss.hip); the seg form reads and writes the part-segmentation models' [B,num_part,N] where it lies
+  Distiller         a frozen teacher as a ForwardStep on the student's input buffers + the loss_fn a TrainStep takes
   TrainStep         fwd + cal_loss + bwd (+ the data-parallel gradient all-reduce) on fixed device buffers, launched eagerly or
                     replayed as ONE captured HIP graph (the step is ~200 short kernels: launch-bound when launched one by one)
   train_epoch       one epoch over a device-resident pool (svnet_amd/data.py: one batch-assembly launch in front of every step);
@@ -19,7 +22,7 @@ import math
 
 import torch
 
-from . import _ops, config
+from . import _lib, _ops, config
 from .dist import GradBucket
 
 
@@ -31,6 +34,53 @@ def cal_loss(pred, target, smoothing=True):
 def seg_loss(pred, target):
     """cal_loss on the [B,num_part,N] logits of the part-segmentation models (main_partseg_dgcnn.py: rows = points)."""
     return cal_loss(pred.permute(0, 2, 1).reshape(-1, pred.shape[1]), target.reshape(-1))
+
+
+def _kd_scalars(name, T, alpha):
+    try:
+        T, alpha = float(T), float(alpha)
+    except (TypeError, ValueError):
+        raise TypeError("%s: T and alpha must be numbers, got %r and %r" % (name, T, alpha)) from None
+    if not (T > 0.0 and math.isfinite(T)):
+        raise ValueError("%s: the temperature T must be a finite number > 0, got %r" % (name, T))
+    if not 0.0 <= alpha <= 1.0:
+        raise ValueError("%s: alpha must lie in [0, 1], got %r" % (name, alpha))
+    return T, alpha
+
+
+def _kd_call(name, layout, pred, teacher, target, T, alpha, smoothing, return_parts):
+    T, alpha = _kd_scalars(name, T, alpha)
+    if not all(isinstance(t, torch.Tensor) for t in (pred, teacher, target)):
+        raise TypeError("%s: pred, teacher and target must be tensors" % name)
+    dims = 2 if layout == _lib.KD_ROWS else 3
+    if pred.dim() != dims:
+        raise ValueError("%s: pred must be %s, got %s" % (name, "[R,C]" if dims == 2 else "[B,C,N]", tuple(pred.shape)))
+    if tuple(teacher.shape) != tuple(pred.shape):
+        raise ValueError("%s: student logits %s and teacher logits %s differ in shape" % (name, tuple(pred.shape), tuple(teacher.shape)))
+    if pred.dtype != torch.float32 or teacher.dtype != torch.float32 or target.dtype != torch.int64:
+        raise TypeError("%s: pred and teacher must be float32 and target int64, got %s, %s and %s" % (name, pred.dtype, teacher.dtype, target.dtype))
+    rows = pred.shape[0] if dims == 2 else pred.shape[0] * pred.shape[2]
+    if target.numel() != rows:
+        raise ValueError("%s: target %s does not hold one class per row of pred %s" % (name, tuple(target.shape), tuple(pred.shape)))
+    if teacher.device != pred.device or target.device != pred.device:
+        raise ValueError("%s: pred on %s, teacher on %s, target on %s" % (name, pred.device, teacher.device, target.device))
+    if not pred.is_cuda:
+        raise ValueError("%s: expected HIP (cuda) tensors, got %s - there is no CPU fallback" % (name, pred.device))
+    loss, parts = _ops.KDLoss.apply(pred, teacher, target, 0.2 if smoothing else 0.0, alpha, T, layout)
+    return (loss, parts) if return_parts else loss
+
+
+def kd_loss(pred, teacher, target, T=4.0, alpha=0.5, smoothing=True, return_parts=False):
+    """(1 - alpha) * cal_loss(pred, target) + alpha * T^2 * KL(softmax(teacher / T) || softmax(pred / T)), means over rows (Hinton et
+    al.; DESIGN.md "Distillation").  pred, teacher [R,C] float32, target [R] int64; the teacher takes no gradient.
+    return_parts: also the detached [3] tensor {L, CE, KL} - the unweighted terms, for logging."""
+    return _kd_call("kd_loss", _lib.KD_ROWS, pred, teacher, target, T, alpha, smoothing, return_parts)
+
+
+def kd_seg_loss(pred, teacher, target, T=4.0, alpha=0.5, smoothing=True, return_parts=False):
+    """kd_loss on the [B,num_part,N] logits of the part-segmentation models (rows = points), target [B,N]: logits and gradient are read
+    and written in that layout - unlike seg_loss, no transposed copy of either is made."""
+    return _kd_call("kd_seg_loss", _lib.KD_CHANNEL_MAJOR, pred, teacher, target, T, alpha, smoothing, return_parts)
 
 
 class TrainStep:
@@ -172,6 +222,56 @@ class ForwardStep:
         return self.out
 
 
+class Distiller:
+    """A full-precision teacher beside a student's TrainStep: a ForwardStep of `teacher_model` on the SAME input buffers the student
+    reads, replayed in front of the student's step, and the loss_fn that blends its logits in.
+
+        d = Distiller(teacher, inputs=(x,), T=4.0, alpha=0.5)      # part segmentation: inputs=(x, onehot), seg=True
+        d.capture()                                                 # optional: the teacher's forward as a HIP graph
+        d.run()                                                     # teacher logits of the batch now in the buffers
+        step = TrainStep(student, (x,), y, loss_fn=d.loss_fn)       # capture it after a first d.run(): the logits buffer must exist
+        per batch: refill x, y -> d.run() -> step.run()             (train_epoch(..., teacher=d) does exactly that)
+
+    The teacher is put in eval() and its parameters take no gradient.  The logits the loss reads live at a FIXED address - the
+    captured ForwardStep's own output buffer, else a buffer of this object that run() copies into - so a captured student step stays
+    correct over an eager teacher as well.  `parts`: {L, CE, KL} of the last loss_fn call (a captured step: of the last replay)."""
+
+    def __init__(self, teacher_model, inputs, T=4.0, alpha=0.5, seg=False, smoothing=True):
+        self.T, self.alpha = _kd_scalars("Distiller", T, alpha)
+        if not isinstance(teacher_model, torch.nn.Module):
+            raise TypeError("Distiller: teacher_model must be a torch.nn.Module, got %s" % type(teacher_model).__name__)
+        inputs = tuple(inputs)
+        if not inputs or not all(isinstance(t, torch.Tensor) for t in inputs):
+            raise TypeError("Distiller: inputs must be a non-empty sequence of tensors (the student's input buffers)")
+        self.seg, self.smoothing = bool(seg), bool(smoothing)
+        self.model = teacher_model.eval()
+        for p in self.model.parameters():
+            p.requires_grad_(False)
+        self.step = ForwardStep(self.model, inputs)
+        self.logits = None
+        self.parts = None
+
+    def capture(self, warmup=2):
+        self.step.capture(warmup)
+        self.logits = self.step.out            # the graph's own output buffer
+        return self
+
+    def run(self):
+        out = self.step.run()
+        if self.step.graph is None:
+            if self.logits is None:
+                self.logits = torch.empty_like(out)
+            self.logits.copy_(out)
+        return self.logits
+
+    def loss_fn(self, out, target):
+        if self.logits is None:
+            raise RuntimeError("Distiller.loss_fn: no teacher logits yet - call run() (or capture() and run()) before the student's step")
+        fn = kd_seg_loss if self.seg else kd_loss
+        loss, self.parts = fn(out, self.logits, target, self.T, self.alpha, self.smoothing, return_parts=True)
+        return loss
+
+
 # ----------------------------------------------------------------------------- epochs over a device-resident pool (svnet_amd/data.py)
 
 def _update_metrics(metrics, out, loader, step_index, count):
@@ -180,17 +280,21 @@ def _update_metrics(metrics, out, loader, step_index, count):
     metrics.update(out, loader.y if loader.seg is None else loader.seg, count, label=loader.y, first=first)
 
 
-def train_epoch(step, loader, optimizer, metrics=None):
+def train_epoch(step, loader, optimizer, metrics=None, teacher=None):
     """One epoch of `step` (a TrainStep built on `loader`'s buffers: inputs=(loader.x, ...), target=loader.y): per step the batch
     assembly launch, the (replayed) step, the optimizer.  The assembly stays outside a captured graph - its step index is an ordinary
     kernel argument - and stream order puts it in front of the replay.  Returns the mean loss as a float: a running sum on the device,
     read by the host once at the end.
     metrics: an EpochMetrics (svnet_amd/metrics.py) that receives every step's output (`step` built with keep_output=True) - one more
-    launch behind the replay, outside the graph like the assembly; nothing is read by the host."""
+    launch behind the replay, outside the graph like the assembly; nothing is read by the host.
+    teacher: a Distiller on the same buffers (`step` built with loss_fn=teacher.loss_fn): its forward runs between the assembly and
+    the step.  The metrics' loss stays the smoothed cross entropy of the student's logits."""
     total = None
     steps = len(loader)
     for i in range(steps):
         count = loader.load(i)
+        if teacher is not None:
+            teacher.run()
         loss = step.run()
         total = loss.detach().clone() if total is None else total.add_(loss.detach())     # (a captured step's loss lives in a fixed buffer)
         if metrics is not None:
