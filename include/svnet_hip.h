@@ -45,9 +45,9 @@ int svnet_slices_sum_f64(double* buf, int64_t L, void* stream);
 
 /* ABI version = 100 * round-of-change + serial.  It changes whenever an entry point gains / loses an argument or a caller-owned buffer
  * changes its required length (200: sliced accumulators, SVNET_SLICED_LEN; 400: this header; 401: the totals of a sliced accumulator are
- * written by its consumer, svnet_slices_sum_*; 402: GX of svnet_v2s_bwd_*, gw of svnet_xyzblock_bwd_f32 and col_sum of svnet_gemm_f32 are sliced accumulators; 403: svnet_binweight_grad_f32 takes sliced inputs).  svnet_version() returns the value the
+ * written by its consumer, svnet_slices_sum_*; 402: GX of svnet_v2s_bwd_*, gw of svnet_xyzblock_bwd_f32 and col_sum of svnet_gemm_f32 are sliced accumulators; 403: svnet_binweight_grad_f32 takes sliced inputs; 421: svnet_three_nn_f32, svnet_three_interpolate_f32).  svnet_version() returns the value the
  * library was BUILT with: a caller compiled against another header must refuse to run (svnet_amd/_lib.py does).                   */
-#define SVNET_ABI_VERSION 420
+#define SVNET_ABI_VERSION 421
 int svnet_version(void);
 const char* svnet_last_error(void);
 
@@ -750,6 +750,30 @@ int svnet_fps_tier(int64_t P);
 int svnet_fps_f32(const float* xyz, int64_t M, int64_t P, int64_t npoint, const int64_t* start, int64_t* idx, void* stream);
 int svnet_pool_gather_f32(const float* data, const int64_t* seg, const int64_t* idx, int64_t M, int64_t P, int64_t N, int normalize,
                           float* out, int64_t* seg_out, void* stream);
+
+/* ------------------------------------------------------------------ feature propagation: sampled points -> dense cloud
+ * (models/utils/pointnet_util.py:281-308 PointNetFeaturePropagation.forward without its MLP: three nearest sampled points,
+ * inverse-squared-distance weights, weighted sum).  Forward only.  Per cloud, query [P,3], ref [N,3], feat [D,N] (channel-first), fp32,
+ * every operation rounded once and never contracted into an fma, both divisions correctly rounded:
+ *     d_c = fl(query[p,c] - ref[n,c]),  dist[p,n] = fl(fl(fl(d_0 d_0) + fl(d_1 d_1)) + fl(d_2 d_2))    (the difference form of svnet_fps_f32:
+ *         never negative, exactly 0 at a coincident point; the reference's expanded form -2 q.r + |q|^2 + |r|^2 is NOT used)
+ *     idx[p,0..2], dist3[p,0..2]: the min(3, N) smallest dist[p,:], ascending, the LOWER index first among equals; a slot no candidate
+ *         took (slots past N when N < 3; candidates whose distance is NaN or +inf are never taken) holds index 0 and dist3 = +inf
+ *     rec_j = fl(1 / fl(dist3_j + fp32(1e-8))),  s = fl(fl(rec_0 + rec_1) + rec_2),  weight[p,j] = fl(rec_j / s)   (an empty slot: 0)
+ *     out[d,p] = fl(fl(fl(feat[d,i_0] w_0) + fl(feat[d,i_1] w_1)) + fl(feat[d,i_2] w_2))       (N = 1: w_0 = 1, out = feat[d,0])
+ * svnet_three_nn_f32: query [B,P,3], ref [B,N,3] -> idx [B,P,3] int64, dist3 [B,P,3], weight [B,P,3].  Every index written lies in
+ *     0 .. N-1 whatever the coordinates hold (NaN / Inf: unspecified neighbours, in range).
+ * svnet_three_interpolate_f32: feat [B,D,N], idx, weight [B,P,3] -> out [B,D,P].  An index outside 0 .. N-1 is clamped into it.
+ * One thread per query point, one launch each, no workspace.  1 <= N <= 32768 (the k-NN's limit), P >= 1, D >= 1,
+ * B * ceil(P / 256) <= 2^31 - 1; past that SVNET_E_UNSUPPORTED.  svnet_propagate_supported (1 / 0, without the B term) and
+ * svnet_propagate_tile (the sampled points per LDS tile of svnet_three_nn_f32: the N at which its loop takes a second tile) are pure
+ * host functions.                                                                                                                  */
+int svnet_propagate_supported(int64_t P, int64_t N, int64_t D);
+int svnet_propagate_tile(void);
+int svnet_three_nn_f32(const float* query, const float* ref, int64_t B, int64_t P, int64_t N, int64_t* idx, float* dist3, float* weight,
+                       void* stream);
+int svnet_three_interpolate_f32(const float* feat, const int64_t* idx, const float* weight, int64_t B, int64_t D, int64_t N, int64_t P,
+                                float* out, void* stream);
 
 /* ------------------------------------------------------------------ epoch metrics (main_cls_dgcnn.py:187-251, main_partseg_dgcnn.py:185-279,
  * utils.py:68-91 calculate_shape_IoU; the accuracy scores of sklearn.metrics are functions of the confusion matrix)

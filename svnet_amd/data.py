@@ -182,6 +182,12 @@ class DevicePool:
                       int(bool(normalize)), _ops._p(new.data), _ops._p(new.seg), _ops._stream())
         return new
 
+    def source_points(self, source_pool):
+        """[M,N,3]: this resampled pool's points in the frame of `source_pool`, the pool it was made from by resample_fps
+        (svnet_amd/propagate.py source_points: source_pool.data gathered by fps_index; raises without an fps_index)."""
+        from .propagate import source_points
+        return source_points(self, source_pool)
+
     @staticmethod
     def synthetic_arrays(seed, M, P, num_class, num_part=None):
         """(data, label, seg or None) of a synthetic pool as numpy: the clouds of synth.cloud_batch, point-major."""

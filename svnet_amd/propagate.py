@@ -1,0 +1,201 @@
+"""Feature propagation from sampled points to the dense cloud they were sampled from (svnet_amd/csrc/propagate.hip).
+
+`DevicePool.resample_fps` (svnet_amd/data.py) reduces dense clouds to the 1024 or 2048 points a model trains and predicts on.  This
+module carries a prediction back: PointNet++'s inverse-squared-distance interpolation over the three nearest sampled points, the
+reference's `PointNetFeaturePropagation.forward` (models/utils/pointnet_util.py:281-308, via `square_distance` and `index_points`)
+without its MLP - farthest point sampling's counterpart from the same file.
+
+    dense = DevicePool(data10k, label, seg, device="cuda:0")            # [M,10000,3]
+    pool = dense.resample_fps(2048, seed=0, normalize=True)             # what the model sees
+    ref = source_points(pool, dense)                                    # [M,2048,3]: the sampled points in `dense`'s frame
+    logits_dense = propagate(dense.data[m0:m1], ref[m0:m1], logits)     # [B,50,2048] -> [B,50,10000]
+    result = train.evaluate_dense(fwd_step, loader, metrics, dense)     # the whole evaluation pass, shape IoU of the CLOUDS
+
+The contract, for one cloud: queries q [P,3], sampled points r [N,3], features f [D,N] (channel-first, as the part-seg models'
+[B,num_part,N] logits lie), all fp32.  Every operation is rounded once and never contracted into an fma (the kernels are compiled
+like fps.hip and batch.hip, with contraction off); fl() is rounding to fp32.
+
+    distances   d_c = fl(q[p,c] - r[n,c]);   dist[p,n] = fl(fl(fl(d_0 d_0) + fl(d_1 d_1)) + fl(d_2 d_2))
+                The difference form fps.hip uses: never negative, exactly 0 at a coincident point.  The reference's expanded form
+                -2 q.r + |q|^2 + |r|^2 is deliberately NOT copied: after resample_fps every sampled point coincides with a dense
+                point, there the expanded form rounds to small values of either sign, and 1 / (dist + 1e-8) turns that into garbage.
+    neighbours  the K = min(3, N) smallest dist[p,:], ascending, the lower index first among equals: idx [P,3] int64 and
+                dist3 [P,3] fp32.  Slots past K (N < 3 only) hold index 0, dist3 = +inf and weight 0.  Indices are always inside
+                [0, N), also when a coordinate is NaN or infinite (a NaN or +inf distance is never taken; its slot stays as a slot
+                past K): results are then unspecified but in range.
+    weights     rec_j = fl(1 / fl(dist3_j + fp32(1e-8)));   s = fl(fl(rec_0 + rec_1) + rec_2);   w_j = fl(rec_j / s)
+                Both divisions are correctly rounded.
+    values      out[d,p] = fl(fl(fl(f[d,i_0] w_0) + fl(f[d,i_1] w_1)) + fl(f[d,i_2] w_2))
+                N = 1 gives w_0 = 1 and out = f[d,0], the reference's `S == 1` branch (finite features: 0 * inf is NaN).
+
+On coordinates whose squares and products are exact in fp32 the two distance forms agree bit for bit, and there the whole contract
+equals the reference's CPU result bit for bit (tests/golden/propagate.npz; tests/propagate_ref.py restates the contract in numpy).
+
+Forward only: the functions take no gradient and build no autograd graph.  There is no CPU fallback: tensors that are not on a
+HIP device raise.  Limits: 1 <= N <= 32768 (the k-NN's limit), P >= 1, D >= 1, B * ceil(P / 256) <= 2^31 - 1.
+"""
+import torch
+
+from . import _lib, _ops
+
+
+def tile():
+    """Sampled points per LDS tile of the three_nn kernel: the N past which its candidate loop takes another tile."""
+    return int(_lib.lib().svnet_propagate_tile())
+
+
+def _check(name, tensors, dtypes):
+    """tensors: {argument name: tensor}; the type, dtype, device-match and contiguity checks shared by the entry points (the HIP
+    device itself is checked after the shapes, by _ops._hip)."""
+    for k, t in tensors.items():
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("%s: %s must be a tensor, got %s" % (name, k, type(t).__name__))
+    for (k, t), dt in zip(tensors.items(), dtypes):
+        if t.dtype != dt:
+            raise TypeError("%s: %s must be %s, got %s" % (name, k, dt, t.dtype))
+    first = next(iter(tensors.values()))
+    for k, t in tensors.items():
+        if t.device != first.device:
+            raise ValueError("%s: %s on %s, %s on %s" % (name, next(iter(tensors)), first.device, k, t.device))
+        if not t.is_contiguous():
+            raise ValueError("%s: %s must be contiguous" % (name, k))
+        if t.requires_grad:
+            raise ValueError("%s: %s requires grad - the propagation is forward only" % (name, k))
+
+
+def _supported(name, P, N, D):
+    if not _lib.lib().svnet_propagate_supported(P, N, D):
+        raise _lib.SvnetHipError("%s: P = %d, N = %d, D = %d is not supported (P >= 1, D >= 1, 1 <= N <= 32768)" % (name, P, N, D))
+
+
+def _nn_shapes(name, query, ref):
+    if query.dim() != 3 or query.shape[2] != 3 or query.shape[0] < 1:
+        raise ValueError("%s: query must be [B,P,3], got %s" % (name, tuple(query.shape)))
+    if ref.dim() != 3 or ref.shape[2] != 3 or ref.shape[0] != query.shape[0]:
+        raise ValueError("%s: ref must be [B,N,3] with B = %d, got %s" % (name, query.shape[0], tuple(ref.shape)))
+    return int(query.shape[0]), int(query.shape[1]), int(ref.shape[1])
+
+
+def _nn_launch(query, ref, B, P, N, idx, dist3, weight):
+    with torch.cuda.device(query.device):
+        _lib.call("svnet_three_nn_f32", _ops._p(query), _ops._p(ref), B, P, N, _ops._p(idx), _ops._p(dist3), _ops._p(weight), _ops._stream())
+
+
+def _interp_launch(feat, idx, weight, B, D, N, P, out):
+    with torch.cuda.device(feat.device):
+        _lib.call("svnet_three_interpolate_f32", _ops._p(feat), _ops._p(idx), _ops._p(weight), B, D, N, P, _ops._p(out), _ops._stream())
+
+
+def three_nn(query, ref):
+    """query [B,P,3], ref [B,N,3] float32 on a HIP device -> (idx [B,P,3] int64, dist3 [B,P,3], weight [B,P,3]): the three nearest
+    `ref` points of every query point and their interpolation weights (module docstring).  One launch, no host read; no gradient."""
+    _check("three_nn", {"query": query, "ref": ref}, (torch.float32, torch.float32))
+    B, P, N = _nn_shapes("three_nn", query, ref)
+    _ops._hip(query, ref)
+    _supported("three_nn", P, N, 1)
+    idx = torch.empty(B, P, 3, dtype=torch.int64, device=query.device)
+    dist3 = torch.empty(B, P, 3, dtype=torch.float32, device=query.device)
+    weight = torch.empty(B, P, 3, dtype=torch.float32, device=query.device)
+    _nn_launch(query, ref, B, P, N, idx, dist3, weight)
+    return idx, dist3, weight
+
+
+def _interp_shapes(name, feat, idx, weight):
+    if feat.dim() != 3 or feat.shape[0] < 1:
+        raise ValueError("%s: feat must be [B,D,N], got %s" % (name, tuple(feat.shape)))
+    if idx.dim() != 3 or idx.shape[2] != 3 or idx.shape[0] != feat.shape[0] or tuple(weight.shape) != tuple(idx.shape):
+        raise ValueError("%s: idx and weight must be [B,P,3] with B = %d, got %s and %s"
+                         % (name, feat.shape[0], tuple(idx.shape), tuple(weight.shape)))
+    return int(feat.shape[0]), int(feat.shape[1]), int(feat.shape[2]), int(idx.shape[1])
+
+
+def _out_buffer(name, out, feat, B, D, P):
+    if out is None:
+        return torch.empty(B, D, P, dtype=torch.float32, device=feat.device)
+    _check(name, {"feat": feat, "out": out}, (torch.float32, torch.float32))
+    if tuple(out.shape) != (B, D, P):
+        raise ValueError("%s: out must be [B,D,P] = %s, got %s" % (name, (B, D, P), tuple(out.shape)))
+    return out
+
+
+def three_interpolate(feat, idx, weight, out=None):
+    """feat [B,D,N] float32, idx [B,P,3] int64, weight [B,P,3] float32 -> [B,D,P]: out[b,d,p] = sum_j feat[b,d,idx[b,p,j]] weight[b,p,j]
+    in the contract's order.  An index outside [0, N) is clamped into it.  One launch, no host read; no gradient."""
+    _check("three_interpolate", {"feat": feat, "idx": idx, "weight": weight}, (torch.float32, torch.int64, torch.float32))
+    B, D, N, P = _interp_shapes("three_interpolate", feat, idx, weight)
+    _ops._hip(feat, idx, weight)
+    _supported("three_interpolate", P, N, D)
+    out = _out_buffer("three_interpolate", out, feat, B, D, P)
+    _interp_launch(feat, idx, weight, B, D, N, P, out)
+    return out
+
+
+def propagate(query, ref, feat, out=None):
+    """three_nn(query, ref) then three_interpolate(feat, ...): feat [B,D,N] at the points ref [B,N,3] -> [B,D,P] at query [B,P,3].
+    Two launches on the current stream, no host read and no synchronisation, so it can be captured in a HIP graph; `out` lets a
+    caller keep a fixed buffer.  No gradient."""
+    _check("propagate", {"query": query, "ref": ref, "feat": feat}, (torch.float32,) * 3)
+    B, P, N = _nn_shapes("propagate", query, ref)
+    if feat.dim() != 3 or feat.shape[0] != B or feat.shape[2] != N:
+        raise ValueError("propagate: feat must be [B,D,N] with B = %d, N = %d, got %s" % (B, N, tuple(feat.shape)))
+    D = int(feat.shape[1])
+    _ops._hip(query, ref, feat)
+    _supported("propagate", P, N, D)
+    out = _out_buffer("propagate", out, feat, B, D, P)
+    idx = torch.empty(B, P, 3, dtype=torch.int64, device=query.device)
+    dist3 = torch.empty(B, P, 3, dtype=torch.float32, device=query.device)
+    weight = torch.empty(B, P, 3, dtype=torch.float32, device=query.device)
+    _nn_launch(query, ref, B, P, N, idx, dist3, weight)
+    _interp_launch(feat, idx, weight, B, D, N, P, out)
+    return out
+
+
+class Propagator:
+    """propagate() on buffers allocated once: the neighbour and weight buffers for up to B clouds of P query points and the output
+    [B,D,P].  run(query, ref, feat) takes the first `count` clouds of each and returns out[:count]; nothing is allocated per call."""
+
+    def __init__(self, B, D, N, P, device):
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError("svnet_amd: Propagator needs a HIP (cuda) device, got %s — the product path has no CPU fallback" % device)
+        self.B, self.D, self.N, self.P = int(B), int(D), int(N), int(P)
+        if self.B < 1:
+            raise ValueError("Propagator: B = %d < 1" % self.B)
+        _supported("Propagator", self.P, self.N, self.D)
+        self.idx = torch.empty(self.B, self.P, 3, dtype=torch.int64, device=device)
+        self.dist3 = torch.empty(self.B, self.P, 3, dtype=torch.float32, device=device)
+        self.weight = torch.empty(self.B, self.P, 3, dtype=torch.float32, device=device)
+        self.out = torch.empty(self.B, self.D, self.P, dtype=torch.float32, device=device)
+
+    def run(self, query, ref, feat):
+        _check("Propagator.run", {"query": query, "ref": ref, "feat": feat}, (torch.float32,) * 3)
+        count, P, N = _nn_shapes("Propagator.run", query, ref)
+        _ops._hip(query, ref, feat)
+        if count > self.B or (P, N) != (self.P, self.N) or tuple(feat.shape) != (count, self.D, N) or query.device != self.out.device:
+            raise ValueError("Propagator.run: query %s, ref %s, feat %s do not fit B <= %d, D %d, N %d, P %d on %s"
+                             % (tuple(query.shape), tuple(ref.shape), tuple(feat.shape), self.B, self.D, self.N, self.P, self.out.device))
+        _nn_launch(query, ref, count, P, N, self.idx, self.dist3, self.weight)
+        _interp_launch(feat, self.idx, self.weight, count, self.D, N, P, self.out)
+        return self.out[:count]
+
+
+def source_points(pool, source_pool):
+    """The [M,N,3] coordinates of a resampled pool's points in the frame of the pool it came from: source_pool.data gathered by
+    pool.fps_index.  (`normalize=True` moved the sampled pool's own coordinates, so pool.data is not that.)  Raises when `pool` has
+    no fps_index or the sizes do not match.  A preparation-time call: the index range is checked with one device reduction and one
+    synchronisation."""
+    from .data import DevicePool
+    if not isinstance(pool, DevicePool) or not isinstance(source_pool, DevicePool):
+        raise TypeError("source_points: pool and source_pool must be DevicePools")
+    index = getattr(pool, "fps_index", None)
+    if index is None:
+        raise ValueError("source_points: the pool has no fps_index - it was not made by DevicePool.resample_fps")
+    if pool.M != source_pool.M or tuple(index.shape) != (pool.M, pool.P) or pool.P > source_pool.P:
+        raise ValueError("source_points: a pool of %d clouds of %d points (fps_index %s) was not sampled from a pool of %d clouds of %d points"
+                         % (pool.M, pool.P, tuple(index.shape), source_pool.M, source_pool.P))
+    if index.device != source_pool.data.device:
+        raise ValueError("source_points: fps_index on %s, the source pool on %s" % (index.device, source_pool.data.device))
+    lo, hi = (int(v) for v in torch.aminmax(index))
+    if lo < 0 or hi >= source_pool.P:
+        raise ValueError("source_points: fps_index outside 0 .. P-1 = %d (min %d, max %d)" % (source_pool.P - 1, lo, hi))
+    return torch.gather(source_pool.data, 1, index.unsqueeze(2).expand(-1, -1, 3)).contiguous()

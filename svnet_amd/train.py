@@ -328,6 +328,46 @@ def evaluate(fwd_step, loader, metrics):
     return metrics.result()
 
 
+def evaluate_dense(fwd_step, loader, metrics, dense_pool):
+    """evaluate()'s pass for a model that predicts on FPS-sampled points, scored on the dense clouds they were sampled from: per batch
+    the assembly, the forward, ONE propagation of the [B,num_part,N] logits onto the batch's dense clouds (svnet_amd/propagate.py: the
+    three nearest sampled points, inverse-squared-distance weights) into a fixed [B,num_part,P] buffer, and one metrics.update with
+    the dense per-point labels dense_pool.seg.  Resets `metrics` (a part-segmentation EpochMetrics) and returns metrics.result(): the
+    loss, accuracies and shape IoU of the CLOUDS, not of the sample.  Nothing is read by the host inside the loop.
+
+    `loader` must run over a pool made by dense_pool.resample_fps(...), whole clouds (num_points = the pool's), with
+    select="first_ordered", shuffle=False, drop_last=False - slot n of the batch must be sampled point n of cloud first + b - else
+    ValueError.  Limits, checked before the first launch: what propagate takes (N <= 32768) and what EpochMetrics.update takes
+    (batch size <= 65535, P <= 2^31, capacity >= the pool's clouds)."""
+    from .data import SELECT_MODES
+    from .propagate import Propagator, source_points
+    pool = loader.pool
+    if getattr(pool, "fps_index", None) is None:
+        raise ValueError("evaluate_dense: the loader's pool has no fps_index - make it with dense_pool.resample_fps(...)")
+    if loader.select_mode != SELECT_MODES["first_ordered"] or loader.shuffle or loader.drop_last or loader.N != pool.P:
+        raise ValueError("evaluate_dense: the loader must use select='first_ordered', shuffle=False, drop_last=False and num_points = "
+                         "the pool's %d points: slot n must be sampled point n" % pool.P)
+    if dense_pool.seg is None:
+        raise ValueError("evaluate_dense: dense_pool has no per-point labels (seg)")
+    if not metrics.seg:
+        raise ValueError("evaluate_dense: metrics must be a part-segmentation EpochMetrics (parts=..., capacity=...)")
+    B, P = loader.B, dense_pool.P
+    if B > 65535 or P > (1 << 31) or metrics.capacity < pool.M:
+        raise ValueError("evaluate_dense: EpochMetrics.update takes batch size <= 65535, P <= 2^31 and first + count <= capacity; "
+                         "got batch size %d, P %d, capacity %d for %d clouds" % (B, P, metrics.capacity, pool.M))
+    ref = source_points(pool, dense_pool)                              # [M,N,3] in the dense clouds' frame (raises on a mismatch)
+    prop = Propagator(B, metrics.C, loader.N, P, dense_pool.device)    # (raises past propagate's limits)
+    metrics.reset()
+    for i in range(len(loader)):
+        count = loader.load(i)
+        if count:
+            first, _ = loader.span(i)
+            logits = fwd_step.run()
+            dense = prop.run(dense_pool.data[first:first + count], ref[first:first + count], logits[:count])
+            metrics.update(dense, dense_pool.seg[first:first + count], count, label=dense_pool.label[first:first + count], first=first)
+    return metrics.result()
+
+
 # ----------------------------------------------------------------------------- augmentation
 
 def rotate_clouds(x, mode, generator=None):
