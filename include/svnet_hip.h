@@ -648,13 +648,13 @@ int svnet_binhead_bwd_f32(const svnet_binhead_desc* d, void* stream);
 int svnet_fplinear_small_bwd_f32(const float* g, const float* x, const float* W, int64_t M, int64_t K, int64_t O, float* dx,
                                  float* dW, float* db, void* stream);
 
-/* ------------------------------------------------------------------ label-smoothed cross entropy (utils.py:33-50 cal_loss)
+/* ------------------------------------------------------------------ label-smoothed cross entropy (utils.py:33-50 cal_loss; csrc/loss.hip)
  * logits [R,C], target [R] int64; loss = mean_r -(soft . log_softmax); dlogits = d loss / d logits.
  * workspace: >= 1024 floats (per-workgroup partial losses, added in a fixed order: bit-reproducible).   */
 int svnet_smooth_ce_f32(const float* logits, const int64_t* target, int64_t R, int64_t C, float eps, float* loss,
                         float* dlogits, float* workspace, int64_t workspace_floats, void* stream);
 
-/* ------------------------------------------------------------------ knowledge distillation fused with cal_loss (csrc/kdloss.hip)
+/* ------------------------------------------------------------------ knowledge distillation fused with cal_loss (csrc/loss.hip)
  * The reference publishes distilled binary models (README, scripts.sh: *_binary_kd_*) without the loss's source; this is Hinton et al.'s:
  *     ce_r = -(soft_r . log_softmax(s_r))   (utils.py:33-50, soft = 1 - eps at the target, eps / (C - 1) elsewhere)
  *     kl_r = sum_c p_rc (logp_rc - logq_rc),  logp = log_softmax(t_r / T), logq = log_softmax(s_r / T), p = exp(logp)
@@ -781,7 +781,7 @@ int svnet_three_interpolate_f32(const float* feat, const int64_t* idx, const flo
  *     state, as int64 words: conf[C*C] (row = true class, column = predicted class) | rows | invalid | loss_sum (a float64)
  * svnet_metrics_state_bytes gives its size; svnet_metrics_reset zero-fills it and marks all `capacity` shape slots empty (one launch).
  * Per valid row: the prediction is the LOWEST index among the row's maxima, a NaN counting as the maximum (torch.max over a dim on the
- * CPU), and loss_sum grows by the row's cal_loss term in the fp32 arithmetic of svnet_smooth_ce_f32.  A row whose target lies outside
+ * CPU), and loss_sum grows by the row's cal_loss term in the fp32 arithmetic of svnet_smooth_ce_f32 (csrc/smooth_ce.h).  A row whose target lies outside
  * 0 .. C-1 (the batch assembly's -1 poison included) indexes nothing: it is counted in `invalid` and otherwise skipped.  Integer counts
  * are integer atomics; loss_sum is added in a fixed order by a finishing launch of the same call (no float atomics): two identical
  * passes give identical bits.  `count`: the valid leading rows / clouds (0: nothing is launched).  `workspace`: scratch of

@@ -1771,6 +1771,12 @@ class _UnitGrad:
 UNIT_GRAD = _UnitGrad()
 
 
+def _scale_saved_grad(dlog, g):
+    """A loss's saved gradient times the upstream `g`; the step's own seed (train.TrainStep: the cached 1.0, known by identity) hands
+    `dlog` back untouched."""
+    return dlog if g is UNIT_GRAD.get(dlog.device) else dlog * g
+
+
 class SmoothCE(torch.autograd.Function):
     """Label-smoothed cross entropy, mean over rows (utils.py:33-50 cal_loss)."""
 
@@ -1790,13 +1796,11 @@ class SmoothCE(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         (dlog,) = ctx.saved_tensors
-        if g is UNIT_GRAD.get(dlog.device):      # the step's own seed (train.TrainStep: a cached 1.0): dL/dlogits is dlog itself
-            return dlog, None, None
-        return dlog * g, None, None
+        return _scale_saved_grad(dlog, g), None, None
 
 
 class KDLoss(torch.autograd.Function):
-    """Knowledge distillation fused with cal_loss (include/svnet_hip.h svnet_kd_loss_f32, csrc/kdloss.hip):
+    """Knowledge distillation fused with cal_loss (include/svnet_hip.h svnet_kd_loss_f32, csrc/loss.hip):
     L = (1 - alpha) * smoothed CE(student, target) + alpha * T^2 * KL(softmax(teacher / T) || softmax(student / T)), means over rows.
     layout _lib.KD_ROWS: student / teacher [R,C], target [R]; _lib.KD_CHANNEL_MAJOR: [B,C,N] (rows = points), target [B,N] - read and
     written where it lies.  Returns (L, parts): parts = the detached [3] tensor {L, CE, KL} (CE, KL unweighted, for logging).  The
@@ -1827,9 +1831,7 @@ class KDLoss(torch.autograd.Function):
         (dlog,) = ctx.saved_tensors
         if g is None:
             return (None,) * 7
-        if g is UNIT_GRAD.get(dlog.device):      # the step's own seed (train.TrainStep: a cached 1.0): dL/dstudent is dlog itself
-            return dlog, None, None, None, None, None, None
-        return dlog * g, None, None, None, None, None, None
+        return _scale_saved_grad(dlog, g), None, None, None, None, None, None
 
 
 # ----------------------------------------------------------------------------- fused edge block (tier 2)

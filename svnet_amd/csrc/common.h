@@ -90,6 +90,11 @@ __device__ __forceinline__ float group_sum_dpp(float v) {
     return v;
 }
 __device__ __forceinline__ float wave_sum(float v) { return group_sum_dpp<64>(v); }
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+    return v;
+}
 // ---- grid-wide column sums without a thousand adders per address.  A reduction kernel used to end in one atomic per output per
 // workgroup onto the SAME L addresses; same-address atomics are served one after the other at the memory side (~2.5 ns each per cache
 // line, measured: 512 workgroups x 340 doubles = 12 us of a 39 us kernel, the float reductions twice that), and removing them from

@@ -1,5 +1,6 @@
-// Knowledge distillation (Hinton et al.) fused with the label-smoothed cross entropy of cal_loss (utils.py:33-50): one launch per
-// layout reads the student's and the teacher's logits once and writes the loss terms and d L / d student.
+// The losses: the label-smoothed cross entropy of cal_loss (utils.py:33-50), alone (svnet_smooth_ce_f32) and fused with knowledge
+// distillation (Hinton et al., svnet_kd_loss_f32): one launch per layout reads the student's - and the teacher's - logits once and
+// writes the loss terms and d L / d student.  The cross entropy's fp32 sequence is smooth_ce.h's, in every kernel here.
 //
 //   ce_r   = -sum_c soft_rc * log_softmax(s_r)_c            soft_rc = 1 - eps at c == y_r, eps / (C - 1) elsewhere
 //   logp_r = log_softmax(t_r / T), logq_r = log_softmax(s_r / T), p = exp(logp)
@@ -10,19 +11,20 @@
 // logp and logq are (x - max) / T - log(sum exp((x - max) / T)): a teacher probability that underflows to 0 meets a FINITE
 // logp - logq, so its term is 0 and never NaN.  Targets are compared with the class index, never used as one (cal_loss's contract).
 //
-// rows layout [R,C]:           one wave per row, lanes over classes - smooth_ce_kernel's (pool.hip) walk, grid and partial order; the CE
-//                              half of the gradient is computed by the same fp32 sequence, so alpha = 0 reproduces its dlogits bit for bit.
+// rows layout [R,C]:           smooth_ce_kernel<KD>, one wave per row, lanes over classes.  KD = false is cal_loss: no teacher, one
+//                              partial per workgroup.  KD = true adds the teacher's sums to the same loops and a second partial; the CE
+//                              half of its gradient is the same code, so alpha = 0 reproduces cal_loss's dlogits bit for bit.
 // channel-major layout [B,C,N]: a workgroup of 4 waves owns 64 consecutive points; lane = point (consecutive addresses along N for every
 //                              class: each wave-level load and store is one 256-byte run), wave g = classes g, g + 4, g + 8, ...  Up to
 //                              KD_CM_REG_CLASSES classes both logit vectors stay in registers between the three passes (max, sums,
 //                              gradient) - every byte is read once and written once; past that the passes re-read global memory.
 //                              The four waves meet in LDS for the per-point max and sums.  No transposed copy exists anywhere.
 //
-// Every workgroup stores ONE (ce, kl) pair of partial sums (waves and lanes added in a fixed order) and a one-wave finishing launch of
-// the same call adds the pairs in a fixed order: no float atomics, {L, CE, KL} and dlogits are bit-identical from run to run.
+// Every workgroup stores ONE partial sum per loss term (waves and lanes added in a fixed order) and a one-wave finishing launch of
+// the same call adds them in a fixed order: no float atomics, the loss, {L, CE, KL} and dlogits are bit-identical from run to run.
 #include <float.h>
 
-#include "common.h"
+#include "smooth_ce.h"
 
 namespace {
 
@@ -41,73 +43,72 @@ struct KdScalars {
     float inv_t;          // 1 / T
     float w_ce, w_kd;     // gradient weights: 1 - alpha, alpha * T
 };
-// the smoothed target and 1 / rows, formed on the device exactly as smooth_ce_kernel forms them
-struct KdDerived {
-    float on, off, inv_r;
-    __device__ KdDerived(float eps, int64_t C, int64_t rows) : on(1.f - eps), off(eps / (float)(C - 1)), inv_r(1.f / (float)rows) {}
-};
 
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-
-// ---- rows layout: one wave per row
-__global__ __launch_bounds__(KD_THREADS) void kd_rows_kernel(const float* __restrict__ student, const float* __restrict__ teacher,
-                                                             const int64_t* __restrict__ target, int64_t R, int64_t C, KdScalars k,
-                                                             float* __restrict__ partial, float* __restrict__ dlogits) {
-    __shared__ float wsum[2][KD_WAVES];
+// ---- rows layout: one wave per row.  KD = false is cal_loss alone: the teacher, its sums, the KL term and the second partial are
+// compiled out (teacher is not read, of k only eps).  Every workgroup writes its partial(s) - four waves added in a fixed order.
+template <bool KD>
+__global__ __launch_bounds__(KD_THREADS) void smooth_ce_kernel(const float* __restrict__ student, const float* __restrict__ teacher,
+                                                               const int64_t* __restrict__ target, int64_t R, int64_t C, KdScalars k,
+                                                               float* __restrict__ partial, float* __restrict__ dlogits) {
+    __shared__ float wsum[KD ? 2 : 1][KD_WAVES];
     const int lane = threadIdx.x & 63;
     const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
-    const KdDerived d(k.eps, C, R);
+    const SmoothCe d(k.eps, C, R);
     float local_ce = 0.f, local_kl = 0.f;
     for (int64_t r = wave; r < R; r += nwaves) {
         const float* srow = student + r * C;
-        const float* trow = teacher + r * C;
+        const float* trow = KD ? teacher + r * C : nullptr;
         float mx = -FLT_MAX, mt = -FLT_MAX;
         for (int64_t c = lane; c < C; c += 64) {
             mx = fmaxf(mx, srow[c]);
-            mt = fmaxf(mt, trow[c]);
+            if constexpr (KD) mt = fmaxf(mt, trow[c]);
         }
         mx = wave_max(mx);
-        mt = wave_max(mt);
+        if constexpr (KD) mt = wave_max(mt);
         float se = 0.f, sq = 0.f, sp = 0.f;
         for (int64_t c = lane; c < C; c += 64) {
             const float x = srow[c] - mx;
             se += expf(x);
-            sq += expf(x * k.inv_t);
-            sp += expf((trow[c] - mt) * k.inv_t);
+            if constexpr (KD) {
+                sq += expf(x * k.inv_t);
+                sp += expf((trow[c] - mt) * k.inv_t);
+            }
         }
         se = wave_sum(se);
-        sq = wave_sum(sq);
-        sp = wave_sum(sp);
-        const float lse = logf(se) + mx, lsq = logf(sq), lsp = logf(sp);
+        if constexpr (KD) {
+            sq = wave_sum(sq);
+            sp = wave_sum(sp);
+        }
+        const float lse = smooth_ce_lse(se, mx), lsq = KD ? logf(sq) : 0.f, lsp = KD ? logf(sp) : 0.f;
         const int64_t t = target[r];
         float part = 0.f, kl = 0.f;
         for (int64_t c = lane; c < C; c += 64) {
             const float x = srow[c];
-            const float logp = x - lse;                              // (smooth_ce_kernel's sequence: same bits)
-            const float soft = (c == t) ? d.on : d.off;
-            part -= soft * logp;
-            const float lq = (x - mx) * k.inv_t - lsq;
-            const float lp = (trow[c] - mt) * k.inv_t - lsp;
-            const float p = expf(lp);
-            kl += p * (lp - lq);
-            if (dlogits) dlogits[r * C + c] = (k.w_ce * (expf(logp) - soft) + k.w_kd * (expf(lq) - p)) * d.inv_r;
+            const float logp = smooth_ce_logp(x, lse);
+            const float soft = d.soft(c, t);
+            smooth_ce_add(part, soft, logp);
+            if constexpr (KD) {
+                const float lq = (x - mx) * k.inv_t - lsq;
+                const float lp = (trow[c] - mt) * k.inv_t - lsp;
+                const float p = expf(lp);
+                kl += p * (lp - lq);
+                if (dlogits) dlogits[r * C + c] = (k.w_ce * smooth_ce_grad(logp, soft) + k.w_kd * (expf(lq) - p)) * d.inv_r;
+            } else {
+                if (dlogits) dlogits[r * C + c] = smooth_ce_grad(logp, soft) * d.inv_r;
+            }
         }
         local_ce += wave_sum(part);
-        local_kl += wave_sum(kl);
+        if constexpr (KD) local_kl += wave_sum(kl);
     }
     if (lane == 0) {
         wsum[0][threadIdx.x >> 6] = local_ce;
-        wsum[1][threadIdx.x >> 6] = local_kl;
+        if constexpr (KD) wsum[1][threadIdx.x >> 6] = local_kl;
     }
     __syncthreads();
     if (threadIdx.x == 0) {
-        partial[2 * blockIdx.x] = ((wsum[0][0] + wsum[0][1]) + (wsum[0][2] + wsum[0][3])) * d.inv_r;
-        partial[2 * blockIdx.x + 1] = ((wsum[1][0] + wsum[1][1]) + (wsum[1][2] + wsum[1][3])) * d.inv_r;
+        partial[(KD ? 2 : 1) * blockIdx.x] = ((wsum[0][0] + wsum[0][1]) + (wsum[0][2] + wsum[0][3])) * d.inv_r;
+        if constexpr (KD) partial[2 * blockIdx.x + 1] = ((wsum[1][0] + wsum[1][1]) + (wsum[1][2] + wsum[1][3])) * d.inv_r;
     }
 }
 
@@ -122,7 +123,7 @@ __global__ __launch_bounds__(KD_THREADS) void kd_cm_kernel(const float* __restri
     const int lane = threadIdx.x & 63, g = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int64_t tiles = (P + SVNET_WAVE - 1) / SVNET_WAVE;
     constexpr int CPT = REG ? KD_CM_CPT : 1;
-    const KdDerived d(k.eps, C, P);
+    const SmoothCe d(k.eps, C, P);
     float block_ce = 0.f, block_kl = 0.f;              // (thread 0 .. 63 of wave 0 only)
     for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
         const int64_t p = tile * SVNET_WAVE + lane;
@@ -181,19 +182,19 @@ __global__ __launch_bounds__(KD_THREADS) void kd_cm_kernel(const float* __restri
         sq = (red[1][0][lane] + red[1][1][lane]) + (red[1][2][lane] + red[1][3][lane]);
         sp = (red[2][0][lane] + red[2][1][lane]) + (red[2][2][lane] + red[2][3][lane]);
         // (an invalid lane's sums are 0: its logs are never used)
-        const float lse = logf(se) + mx, lsq = logf(sq), lsp = logf(sp);
+        const float lse = smooth_ce_lse(se, mx), lsq = logf(sq), lsp = logf(sp);
         const int64_t t = valid ? target[p] : -1;
         float part = 0.f, kl = 0.f;
         float* dp_ = dlogits ? dlogits + b * C * N + n : nullptr;
         auto one = [&](int64_t c, float x, float y) {
-            const float logp = x - lse;
-            const float soft = (c == t) ? d.on : d.off;
-            part -= soft * logp;
+            const float logp = smooth_ce_logp(x, lse);
+            const float soft = d.soft(c, t);
+            smooth_ce_add(part, soft, logp);
             const float lq = (x - mx) * k.inv_t - lsq;
             const float lp = (y - mt) * k.inv_t - lsp;
             const float pr = expf(lp);
             kl += pr * (lp - lq);
-            if (dp_) dp_[c * N] = (k.w_ce * (expf(logp) - soft) + k.w_kd * (expf(lq) - pr)) * d.inv_r;
+            if (dp_) dp_[c * N] = (k.w_ce * smooth_ce_grad(logp, soft) + k.w_kd * (expf(lq) - pr)) * d.inv_r;
         };
         if (REG) {
 #pragma unroll
@@ -221,19 +222,24 @@ __global__ __launch_bounds__(KD_THREADS) void kd_cm_kernel(const float* __restri
     }
 }
 
-// result = {L, CE, KL}: the workgroups' (ce, kl) pairs added in a fixed order
-__global__ void kd_finish_kernel(const float* __restrict__ partial, int n, float w_ce, float w_kl, float* __restrict__ result) {
+// One wave adds the workgroups' partials in a fixed order.  KD: (ce, kl) pairs, result = {L, CE, KL}; otherwise result[0] = the loss.
+template <bool KD>
+__global__ void smooth_ce_finish_kernel(const float* __restrict__ partial, int n, float w_ce, float w_kl, float* __restrict__ result) {
     float ce = 0.f, kl = 0.f;
     for (int i = threadIdx.x; i < n; i += 64) {
-        ce += partial[2 * i];
-        kl += partial[2 * i + 1];
+        ce += partial[KD ? 2 * i : i];
+        if constexpr (KD) kl += partial[2 * i + 1];
     }
     ce = wave_sum(ce);
-    kl = wave_sum(kl);
+    if constexpr (KD) kl = wave_sum(kl);
     if (threadIdx.x == 0) {
-        result[0] = w_ce * ce + w_kl * kl;
-        result[1] = ce;
-        result[2] = kl;
+        if constexpr (KD) {
+            result[0] = w_ce * ce + w_kl * kl;
+            result[1] = ce;
+            result[2] = kl;
+        } else {
+            result[0] = ce;
+        }
     }
 }
 
@@ -249,6 +255,21 @@ bool kd_rows_of(int layout, int64_t B, int64_t N, int64_t* rows) {
 }
 
 }  // namespace
+
+extern "C" int svnet_smooth_ce_f32(const float* logits, const int64_t* target, int64_t R, int64_t C, float eps, float* loss,
+                                   float* dlogits, float* workspace, int64_t workspace_floats, void* stream) {
+    SVNET_REQUIRE(logits && target && loss && R > 0 && C > 1, SVNET_E_ARG, "svnet_smooth_ce_f32: bad arguments");
+    hipStream_t st = (hipStream_t)stream;
+    const int blocks = svnet_grid(R * 64, KD_THREADS, KD_ROWS_MAX_BLOCKS);
+    SVNET_REQUIRE(workspace && workspace_floats >= blocks, SVNET_E_ARG, "svnet_smooth_ce_f32: workspace of 1024 floats required");
+    const KdScalars k = {eps, 0.f, 0.f, 0.f};
+    hipLaunchKernelGGL(smooth_ce_kernel<false>, dim3(blocks), dim3(KD_THREADS), 0, st, logits, (const float*)nullptr, target, R, C, k,
+                       workspace, dlogits);
+    SVNET_CHECK_LAUNCH("smooth_ce_kernel<false>");
+    hipLaunchKernelGGL(smooth_ce_finish_kernel<false>, dim3(1), dim3(64), 0, st, workspace, blocks, 0.f, 0.f, loss);
+    SVNET_CHECK_LAUNCH("smooth_ce_finish_kernel<false>");
+    return SVNET_OK;
+}
 
 extern "C" int svnet_kd_tier(int layout, int64_t B, int64_t C, int64_t N) {
     int64_t rows = 0;
@@ -280,8 +301,8 @@ extern "C" int svnet_kd_loss_f32(int layout, const float* student, const float* 
     int blocks;
     if (layout == SVNET_KD_ROWS) {
         blocks = (int)svnet_grid(rows * 64, KD_THREADS, KD_ROWS_MAX_BLOCKS);
-        hipLaunchKernelGGL(kd_rows_kernel, dim3(blocks), dim3(KD_THREADS), 0, st, student, teacher, target, rows, C, k, workspace, dlogits);
-        SVNET_CHECK_LAUNCH("kd_rows_kernel");
+        hipLaunchKernelGGL(smooth_ce_kernel<true>, dim3(blocks), dim3(KD_THREADS), 0, st, student, teacher, target, rows, C, k, workspace, dlogits);
+        SVNET_CHECK_LAUNCH("smooth_ce_kernel<true>");
     } else {
         blocks = (int)svnet_grid(rows, SVNET_WAVE, KD_CM_MAX_BLOCKS);
         if (tier & 1)
@@ -290,7 +311,7 @@ extern "C" int svnet_kd_loss_f32(int layout, const float* student, const float* 
             hipLaunchKernelGGL(kd_cm_kernel<true>, dim3(blocks), dim3(KD_THREADS), 0, st, student, teacher, target, rows, C, N, k, workspace, dlogits);
         SVNET_CHECK_LAUNCH("kd_cm_kernel");
     }
-    hipLaunchKernelGGL(kd_finish_kernel, dim3(1), dim3(64), 0, st, workspace, blocks, 1.f - alpha, alpha * T * T, result);
-    SVNET_CHECK_LAUNCH("kd_finish_kernel");
+    hipLaunchKernelGGL(smooth_ce_finish_kernel<true>, dim3(1), dim3(64), 0, st, workspace, blocks, 1.f - alpha, alpha * T * T, result);
+    SVNET_CHECK_LAUNCH("smooth_ce_finish_kernel<true>");
     return SVNET_OK;
 }

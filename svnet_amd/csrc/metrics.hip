@@ -7,13 +7,12 @@
 // Integers are added with integer atomics (order-independent).  The loss is never added atomically: every workgroup stores ONE
 // float64 partial (its waves in a fixed order), and a one-workgroup finishing launch of the same C call adds the partials in a fixed
 // order onto loss_sum - the hand-off is a kernel boundary of the stream, and two identical passes give identical bits.
-// The per-row loss term is the fp32 arithmetic of smooth_ce_kernel (pool.hip): mx, se = sum expf(x - mx), lse = logf(se) + mx,
-// term = -sum soft_c * (x_c - lse).
+// The per-row loss term is cal_loss's, formed by the functions of smooth_ce.h that the loss kernels (loss.hip) call too.
 //
 // The prediction of a row is the LOWEST index among its maxima, a NaN counting as the maximum (torch.max(dim) on the CPU).
 #include <float.h>
 
-#include "common.h"
+#include "smooth_ce.h"
 
 namespace {
 
@@ -43,7 +42,7 @@ __global__ __launch_bounds__(METRICS_THREADS) void metrics_cls_kernel(const floa
     const int lane = threadIdx.x & 63;
     const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
-    const float off = eps / (float)(C - 1), on = 1.f - eps;
+    const SmoothCe d(eps, C);
     double local = 0.0;
     u64 rows = 0, invalid = 0;
     for (int64_t r = wave; r < count; r += nwaves) {
@@ -70,13 +69,9 @@ __global__ __launch_bounds__(METRICS_THREADS) void metrics_cls_kernel(const floa
         float se = 0.f;
         for (int64_t c = lane; c < C; c += 64) se += expf(row[c] - mx);
         se = wave_sum(se);
-        const float lse = logf(se) + mx;
+        const float lse = smooth_ce_lse(se, mx);
         float part = 0.f;
-        for (int64_t c = lane; c < C; c += 64) {
-            const float logp = row[c] - lse;
-            const float soft = (c == t) ? on : off;
-            part -= soft * logp;
-        }
+        for (int64_t c = lane; c < C; c += 64) smooth_ce_add(part, d.soft(c, t), smooth_ce_logp(row[c], lse));
         local += (double)wave_sum(part);
         ++rows;
         if (lane == 0) atomicAdd(&state[t * C + bi], (u64)1);
@@ -117,7 +112,7 @@ __global__ __launch_bounds__(METRICS_THREADS) void metrics_seg_kernel(const SegA
     for (int i = t; i < nlds; i += METRICS_THREADS) cnt[i] = 0u;
     __syncthreads();
 
-    const float off = a.eps / (float)(P - 1), on = 1.f - a.eps;
+    const SmoothCe d(a.eps, P);
     float term = 0.f;
     bool valid = false, inside = n < N;
     if (inside) {
@@ -160,13 +155,13 @@ __global__ __launch_bounds__(METRICS_THREADS) void metrics_seg_kernel(const SegA
             } else {
                 for (int c = 0; c < P; ++c) se += expf(x[(int64_t)c * N] - mx);
             }
-            const float lse = logf(se) + mx;
+            const float lse = smooth_ce_lse(se, mx);
             if constexpr (REG) {
 #pragma unroll
                 for (int c = 0; c < METRICS_REG_PART; ++c)
-                    if (c < P) term -= ((c == s) ? on : off) * (v[c] - lse);
+                    if (c < P) smooth_ce_add(term, d.soft(c, s), smooth_ce_logp(v[c], lse));
             } else {
-                for (int c = 0; c < P; ++c) term -= ((c == s) ? on : off) * (x[(int64_t)c * N] - lse);
+                for (int c = 0; c < P; ++c) smooth_ce_add(term, d.soft(c, s), smooth_ce_logp(x[(int64_t)c * N], lse));
             }
         }
     }

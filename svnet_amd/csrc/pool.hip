@@ -1,13 +1,11 @@
-// Neighbour / point pooling, gate activations and the loss.
+// Neighbour / point pooling and the gate's activations and MLP.
 //
 // Replaces  models/utils/sv_util.py:118-132 (svpool: max over scalars, mean over vectors),
 //           models/sv_dgcnn_cls.py:72-73 (adaptive max / avg pool over points),
-//           the ReLU / Sigmoid of the gate (sv_layers.py:156-161) and utils.py:33-50 (cal_loss).
+//           the ReLU / Sigmoid of the gate (sv_layers.py:156-161).
 // x is viewed as [outer, R, inner]; lanes run over `inner` (coalesced), the reduced axis R is walked
 // sequentially (R = k = 20..40 for neighbour pooling).  Long reductions with few outputs (gate mean over
 // 20 480 edge rows) are split over workgroups and combined with float atomics.
-#include <float.h>
-
 #include "common.h"
 #include "gate_mlp.h"
 
@@ -418,50 +416,6 @@ __global__ __launch_bounds__(256) void act_bwd_kernel(const float* __restrict__ 
     }
 }
 
-// one wave per row: log-softmax, smoothed target, loss and gradient.  Every workgroup writes ONE partial loss (its four
-// waves added in a fixed order); smooth_ce_finish_kernel adds the partials in a fixed order: no float atomics, so the loss
-// is reproducible bit for bit.
-__global__ __launch_bounds__(256) void smooth_ce_kernel(const float* __restrict__ logits, const int64_t* __restrict__ target,
-                                                        int64_t R, int64_t C, float eps, float* __restrict__ partial,
-                                                        float* __restrict__ dlogits) {
-    __shared__ float wsum[4];
-    const int lane = threadIdx.x & 63;
-    const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
-    const float off = eps / (float)(C - 1), on = 1.f - eps;
-    const float invR = 1.f / (float)R;
-    float local = 0.f;
-    for (int64_t r = wave; r < R; r += nwaves) {
-        const float* row = logits + r * C;
-        float mx = -FLT_MAX;
-        for (int64_t c = lane; c < C; c += 64) mx = fmaxf(mx, row[c]);
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-        float se = 0.f;
-        for (int64_t c = lane; c < C; c += 64) se += expf(row[c] - mx);
-        se = wave_sum(se);
-        const float lse = logf(se) + mx;
-        const int64_t t = target[r];
-        float part = 0.f;
-        for (int64_t c = lane; c < C; c += 64) {
-            const float logp = row[c] - lse;
-            const float soft = (c == t) ? on : off;
-            part -= soft * logp;
-            if (dlogits) dlogits[r * C + c] = (expf(logp) - soft) * invR;
-        }
-        local += wave_sum(part);
-    }
-    if (lane == 0) wsum[threadIdx.x >> 6] = local;
-    __syncthreads();
-    if (threadIdx.x == 0) partial[blockIdx.x] = ((wsum[0] + wsum[1]) + (wsum[2] + wsum[3])) * invR;
-}
-__global__ void smooth_ce_finish_kernel(const float* __restrict__ partial, int n, float* __restrict__ loss) {
-    float s = 0.f;
-    for (int i = threadIdx.x; i < n; i += 64) s += partial[i];
-    s = wave_sum(s);
-    if (threadIdx.x == 0) *loss = s;
-}
-
 }  // namespace
 
 // Threads per workgroup of the (row chunk, outer) kernels whose threads own COLUMNS (`for i = threadIdx.x; i < inner; i += blockDim.x`): one
@@ -687,19 +641,6 @@ extern "C" int svnet_act_bwd_f32(const float* g, const float* y, int64_t n, int 
     if (n == 0) return SVNET_OK;
     hipLaunchKernelGGL(act_bwd_kernel, dim3(svnet_grid(n, 256)), dim3(256), 0, (hipStream_t)stream, g, y, n, kind, dx);
     SVNET_CHECK_LAUNCH("act_bwd_kernel");
-    return SVNET_OK;
-}
-
-extern "C" int svnet_smooth_ce_f32(const float* logits, const int64_t* target, int64_t R, int64_t C, float eps, float* loss,
-                                   float* dlogits, float* workspace, int64_t workspace_floats, void* stream) {
-    SVNET_REQUIRE(logits && target && loss && R > 0 && C > 1, SVNET_E_ARG, "svnet_smooth_ce_f32: bad arguments");
-    hipStream_t st = (hipStream_t)stream;
-    const int blocks = svnet_grid(R * 64, 256, 1024);
-    SVNET_REQUIRE(workspace && workspace_floats >= blocks, SVNET_E_ARG, "svnet_smooth_ce_f32: workspace of 1024 floats required");
-    hipLaunchKernelGGL(smooth_ce_kernel, dim3(blocks), dim3(256), 0, st, logits, target, R, C, eps, workspace, dlogits);
-    SVNET_CHECK_LAUNCH("smooth_ce_kernel");
-    hipLaunchKernelGGL(smooth_ce_finish_kernel, dim3(1), dim3(64), 0, st, workspace, blocks, loss);
-    SVNET_CHECK_LAUNCH("smooth_ce_finish_kernel");
     return SVNET_OK;
 }
 

@@ -6,7 +6,7 @@ CosineAnnealingLR.step (:128-135,187).  Here:
 
   cal_loss          utils.py:33-50 as one HIP kernel (label-smoothed cross entropy)
   kd_loss           cal_loss blended with the distillation term against a teacher's logits, loss and gradient in ONE HIP kernel
-  kd_seg_loss       (svnet_amd/csrc/kdloss.hip); the seg form reads and writes the part-segmentation models' [B,num_part,N] where it lies
+  kd_seg_loss       (svnet_amd/csrc/loss.hip); the seg form reads and writes the part-segmentation models' [B,num_part,N] where it lies
   Distiller         a frozen teacher as a ForwardStep on the student's input buffers + the loss_fn a TrainStep takes
   TrainStep         fwd + cal_loss + bwd (+ the data-parallel gradient all-reduce) on fixed device buffers, launched eagerly or
                     replayed as ONE captured HIP graph (the step is ~200 short kernels: launch-bound when launched one by one)

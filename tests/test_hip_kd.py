@@ -1,4 +1,4 @@
-"""GPU tests (-m gpu) of the distillation loss (svnet_amd/csrc/kdloss.hip through svnet_amd.train.kd_loss / kd_seg_loss) against the
+"""GPU tests (-m gpu) of the distillation loss (svnet_amd/csrc/loss.hip through svnet_amd.train.kd_loss / kd_seg_loss) against the
 float64 restatement tests/kd_ref.py, and of a teacher run beside a student's train step (svnet_amd.train.Distiller, train_epoch).
 
 Bounds are the loss family's own (tests/test_hip_kernel_tiers.py): {L, CE, KL} at OUT_RTOL of max(|reference|, 1), dlogits at GRAD_RTOL of
@@ -144,9 +144,9 @@ def test_channel_major_kernel_matches_float64_and_the_rows_kernel(case, params, 
 @pytest.mark.parametrize("smoothing", [True, False])
 def test_alpha_zero_is_cal_loss(case, smoothing, hip_device):
     """Rows layout, alpha = 0: dlogits equal SmoothCE's bit for bit (+-0 compare equal: the KD half adds 0 * finite), whatever the teacher;
-    the loss equals cal_loss's within OUT_RTOL.  (kd_rows_kernel restates smooth_ce_kernel's row walk in its own translation unit: the
-    gradient's operations are single-rounded and identical; the loss's fused multiply-adds are the compiler's choice per kernel, so the loss
-    is not asserted bitwise.)"""
+    the loss equals cal_loss's within OUT_RTOL.  (Both are instantiations of one kernel template, smooth_ce_kernel<KD> (csrc/loss.hip),
+    and the cross entropy's operations are smooth_ce.h's in both: the gradient's are single-rounded and identical.  The loss's fused
+    multiply-adds remain the compiler's choice per instantiation, so the loss is not asserted bitwise.)"""
     from svnet_amd.train import cal_loss, kd_loss
     s, t, y = _inputs(*case)
     a, b = s.to(hip_device).requires_grad_(True), s.to(hip_device).requires_grad_(True)

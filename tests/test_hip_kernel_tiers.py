@@ -521,7 +521,7 @@ def test_edge_xyz_tiers(mode, m, hip_device):
     check(*run_edge_xyz(3, 1027, 20, m, mode, hip_device), name="edge_xyz mode=%d m=%d" % (mode, m))
 
 
-# ----------------------------------------------------------------------------- loss (csrc/pool.hip smooth_ce_kernel)
+# ----------------------------------------------------------------------------- loss (csrc/loss.hip smooth_ce_kernel<false>)
 # One wave per row, at most 1024 workgroups of 4 waves: grid-stride past 4096 rows (part-seg: 65 536).
 
 def run_smooth_ce(R, C, eps, dev):

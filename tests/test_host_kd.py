@@ -1,5 +1,5 @@
 """CPU tests of the distillation loss's host side: the float64 restatement tests/kd_ref.py against torch's kl_div, the oracle's cal_loss
-and a finite difference; the pure-host shape queries of svnet_amd/csrc/kdloss.hip; argument validation that needs no device."""
+and a finite difference; the pure-host shape queries of svnet_amd/csrc/loss.hip; argument validation that needs no device."""
 import numpy as np
 import pytest
 import torch

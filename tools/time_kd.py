@@ -1,4 +1,4 @@
-"""Times of the distillation loss on the GPU (svnet_amd.train.kd_loss / kd_seg_loss / Distiller, csrc/kdloss.hip):
+"""Times of the distillation loss on the GPU (svnet_amd.train.kd_loss / kd_seg_loss / Distiller, csrc/loss.hip):
 
   rows   kd_loss forward + backward at (R, C) = (32, 40), beside cal_loss at the same shape;
   seg    kd_seg_loss forward + backward at (B, C, N) = (32, 50, 2048), beside seg_loss forward + backward at the same shape;
