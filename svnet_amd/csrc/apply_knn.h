@@ -5,9 +5,8 @@
 // ATen's recipe and writes them transposed.  The k-NN sits on the forward's critical path (nothing else can run beside it), so its
 // preparation is done here, by the kernel that has the rows in flight: a 4-wave workgroup takes TP consecutive points of a cloud,
 // evaluates their rows exactly as the plain apply kernel does (the SAME functor: same expressions, same contraction), stores them to
-// s_out / v_out (+ the concatenation slices) AND to LDS; wave 0 then walks the LDS rows for ||x||^2 (knn_xx_walk, contiguous-row mode:
-// the feature row is cat[s, v.view(3 Ov)], sv_util.py:100) and all four waves write the channel-major table, TP consecutive points of
-// a channel per store instruction - what knn_prep_rows_kernel does, minus its read of the rows.
+// s_out / v_out (+ the concatenation slices) AND to LDS; knn_table_from_staged (knn_table.h, contiguous-row mode: the feature row is
+// cat[s, v.view(3 Ov)], sv_util.py:100) then makes ||x||^2 and the channel-major table from the LDS rows, as knn_prep_rows_kernel does.
 #pragma once
 #include "common.h"
 #include "knn_table.h"
@@ -21,7 +20,7 @@ __device__ __forceinline__ void apply_knn_tiles(const Math& m, int64_t P, int64_
                                                 float* __restrict__ v_cat, int64_t v_ld, float* __restrict__ xT, float* __restrict__ xx,
                                                 int64_t Cpad, float* staged) {
     const int C = Os + 3 * Ov, LD = C | 1;                                        // (odd row stride: a lane per row is conflict-free)
-    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = (int)threadIdx.x;
     const int64_t tiles = P / TP;                                                 // (N % TP == 0, checked on the host: a tile lies in one cloud)
     for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
         const int64_t p0 = tile * TP, b = p0 / N, n0 = p0 - b * N;
@@ -82,15 +81,7 @@ __device__ __forceinline__ void apply_knn_tiles(const Math& m, int64_t P, int64_
         }
         if (!xT) continue;                                                        // (no table asked for: the apply pass alone; uniform)
         __syncthreads();
-        if (wave == 0 && lane < TP) {
-            struct Src { const float* a; __device__ __forceinline__ float operator[](int64_t off) const { return a[off]; } } src = {staged + lane * LD};
-            struct Dst { __device__ __forceinline__ void put(int64_t, float) const {} } dst;
-            xx[p0 + lane] = knn_xx_walk(src, dst, (int64_t)C, N, n0 + lane, 1, /*xx_mode=*/1);
-        }
-        constexpr int CPI = 64 / TP;
-        const int pl = lane % TP, cl = lane / TP;
-        float* out = xT + (size_t)b * Cpad * N + n0 + pl;
-        for (int c = wave * CPI + cl; c < (int)Cpad; c += 4 * CPI) out[(size_t)c * N] = c < C ? staged[pl * LD + c] : 0.f;   // (rows past C: zeros)
+        knn_table_from_staged<TP>(staged, LD, C, Cpad, N, b, n0, p0, /*xx_mode=*/1, xT, xx);
     }
 }
 

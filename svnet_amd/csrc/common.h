@@ -62,39 +62,13 @@ static inline unsigned svnet_grid(int64_t work_items, int block, int64_t cap = 2
     return (unsigned)g;
 }
 
+// Floats per row of the fused edge block's backward message table [dn (Cs) | dve (3 Cv) | dz (9)], rounded up to whole float4s.
+template <typename T>
+__host__ __device__ inline T msg_stride(T Cs, T Cv, T Ov) { (void)Ov; return ((Cs + 3 * Cv + 9) + 3) / 4 * 4; }
+
+#include "wave.h"
+
 #ifdef __HIPCC__
-// Sums over groups of G consecutive lanes (G = 4 .. 64), every lane of a group ending up with its group's sum, WITHOUT the LDS
-// crossbar: __shfl_xor is a ds_bpermute (an LDS round trip per step, six dependent ones per sum); here the steps inside a 16-lane
-// row are DPP operand modifiers of the adds themselves and the two steps across rows are the gfx950 row / half swaps.
-template <int CTRL>
-__device__ __forceinline__ float svnet_dpp_f32(float v) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true));
-}
-template <int G>
-__device__ __forceinline__ float group_sum_dpp(float v) {
-    static_assert(G == 1 || G == 4 || G == 8 || G == 16 || G == 32 || G == 64, "group size");
-    if (G >= 4) {
-        v += svnet_dpp_f32<0xB1>(v);    // quad_perm [1,0,3,2]
-        v += svnet_dpp_f32<0x4E>(v);    // quad_perm [2,3,0,1]
-    }
-    if (G >= 8) v += svnet_dpp_f32<0x141>(v);    // row_half_mirror: the other quad of the 8
-    if (G >= 16) v += svnet_dpp_f32<0x140>(v);   // row_mirror: the other half of the row
-    if (G >= 32) {
-        const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-        v = __uint_as_float(r[0]) + __uint_as_float(r[1]);      // rows 0+1 | 0+1 | 2+3 | 2+3
-    }
-    if (G >= 64) {
-        const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-        v = __uint_as_float(r[0]) + __uint_as_float(r[1]);
-    }
-    return v;
-}
-__device__ __forceinline__ float wave_sum(float v) { return group_sum_dpp<64>(v); }
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
 // ---- grid-wide column sums without a thousand adders per address.  A reduction kernel used to end in one atomic per output per
 // workgroup onto the SAME L addresses; same-address atomics are served one after the other at the memory side (~2.5 ns each per cache
 // line, measured: 512 workgroups x 340 doubles = 12 us of a 39 us kernel, the float reductions twice that), and removing them from
@@ -124,57 +98,44 @@ __device__ __forceinline__ T svnet_slices_total(const T* buf, int L, int i) {
     return s;
 }
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-__device__ __forceinline__ int lane_id() { return (int)(threadIdx.x & 63); }
 // Single-instruction square root / reciprocal (v_sqrt_f32, v_rcp_f32: 1 ulp each) for the per-edge vector norms of the fused
 // kernels, where the correctly rounded sequences (10 instructions each) were a fifth of the instruction stream.
 __device__ __forceinline__ float fast_sqrt(float x) { return __builtin_amdgcn_sqrtf(x); }
 __device__ __forceinline__ float fast_rcp(float x) { return __builtin_amdgcn_rcpf(x); }
 
-// Value of lane (l ^ S) without the LDS crossbar: DPP modifiers inside a 16-lane row, the gfx950 row / half swaps across rows.
-template <int CTRL>
-__device__ __forceinline__ uint32_t svnet_dpp_u32(uint32_t x) {
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, CTRL, 0xF, 0xF, false);
+// Activation of the BatchNorm kernels and its derivative: act 0 = none, 1 = LeakyReLU(slope), 2 = ReLU
+__device__ __forceinline__ float act_apply(float z, int act, float slope) {
+    if (act == 1) return z > 0.f ? z : z * slope;
+    if (act == 2) return z > 0.f ? z : 0.f;
+    return z;
 }
-template <int S>
-__device__ __forceinline__ uint32_t svnet_lane_xor_u32(uint32_t x, int lane) {
-    if (S == 1) return svnet_dpp_u32<0xB1>(x);                       // quad_perm [1,0,3,2]
-    if (S == 2) return svnet_dpp_u32<0x4E>(x);                       // quad_perm [2,3,0,1]
-    if (S == 4) {                                                    // rotate the row by 4 either way, keep the one that is l ^ 4
-        const uint32_t a = svnet_dpp_u32<0x124>(x), b = svnet_dpp_u32<0x12C>(x);
-        return (lane & 4) ? a : b;
-    }
-    if (S == 8) return svnet_dpp_u32<0x128>(x);                      // row_ror:8
-    if (S == 16) {
-        const auto r = __builtin_amdgcn_permlane16_swap(x, x, false, false);
-        return (lane & 16) ? r[0] : r[1];
-    }
-    const auto r = __builtin_amdgcn_permlane32_swap(x, x, false, false);
-    return (lane & 32) ? r[0] : r[1];
+__device__ __forceinline__ float act_grad(float z, int act, float slope) {
+    if (act == 1) return z > 0.f ? 1.f : slope;
+    if (act == 2) return z > 0.f ? 1.f : 0.f;
+    return 1.f;
 }
-// 32 x 32 bit-matrix transpose across 32 consecutive lanes (both halves of the wave at once): lane r of a half holds row r
-// (bit b = element [r][b]); afterwards lane b holds column b (bit r = element [r][b]).  Five butterfly stages of ~7 instructions
-// (swap the off-diagonal J x J blocks of every 2J x 2J block) instead of 32 ballots + selects.
-template <int J>
-__device__ __forceinline__ uint32_t svnet_bt_stage(uint32_t x, int lane) {
-    constexpr uint32_t MLO = J == 16 ? 0x0000FFFFu : J == 8 ? 0x00FF00FFu : J == 4 ? 0x0F0F0F0Fu : J == 2 ? 0x33333333u : 0x55555555u;
-    const uint32_t p = svnet_lane_xor_u32<J>(x, lane);
-    const bool lower = (lane & J) != 0;
-    const uint32_t keep = lower ? (x & ~MLO) : (x & MLO);
-    const uint32_t take = lower ? ((p >> J) & MLO) : ((p & MLO) << J);
-    return keep | take;
+
+// Ternary dot product of two bit-plane words (sign plane s, non-zero plane z; 64 or 32 bits wide) of the fused edge block.
+__device__ __forceinline__ int popcw(uint64_t x) { return __popcll(x); }
+__device__ __forceinline__ int popcw(uint32_t x) { return __popc(x); }
+template <typename W>
+__device__ __forceinline__ int tdot(W xs, W xz, W ws, W wz) {
+    const W m = xz & wz;
+    return popcw(m) - 2 * popcw(m & (xs ^ ws));
 }
-__device__ __forceinline__ uint32_t svnet_bit_transpose32(uint32_t x, int lane) {
-    x = svnet_bt_stage<16>(x, lane);
-    x = svnet_bt_stage<8>(x, lane);
-    x = svnet_bt_stage<4>(x, lane);
-    x = svnet_bt_stage<2>(x, lane);
-    return svnet_bt_stage<1>(x, lane);
+// The same product as two running popcounts, pm += popc(m), pd += popc(m & (xs ^ ws)): v_bcnt_u32_b32 adds into its third operand
+// for free, so a row of words costs one "pm - 2*pd" instead of a subtract-and-add per word.
+template <typename W>
+__device__ __forceinline__ void tacc(W xs, W xz, W ws, W wz, int& pm, int& pd) {
+    const W m = xz & wz;
+    pm += popcw(m);
+    pd += popcw(m & (xs ^ ws));
 }
+// DENSE weights (no exact zero in W1: *w_dense, set by svnet_edgeblock_prepare_f32): the mask of a product is the edge's own non-zero plane,
+// so popc(m) is ONE wave-uniform count per edge (scalar unit) and a word costs xor + and + bcnt instead of and + bcnt + xor + and + bcnt:
+// 40 % fewer instructions in the half of the kernel that is popcounts.  Same integer, bit for bit.
+template <typename W>
+__device__ __forceinline__ void tacc_dense(W xs, W xz, W ws, int& pd) { pd += popcw(xz & (xs ^ ws)); }
 
 // A float at wave-uniform `base` + per-lane BYTE offset, loaded with the SGPR-base addressing mode (global_load v, voff, s[base]).
 // The empty asm keeps the 32->64-bit extension of the lane offset next to the load: once it is hoisted out of a loop, instruction

@@ -31,11 +31,6 @@ namespace {
 constexpr float VEPS = 1e-6f;
 constexpr int NW = 5;  // ternary words per edge row in fused bit order
 
-__device__ __forceinline__ int tdot(uint64_t xs, uint64_t xz, uint64_t ws, uint64_t wz) {
-    const uint64_t m = xz & wz;
-    return __popcll(m) - 2 * __popcll(m & (xs ^ ws));
-}
-
 // feature index of (word, bit) in the reference's K1 ordering [s_j-s_i (Cs) | s_i (Cs) | s_v (2Cv x 3)], or -1
 __device__ __forceinline__ int fused_feature(int w, int b, int Cs, int Cv) {
     if (w == 0) return b < Cs ? b : -1;
@@ -69,29 +64,6 @@ struct FwdArgs {
 };
 
 // OP = scalar outputs per lane (Os <= 64*OP)
-__device__ __forceinline__ int tdot(uint32_t xs, uint32_t xz, uint32_t ws, uint32_t wz) {
-    const uint32_t m = xz & wz;
-    return __popc(m) - 2 * __popc(m & (xs ^ ws));
-}
-// The same product as two running popcounts, pm += popc(m), pd += popc(m & (xs ^ ws)): v_bcnt_u32_b32 adds into its third operand
-// for free, so a row of words costs one "pm - 2*pd" instead of a subtract-and-add per word.
-__device__ __forceinline__ void tacc(uint64_t xs, uint64_t xz, uint64_t ws, uint64_t wz, int& pm, int& pd) {
-    const uint64_t m = xz & wz;
-    pm += __popcll(m);
-    pd += __popcll(m & (xs ^ ws));
-}
-__device__ __forceinline__ void tacc(uint32_t xs, uint32_t xz, uint32_t ws, uint32_t wz, int& pm, int& pd) {
-    const uint32_t m = xz & wz;
-    pm += __popc(m);
-    pd += __popc(m & (xs ^ ws));
-}
-
-// DENSE weights (no exact zero in W1: *w_dense, set by svnet_edgeblock_prepare_f32): the mask of a product is the edge's own non-zero plane,
-// so popc(m) is ONE wave-uniform count per edge (scalar unit) and a word costs xor + and + bcnt instead of and + bcnt + xor + and + bcnt:
-// 40 % fewer instructions in the half of the kernel that is popcounts.  Same integer, bit for bit.
-__device__ __forceinline__ void tacc_dense(uint64_t xs, uint64_t xz, uint64_t ws, int& pd) { pd += __popcll(xz & (xs ^ ws)); }
-__device__ __forceinline__ void tacc_dense(uint32_t xs, uint32_t xz, uint32_t ws, int& pd) { pd += __popc(xz & (xs ^ ws)); }
-
 __device__ __forceinline__ bool edge_weights_dense(const uint32_t* __restrict__ w_dense) {      // (wave-uniform: a scalar load)
     return w_dense && *w_dense == 1u;
 }
@@ -375,12 +347,6 @@ __global__ __launch_bounds__(256, (OP == 1 ? 4 : 3)) void edgeblock_fwd_kernel(F
 // once per point (arg-max / arg-min with the lower slot winning ties, sums added).  Lane l of either half owns the output channels
 // l + 32*q (q < OP2), the scalar channel l, the vector channel l and the v2s channel l.  Same arithmetic per edge as the kernel
 // above (bit-identical results).
-__device__ __forceinline__ uint32_t half_swap_u32(uint32_t x) {      // value held by lane (l ^ 32)
-    const auto r = __builtin_amdgcn_permlane32_swap(x, x, false, false);
-    return (threadIdx.x & 32) ? r[0] : r[1];
-}
-__device__ __forceinline__ float half_swap_f32(float x) { return __uint_as_float(half_swap_u32(__float_as_uint(x))); }
-
 template <int OP2, bool DENSE>
 __device__ __forceinline__ void edgeblock_fwd2_body(const FwdArgs& fa) {
     const svnet_edgeblock_desc& d = fa.d;
@@ -579,9 +545,9 @@ __device__ __forceinline__ void edgeblock_fwd2_body(const FwdArgs& fa) {
         const float invk = 1.f / (float)k;
 #pragma unroll
         for (int q = 0; q < OP2; ++q) {
-            const int on = (int)half_swap_u32((uint32_t)nmax[q]), os = (int)half_swap_u32((uint32_t)smax[q]);
+            const int on = (int)lane_half_swap((uint32_t)nmax[q]), os = (int)lane_half_swap((uint32_t)smax[q]);
             if (on > nmax[q] || (on == nmax[q] && os < smax[q])) { nmax[q] = on; smax[q] = os; }
-            const int un = (int)half_swap_u32((uint32_t)nmin[q]), us = (int)half_swap_u32((uint32_t)smin[q]);
+            const int un = (int)lane_half_swap((uint32_t)nmin[q]), us = (int)lane_half_swap((uint32_t)smin[q]);
             if (un < nmin[q] || (un == nmin[q] && us < smin[q])) { nmin[q] = un; smin[q] = us; }
             const int o = l + 32 * q;
             if (!hi && o < Os) {
@@ -593,7 +559,7 @@ __device__ __forceinline__ void edgeblock_fwd2_body(const FwdArgs& fa) {
         }
 #pragma unroll
         for (int dd = 0; dd < 3; ++dd) {
-            const float a = av[dd] + half_swap_f32(av[dd]), an = avn[dd] + half_swap_f32(avn[dd]);
+            const float a = av[dd] + lane_half_swap(av[dd]), an = avn[dd] + lane_half_swap(avn[dd]);
             if (!hi && o_lane) {
                 d.mv[(gp * 3 + dd) * Ov + l] = a * invk;
                 d.mvn[(gp * 3 + dd) * Ov + l] = an * invk;
@@ -715,7 +681,7 @@ struct EdgeApplyMath {
     __device__ __forceinline__ float s(int64_t p, int o) const {
         const float a = A1[o];
         const float y = a * (float)(a >= 0.f ? n_max[p * Os + o] : n_min[p * Os + o]) + B1[o];
-        return y > 0.f ? y : y * slope;
+        return act_apply(y, 1, slope);
     }
     __device__ __forceinline__ float v(int64_t p, int64_t b, int q, int c) const {
         const int64_t e = p * 3 * Ov + q;

@@ -19,6 +19,7 @@
 // writes (4 B + 0.25 B per edge-channel instead of the 4 B fp32 input the layer-wise path keeps).
 #include <stdlib.h>
 
+#include "bf16_split.h"
 #include "common.h"
 #include "gate_mlp.h"
 #include "prelude.h"
@@ -48,7 +49,6 @@ namespace {
 #define PHASE_FLUSH() do { } while (0)
 #endif
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 
 // bf16 pieces of dL/dn that phase B of the tile kernel multiplies: 3 = the exact split (fp32-exact products); 2 = hi + mid only (a relative
@@ -65,57 +65,9 @@ constexpr int TE = 32;             // edges per tile
 // the stride is odd, so row-wise and column-wise walks are both free of bank conflicts.
 __host__ __device__ __forceinline__ int dx_stride(int Cs, int Cv) { return (2 * Cs + 6 * Cv) | 1; }
 
-__device__ __forceinline__ int tdot(uint64_t xs, uint64_t xz, uint64_t ws, uint64_t wz) {
-    const uint64_t m = xz & wz;
-    return __popcll(m) - 2 * __popcll(m & (xs ^ ws));
-}
-__device__ __forceinline__ __bf16 bf16_from_bits(uint32_t b) { return __builtin_bit_cast(__bf16, (unsigned short)b); }
-
-__device__ __forceinline__ void split3_frag(const float (&x)[8], bf16x8& fh, bf16x8& fm, bf16x8& fl) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const uint32_t hu = __float_as_uint(x[j]) & 0xFFFF0000u;
-        const float r1 = x[j] - __uint_as_float(hu);
-        const uint32_t mu = __float_as_uint(r1) & 0xFFFF0000u;
-        const float r2 = r1 - __uint_as_float(mu);
-        fh[j] = bf16_from_bits(hu >> 16);
-        fm[j] = bf16_from_bits(mu >> 16);
-        fl[j] = bf16_from_bits(__float_as_uint(r2) >> 16);
-    }
-}
-
-// The same exact split for a pair of values, packed as two bf16 per word (low half = a): the phase-A producer of the tile kernel
-// splits each dL/dn once and leaves the three bf16 planes in LDS (the four waves of phase B used to split the same 32 x Os tile
-// four times over, 40 VALU instructions per k-step and wave).
-__device__ __forceinline__ void split3_pair(float a, float b, uint32_t& h, uint32_t& m, uint32_t& l) {
-    const float a1 = a - __uint_as_float(__float_as_uint(a) & 0xFFFF0000u), b1 = b - __uint_as_float(__float_as_uint(b) & 0xFFFF0000u);
-    const float a2 = a1 - __uint_as_float(__float_as_uint(a1) & 0xFFFF0000u), b2 = b1 - __uint_as_float(__float_as_uint(b1) & 0xFFFF0000u);
-    h = __builtin_amdgcn_perm(__float_as_uint(b), __float_as_uint(a), 0x07060302u);      // upper halves of (a, b)
-    m = __builtin_amdgcn_perm(__float_as_uint(b1), __float_as_uint(a1), 0x07060302u);
-    l = __builtin_amdgcn_perm(__float_as_uint(b2), __float_as_uint(a2), 0x07060302u);
-}
 // bf16 elements per row of the dL/dn planes in LDS: 16 bytes of padding put consecutive rows 4 banks apart (16-byte fragment reads)
 __host__ __device__ __forceinline__ int dn_stride(int Os) { return Os + 8; }
 
-// ---- cross-lane sums without the LDS crossbar (DPP modifiers + the gfx950 half / row swaps)
-// (bound_ctrl for the controls that read a valid lane everywhere: the `old` operand is then dead and the DPP read folds into
-//  the consuming add instead of costing a v_mov for `old` plus a v_mov_dpp)
-template <int CTRL, int ROW_MASK = 0xF>
-__device__ __forceinline__ float dpp_get(float v) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, ROW_MASK, 0xF, ROW_MASK == 0xF));
-}
-constexpr int DPP_QUAD_1032 = 0xB1, DPP_QUAD_2301 = 0x4E, DPP_ROW_ROR8 = 0x128, DPP_ROW_MIRROR = 0x140, DPP_ROW_HALF_MIRROR = 0x141,
-              DPP_ROW_BCAST15 = 0x142, DPP_ROW_BCAST31 = 0x143;
-// sum over the wave of a (lanes 0..31 of the result) and of b (lanes 32..63), each still spread over its 32 lanes
-__device__ __forceinline__ float fold32(float a, float b) {
-    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(b), false, false);
-    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-// rows (16 lanes) 0..3 of the result: a.row0+a.row1 | b.row0+b.row1 | a.row2+a.row3 | b.row2+b.row3
-__device__ __forceinline__ float fold16(float a, float b) {
-    const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(a), __float_as_uint(b), false, false);
-    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
 // index of the n-th (0-based) set bit among the low 10 bits of mask, or -1
 __device__ __forceinline__ int nth_set_bit10(uint32_t mask, int n) {
     int res = -1;
@@ -127,34 +79,6 @@ __device__ __forceinline__ int nth_set_bit10(uint32_t mask, int n) {
     }
     return res;
 }
-// value held by lane (l ^ 32)
-__device__ __forceinline__ uint32_t lane_half_swap(uint32_t x) {
-    const auto r = __builtin_amdgcn_permlane32_swap(x, x, false, false);
-    return (threadIdx.x & 32) ? r[0] : r[1];
-}
-// Eight wave-wide sums in 18 VALU instructions: every lane of the 8-lane group g = lane >> 3 ends up with the sum over the
-// wave of s[bitreverse3(g)]  (groups 0..7 hold s0, s4, s2, s6, s1, s5, s3, s7).
-__device__ __forceinline__ float wave_sum8_packed(const float (&s)[8], int lane) {
-    const float x0 = fold16(fold32(s[0], s[1]), fold32(s[2], s[3]));   // rows: s0 | s2 | s1 | s3
-    const float x1 = fold16(fold32(s[4], s[5]), fold32(s[6], s[7]));   // rows: s4 | s6 | s5 | s7
-    const bool hi = (lane & 8) != 0;
-    float y = (hi ? x1 : x0) + dpp_get<DPP_ROW_ROR8>(hi ? x0 : x1);
-    y += dpp_get<DPP_QUAD_1032>(y);
-    y += dpp_get<DPP_QUAD_2301>(y);
-    y += dpp_get<DPP_ROW_HALF_MIRROR>(y);
-    return y;
-}
-// wave-wide sum, valid in lane 63
-__device__ __forceinline__ float wave_sum_last(float v) {
-    v += dpp_get<DPP_QUAD_1032>(v);
-    v += dpp_get<DPP_QUAD_2301>(v);
-    v += dpp_get<DPP_ROW_HALF_MIRROR>(v);
-    v += dpp_get<DPP_ROW_MIRROR>(v);
-    v += dpp_get<DPP_ROW_BCAST15, 0xA>(v);
-    v += dpp_get<DPP_ROW_BCAST31, 0xC>(v);
-    return v;
-}
-
 // sign(W1) in fused column order as bf16, in MFMA B-FRAGMENT order: [column tile ct (10)][k-step ks (ceil(Os/16))][lane (64)][8],
 // lane = h*32 + r holding column ct*32 + r, outputs o = ks*16 + 8h .. +7 (zero past Os).  A wave's fragment load is then 1 KiB
 // contiguous (8 cache lines); with the plain [column][o] table every lane pair sat on its own line - 32 lines per load instruction,
@@ -256,7 +180,6 @@ __global__ void edgeblock_bwd_coeffs_kernel(const float* __restrict__ red, const
     }
 }
 
-__device__ __forceinline__ int msg_stride(int Cs, int Cv, int Ov) { (void)Ov; return ((Cs + 3 * Cv + 9) + 3) / 4 * 4; }   // = svnet_edgeblock_msg_stride
 
 // ---------------------------------------------------------------------------------------------- vector path
 // dL/dv' of every edge (v' = U_j - U_i + T_i, out = gate * mean_k v'*(Av + Bv/n'), n' = |v'| + eps):
@@ -792,7 +715,7 @@ __global__ __launch_bounds__(256, 4) void edgeblock_bwd_kernel(svnet_edgeblock_b
                     if (in_use) dxl[row * DXS + ccol] = v;
                     csum += v;
                 }
-                const float other = __uint_as_float(lane_half_swap(__float_as_uint(csum)));
+                const float other = lane_half_swap(csum);
                 if (h == 0 && in_use) { const float t = csum + other; if (t != 0.f) ATOMIC_ADD(&d.dbeta_perm[(tile_lin & (SVNET_DBETA_SLICES - 1)) * NCOL + col], t); }
             }
         }
@@ -898,8 +821,8 @@ __global__ __launch_bounds__(256, 4) void edgeblock_bwd_kernel(svnet_edgeblock_b
                 const bool con = c < Cv;
                 const int cc = min(c, Cv - 1);
                 const float gd = (con && valid) ? gmine[cc] : 0.f, gc = (con && valid) ? gmine[Cv + cc] : 0.f;
-                const float gd0 = dpp_get<QB0>(gd), gd1 = dpp_get<QB1>(gd), gd2 = dpp_get<QB2>(gd);
-                const float gc0 = dpp_get<QB0>(gc), gc1 = dpp_get<QB1>(gc), gc2 = dpp_get<QB2>(gc);
+                const float gd0 = svnet_dpp_f32<QB0>(gd), gd1 = svnet_dpp_f32<QB1>(gd), gd2 = svnet_dpp_f32<QB2>(gd);
+                const float gc0 = svnet_dpp_f32<QB0>(gc), gc1 = svnet_dpp_f32<QB1>(gc), gc2 = svnet_dpp_f32<QB2>(gc);
                 const float ved = vjl[cc] - vi[i], vec = vi[i];
                 const float dved = gd0 * z0 + gd1 * z1 + gd2 * z2;                          // dL/dve of the difference channel -> the neighbour
                 const float dvc = (gc0 - gd0) * z0 + (gc1 - gd1) * z1 + (gc2 - gd2) * z2;   // centre: dve[Cv + c] - dve[c]
@@ -907,7 +830,7 @@ __global__ __launch_bounds__(256, 4) void edgeblock_bwd_kernel(svnet_edgeblock_b
                 if (q < 3 && con) { gmine[c] = dved; gmine[Cv + c] = dvc; }
             }
             constexpr int DPP_ROW_SHR4 = 0x114;                    // the two channel halves of an edge sit 4 lanes apart: the upper one collects
-            dz0 += dpp_get<DPP_ROW_SHR4>(dz0); dz1 += dpp_get<DPP_ROW_SHR4>(dz1); dz2 += dpp_get<DPP_ROW_SHR4>(dz2);
+            dz0 += svnet_dpp_f32<DPP_ROW_SHR4>(dz0); dz1 += svnet_dpp_f32<DPP_ROW_SHR4>(dz1); dz2 += svnet_dpp_f32<DPP_ROW_SHR4>(dz2);
             if (ch == 1 && q < 3) { zs[r * 9 + q * 3 + 0] = dz0; zs[r * 9 + q * 3 + 1] = dz1; zs[r * 9 + q * 3 + 2] = dz2; }
         }
         PHASE_MARK(9);   // phase C passes 2 + 3

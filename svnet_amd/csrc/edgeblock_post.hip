@@ -409,7 +409,7 @@ extern "C" int svnet_edgeblock_bwd_gather_f32(const float* msg, const int32_t* r
     SVNET_REQUIRE(acat_ld >= 2 * Ov + 6, SVNET_E_ARG, "svnet_edgeblock_bwd_gather_f32: acat_ld < 2*Ov + 6");
     SVNET_REQUIRE(Cs > 0 && Cs <= 64 && Cv > 0 && 2 * Cv <= 64 && Ov > 0 && Ov <= 64, SVNET_E_UNSUPPORTED,
                   "svnet_edgeblock_bwd_gather_f32: needs Cs <= 64, 2*Cv <= 64, Ov <= 64");
-    const int R = (int)svnet_edgeblock_msg_stride(Cs, Cv, Ov);
+    const int R = msg_stride(Cs, Cv, Ov);
     const int nch = (R + 63) / 64;
     const unsigned grid = (unsigned)svnet_cdiv(P, 4);
     const int bpc = ((P / N) % 8 == 0 && N % 4 == 0) ? (int)(N / 4) : 0;   // clouds in groups of 8, whole workgroups per cloud
@@ -440,4 +440,4 @@ extern "C" int svnet_edgeblock_bwd_gather_f32(const float* msg, const int32_t* r
     return SVNET_OK;
 }
 
-extern "C" int64_t svnet_edgeblock_msg_stride(int64_t Cs, int64_t Cv, int64_t Ov) { (void)Ov; return ((Cs + 3 * Cv + 9) + 3) / 4 * 4; }
+extern "C" int64_t svnet_edgeblock_msg_stride(int64_t Cs, int64_t Cv, int64_t Ov) { return msg_stride(Cs, Cv, Ov); }

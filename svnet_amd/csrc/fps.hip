@@ -13,7 +13,7 @@
 // registers for the whole loop; the loop is npoint DEPENDENT iterations, so the workgroup is sized for the shortest iteration, not for
 // occupancy.  One iteration: (1) the new centroid's three coordinates, read at a wave-uniform address from the cloud's copy in LDS
 // (tiers 0-3) or from global memory (tier 4: 16384 x 12 B do not fit); (2) PPL updates of mind and the lane's best (value, j);
-// (3) an argmax butterfly over the wave (DPP / row swaps, svnet_lane_xor_u32: no LDS); (4) lane 0 of every wave puts the wave's best
+// (3) an argmax butterfly over the wave (argmax_group, wave.h: no LDS); (4) lane 0 of every wave puts the wave's best
 // into one of TWO sets of LDS slots, ONE barrier, every wave reads the W slots (lane l reads slot l % W) and runs the butterfly over
 // them.  Writing set i & 1 in iteration i needs no second barrier: whoever writes set b again in iteration i + 2 has passed the
 // barrier of iteration i + 1, which every thread reaches only after its read of iteration i.
@@ -32,25 +32,6 @@ constexpr float FPS_PAD = -1.f;
 constexpr int FPS_TIERS = 5;
 constexpr int FPS_THREADS[FPS_TIERS] = {64, 256, 1024, 1024, 1024};
 constexpr int FPS_PPL[FPS_TIERS] = {1, 4, 4, 10, 16};
-
-template <int S>
-__device__ __forceinline__ void argmax_step(float& v, int& i, int lane) {
-    const float ov = __uint_as_float(svnet_lane_xor_u32<S>(__float_as_uint(v), lane));
-    const int oi = (int)svnet_lane_xor_u32<S>((uint32_t)i, lane);
-    const bool take = (ov > v) | ((ov == v) & (oi < i));        // (bitwise: selects, not branches)
-    v = take ? ov : v;
-    i = take ? oi : i;
-}
-// (value, index) of the best pair among groups of G consecutive lanes, in every lane of the group; the lower index wins equal values
-template <int G>
-__device__ __forceinline__ void argmax_group(float& v, int& i, int lane) {
-    if (G >= 2) argmax_step<1>(v, i, lane);
-    if (G >= 4) argmax_step<2>(v, i, lane);
-    if (G >= 8) argmax_step<4>(v, i, lane);
-    if (G >= 16) argmax_step<8>(v, i, lane);
-    if (G >= 32) argmax_step<16>(v, i, lane);
-    if (G >= 64) argmax_step<32>(v, i, lane);
-}
 
 struct FpsSlot { float v; int i; };
 

@@ -16,41 +16,12 @@
 // Bit-plane layout ("row-sliced", written by binlinear_fwd): word [(m >> 6) * K + k] holds bit (m & 63) of rows
 // 64*(m>>6) .. +63 for column k — one coalesced u64 per lane gives a column's bits for 64 consecutive rows, which
 // is exactly what the k(=m)-strided MFMA operand and the per-column epilogue mask need.
+#include "bf16_split.h"
 #include "common.h"
 
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
-
-__device__ __forceinline__ __bf16 bf16_from_bits(uint32_t b) { return __builtin_bit_cast(__bf16, (unsigned short)b); }
-
-struct Split3 {
-    bf16x8 h, m, l;
-};
-
-__device__ __forceinline__ void split3(float x, uint32_t& h, uint32_t& m, uint32_t& l) {
-    const uint32_t hu = __float_as_uint(x) & 0xFFFF0000u;
-    const float r1 = x - __uint_as_float(hu);  // exact
-    const uint32_t mu = __float_as_uint(r1) & 0xFFFF0000u;
-    const float r2 = r1 - __uint_as_float(mu);  // exact, <= 8 significant bits
-    h = hu >> 16;
-    m = mu >> 16;
-    l = __float_as_uint(r2) >> 16;
-}
-
-__device__ __forceinline__ Split3 split_frag(const float (&x)[8]) {
-    Split3 s;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        uint32_t h, m, l;
-        split3(x[j], h, m, l);
-        s.h[j] = bf16_from_bits(h);
-        s.m[j] = bf16_from_bits(m);
-        s.l[j] = bf16_from_bits(l);
-    }
-    return s;
-}
 
 #define MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16((a), (b), (c), 0, 0, 0)
 // Diagnostic builds only (-DSVNET_ROWS_ABLATE=n, results WRONG): 1 no C stores, 2 no A loads, 3 no B staging loads, 4 no MFMAs

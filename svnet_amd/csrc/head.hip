@@ -21,12 +21,6 @@ namespace {
 
 constexpr int MROWS = 64;          // most rows these kernels take (lane = row)
 
-__device__ __forceinline__ float head_act_grad(float z, int act, float slope) {
-    if (act == 1) return z > 0.f ? 1.f : slope;
-    if (act == 2) return z > 0.f ? 1.f : 0.f;
-    return 1.f;
-}
-
 // ---------------------------------------------------------------------------------------------- pack
 // One wave per 64-column word: lane = column.  Row-major words by ballots (lane 0 stores), column words by shifting the lane's
 // own bit of every row into place.
@@ -137,9 +131,7 @@ __global__ __launch_bounds__(256) void binhead_fwd_kernel(HeadFwdArgs a) {
         is = 1.f / sqrtf(a.rvar[o] + a.eps);
     }
     if (lane == 0) { a.mean[o] = mu; a.invstd[o] = is; }
-    float z = (yv - mu) * is * a.gamma[o] + a.bn_beta[o];
-    if (a.act == 1) z = z > 0.f ? z : z * a.slope;
-    else if (a.act == 2) z = z > 0.f ? z : 0.f;
+    const float z = act_apply((yv - mu) * is * a.gamma[o] + a.bn_beta[o], a.act, a.slope);
     if (row) {
         a.y[(int64_t)m * a.O + o] = yv;
         a.out[(int64_t)m * a.O + o] = z;
@@ -166,7 +158,7 @@ __global__ __launch_bounds__(256) void binhead_bwd_w_kernel(HeadBwdArgs a) {
     const float yv = a.y[(int64_t)mc * a.O + o], gv = row ? a.g[(int64_t)mc * a.O + o] : 0.f;
     const float mu = a.mean[o], is = a.invstd[o], ga = a.gamma[o], be = a.bn_beta[o], sc = a.scale[o];
     const float xh = (yv - mu) * is;
-    const float gp = row ? gv * head_act_grad(xh * ga + be, a.act, a.slope) : 0.f;
+    const float gp = row ? gv * act_grad(xh * ga + be, a.act, a.slope) : 0.f;
     const float r0 = (float)wave_sum((double)gp), r1 = (float)wave_sum((double)gp * (double)xh);
     float dy = gp;
     if (a.training) dy -= (r0 + xh * r1) * (1.f / (float)M);

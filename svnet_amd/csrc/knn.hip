@@ -81,7 +81,7 @@ __global__ __launch_bounds__(256) void knn_prep_rows_kernel(const float* __restr
                                                             const float* __restrict__ x2, int64_t split, int64_t Cpad) {
     extern __shared__ float staged[];                                             // [TP][C | 1]
     const int LD = (int)C | 1;
-    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = (int)threadIdx.x;
     const int64_t tiles = B * N / TP;
     const int cut = (int)(x2 ? split : C);
     for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
@@ -105,20 +105,12 @@ __global__ __launch_bounds__(256) void knn_prep_rows_kernel(const float* __restr
         }
         __syncthreads();
         const int64_t b = p0 / N, n0 = p0 - b * N;
-        if (wave == 0 && lane < TP) {
-            struct Src { const float* a; __device__ __forceinline__ float operator[](int64_t off) const { return a[off]; } } src = {staged + lane * LD};
-            struct Dst { __device__ __forceinline__ void put(int64_t, float) const {} } dst;
-            xx[p0 + lane] = knn_xx_walk(src, dst, C, N, n0 + lane, 1, xx_mode);
-        }
-        // the channel-major table: TP consecutive points of a channel per store instruction (64 / TP channels per wave and instruction)
-        constexpr int CPI = 64 / TP;
-        const int pl = lane % TP, cl = lane / TP;
-        float* out = xT + (size_t)b * Cpad * N + n0 + pl;
-        for (int c = wave * CPI + cl; c < (int)Cpad; c += 4 * CPI) out[(size_t)c * N] = c < (int)C ? staged[pl * LD + c] : 0.f;   // (rows past C: zeros)
+        knn_table_from_staged<TP>(staged, LD, C, Cpad, N, b, n0, p0, xx_mode, xT, xx);
     }
 }
 
-// (value, index) arg-max across the wave; larger value wins, equal values -> smaller index.
+// (value, index) arg-max across the wave; larger value wins, equal values -> smaller index.  Not argmax_group<64> (wave.h), and its
+// own short-circuit comparison: either change alters the fp32 compares of the streamed kernels and costs knn_main<64, 2> instructions.
 __device__ __forceinline__ void wave_argmax(float& v, int& j) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
@@ -130,81 +122,25 @@ __device__ __forceinline__ void wave_argmax(float& v, int& j) {
     }
 }
 
-// "a ranks before b": larger value first, equal values -> smaller index first
-__device__ __forceinline__ bool ranks_before(float va, int ja, float vb, int jb) { return (va > vb) || (va == vb && ja < jb); }
-
-// Value of lane (l ^ S) without the LDS crossbar: DPP modifiers inside a 16-lane row, the gfx950 row / half swaps across rows
-// (a bitonic sort is a chain of 21 dependent exchanges, so the ~100-cycle ds_bpermute round trip was its whole cost).
-template <int CTRL>
-__device__ __forceinline__ uint32_t dpp_u32(uint32_t x) {
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, CTRL, 0xF, 0xF, true);      // (every lane has a source: bound_ctrl only spares the v_mov of "old")
-}
-template <int S>
-__device__ __forceinline__ uint32_t lane_xor_u32(uint32_t x, int lane) {
-    if (S == 1) return dpp_u32<0xB1>(x);                       // quad_perm [1,0,3,2]
-    if (S == 2) return dpp_u32<0x4E>(x);                       // quad_perm [2,3,0,1]
-    if (S == 4) {                                              // rotate the row by 4 either way, keep the one that is l ^ 4
-        const uint32_t a = dpp_u32<0x124>(x), b = dpp_u32<0x12C>(x);   // row_ror:4 reads lane l-4, row_ror:12 reads lane l+4 (mod 16)
-        return (lane & 4) ? a : b;
-    }
-    if (S == 8) return dpp_u32<0x128>(x);                      // row_ror:8
-    if (S == 16) {
-        const auto r = __builtin_amdgcn_permlane16_swap(x, x, false, false);
-        return (lane & 16) ? r[0] : r[1];
-    }
-    const auto r = __builtin_amdgcn_permlane32_swap(x, x, false, false);
-    return (lane & 32) ? r[0] : r[1];
-}
-
-// Bitonic sort of one (value, index) pair per lane across the wave; afterwards lane 0 holds the best pair, lane 63 the worst.
-template <int K2, int S2>
-__device__ __forceinline__ void sort_step(float& v, int& j, int lane) {
-    const float ov = __uint_as_float(lane_xor_u32<S2>(__float_as_uint(v), lane));
-    const int oj = (int)lane_xor_u32<S2>((uint32_t)j, lane);
-    const bool desc = (lane & K2) == 0 || K2 == 64;   // final merge: whole wave descending
-    const bool lower = (lane & S2) == 0;
-    const bool other_first = (ov > v) || (ov == v && oj < j);
-    // in a descending block the lower lane keeps the pair that ranks first, the upper lane the other one
-    const bool take = (lower == desc) ? other_first : !other_first;
-    v = take ? ov : v;
-    j = take ? oj : j;
-}
-__device__ __forceinline__ void wave_sort_desc(float& v, int& j, int lane) {
-    sort_step<2, 1>(v, j, lane);
-    sort_step<4, 2>(v, j, lane); sort_step<4, 1>(v, j, lane);
-    sort_step<8, 4>(v, j, lane); sort_step<8, 2>(v, j, lane); sort_step<8, 1>(v, j, lane);
-    sort_step<16, 8>(v, j, lane); sort_step<16, 4>(v, j, lane); sort_step<16, 2>(v, j, lane); sort_step<16, 1>(v, j, lane);
-    sort_step<32, 16>(v, j, lane); sort_step<32, 8>(v, j, lane); sort_step<32, 4>(v, j, lane); sort_step<32, 2>(v, j, lane);
-    sort_step<32, 1>(v, j, lane);
-    sort_step<64, 32>(v, j, lane); sort_step<64, 16>(v, j, lane); sort_step<64, 8>(v, j, lane); sort_step<64, 4>(v, j, lane);
-    sort_step<64, 2>(v, j, lane); sort_step<64, 1>(v, j, lane);
-}
-// The same two sorts on integer keys.  ord_key() maps a float to a uint32 whose unsigned order is the float order (-0 is first
-// made +0, so equal floats have equal keys); a (value, index) pair becomes the 64-bit composite (ord_key(value) << 32) | ~index,
-// whose unsigned order is "larger value first, equal values: smaller index first".  One exchange step is then two DPP moves, ONE
-// 64-bit compare, an exclusive-or with a lane pattern that depends on the step only, and two selects - the float version's
-// three compares and their and / or / select went through the scalar unit (800 of its 1 100 instructions per four queries), which
-// the CU's four SIMDs share.  Rankings are identical (no NaNs: distances of finite points).
-__device__ __forceinline__ uint32_t ord_key(float v) {
-    const uint32_t u = __float_as_uint(v + 0.f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float ord_val(uint32_t key) {
-    return __uint_as_float((key & 0x80000000u) ? (key & 0x7FFFFFFFu) : ~key);
-}
+// Bitonic sorts across the wave on integer keys; afterwards lane 0 holds the first-ranked entry, lane 63 the last.  A (value, index)
+// pair is the 64-bit composite (ord_key(value) << 32) | ~index (wave.h), whose unsigned order is "larger value first, equal values:
+// smaller index first".  One exchange step is two DPP moves, ONE 64-bit compare, an exclusive-or with a lane pattern that depends on
+// the step only, and two selects - a float (value, index) sort's three compares and their and / or / select went through the scalar
+// unit (800 of its 1 100 instructions per four queries), which the CU's four SIMDs share.  Rankings are identical (no NaNs: distances
+// of finite points).
 template <int K2, int S2>
 __device__ __forceinline__ bool sort_flip(int lane) {   // lower lane of a descending block / upper lane of an ascending one keeps the first-ranked
     return (((lane & K2) == 0 || K2 == 64) != ((lane & S2) == 0));
 }
 template <int K2, int S2>
 __device__ __forceinline__ void sort_step_key(uint32_t& key, int lane) {
-    const uint32_t ok = lane_xor_u32<S2>(key, lane);
+    const uint32_t ok = svnet_lane_xor_u32<S2>(key, lane);
     const bool take = (ok > key) != sort_flip<K2, S2>(lane);
     key = take ? ok : key;
 }
 template <int K2, int S2>
 __device__ __forceinline__ void sort_step_pair(uint32_t& hi, uint32_t& lo, int lane) {
-    const uint32_t ohi = lane_xor_u32<S2>(hi, lane), olo = lane_xor_u32<S2>(lo, lane);
+    const uint32_t ohi = svnet_lane_xor_u32<S2>(hi, lane), olo = svnet_lane_xor_u32<S2>(lo, lane);
     const bool take = ((((uint64_t)ohi << 32) | olo) > (((uint64_t)hi << 32) | lo)) != sort_flip<K2, S2>(lane);
     hi = take ? ohi : hi;
     lo = take ? olo : lo;
@@ -223,13 +159,13 @@ template <int K2>
 __device__ __forceinline__ uint32_t xform(int lane) { return stage_mask<K2 / 2>(lane) ^ stage_mask<K2>(lane); }   // (K2 = 2: from the plain keys)
 template <int S2>
 __device__ __forceinline__ void cx_key(uint32_t& key, int lane) {
-    const uint32_t ok = lane_xor_u32<S2>(key, lane);
+    const uint32_t ok = svnet_lane_xor_u32<S2>(key, lane);
     const bool take = (ok > key) != ((lane & S2) != 0);
     key = take ? ok : key;
 }
 template <int S2>
 __device__ __forceinline__ void cx_pair(uint32_t& hi, uint32_t& lo, int lane) {
-    const uint32_t ohi = lane_xor_u32<S2>(hi, lane), olo = lane_xor_u32<S2>(lo, lane);
+    const uint32_t ohi = svnet_lane_xor_u32<S2>(hi, lane), olo = svnet_lane_xor_u32<S2>(lo, lane);
     const bool take = ((((uint64_t)ohi << 32) | olo) > (((uint64_t)hi << 32) | lo)) != ((lane & S2) != 0);
     hi = take ? ohi : hi;
     lo = take ? olo : lo;

@@ -154,4 +154,22 @@ __device__ __forceinline__ float knn_xx_walk(const SrcT& src, const DstT& dst, i
     return result;
 }
 
+// The tail of the producers that hold a tile of TP consecutive points' rows in LDS (staged[TP][LD], a 4-wave workgroup, behind a
+// barrier): wave 0 walks the rows for ||x||^2 and all four waves write the channel-major table, TP consecutive points of a channel per
+// store instruction (64 / TP channels per wave and instruction).  The tile starts at point p0 = b * N + n0.
+template <int TP>
+__device__ __forceinline__ void knn_table_from_staged(const float* staged, int LD, int64_t C, int64_t Cpad, int64_t N, int64_t b, int64_t n0,
+                                                      int64_t p0, int xx_mode, float* __restrict__ xT, float* __restrict__ xx) {
+    const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
+    if (wave == 0 && lane < TP) {
+        struct Src { const float* a; __device__ __forceinline__ float operator[](int64_t off) const { return a[off]; } } src = {staged + lane * LD};
+        struct Dst { __device__ __forceinline__ void put(int64_t, float) const {} } dst;
+        xx[p0 + lane] = knn_xx_walk(src, dst, C, N, n0 + lane, 1, xx_mode);
+    }
+    constexpr int CPI = 64 / TP;
+    const int pl = lane % TP, cl = lane / TP;
+    float* out = xT + (size_t)b * Cpad * N + n0 + pl;
+    for (int c = wave * CPI + cl; c < (int)Cpad; c += 4 * CPI) out[(size_t)c * N] = c < (int)C ? staged[pl * LD + c] : 0.f;   // (rows past C: zeros)
+}
+
 }  // namespace

@@ -24,14 +24,6 @@ constexpr int64_t METRICS_LDS_CONF_MAX = 64;       // the workgroup's confusion 
 constexpr int64_t METRICS_MAX_PART = 4096;         // three histograms of num_part counters in LDS
 constexpr int METRICS_REG_PART = 64;               // a point's logits are kept in registers up to 64 channels
 
-// a beats b as a row's maximum: NaN first, then the larger value, then the lower index
-__device__ __forceinline__ bool better(float a, int64_t ia, float b, int64_t ib) {
-    const bool na = a != a, nb = b != b;
-    if (na != nb) return na;
-    if (!na && a != b) return a > b;
-    return ia < ib;
-}
-
 __device__ __forceinline__ u64* state_rows(u64* state, int64_t C) { return state + C * C; }
 
 // ---- classification: one wave per row
@@ -52,14 +44,14 @@ __global__ __launch_bounds__(METRICS_THREADS) void metrics_cls_kernel(const floa
         for (int64_t c = lane; c < C; c += 64) {
             const float v = row[c];
             mx = fmaxf(mx, v);
-            if (bi == INT64_MAX || better(v, c, best, bi)) { best = v; bi = c; }
+            if (bi == INT64_MAX || ranks_before_nan_first(v, c, best, bi)) { best = v; bi = c; }
         }
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) {
             mx = fmaxf(mx, __shfl_xor(mx, o, 64));
             const float ov = __shfl_xor(best, o, 64);
             const int64_t oi = __shfl_xor(bi, o, 64);
-            if (oi != INT64_MAX && (bi == INT64_MAX || better(ov, oi, best, bi))) { best = ov; bi = oi; }
+            if (oi != INT64_MAX && (bi == INT64_MAX || ranks_before_nan_first(ov, oi, best, bi))) { best = ov; bi = oi; }
         }
         const int64_t t = target[r];
         if (t < 0 || t >= C) {          // the loader's -1 poison, or anything else outside the classes: indexes nothing
@@ -129,13 +121,13 @@ __global__ __launch_bounds__(METRICS_THREADS) void metrics_seg_kernel(const SegA
                 if (c < P) {
                     const float w = v[c];
                     mx = fmaxf(mx, w);
-                    if (c == 0 || better(w, c, best, pred)) { best = w; pred = c; }
+                    if (c == 0 || ranks_before_nan_first(w, c, best, pred)) { best = w; pred = c; }
                 }
         } else {
             for (int c = 0; c < P; ++c) {
                 const float w = x[(int64_t)c * N];
                 mx = fmaxf(mx, w);
-                if (c == 0 || better(w, c, best, pred)) { best = w; pred = c; }
+                if (c == 0 || ranks_before_nan_first(w, c, best, pred)) { best = w; pred = c; }
             }
         }
         atomicAdd(&hp[pred], 1u);

@@ -23,12 +23,6 @@ struct ColMap {
     }
 };
 
-__device__ __forceinline__ float act_grad(float z, int act, float slope) {
-    if (act == 1) return z > 0.f ? 1.f : slope;
-    if (act == 2) return z > 0.f ? 1.f : 0.f;
-    return 1.f;
-}
-
 // Block-level reduction of per-thread doubles over the row lanes, then one atomic per column.
 template <int NQ>
 __device__ __forceinline__ void block_col_reduce(double (&val)[NQ], int col_in, int rl, int RL, int CW, bool col_ok,
@@ -159,10 +153,7 @@ __global__ __launch_bounds__(256) void bn_act_fwd_kernel(const float* __restrict
         const float mu = mean[c], is = invstd[c], ga = gamma[c], be = beta[c];
 #pragma unroll 4
         for (int64_t r = rstart; r < M; r += rstride) {
-            float z = (x[r * C + c] - mu) * is * ga + be;
-            if (act == 1) z = z > 0.f ? z : z * slope;
-            else if (act == 2) z = z > 0.f ? z : 0.f;
-            y[r * C + c] = z;
+            y[r * C + c] = act_apply((x[r * C + c] - mu) * is * ga + be, act, slope);
         }
     }
 }

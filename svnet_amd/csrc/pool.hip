@@ -71,11 +71,6 @@ __global__ __launch_bounds__(256) void pool_mean_finish_kernel(const float* __re
 // max with a long reduced axis: grid (chunks, outer); each (o,i) keeps one packed 64-bit key
 //   key = (order-preserving bits of the value) << 32 | (0xFFFFFFFF - r)      -> atomicMax = largest value, first index
 // in `keys` (pre-filled with 0 by the caller's memset); a second tiny kernel unpacks value and arg-max.
-__device__ __forceinline__ unsigned long long pack_key(float v, int64_t r) {
-    uint32_t u = __float_as_uint(v);
-    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-    return ((unsigned long long)u << 32) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)r);
-}
 __global__ __launch_bounds__(1024) void pool_max_split_kernel(const float* __restrict__ x, int64_t R, int64_t inner,
                                                              int64_t rows_per_chunk, unsigned long long* __restrict__ keys) {
     const int64_t o = blockIdx.y;
@@ -136,16 +131,6 @@ __global__ __launch_bounds__(1024) void pool_maxmean_split_kernel(const float* _
 // classifier, whose activated output is only ever pooled, sv_dgcnn_cls.py:69-74): the activated tensor is never written, and
 // its gradient - (point == arg-max ? g_max : 0) + g_mean / R, the edge block's trick - is never written either: the two
 // BatchNorm backward passes below build it from the pooled gradients.
-__device__ __forceinline__ float bnp_act(float z, int act, float slope) {
-    if (act == 1) return z > 0.f ? z : z * slope;
-    if (act == 2) return z > 0.f ? z : 0.f;
-    return z;
-}
-__device__ __forceinline__ float bnp_act_grad(float z, int act, float slope) {
-    if (act == 1) return z > 0.f ? 1.f : slope;
-    if (act == 2) return z > 0.f ? 1.f : 0.f;
-    return 1.f;
-}
 __global__ __launch_bounds__(1024) void bn_pool_split_kernel(const float* __restrict__ x, const float* __restrict__ mean,
                                                             const float* __restrict__ invstd, const float* __restrict__ gamma,
                                                             const float* __restrict__ beta, int act, float slope, int64_t R,
@@ -157,7 +142,7 @@ __global__ __launch_bounds__(1024) void bn_pool_split_kernel(const float* __rest
         const float mu = mean[i], is = invstd[i], ga = gamma[i], be = beta[i];
         const float* p = x + o * R * inner + i;
         // (the same arithmetic, in the same order, as bn_act_fwd_kernel: the pooled values equal pooling its output)
-        float best = bnp_act((p[r0 * inner] - mu) * is * ga + be, act, slope), s = best;
+        float best = act_apply((p[r0 * inner] - mu) * is * ga + be, act, slope), s = best;
         int64_t bi = r0;
         int64_t r = r0 + 1;
         for (; r + 15 < r1; r += 16) {
@@ -166,7 +151,7 @@ __global__ __launch_bounds__(1024) void bn_pool_split_kernel(const float* __rest
             for (int u = 0; u < 16; ++u) t[u] = p[(r + u) * inner];
 #pragma unroll
             for (int u = 0; u < 16; ++u) {
-                const float z = bnp_act((t[u] - mu) * is * ga + be, act, slope);
+                const float z = act_apply((t[u] - mu) * is * ga + be, act, slope);
                 s += z;
                 if (z > best) { best = z; bi = r + u; }
             }
@@ -177,13 +162,13 @@ __global__ __launch_bounds__(1024) void bn_pool_split_kernel(const float* __rest
             for (int u = 0; u < 8; ++u) t[u] = p[(r + u) * inner];
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
-                const float z = bnp_act((t[u] - mu) * is * ga + be, act, slope);
+                const float z = act_apply((t[u] - mu) * is * ga + be, act, slope);
                 s += z;
                 if (z > best) { best = z; bi = r + u; }
             }
         }
         for (; r < r1; ++r) {
-            const float z = bnp_act((p[r * inner] - mu) * is * ga + be, act, slope);
+            const float z = act_apply((p[r * inner] - mu) * is * ga + be, act, slope);
             s += z;
             if (z > best) { best = z; bi = r; }
         }
@@ -215,7 +200,7 @@ __global__ __launch_bounds__(1024) void bn_pool_bwd_reduce_kernel(const float* _
 #pragma unroll
             for (int u = 0; u < 16; ++u) {
                 const float xh = (t[u] - mu) * is;
-                const float gp = (gm + (am == (int32_t)(r + u) ? gx : 0.f)) * bnp_act_grad(xh * ga + be, act, slope);
+                const float gp = (gm + (am == (int32_t)(r + u) ? gx : 0.f)) * act_grad(xh * ga + be, act, slope);
                 a0 += (double)gp;
                 a1 += (double)gp * (double)xh;
             }
@@ -227,14 +212,14 @@ __global__ __launch_bounds__(1024) void bn_pool_bwd_reduce_kernel(const float* _
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
                 const float xh = (t[u] - mu) * is;
-                const float gp = (gm + (am == (int32_t)(r + u) ? gx : 0.f)) * bnp_act_grad(xh * ga + be, act, slope);
+                const float gp = (gm + (am == (int32_t)(r + u) ? gx : 0.f)) * act_grad(xh * ga + be, act, slope);
                 a0 += (double)gp;
                 a1 += (double)gp * (double)xh;
             }
         }
         for (; r < r1; ++r) {
             const float xh = (p[r * inner] - mu) * is;
-            const float gp = (gm + (am == (int32_t)r ? gx : 0.f)) * bnp_act_grad(xh * ga + be, act, slope);
+            const float gp = (gm + (am == (int32_t)r ? gx : 0.f)) * act_grad(xh * ga + be, act, slope);
             a0 += (double)gp;
             a1 += (double)gp * (double)xh;
         }
@@ -271,14 +256,14 @@ __global__ __launch_bounds__(1024) void bn_pool_bwd_apply_kernel(const float* __
 #pragma unroll
             for (int u = 0; u < 16; ++u) {
                 const float xh = (t[u] - mu) * is;
-                float gp = (gm + (am == (int32_t)(r + u) ? gx : 0.f)) * bnp_act_grad(xh * ga + be, act, slope);
+                float gp = (gm + (am == (int32_t)(r + u) ? gx : 0.f)) * act_grad(xh * ga + be, act, slope);
                 if (train_stats) gp -= (q0 + xh * q1) * invM;
                 d[(r + u) * inner] = gp * ga * is;
             }
         }
         for (; r < r1; ++r) {
             const float xh = (p[r * inner] - mu) * is;
-            float gp = (gm + (am == (int32_t)r ? gx : 0.f)) * bnp_act_grad(xh * ga + be, act, slope);
+            float gp = (gm + (am == (int32_t)r ? gx : 0.f)) * act_grad(xh * ga + be, act, slope);
             if (train_stats) gp -= (q0 + xh * q1) * invM;
             d[r * inner] = gp * ga * is;
         }

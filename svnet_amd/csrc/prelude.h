@@ -54,7 +54,7 @@ __device__ __forceinline__ void svnet_prelude_body(const float* __restrict__ gs,
 #pragma unroll
                 for (int u = 0; u < 8; ++u) {
                     const float y = a * sv[u] + bb;
-                    const float g = gv8[u] * (y > 0.f ? 1.f : slope);
+                    const float g = gv8[u] * act_grad(y, 1, slope);
                     gy[(p + u * RG) * Os + o] = g;
                     r1 += g;
                     r2 += g * (sc * sv[u] - my) * iy;
@@ -63,7 +63,7 @@ __device__ __forceinline__ void svnet_prelude_body(const float* __restrict__ gs,
             for (; p < p1; p += RG) {
                 const float sel = (float)selp[p * Os + o];
                 const float y = a * sel + bb;
-                const float g = ((gs ? gs[p * Os + o] : 0.f) + (gs2 ? gs2[p * gs2_ld + o] : 0.f)) * (y > 0.f ? 1.f : slope);
+                const float g = ((gs ? gs[p * Os + o] : 0.f) + (gs2 ? gs2[p * gs2_ld + o] : 0.f)) * act_grad(y, 1, slope);
                 gy[p * Os + o] = g;
                 r1 += g;
                 r2 += g * (sc * sel - my) * iy;

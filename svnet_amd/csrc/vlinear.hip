@@ -11,14 +11,12 @@
 // Arithmetic: the fp32 activations are split exactly into three bf16 pieces (x = h + m + l, as in gemm_mfma.hip), the +-1 / 0 weights are
 // exact in bf16, fp32 accumulation - the rows kernels' recipe.  Measured: faster alone, not in the step - the product
 // path uses it only with config.FUSE_VBN_STATS.
+#include "bf16_split.h"
 #include "common.h"
 
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
-
-__device__ __forceinline__ __bf16 vl_bf16_from_bits(uint32_t b) { return __builtin_bit_cast(__bf16, (unsigned short)b); }
 
 struct VlinArgs {
     const float* v; const float* wb; const float* cs; float* y; double* sums;
@@ -54,7 +52,7 @@ __global__ __launch_bounds__(512, 2) void vlinear_stats_kernel(VlinArgs a) {
     for (int e = tid; e < 32 * nct * KP; e += NTH) {
         const int o = e / KP, k = e - o * KP;
         const float w = (o < O && k < K) ? a.wb[(size_t)o * K + k] : 0.f;
-        Bs[o * BS + k] = vl_bf16_from_bits(__float_as_uint(w) >> 16);
+        Bs[o * BS + k] = bf16_from_bits(__float_as_uint(w) >> 16);
     }
     for (int e = tid; e < 3 * AP; e += NTH) As[e] = 0;
     const int col = 32 * wave + r;
@@ -85,15 +83,13 @@ __global__ __launch_bounds__(512, 2) void vlinear_stats_kernel(VlinArgs a) {
             const int row = (int)(((float)i + 0.5f) * inv_k);                   // (i < 96 * 96: exact)
             const int k = i - row * K;
             const float x = (base + i < total_floats) ? stg[u] : 0.f;           // (rows past P: zeros)
-            const uint32_t hu = __float_as_uint(x) & 0xFFFF0000u;               // x = h + m + l exactly (three bf16 pieces)
-            const float r1 = x - __uint_as_float(hu);
-            const uint32_t mu = __float_as_uint(r1) & 0xFFFF0000u;
-            const float r2 = r1 - __uint_as_float(mu);
+            uint32_t h_, m_, l_;
+            split3(x, h_, m_, l_);
             if (i < tile_floats) {
                 uint16_t* o_ = As + row * BS + k;
-                o_[0] = (uint16_t)(hu >> 16);
-                o_[AP] = (uint16_t)(mu >> 16);
-                o_[2 * AP] = (uint16_t)(__float_as_uint(r2) >> 16);
+                o_[0] = (uint16_t)h_;
+                o_[AP] = (uint16_t)m_;
+                o_[2 * AP] = (uint16_t)l_;
             }
         }
         __syncthreads();

@@ -21,39 +21,15 @@ namespace {
 constexpr int J = 3;
 constexpr float VT_VEPS = 1e-6f;      // EPS of sv_layers.py:18, added to the norm before BatchNorm (:94)
 
-__device__ __forceinline__ unsigned long long vt_pack_key(float v, uint32_t r) {     // pool.hip pack_key: larger value, then lower row
-    uint32_t u = __float_as_uint(v);
-    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-    return ((unsigned long long)u << 32) | (unsigned long long)(0xFFFFFFFFu - r);
-}
-
-// ---- nine wave-wide sums per point (the 3 x 3 frame): eight of them packed (18 VALU: permlane swaps fold two quantities per step, as
-// edgeblock_bwd.hip wave_sum8_packed) + one plain, results as WAVE-UNIFORM scalars (v_readlane) - nine separate 6-step DPP chains were
-// most of the kernel's dependent latency
-template <int CTRL>
-__device__ __forceinline__ float vt_dpp(float v) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true));
-}
-__device__ __forceinline__ float vt_fold32(float a, float b) {      // lanes 0-31: sum of a's halves, lanes 32-63: of b's
-    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(b), false, false);
-    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-__device__ __forceinline__ float vt_fold16(float a, float b) {      // rows: a.r0+a.r1 | b.r0+b.r1 | a.r2+a.r3 | b.r2+b.r3
-    const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(a), __float_as_uint(b), false, false);
-    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
+// ---- nine wave-wide sums per point (the 3 x 3 frame): eight of them packed (wave_sum8_packed, 18 VALU) + one plain, results as
+// WAVE-UNIFORM scalars (v_readlane) - nine separate 6-step DPP chains were most of the kernel's dependent latency
 __device__ __forceinline__ float vt_lane(float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); }
 __device__ __forceinline__ void vt_sum9(const float (&p)[3][J], int lane, float (&z)[3][J]) {
-    const float x0 = vt_fold16(vt_fold32(p[0][0], p[0][1]), vt_fold32(p[0][2], p[1][0]));   // rows: s0 | s2 | s1 | s3
-    const float x1 = vt_fold16(vt_fold32(p[1][1], p[1][2]), vt_fold32(p[2][0], p[2][1]));   // rows: s4 | s6 | s5 | s7
-    const bool hi = (lane & 8) != 0;
-    float y = (hi ? x1 : x0) + vt_dpp<0x128>(hi ? x0 : x1);                                  // row_ror:8 - 8-lane groups: s0 s4 s2 s6 s1 s5 s3 s7
-    y += vt_dpp<0xB1>(y);
-    y += vt_dpp<0x4E>(y);
-    y += vt_dpp<0x141>(y);
+    const float s[8] = {p[0][0], p[0][1], p[0][2], p[1][0], p[1][1], p[1][2], p[2][0], p[2][1]};
+    const float y = wave_sum8_packed(s, lane);                                               // 8-lane groups: s0 s4 s2 s6 s1 s5 s3 s7
     z[0][0] = vt_lane(y, 0);  z[1][1] = vt_lane(y, 8);  z[0][2] = vt_lane(y, 16); z[2][0] = vt_lane(y, 24);
     z[0][1] = vt_lane(y, 32); z[1][2] = vt_lane(y, 40); z[1][0] = vt_lane(y, 48); z[2][1] = vt_lane(y, 56);
-    z[2][2] = vt_lane(group_sum_dpp<64>(p[2][2]), 0);
+    z[2][2] = vt_lane(wave_sum(p[2][2]), 0);
 }
 
 struct VtStats {        // training: the sliced fp64 sums of svnet_colstats_f64(kind 1); every lane derives its channels' statistics itself
@@ -222,7 +198,7 @@ __global__ __launch_bounds__(256) void vtail_fwd_kernel(const float* __restrict_
 #pragma unroll
         for (int j = 0; j < J; ++j) {
             const int slot = (t * J + j) * 64 + lane;
-            lkey[wave][slot] = any ? vt_pack_key(best[t][j], bi[t][j]) : 0ull;
+            lkey[wave][slot] = any ? pack_key(best[t][j], bi[t][j]) : 0ull;
             lsum[wave][slot] = sum[t][j];
         }
     __syncthreads();

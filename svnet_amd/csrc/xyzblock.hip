@@ -89,12 +89,6 @@ struct FeatRow {
     static constexpr int NF = 6 * NC, NV = 3 * NC, NE = BWD ? NC * (NC + 1) / 2 : 0, NP = (NF + NV + NE + 3) & ~3;
 };
 
-// value held by lane (l ^ 32)
-__device__ __forceinline__ float xyz_swap32(float x) {
-    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-    return __uint_as_float((threadIdx.x & 32) ? r[0] : r[1]);
-}
-
 // One wave per point.  An edge row is a function of six floats, so its features are computed ONCE, by the lane that owns the edge
 // (lane t = neighbour slot t: phase 1, ~80 instructions per POINT, the lane's own neighbour id - no cross-lane read), and left in a
 // per-wave LDS row; the output channels then walk the point's edges with lanes = channels (phase 2), EPI = 2 edges per iteration when
@@ -215,12 +209,12 @@ __global__ __launch_bounds__(256) void xyzblock_fwd_kernel(XyzFwdArgs fa) {
         }
         __builtin_amdgcn_wave_barrier();          // the next point's rows overwrite these
         if (EPI == 2) {   // the two halves hold the even / the odd slots: first occurrence of the extremum = larger value, then lower slot
-            const float omax = xyz_swap32(ymax), omin = xyz_swap32(ymin);
-            const int osmax = __float_as_int(xyz_swap32(__int_as_float(smax))), osmin = __float_as_int(xyz_swap32(__int_as_float(smin)));
+            const float omax = lane_half_swap(ymax), omin = lane_half_swap(ymin);
+            const int osmax = (int)lane_half_swap((uint32_t)smax), osmin = (int)lane_half_swap((uint32_t)smin);
             if (omax > ymax || (omax == ymax && osmax < smax)) { ymax = omax; smax = osmax; }
             if (omin < ymin || (omin == ymin && osmin < smin)) { ymin = omin; smin = osmin; }
 #pragma unroll
-            for (int dd = 0; dd < 3; ++dd) { av[dd] += xyz_swap32(av[dd]); avn[dd] += xyz_swap32(avn[dd]); }
+            for (int dd = 0; dd < 3; ++dd) { av[dd] += lane_half_swap(av[dd]); avn[dd] += lane_half_swap(avn[dd]); }
         }
         const float invk = 1.f / (float)k;
         if (o_lane && half == 0) {
@@ -317,7 +311,7 @@ struct XyzApplyMath {
     __device__ __forceinline__ float s(int64_t p, int o) const {
         const float a = A1[o];
         const float y = a * (a >= 0.f ? y_max[p * Os + o] : y_min[p * Os + o]) + B1[o];
-        return y > 0.f ? y : y * slope;
+        return act_apply(y, 1, slope);
     }
     __device__ __forceinline__ float v(int64_t p, int64_t b, int q, int c) const {
         const int64_t e = p * 3 * Ov + q;
