@@ -45,9 +45,9 @@ int svnet_slices_sum_f64(double* buf, int64_t L, void* stream);
 
 /* ABI version = 100 * round-of-change + serial.  It changes whenever an entry point gains / loses an argument or a caller-owned buffer
  * changes its required length (200: sliced accumulators, SVNET_SLICED_LEN; 400: this header; 401: the totals of a sliced accumulator are
- * written by its consumer, svnet_slices_sum_*; 402: GX of svnet_v2s_bwd_*, gw of svnet_xyzblock_bwd_f32 and col_sum of svnet_gemm_f32 are sliced accumulators; 403: svnet_binweight_grad_f32 takes sliced inputs; 421: svnet_three_nn_f32, svnet_three_interpolate_f32).  svnet_version() returns the value the
+ * written by its consumer, svnet_slices_sum_*; 402: GX of svnet_v2s_bwd_*, gw of svnet_xyzblock_bwd_f32 and col_sum of svnet_gemm_f32 are sliced accumulators; 403: svnet_binweight_grad_f32 takes sliced inputs; 421: svnet_three_nn_f32, svnet_three_interpolate_f32; 422: svnet_ball_query_f32, svnet_group_points_f32).  svnet_version() returns the value the
  * library was BUILT with: a caller compiled against another header must refuse to run (svnet_amd/_lib.py does).                   */
-#define SVNET_ABI_VERSION 421
+#define SVNET_ABI_VERSION 422
 int svnet_version(void);
 const char* svnet_last_error(void);
 
@@ -774,6 +774,29 @@ int svnet_three_nn_f32(const float* query, const float* ref, int64_t B, int64_t 
                        void* stream);
 int svnet_three_interpolate_f32(const float* feat, const int64_t* idx, const float* weight, int64_t B, int64_t D, int64_t N, int64_t P,
                                 float* out, void* stream);
+
+/* ------------------------------------------------------------------ ball query and neighbourhood grouping: centres -> local groups
+ * (models/utils/pointnet_util.py:87-107 query_ball_point, 110-143 sample_and_group without its sampling).  Forward only.  Per cloud,
+ * xyz [N,3], new_xyz [S,3], points [N,D] (channel-last, or NULL with D = 0), fp32, every operation rounded once and never contracted:
+ *     d_c = fl(new_xyz[s,c] - xyz[n,c]),  dist[s,n] = fl(fl(fl(d_0 d_0) + fl(d_1 d_1)) + fl(d_2 d_2))    (the difference form of svnet_fps_f32;
+ *         the reference's expanded form -2 a.b + |a|^2 + |b|^2 is NOT used)
+ *     point n is inside group s when dist[s,n] <= r2 (the reference: sqrdists > radius ** 2 is outside); a NaN distance is never inside
+ *     idx[s,0..nsample-1]: the first nsample inside points in ASCENDING POINT INDEX; slots past the number found hold the first inside
+ *         index; count[s] = min(found, nsample).  An empty group (the reference would write index N and fail): count 0, every slot 0.
+ *     out[s,j,c] = fl(xyz[idx[s,j],c] - new_xyz[s,c]) for c = 0..2 (point minus centre),  out[s,j,3+d] = points[idx[s,j],d] bit for bit
+ * svnet_ball_query_f32: xyz [B,N,3], new_xyz [B,S,3] -> idx [B,S,nsample] int64, count [B,S] int32.  Every index written lies in
+ *     0 .. N-1 whatever the coordinates and r2 hold.  One wave per centre, leaving its candidate loop once the group is full.
+ * svnet_group_points_f32: idx [B,S,nsample] -> out [B,S,nsample,3+D].  An index outside 0 .. N-1 is clamped into it, never followed.
+ * One launch each, no workspace.  1 <= nsample <= N <= 32768 (the k-NN's limit), S >= 1, D >= 0; B * ceil(S / 32) <= 2^31 - 1 for the
+ * query and B * S * nsample <= 2^31 - 1 for the grouping; past that SVNET_E_UNSUPPORTED.  svnet_group_supported (1 / 0, without the
+ * B terms) and svnet_ball_query_tile (the points per LDS tile of svnet_ball_query_f32: the N at which its candidate loop takes a
+ * second tile) are pure host functions.                                                                                            */
+int svnet_group_supported(int64_t N, int64_t S, int64_t nsample, int64_t D);
+int svnet_ball_query_tile(void);
+int svnet_ball_query_f32(const float* xyz, const float* new_xyz, int64_t B, int64_t N, int64_t S, float r2, int64_t nsample, int64_t* idx,
+                         int* count, void* stream);
+int svnet_group_points_f32(const float* xyz, const float* new_xyz, const float* points, const int64_t* idx, int64_t B, int64_t N, int64_t S,
+                           int64_t nsample, int64_t D, float* out, void* stream);
 
 /* ------------------------------------------------------------------ epoch metrics (main_cls_dgcnn.py:187-251, main_partseg_dgcnn.py:185-279,
  * utils.py:68-91 calculate_shape_IoU; the accuracy scores of sklearn.metrics are functions of the confusion matrix)

@@ -10,7 +10,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SVNET_DIAG_LIB") or os.path.join(_HERE, "libsvnet_hip.so")    # (SVNET_DIAG_LIB: an ablation build, tools/ only)
 _lib = None
-ABI_VERSION = 421       # include/svnet_hip.h SVNET_ABI_VERSION: argument lists / buffer-length contracts this binding was written against
+ABI_VERSION = 422       # include/svnet_hip.h SVNET_ABI_VERSION: argument lists / buffer-length contracts this binding was written against
 
 c_p = ctypes.c_void_p
 c_i64 = ctypes.c_int64
@@ -276,6 +276,10 @@ SIGNATURES = {
     "svnet_propagate_tile": (c_int, []),
     "svnet_three_nn_f32": (c_int, [c_p, c_p, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_p]),
     "svnet_three_interpolate_f32": (c_int, [c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_p, c_p]),
+    "svnet_group_supported": (c_int, [c_i64, c_i64, c_i64, c_i64]),
+    "svnet_ball_query_tile": (c_int, []),
+    "svnet_ball_query_f32": (c_int, [c_p, c_p, c_i64, c_i64, c_i64, c_f, c_i64, c_p, c_p, c_p]),
+    "svnet_group_points_f32": (c_int, [c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_p, c_p]),
     "svnet_metrics_state_bytes": (c_sz, [c_i64]),
     "svnet_metrics_workspace_bytes": (c_sz, [c_i64, c_i64, c_i64]),
     "svnet_metrics_reset": (c_int, [c_p, c_i64, c_p, c_p, c_i64, c_p]),

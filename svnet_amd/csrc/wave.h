@@ -1,5 +1,5 @@
 // Wave-level primitives of the gfx950 kernels, each stated once: DPP moves, the row / half swaps, the sums and arg-max butterflies built
-// from them, and the order-preserving float keys.  CDNA4 only: wave = 64 lanes = 4 rows of 16.  Included by common.h.
+// from them, a lane's rank in a ballot, and the order-preserving float keys.  CDNA4 only: wave = 64 lanes = 4 rows of 16.  Included by common.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -102,6 +102,12 @@ __device__ __forceinline__ float wave_sum_last(float v) {
     v += svnet_dpp_f32<DPP_ROW_BCAST15, 0xA>(v);
     v += svnet_dpp_f32<DPP_ROW_BCAST31, 0xC>(v);
     return v;
+}
+
+// ---- rank of a lane among the set lanes of a ballot: the number of set bits of `mask` BELOW this lane (v_mbcnt_lo + v_mbcnt_hi).
+// With mask = __ballot(keep), found + lanes_below(mask) is the slot of a kept lane in a list the wave appends to in lane order.
+__device__ __forceinline__ int lanes_below(unsigned long long mask) {
+    return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
 }
 
 // ---- (value, index) ranking: "a ranks before b" = larger value first, equal values -> smaller index first

@@ -1,0 +1,255 @@
+"""Ball query and neighbourhood grouping around sampled centres (svnet_amd/csrc/group.hip).
+
+The third point-set helper of the reference's models/utils/pointnet_util.py beside farthest point sampling (svnet_amd/data.py) and
+the three-nearest-neighbour interpolation (svnet_amd/propagate.py): `query_ball_point` (lines 87-107) and `sample_and_group` /
+`sample_and_group_all` (lines 110-163), the step that turns sampled centres into fixed-size local neighbourhoods - the first level
+of a hierarchical encoder, which groups raw coordinates and input attributes.
+
+    new_xyz, new_points = sample_and_group(512, 0.2, 32, xyz, points)           # [B,512,3], [B,512,32,3+D]
+    idx, count = query_ball_point(0.2, 32, xyz, new_xyz, return_count=True)     # [B,512,32] int64, [B,512] int32
+    grouped = group_points(xyz, new_xyz, idx, points)                           # [B,512,32,3+D]
+
+The contract, for one cloud: points xyz [N,3], centres new_xyz [S,3], optional attributes points [N,D] (channel-last, as the
+reference's `sample_and_group` takes them), all fp32.  Every operation is rounded once and never contracted into an fma (the kernels
+are compiled like fps.hip and propagate.hip, with contraction off); fl() is rounding to fp32.
+
+    distance    d_c = fl(new_xyz[s,c] - xyz[n,c]);   dist[s,n] = fl(fl(fl(d_0 d_0) + fl(d_1 d_1)) + fl(d_2 d_2))
+                The difference form of fps.hip and propagate.hip.  The reference's expanded form -2 a.b + |a|^2 + |b|^2 is
+                deliberately NOT copied, for the reason given in propagate.py: centres coincide with points, and there the expanded
+                form rounds to small values of either sign.  On coordinates whose squares and products are exact in fp32 the two
+                forms agree bit for bit.
+    membership  point n is inside group s when dist[s,n] <= r2 (the reference writes `sqrdists > radius ** 2` -> outside).  r2 is
+                an fp32 argument of the C entry point; this layer passes fp32(radius * radius) with the square taken in double, the
+                scalar torch's comparison sees.  A NaN distance is never inside.  (Whether torch compares in fp32 or wider does not
+                enter any test or recorded case: there r2 is either exact in fp32 - radii 0.125, 0.25, 0.5 - or, for the PointNet++
+                radii 0.1, 0.2, 0.4, not a value a distance of lattice coordinates, a multiple of 2^-20, can take, so both
+                readings agree.)
+    indices     idx [S,nsample] int64: the first nsample inside points in ASCENDING POINT INDEX - what the reference's sort of the
+                masked arange(N) yields.  Slots past the number found hold the first inside index (`group_first`).
+                count [S] int32 = min(found, nsample); the reference does not return it, a caller that pools over a group wants it.
+    empty group no inside point: only when a centre is not one of the points, or a coordinate is not finite.  The reference would
+                write index N and fail in `index_points`; HERE count = 0, every slot 0, the rows grouped from point 0 - a stated
+                divergence.  Every index written is inside [0, N), always.
+    grouping    new_points [S,nsample,3+D]: columns 0..2 = fl(xyz[i,c] - new_xyz[s,c]) (point MINUS centre, line 132), columns 3..
+                = points[i,:] copied bit for bit; points=None gives [S,nsample,3].  An index outside [0, N) handed to
+                `group_points` is clamped into it, never followed.
+
+On lattice coordinates the whole contract equals the reference's CPU result bit for bit (tests/golden/group.npz; tests/group_ref.py
+restates the contract in numpy).
+
+Forward only: the first set-abstraction level groups data, not activations; the functions take no gradient and build no autograd
+graph.  There is no CPU fallback: tensors that are not on a HIP device raise.  Limits: 1 <= nsample <= N <= 32768 (the reference
+silently returns N columns when nsample > N; here it is refused), S >= 1, D >= 0, B * ceil(S / 32) <= 2^31 - 1 for the query and
+B * S * nsample <= 2^31 - 1 for the grouping; `sample_and_group` also has farthest point sampling's N <= 16384.
+"""
+import numpy as np
+import torch
+
+from . import _lib, _ops
+from .data import fps_start
+
+
+def tile():
+    """Points per LDS tile of the ball-query kernel: the N past which its candidate loop takes another tile."""
+    return int(_lib.lib().svnet_ball_query_tile())
+
+
+def _r2(radius):
+    """fp32(radius * radius), the square taken in double."""
+    radius = float(radius)
+    with np.errstate(over="ignore"):          # a square past fp32's range is +inf: every finite distance is inside
+        return float(np.float32(radius * radius))
+
+
+def _check(name, tensors, dtypes):
+    """tensors: {argument name: tensor}; the type, dtype, device-match, contiguity and no-gradient checks shared by the entry points
+    (the HIP device itself is checked after the shapes, by _ops._hip)."""
+    for k, t in tensors.items():
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("%s: %s must be a tensor, got %s" % (name, k, type(t).__name__))
+    for (k, t), dt in zip(tensors.items(), dtypes):
+        if t.dtype != dt:
+            raise TypeError("%s: %s must be %s, got %s" % (name, k, dt, t.dtype))
+    first = next(iter(tensors.values()))
+    for k, t in tensors.items():
+        if t.device != first.device:
+            raise ValueError("%s: %s on %s, %s on %s" % (name, next(iter(tensors)), first.device, k, t.device))
+        if not t.is_contiguous():
+            raise ValueError("%s: %s must be contiguous" % (name, k))
+        if t.requires_grad:
+            raise ValueError("%s: %s requires grad - the grouping is forward only" % (name, k))
+
+
+def _supported(name, N, S, nsample, D):
+    if not _lib.lib().svnet_group_supported(N, S, nsample, D):
+        raise _lib.SvnetHipError("%s: N = %d, S = %d, nsample = %d, D = %d is not supported (1 <= nsample <= N <= 32768, S >= 1, D >= 0)"
+                                 % (name, N, S, nsample, D))
+
+
+def _cloud_shapes(name, xyz, new_xyz):
+    if xyz.dim() != 3 or xyz.shape[2] != 3 or xyz.shape[0] < 1:
+        raise ValueError("%s: xyz must be [B,N,3], got %s" % (name, tuple(xyz.shape)))
+    if new_xyz.dim() != 3 or new_xyz.shape[2] != 3 or new_xyz.shape[0] != xyz.shape[0]:
+        raise ValueError("%s: new_xyz must be [B,S,3] with B = %d, got %s" % (name, xyz.shape[0], tuple(new_xyz.shape)))
+    return int(xyz.shape[0]), int(xyz.shape[1]), int(new_xyz.shape[1])
+
+
+def _points_shape(name, points, B, N):
+    if points.dim() != 3 or points.shape[0] != B or points.shape[1] != N:
+        raise ValueError("%s: points must be [B,N,D] with B = %d, N = %d, got %s" % (name, B, N, tuple(points.shape)))
+    return int(points.shape[2])
+
+
+def _query_launch(xyz, new_xyz, B, N, S, r2, nsample, idx, count):
+    with torch.cuda.device(xyz.device):
+        _lib.call("svnet_ball_query_f32", _ops._p(xyz), _ops._p(new_xyz), B, N, S, r2, nsample, _ops._p(idx), _ops._p(count), _ops._stream())
+
+
+def _group_launch(xyz, new_xyz, points, idx, B, N, S, nsample, D, out):
+    with torch.cuda.device(xyz.device):
+        _lib.call("svnet_group_points_f32", _ops._p(xyz), _ops._p(new_xyz), _ops._p(points if D else None), _ops._p(idx), B, N, S, nsample, D,
+                  _ops._p(out), _ops._stream())
+
+
+def query_ball_point(radius, nsample, xyz, new_xyz, return_count=False):
+    """The reference's name and argument order: xyz [B,N,3], new_xyz [B,S,3] float32 on a HIP device -> idx [B,S,nsample] int64, the
+    first nsample points within `radius` of every centre in ascending index, padded with the first (module docstring); with
+    return_count also count [B,S] int32.  One launch, no host read; no gradient."""
+    _check("query_ball_point", {"xyz": xyz, "new_xyz": new_xyz}, (torch.float32, torch.float32))
+    B, N, S = _cloud_shapes("query_ball_point", xyz, new_xyz)
+    nsample = int(nsample)
+    _ops._hip(xyz, new_xyz)
+    _supported("query_ball_point", N, S, nsample, 0)
+    idx = torch.empty(B, S, nsample, dtype=torch.int64, device=xyz.device)
+    count = torch.empty(B, S, dtype=torch.int32, device=xyz.device)
+    _query_launch(xyz, new_xyz, B, N, S, _r2(radius), nsample, idx, count)
+    return (idx, count) if return_count else idx
+
+
+def _group_args(name, xyz, new_xyz, idx, points):
+    tensors, dtypes = {"xyz": xyz, "new_xyz": new_xyz, "idx": idx}, [torch.float32, torch.float32, torch.int64]
+    if points is not None:
+        tensors["points"] = points
+        dtypes.append(torch.float32)
+    _check(name, tensors, dtypes)
+    B, N, S = _cloud_shapes(name, xyz, new_xyz)
+    if idx.dim() != 3 or idx.shape[0] != B or idx.shape[1] != S:
+        raise ValueError("%s: idx must be [B,S,nsample] with B = %d, S = %d, got %s" % (name, B, S, tuple(idx.shape)))
+    D = 0 if points is None else _points_shape(name, points, B, N)
+    return B, N, S, int(idx.shape[2]), D
+
+
+def group_points(xyz, new_xyz, idx, points=None, out=None):
+    """xyz [B,N,3], new_xyz [B,S,3], idx [B,S,nsample] int64, points [B,N,D] or None -> [B,S,nsample,3+D]: the centred coordinates
+    of every group's points followed by their attributes (module docstring).  An index outside [0, N) is clamped into it.  One
+    launch, no host read; `out` lets a caller keep a fixed buffer.  No gradient."""
+    B, N, S, nsample, D = _group_args("group_points", xyz, new_xyz, idx, points)
+    _ops._hip(xyz, new_xyz, idx, points)
+    _supported("group_points", N, S, nsample, D)
+    if out is None:
+        out = torch.empty(B, S, nsample, 3 + D, dtype=torch.float32, device=xyz.device)
+    else:
+        _check("group_points", {"xyz": xyz, "out": out}, (torch.float32, torch.float32))
+        if tuple(out.shape) != (B, S, nsample, 3 + D):
+            raise ValueError("group_points: out must be [B,S,nsample,3+D] = %s, got %s" % ((B, S, nsample, 3 + D), tuple(out.shape)))
+    _group_launch(xyz, new_xyz, points, idx, B, N, S, nsample, D, out)
+    return out
+
+
+def sample_and_group(npoint, radius, nsample, xyz, points, returnfps=False, start=None, seed=0):
+    """The reference's name and return convention: xyz [B,N,3], points [B,N,D] or None -> (new_xyz [B,npoint,3], new_points
+    [B,npoint,nsample,3+D]), with returnfps also (grouped_xyz [B,npoint,nsample,3], the un-centred gather, and fps_idx [B,npoint]).
+    Farthest point sampling -> gather of the centres -> ball query -> grouping, on the current stream with no host read between them.
+    The reference's torch.randint start is an input, as in data.farthest_point_sample: `start` [B] int64 (a start outside 0 .. N-1 is
+    clamped into the cloud by the sampling kernel), or None for data.fps_start(seed, B, N), which is copied from the host: a caller
+    that captures the call into a HIP graph passes a device tensor.  No gradient."""
+    tensors, dtypes = {"xyz": xyz}, [torch.float32]
+    if points is not None:
+        tensors["points"] = points
+        dtypes.append(torch.float32)
+    if start is not None and isinstance(start, torch.Tensor):
+        tensors["start"] = start
+        dtypes.append(torch.int64)
+    _check("sample_and_group", tensors, dtypes)
+    if xyz.dim() != 3 or xyz.shape[2] != 3 or xyz.shape[0] < 1:
+        raise ValueError("sample_and_group: xyz must be [B,N,3], got %s" % (tuple(xyz.shape),))
+    B, N, S, nsample = int(xyz.shape[0]), int(xyz.shape[1]), int(npoint), int(nsample)
+    D = 0 if points is None else _points_shape("sample_and_group", points, B, N)
+    _ops._hip(xyz, points)
+    if not _lib.lib().svnet_fps_supported(N, S):
+        raise _lib.SvnetHipError("sample_and_group: N = %d, npoint = %d is not supported (1 <= npoint <= N <= 16384)" % (N, S))
+    _supported("sample_and_group", N, S, nsample, D)
+    if start is None:
+        start = torch.from_numpy(fps_start(seed, B, N)).to(xyz.device)
+    elif not isinstance(start, torch.Tensor):
+        start = torch.from_numpy(np.ascontiguousarray(start, dtype=np.int64)).to(xyz.device)
+    if tuple(start.shape) != (B,):
+        raise ValueError("sample_and_group: start must be [B] = [%d], got %s" % (B, tuple(start.shape)))
+    dev = xyz.device
+    fps_idx = torch.empty(B, S, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        _lib.call("svnet_fps_f32", _ops._p(xyz), B, N, S, _ops._p(start), _ops._p(fps_idx), _ops._stream())
+    new_xyz = torch.gather(xyz, 1, fps_idx.unsqueeze(2).expand(-1, -1, 3)).contiguous()
+    idx = torch.empty(B, S, nsample, dtype=torch.int64, device=dev)
+    count = torch.empty(B, S, dtype=torch.int32, device=dev)
+    new_points = torch.empty(B, S, nsample, 3 + D, dtype=torch.float32, device=dev)
+    _query_launch(xyz, new_xyz, B, N, S, _r2(radius), nsample, idx, count)
+    _group_launch(xyz, new_xyz, points, idx, B, N, S, nsample, D, new_points)
+    if not returnfps:
+        return new_xyz, new_points
+    grouped_xyz = torch.gather(xyz, 1, idx.view(B, S * nsample, 1).expand(-1, -1, 3)).view(B, S, nsample, 3)
+    return new_xyz, new_points, grouped_xyz, fps_idx
+
+
+def sample_and_group_all(xyz, points):
+    """The reference's trivial form: one group of all N points around centre 0, in order.  xyz [B,N,3], points [B,N,D] or None ->
+    (new_xyz [B,1,3] of zeros, new_points [B,1,N,3+D]).  torch views and one cat."""
+    tensors, dtypes = {"xyz": xyz}, [torch.float32]
+    if points is not None:
+        tensors["points"] = points
+        dtypes.append(torch.float32)
+    _check("sample_and_group_all", tensors, dtypes)
+    if xyz.dim() != 3 or xyz.shape[2] != 3 or xyz.shape[0] < 1:
+        raise ValueError("sample_and_group_all: xyz must be [B,N,3], got %s" % (tuple(xyz.shape),))
+    B, N = int(xyz.shape[0]), int(xyz.shape[1])
+    if points is not None:
+        _points_shape("sample_and_group_all", points, B, N)
+    _ops._hip(xyz, points)
+    new_xyz = torch.zeros(B, 1, 3, dtype=torch.float32, device=xyz.device)
+    grouped = xyz.view(B, 1, N, 3)
+    return new_xyz, (grouped if points is None else torch.cat([grouped, points.view(B, 1, N, -1)], dim=-1))
+
+
+class Grouper:
+    """query_ball_point() + group_points() on buffers allocated once: idx [B,S,nsample], count [B,S] and out [B,S,nsample,3+D] for
+    up to B clouds.  run(xyz, new_xyz, radius, points) takes the first `count` clouds of each and returns out[:count] (the indices
+    and counts of that call are in .idx[:count] / .count[:count]); nothing is allocated per call."""
+
+    def __init__(self, B, N, S, nsample, D, device):
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError("svnet_amd: Grouper needs a HIP (cuda) device, got %s — the product path has no CPU fallback" % device)
+        self.B, self.N, self.S, self.nsample, self.D = int(B), int(N), int(S), int(nsample), int(D)
+        if self.B < 1:
+            raise ValueError("Grouper: B = %d < 1" % self.B)
+        _supported("Grouper", self.N, self.S, self.nsample, self.D)
+        self.idx = torch.empty(self.B, self.S, self.nsample, dtype=torch.int64, device=device)
+        self.count = torch.empty(self.B, self.S, dtype=torch.int32, device=device)
+        self.out = torch.empty(self.B, self.S, self.nsample, 3 + self.D, dtype=torch.float32, device=device)
+
+    def run(self, xyz, new_xyz, radius, points=None):
+        tensors, dtypes = {"xyz": xyz, "new_xyz": new_xyz}, [torch.float32, torch.float32]
+        if points is not None:
+            tensors["points"] = points
+            dtypes.append(torch.float32)
+        _check("Grouper.run", tensors, dtypes)
+        count, N, S = _cloud_shapes("Grouper.run", xyz, new_xyz)
+        D = 0 if points is None else _points_shape("Grouper.run", points, count, N)
+        _ops._hip(xyz, new_xyz, points)
+        if count > self.B or (N, S, D) != (self.N, self.S, self.D) or xyz.device != self.out.device:
+            raise ValueError("Grouper.run: xyz %s, new_xyz %s, points %s do not fit B <= %d, N %d, S %d, D %d on %s"
+                             % (tuple(xyz.shape), tuple(new_xyz.shape), None if points is None else tuple(points.shape), self.B, self.N,
+                                self.S, self.D, self.out.device))
+        _query_launch(xyz, new_xyz, count, N, S, _r2(radius), self.nsample, self.idx, self.count)
+        _group_launch(xyz, new_xyz, points, self.idx, count, N, S, self.nsample, D, self.out)
+        return self.out[:count]
