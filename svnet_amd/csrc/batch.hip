@@ -14,7 +14,7 @@
 // Shape of the kernel: one workgroup per cloud.  The S keys (8 B each, padded with ~0 to a power of two) are written to LDS, sorted
 // there by a bitonic network (one workgroup barrier per compare-exchange step), then the same workgroup gathers the first N rows of
 // the order: 12-byte rows of the pool in, three coalesced channel planes out.
-#include "common.h"
+#include "pointset.h"
 
 namespace {
 
@@ -117,12 +117,11 @@ __global__ __launch_bounds__(BATCH_THREADS) void batch_assemble_kernel(const Bat
     }
 
     // ---- gather + transform: pool rows in, channel planes out
-    const float nanf_ = __int_as_float(0x7fc00000);
     const int64_t N = a.N;
     float* xb = a.x + (int64_t)b * 3 * N;
     for (int64_t n = t; n < N; n += T) {
         const int64_t p = sorted ? (int64_t)(keys[n] & 0xFFFFull) : n;
-        float v0 = nanf_, v1 = nanf_, v2 = nanf_;
+        float v0 = SVNET_QNAN, v1 = SVNET_QNAN, v2 = SVNET_QNAN;
         int64_t sg = -1;
         if (valid) {
             const float* row = a.data + ((int64_t)m * a.P + p) * 3;

@@ -10,6 +10,12 @@
 
 #define SVNET_WAVE 64
 
+// The range of the k-NN's bit-exact contract (knn.hip): past it the streamed form's limits (ids are 32-bit keys; a list holds 128)
+// and MKL's K blocking.  SVNET_KNN_MAX_N is also the limit on the points of a cloud in propagate.hip and group.hip.
+#define SVNET_KNN_MAX_N 32768
+#define SVNET_KNN_MAX_K 128
+#define SVNET_KNN_MAX_C 384
+
 void svnet_set_error(const char* fmt, ...);
 
 #define SVNET_REQUIRE(cond, code, ...)        \

@@ -5,9 +5,8 @@
 // The sampler's result is a list of integer indices fixed by the fp32 rounding sequence and a tie rule (the derivation is in
 // svnet_amd/data.py's docstring, tests/fps_ref.py restates it independently):
 //   mind[p] = fp32(1e10);  f = start
-//   npoint times:  idx[i] = f;  d_c = fl(x[p,c] - x[f,c]);  dist = fl(fl(fl(d_0 d_0) + fl(d_1 d_1)) + fl(d_2 d_2));
+//   npoint times:  idx[i] = f;  d_c = fl(x[p,c] - x[f,c]);  dist = sq_len(d_0, d_1, d_2)   (pointset.h: the distance, single-rounded);
 //                  mind[p] = dist < mind[p] ? dist : mind[p];  f = the SMALLEST p with mind[p] == max mind
-// This file is compiled with -ffp-contract=off (Makefile): every product and sum is its own correctly rounded fp32 operation.
 //
 // Shape of the sampler: one workgroup per cloud, grid M.  Thread t keeps points p = j T + t (j = 0 .. PPL-1) and their mind in
 // registers for the whole loop; the loop is npoint DEPENDENT iterations, so the workgroup is sized for the shortest iteration, not for
@@ -20,7 +19,7 @@
 // Every comparison is on (value, global index) and prefers the lower index on equal values: a lane walks its points in ascending
 // index order with a strict >, the butterflies compare the pair.  Padding points (p >= P) carry mind = -1 and coordinates 0: their
 // distance is >= 0, so they stay at -1, below every real point's mind >= 0.
-#include "common.h"
+#include "pointset.h"
 
 namespace {
 
@@ -80,7 +79,7 @@ __global__ __launch_bounds__(T) void fps_kernel(const float* __restrict__ xyz, i
 #pragma unroll
         for (int j = 0; j < PPL; ++j) {
             const float d0 = x[j] - cx, d1 = y[j] - cy, d2 = z[j] - cz;
-            const float dist = (d0 * d0 + d1 * d1) + d2 * d2;
+            const float dist = sq_len(d0, d1, d2);
             mind[j] = dist < mind[j] ? dist : mind[j];
             if (mind[j] > bv) { bv = mind[j]; bj = j; }
         }
@@ -104,7 +103,7 @@ constexpr int GATHER_THREADS = 256;
 // out[m,n,:] = data[m, idx[m,n], :] (+ seg), one workgroup per cloud; with `normalize` the pc_normalize of the selection:
 //   c = fp32(float64 mean), the sum in a FIXED order: thread t adds its points n = t, t + 256, .. in ascending order to 0.0, the 64
 //       partials of a wave are combined by the xor butterfly 32, 16, .. 1, the four wave sums as ((w0 + w1) + w2) + w3, then / N
-//   d = fl(p - c);  m = sqrt(max_n fl(fl(d0 d0 + d1 d1) + d2 d2)) (sqrt is monotone: the max of the roots);  out = fl(d / m)
+//   d = fl(p - c);  m = sqrt(max_n sq_len(d0, d1, d2)) (sqrt is monotone: the max of the roots);  out = fl(d / m)
 // An index outside 0 .. P-1 reads nothing: its row is NaN and its seg -1 (and, normalised, so is the whole cloud).
 __global__ __launch_bounds__(GATHER_THREADS) void pool_gather_kernel(const float* __restrict__ data, const int64_t* __restrict__ seg,
                                                                      const int64_t* __restrict__ idx, int64_t P, int64_t N, int normalize,
@@ -117,7 +116,6 @@ __global__ __launch_bounds__(GATHER_THREADS) void pool_gather_kernel(const float
     const float* src = data + m * P * 3;
     const int64_t* id = idx + m * N;
     float* dst = out + m * N * 3;
-    const float nanf_ = __int_as_float(0x7fc00000);
 
     float c0 = 0.f, c1 = 0.f, c2 = 0.f;
     if (normalize) {
@@ -125,9 +123,9 @@ __global__ __launch_bounds__(GATHER_THREADS) void pool_gather_kernel(const float
         for (int64_t n = t; n < N; n += GATHER_THREADS) {
             const int64_t p = id[n];
             const bool ok = p >= 0 && p < P;
-            s0 += ok ? (double)src[p * 3 + 0] : (double)nanf_;
-            s1 += ok ? (double)src[p * 3 + 1] : (double)nanf_;
-            s2 += ok ? (double)src[p * 3 + 2] : (double)nanf_;
+            s0 += ok ? (double)src[p * 3 + 0] : (double)SVNET_QNAN;
+            s1 += ok ? (double)src[p * 3 + 1] : (double)SVNET_QNAN;
+            s2 += ok ? (double)src[p * 3 + 2] : (double)SVNET_QNAN;
         }
         s0 = wave_sum(s0); s1 = wave_sum(s1); s2 = wave_sum(s2);
         if (lane == 0) { wsum[0][wave] = s0; wsum[1][wave] = s1; wsum[2][wave] = s2; }
@@ -145,13 +143,13 @@ __global__ __launch_bounds__(GATHER_THREADS) void pool_gather_kernel(const float
             const int64_t p = id[n];
             if (p >= 0 && p < P) {
                 const float d0 = src[p * 3 + 0] - c0, d1 = src[p * 3 + 1] - c1, d2 = src[p * 3 + 2] - c2;
-                const float q = (d0 * d0 + d1 * d1) + d2 * d2;
+                const float q = sq_len(d0, d1, d2);
                 r2 = q > r2 ? q : r2;
             } else {
                 bad = true;
             }
         }
-        if (bad) r2 = nanf_;
+        if (bad) r2 = SVNET_QNAN;
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) {
             const float o = __shfl_xor(r2, off, 64);
@@ -166,7 +164,7 @@ __global__ __launch_bounds__(GATHER_THREADS) void pool_gather_kernel(const float
     }
     for (int64_t n = t; n < N; n += GATHER_THREADS) {
         const int64_t p = id[n];
-        float v0 = nanf_, v1 = nanf_, v2 = nanf_;
+        float v0 = SVNET_QNAN, v1 = SVNET_QNAN, v2 = SVNET_QNAN;
         int64_t sg = -1;
         if (p >= 0 && p < P) {
             v0 = src[p * 3 + 0]; v1 = src[p * 3 + 1]; v2 = src[p * 3 + 2];

@@ -4,17 +4,17 @@
 //
 // For one cloud, points xyz [N,3], centres new_xyz [S,3], optional attributes points [N,D] (channel-last); the contract is in
 // svnet_amd/group.py's docstring, tests/group_ref.py restates it independently:
-//   d_c = fl(new_xyz[s,c] - xyz[n,c]);  dist[s,n] = fl(fl(fl(d_0 d_0) + fl(d_1 d_1)) + fl(d_2 d_2))      (the difference form of fps.hip)
+//   d_c = fl(new_xyz[s,c] - xyz[n,c]);  dist[s,n] = sq_len(d_0, d_1, d_2)            (pointset.h: the distance, single-rounded)
 //   inside(s,n) = dist[s,n] <= r2                     (a NaN distance compares false: never inside)
 //   idx[s,0..nsample-1] = the first nsample inside points in ascending point index, slots past the number found = the first inside
 //                         index; count[s] = min(found, nsample); an empty group: count 0, every slot 0
 //   out[s,j,0..2] = fl(xyz[idx[s,j],c] - new_xyz[s,c]);  out[s,j,3..] = points[idx[s,j],:] copied bit for bit
-// This file is compiled with -ffp-contract=off (Makefile): every product, sum and difference is its own correctly rounded fp32 operation.
+// Every product, sum and difference is its own correctly rounded fp32 operation (pointset.h).
 //
 // ball_query: one wave per centre at a time, BQ_CPW centres after each other per wave, four waves (32 centres) per workgroup, the
-// workgroups of a cloud side by side.  The cloud's points pass through LDS in tiles of BQ_TILE points, packed as they lie in memory
-// (12 B each, 24 KiB: no opt-in, six workgroups per CU) and shared by the workgroup's 32 centres; lane l of a wave reads point
-// n0 + l, a stride of three dwords across the lanes (odd: no bank conflict).  A step takes 64 candidates in index order: the ballot
+// workgroups of a cloud side by side.  The cloud's points pass through LDS in tiles of POINTSET_TILE points (pointset.h: stage_xyz,
+// no padding), shared by the workgroup's 32 centres; lane l of a wave reads point n0 + l, a stride of three dwords across the
+// lanes (odd: no bank conflict).  A step takes 64 candidates in index order: the ballot
 // of `inside` is the step's membership mask, a lane's slot is found + (set lanes below it) (lanes_below, wave.h), so the row is
 // written in order and coalesced, and `found` grows by the mask's population.  The wave leaves a centre's loop as soon as
 // found >= nsample - uniform per wave, no divergence - which is the point of the kernel: at PointNet++ radii most groups fill after
@@ -26,23 +26,22 @@
 // rows' columns flat - consecutive threads, consecutive addresses, whatever 3 + D is, several rows per wave when 3 + D is small.
 // When 3 + D is a multiple of 4 and `out` is 16-byte aligned a thread writes one float4 (rows then start on 16-byte boundaries; the
 // attribute row is read with dword loads, shifted by three columns against the output it cannot be aligned with both).
-#include "common.h"
+#include "pointset.h"
 
 namespace {
 
 constexpr int BQ_THREADS = 256;
 constexpr int BQ_CPW = 8;                                        // centres per wave, one after the other
 constexpr int BQ_CENTRES = (BQ_THREADS / SVNET_WAVE) * BQ_CPW;   // centres per workgroup
-constexpr int BQ_TILE = 2048;                                    // points per LDS tile (x 12 B = 24 KiB), a multiple of 64
-constexpr int64_t GROUP_MAX_N = 32768;                           // the k-NN's limit on the points of a cloud
 constexpr int GP_THREADS = 256;
 constexpr int GP_MAX_ROWS = 1024;                                // output rows per workgroup, at most
 constexpr int GP_UNITS = 4096;                                   // floats or float4s per workgroup, about
+static_assert(POINTSET_TILE % SVNET_WAVE == 0, "ball_query_kernel takes the tile in whole 64-candidate steps");
 
 __global__ __launch_bounds__(BQ_THREADS) void ball_query_kernel(const float* __restrict__ xyz, const float* __restrict__ new_xyz, int64_t N,
                                                                 int64_t S, int64_t chunks, float r2, int nsample,
                                                                 int64_t* __restrict__ idx, int* __restrict__ count) {
-    __shared__ __align__(16) float tile[BQ_TILE * 3];
+    __shared__ __align__(16) float tile[POINTSET_TILE * 3];
     const int t = threadIdx.x, lane = lane_id(), wave = t >> 6;
     const int64_t b = blockIdx.x / chunks;
     const int64_t s0 = (blockIdx.x % chunks) * BQ_CENTRES + wave * BQ_CPW;            // this wave's first centre
@@ -55,11 +54,10 @@ __global__ __launch_bounds__(BQ_THREADS) void ball_query_kernel(const float* __r
 #pragma unroll
     for (int c = 0; c < BQ_CPW; ++c) { found[c] = 0; first[c] = 0; }
     int pending = mine > 0;
-    for (int64_t base = 0; base < N; base += BQ_TILE) {
-        const int cnt = (int)(N - base < BQ_TILE ? N - base : BQ_TILE);
+    for (int64_t base = 0; base < N; base += POINTSET_TILE) {
+        const int cnt = (int)(N - base < POINTSET_TILE ? N - base : POINTSET_TILE);
         if (base && !__syncthreads_or(pending)) break;           // the previous tile has been read by every wave; all full: done
-        const float* src = pts + base * 3;
-        for (int n = t; n < cnt * 3; n += BQ_THREADS) tile[n] = src[n];
+        stage_xyz<BQ_THREADS>(tile, pts + base * 3, cnt, t);
         __syncthreads();
         pending = 0;
 #pragma unroll
@@ -73,7 +71,7 @@ __global__ __launch_bounds__(BQ_THREADS) void ball_query_kernel(const float* __r
                 bool inside = false;
                 if (n < cnt) {
                     const float d0 = qx - tile[3 * n], d1 = qy - tile[3 * n + 1], d2 = qz - tile[3 * n + 2];
-                    inside = (d0 * d0 + d1 * d1) + d2 * d2 <= r2;
+                    inside = sq_len(d0, d1, d2) <= r2;
                 }
                 const unsigned long long mask = __ballot(inside);
                 if (mask) {
@@ -97,8 +95,6 @@ __global__ __launch_bounds__(BQ_THREADS) void ball_query_kernel(const float* __r
         if (lane == 0) count[b * S + s0 + c] = f;
     }
 }
-
-__device__ __forceinline__ int64_t clamp_index(int64_t i, int64_t N) { return i < 0 ? 0 : i >= N ? N - 1 : i; }
 
 // U = units per output row: (3 + D) / 4 float4s (VEC) or 3 + D floats; rows_per_block rows per workgroup; R = B * S * nsample rows.
 template <bool VEC>
@@ -150,10 +146,10 @@ inline int gp_rows(int64_t U) {
 
 }  // namespace
 
-extern "C" int svnet_ball_query_tile(void) { return BQ_TILE; }
+extern "C" int svnet_ball_query_tile(void) { return POINTSET_TILE; }
 
 extern "C" int svnet_group_supported(int64_t N, int64_t S, int64_t nsample, int64_t D) {
-    return N >= 1 && N <= GROUP_MAX_N && nsample >= 1 && nsample <= N && S >= 1 && S <= 0x7fffffffll && D >= 0 && D <= 0x7ffffff0ll ? 1 : 0;
+    return N >= 1 && N <= SVNET_KNN_MAX_N && nsample >= 1 && nsample <= N && S >= 1 && S <= 0x7fffffffll && D >= 0 && D <= 0x7ffffff0ll ? 1 : 0;
 }
 
 extern "C" int svnet_ball_query_f32(const float* xyz, const float* new_xyz, int64_t B, int64_t N, int64_t S, float r2, int64_t nsample,
@@ -162,11 +158,11 @@ extern "C" int svnet_ball_query_f32(const float* xyz, const float* new_xyz, int6
     SVNET_REQUIRE(B >= 1, SVNET_E_ARG, "svnet_ball_query_f32: B %lld must be positive", (long long)B);
     SVNET_REQUIRE(svnet_group_supported(N, S, nsample, 0), SVNET_E_UNSUPPORTED,
                   "svnet_ball_query_f32: N %lld, S %lld, nsample %lld: needs 1 <= nsample <= N <= %lld (the k-NN's limit on the points of a cloud), S >= 1",
-                  (long long)N, (long long)S, (long long)nsample, (long long)GROUP_MAX_N);
-    const int64_t chunks = svnet_cdiv(S, BQ_CENTRES);
-    SVNET_REQUIRE(B <= 0x7fffffffll / chunks, SVNET_E_UNSUPPORTED, "svnet_ball_query_f32: B %lld x ceil(S %lld / %d) workgroups > 2^31 - 1",
+                  (long long)N, (long long)S, (long long)nsample, (long long)SVNET_KNN_MAX_N);
+    const CloudGrid grid = cloud_grid(B, S, BQ_CENTRES);
+    SVNET_REQUIRE(grid.blocks > 0, SVNET_E_UNSUPPORTED, "svnet_ball_query_f32: B %lld x ceil(S %lld / %d) workgroups > 2^31 - 1",
                   (long long)B, (long long)S, BQ_CENTRES);
-    hipLaunchKernelGGL(ball_query_kernel, dim3((unsigned)(B * chunks)), dim3(BQ_THREADS), 0, (hipStream_t)stream, xyz, new_xyz, N, S, chunks,
+    hipLaunchKernelGGL(ball_query_kernel, dim3((unsigned)grid.blocks), dim3(BQ_THREADS), 0, (hipStream_t)stream, xyz, new_xyz, N, S, grid.chunks,
                        r2, (int)nsample, idx, count);
     SVNET_CHECK_LAUNCH("ball_query_kernel");
     return SVNET_OK;
@@ -179,7 +175,7 @@ extern "C" int svnet_group_points_f32(const float* xyz, const float* new_xyz, co
     SVNET_REQUIRE(B >= 1, SVNET_E_ARG, "svnet_group_points_f32: B %lld must be positive", (long long)B);
     SVNET_REQUIRE(svnet_group_supported(N, S, nsample, D), SVNET_E_UNSUPPORTED,
                   "svnet_group_points_f32: N %lld, S %lld, nsample %lld, D %lld: needs 1 <= nsample <= N <= %lld (the k-NN's limit on the points of a cloud), S >= 1, D >= 0",
-                  (long long)N, (long long)S, (long long)nsample, (long long)D, (long long)GROUP_MAX_N);
+                  (long long)N, (long long)S, (long long)nsample, (long long)D, (long long)SVNET_KNN_MAX_N);
     SVNET_REQUIRE(B <= 0x7fffffffll / S / nsample, SVNET_E_UNSUPPORTED, "svnet_group_points_f32: B %lld x S %lld x nsample %lld rows > 2^31 - 1",
                   (long long)B, (long long)S, (long long)nsample);
     const int64_t R = B * S * nsample, W = 3 + D;

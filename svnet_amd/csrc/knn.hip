@@ -1111,10 +1111,7 @@ static int knn_run_stream(const float* xT, const float* xx, int64_t B, int64_t N
 
 // The range the register-resident forms take (every shape they took before the streamed form existed still takes them) ...
 static bool knn_in_register_range(int64_t N, int k) { return N <= 4096 && k <= 64; }
-// ... and the whole range of the contract: past it the streamed form's limits (ids are 32-bit keys; a list holds 128) and MKL's K blocking
-#define SVNET_KNN_MAX_N 32768
-#define SVNET_KNN_MAX_K 128
-#define SVNET_KNN_MAX_C 384
+// ... and the whole range of the contract: SVNET_KNN_MAX_N, _MAX_K and _MAX_C (common.h)
 
 extern "C" int svnet_knn_table_fusable(int64_t B, int64_t N, int64_t C) {
     return B > 0 && N > 0 && (N % 32) == 0 && C >= 8 && C <= 384 && N <= 4096 && svnet_knn_table_is_channel_major(N, C, nullptr) ? 1 : 0;

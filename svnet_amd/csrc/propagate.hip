@@ -4,36 +4,35 @@
 //
 // For one cloud, queries q [P,3], sampled points r [N,3], features f [D,N] (the contract is in svnet_amd/propagate.py's docstring,
 // tests/propagate_ref.py restates it independently):
-//   d_c = fl(q[p,c] - r[n,c]);  dist[p,n] = fl(fl(fl(d_0 d_0) + fl(d_1 d_1)) + fl(d_2 d_2))          (the difference form of fps.hip)
+//   d_c = fl(q[p,c] - r[n,c]);  dist[p,n] = sq_len(d_0, d_1, d_2)                    (pointset.h: the distance, single-rounded)
 //   (dist3_j, i_j), j = 0..2: the min(3, N) smallest dist[p,:], ascending, the lower index first among equals; a slot that no
 //                             candidate took (N < 3; NaN and +inf distances) holds (+inf, 0)
 //   rec_j = fl(1 / fl(dist3_j + fp32(1e-8)));  s = fl(fl(rec_0 + rec_1) + rec_2);  w_j = fl(rec_j / s)
 //   out[d,p] = fl(fl(fl(f[d,i_0] w_0) + fl(f[d,i_1] w_1)) + fl(f[d,i_2] w_2))
-// This file is compiled with -ffp-contract=off (Makefile): every product, sum and quotient is its own correctly rounded fp32 operation.
+// Every product, sum and quotient is its own correctly rounded fp32 operation (pointset.h).
 //
 // three_nn: one thread per query point, 256 per workgroup, the workgroups of a cloud side by side.  The cloud's sampled points pass
-// through LDS in tiles of PROP_TILE points, packed as they lie in memory (12 B each, 24 KiB: no opt-in, six workgroups per CU); in
-// the candidate loop every lane reads the SAME address - three ds_read_b128 broadcasts per four candidates and wave, no bank
-// conflict - and the thread keeps its three best (distance, index) pairs in registers.  Candidates arrive in ascending index order
-// and are inserted on a strict <, so among equal distances the lower index stays in front: the tie rule costs nothing.  A NaN distance compares false and is never inserted;
-// the slots start at (+inf, 0), so every index written is inside [0, N) whatever the coordinates hold.
+// through LDS in tiles of POINTSET_TILE points (pointset.h: stage_xyz, padded with NaN to whole groups of four); in the candidate
+// loop every lane reads the SAME address - three ds_read_b128 broadcasts per four candidates and wave, no bank conflict - and the
+// thread keeps its three best (distance, index) pairs in registers.  Candidates arrive in ascending index order and are inserted
+// on a strict <, so among equal distances the lower index stays in front: the tie rule costs nothing.  A NaN distance compares
+// false and is never inserted; the slots start at (+inf, 0), so every index written is inside [0, N) whatever the coordinates hold.
 // three_interpolate: one thread per query point again, looping over the D channels: three gathers inside one 4 N-byte row per
 // channel (L2-resident), one store per channel, coalesced along p.  An index outside [0, N) is clamped into it: nothing is read
 // out of bounds whatever the caller hands in.
-#include "common.h"
+#include "pointset.h"
 
 namespace {
 
 constexpr int PROP_THREADS = 256;
-constexpr int PROP_TILE = 2048;                  // sampled points per LDS tile (x 12 B = 24 KiB), a multiple of 4
-constexpr int64_t PROP_MAX_N = 32768;            // the k-NN's limit on the points of a cloud
 constexpr float PROP_EPS = 1e-8f;                // pointnet_util.py:305
+static_assert(POINTSET_TILE % 4 == 0, "three_nn_kernel reads the tile in groups of four points");
 
 struct Best3 { float b0, b1, b2; int i0, i1, i2; };
 
 // the candidate at offset (d0, d1, d2) with index g against the three best: a strict < at every level, so an equal distance stays behind
 __device__ __forceinline__ void offer(Best3& s, float d0, float d1, float d2, int g) {
-    const float dist = (d0 * d0 + d1 * d1) + d2 * d2;
+    const float dist = sq_len(d0, d1, d2);
     if (dist < s.b2) {
         if (dist < s.b1) {
             s.b2 = s.b1; s.i2 = s.i1;
@@ -48,7 +47,7 @@ __device__ __forceinline__ void offer(Best3& s, float d0, float d1, float d2, in
 __global__ __launch_bounds__(PROP_THREADS) void three_nn_kernel(const float* __restrict__ query, const float* __restrict__ ref, int64_t P,
                                                                 int64_t N, int64_t chunks, int64_t* __restrict__ idx,
                                                                 float* __restrict__ dist3, float* __restrict__ weight) {
-    __shared__ __align__(16) float tile[PROP_TILE * 3];
+    __shared__ __align__(16) float tile[POINTSET_TILE * 3];
     const int t = threadIdx.x;
     const int64_t b = blockIdx.x / chunks;
     const int64_t p = (blockIdx.x % chunks) * PROP_THREADS + t;
@@ -57,14 +56,12 @@ __global__ __launch_bounds__(PROP_THREADS) void three_nn_kernel(const float* __r
     const float* r = ref + b * N * 3;
     const float qx = q[0], qy = q[1], qz = q[2];
 
-    const float inf = __int_as_float(0x7f800000), nan = __int_as_float(0x7fc00000);
-    Best3 best = {inf, inf, inf, 0, 0, 0};
-    for (int64_t base = 0; base < N; base += PROP_TILE) {
-        const int cnt = (int)(N - base < PROP_TILE ? N - base : PROP_TILE);
+    Best3 best = {SVNET_INF, SVNET_INF, SVNET_INF, 0, 0, 0};
+    for (int64_t base = 0; base < N; base += POINTSET_TILE) {
+        const int cnt = (int)(N - base < POINTSET_TILE ? N - base : POINTSET_TILE);
         const int groups = (cnt + 3) >> 2;                       // four points = 48 B = three 16-byte reads
         if (base) __syncthreads();                               // the previous tile has been read by every wave
-        const float* src = r + base * 3;
-        for (int n = t; n < groups * 12; n += PROP_THREADS) tile[n] = n < cnt * 3 ? src[n] : nan;    // (NaN padding: never taken)
+        stage_xyz<PROP_THREADS, 4>(tile, r + base * 3, cnt, t);  // (NaN padding to whole groups: never taken)
         __syncthreads();
         const float4* v = reinterpret_cast<const float4*>(tile);
         const int g0 = (int)base;
@@ -88,8 +85,6 @@ __global__ __launch_bounds__(PROP_THREADS) void three_nn_kernel(const float* __r
     weight[o + 0] = r0 / s; weight[o + 1] = r1 / s; weight[o + 2] = r2 / s;
 }
 
-__device__ __forceinline__ int64_t clamp_index(int64_t i, int64_t N) { return i < 0 ? 0 : i >= N ? N - 1 : i; }
-
 __global__ __launch_bounds__(PROP_THREADS) void three_interpolate_kernel(const float* __restrict__ feat, const int64_t* __restrict__ idx,
                                                                          const float* __restrict__ weight, int64_t D, int64_t N, int64_t P,
                                                                          int64_t chunks, float* __restrict__ out) {
@@ -110,16 +105,10 @@ __global__ __launch_bounds__(PROP_THREADS) void three_interpolate_kernel(const f
 
 }  // namespace
 
-extern "C" int svnet_propagate_tile(void) { return PROP_TILE; }
+extern "C" int svnet_propagate_tile(void) { return POINTSET_TILE; }
 
 extern "C" int svnet_propagate_supported(int64_t P, int64_t N, int64_t D) {
-    return P >= 1 && D >= 1 && N >= 1 && N <= PROP_MAX_N && svnet_cdiv(P, PROP_THREADS) <= 0x7fffffffll ? 1 : 0;
-}
-
-// workgroups of a launch over B clouds of P query points, 0 when they do not fit a 32-bit grid
-static int64_t prop_blocks(int64_t B, int64_t P) {
-    const int64_t chunks = svnet_cdiv(P, PROP_THREADS);
-    return B <= 0x7fffffffll / chunks ? B * chunks : 0;
+    return P >= 1 && D >= 1 && N >= 1 && N <= SVNET_KNN_MAX_N && svnet_cdiv(P, PROP_THREADS) <= 0x7fffffffll ? 1 : 0;
 }
 
 extern "C" int svnet_three_nn_f32(const float* query, const float* ref, int64_t B, int64_t P, int64_t N, int64_t* idx, float* dist3,
@@ -129,12 +118,12 @@ extern "C" int svnet_three_nn_f32(const float* query, const float* ref, int64_t 
                   (long long)P, (long long)N);
     SVNET_REQUIRE(svnet_propagate_supported(P, N, 1), SVNET_E_UNSUPPORTED,
                   "svnet_three_nn_f32: N %lld > %lld (the k-NN's limit on the points of a cloud) or P %lld past a 32-bit grid", (long long)N,
-                  (long long)PROP_MAX_N, (long long)P);
-    const int64_t blocks = prop_blocks(B, P);
-    SVNET_REQUIRE(blocks > 0, SVNET_E_UNSUPPORTED, "svnet_three_nn_f32: B %lld x ceil(P %lld / %d) workgroups > 2^31 - 1", (long long)B,
+                  (long long)SVNET_KNN_MAX_N, (long long)P);
+    const CloudGrid grid = cloud_grid(B, P, PROP_THREADS);
+    SVNET_REQUIRE(grid.blocks > 0, SVNET_E_UNSUPPORTED, "svnet_three_nn_f32: B %lld x ceil(P %lld / %d) workgroups > 2^31 - 1", (long long)B,
                   (long long)P, PROP_THREADS);
-    hipLaunchKernelGGL(three_nn_kernel, dim3((unsigned)blocks), dim3(PROP_THREADS), 0, (hipStream_t)stream, query, ref, P, N,
-                       svnet_cdiv(P, PROP_THREADS), idx, dist3, weight);
+    hipLaunchKernelGGL(three_nn_kernel, dim3((unsigned)grid.blocks), dim3(PROP_THREADS), 0, (hipStream_t)stream, query, ref, P, N,
+                       grid.chunks, idx, dist3, weight);
     SVNET_CHECK_LAUNCH("three_nn_kernel");
     return SVNET_OK;
 }
@@ -146,12 +135,12 @@ extern "C" int svnet_three_interpolate_f32(const float* feat, const int64_t* idx
                   (long long)B, (long long)D, (long long)N, (long long)P);
     SVNET_REQUIRE(svnet_propagate_supported(P, N, D), SVNET_E_UNSUPPORTED,
                   "svnet_three_interpolate_f32: N %lld > %lld (the k-NN's limit on the points of a cloud) or P %lld past a 32-bit grid",
-                  (long long)N, (long long)PROP_MAX_N, (long long)P);
-    const int64_t blocks = prop_blocks(B, P);
-    SVNET_REQUIRE(blocks > 0, SVNET_E_UNSUPPORTED, "svnet_three_interpolate_f32: B %lld x ceil(P %lld / %d) workgroups > 2^31 - 1",
+                  (long long)N, (long long)SVNET_KNN_MAX_N, (long long)P);
+    const CloudGrid grid = cloud_grid(B, P, PROP_THREADS);
+    SVNET_REQUIRE(grid.blocks > 0, SVNET_E_UNSUPPORTED, "svnet_three_interpolate_f32: B %lld x ceil(P %lld / %d) workgroups > 2^31 - 1",
                   (long long)B, (long long)P, PROP_THREADS);
-    hipLaunchKernelGGL(three_interpolate_kernel, dim3((unsigned)blocks), dim3(PROP_THREADS), 0, (hipStream_t)stream, feat, idx, weight, D,
-                       N, P, svnet_cdiv(P, PROP_THREADS), out);
+    hipLaunchKernelGGL(three_interpolate_kernel, dim3((unsigned)grid.blocks), dim3(PROP_THREADS), 0, (hipStream_t)stream, feat, idx, weight, D,
+                       N, P, grid.chunks, out);
     SVNET_CHECK_LAUNCH("three_interpolate_kernel");
     return SVNET_OK;
 }

@@ -48,6 +48,7 @@ by `farthest_point_sample`, models/utils/pointnet_util.py:63-84, then `pc_normal
     for one cloud xyz [P,3], a start index s and npoint <= P (all fp32, each operation rounded once, never an fma):
         mind[p] = fp32(1e10);  f = s
         for i in 0 .. npoint-1:  idx[i] = f;  d_c = fl(xyz[p,c] - xyz[f,c]);  dist = fl(fl(fl(d_0 d_0) + fl(d_1 d_1)) + fl(d_2 d_2))
+                                 (the point-set helpers' one distance: svnet_amd/csrc/pointset.h)
                                  mind[p] = dist < mind[p] ? dist : mind[p];  f = the smallest p with mind[p] == max_p mind[p]
     which is the reference's loop with its `torch.randint` start made an input (default: fps_start, counter-based like everything
     above): given the start, the index list equals the reference's CPU result bit for bit.  Coordinates must be finite.
@@ -62,7 +63,7 @@ import ctypes
 import numpy as np
 import torch
 
-from . import _lib, _ops, synth
+from . import _lib, _ops, _pointset, synth
 
 SELECT_MODES = {"first_shuffled": 0, "subset": 1, "first_ordered": 2}      # SVNET_BATCH_* (include/svnet_hip.h)
 ROTATE_MODES = {"none": 0, None: 0, "z": 1, "so3": 2}                      # SVNET_BATCH_ROTATE_*
@@ -110,23 +111,20 @@ def farthest_point_sample(xyz, npoint, start):
     _ops._hip(xyz, start)
     if xyz.dtype != torch.float32 or start.dtype != torch.int64:
         raise TypeError("farthest_point_sample: xyz must be float32 and start int64, got %s and %s" % (xyz.dtype, start.dtype))
-    if xyz.dim() != 3 or xyz.shape[2] != 3 or xyz.shape[0] < 1:
-        raise ValueError("farthest_point_sample: xyz must be [B,P,3], got %s" % (tuple(xyz.shape),))
-    B, P, npoint = int(xyz.shape[0]), int(xyz.shape[1]), int(npoint)
+    B, P = _pointset.check_cloud("farthest_point_sample", "xyz", xyz, "P")
+    npoint = int(npoint)
     if tuple(start.shape) != (B,):
         raise ValueError("farthest_point_sample: start must be [B] = [%d], got %s" % (B, tuple(start.shape)))
     if not xyz.is_contiguous() or not start.is_contiguous():
         raise ValueError("farthest_point_sample: xyz and start must be contiguous")
     if start.device != xyz.device:
         raise ValueError("farthest_point_sample: xyz on %s, start on %s" % (xyz.device, start.device))
-    if not _lib.lib().svnet_fps_supported(P, npoint):
-        raise _lib.SvnetHipError("farthest_point_sample: P = %d, npoint = %d is not supported (1 <= npoint <= P <= 16384)" % (P, npoint))
+    _pointset.fps_supported("farthest_point_sample", "P", P, npoint)
     lo, hi = (int(v) for v in torch.aminmax(start))
     if lo < 0 or hi >= P:
         raise ValueError("farthest_point_sample: start outside 0 .. P-1 = %d (min %d, max %d)" % (P - 1, lo, hi))
     idx = torch.empty(B, npoint, dtype=torch.int64, device=xyz.device)
-    with torch.cuda.device(xyz.device):
-        _lib.call("svnet_fps_f32", _ops._p(xyz), B, P, npoint, _ops._p(start), _ops._p(idx), _ops._stream())
+    _pointset.fps_launch(xyz, B, P, npoint, start, idx)
     return idx
 
 
@@ -153,9 +151,7 @@ class DevicePool:
             seg = _as_tensor(seg, torch.int64, "seg")
             if tuple(seg.shape) != (M, P):
                 raise ValueError("DevicePool: seg must be [M,P] = %s, got %s" % ((M, P), tuple(seg.shape)))
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise RuntimeError("svnet_amd: DevicePool needs a HIP (cuda) device, got %s — the product path has no CPU fallback" % device)
+        device = _pointset.hip_device("DevicePool", device)
         self.M, self.P, self.device = M, P, device
         self.data = data.to(device).contiguous()
         self.label = label.reshape(M).to(device).contiguous()

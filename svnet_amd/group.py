@@ -10,14 +10,13 @@ of a hierarchical encoder, which groups raw coordinates and input attributes.
     grouped = group_points(xyz, new_xyz, idx, points)                           # [B,512,32,3+D]
 
 The contract, for one cloud: points xyz [N,3], centres new_xyz [S,3], optional attributes points [N,D] (channel-last, as the
-reference's `sample_and_group` takes them), all fp32.  Every operation is rounded once and never contracted into an fma (the kernels
-are compiled like fps.hip and propagate.hip, with contraction off); fl() is rounding to fp32.
+reference's `sample_and_group` takes them), all fp32.  Every operation is rounded once and never contracted into an fma; fl() is
+rounding to fp32.
 
     distance    d_c = fl(new_xyz[s,c] - xyz[n,c]);   dist[s,n] = fl(fl(fl(d_0 d_0) + fl(d_1 d_1)) + fl(d_2 d_2))
-                The difference form of fps.hip and propagate.hip.  The reference's expanded form -2 a.b + |a|^2 + |b|^2 is
-                deliberately NOT copied, for the reason given in propagate.py: centres coincide with points, and there the expanded
-                form rounds to small values of either sign.  On coordinates whose squares and products are exact in fp32 the two
-                forms agree bit for bit.
+                The point-set helpers' one distance, the difference form (svnet_amd/csrc/pointset.h states it and why the reference's
+                expanded form is not copied).  On coordinates whose squares and products are exact in fp32 the two forms agree bit
+                for bit.
     membership  point n is inside group s when dist[s,n] <= r2 (the reference writes `sqrdists > radius ** 2` -> outside).  r2 is
                 an fp32 argument of the C entry point; this layer passes fp32(radius * radius) with the square taken in double, the
                 scalar torch's comparison sees.  A NaN distance is never inside.  (Whether torch compares in fp32 or wider does not
@@ -45,8 +44,10 @@ B * S * nsample <= 2^31 - 1 for the grouping; `sample_and_group` also has farthe
 import numpy as np
 import torch
 
-from . import _lib, _ops
+from . import _lib, _ops, _pointset
 from .data import fps_start
+
+_WHAT = "the grouping"          # in the messages of _pointset.check_tensors
 
 
 def tile():
@@ -61,37 +62,19 @@ def _r2(radius):
         return float(np.float32(radius * radius))
 
 
-def _check(name, tensors, dtypes):
-    """tensors: {argument name: tensor}; the type, dtype, device-match, contiguity and no-gradient checks shared by the entry points
-    (the HIP device itself is checked after the shapes, by _ops._hip)."""
-    for k, t in tensors.items():
-        if not isinstance(t, torch.Tensor):
-            raise TypeError("%s: %s must be a tensor, got %s" % (name, k, type(t).__name__))
-    for (k, t), dt in zip(tensors.items(), dtypes):
-        if t.dtype != dt:
-            raise TypeError("%s: %s must be %s, got %s" % (name, k, dt, t.dtype))
-    first = next(iter(tensors.values()))
-    for k, t in tensors.items():
-        if t.device != first.device:
-            raise ValueError("%s: %s on %s, %s on %s" % (name, next(iter(tensors)), first.device, k, t.device))
-        if not t.is_contiguous():
-            raise ValueError("%s: %s must be contiguous" % (name, k))
-        if t.requires_grad:
-            raise ValueError("%s: %s requires grad - the grouping is forward only" % (name, k))
+def _with_points(tensors, dtypes, points):
+    """(tensors, dtypes) for _pointset.check_tensors, with the optional float32 attributes `points` after them when given."""
+    return (tensors, dtypes) if points is None else (dict(tensors, points=points), dtypes + [torch.float32])
 
 
 def _supported(name, N, S, nsample, D):
     if not _lib.lib().svnet_group_supported(N, S, nsample, D):
-        raise _lib.SvnetHipError("%s: N = %d, S = %d, nsample = %d, D = %d is not supported (1 <= nsample <= N <= 32768, S >= 1, D >= 0)"
-                                 % (name, N, S, nsample, D))
+        raise _lib.SvnetHipError("%s: N = %d, S = %d, nsample = %d, D = %d is not supported (1 <= nsample <= N <= %d, S >= 1, D >= 0)"
+                                 % (name, N, S, nsample, D, _pointset.MAX_N))
 
 
 def _cloud_shapes(name, xyz, new_xyz):
-    if xyz.dim() != 3 or xyz.shape[2] != 3 or xyz.shape[0] < 1:
-        raise ValueError("%s: xyz must be [B,N,3], got %s" % (name, tuple(xyz.shape)))
-    if new_xyz.dim() != 3 or new_xyz.shape[2] != 3 or new_xyz.shape[0] != xyz.shape[0]:
-        raise ValueError("%s: new_xyz must be [B,S,3] with B = %d, got %s" % (name, xyz.shape[0], tuple(new_xyz.shape)))
-    return int(xyz.shape[0]), int(xyz.shape[1]), int(new_xyz.shape[1])
+    return _pointset.check_cloud_pair(name, ("xyz", "new_xyz"), xyz, new_xyz, "NS")
 
 
 def _points_shape(name, points, B, N):
@@ -115,7 +98,7 @@ def query_ball_point(radius, nsample, xyz, new_xyz, return_count=False):
     """The reference's name and argument order: xyz [B,N,3], new_xyz [B,S,3] float32 on a HIP device -> idx [B,S,nsample] int64, the
     first nsample points within `radius` of every centre in ascending index, padded with the first (module docstring); with
     return_count also count [B,S] int32.  One launch, no host read; no gradient."""
-    _check("query_ball_point", {"xyz": xyz, "new_xyz": new_xyz}, (torch.float32, torch.float32))
+    _pointset.check_tensors("query_ball_point", {"xyz": xyz, "new_xyz": new_xyz}, (torch.float32, torch.float32), _WHAT)
     B, N, S = _cloud_shapes("query_ball_point", xyz, new_xyz)
     nsample = int(nsample)
     _ops._hip(xyz, new_xyz)
@@ -127,11 +110,8 @@ def query_ball_point(radius, nsample, xyz, new_xyz, return_count=False):
 
 
 def _group_args(name, xyz, new_xyz, idx, points):
-    tensors, dtypes = {"xyz": xyz, "new_xyz": new_xyz, "idx": idx}, [torch.float32, torch.float32, torch.int64]
-    if points is not None:
-        tensors["points"] = points
-        dtypes.append(torch.float32)
-    _check(name, tensors, dtypes)
+    tensors, dtypes = _with_points({"xyz": xyz, "new_xyz": new_xyz, "idx": idx}, [torch.float32, torch.float32, torch.int64], points)
+    _pointset.check_tensors(name, tensors, dtypes, _WHAT)
     B, N, S = _cloud_shapes(name, xyz, new_xyz)
     if idx.dim() != 3 or idx.shape[0] != B or idx.shape[1] != S:
         raise ValueError("%s: idx must be [B,S,nsample] with B = %d, S = %d, got %s" % (name, B, S, tuple(idx.shape)))
@@ -149,9 +129,7 @@ def group_points(xyz, new_xyz, idx, points=None, out=None):
     if out is None:
         out = torch.empty(B, S, nsample, 3 + D, dtype=torch.float32, device=xyz.device)
     else:
-        _check("group_points", {"xyz": xyz, "out": out}, (torch.float32, torch.float32))
-        if tuple(out.shape) != (B, S, nsample, 3 + D):
-            raise ValueError("group_points: out must be [B,S,nsample,3+D] = %s, got %s" % ((B, S, nsample, 3 + D), tuple(out.shape)))
+        _pointset.check_out("group_points", {"xyz": xyz}, out, "[B,S,nsample,3+D]", (B, S, nsample, 3 + D), _WHAT)
     _group_launch(xyz, new_xyz, points, idx, B, N, S, nsample, D, out)
     return out
 
@@ -163,21 +141,16 @@ def sample_and_group(npoint, radius, nsample, xyz, points, returnfps=False, star
     The reference's torch.randint start is an input, as in data.farthest_point_sample: `start` [B] int64 (a start outside 0 .. N-1 is
     clamped into the cloud by the sampling kernel), or None for data.fps_start(seed, B, N), which is copied from the host: a caller
     that captures the call into a HIP graph passes a device tensor.  No gradient."""
-    tensors, dtypes = {"xyz": xyz}, [torch.float32]
-    if points is not None:
-        tensors["points"] = points
-        dtypes.append(torch.float32)
+    tensors, dtypes = _with_points({"xyz": xyz}, [torch.float32], points)
     if start is not None and isinstance(start, torch.Tensor):
         tensors["start"] = start
         dtypes.append(torch.int64)
-    _check("sample_and_group", tensors, dtypes)
-    if xyz.dim() != 3 or xyz.shape[2] != 3 or xyz.shape[0] < 1:
-        raise ValueError("sample_and_group: xyz must be [B,N,3], got %s" % (tuple(xyz.shape),))
-    B, N, S, nsample = int(xyz.shape[0]), int(xyz.shape[1]), int(npoint), int(nsample)
+    _pointset.check_tensors("sample_and_group", tensors, dtypes, _WHAT)
+    B, N = _pointset.check_cloud("sample_and_group", "xyz", xyz, "N")
+    S, nsample = int(npoint), int(nsample)
     D = 0 if points is None else _points_shape("sample_and_group", points, B, N)
     _ops._hip(xyz, points)
-    if not _lib.lib().svnet_fps_supported(N, S):
-        raise _lib.SvnetHipError("sample_and_group: N = %d, npoint = %d is not supported (1 <= npoint <= N <= 16384)" % (N, S))
+    _pointset.fps_supported("sample_and_group", "N", N, S)
     _supported("sample_and_group", N, S, nsample, D)
     if start is None:
         start = torch.from_numpy(fps_start(seed, B, N)).to(xyz.device)
@@ -187,9 +160,8 @@ def sample_and_group(npoint, radius, nsample, xyz, points, returnfps=False, star
         raise ValueError("sample_and_group: start must be [B] = [%d], got %s" % (B, tuple(start.shape)))
     dev = xyz.device
     fps_idx = torch.empty(B, S, dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
-        _lib.call("svnet_fps_f32", _ops._p(xyz), B, N, S, _ops._p(start), _ops._p(fps_idx), _ops._stream())
-    new_xyz = torch.gather(xyz, 1, fps_idx.unsqueeze(2).expand(-1, -1, 3)).contiguous()
+    _pointset.fps_launch(xyz, B, N, S, start, fps_idx)
+    new_xyz = _pointset.gather_rows(xyz, fps_idx).contiguous()
     idx = torch.empty(B, S, nsample, dtype=torch.int64, device=dev)
     count = torch.empty(B, S, dtype=torch.int32, device=dev)
     new_points = torch.empty(B, S, nsample, 3 + D, dtype=torch.float32, device=dev)
@@ -197,21 +169,15 @@ def sample_and_group(npoint, radius, nsample, xyz, points, returnfps=False, star
     _group_launch(xyz, new_xyz, points, idx, B, N, S, nsample, D, new_points)
     if not returnfps:
         return new_xyz, new_points
-    grouped_xyz = torch.gather(xyz, 1, idx.view(B, S * nsample, 1).expand(-1, -1, 3)).view(B, S, nsample, 3)
+    grouped_xyz = _pointset.gather_rows(xyz, idx.view(B, S * nsample)).view(B, S, nsample, 3)
     return new_xyz, new_points, grouped_xyz, fps_idx
 
 
 def sample_and_group_all(xyz, points):
     """The reference's trivial form: one group of all N points around centre 0, in order.  xyz [B,N,3], points [B,N,D] or None ->
     (new_xyz [B,1,3] of zeros, new_points [B,1,N,3+D]).  torch views and one cat."""
-    tensors, dtypes = {"xyz": xyz}, [torch.float32]
-    if points is not None:
-        tensors["points"] = points
-        dtypes.append(torch.float32)
-    _check("sample_and_group_all", tensors, dtypes)
-    if xyz.dim() != 3 or xyz.shape[2] != 3 or xyz.shape[0] < 1:
-        raise ValueError("sample_and_group_all: xyz must be [B,N,3], got %s" % (tuple(xyz.shape),))
-    B, N = int(xyz.shape[0]), int(xyz.shape[1])
+    _pointset.check_tensors("sample_and_group_all", *_with_points({"xyz": xyz}, [torch.float32], points), _WHAT)
+    B, N = _pointset.check_cloud("sample_and_group_all", "xyz", xyz, "N")
     if points is not None:
         _points_shape("sample_and_group_all", points, B, N)
     _ops._hip(xyz, points)
@@ -226,9 +192,7 @@ class Grouper:
     and counts of that call are in .idx[:count] / .count[:count]); nothing is allocated per call."""
 
     def __init__(self, B, N, S, nsample, D, device):
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise RuntimeError("svnet_amd: Grouper needs a HIP (cuda) device, got %s — the product path has no CPU fallback" % device)
+        device = _pointset.hip_device("Grouper", device)
         self.B, self.N, self.S, self.nsample, self.D = int(B), int(N), int(S), int(nsample), int(D)
         if self.B < 1:
             raise ValueError("Grouper: B = %d < 1" % self.B)
@@ -238,11 +202,7 @@ class Grouper:
         self.out = torch.empty(self.B, self.S, self.nsample, 3 + self.D, dtype=torch.float32, device=device)
 
     def run(self, xyz, new_xyz, radius, points=None):
-        tensors, dtypes = {"xyz": xyz, "new_xyz": new_xyz}, [torch.float32, torch.float32]
-        if points is not None:
-            tensors["points"] = points
-            dtypes.append(torch.float32)
-        _check("Grouper.run", tensors, dtypes)
+        _pointset.check_tensors("Grouper.run", *_with_points({"xyz": xyz, "new_xyz": new_xyz}, [torch.float32, torch.float32], points), _WHAT)
         count, N, S = _cloud_shapes("Grouper.run", xyz, new_xyz)
         D = 0 if points is None else _points_shape("Grouper.run", points, count, N)
         _ops._hip(xyz, new_xyz, points)

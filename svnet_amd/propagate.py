@@ -12,13 +12,12 @@ without its MLP - farthest point sampling's counterpart from the same file.
     result = train.evaluate_dense(fwd_step, loader, metrics, dense)     # the whole evaluation pass, shape IoU of the CLOUDS
 
 The contract, for one cloud: queries q [P,3], sampled points r [N,3], features f [D,N] (channel-first, as the part-seg models'
-[B,num_part,N] logits lie), all fp32.  Every operation is rounded once and never contracted into an fma (the kernels are compiled
-like fps.hip and batch.hip, with contraction off); fl() is rounding to fp32.
+[B,num_part,N] logits lie), all fp32.  Every operation is rounded once and never contracted into an fma; fl() is rounding to fp32.
 
     distances   d_c = fl(q[p,c] - r[n,c]);   dist[p,n] = fl(fl(fl(d_0 d_0) + fl(d_1 d_1)) + fl(d_2 d_2))
-                The difference form fps.hip uses: never negative, exactly 0 at a coincident point.  The reference's expanded form
-                -2 q.r + |q|^2 + |r|^2 is deliberately NOT copied: after resample_fps every sampled point coincides with a dense
-                point, there the expanded form rounds to small values of either sign, and 1 / (dist + 1e-8) turns that into garbage.
+                The point-set helpers' one distance, the difference form: never negative, exactly 0 at a coincident point - which
+                every sampled point is after resample_fps (svnet_amd/csrc/pointset.h states it and why the reference's expanded form
+                -2 q.r + |q|^2 + |r|^2 is not copied).
     neighbours  the K = min(3, N) smallest dist[p,:], ascending, the lower index first among equals: idx [P,3] int64 and
                 dist3 [P,3] fp32.  Slots past K (N < 3 only) hold index 0, dist3 = +inf and weight 0.  Indices are always inside
                 [0, N), also when a coordinate is NaN or infinite (a NaN or +inf distance is never taken; its slot stays as a slot
@@ -36,7 +35,9 @@ HIP device raise.  Limits: 1 <= N <= 32768 (the k-NN's limit), P >= 1, D >= 1, B
 """
 import torch
 
-from . import _lib, _ops
+from . import _lib, _ops, _pointset
+
+_WHAT = "the propagation"        # in the messages of _pointset.check_tensors
 
 
 def tile():
@@ -44,36 +45,13 @@ def tile():
     return int(_lib.lib().svnet_propagate_tile())
 
 
-def _check(name, tensors, dtypes):
-    """tensors: {argument name: tensor}; the type, dtype, device-match and contiguity checks shared by the entry points (the HIP
-    device itself is checked after the shapes, by _ops._hip)."""
-    for k, t in tensors.items():
-        if not isinstance(t, torch.Tensor):
-            raise TypeError("%s: %s must be a tensor, got %s" % (name, k, type(t).__name__))
-    for (k, t), dt in zip(tensors.items(), dtypes):
-        if t.dtype != dt:
-            raise TypeError("%s: %s must be %s, got %s" % (name, k, dt, t.dtype))
-    first = next(iter(tensors.values()))
-    for k, t in tensors.items():
-        if t.device != first.device:
-            raise ValueError("%s: %s on %s, %s on %s" % (name, next(iter(tensors)), first.device, k, t.device))
-        if not t.is_contiguous():
-            raise ValueError("%s: %s must be contiguous" % (name, k))
-        if t.requires_grad:
-            raise ValueError("%s: %s requires grad - the propagation is forward only" % (name, k))
-
-
 def _supported(name, P, N, D):
     if not _lib.lib().svnet_propagate_supported(P, N, D):
-        raise _lib.SvnetHipError("%s: P = %d, N = %d, D = %d is not supported (P >= 1, D >= 1, 1 <= N <= 32768)" % (name, P, N, D))
+        raise _lib.SvnetHipError("%s: P = %d, N = %d, D = %d is not supported (P >= 1, D >= 1, 1 <= N <= %d)" % (name, P, N, D, _pointset.MAX_N))
 
 
 def _nn_shapes(name, query, ref):
-    if query.dim() != 3 or query.shape[2] != 3 or query.shape[0] < 1:
-        raise ValueError("%s: query must be [B,P,3], got %s" % (name, tuple(query.shape)))
-    if ref.dim() != 3 or ref.shape[2] != 3 or ref.shape[0] != query.shape[0]:
-        raise ValueError("%s: ref must be [B,N,3] with B = %d, got %s" % (name, query.shape[0], tuple(ref.shape)))
-    return int(query.shape[0]), int(query.shape[1]), int(ref.shape[1])
+    return _pointset.check_cloud_pair(name, ("query", "ref"), query, ref, "PN")
 
 
 def _nn_launch(query, ref, B, P, N, idx, dist3, weight):
@@ -89,7 +67,7 @@ def _interp_launch(feat, idx, weight, B, D, N, P, out):
 def three_nn(query, ref):
     """query [B,P,3], ref [B,N,3] float32 on a HIP device -> (idx [B,P,3] int64, dist3 [B,P,3], weight [B,P,3]): the three nearest
     `ref` points of every query point and their interpolation weights (module docstring).  One launch, no host read; no gradient."""
-    _check("three_nn", {"query": query, "ref": ref}, (torch.float32, torch.float32))
+    _pointset.check_tensors("three_nn", {"query": query, "ref": ref}, (torch.float32, torch.float32), _WHAT)
     B, P, N = _nn_shapes("three_nn", query, ref)
     _ops._hip(query, ref)
     _supported("three_nn", P, N, 1)
@@ -112,16 +90,14 @@ def _interp_shapes(name, feat, idx, weight):
 def _out_buffer(name, out, feat, B, D, P):
     if out is None:
         return torch.empty(B, D, P, dtype=torch.float32, device=feat.device)
-    _check(name, {"feat": feat, "out": out}, (torch.float32, torch.float32))
-    if tuple(out.shape) != (B, D, P):
-        raise ValueError("%s: out must be [B,D,P] = %s, got %s" % (name, (B, D, P), tuple(out.shape)))
+    _pointset.check_out(name, {"feat": feat}, out, "[B,D,P]", (B, D, P), _WHAT)
     return out
 
 
 def three_interpolate(feat, idx, weight, out=None):
     """feat [B,D,N] float32, idx [B,P,3] int64, weight [B,P,3] float32 -> [B,D,P]: out[b,d,p] = sum_j feat[b,d,idx[b,p,j]] weight[b,p,j]
     in the contract's order.  An index outside [0, N) is clamped into it.  One launch, no host read; no gradient."""
-    _check("three_interpolate", {"feat": feat, "idx": idx, "weight": weight}, (torch.float32, torch.int64, torch.float32))
+    _pointset.check_tensors("three_interpolate", {"feat": feat, "idx": idx, "weight": weight}, (torch.float32, torch.int64, torch.float32), _WHAT)
     B, D, N, P = _interp_shapes("three_interpolate", feat, idx, weight)
     _ops._hip(feat, idx, weight)
     _supported("three_interpolate", P, N, D)
@@ -134,7 +110,7 @@ def propagate(query, ref, feat, out=None):
     """three_nn(query, ref) then three_interpolate(feat, ...): feat [B,D,N] at the points ref [B,N,3] -> [B,D,P] at query [B,P,3].
     Two launches on the current stream, no host read and no synchronisation, so it can be captured in a HIP graph; `out` lets a
     caller keep a fixed buffer.  No gradient."""
-    _check("propagate", {"query": query, "ref": ref, "feat": feat}, (torch.float32,) * 3)
+    _pointset.check_tensors("propagate", {"query": query, "ref": ref, "feat": feat}, (torch.float32,) * 3, _WHAT)
     B, P, N = _nn_shapes("propagate", query, ref)
     if feat.dim() != 3 or feat.shape[0] != B or feat.shape[2] != N:
         raise ValueError("propagate: feat must be [B,D,N] with B = %d, N = %d, got %s" % (B, N, tuple(feat.shape)))
@@ -155,9 +131,7 @@ class Propagator:
     [B,D,P].  run(query, ref, feat) takes the first `count` clouds of each and returns out[:count]; nothing is allocated per call."""
 
     def __init__(self, B, D, N, P, device):
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise RuntimeError("svnet_amd: Propagator needs a HIP (cuda) device, got %s — the product path has no CPU fallback" % device)
+        device = _pointset.hip_device("Propagator", device)
         self.B, self.D, self.N, self.P = int(B), int(D), int(N), int(P)
         if self.B < 1:
             raise ValueError("Propagator: B = %d < 1" % self.B)
@@ -168,7 +142,7 @@ class Propagator:
         self.out = torch.empty(self.B, self.D, self.P, dtype=torch.float32, device=device)
 
     def run(self, query, ref, feat):
-        _check("Propagator.run", {"query": query, "ref": ref, "feat": feat}, (torch.float32,) * 3)
+        _pointset.check_tensors("Propagator.run", {"query": query, "ref": ref, "feat": feat}, (torch.float32,) * 3, _WHAT)
         count, P, N = _nn_shapes("Propagator.run", query, ref)
         _ops._hip(query, ref, feat)
         if count > self.B or (P, N) != (self.P, self.N) or tuple(feat.shape) != (count, self.D, N) or query.device != self.out.device:
@@ -198,4 +172,4 @@ def source_points(pool, source_pool):
     lo, hi = (int(v) for v in torch.aminmax(index))
     if lo < 0 or hi >= source_pool.P:
         raise ValueError("source_points: fps_index outside 0 .. P-1 = %d (min %d, max %d)" % (source_pool.P - 1, lo, hi))
-    return torch.gather(source_pool.data, 1, index.unsqueeze(2).expand(-1, -1, 3)).contiguous()
+    return _pointset.gather_rows(source_pool.data, index).contiguous()

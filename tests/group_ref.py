@@ -1,8 +1,7 @@
 """numpy restatement of the ball query and the grouping (svnet_amd/csrc/group.hip), written from the contract in svnet_amd/group.py's
 docstring and independent of the kernels; plus the procedural inputs of the tests.
 
-    distances(c, x)                    dist [S,N] float32 in the contract's order: every operation a single-rounded fp32 operation
-                                       (numpy float32 arrays round each operation once and never fuse)
+    distances(c, x)                    dist [S,N] float32 in the contract's order (tests/pointset_ref.py)
     r2_of(radius)                      fp32(radius * radius), the square taken in double
     query_ball(x, c, r2, nsample)      idx [S,nsample] int64, count [S] int32: a plain loop over the centres
     group(x, c, idx, pts)              [S,nsample,3+D]: point minus centre, then the attributes; an index outside [0, N) is clamped
@@ -11,18 +10,9 @@ docstring and independent of the kernels; plus the procedural inputs of the test
 import numpy as np
 
 from svnet_amd import synth
+from tests.pointset_ref import distances, lattice         # noqa: F401  (the tests reach them through this module)
 
 F32 = np.float32
-
-
-def distances(c, x):
-    """dist [S,N] float32: d = fl(centre - point) per coordinate, fl(fl(fl(d0 d0) + fl(d1 d1)) + fl(d2 d2))."""
-    c, x = np.ascontiguousarray(c, dtype=F32), np.ascontiguousarray(x, dtype=F32)
-    with np.errstate(invalid="ignore", over="ignore"):
-        d0 = (c[:, None, 0] - x[None, :, 0]).astype(F32)
-        d1 = (c[:, None, 1] - x[None, :, 1]).astype(F32)
-        d2 = (c[:, None, 2] - x[None, :, 2]).astype(F32)
-        return (((d0 * d0).astype(F32) + (d1 * d1).astype(F32)).astype(F32) + (d2 * d2).astype(F32)).astype(F32)
 
 
 def r2_of(radius):
@@ -77,13 +67,7 @@ def scanned_fraction(idx, count, nsample, N):
     return float(seen.mean()) / N
 
 
-# ---- procedural inputs
-def lattice(seed, stream, shape):
-    """Integer multiples of 2^-10 in [-1, 1): differences, squares and their sums are exact in fp32, so the reference's expanded
-    distance form and the contract's difference form agree bit for bit, and every distance is a multiple of 2^-20."""
-    return ((synth.integers(seed, stream, shape, 2048) - 1024).astype(np.float64) / 1024.0).astype(F32)
-
-
+# ---- procedural inputs (lattice: tests/pointset_ref.py)
 def _copy_centres(seed, x, c, every):
     """Centres 0, every, 2 every, ... become copies of distinct points (as far as there are points)."""
     B, N, S = x.shape[0], x.shape[1], c.shape[1]

@@ -11,20 +11,11 @@ docstring and independent of the kernels; plus the procedural inputs of the test
 import numpy as np
 
 from svnet_amd import synth
+from tests.pointset_ref import distances, lattice         # noqa: F401  (the tests reach them through this module)
 
 F32 = np.float32
 EPS = F32(1e-8)
 CHUNK = 512                    # query points per distance block (memory only: no effect on any result)
-
-
-def distances(q, r):
-    """dist [P,N] float32 in the contract's order."""
-    q, r = np.ascontiguousarray(q, dtype=F32), np.ascontiguousarray(r, dtype=F32)
-    d0 = (q[:, None, 0] - r[None, :, 0]).astype(F32)
-    d1 = (q[:, None, 1] - r[None, :, 1]).astype(F32)
-    d2 = (q[:, None, 2] - r[None, :, 2]).astype(F32)
-    with np.errstate(invalid="ignore", over="ignore"):
-        return (((d0 * d0).astype(F32) + (d1 * d1).astype(F32)).astype(F32) + (d2 * d2).astype(F32)).astype(F32)
 
 
 def weights(dist3):
@@ -96,13 +87,7 @@ def bound_f32(f):
     return 20.0 * 2.0 ** -24 * float(np.abs(np.asarray(f, dtype=np.float64)).max())
 
 
-# ---- procedural inputs
-def lattice(seed, stream, shape):
-    """Integer multiples of 2^-10 in [-1, 1): differences, squares and their sums are exact in fp32, so the reference's expanded
-    distance form and the contract's difference form agree bit for bit."""
-    return ((synth.integers(seed, stream, shape, 2048) - 1024).astype(np.float64) / 1024.0).astype(F32)
-
-
+# ---- procedural inputs (lattice: tests/pointset_ref.py)
 def lattice_case(seed, B, P, N, D):
     """(q [B,P,3], r [B,N,3], f [B,D,N]): lattice queries; every second sampled point (as far as there are queries: each is copied
     at most once) is a copy of a query, the coincident points a resampled pool consists of; Gaussian features."""

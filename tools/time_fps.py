@@ -12,11 +12,10 @@ Both legs run in this one process, alternating, after a warm-up of each shape.
     python tools/time_fps.py [--out profiles/fps_times.txt]
 """
 import argparse
-import os
-import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from event_timing import ROOT, emit, header, median, timed
+
 sys.path.insert(0, ROOT)
 
 SHAPES = ((64, 10000, 1024), (256, 2048, 1024))
@@ -36,18 +35,6 @@ def torch_ops_fps(torch, xyz, npoint, start):
     return idx
 
 
-def timed(torch, fn, reps):
-    out = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        res = fn()
-        b.record()
-        torch.cuda.synchronize()
-        out.append(a.elapsed_time(b))
-    return out, res
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
@@ -57,23 +44,17 @@ def main():
     if not torch.cuda.is_available():
         sys.exit("time_fps.py measures on the GPU: no HIP device here")
     import numpy as np
-    from svnet_amd import _lib, _ops, synth
+    from svnet_amd import _lib, _pointset, synth
     from svnet_amd.data import farthest_point_sample, fps_start
     dev = torch.device("cuda:0")
-    lines = []
-    try:
-        commit = subprocess.run(["git", "-C", ROOT, "rev-parse", "--short", "HEAD"], stdout=subprocess.PIPE, stderr=subprocess.DEVNULL,
-                                text=True).stdout.strip()
-    except OSError:
-        commit = ""
-    lines.append("commit %s   GPU %s   torch %s" % (commit or "(not a git checkout)", torch.cuda.get_device_name(0), torch.__version__))
+    lines = [header(torch)]
     for M, P, npoint in SHAPES:
         xyz = torch.from_numpy(np.ascontiguousarray(synth.normal(90 + P, 0, (M, P, 3)))).to(dev)
         start = torch.from_numpy(fps_start(1, M, P)).to(dev)
         idx = torch.empty(M, npoint, dtype=torch.int64, device=dev)
 
         def kernel():            # the entry point alone: no start check, no allocation
-            _lib.call("svnet_fps_f32", _ops._p(xyz), M, P, npoint, _ops._p(start), _ops._p(idx), _ops._stream())
+            _pointset.fps_launch(xyz, M, P, npoint, start, idx)
             return idx
 
         def whole():             # what a caller pays: + the start range check (one reduction, one synchronisation) and the allocation
@@ -88,24 +69,19 @@ def main():
         for _ in range(args.reps):               # alternating legs
             for name, fn in (("kernel", kernel), ("whole", whole), ("ops", ops)):
                 t, out = timed(torch, fn, 1)
-                res[name] += t
+                res[name].append(t)
                 if name == "kernel":
                     mine = out.clone()
                 elif name == "ops":
                     agree = float((out == mine).float().mean())
-        med = {k: sorted(v)[len(v) // 2] for k, v in res.items()}
+        med = {k: median(v) for k, v in res.items()}
         tag = "M %3d P %5d npoint %4d  (tier %d)" % (M, P, npoint, _lib.lib().svnet_fps_tier(P))
         for name, label in (("kernel", "svnet_fps_f32 alone        "), ("whole", "farthest_point_sample()    "),
                             ("ops", "torch ops on the device    ")):
             lines.append("%s  %s %10.3f ms (median of %d; %s)" % (tag, label, med[name], args.reps, " ".join("%.3f" % v for v in res[name])))
         lines.append("%s  torch ops / kernel = %.1f x;  %.2f us per iteration per cloud-wave of the kernel;  %.4f of the indices agree"
                      % (tag, med["ops"] / med["kernel"], med["kernel"] * 1e3 / npoint / (-(-M // 256)), agree))
-    text = "\n".join(lines) + "\n"
-    print(text, end="")
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(text)
+    emit(lines, args.out)
 
 
 if __name__ == "__main__":

@@ -19,11 +19,10 @@ wave of the ball query looks at before it leaves its loop (a full group ends wit
     python tools/time_group.py [--out profiles/group_times.txt]
 """
 import argparse
-import os
-import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from event_timing import ROOT, emit, header, median, timed
+
 sys.path.insert(0, ROOT)
 
 SHAPES = ((32, 1024, 512, 0.2, 32, 0), (32, 2048, 512, 0.4, 64, 64))
@@ -58,21 +57,6 @@ def torch_ops_group(torch, xyz, new_xyz, idx, points):
     return centred if points is None else torch.cat([centred, points[batch, idx, :]], dim=-1)
 
 
-def timed(torch, fn, inner):
-    """ms per call: events around `inner` back-to-back calls, then a synchronise."""
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(inner):
-        res = fn()
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b) / inner, res
-
-
-def median(v):
-    return sorted(v)[len(v) // 2]
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
@@ -87,13 +71,7 @@ def main():
     from svnet_amd import group as Gr
     from svnet_amd.data import DevicePool, farthest_point_sample, fps_start
     dev = torch.device("cuda:0")
-    lines = []
-    try:
-        commit = subprocess.run(["git", "-C", ROOT, "rev-parse", "--short", "HEAD"], stdout=subprocess.PIPE, stderr=subprocess.DEVNULL,
-                                text=True).stdout.strip()
-    except OSError:
-        commit = ""
-    lines.append("commit %s   GPU %s   torch %s" % (commit or "(not a git checkout)", torch.cuda.get_device_name(0), torch.__version__))
+    lines = [header(torch)]
     lines.append("ms per call = HIP events around %d back-to-back calls; median of %d alternating rounds (all rounds listed)" % (args.inner, args.reps))
     for B, N, S, radius, nsample, D in SHAPES:
         xyz = DevicePool.synthetic(400 + N, B, N, 16, device=dev).data
@@ -173,12 +151,7 @@ def main():
                         out_bytes / (med["group"] * 1e-3) / 1e12, out_bytes / (med["group"] * 1e-3) / HBM_PEAK))
         del xyz, points, new_xyz, grouper, ops_idx
         torch.cuda.empty_cache()
-    text = "\n".join(lines) + "\n"
-    print(text, end="")
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(text)
+    emit(lines, args.out)
 
 
 if __name__ == "__main__":

@@ -17,11 +17,10 @@ time is reported as a fraction of the 8 TB/s HBM peak.
     python tools/time_propagate.py [--out profiles/propagate_times.txt]
 """
 import argparse
-import os
-import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from event_timing import ROOT, emit, header, median, timed
+
 sys.path.insert(0, ROOT)
 
 SHAPES = ((32, 10000, 2048, 50), (32, 10000, 1024, 50))
@@ -45,21 +44,6 @@ def torch_ops_propagate(torch, q, r, f):
     P, K = idx.shape[1], idx.shape[2]
     g = torch.gather(f, 2, idx.reshape(B, 1, P * K).expand(B, D, P * K)).view(B, D, P, K)
     return (g * w[:, None]).sum(dim=3)
-
-
-def timed(torch, fn, inner):
-    """ms per call: events around `inner` back-to-back calls, then a synchronise."""
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(inner):
-        res = fn()
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b) / inner, res
-
-
-def median(v):
-    return sorted(v)[len(v) // 2]
 
 
 class StandIn:
@@ -92,13 +76,7 @@ def main():
     from svnet_amd.metrics import SHAPENET_PARTS, EpochMetrics
     from svnet_amd.train import evaluate, evaluate_dense
     dev = torch.device("cuda:0")
-    lines = []
-    try:
-        commit = subprocess.run(["git", "-C", ROOT, "rev-parse", "--short", "HEAD"], stdout=subprocess.PIPE, stderr=subprocess.DEVNULL,
-                                text=True).stdout.strip()
-    except OSError:
-        commit = ""
-    lines.append("commit %s   GPU %s   torch %s" % (commit or "(not a git checkout)", torch.cuda.get_device_name(0), torch.__version__))
+    lines = [header(torch)]
     lines.append("ms per call = HIP events around %d back-to-back calls; median of %d alternating rounds (all rounds listed)" % (args.inner, args.reps))
     for B, P, N, D in SHAPES:
         q = torch.from_numpy(np.ascontiguousarray(synth.normal(300 + N, 0, (B, P, 3)))).to(dev)
@@ -187,12 +165,7 @@ def main():
         lines.append("%s  %-15s %9.3f ms per batch  (%s)" % (tag, name, median(res[name]), " ".join("%.3f" % v for v in res[name])))
     lines.append("%s  (the pass includes its one host read and, for evaluate_dense, source_points and the buffer allocation;  shape IoU of the "
                  "sample %.4f, of the clouds %.4f)" % (tag, sample_iou, dense_iou))
-    text = "\n".join(lines) + "\n"
-    print(text, end="")
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(text)
+    emit(lines, args.out)
 
 
 if __name__ == "__main__":
