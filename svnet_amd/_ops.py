@@ -522,9 +522,8 @@ def begin_step(dev, planes_external=False, arena=None):
 
 
 def end_step():
-    global ARENA, _FUSED_COLSUMS, _FUSED_VSTATS
+    global ARENA, _FUSED_COLSUMS
     knn_table_ahead.table = None                          # (a prepared k-NN table nobody asked for is not held across steps)
-    _FUSED_VSTATS = None
     _FUSED_COLSUMS = None                                 # (the producer's [M, O] output and its arena slice are not held across steps)
     ARENA.end()
     ARENA = _DEFAULT_ARENA
@@ -617,10 +616,7 @@ class BwLinear(torch.autograd.Function):
     """y = (x sign(W)^T) * scale with fp32 activations (sv_layers.py:44-49 with bw only: linear2, v2s.linear, svfuse)."""
 
     @staticmethod
-    def forward(ctx, x, W, scale, training=True, vstats=False):
-        """vstats: x is [..., 3, K] vectors and a VectorBN in training mode consumes the output next (SVBlock's linear2): the product
-        also leaves the VectorBN's batch sums (csrc/vlinear.hip) in _FUSED_VSTATS, where VBN.forward finds them - no statistics pass."""
-        global _FUSED_VSTATS
+    def forward(ctx, x, W, scale, training=True):
         _hip(x, W, scale)
         ctx.training = bool(training)
         x2 = _f32c(x).reshape(-1, x.shape[-1])
@@ -630,14 +626,7 @@ class BwLinear(torch.autograd.Function):
         sc = _f32c(scale).view(-1)
         w_b = _binweight(W_in, scale)["w_b"]
         y = torch.empty((M, O), dtype=torch.float32, device=x.device)
-        _FUSED_VSTATS = None
-        if (vstats and training and config.FUSE_VBN_STATS and x.dim() >= 2 and x.shape[-2] == 3 and M % 3 == 0 and M > 0
-                and K <= 96 and O <= 256):
-            sums = _zeros((_sliced_len(2 * O),), torch.float64, x.device)
-            call("svnet_vlinear_stats_f32", _p(x2), M // 3, K, _p(w_b), _p(sc), O, _p(y), _p(sums), _stream())
-            _FUSED_VSTATS = (y, y._version, sums)
-        else:
-            gemm(M, O, K, A=x2, a_rs=K, a_cs=1, B=w_b, b_rs=1, b_cs=K, b_exact=True, C=y, ldc=O, col_scale=sc)
+        gemm(M, O, K, A=x2, a_rs=K, a_cs=1, B=w_b, b_rs=1, b_cs=K, b_exact=True, C=y, ldc=O, col_scale=sc)
         ctx.save_for_backward(x2, W, sc, w_b)
         ctx.xshape, ctx.sshape = x.shape, scale.shape
         return y.view(x.shape[:-1] + (O,))
@@ -650,21 +639,16 @@ class BwLinear(torch.autograd.Function):
         g2 = _f32c(g).reshape(M, O)
         dx = dW = dsc = None
         need_w = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
-        # many rows: the weight-gradient product runs beside the input-gradient product (its three phases - stage B, MFMA, write C -
-        # are in lockstep over the whole chip, one row block per workgroup, so each leaves the other two resources idle)
-        beside = _Beside(g.device, config.DW_BESIDE and need_w and ctx.needs_input_grad[0] and M >= config.TWO_STREAM_MIN_ROWS)
         if need_w:
             GX = _zeros((O, K), torch.float32, g.device)
-            with beside:
-                gemm(O, K, M, A=g2, a_rs=1, a_cs=O, B=x2, b_rs=K, b_cs=1, C=GX, ldc=K, accumulate=True)
-                dW, dsc = _binweight_grad(GX, W, sc, O, K, ctx.training)
-                dsc = dsc.view(ctx.sshape)
+            gemm(O, K, M, A=g2, a_rs=1, a_cs=O, B=x2, b_rs=K, b_cs=1, C=GX, ldc=K, accumulate=True)
+            dW, dsc = _binweight_grad(GX, W, sc, O, K, ctx.training)
+            dsc = dsc.view(ctx.sshape)
         if ctx.needs_input_grad[0]:
             dx = torch.empty((M, K), dtype=torch.float32, device=g.device)
             gemm(M, K, O, A=g2, a_rs=O, a_cs=1, a_scale=sc, B=w_b, b_rs=K, b_cs=1, b_exact=True, C=dx, ldc=K)
             dx = dx.view(ctx.xshape)
-        beside.join(dW, dsc)
-        return dx, dW, dsc, None, None
+        return dx, dW, dsc, None
 
 
 class BinLinear(torch.autograd.Function):
@@ -718,7 +702,6 @@ class BinLinear(torch.autograd.Function):
         g2 = _f32c(g).reshape(M, O)
         dx = dW = dbeta = dsc = dbias = None
         need_x, need_w = ctx.needs_input_grad[0] or ctx.needs_input_grad[2], ctx.needs_input_grad[1] or ctx.needs_input_grad[3]
-        beside = _Beside(dev, config.DW_BESIDE and need_x and need_w and ctx.training and M >= config.TWO_STREAM_MIN_ROWS)    # (see BwLinear.backward)
         def wgrad(sum_buf=None, sum_len=0):
             # GX[o,k] = sum_m g[m,o] x_b[m,k], computed as (x_b^T g)[k,o] with the ternary operand on the A side
             GX = _zeros((O, K), torch.float32, dev)           # (accumulate onto zeros from the step's arena: no zero-fill launch of its own)
@@ -726,14 +709,11 @@ class BinLinear(torch.autograd.Function):
             dW_, dsc_ = _binweight_grad(GX, W, sc, O, K, ctx.training, sum_buf=sum_buf, sum_len=sum_len)
             return dW_.view(wshape), dsc_.view(sshape)
 
-        if need_w and beside.on:                              # helper-stream form: the weight gradient is issued first, beside the input gradient
-            with beside:
-                dW, dsc = wgrad()
         # TrainStep (svnet_amd.train) gathers the parameter gradients ONCE, after the backward: a big layer's weight-gradient chain then goes
         # to the TAIL of the side stream, unjoined (_Deferred) - the main stream carries on with what the layer in front waits for (dx) and
         # the chain fills the chip under the launch-bound kernels that follow it there (conv5 of the classifier: gate MLP, mean / Vector2Scalar
         # backward, the next layer's prelude)
-        defer = (need_w and not beside.on and need_x and ctx.training and DEFERRED.active and config.DEFER_ROWS_WGRAD and ctx.defer_ok
+        defer = (need_w and need_x and ctx.training and DEFERRED.active and config.DEFER_ROWS_WGRAD and ctx.defer_ok
                  and M >= config.TWO_STREAM_MIN_ROWS and DEFERRED.first_use(W, sc))
         dbuf = None
         if need_x:
@@ -756,12 +736,11 @@ class BinLinear(torch.autograd.Function):
                 dW, dsc = wgrad(dbuf, K)                      # (its epilogue launch also totals dL/dbeta: a parameter gradient, like dW)
             DEFERRED.keep.append((g2, x_sign, x_nz, W, sc, dbuf))     # (NOT the returned gradients: see EdgeBlock.backward)
             pending = False
-        elif need_w and not beside.on:
+        elif need_w:
             dW, dsc = wgrad(dbuf if pending else None, K if pending else 0)
             pending = False
         if pending:
             call("svnet_slices_sum_f32", _p(dbuf), K, _stream())
-        beside.join(dW, dsc)
         if has_bias and ctx.needs_input_grad[4]:
             dbias = pool_raw(g2, 1, M, O, 1)[0].view(O) * float(M)
         return dx, dW, dbeta, dsc, dbias, None
@@ -1175,7 +1154,6 @@ class VProject(torch.autograd.Function):
 # Column sums a producer left for the BatchNorm over its output: (the [M, C] tensor itself - held, so that its memory cannot be handed to
 # another tensor while the record lives -, its version at the time, sums [2C] double).  Consumed once; any later producer replaces it.
 _FUSED_COLSUMS = None
-_FUSED_VSTATS = None          # (y, version, sums) of the last BwLinear(vstats=True): the VectorBN sums of ITS output
 
 
 def _batch_stats(x, M, C, kind, running_mean, running_var, training, momentum, eps, nbt=None):
@@ -1253,16 +1231,10 @@ class VBN(torch.autograd.Function):
         M, _, C = v3.shape
         gate2 = None if gate is None else _f32c(gate).reshape(-1, C)
         out = torch.empty_like(v3)
-        global _FUSED_VSTATS
-        rec, _FUSED_VSTATS = _FUSED_VSTATS, None
         if training and M > 0:
             # statistics pass, then ONE kernel that finalises them per thread and applies them (no one-workgroup launch in between)
-            if (rec is not None and rec[0].data_ptr() == v3.data_ptr() and rec[0].numel() == v3.numel() and rec[0]._version == rec[1]
-                    and tuple(rec[0].shape) == (3 * M, C)):
-                sums = rec[2]                                   # the producing product's sums (csrc/vlinear.hip)
-            else:
-                sums = _zeros((_sliced_len(2 * C),), torch.float64, v3.device)
-                call("svnet_colstats_f64", _p(v3), M, C, 1, _p(sums), _stream())
+            sums = _zeros((_sliced_len(2 * C),), torch.float64, v3.device)
+            call("svnet_colstats_f64", _p(v3), M, C, 1, _p(sums), _stream())
             mean = torch.empty((C,), dtype=torch.float32, device=v3.device)
             invstd = torch.empty((C,), dtype=torch.float32, device=v3.device)
             call("svnet_vbn_fwd_stats_f32", _p(v3), _p(sums), eps, momentum, _p(mean), _p(invstd), _p(running_mean), _p(running_var), _p(nbt),
@@ -1554,7 +1526,6 @@ class GlobalMaxMeanPoolBNV(torch.autograd.Function):
                 eps=BN_EPS, momentum=BN_MOMENTUM, v_on_side=False):
         """v_on_side: v_lin was produced on the side stream (SVBlock.vector_path_on_side), so autograd runs linear2's backward - the
         consumer of dv - there too; False (the single-stream path) = it runs on the main stream."""
-        global _FUSED_VSTATS
         _hip(y, v_lin, gate, g1, b1, g2, b2, Wz, scz)
         y, v_lin = _f32c(y), _f32c(v_lin)
         B, N, Ca = y.shape
@@ -1578,17 +1549,13 @@ class GlobalMaxMeanPoolBNV(torch.autograd.Function):
         arg_b = torch.empty((B, Cb), dtype=torch.int32, device=dev)
         nbw = L.svnet_vtail_workspace_bytes(B, N, C)
         wsb = _zeros((nbw,), torch.uint8, dev)              # (zero keys from the step's one fill: no memset launch in front of the pass)
-        rec, _FUSED_VSTATS = _FUSED_VSTATS, None
         main, side = torch.cuda.current_stream(dev), _side_stream(dev)
         side.wait_stream(main)                                          # (the gate and the statistics buffers come from this stream)
         with torch.cuda.stream(side):                                   # the vector half beside the scalar half
             sums = None
             if training:
-                if (rec is not None and rec[0].data_ptr() == v3.data_ptr() and rec[0].numel() == v3.numel() and rec[0]._version == rec[1]):
-                    sums = rec[2]                                       # the producing product's sums (csrc/vlinear.hip)
-                else:
-                    sums = _zeros((_sliced_len(2 * C),), torch.float64, dev)
-                    call("svnet_colstats_f64", _p(v3), P, C, 1, _p(sums), _stream())
+                sums = _zeros((_sliced_len(2 * C),), torch.float64, dev)
+                call("svnet_colstats_f64", _p(v3), P, C, 1, _p(sums), _stream())
             else:
                 call("svnet_bn_eval_stats_f32", _p(rm2), _p(rv2), C, eps, _p(mean2), _p(invstd2), _stream())
             call("svnet_vtail_fwd_f32", _p(v3), _p(sums), eps, momentum, _p(mean2), _p(invstd2), _p(rm2) if training else None,
@@ -2121,7 +2088,7 @@ class EdgeBlock(torch.autograd.Function):
         job = _lib.GateBwdJob(_p(dgate), _p(gate), _p(h), _p(gin), inv_nk, _p(Wg0), _p(Wg2), B, 2 * Cs, H, Ov, inv_nk, _p(gconst), _p(dWg0), _p(dWg2))
         call("svnet_edgeblock_bwd_coeffs_f32", _p(red), _p(redv), _p(coef), _p(g1), _p(g2), E, Os, Ov, int(training), _p(sc1), _p(bcoef),
              _p(dg1), _p(db1), _p(dg2), _p(db2), ctypes.byref(job), _stream())
-        coeffs_done = main.record_event() if config.VEC_EARLY else None      # (what the vector path waits for)
+        coeffs_done = main.record_event()                                    # (what the vector path waits for)
 
         # ---- the edge pass
         affine = k >= 8        # the weight-gradient GEMM recomputes dL/dy_pre from n16: the tile kernel then writes no fp32 [E,Os] tensor
@@ -2146,10 +2113,7 @@ class EdgeBlock(torch.autograd.Function):
         d.debug = _p(DEBUG_BUFFER)
         # the vector path (wave per point) and the scalar path (32-edge tiles) are independent: two streams, so that the
         # register/LDS-bound tile kernel and the light vector kernel share the CUs
-        if coeffs_done is not None:
-            side.wait_event(coeffs_done)
-        else:
-            side.wait_stream(main)
+        side.wait_event(coeffs_done)
         with torch.cuda.stream(side):
             d.parts = 1
             call("svnet_edgeblock_bwd_f32", ctypes.byref(d), _stream())
@@ -2337,51 +2301,8 @@ def _side_stream(dev):
     key = torch.device(dev).index if torch.device(dev).index is not None else torch.cuda.current_device()
     if key not in _SIDE_STREAMS:
         # (a high-priority side stream was measured: 10.7 ms per step against 6.4 - the tile kernel on the main stream starves)
-        _SIDE_STREAMS[key] = torch.cuda.Stream(device=key, priority=config.SIDE_PRIORITY)
+        _SIDE_STREAMS[key] = torch.cuda.Stream(device=key, priority=0)
     return _SIDE_STREAMS[key]
-
-
-def _aux_stream(dev, cur):
-    """A helper stream OF the stream `cur`: the weight-gradient product of a big dense layer's backward beside its input-gradient
-    product (the two only share their inputs).  One per origin stream (main, and _side_stream when it carries the other path of an
-    SVBlock): a helper forked from two different streams of one hipGraph capture crashed hipStreamEndCapture."""
-    key = ("aux", torch.device(dev).index if torch.device(dev).index is not None else torch.cuda.current_device(), cur.cuda_stream)
-    if key not in _SIDE_STREAMS:
-        _SIDE_STREAMS[key] = torch.cuda.Stream(device=key[1])
-    return _SIDE_STREAMS[key]
-
-
-class _Beside:
-    """`with _Beside(dev, on): ...` runs the block on the aux stream, forked from the current stream at entry; .join() makes the
-    current stream wait for it and hands the given tensors (allocated in the block) over to it.  `on` False: a no-op."""
-
-    def __init__(self, dev, on):
-        self.on = bool(on)
-        if self.on:
-            self.cur = torch.cuda.current_stream(dev)
-            if self.cur.cuda_stream == _side_stream(dev).cuda_stream:
-                self.on = False        # already on a forked stream (the vector path of an SVBlock): a second-level fork crashed hipStreamEndCapture
-                return
-            self.aux = _aux_stream(dev, self.cur)
-            self.ctx = torch.cuda.stream(self.aux)
-
-    def __enter__(self):
-        if self.on:
-            self.aux.wait_stream(self.cur)
-            self.ctx.__enter__()
-        return self
-
-    def __exit__(self, *exc):
-        if self.on:
-            self.ctx.__exit__(*exc)
-        return False
-
-    def join(self, *tensors):
-        if self.on:
-            self.cur.wait_stream(self.aux)
-            for t in tensors:
-                if t is not None:
-                    t.record_stream(self.cur)
 
 
 _PERM_CACHE = {}

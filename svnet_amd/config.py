@@ -22,9 +22,8 @@ TWO_STREAM_MIN_ROWS = 4096
 # through the second, atomic launch; 128 keeps a bound on what one wave may be handed (a pathological hub) at the price of 0.008 ms.
 GATHER_CHUNK = 128
 
-# Backward of a dense (sign-weight / binarized) layer with many rows: the weight-gradient product on a helper stream beside the
-# input-gradient product.
-DW_BESIDE = False      # measured: +0.12 ms per step on sv_dgcnn_cls B=32 (5.75 against 5.62): the two products compete for the same CUs
+# (a dense layer's weight-gradient product on a helper stream beside its input-gradient product, DW_BESIDE: measured +0.12 ms per step
+#  (5.75 against 5.62), re-measured +0.04 ms - the two products compete for the same CUs; the switch and its code path are gone.)
 
 # Classifier: conv5's BatchNorm + LeakyReLU inside the global [max | mean] pooling pass (no activated [B,N,512] tensor, no gradient of it).
 FUSE_BN_POOL = True
@@ -55,7 +54,6 @@ FUSE_HEAD = True
 # TrainStep: the fused edge layers' weight-gradient chains stay on the side stream until the one join before the gradients are packed
 # (svnet_amd._ops._Deferred); False = every backward joins before it returns
 DEFER_WGRAD = True
-VEC_EARLY = True
 # ... and so do the weight-gradient chains of the big rows layers (conv5.linear1 of the classifier: 111 + 11 us at the tail of the side
 # stream instead of in front of the launch-bound end of conv5's backward): 4.29 -> 4.23 ms (profiles/r05_ab_defer_rows.log).  Opt-in per
 # call site (_ops.defer_rows_wgrad): on every rows layer of sv_pointnet_cls it cost 0.38 ms per step
@@ -65,18 +63,8 @@ DEFER_ROWS_WGRAD = True
 # sign-weight products with many rows and more than 128 columns go to the LDS-tiled rows kernel from this K on (it needs K >= 64)
 ROWS2_MIN_K = 64
 
-# Stream priorities (torch: lower number = higher priority; -1 is the highest this build hands out, 0 the default).  MAIN_PRIORITY is the
-# priority of the stream a step is captured on (svnet_amd.train), SIDE_PRIORITY that of the side stream (_ops._side_stream: the vector
-# path of an SVBlock on rows and the deferred weight-gradient chains).
-MAIN_PRIORITY = 0
-SIDE_PRIORITY = 0
-
-# SVBlock on rows: linear2's product also forms the batch sums of the VectorBN behind it (csrc/vlinear.hip; K <= 96, O <= 256) - no
-# statistics pass over its output.  Measured at conv5 of the classifier (32 768 points, 83 -> 170): alone 51 us + 57 us for the apply
-# pass (which then reads the product cold) against 72 + 21 + 44 for rows GEMM + statistics + apply, but IN the step 4.44 ms against 4.40
-# (two alternating runs: one 8-wave workgroup per CU holding 100 KB of LDS shares the CUs worse with the scalar path beside it than the
-# three lighter kernels did), and nothing on sv_pointnet_cls (5.61 against 5.62): off.
-FUSE_VBN_STATS = False
+# (SVBlock on rows, FUSE_VBN_STATS: linear2's product also forming the batch sums of the VectorBN behind it (csrc/vlinear.hip) was measured
+#  at 4.44 ms against 4.40 in the step and nothing on sv_pointnet_cls (5.61 against 5.62); the switch, its kernel and its code path are gone.)
 
 # SVBlock on rows, narrow s (the PointNet callers): the per-cloud mean of s the gate MLP starts from is formed inside the MLP's launch
 # (_ops.GateMLPRows) instead of by a pooling pass of two launches in front of it

@@ -1,5 +1,5 @@
 // The exact three-way bf16 split of an fp32 value, x = h + m + l: what lets the bf16 matrix cores form fp32-exact products
-// (gemm_mfma.hip, vlinear.hip, phase B of edgeblock_bwd.hip).  Both subtractions are exact; l has at most 8 significant bits.
+// (gemm_mfma.hip, phase B of edgeblock_bwd.hip).  Both subtractions are exact; l has at most 8 significant bits.
 #pragma once
 #include "common.h"
 

@@ -723,14 +723,12 @@ extern "C" int svnet_edgeblock_fwd_f32(const svnet_edgeblock_desc* desc, void* s
     const int64_t waves = d.B * fa.waves_per_cloud;
     const unsigned grid = (unsigned)svnet_cdiv(waves, 4);
     const bool narrow = d.Cs <= 32 && 2 * d.Cv <= 32;
-    static const bool no_pairs = getenv("SVNET_FWD_NO_PAIRS") != nullptr;      // (diagnostic: the one-edge-per-iteration kernel for narrow layers too)
-    static const bool pairs64 = getenv("SVNET_FWD_PAIRS64") != nullptr;
-    if (narrow && d.Ov <= 32 && (d.Os <= 32 || (pairs64 && d.Os <= 64)) && !no_pairs && d.B * d.N * 6 * (int64_t)d.Ov < ((int64_t)1 << 30)) {
+    if (narrow && d.Ov <= 32 && d.Os <= 32 && d.B * d.N * 6 * (int64_t)d.Ov < ((int64_t)1 << 30)) {
         // two edges per wave iteration (32-bit element offsets: the largest table, ut, has B*N*6*Ov floats).  Measured at B=32,
         // N=1024, k=20: Os = 32 (conv2) 196 -> 159 us; Os = 64 (conv3: two output channels per lane, so the popcount part does
-        // not shrink, and 72 B of spills at 4 waves per SIMD) 197 -> 195 us - conv3 stays on the one-edge kernel
-        if (d.Os <= 32) hipLaunchKernelGGL((edgeblock_fwd2_kernel<1>), dim3(grid), dim3(256), 0, (hipStream_t)stream, fa);
-        else hipLaunchKernelGGL((edgeblock_fwd2_kernel<2>), dim3(grid), dim3(256), 0, (hipStream_t)stream, fa);
+        // not shrink, and 72 B of spills at 4 waves per SIMD) 197 -> 195 us - conv3 stays on the one-edge kernel (OP2 = 1 is the
+        // only instantiation)
+        hipLaunchKernelGGL((edgeblock_fwd2_kernel<1>), dim3(grid), dim3(256), 0, (hipStream_t)stream, fa);
         SVNET_CHECK_LAUNCH("edgeblock_fwd2_kernel");
         return SVNET_OK;
     }

@@ -420,7 +420,7 @@ _Pragma("unroll") \
             for (int i = 0; i < 6; ++i) pc_zi[i] = zip_[i]; \
     } while (0)
 
-// MODE: 0 = product; 1..3 = timing-only ablations (SVNET_BWD_MODE), wrong results.  NKS = k-steps of phase B (Os <= 16*NKS)
+// MODE: 0 = product; 1..3 = timing-only ablations (-DSVNET_BWD_MODES builds, picked there by SVNET_BWD_MODE), wrong results.  NKS = k-steps of phase B (Os <= 16*NKS)
 // NC2: 0 = phase C as one edge per wave iteration (lanes = channels); > 0 = the lanes = (edge, axis) form of phase C for 2 Cv <= NC2
 // (20: Cv <= 10 - five channel pairs per lane; 24: Cv <= 12; 44: Cv <= 21 - a neighbour's [3][Cv] row fits one 64-lane load and 11 channel pairs per lane; 48: Cv <= 24)
 // (One tile per workgroup.  A loop over two tiles per workgroup - so that the drain of a tile's last atomics and the next workgroup's
@@ -1068,7 +1068,11 @@ extern "C" int svnet_edgeblock_bwd_f32(const svnet_edgeblock_bwd_desc* desc, voi
     const int64_t E = d.B * d.N * d.k;
     if (E == 0) return SVNET_OK;
     hipStream_t st = (hipStream_t)stream;
+#ifdef SVNET_BWD_MODES     /* diagnostic builds only (tools/time_bwd_modes.py): SVNET_BWD_MODE=1|2|3 picks a timing ablation, results WRONG */
     static const int mode = getenv("SVNET_BWD_MODE") ? atoi(getenv("SVNET_BWD_MODE")) : 0;
+#else
+    constexpr int mode = 0;
+#endif
 
     // vector path: wave per point
     VecArgs va;
@@ -1081,8 +1085,11 @@ extern "C" int svnet_edgeblock_bwd_f32(const svnet_edgeblock_bwd_desc* desc, voi
     const unsigned vgrid = (unsigned)svnet_cdiv(d.B * va.waves_per_cloud, 4);
     const bool do_vec = d.parts == 0 || (d.parts & 1), do_tile = d.parts == 0 || (d.parts & 2);
     if (do_vec) {
+#ifdef SVNET_BWD_MODES
         if (mode == 1) hipLaunchKernelGGL((edgeblock_bwd_vec_kernel<1>), dim3(vgrid), dim3(256), 0, st, va);
-        else hipLaunchKernelGGL((edgeblock_bwd_vec_kernel<0>), dim3(vgrid), dim3(256), 0, st, va);
+        else
+#endif
+        hipLaunchKernelGGL((edgeblock_bwd_vec_kernel<0>), dim3(vgrid), dim3(256), 0, st, va);
         SVNET_CHECK_LAUNCH("edgeblock_bwd_vec_kernel");
     }
     if (!do_tile) return SVNET_OK;
@@ -1108,7 +1115,11 @@ extern "C" int svnet_edgeblock_bwd_f32(const svnet_edgeblock_bwd_desc* desc, voi
     static const bool c_old = getenv("SVNET_BWD_C_OLD") != nullptr;      // (diagnostic: the one-edge-per-iteration phase C)
     if (mode == 0 && !c_old && d.Cv >= 3 && d.Cv <= 24 && 3 * d.Cv <= 2 * d.Cs && 3 * d.Cv <= 128) {     // (else the one-edge form)
         if (d.Os <= 32) SVNET_LAUNCH_BWD_C(2); else if (d.Os <= 64) SVNET_LAUNCH_BWD_C(4); else SVNET_LAUNCH_BWD_C(8);
-    } else if (mode == 1) SVNET_LAUNCH_BWD(1); else if (mode == 2) SVNET_LAUNCH_BWD(2); else if (mode == 3) SVNET_LAUNCH_BWD(3); else SVNET_LAUNCH_BWD(0);
+    }
+#ifdef SVNET_BWD_MODES
+    else if (mode == 1) SVNET_LAUNCH_BWD(1); else if (mode == 2) SVNET_LAUNCH_BWD(2); else if (mode == 3) SVNET_LAUNCH_BWD(3);
+#endif
+    else SVNET_LAUNCH_BWD(0);
 #undef SVNET_LAUNCH_BWD
 #undef SVNET_LAUNCH_BWD_C
     SVNET_CHECK_LAUNCH("edgeblock_bwd_kernel");

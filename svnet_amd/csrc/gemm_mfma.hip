@@ -290,7 +290,8 @@ constexpr int R2_BUF_BYTES = R2_A_BYTES + R2_B_BYTES;      // 38 912 bytes per b
 
 // NP = bf16 pieces of B (1: B exact in bf16; 3: general fp32 B split exactly as Bh + Bm + Bl, packed one after the other in B16 with
 // a.b_piece elements between them).  The pipeline stage is (k tile, piece): the B tile changes every stage, the A tile every NP stages -
-// A is read from HBM once for all three pieces, C is written once.
+// A is read from HBM once for all three pieces, C is written once.  Only NP = 1 is instantiated (general fp32 B goes to mfma_rows3_kernel);
+// the source keeps the parameter because the kernel written without it compiles to a different instruction stream.
 // AV: A rows 16-byte aligned with K % 4 == 0 (float4 loads); else four clamped scalar loads per float4 slot (e.g. K = 127 feature rows).
 template <int NP, bool AV = true>
 __global__ __launch_bounds__(256, 2) void mfma_rows2_kernel(RowsArgs a) {
@@ -451,8 +452,8 @@ __global__ __launch_bounds__(256, 2) void mfma_rows2_kernel(RowsArgs a) {
 }
 
 // ---- many rows x GENERAL fp32 weights in one launch: C[M x N] = A[M x K] . (Bh + Bm + Bl), A split ONCE per element.
-// mfma_rows2_kernel<3> reads the fp32 A tile from LDS and splits it into its three bf16 pieces in the wave that multiplies - every A
-// element was split six times (two column waves x three B pieces), ~130 vector instructions per 16-wide k-step beside its 24 MFMAs at two
+// The form this replaced (mfma_rows2_kernel over three pieces) read the fp32 A tile from LDS and split it into its three bf16 pieces in
+// the wave that multiplied - every A element was split six times (two column waves x three B pieces), ~130 vector instructions per 16-wide k-step beside its 24 MFMAs at two
 // waves per SIMD.  Here the threads that STAGE the A tile split it (16 values per thread and k tile) and leave three bf16 tiles in LDS;
 // the multiplying waves only read fragments.  Six bf16 products per fp32 product (the leading terms of the 3 x 3 expansion, see the stage
 // macro): the result is within one fp32 rounding per product of the exact product sum, accumulated in fp32 - fp32-GEMM accuracy.
@@ -614,8 +615,8 @@ __global__ __launch_bounds__(256, 2) void mfma_rows3_kernel(RowsArgs a) {
 // ------------------------------------------------------------------------------------------------ tn kernel
 struct TnArgs {
     const float* A; int64_t lda;        // [M, P] fp32 rows (p contiguous)
-    const float* B; int64_t ldb;        // BMODE 0: [M, Q] fp32 rows
-    const uint64_t* b_sign; const uint64_t* b_nz;   // BMODE 1: row-sliced planes [ceil(M/64)][Q]
+    const float* B; int64_t ldb;        // fp32 B (mfma_tn2_kernel): [M, Q] fp32 rows
+    const uint64_t* b_sign; const uint64_t* b_nz;   // ternary B: row-sliced planes [ceil(M/64)][Q]
     float* C; int64_t c_ps, c_qs;       // out(p,q) at C[p*c_ps + q*c_qs], accumulated with atomics (pre-zeroed)
     int64_t M; int P, Q;
     int64_t rows_per_block;             // multiple of 256
@@ -637,110 +638,13 @@ __device__ __forceinline__ bool qtile_live(uint32_t qmask, int qt) {
 }
 
 
-// NQ 32-wide q tiles per workgroup (blockIdx.z picks the group).  The 4 waves cover `ptw` p tiles (1, 2 or 4 per
-// workgroup); when P is narrow (ptw < 4) the spare waves split the workgroup's row range instead of idling.
-template <int NQ, int BMODE>
-__global__ __launch_bounds__(256, 2) void mfma_tn_kernel(TnArgs a) {
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));   // row ranges stay in SGPRs
-    const int r = lane & 31, h = lane >> 5;
-    const int ptw = a.ptiles_per_block;                      // 1, 2 or 4
-    const int p0 = (blockIdx.y * ptw + (wave % ptw)) * 32;
-    const int q0 = blockIdx.z * (NQ * 32);
-    if (p0 >= a.P) return;  // wave-uniform; no barriers in this kernel
-    const int nsub = 4 / ptw, sub = wave / ptw;
-    const int64_t rows_sub = ((a.rows_per_block / nsub + 63) >> 6) << 6;   // multiple of 64
-    const int64_t mb = (int64_t)blockIdx.x * a.rows_per_block + (int64_t)sub * rows_sub;
-    const int64_t me = min(min(a.M, (int64_t)(blockIdx.x + 1) * a.rows_per_block), mb + rows_sub);
-
-    f32x16 acc[NQ];
-#pragma unroll
-    for (int t = 0; t < NQ; ++t)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[t][i] = 0.f;
-
-    // fp32 x fp32 (BMODE 0 is the only mode left here; ternary B runs in mfma_tn_tern_kernel).  The A fragment and the NQ B
-    // fragments of the next 16-row step are requested before the MFMAs of the current one.  Columns past P / Q are computed
-    // from clamped (valid) addresses and never stored, so only rows past the range's end need zeroing, and the k-step has no
-    // per-tile branches (one basic block: the splits of one tile overlap the MFMAs of another).
-    {
-        const int64_t mlast = a.M - 1;
-        const int pc = min(p0 + r, a.P - 1);
-        int qc[NQ];
-#pragma unroll
-        for (int t = 0; t < NQ; ++t) qc[t] = min(q0 + t * 32 + r, a.Q - 1);
-        float xn[8], yn[NQ][8];
-#define SVNET_TN0_LOAD(MROW)                                                                                  \
-    do {                                                                                                      \
-        _Pragma("unroll") for (int j = 0; j < 8; ++j) {                                                        \
-            const int64_t row_ = min((MROW) + j, mlast);                                                      \
-            xn[j] = a.A[row_ * a.lda + pc];                                                                   \
-            _Pragma("unroll") for (int t = 0; t < NQ; ++t) yn[t][j] = a.B[row_ * a.ldb + qc[t]];              \
-        }                                                                                                     \
-    } while (0)
-        if (mb < me) SVNET_TN0_LOAD(mb + 8 * h);
-        for (int64_t m16 = mb; m16 < me; m16 += 16) {
-            float x[8], y[NQ][8];
-            const int lim = (int)min((int64_t)16, me - m16) - 8 * h;   // rows of this lane's slice inside the range (32-bit compares)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const bool ok = j < lim;
-                x[j] = ok ? xn[j] : 0.f;
-#pragma unroll
-                for (int t = 0; t < NQ; ++t) y[t][j] = yn[t][j];   // (x = 0 is enough to drop the row)
-            }
-            if (m16 + 16 < me) SVNET_TN0_LOAD(m16 + 16 + 8 * h);
-            const Split3 sa = split_frag(x);
-#pragma unroll
-            for (int t = 0; t < NQ; ++t) {
-                const Split3 sb = split_frag(y[t]);
-                acc[t] = MFMA(sa.h, sb.h, acc[t]);
-                acc[t] = MFMA(sa.h, sb.m, acc[t]);
-                acc[t] = MFMA(sa.m, sb.h, acc[t]);
-                acc[t] = MFMA(sa.h, sb.l, acc[t]);
-                acc[t] = MFMA(sa.l, sb.h, acc[t]);
-                acc[t] = MFMA(sa.m, sb.m, acc[t]);
-            }
-        }
-#undef SVNET_TN0_LOAD
-    }
-    // Waves that split the row range of one p tile (narrow P) first combine their partial tiles in LDS: the output
-    // matrix is tiny and shared by the whole grid, and same-address float atomics serialise at the memory side.
-    if (a.lds_reduce) {   // uniform; every wave of the workgroup is live in this configuration
-        extern __shared__ float tnred[];                     // [nsub-1][NQ][16][64]
-        if (sub > 0) {
-#pragma unroll
-            for (int t = 0; t < NQ; ++t)
-#pragma unroll
-                for (int i = 0; i < 16; ++i) tnred[(((sub - 1) * ptw + (wave % ptw)) * NQ + t) * 1024 + i * 64 + lane] = acc[t][i];
-        }
-        __syncthreads();
-        if (sub > 0) return;
-        for (int s2 = 1; s2 < nsub; ++s2)
-#pragma unroll
-            for (int t = 0; t < NQ; ++t)
-#pragma unroll
-                for (int i = 0; i < 16; ++i) acc[t][i] += tnred[(((s2 - 1) * ptw + (wave % ptw)) * NQ + t) * 1024 + i * 64 + lane];
-    }
-#pragma unroll
-    for (int t = 0; t < NQ; ++t) {
-        const int q = q0 + t * 32 + r;  // D col = lane & 31  <-> B operand column (q)
-        if (q < a.Q) {
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const int pp = p0 + (i & 3) + 8 * (i >> 2) + 4 * h;  // D row <-> A operand row (p)
-                if (pp < a.P) atomicAdd(&a.C[(int64_t)pp * a.c_ps + (int64_t)q * a.c_qs], acc[t][i] * a.alpha);
-            }
-        }
-    }
-}
-
 // ---- tn, fp32 x fp32, LDS-tiled: out[P x Q] += A[rows, P]^T . B[rows, Q] over a workgroup's row range.
-// mfma_tn_kernel above splits every operand value in the wave that multiplies it: at four p tiles per workgroup each B value was split
-// four times per workgroup (and again by every workgroup of another p group) - ~320 vector instructions per 16-row step beside 24 MFMAs.
-// Here the 256 threads stage a 32-row slab of both operands ONCE: thread (column c, row group g) loads 8 rows of its column (coalesced
+// The kernel this one replaced split every operand value in the wave that multiplied it: at four p tiles per workgroup each B value was
+// split four times per workgroup (and again by every workgroup of another p group) - ~320 vector instructions per 16-row step beside 24
+// MFMAs.  Here the 256 threads stage a 32-row slab of both operands ONCE: thread (column c, row group g) loads 8 rows of its column (coalesced
 // across the columns), splits them and leaves three bf16x8 fragments per operand in LDS, [piece][column][row] - exactly the layout the
 // MFMA operands are read in.  2 x 2 waves, a wave = (32 IP) x (32 JQ) outputs; six bf16 products per fp32 product (h.h, h.m, m.h, h.l,
-// l.h, m.m: the dropped terms are below 2^-24 of the product, as in the kernel above).  The next slab travels global -> registers while
+// l.h, m.m: the dropped terms are below 2^-24 of the product).  The next slab travels global -> registers while
 // the current one is multiplied (requests TWO slabs ahead, a second register set, measured no faster: 536 against 516 us on
 // [512 x 2044], 185 against 166 on [170 x 340]).  Output: float atomics into the pre-zeroed / accumulated C, one per element and row split.
 #ifndef SVNET_TN2_ABLATE
@@ -875,9 +779,10 @@ __global__ __launch_bounds__(256, 2) void mfma_tn2_kernel(TnArgs a) {
 }
 
 // ---- tn with a TERNARY B operand (row-sliced planes): the weight-gradient product GX = x_b^T . dy of every binarized layer.
-// Same tiling as mfma_tn_kernel<NQ, 1>, but (a) the 8-row slices of the planes are expanded to bf16 fragments through two
-// 256-entry LDS tables (magnitude from the non-zero byte, sign bit from the negative byte) instead of 48 VALU operations
-// per fragment, (b) the A fragment of the next k-step and the plane words of the next 64-row block are loaded before the
+// NQ 32-wide q tiles per workgroup (blockIdx.z picks the group).  The 4 waves cover `ptw` p tiles (1, 2 or 4 per workgroup); when P
+// is narrow (ptw < 4) the spare waves split the workgroup's row range instead of idling.  (a) the 8-row slices of the planes are
+// expanded to bf16 fragments through two 256-entry LDS tables (magnitude from the non-zero byte, sign bit from the negative byte)
+// instead of 48 VALU operations per fragment, (b) the A fragment of the next k-step and the plane words of the next 64-row block are loaded before the
 // MFMAs of the current one, (c) <= 256 VGPRs so that two waves per SIMD overlap each other's loads.
 template <int NQ, bool AFF = false>
 __global__ __launch_bounds__(256, 2) void mfma_tn_tern_kernel(TnArgs a) {
@@ -1308,13 +1213,13 @@ bool launch_rows2(const RowsArgs& a, hipStream_t st) {
     if (!rows2_eligible(a)) return false;
     const size_t lds = (size_t)2 * R2_BUF_BYTES;
     bool ok = true;
-    SVNET_LDS_OPTIN(ok, lds, "mfma_rows2_kernel", reinterpret_cast<const void*>(&mfma_rows2_kernel<1, true>), reinterpret_cast<const void*>(&mfma_rows2_kernel<3, true>),
-                    reinterpret_cast<const void*>(&mfma_rows2_kernel<1, false>), reinterpret_cast<const void*>(&mfma_rows2_kernel<3, false>));
+    SVNET_LDS_OPTIN(ok, lds, "mfma_rows2_kernel", reinterpret_cast<const void*>(&mfma_rows2_kernel<1, true>),
+                    reinterpret_cast<const void*>(&mfma_rows2_kernel<1, false>));
     (void)ok;
     const dim3 grid((unsigned)svnet_cdiv(a.M, R2_BM), (unsigned)svnet_cdiv(a.N, R2_BN));
     const bool av = rows2_aligned(a);
-    if (a.b_piece) { if (av) hipLaunchKernelGGL((mfma_rows2_kernel<3, true>), grid, dim3(256), lds, st, a); else hipLaunchKernelGGL((mfma_rows2_kernel<3, false>), grid, dim3(256), lds, st, a); }
-    else { if (av) hipLaunchKernelGGL((mfma_rows2_kernel<1, true>), grid, dim3(256), lds, st, a); else hipLaunchKernelGGL((mfma_rows2_kernel<1, false>), grid, dim3(256), lds, st, a); }
+    if (av) hipLaunchKernelGGL((mfma_rows2_kernel<1, true>), grid, dim3(256), lds, st, a);
+    else hipLaunchKernelGGL((mfma_rows2_kernel<1, false>), grid, dim3(256), lds, st, a);
     return true;
 }
 template <int NJ>
@@ -1331,13 +1236,10 @@ void launch_rows3_nj(const RowsArgs& a, hipStream_t st) {
     else hipLaunchKernelGGL((mfma_rows3_kernel<NJ, 1>), grid, dim3(256), lds, st, a);
 }
 // general fp32 B (three packed pieces, a.b_piece apart), any K >= 1 / N >= 1, plain / alpha / bias / accumulate epilogue
-bool launch_rows3(const RowsArgs& a, hipStream_t st) {
-    static const bool off = getenv("SVNET_ROWS3_OFF") != nullptr;       // (diagnostic switch: the older one- / three-launch forms)
-    if (off || !a.B16 || !a.b_piece || a.col_scale || a.mask || a.col_sum || a.a_scale || a.M < 1024) return false;
+void launch_rows3(const RowsArgs& a, hipStream_t st) {
     if (a.N <= 64) launch_rows3_nj<1>(a, st);
     else if (a.N <= 128) launch_rows3_nj<2>(a, st);
     else launch_rows3_nj<4>(a, st);
-    return true;
 }
 template <int NT>
 void launch_rows(const RowsArgs& a, hipStream_t st) {
@@ -1346,6 +1248,9 @@ void launch_rows(const RowsArgs& a, hipStream_t st) {
     if (a.K > 64) { if (vec) launch_rows_v<NT, true, true>(a, st); else launch_rows_v<NT, false, true>(a, st); }
     else { if (vec) launch_rows_v<NT, true, false>(a, st); else launch_rows_v<NT, false, false>(a, st); }
 }
+// columns per workgroup (NT * 32) of the rows kernels.  Few row blocks (the classifier head: M = batch): narrow column tiles so that the
+// grid still has tens of workgroups
+int rows_cpb(int64_t M, int64_t N) { return (N <= 32 || M <= 512) ? 32 : (N <= 64 ? 64 : (N <= 128 ? 128 : 256)); }
 
 template <int IP, int JQ>
 void launch_tn2(TnArgs a, hipStream_t st) {
@@ -1357,14 +1262,14 @@ void launch_tn2(TnArgs a, hipStream_t st) {
     hipLaunchKernelGGL((mfma_tn2_kernel<IP, JQ>), dim3((unsigned)svnet_cdiv(a.M, rpb), (unsigned)svnet_cdiv(a.P, 64 * IP), (unsigned)svnet_cdiv(a.Q, 64 * JQ)),
                        dim3(256), 0, st, a);
 }
-template <int NQ, int BMODE>
-void launch_tn(TnArgs a, hipStream_t st) {
+template <int NQ>
+void launch_tn_tern(TnArgs a, hipStream_t st) {
     // (a partial tile mask names tiles 0..31 only: svnet_mfma_tn refuses one for Q > 1024)
     const int ptiles = (int)svnet_cdiv(a.P, 32);
     a.ptiles_per_block = ptiles >= 3 ? 4 : ptiles;
     int gz = (int)svnet_cdiv(a.Q, NQ * 32);
     a.qlist = 0;
-    if (BMODE == 1 && a.qmask != 0xFFFFFFFFu) {   // few tiles in use: one z group over exactly those (the A split is then shared)
+    if (a.qmask != 0xFFFFFFFFu) {   // few tiles in use: one z group over exactly those (the A split is then shared)
         int used = 0;
         uint32_t list = 0;
         for (int t = 0; t < 15 && t * 32 < a.Q; ++t)
@@ -1372,11 +1277,9 @@ void launch_tn(TnArgs a, hipStream_t st) {
         if (used > 0 && used <= NQ) { a.qlist = list; gz = 1; }
     }
     const int gy = (int)svnet_cdiv(ptiles, a.ptiles_per_block);
-    // ~4 workgroups per CU in total; 2 when the output is large (every row split ends in P*Q float atomics, which the memory
-    // side executes at ~1 TB/s: conv5's 512 x 505 gradient spent half its time there with 128 splits)
-    int64_t target = (BMODE == 1 || (int64_t)a.P * a.Q >= 128 * 1024) ? 512 : 1024;   // ternary: exactly one resident round (2 per CU)
-    if (const char* e = getenv("SVNET_TN_TARGET")) target = atoi(e);
-    int64_t want = svnet_cdiv(target, (int64_t)gy * gz);
+    // exactly one resident round (2 workgroups per CU): every row split ends in P*Q float atomics, which the memory side executes at
+    // ~1 TB/s (conv5's 512 x 505 gradient spent half its time there with 128 splits)
+    int64_t want = svnet_cdiv(512, (int64_t)gy * gz);
     int64_t rpb = svnet_cdiv(svnet_cdiv(a.M, want), 256) * 256;
     if (rpb < 256) rpb = 256;
     a.rows_per_block = rpb;
@@ -1384,18 +1287,14 @@ void launch_tn(TnArgs a, hipStream_t st) {
     const int nsub = 4 / a.ptiles_per_block;
     const size_t lds = (size_t)(nsub - 1) * a.ptiles_per_block * NQ * 1024 * sizeof(float);
     a.lds_reduce = (nsub > 1 && ptiles == a.ptiles_per_block && lds <= 64 * 1024) ? 1 : 0;
-    if (BMODE == 1) {
-        bool ok = true;                 // 8 KiB of static tables + up to 64 KiB of dynamic LDS: above the 64 KiB default
-        SVNET_LDS_OPTIN(ok, 64 * 1024, "mfma_tn_tern_kernel", reinterpret_cast<const void*>(&mfma_tn_tern_kernel<NQ, false>),
-                        reinterpret_cast<const void*>(&mfma_tn_tern_kernel<NQ, true>));
-        (void)ok;
-    }
-    if (BMODE == 1 && a.n16)
+    bool ok = true;                     // 8 KiB of static tables + up to 64 KiB of dynamic LDS: above the 64 KiB default
+    SVNET_LDS_OPTIN(ok, 64 * 1024, "mfma_tn_tern_kernel", reinterpret_cast<const void*>(&mfma_tn_tern_kernel<NQ, false>),
+                    reinterpret_cast<const void*>(&mfma_tn_tern_kernel<NQ, true>));
+    (void)ok;
+    if (a.n16)
         hipLaunchKernelGGL((mfma_tn_tern_kernel<NQ, true>), dim3((unsigned)gx, (unsigned)gy, (unsigned)gz), dim3(256), a.lds_reduce ? lds : 0, st, a);
-    else if (BMODE == 1)
-        hipLaunchKernelGGL((mfma_tn_tern_kernel<NQ, false>), dim3((unsigned)gx, (unsigned)gy, (unsigned)gz), dim3(256), a.lds_reduce ? lds : 0, st, a);
     else
-        hipLaunchKernelGGL((mfma_tn_kernel<NQ, 0>), dim3((unsigned)gx, (unsigned)gy, (unsigned)gz), dim3(256), a.lds_reduce ? lds : 0, st, a);
+        hipLaunchKernelGGL((mfma_tn_tern_kernel<NQ, false>), dim3((unsigned)gx, (unsigned)gy, (unsigned)gz), dim3(256), a.lds_reduce ? lds : 0, st, a);
 }
 
 }  // namespace
@@ -1418,7 +1317,7 @@ int svnet_mfma_rows(const svnet_gemm_desc& d, hipStream_t st) {
     a.mask = d.mask; a.col_sum = d.col_sum; a.accumulate = d.accumulate;
     a.a_vec = (d.a_rs % 4 == 0) && (reinterpret_cast<uintptr_t>(d.A) % 16 == 0);
     a.B16 = nullptr; a.Kp = 0; a.b_piece = 0;
-    const int cpb = (d.N <= 32 || d.M <= 512) ? 32 : (d.N <= 64 ? 64 : (d.N <= 128 ? 128 : 256));   // columns per workgroup (NT * 32)
+    const int cpb = rows_cpb(d.M, d.N);
     if (d.workspace && d.workspace_bytes >= svnet_gemm_workspace_bytes(d.N, d.K) && reinterpret_cast<uintptr_t>(d.workspace) % 16 == 0) {
         const int Kp = (int)((d.K + 15) / 16 * 16), Np = (int)((d.N + cpb - 1) / cpb * cpb);
         uint16_t* w = reinterpret_cast<uint16_t*>(d.workspace);
@@ -1427,10 +1326,9 @@ int svnet_mfma_rows(const svnet_gemm_desc& d, hipStream_t st) {
         SVNET_CHECK_LAUNCH("pack_b_bf16_kernel");
         a.B16 = w; a.Kp = Kp;
     }
-    // few row blocks (the classifier head: M = batch): narrow column tiles so that the grid still has tens of workgroups
-    if (d.N <= 32 || d.M <= 512) launch_rows<1>(a, st);
-    else if (d.N <= 64) launch_rows<2>(a, st);
-    else if (d.N <= 128) launch_rows<4>(a, st);
+    if (cpb == 32) launch_rows<1>(a, st);
+    else if (cpb == 64) launch_rows<2>(a, st);
+    else if (cpb == 128) launch_rows<4>(a, st);
     else launch_rows<8>(a, st);
     SVNET_CHECK_LAUNCH("mfma_rows_kernel");
     return SVNET_OK;
@@ -1440,13 +1338,14 @@ int svnet_mfma_rows(const svnet_gemm_desc& d, hipStream_t st) {
 // tile GEMM at 18 % of the f32 rate): B is split exactly into three bf16 pieces B = Bh + Bm + Bl, packed once (one launch), and
 // mfma_rows3_kernel multiplies them with the three pieces of A - the six leading bf16 x bf16 products per fp32 product (the dropped
 // ones are below 2^-24 of the product), fp32 accumulation: fp32-GEMM accuracy (tests: 2e-6 of the largest output against float64).
-// On the bf16 matrix cores six passes cost 6/16 of ONE f32-input MFMA pass.  (SVNET_ROWS3_OFF: the older nine-product forms below.)
+// On the bf16 matrix cores six passes cost 6/16 of ONE f32-input MFMA pass.
 // Epilogue terms that are not linear in B (column scale, mask, column sums, per-k scale) are not taken here (checked by the caller).
 int svnet_mfma_rows_split(const svnet_gemm_desc& d, hipStream_t st) {
     const size_t one = svnet_gemm_workspace_bytes(d.N, d.K);
     SVNET_REQUIRE(d.workspace && d.workspace_bytes >= 3 * one && reinterpret_cast<uintptr_t>(d.workspace) % 16 == 0 && one % 16 == 0, SVNET_E_WORKSPACE,
                   "svnet_mfma_rows_split: needs 3 x svnet_gemm_workspace_bytes of 16-byte aligned workspace");
     SVNET_REQUIRE(!d.col_scale && !d.mask && !d.col_sum && !d.a_scale, SVNET_E_UNSUPPORTED, "svnet_mfma_rows_split: plain or bias epilogue only");
+    SVNET_REQUIRE(d.M >= 1024, SVNET_E_UNSUPPORTED, "svnet_mfma_rows_split: M = %lld < 1024", (long long)d.M);
     SVNET_REQUIRE(d.a_rs < ((int64_t)1 << 24), SVNET_E_UNSUPPORTED, "svnet_mfma_rows_split: A row stride %lld >= 2^24", (long long)d.a_rs);
     RowsArgs a;
     a.A = d.A; a.lda = d.a_rs; a.a_scale = nullptr;
@@ -1456,7 +1355,7 @@ int svnet_mfma_rows_split(const svnet_gemm_desc& d, hipStream_t st) {
     a.alpha = d.alpha; a.col_scale = nullptr; a.bias = d.bias;
     a.mask = nullptr; a.col_sum = nullptr;
     a.a_vec = (d.a_rs % 4 == 0) && (reinterpret_cast<uintptr_t>(d.A) % 16 == 0);
-    const int cpb = (d.N <= 32 || d.M <= 512) ? 32 : (d.N <= 64 ? 64 : (d.N <= 128 ? 128 : 256));
+    const int cpb = rows_cpb(d.M, d.N);
     const int Kp = (int)((d.K + 15) / 16 * 16), Np = (int)((d.N + cpb - 1) / cpb * cpb);
     a.Kp = Kp;
     hipLaunchKernelGGL(pack_b_bf16_kernel, dim3(svnet_grid((int64_t)Kp * Np, 256)), dim3(256), 0, st, d.B, d.b_rs, d.b_cs, (int)d.K, (int)d.N, Kp, Np,
@@ -1465,25 +1364,8 @@ int svnet_mfma_rows_split(const svnet_gemm_desc& d, hipStream_t st) {
     a.B16 = reinterpret_cast<uint16_t*>(d.workspace);
     a.accumulate = d.accumulate;
     a.b_piece = (int64_t)(one / 2);
-    if (launch_rows3(a, st)) {                                            // A split once per element, one launch
-        SVNET_CHECK_LAUNCH("mfma_rows3_kernel");
-        return SVNET_OK;
-    }
-    if (launch_rows2(a, st)) {                                            // one launch: A read once for the three pieces, C written once
-        SVNET_CHECK_LAUNCH("mfma_rows2_kernel (split B)");
-        return SVNET_OK;
-    }
-    a.b_piece = 0;
-    for (int piece = 0; piece < 3; ++piece) {                             // other shapes: the exact-B kernel once per piece, accumulating
-        a.B16 = reinterpret_cast<uint16_t*>(reinterpret_cast<char*>(d.workspace) + piece * one);
-        a.accumulate = (piece > 0 || d.accumulate) ? 1 : 0;
-        if (piece > 0) a.bias = nullptr;                                  // (the bias goes in once)
-        if (d.N <= 32 || d.M <= 512) launch_rows<1>(a, st);
-        else if (d.N <= 64) launch_rows<2>(a, st);
-        else if (d.N <= 128) launch_rows<4>(a, st);
-        else launch_rows<8>(a, st);
-        SVNET_CHECK_LAUNCH("mfma_rows_kernel (split B)");
-    }
+    launch_rows3(a, st);                                                  // A split once per element, one launch
+    SVNET_CHECK_LAUNCH("mfma_rows3_kernel");
     return SVNET_OK;
 }
 
@@ -1503,9 +1385,7 @@ int svnet_mfma_tn(const float* A, int64_t lda, const float* B, int64_t ldb, cons
     a.C = C; a.c_ps = c_ps; a.c_qs = c_qs; a.M = M; a.P = (int)P; a.Q = (int)Q; a.alpha = alpha; a.rows_per_block = 0; a.lds_reduce = 0;
     a.qmask = q_tile_mask ? q_tile_mask : 0xFFFFFFFFu;
     a.n16 = nullptr; a.gy = nullptr; a.smax = a.smin = nullptr; a.chc = nullptr; a.kk = 1; a.kmagic = 0; a.npts = 0;
-    const bool tern = b_sign != nullptr;
-    static const bool tn2_off = getenv("SVNET_TN2_OFF") != nullptr;     // (diagnostic switch: the per-wave-split kernel)
-    if (!tern && !tn2_off) {                                            // fp32 x fp32: the LDS-tiled kernel
+    if (!b_sign) {                                                      // fp32 x fp32: the LDS-tiled kernel
         // the largest tile that still leaves >= 32 tiles: every row split adds one float atomic per output element, and with few tiles
         // the grid is filled by row splits ([512 x 127] as four 128 x 128 tiles: 128 splits, 50 of its 82 us in the atomics)
         auto tiles = [&](int ip, int jq) { return svnet_cdiv(P, 64 * ip) * svnet_cdiv(Q, 64 * jq); };
@@ -1517,12 +1397,13 @@ int svnet_mfma_tn(const float* A, int64_t lda, const float* B, int64_t ldb, cons
         SVNET_CHECK_LAUNCH("mfma_tn2_kernel");
         return SVNET_OK;
     }
-    if (Q <= 32) { if (tern) launch_tn<1, 1>(a, st); else launch_tn<1, 0>(a, st); }
-    else if (Q <= 64) { if (tern) launch_tn<2, 1>(a, st); else launch_tn<2, 0>(a, st); }
-    else if (Q <= 128) { if (tern) launch_tn<4, 1>(a, st); else launch_tn<4, 0>(a, st); }
-    else if (Q <= 160 || Q == 320) { if (tern) launch_tn<5, 1>(a, st); else launch_tn<5, 0>(a, st); }   // 320 = fused edge block
-    else { if (tern) launch_tn<5, 1>(a, st); else launch_tn<4, 0>(a, st); }   // ternary: 160-column groups too - the 5-tile kernel keeps a whole block of A and the next plane words in flight (8 tiles: 255 VGPRs, neither), worth more than the extra L2 reads of A (conv5: -60 us per step)   // fp32 B: 128-column groups (register budget of the prefetch)
-    SVNET_CHECK_LAUNCH("mfma_tn_kernel");
+    // ternary B.  Past 128 columns: 160-column groups - the 5-tile kernel keeps a whole block of A and the next plane words in flight
+    // (8 tiles: 255 VGPRs, neither), worth more than the extra L2 reads of A (conv5: -60 us per step)
+    if (Q <= 32) launch_tn_tern<1>(a, st);
+    else if (Q <= 64) launch_tn_tern<2>(a, st);
+    else if (Q <= 128) launch_tn_tern<4>(a, st);
+    else launch_tn_tern<5>(a, st);
+    SVNET_CHECK_LAUNCH("mfma_tn_tern_kernel");
     return SVNET_OK;
 }
 
@@ -1548,9 +1429,7 @@ extern "C" int svnet_edgeblock_wgrad_f32(const int16_t* n16, const uint8_t* slot
         // (one 8-wave workgroup per CU: 126 KB of LDS.  256 workgroups - one round, every CU held for the whole launch - measured 4.356 /
         //  4.370 / 4.366 ms per step against 4.339 / 4.338 / 4.349 with 384: the shorter workgroups hand their CUs back to the gather on the main
         //  stream half-way; 320: 4.351, 448: 4.361, 512: 4.406, 128: 4.417; profiles/r04_ab_aff2_target.log)
-        int64_t target = 384;
-        if (const char* e = getenv("SVNET_AFF2_TARGET")) target = atoi(e);
-        int64_t rpb = svnet_cdiv(svnet_cdiv(E, target), 64) * 64;
+        int64_t rpb = svnet_cdiv(svnet_cdiv(E, 384), 64) * 64;
         if (rpb < 256) rpb = 256;
         a.rows_per_block = rpb;
         bool ok = true;
@@ -1560,7 +1439,7 @@ extern "C" int svnet_edgeblock_wgrad_f32(const int16_t* n16, const uint8_t* slot
         SVNET_CHECK_LAUNCH("mfma_tn_aff2_kernel");
         return SVNET_OK;
     }
-    launch_tn<5, 1>(a, st);
+    launch_tn_tern<5>(a, st);
     SVNET_CHECK_LAUNCH("mfma_tn_tern_kernel (affine)");
     return SVNET_OK;
 }

@@ -75,12 +75,11 @@ class Linear(nn.Linear):
         if bw:
             self.scale = nn.Parameter(torch.ones(1, out_channels) / math.sqrt(in_channels))
 
-    def forward(self, x, vstats=False):
-        """vstats: a hint from SVBlock - x holds [..., 3, K] vectors and a VectorBN takes the output next (see _ops.BwLinear)."""
+    def forward(self, x):
         if self.bw and self.ba:
             return _ops.BinLinear.apply(x, self.weight, self.beta, self.scale, self.bias, self.training)
         if self.bw:
-            y = _ops.BwLinear.apply(x, self.weight, self.scale, self.training, bool(vstats) and self.bias is None)
+            y = _ops.BwLinear.apply(x, self.weight, self.scale, self.training)
             return y if self.bias is None else y + self.bias
         if self.ba:
             raise AttributeError("'Linear' object has no attribute 'scale'")  # same failure as the reference (:49)
@@ -383,7 +382,7 @@ class SVBlock(nn.Module):
             main, side = torch.cuda.current_stream(s_point.device), _ops._side_stream(s_point.device)
             side.wait_stream(main)
             with torch.cuda.stream(side):
-                v_lin = self.linear2(v, vstats=True)
+                v_lin = self.linear2(v)
         # cat[s_point, Vector2Scalar(v)] in place + the per-cloud mean of s_point (one consumer of s_point in the autograd graph)
         cat_pt, mean_pt = _ops.V2SCat.apply(s_point, v, lz.weight, lz.scale if lz.bw else None, self.training, B)
         v_scale = _ops.GateMLP.apply(torch.cat([mean_pt, s_cloud], dim=-1), self.gate[0].weight, self.gate[2].weight)
@@ -403,7 +402,7 @@ class SVBlock(nn.Module):
             main.wait_stream(side)
             v_out.record_stream(main)
         else:
-            v_out = self.bn2(self.linear2(v, vstats=True), gate=v_scale)
+            v_out = self.bn2(self.linear2(v), gate=v_scale)
         return (s_out, v_out)
 
     @staticmethod
@@ -423,7 +422,7 @@ class SVBlock(nn.Module):
             main, side = torch.cuda.current_stream(s.device), _ops._side_stream(s.device)
             side.wait_stream(main)
             with torch.cuda.stream(side):
-                v_lin = self.linear2(v, vstats=True)
+                v_lin = self.linear2(v)
             fused = self._cat_and_gate(s, v)
             if fused is not None:
                 s_cat, v_scale = fused
@@ -446,7 +445,7 @@ class SVBlock(nn.Module):
         if not prebn:
             s = batch_norm_act(self.bn1, s, _ACT_LEAKY, self.relu.negative_slope)
 
-        v = self.linear2(v, vstats=True)
+        v = self.linear2(v)
         if pretail:
             return (s, v, v_scale)
         v = self.bn2(v, gate=v_scale)

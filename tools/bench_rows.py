@@ -1,5 +1,5 @@
 """Diagnostic: one rows-GEMM shape (default: conv5's dx product, [32768 x 512] x [512 x 505] against sign weights, with the per-k scale,
-the STE mask and the column sums the step passes), timed alone with HIP events.  SVNET_ROWS_NO_DB=1 selects the unpipelined kernel.
+the STE mask and the column sums the step passes), timed alone with HIP events.
     python tools/bench_rows.py [M K N] [--plain] [--reps R]"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

@@ -21,4 +21,4 @@ for (Cs, Cv, Os) in [(64, 21, 128), (32, 10, 64), (32, 10, 32)]:
     a.record()
     for _ in range(20): run()
     b.record(); torch.cuda.synchronize()
-    print("Os=%d used=%x  %.1f us   target=%s dbg=%s" % (Os, used, a.elapsed_time(b) / 20 * 1e3, os.environ.get("SVNET_TN_TARGET"), os.environ.get("SVNET_TN_DBG")), flush=True)
+    print("Os=%d used=%x  %.1f us" % (Os, used, a.elapsed_time(b) / 20 * 1e3), flush=True)

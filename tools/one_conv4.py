@@ -1,5 +1,6 @@
 """Runs the fused fwd+bwd of one conv4-shaped edge layer (Cs=64 Cv=21 -> Os=128 Ov=42, B=32 N=1024 k=20) a few times: the profiling
-target of tools/tile_pmc.sh (SVNET_BWD_MODE = 0 product, 2 return after phase A, 3 return after phase B)."""
+target of tools/tile_pmc.sh (SVNET_BWD_MODE = 0 product, 2 return after phase A, 3 return after phase B: read only by a -DSVNET_BWD_MODES
+build of the library, which tile_pmc.sh selects through SVNET_DIAG_LIB)."""
 import contextlib, io, os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from svnet_amd import config

@@ -1,11 +1,15 @@
 #!/bin/bash
 # Run ON the GPU box: SQ counters of the conv4 tile kernel (edgeblock_bwd_kernel<.,8,44>) per PHASE, by difference of its timing-only
-# ablation builds (SVNET_BWD_MODE=2: return after phase A, 3: return after phase B, 0: the product) - three counter passes per mode,
+# ablations (SVNET_BWD_MODE=2: return after phase A, 3: return after phase B, 0: the product) - three counter passes per mode,
 # each its own run with --kernel-trace + --pmc only.  Output: gpurun_out/$TAG_mode{0,2,3}_{a,b,c}_summary.csv
+# The ablations are compiled into a variant build only (the product library never reads SVNET_BWD_MODE), loaded through SVNET_DIAG_LIB:
+#   make -C svnet_amd/csrc BUILD=_build_bwd_modes OUT=../../_ab/libsvnet_bwd_modes.so EXTRA=-DSVNET_BWD_MODES
 # usage: TAG=r04_tile bash tools/tile_pmc.sh
 TAG=${TAG:-r04_tile}
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out
+export SVNET_DIAG_LIB=${SVNET_DIAG_LIB:-$ROOT/_ab/libsvnet_bwd_modes.so}
+[ -f "$SVNET_DIAG_LIB" ] || { echo "$SVNET_DIAG_LIB is missing: build it with EXTRA=-DSVNET_BWD_MODES"; exit 1; }
 cd /tmp && export TMPDIR=/tmp
 for m in 0 2 3; do
   export SVNET_BWD_MODE=$m

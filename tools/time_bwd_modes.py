@@ -1,4 +1,6 @@
-"""Times edgeblock_bwd_kernel ablations (SVNET_BWD_MODE) on conv2- and conv4-shaped layers at the headline size."""
+"""Times edgeblock_bwd_kernel ablations (SVNET_BWD_MODE) on conv2- and conv4-shaped layers at the headline size.  The product library
+has MODE 0 only; the ablations live in a variant build, loaded through SVNET_DIAG_LIB (default _ab/libsvnet_bwd_modes.so):
+make -C svnet_amd/csrc BUILD=_build_bwd_modes OUT=../../_ab/libsvnet_bwd_modes.so EXTRA=-DSVNET_BWD_MODES"""
 import os, sys, subprocess, json
 if len(sys.argv) > 1:
     import torch, contextlib, io
@@ -25,5 +27,8 @@ if len(sys.argv) > 1:
             res["%s Os=%d" % (name[16:19], Os)] = round(min(t.elapsed_ms()[1:]), 3)
     print("MODE", os.environ.get("SVNET_BWD_MODE", "0"), json.dumps(res), flush=True)
 else:
+    lib = os.environ.get("SVNET_DIAG_LIB") or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "_ab", "libsvnet_bwd_modes.so")
+    if not os.path.exists(lib):
+        sys.exit("%s is missing: build it with EXTRA=-DSVNET_BWD_MODES (see the top of this file)" % lib)
     for m in ("0", "1", "2", "3"):
-        subprocess.run([sys.executable, __file__, "run"], env=dict(os.environ, SVNET_BWD_MODE=m))
+        subprocess.run([sys.executable, __file__, "run"], env=dict(os.environ, SVNET_BWD_MODE=m, SVNET_DIAG_LIB=lib))
