@@ -1274,6 +1274,43 @@ class VBN(torch.autograd.Function):
 
 # ----------------------------------------------------------------------------- pooling / activations / loss
 
+def _pool_dims(x, dim):
+    """(dim, outer, R, inner) of x viewed as [outer, R, inner] around its axis `dim`."""
+    dim = dim % x.dim()
+    outer = inner = 1
+    for d in x.shape[:dim]:
+        outer *= d
+    for d in x.shape[dim + 1:]:
+        inner *= d
+    return dim, outer, x.shape[dim], inner
+
+
+def _split_workspace_bytes(outer, R, inner, vtail=False):
+    """Bytes of the workspace [arg-max keys | partial sums] that lets a [max | mean] pass over a long axis be split over workgroups
+    (csrc/split_reduce.h); 0 = the library has no split path for this shape.  vtail: the vector tail's pass over [outer, R, 3, inner]."""
+    L = _lib.lib()
+    if vtail:
+        return L.svnet_vtail_workspace_bytes(outer, R, inner)
+    nb0, nb1 = L.svnet_pool_workspace_bytes(outer, R, inner, 0), L.svnet_pool_workspace_bytes(outer, R, inner, 1)
+    return nb0 + nb1 if nb0 and nb1 else 0
+
+
+def _split_workspace(dev, outer, R, inner, zeroed=False, vtail=False):
+    """(block, bytes) of that workspace, (None, 0) without a split path.  zeroed: from the step's zero-filled arena, i.e. zero keys from
+    the step's one fill and no memset launch in front of the pass (the entry point's workspace_zeroed = 1); otherwise a plain block
+    whose keys the entry point fills."""
+    nb = _split_workspace_bytes(outer, R, inner, vtail)
+    if not nb:
+        return None, 0
+    return (_zeros((nb,), torch.uint8, dev) if zeroed else torch.empty((nb,), dtype=torch.uint8, device=dev)), nb
+
+
+def _tap_pools(*args):
+    """Decision tap (tests): the arg-max of a pooling; the parts of a pooled concatenation make one record, as the concatenation's."""
+    if TAP is not None:
+        TAP["pools"].append(args[0] if len(args) == 1 else torch.cat(args, dim=1))
+
+
 def pool_raw(x, outer, R, inner, mode, out=None):
     """x contiguous viewed as [outer,R,inner] -> (out [outer,inner], argmax int32 or None).  `out`: an [outer, inner] column slice
     of a wider row-major tensor (stride(0) = its row length) to write into instead of a fresh tensor."""
@@ -1288,13 +1325,11 @@ def pool_raw(x, outer, R, inner, mode, out=None):
 
 def pool_maxmean_raw(x, outer, R, inner, out_max, out_mean):
     """[max | mean] of x viewed as [outer,R,inner] into two [outer, inner] column slices of one row-major tensor (same row stride);
-    returns the arg-max.  One pass over x when the reduced axis is long, two pool_raw calls otherwise."""
-    L = _lib.lib()
-    nb0, nb1 = L.svnet_pool_workspace_bytes(outer, R, inner, 0), L.svnet_pool_workspace_bytes(outer, R, inner, 1)
-    if R >= 256 and nb0 and nb1 and out_max.stride(0) == out_mean.stride(0):
+    returns the arg-max.  One pass over x when the library has a split path for the shape, two pool_raw calls otherwise."""
+    ws, nb = _split_workspace(x.device, outer, R, inner) if out_max.stride(0) == out_mean.stride(0) else (None, 0)
+    if nb:
         arg = torch.empty((outer, inner), dtype=torch.int32, device=x.device)
-        ws = torch.empty((nb0 + nb1,), dtype=torch.uint8, device=x.device)
-        call("svnet_pool_maxmean_fwd_f32", _p(x), outer, R, inner, _p(out_max), _p(out_mean), out_max.stride(0), _p(arg), _p(ws), nb0 + nb1,
+        call("svnet_pool_maxmean_fwd_f32", _p(x), outer, R, inner, _p(out_max), _p(out_mean), out_max.stride(0), _p(arg), _p(ws), nb,
              _stream())
         return arg
     _, arg = pool_raw(x, outer, R, inner, 0, out=out_max)
@@ -1309,19 +1344,11 @@ class Pool(torch.autograd.Function):
     def forward(ctx, x, dim, mode):
         _hip(x)
         x = _f32c(x)
-        dim = dim % x.dim()
-        outer = 1
-        for d in x.shape[:dim]:
-            outer *= d
-        R = x.shape[dim]
-        inner = 1
-        for d in x.shape[dim + 1:]:
-            inner *= d
+        dim, outer, R, inner = _pool_dims(x, dim)
         out, arg = pool_raw(x, outer, R, inner, mode)
         if arg is not None:
             ctx.save_for_backward(arg)
-            if TAP is not None:
-                TAP["pools"].append(arg)
+            _tap_pools(arg)
         ctx.meta = (outer, R, inner, mode, x.shape)
         return out.view(x.shape[:dim] + x.shape[dim + 1:])
 
@@ -1350,8 +1377,7 @@ class PoolMaxParts(torch.autograd.Function):
         _, arg_a = pool_raw(a, B, N, Ca, 0, out=out[:, :Ca])
         _, arg_b = pool_raw(b, B, N, Cb, 0, out=out[:, Ca:])
         ctx.save_for_backward(arg_a, arg_b)
-        if TAP is not None:
-            TAP["pools"].append(torch.cat([arg_a, arg_b], dim=1))
+        _tap_pools(arg_a, arg_b)
         ctx.meta = (B, N, Ca, Cb)
         return out
 
@@ -1376,19 +1402,11 @@ class PoolMaxMean(torch.autograd.Function):
     def forward(ctx, x, dim):
         _hip(x)
         x = _f32c(x)
-        dim = dim % x.dim()
-        outer = 1
-        for d in x.shape[:dim]:
-            outer *= d
-        R = x.shape[dim]
-        inner = 1
-        for d in x.shape[dim + 1:]:
-            inner *= d
+        dim, outer, R, inner = _pool_dims(x, dim)
         out = torch.empty((outer, 2 * inner), dtype=torch.float32, device=x.device)
         arg = pool_maxmean_raw(x, outer, R, inner, out[:, :inner], out[:, inner:])
         ctx.save_for_backward(arg)
-        if TAP is not None:
-            TAP["pools"].append(arg)
+        _tap_pools(arg)
         ctx.meta = (outer, R, inner, x.shape)
         return out.view(x.shape[:dim] + (2 * inner,)) if x.dim() - dim == 2 else out
 
@@ -1400,6 +1418,79 @@ class PoolMaxMean(torch.autograd.Function):
         dx = torch.empty(xshape, dtype=torch.float32, device=g.device)
         call("svnet_pool_maxmean_bwd_f32", _p(g2), _p(g2[:, inner:]), 2 * inner, _p(arg), outer, R, inner, _p(dx), _stream())
         return dx, None
+
+
+# ---- the global pooling family: [max | mean] over the points of cat[a, b], computed from the two parts where they lie.  Stated once
+# here: the column layout (_maxmean_slices), the plain half (_plain_half_fwd / _bwd: a part that is pooled as it lies), the BatchNorm
+# half (_bn_half_fwd / _bwd: a part whose BatchNorm + activation run inside the pooling pass).  The Functions below compose them; a
+# half that runs `beside` runs on the side stream, and the Function joins (main.wait_stream(side)) behind its main-stream half.
+
+def _maxmean_slices(t, Ca, Cb):
+    """The columns of `out` [B, 2*(Ca+Cb)] = [max a | max b | mean a | mean b], and of its gradient: (max a, mean a, max b, mean b)
+    as slices of t (rows of stride 2*(Ca+Cb))."""
+    C = Ca + Cb
+    return t[:, :Ca], t[:, C:C + Ca], t[:, Ca:C], t[:, C + Ca:]
+
+
+def _plain_half_fwd(x, out_max, out_mean, beside=False):
+    """x [B,N,Cx] pooled into its two slices; returns the arg-max.  beside: on the side stream (the two parts are independent)."""
+    B, N, Cx = x.shape
+    if not beside:
+        return pool_maxmean_raw(x, B, N, Cx, out_max, out_mean)
+    main, side = torch.cuda.current_stream(x.device), _side_stream(x.device)
+    side.wait_stream(main)
+    with torch.cuda.stream(side):
+        arg = pool_maxmean_raw(x, B, N, Cx, out_max, out_mean)
+        arg.record_stream(main)
+    return arg
+
+
+def _plain_half_bwd(g_max, g_mean, arg, N, beside=False):
+    """dx [B,N,Cx] of a plain half from its two slices of the gradient."""
+    B, Cx = arg.shape
+    dev = arg.device
+    dx = torch.empty((B, N, Cx), dtype=torch.float32, device=dev)      # (the main stream's pool: its consumer runs there)
+
+    def run():
+        call("svnet_pool_maxmean_bwd_f32", _p(g_max), _p(g_mean), g_max.stride(0), _p(arg), B, N, Cx, _p(dx), _stream())
+
+    if beside:
+        side = _side_stream(dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):
+            run()
+    else:
+        run()
+    return dx
+
+
+def _bn_half_fwd(y2, mean, invstd, gamma, beta, B, N, act, slope, out_max, out_mean):
+    """act(bn(y)) of the pre-BN y2 [B*N, Ca] pooled into its two slices without being written (svnet_bn_pool_fwd_f32); returns the
+    arg-max."""
+    Ca = y2.shape[1]
+    ws, nb = _split_workspace(y2.device, B, N, Ca, zeroed=True)
+    arg = torch.empty((B, Ca), dtype=torch.int32, device=y2.device)
+    call("svnet_bn_pool_fwd_f32", _p(y2), _p(mean), _p(invstd), _p(gamma), _p(beta), B, N, Ca, act, slope, _p(out_max), _p(out_mean),
+         out_max.stride(0), _p(arg), _p(ws), nb, 1, _stream())
+    return arg
+
+
+def _tap_bn_half(y2, mean, invstd, gamma, beta, act):
+    """Decision tap (tests): the kink decisions of the BatchNorm + activation the pooling pass evaluates (same expression)."""
+    if TAP is not None and "acts" in TAP and act in (1, 2):
+        TAP["acts"].append((gamma.data_ptr(), ((y2 - mean) * invstd * gamma + beta) > 0))
+
+
+def _bn_half_bwd(g_max, g_mean, arg, y2, mean, invstd, gamma, beta, N, act, slope, training, need_dy, red=None):
+    """(dy [B,N,Ca] or None, red) of a BatchNorm half from its two slices of the gradient (svnet_bn_pool_bwd_f32): red[:Ca] = dbeta,
+    red[Ca:2*Ca] = dgamma.  red: a zero-filled sliced accumulator of 2*Ca the caller already holds."""
+    B, Ca = arg.shape
+    dy = torch.empty((B, N, Ca), dtype=torch.float32, device=arg.device) if need_dy else None
+    if red is None:
+        red = _zeros((_sliced_len(2 * Ca),), torch.float32, arg.device)
+    call("svnet_bn_pool_bwd_f32", _p(g_max), _p(g_mean), g_max.stride(0), _p(arg), _p(y2), _p(mean), _p(invstd), _p(gamma), _p(beta), B, N, Ca,
+         act, slope, int(training), _p(red), _p(dy), _stream())
+    return dy, red
 
 
 class GlobalMaxMeanPool(torch.autograd.Function):
@@ -1414,35 +1505,24 @@ class GlobalMaxMeanPool(torch.autograd.Function):
         a, b = _f32c(a), _f32c(b)
         B, N, Ca = a.shape
         Cb = b.shape[-1]
-        C = Ca + Cb
-        out = torch.empty((B, 2 * C), dtype=torch.float32, device=a.device)
-        main, side = torch.cuda.current_stream(a.device), _side_stream(a.device)
-        side.wait_stream(main)
-        with torch.cuda.stream(side):                                   # the two parts are independent: b beside a
-            arg_b = pool_maxmean_raw(b, B, N, Cb, out[:, Ca:C], out[:, C + Ca:])
-            arg_b.record_stream(main)
-        arg_a = pool_maxmean_raw(a, B, N, Ca, out[:, :Ca], out[:, C:C + Ca])
-        main.wait_stream(side)
+        out = torch.empty((B, 2 * (Ca + Cb)), dtype=torch.float32, device=a.device)
+        max_a, mean_a, max_b, mean_b = _maxmean_slices(out, Ca, Cb)
+        arg_b = _plain_half_fwd(b, max_b, mean_b, beside=True)
+        arg_a = _plain_half_fwd(a, max_a, mean_a)
+        torch.cuda.current_stream(a.device).wait_stream(_side_stream(a.device))
         ctx.save_for_backward(arg_a, arg_b)
-        if TAP is not None:
-            TAP["pools"].append(torch.cat([arg_a, arg_b], dim=1))
-        ctx.meta = (B, N, Ca, Cb)
+        _tap_pools(arg_a, arg_b)
+        ctx.N = N
         return out
 
     @staticmethod
     def backward(ctx, g):
-        B, N, Ca, Cb = ctx.meta
         arg_a, arg_b = ctx.saved_tensors
-        C = Ca + Cb
         g = _f32c(g)
-        da = torch.empty((B, N, Ca), dtype=torch.float32, device=g.device)
-        db = torch.empty((B, N, Cb), dtype=torch.float32, device=g.device)
-        main, side = torch.cuda.current_stream(g.device), _side_stream(g.device)
-        side.wait_stream(main)
-        with torch.cuda.stream(side):
-            call("svnet_pool_maxmean_bwd_f32", _p(g[:, Ca:]), _p(g[:, C + Ca:]), 2 * C, _p(arg_b), B, N, Cb, _p(db), _stream())
-        call("svnet_pool_maxmean_bwd_f32", _p(g), _p(g[:, C:]), 2 * C, _p(arg_a), B, N, Ca, _p(da), _stream())
-        main.wait_stream(side)
+        gmax_a, gmean_a, gmax_b, gmean_b = _maxmean_slices(g, arg_a.shape[1], arg_b.shape[1])
+        db = _plain_half_bwd(gmax_b, gmean_b, arg_b, ctx.N, beside=True)
+        da = _plain_half_bwd(gmax_a, gmean_a, arg_a, ctx.N)
+        torch.cuda.current_stream(g.device).wait_stream(_side_stream(g.device))
         return da, db
 
 
@@ -1459,52 +1539,33 @@ class GlobalMaxMeanPoolBN(torch.autograd.Function):
         y, b = _f32c(y), _f32c(b)
         B, N, Ca = y.shape
         Cb = b.shape[-1]
-        C = Ca + Cb
-        L = _lib.lib()
         y2 = y.reshape(B * N, Ca)
         mean, invstd = _batch_stats(y2, B * N, Ca, 0, running_mean, running_var, training, momentum, eps, nbt)
-        out = torch.empty((B, 2 * C), dtype=torch.float32, device=y.device)
-        main, side = torch.cuda.current_stream(y.device), _side_stream(y.device)
-        side.wait_stream(main)
-        with torch.cuda.stream(side):                                   # the two parts are independent: b beside a
-            arg_b = pool_maxmean_raw(b, B, N, Cb, out[:, Ca:C], out[:, C + Ca:])
-            arg_b.record_stream(main)
-        nb = L.svnet_pool_workspace_bytes(B, N, Ca, 0) + L.svnet_pool_workspace_bytes(B, N, Ca, 1)
-        ws = _zeros((nb,), torch.uint8, y.device)          # (zero keys from the step's one fill: no memset launch in front of the pass)
-        arg_a = torch.empty((B, Ca), dtype=torch.int32, device=y.device)
-        call("svnet_bn_pool_fwd_f32", _p(y2), _p(mean), _p(invstd), _p(gamma), _p(beta), B, N, Ca, act, slope, _p(out), _p(out[:, C:]),
-             2 * C, _p(arg_a), _p(ws), nb, 1, _stream())
-        main.wait_stream(side)
+        out = torch.empty((B, 2 * (Ca + Cb)), dtype=torch.float32, device=y.device)
+        max_a, mean_a, max_b, mean_b = _maxmean_slices(out, Ca, Cb)
+        arg_b = _plain_half_fwd(b, max_b, mean_b, beside=True)
+        arg_a = _bn_half_fwd(y2, mean, invstd, gamma, beta, B, N, act, slope, max_a, mean_a)
+        torch.cuda.current_stream(y.device).wait_stream(_side_stream(y.device))
         ctx.save_for_backward(y2, mean, invstd, gamma, beta, arg_a, arg_b)
-        if TAP is not None:
-            TAP["pools"].append(torch.cat([arg_a, arg_b], dim=1))
-            if "acts" in TAP and act in (1, 2):      # the kink decisions of the BatchNorm + activation the pooling pass evaluates (same expression)
-                TAP["acts"].append((gamma.data_ptr(), ((y2 - mean) * invstd * gamma + beta) > 0))
-        ctx.meta = (B, N, Ca, Cb, act, slope, bool(training))
+        _tap_pools(arg_a, arg_b)
+        _tap_bn_half(y2, mean, invstd, gamma, beta, act)
+        ctx.meta = (N, act, slope, bool(training))
         return out
 
     @staticmethod
     def supported(B, N, Ca):
-        L = _lib.lib()
-        return N >= 256 and L.svnet_pool_workspace_bytes(B, N, Ca, 0) > 0 and L.svnet_pool_workspace_bytes(B, N, Ca, 1) > 0
+        return _split_workspace_bytes(B, N, Ca) > 0
 
     @staticmethod
     def backward(ctx, g):
         y2, mean, invstd, gamma, beta, arg_a, arg_b = ctx.saved_tensors
-        B, N, Ca, Cb, act, slope, training = ctx.meta
-        C = Ca + Cb
+        N, act, slope, training = ctx.meta
+        Ca = arg_a.shape[1]
         g = _f32c(g)
-        dev = g.device
-        db = torch.empty((B, N, Cb), dtype=torch.float32, device=dev)
-        dy = torch.empty((B, N, Ca), dtype=torch.float32, device=dev) if ctx.needs_input_grad[0] else None
-        red = _zeros((_sliced_len(2 * Ca),), torch.float32, dev)
-        main, side = torch.cuda.current_stream(dev), _side_stream(dev)
-        side.wait_stream(main)
-        with torch.cuda.stream(side):
-            call("svnet_pool_maxmean_bwd_f32", _p(g[:, Ca:]), _p(g[:, C + Ca:]), 2 * C, _p(arg_b), B, N, Cb, _p(db), _stream())
-        call("svnet_bn_pool_bwd_f32", _p(g), _p(g[:, C:]), 2 * C, _p(arg_a), _p(y2), _p(mean), _p(invstd), _p(gamma), _p(beta), B, N, Ca,
-             act, slope, int(training), _p(red), _p(dy), _stream())
-        main.wait_stream(side)
+        gmax_a, gmean_a, gmax_b, gmean_b = _maxmean_slices(g, Ca, arg_b.shape[1])
+        db = _plain_half_bwd(gmax_b, gmean_b, arg_b, N, beside=True)
+        dy, red = _bn_half_bwd(gmax_a, gmean_a, arg_a, y2, mean, invstd, gamma, beta, N, act, slope, training, ctx.needs_input_grad[0])
+        torch.cuda.current_stream(g.device).wait_stream(_side_stream(g.device))
         return dy, db, red[Ca:2 * Ca], red[:Ca], None, None, None, None, None, None, None, None
 
 
@@ -1531,8 +1592,6 @@ class GlobalMaxMeanPoolBNV(torch.autograd.Function):
         B, N, Ca = y.shape
         C = v_lin.shape[-1]
         Cb, P = 3 * C, B * N
-        Ct = Ca + Cb
-        L = _lib.lib()
         dev = y.device
         y2, v3 = y.reshape(P, Ca), v_lin.reshape(P, 3, C)
         gate2 = None if gate is None else _f32c(gate).reshape(B, C)
@@ -1543,12 +1602,12 @@ class GlobalMaxMeanPoolBNV(torch.autograd.Function):
         else:
             sczf, w_eff = None, Wzc
         mean1, invstd1 = _batch_stats(y2, P, Ca, 0, rm1, rv1, training, momentum, eps, nbt1)
-        out = torch.empty((B, 2 * Ct), dtype=torch.float32, device=dev)
+        out = torch.empty((B, 2 * (Ca + Cb)), dtype=torch.float32, device=dev)
+        max_a, mean_a, max_b, mean_b = _maxmean_slices(out, Ca, Cb)
         mean2 = torch.empty((C,), dtype=torch.float32, device=dev)
         invstd2 = torch.empty((C,), dtype=torch.float32, device=dev)
         arg_b = torch.empty((B, Cb), dtype=torch.int32, device=dev)
-        nbw = L.svnet_vtail_workspace_bytes(B, N, C)
-        wsb = _zeros((nbw,), torch.uint8, dev)              # (zero keys from the step's one fill: no memset launch in front of the pass)
+        wsb, nbw = _split_workspace(dev, B, N, C, zeroed=True, vtail=True)
         main, side = torch.cuda.current_stream(dev), _side_stream(dev)
         side.wait_stream(main)                                          # (the gate and the statistics buffers come from this stream)
         with torch.cuda.stream(side):                                   # the vector half beside the scalar half
@@ -1560,18 +1619,12 @@ class GlobalMaxMeanPoolBNV(torch.autograd.Function):
                 call("svnet_bn_eval_stats_f32", _p(rm2), _p(rv2), C, eps, _p(mean2), _p(invstd2), _stream())
             call("svnet_vtail_fwd_f32", _p(v3), _p(sums), eps, momentum, _p(mean2), _p(invstd2), _p(rm2) if training else None,
                  _p(rv2) if training else None, _p(nbt2) if training else None, _p(g2), _p(b2), _p(gate2), _p(w_eff), B, N, C,
-                 _p(out[:, Ca:]), _p(out[:, Ct + Ca:]), 2 * Ct, _p(arg_b), _p(wsb), nbw, 1, _stream())
-        nb = L.svnet_pool_workspace_bytes(B, N, Ca, 0) + L.svnet_pool_workspace_bytes(B, N, Ca, 1)
-        ws = _zeros((nb,), torch.uint8, dev)
-        arg_a = torch.empty((B, Ca), dtype=torch.int32, device=dev)
-        call("svnet_bn_pool_fwd_f32", _p(y2), _p(mean1), _p(invstd1), _p(g1), _p(b1), B, N, Ca, act, slope, _p(out), _p(out[:, Ct:]),
-             2 * Ct, _p(arg_a), _p(ws), nb, 1, _stream())
+                 _p(max_b), _p(mean_b), out.stride(0), _p(arg_b), _p(wsb), nbw, 1, _stream())
+        arg_a = _bn_half_fwd(y2, mean1, invstd1, g1, b1, B, N, act, slope, max_a, mean_a)
         main.wait_stream(side)
         ctx.save_for_backward(y2, mean1, invstd1, g1, b1, arg_a, arg_b, v3, mean2, invstd2, g2, b2, gate2, w_eff, Wzc, sczf)
-        if TAP is not None:
-            TAP["pools"].append(torch.cat([arg_a, arg_b], dim=1))
-            if "acts" in TAP and act in (1, 2):
-                TAP["acts"].append((g1.data_ptr(), ((y2 - mean1) * invstd1 * g1 + b1) > 0))
+        _tap_pools(arg_a, arg_b)
+        _tap_bn_half(y2, mean1, invstd1, g1, b1, act)
         ctx.meta = (B, N, Ca, C, act, slope, bool(training), v_lin.shape, None if gate is None else gate.shape,
                     None if scz is None else scz.shape)
         ctx.v_on_side = bool(v_on_side)
@@ -1582,11 +1635,10 @@ class GlobalMaxMeanPoolBNV(torch.autograd.Function):
         y2, mean1, invstd1, g1, b1, arg_a, arg_b, v3, mean2, invstd2, g2, b2, gate2, w_eff, Wzc, sczf = ctx.saved_tensors
         B, N, Ca, C, act, slope, training, vshape, gshape, scshape = ctx.meta
         Cb, P = 3 * C, B * N
-        Ct = Ca + Cb
         g = _f32c(g)
+        gmax_a, gmean_a, gmax_b, gmean_b = _maxmean_slices(g, Ca, Cb)
         dev = g.device
         F = torch.float32
-        dy = torch.empty((B, N, Ca), dtype=F, device=dev) if ctx.needs_input_grad[0] else None
         red1, red2, dgate, gxb = _zeros_pool(dev, ((_sliced_len(2 * Ca),), F), ((_sliced_len(2 * C),), F), ((B, C), F), ((_sliced_len(3 * C),), F))
         main, side = torch.cuda.current_stream(dev), _side_stream(dev)
         # dv belongs to the pool of the stream that consumes it: linear2's backward, which autograd runs where linear2's forward ran.
@@ -1603,11 +1655,11 @@ class GlobalMaxMeanPoolBNV(torch.autograd.Function):
                 dv = torch.empty((P, 3, C), dtype=F, device=dev)
             recompute = bool(config.FUSE_VTAIL_APPLY)
             g5 = None if recompute else torch.empty((P, 3, C), dtype=F, device=dev)
-            call("svnet_vtail_bwd_f32", _p(v3), _p(mean2), _p(invstd2), _p(g2), _p(b2), _p(gate2), _p(w_eff), _p(g[:, Ca:]), _p(g[:, Ct + Ca:]),
-                 2 * Ct, _p(arg_b), B, N, C, _p(red2), _p(dgate) if gate2 is not None else None, _p(gxb), _p(g5), _stream())
+            call("svnet_vtail_bwd_f32", _p(v3), _p(mean2), _p(invstd2), _p(g2), _p(b2), _p(gate2), _p(w_eff), _p(gmax_b), _p(gmean_b),
+                 g.stride(0), _p(arg_b), B, N, C, _p(red2), _p(dgate) if gate2 is not None else None, _p(gxb), _p(g5), _stream())
             if recompute:   # the apply pass recomputes dL/d(VectorBN's output) from the product instead of reading a stored copy (134 MB less)
-                call("svnet_vtail_bwd_apply_f32", _p(v3), _p(mean2), _p(invstd2), _p(g2), _p(b2), _p(gate2), _p(w_eff), _p(g[:, Ca:]),
-                     _p(g[:, Ct + Ca:]), 2 * Ct, _p(arg_b), B, N, C, _p(red2), int(training), _p(dv), _stream())
+                call("svnet_vtail_bwd_apply_f32", _p(v3), _p(mean2), _p(invstd2), _p(g2), _p(b2), _p(gate2), _p(w_eff), _p(gmax_b),
+                     _p(gmean_b), g.stride(0), _p(arg_b), B, N, C, _p(red2), int(training), _p(dv), _stream())
             else:
                 call("svnet_vbn_bwd_apply_f32", _p(g5), _p(v3), _p(mean2), _p(invstd2), _p(g2), _p(b2), _p(gate2), _p(red2), N, P, C,
                      int(training), _p(dv), _stream())
@@ -1617,8 +1669,7 @@ class GlobalMaxMeanPoolBNV(torch.autograd.Function):
             else:
                 call("svnet_slices_sum_f32", _p(gxb), 3 * C, _stream())
                 dWz, dscz = gxb[:3 * C].view(3, C), None
-        call("svnet_bn_pool_bwd_f32", _p(g), _p(g[:, Ct:]), 2 * Ct, _p(arg_a), _p(y2), _p(mean1), _p(invstd1), _p(g1), _p(b1), B, N, Ca,
-             act, slope, int(training), _p(red1), _p(dy), _stream())
+        dy, _ = _bn_half_bwd(gmax_a, gmean_a, arg_a, y2, mean1, invstd1, g1, b1, N, act, slope, training, ctx.needs_input_grad[0], red=red1)
         # (main waits for the WHOLE vector half here.  Waiting for the gate's gradient only - all the main stream goes on to read - measured
         #  4.219 against 4.227 ms and a captured step's first replay then held a stale weight gradient of linear2: not kept)
         main.wait_stream(side)

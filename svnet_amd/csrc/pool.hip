@@ -8,6 +8,7 @@
 // 20 480 edge rows) are split over workgroups and combined with float atomics.
 #include "common.h"
 #include "gate_mlp.h"
+#include "split_reduce.h"
 
 namespace {
 
@@ -37,95 +38,29 @@ __global__ __launch_bounds__(256) void pool_fwd_kernel(const float* __restrict__
     }
 }
 
-// mean with a long reduced axis: grid (chunks, outer); every chunk writes its partial sums to part[chunk][outer*inner] and
-// pool_mean_finish_kernel adds the chunks in a fixed order (no float atomics: the result is reproducible bit for bit, which
-// matters because these means feed sign() one layer later)
+// ---- the long reduced axis, split over workgroups (split_reduce.h): grid (chunks, outer), one body (split_fwd_columns), four kernels.
+// mean: every chunk writes its partial sums to part[chunk][outer*inner] and pool_mean_finish_kernel adds the chunks in a fixed order
 __global__ __launch_bounds__(1024) void pool_mean_split_kernel(const float* __restrict__ x, int64_t R, int64_t inner,
                                                               int64_t rows_per_chunk, float* __restrict__ part, int64_t total) {
-    const int64_t o = blockIdx.y;
-    const int64_t r0 = (int64_t)blockIdx.x * rows_per_chunk, r1 = min(R, r0 + rows_per_chunk);
-    for (int64_t i = threadIdx.x; i < inner; i += blockDim.x) {
-        const float* p = x + o * R * inner + i;
-        float s = 0.f;
-        int64_t r = r0;
-        for (; r + 7 < r1; r += 8) {          // eight rows' loads in flight per thread
-            float t[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) t[u] = p[(r + u) * inner];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) s += t[u];
-        }
-        for (; r < r1; ++r) s += p[r * inner];
-        part[(int64_t)blockIdx.x * total + o * inner + i] = s;
-    }
+    split_fwd_columns<false, true, false>(x, R, inner, rows_per_chunk, nullptr, part, total, MapIdentity{});
 }
 __global__ __launch_bounds__(256) void pool_mean_finish_kernel(const float* __restrict__ part, int64_t chunks, int64_t total, float invR,
                                                                float* __restrict__ out, int64_t inner, int64_t out_ld) {
-    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
-        float s = 0.f;
-        for (int64_t c = 0; c < chunks; ++c) s += part[c * total + e];
-        out[(e / inner) * out_ld + e % inner] = s * invR;
-    }
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x)
+        out[(e / inner) * out_ld + e % inner] = ordered_chunk_sum(part, chunks, total, e) * invR;
 }
 
-// max with a long reduced axis: grid (chunks, outer); each (o,i) keeps one packed 64-bit key
-//   key = (order-preserving bits of the value) << 32 | (0xFFFFFFFF - r)      -> atomicMax = largest value, first index
-// in `keys` (pre-filled with 0 by the caller's memset); a second tiny kernel unpacks value and arg-max.
+// max: each (o,i) keeps one packed 64-bit key (pack_key, wave.h) in `keys` (pre-filled with 0 by the caller's memset); a second tiny
+// kernel unpacks value and arg-max.
 __global__ __launch_bounds__(1024) void pool_max_split_kernel(const float* __restrict__ x, int64_t R, int64_t inner,
                                                              int64_t rows_per_chunk, unsigned long long* __restrict__ keys) {
-    const int64_t o = blockIdx.y;
-    const int64_t r0 = (int64_t)blockIdx.x * rows_per_chunk, r1 = min(R, r0 + rows_per_chunk);
-    for (int64_t i = threadIdx.x; i < inner; i += blockDim.x) {
-        const float* p = x + o * R * inner + i;
-        float best = p[r0 * inner];
-        int64_t bi = r0;
-        int64_t r = r0 + 1;
-        for (; r + 7 < r1; r += 8) {          // eight rows' loads in flight per thread; strict '>' keeps the first index
-            float t[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) t[u] = p[(r + u) * inner];
-#pragma unroll
-            for (int u = 0; u < 8; ++u)
-                if (t[u] > best) { best = t[u]; bi = r + u; }
-        }
-        for (; r < r1; ++r) {
-            const float v = p[r * inner];
-            if (v > best) { best = v; bi = r; }
-        }
-        atomicMax(&keys[o * inner + i], pack_key(best, bi));
-    }
+    split_fwd_columns<true, false, false>(x, R, inner, rows_per_chunk, keys, nullptr, 0, MapIdentity{});
 }
-// max AND mean of a long reduced axis in ONE pass over x (the classifiers' global pooling reads its [B,N,C] features once instead
-// of twice): the max part as pool_max_split_kernel (packed keys, atomicMax), the mean part as pool_mean_split_kernel (ordered
-// partial sums).
+// max AND mean in ONE pass over x (the classifiers' global pooling reads its [B,N,C] features once instead of twice)
 __global__ __launch_bounds__(1024) void pool_maxmean_split_kernel(const float* __restrict__ x, int64_t R, int64_t inner,
                                                                  int64_t rows_per_chunk, unsigned long long* __restrict__ keys,
                                                                  float* __restrict__ part, int64_t total) {
-    const int64_t o = blockIdx.y;
-    const int64_t r0 = (int64_t)blockIdx.x * rows_per_chunk, r1 = min(R, r0 + rows_per_chunk);
-    for (int64_t i = threadIdx.x; i < inner; i += blockDim.x) {
-        const float* p = x + o * R * inner + i;
-        float best = p[r0 * inner], s = best;
-        int64_t bi = r0;
-        int64_t r = r0 + 1;
-        for (; r + 7 < r1; r += 8) {          // eight rows' loads in flight per thread; strict '>' keeps the first index
-            float t[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) t[u] = p[(r + u) * inner];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                s += t[u];
-                if (t[u] > best) { best = t[u]; bi = r + u; }
-            }
-        }
-        for (; r < r1; ++r) {
-            const float v = p[r * inner];
-            s += v;
-            if (v > best) { best = v; bi = r; }
-        }
-        atomicMax(&keys[o * inner + i], pack_key(best, bi));
-        part[(int64_t)blockIdx.x * total + o * inner + i] = s;
-    }
+    split_fwd_columns<true, true, false>(x, R, inner, rows_per_chunk, keys, part, total, MapIdentity{});
 }
 // ---- BatchNorm (+ activation) and [max | mean] over the points in ONE pass over the pre-BN tensor y [outer, R, inner] (conv5 of the
 // classifier, whose activated output is only ever pooled, sv_dgcnn_cls.py:69-74): the activated tensor is never written, and
@@ -136,45 +71,7 @@ __global__ __launch_bounds__(1024) void bn_pool_split_kernel(const float* __rest
                                                             const float* __restrict__ beta, int act, float slope, int64_t R,
                                                             int64_t inner, int64_t rows_per_chunk, unsigned long long* __restrict__ keys,
                                                             float* __restrict__ part, int64_t total) {
-    const int64_t o = blockIdx.y;
-    const int64_t r0 = (int64_t)blockIdx.x * rows_per_chunk, r1 = min(R, r0 + rows_per_chunk);
-    for (int64_t i = threadIdx.x; i < inner; i += blockDim.x) {
-        const float mu = mean[i], is = invstd[i], ga = gamma[i], be = beta[i];
-        const float* p = x + o * R * inner + i;
-        // (the same arithmetic, in the same order, as bn_act_fwd_kernel: the pooled values equal pooling its output)
-        float best = act_apply((p[r0 * inner] - mu) * is * ga + be, act, slope), s = best;
-        int64_t bi = r0;
-        int64_t r = r0 + 1;
-        for (; r + 15 < r1; r += 16) {
-            float t[16];
-#pragma unroll
-            for (int u = 0; u < 16; ++u) t[u] = p[(r + u) * inner];
-#pragma unroll
-            for (int u = 0; u < 16; ++u) {
-                const float z = act_apply((t[u] - mu) * is * ga + be, act, slope);
-                s += z;
-                if (z > best) { best = z; bi = r + u; }
-            }
-        }
-        for (; r + 7 < r1; r += 8) {
-            float t[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) t[u] = p[(r + u) * inner];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const float z = act_apply((t[u] - mu) * is * ga + be, act, slope);
-                s += z;
-                if (z > best) { best = z; bi = r + u; }
-            }
-        }
-        for (; r < r1; ++r) {
-            const float z = act_apply((p[r * inner] - mu) * is * ga + be, act, slope);
-            s += z;
-            if (z > best) { best = z; bi = r; }
-        }
-        atomicMax(&keys[o * inner + i], pack_key(best, bi));
-        part[(int64_t)blockIdx.x * total + o * inner + i] = s;
-    }
+    split_fwd_columns<true, true, true>(x, R, inner, rows_per_chunk, keys, part, total, MapBnAct{mean, invstd, gamma, beta, act, slope});
 }
 // red[0:C] += sum g', red[C:2C] += sum g' xhat with g' = g * act'(z), g = (r == argmax ? gmax : 0) + gmean / R
 __global__ __launch_bounds__(1024) void bn_pool_bwd_reduce_kernel(const float* __restrict__ gmax, const float* __restrict__ gmean, int64_t g_ld,
@@ -192,37 +89,12 @@ __global__ __launch_bounds__(1024) void bn_pool_bwd_reduce_kernel(const float* _
         const int am = argmax[o * inner + i];
         const float* p = x + o * R * inner + i;
         double a0 = 0.0, a1 = 0.0;
-        int64_t r = r0;
-        for (; r + 15 < r1; r += 16) {
-            float t[16];
-#pragma unroll
-            for (int u = 0; u < 16; ++u) t[u] = p[(r + u) * inner];
-#pragma unroll
-            for (int u = 0; u < 16; ++u) {
-                const float xh = (t[u] - mu) * is;
-                const float gp = (gm + (am == (int32_t)(r + u) ? gx : 0.f)) * act_grad(xh * ga + be, act, slope);
-                a0 += (double)gp;
-                a1 += (double)gp * (double)xh;
-            }
-        }
-        for (; r + 7 < r1; r += 8) {
-            float t[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) t[u] = p[(r + u) * inner];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const float xh = (t[u] - mu) * is;
-                const float gp = (gm + (am == (int32_t)(r + u) ? gx : 0.f)) * act_grad(xh * ga + be, act, slope);
-                a0 += (double)gp;
-                a1 += (double)gp * (double)xh;
-            }
-        }
-        for (; r < r1; ++r) {
-            const float xh = (p[r * inner] - mu) * is;
+        row_ladder<16, 8, 1>(r0, r1, [&](int64_t r) { return p[r * inner]; }, [&](int64_t r, float t) {
+            const float xh = (t - mu) * is;
             const float gp = (gm + (am == (int32_t)r ? gx : 0.f)) * act_grad(xh * ga + be, act, slope);
             a0 += (double)gp;
             a1 += (double)gp * (double)xh;
-        }
+        });
         float* sl = svnet_slice_ptr(red, 2 * (int)inner);   // (chunks x outer adders per column: a few hundred - spread over slices)
         svnet_slice_add(&sl[i], (float)a0);
         svnet_slice_add(&sl[inner + i], (float)a1);
@@ -248,35 +120,22 @@ __global__ __launch_bounds__(1024) void bn_pool_bwd_apply_kernel(const float* __
         const float* p = x + o * R * inner + i;
         float* d = dx + o * R * inner + i;
         // (sixteen rows requested before the first is used: with four, a CU had 32 KB in flight and the pass ran at 2.3 TB/s)
-        int64_t r = r0;
-        for (; r + 15 < r1; r += 16) {
-            float t[16];
-#pragma unroll
-            for (int u = 0; u < 16; ++u) t[u] = p[(r + u) * inner];
-#pragma unroll
-            for (int u = 0; u < 16; ++u) {
-                const float xh = (t[u] - mu) * is;
-                float gp = (gm + (am == (int32_t)(r + u) ? gx : 0.f)) * act_grad(xh * ga + be, act, slope);
-                if (train_stats) gp -= (q0 + xh * q1) * invM;
-                d[(r + u) * inner] = gp * ga * is;
-            }
-        }
-        for (; r < r1; ++r) {
-            const float xh = (p[r * inner] - mu) * is;
+        row_ladder<16, 1>(r0, r1, [&](int64_t r) { return p[r * inner]; }, [&](int64_t r, float t) {
+            const float xh = (t - mu) * is;
             float gp = (gm + (am == (int32_t)r ? gx : 0.f)) * act_grad(xh * ga + be, act, slope);
             if (train_stats) gp -= (q0 + xh * q1) * invM;
             d[r * inner] = gp * ga * is;
-        }
+        });
     }
 }
 __global__ __launch_bounds__(256) void pool_max_unpack_kernel(const unsigned long long* __restrict__ keys, int64_t total,
                                                               float* __restrict__ out, int32_t* __restrict__ argmax, int64_t inner, int64_t out_ld) {
     for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
-        const unsigned long long kk = keys[e];
-        uint32_t u = (uint32_t)(kk >> 32);
-        u = (u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u;
-        out[(e / inner) * out_ld + e % inner] = __uint_as_float(u);
-        if (argmax) argmax[e] = (int32_t)(0xFFFFFFFFu - (uint32_t)(kk & 0xFFFFFFFFull));
+        float v;
+        int32_t r;
+        unpack_key(keys[e], v, r);
+        out[(e / inner) * out_ld + e % inner] = v;
+        if (argmax) argmax[e] = r;
     }
 }
 
@@ -286,26 +145,15 @@ __global__ __launch_bounds__(256) void pool_maxmean_finish_kernel(const unsigned
                                                                   float* __restrict__ out_mean, int32_t* __restrict__ argmax, int64_t inner,
                                                                   int64_t out_ld) {
     for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
-        const unsigned long long kk = keys[e];
-        uint32_t u = (uint32_t)(kk >> 32);
-        u = (u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u;
-        // (the chunks' partial sums in order - bit-reproducible - with eight loads in flight: one dependent L2 round trip per chunk made
-        //  this 16 K-element kernel 8 - 10 us long; 32-bit division: total < 2^20)
-        float s = 0.f;
-        int64_t c = 0;
-        for (; c + 7 < chunks; c += 8) {
-            float t[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) t[u] = part[(c + u) * total + e];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) s += t[u];
-        }
-        for (; c < chunks; ++c) s += part[c * total + e];
-        const uint32_t o32 = (uint32_t)e / (uint32_t)inner;
+        float v;
+        int32_t r;
+        unpack_key(keys[e], v, r);
+        const float s = ordered_chunk_sum(part, chunks, total, e);
+        const uint32_t o32 = (uint32_t)e / (uint32_t)inner;      // (32-bit division: total < 2^20)
         const int64_t o = o32, i = e - o * inner;
-        out_max[o * out_ld + i] = __uint_as_float(u);
+        out_max[o * out_ld + i] = v;
         out_mean[o * out_ld + i] = s * invR;
-        argmax[e] = (int32_t)(0xFFFFFFFFu - (uint32_t)(kk & 0xFFFFFFFFull));
+        argmax[e] = r;
     }
 }
 
@@ -335,15 +183,7 @@ __global__ __launch_bounds__(1024) void pool_mean_bwd_add_kernel(const float* __
         const float gm = gmean[o * inner + i] * invR;
         const float* a = add + (o * R) * add_ld + i;
         float* d = dx + (o * R) * inner + i;
-        int64_t r = r0;
-        for (; r + 7 < r1; r += 8) {
-            float t[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) t[u] = a[(r + u) * add_ld];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) d[(r + u) * inner] = t[u] + gm;
-        }
-        for (; r < r1; ++r) d[r * inner] = a[r * add_ld] + gm;
+        row_ladder<8, 1>(r0, r1, [&](int64_t r) { return a[r * add_ld]; }, [&](int64_t r, float t) { d[r * inner] = t + gm; });
     }
 }
 
@@ -410,20 +250,20 @@ static unsigned pool_col_block(int64_t inner) {
     const int64_t b = (inner + 63) / 64 * 64;
     return (unsigned)(b > 1024 ? 1024 : (b < 64 ? 64 : b));
 }
-static int64_t pool_split_chunks(int64_t outer, int64_t R) {
-    int64_t chunks = svnet_cdiv(256 * 8, outer);
-    if (chunks > svnet_cdiv(R, 32)) chunks = svnet_cdiv(R, 32);
-    return chunks < 1 ? 1 : chunks;
+static SplitPlan pool_fwd_plan(int64_t outer, int64_t R) { return split_plan(outer, R, SPLIT_FWD_TARGET, SPLIT_FWD_LEAST_ROWS); }
+
+int split_maxmean_finish(const unsigned long long* keys, const float* part, int64_t chunks, int64_t total, int64_t R, float* out_max,
+                         float* out_mean, int32_t* argmax, int64_t inner, int64_t out_ld, hipStream_t st) {
+    hipLaunchKernelGGL(pool_maxmean_finish_kernel, dim3(svnet_grid(total, 256)), dim3(256), 0, st, keys, part, chunks, total, 1.f / (float)R,
+                       out_max, out_mean, argmax, inner, out_ld);
+    SVNET_CHECK_LAUNCH("pool_maxmean_finish_kernel");
+    return SVNET_OK;
 }
 
-/* bytes of workspace that let a long reduction (R >= 256, few outputs) be split over workgroups; 0 = no split path */
+/* bytes of workspace that let a long reduction (split_eligible: R >= 256, few outputs) be split over workgroups; 0 = no split path */
 extern "C" size_t svnet_pool_workspace_bytes(int64_t outer, int64_t R, int64_t inner, int mode) {
-    const int64_t total = outer * inner;
-    if (R < 256 || total >= (1 << 20) || outer > 65535 || outer <= 0) return 0;
-    if (mode == 0) return (size_t)total * 8;
-    int64_t chunks = pool_split_chunks(outer, R);
-    chunks = svnet_cdiv(R, svnet_cdiv(R, chunks));
-    return (size_t)(chunks * total) * sizeof(float);
+    if (!split_eligible(outer, R, inner)) return 0;
+    return split_workspace_bytes(outer * inner, pool_fwd_plan(outer, R).chunks, mode == 0, mode != 0);
 }
 
 extern "C" int svnet_pool_fwd_f32(const float* x, int64_t outer, int64_t R, int64_t inner, int mode, float* out, int64_t out_ld,
@@ -433,34 +273,28 @@ extern "C" int svnet_pool_fwd_f32(const float* x, int64_t outer, int64_t R, int6
     if (outer == 0) return SVNET_OK;
     hipStream_t st = (hipStream_t)stream;
     const int64_t total = outer * inner;
-    if (mode == 1 && R >= 256 && total < (1 << 20) && outer <= 65535) {
-        int64_t chunks = pool_split_chunks(outer, R);
-        const int64_t rpc = svnet_cdiv(R, chunks);
-        chunks = svnet_cdiv(R, rpc);
-        if (workspace && workspace_bytes >= (size_t)(chunks * total) * sizeof(float)) {
-            float* part = (float*)workspace;
-            hipLaunchKernelGGL(pool_mean_split_kernel, dim3((unsigned)chunks, (unsigned)outer), dim3(pool_col_block(inner)), 0, st, x, R, inner, rpc, part,
-                               total);
-            SVNET_CHECK_LAUNCH("pool_mean_split_kernel");
-            hipLaunchKernelGGL(pool_mean_finish_kernel, dim3(svnet_grid(total, 256)), dim3(256), 0, st, part, chunks, total,
-                               1.f / (float)R, out, inner, out_ld);
-            SVNET_CHECK_LAUNCH("pool_mean_finish_kernel");
+    if (split_eligible(outer, R, inner)) {
+        // long reduction with few outputs (point pooling over N): split the rows over workgroups
+        const SplitPlan pl = pool_fwd_plan(outer, R);
+        const dim3 grid((unsigned)pl.chunks, (unsigned)outer), block(pool_col_block(inner));
+        if (workspace && workspace_bytes >= split_workspace_bytes(total, pl.chunks, mode == 0, mode == 1)) {
+            const SplitWorkspace ws = split_workspace_carve(workspace, total, mode == 0, mode == 1);
+            if (mode == 1) {
+                hipLaunchKernelGGL(pool_mean_split_kernel, grid, block, 0, st, x, R, inner, pl.rows, ws.part, total);
+                SVNET_CHECK_LAUNCH("pool_mean_split_kernel");
+                hipLaunchKernelGGL(pool_mean_finish_kernel, dim3(svnet_grid(total, 256)), dim3(256), 0, st, ws.part, pl.chunks, total,
+                                   1.f / (float)R, out, inner, out_ld);
+                SVNET_CHECK_LAUNCH("pool_mean_finish_kernel");
+                return SVNET_OK;
+            }
+            hipError_t e = hipMemsetAsync(ws.keys, 0, sizeof(unsigned long long) * total, st);
+            SVNET_REQUIRE(e == hipSuccess, SVNET_E_LAUNCH, "svnet_pool_fwd_f32: memset failed");
+            hipLaunchKernelGGL(pool_max_split_kernel, grid, block, 0, st, x, R, inner, pl.rows, ws.keys);
+            SVNET_CHECK_LAUNCH("pool_max_split_kernel");
+            hipLaunchKernelGGL(pool_max_unpack_kernel, dim3(svnet_grid(total, 256)), dim3(256), 0, st, ws.keys, total, out, argmax, inner, out_ld);
+            SVNET_CHECK_LAUNCH("pool_max_unpack_kernel");
             return SVNET_OK;
         }
-    }
-    if (mode == 0 && R >= 256 && total < (1 << 20) && workspace && workspace_bytes >= (size_t)total * 8 && outer <= 65535) {
-        // long max-reduction with few outputs (point pooling over N): split the rows over workgroups
-        unsigned long long* keys = (unsigned long long*)workspace;
-        hipError_t e = hipMemsetAsync(keys, 0, sizeof(unsigned long long) * total, st);
-        SVNET_REQUIRE(e == hipSuccess, SVNET_E_LAUNCH, "svnet_pool_fwd_f32: memset failed");
-        int64_t chunks = pool_split_chunks(outer, R);
-        const int64_t rpc = svnet_cdiv(R, chunks);
-        chunks = svnet_cdiv(R, rpc);
-        hipLaunchKernelGGL(pool_max_split_kernel, dim3((unsigned)chunks, (unsigned)outer), dim3(pool_col_block(inner)), 0, st, x, R, inner, rpc, keys);
-        SVNET_CHECK_LAUNCH("pool_max_split_kernel");
-        hipLaunchKernelGGL(pool_max_unpack_kernel, dim3(svnet_grid(total, 256)), dim3(256), 0, st, keys, total, out, argmax, inner, out_ld);
-        SVNET_CHECK_LAUNCH("pool_max_unpack_kernel");
-        return SVNET_OK;
     }
     hipLaunchKernelGGL(pool_fwd_kernel, dim3(svnet_grid(total, 256, 256 * 32)), dim3(256), 0, st, x, outer, R, inner, mode, out, out_ld, argmax);
     SVNET_CHECK_LAUNCH("pool_fwd_kernel");
@@ -471,27 +305,21 @@ extern "C" int svnet_pool_fwd_f32(const float* x, int64_t outer, int64_t R, int6
  * workspace: svnet_pool_workspace_bytes(.., 0) + svnet_pool_workspace_bytes(.., 1) bytes, the key part first.               */
 extern "C" int svnet_pool_maxmean_fwd_f32(const float* x, int64_t outer, int64_t R, int64_t inner, float* out_max, float* out_mean,
                                           int64_t out_ld, int32_t* argmax, void* workspace, size_t workspace_bytes, void* stream) {
-    SVNET_REQUIRE(x && out_max && out_mean && argmax && outer > 0 && R >= 256 && inner > 0 && out_ld >= inner, SVNET_E_ARG,
+    SVNET_REQUIRE(x && out_max && out_mean && argmax && outer > 0 && R >= SPLIT_MIN_ROWS && inner > 0 && out_ld >= inner, SVNET_E_ARG,
                   "svnet_pool_maxmean_fwd_f32: bad arguments (R >= 256)");
+    SVNET_REQUIRE(split_eligible(outer, R, inner), SVNET_E_UNSUPPORTED, "svnet_pool_maxmean_fwd_f32: too many outputs");
     const int64_t total = outer * inner;
-    SVNET_REQUIRE(total < (1 << 20) && outer <= 65535, SVNET_E_UNSUPPORTED, "svnet_pool_maxmean_fwd_f32: too many outputs");
-    int64_t chunks = pool_split_chunks(outer, R);
-    const int64_t rpc = svnet_cdiv(R, chunks);
-    chunks = svnet_cdiv(R, rpc);
-    const size_t key_bytes = (size_t)total * 8;
-    SVNET_REQUIRE(workspace && workspace_bytes >= key_bytes + (size_t)(chunks * total) * sizeof(float), SVNET_E_ARG,
+    const SplitPlan pl = pool_fwd_plan(outer, R);
+    SVNET_REQUIRE(workspace && workspace_bytes >= split_workspace_bytes(total, pl.chunks, true, true), SVNET_E_ARG,
                   "svnet_pool_maxmean_fwd_f32: workspace too small");
     hipStream_t st = (hipStream_t)stream;
-    unsigned long long* keys = (unsigned long long*)workspace;
-    float* part = (float*)((char*)workspace + key_bytes);
-    hipError_t e = hipMemsetAsync(keys, 0, key_bytes, st);
+    const SplitWorkspace ws = split_workspace_carve(workspace, total, true, true);
+    hipError_t e = hipMemsetAsync(ws.keys, 0, split_workspace_bytes(total, 0, true, false), st);
     SVNET_REQUIRE(e == hipSuccess, SVNET_E_LAUNCH, "svnet_pool_maxmean_fwd_f32: memset failed");
-    hipLaunchKernelGGL(pool_maxmean_split_kernel, dim3((unsigned)chunks, (unsigned)outer), dim3(pool_col_block(inner)), 0, st, x, R, inner, rpc, keys, part, total);
+    hipLaunchKernelGGL(pool_maxmean_split_kernel, dim3((unsigned)pl.chunks, (unsigned)outer), dim3(pool_col_block(inner)), 0, st, x, R, inner, pl.rows,
+                       ws.keys, ws.part, total);
     SVNET_CHECK_LAUNCH("pool_maxmean_split_kernel");
-    hipLaunchKernelGGL(pool_maxmean_finish_kernel, dim3(svnet_grid(total, 256)), dim3(256), 0, st, keys, part, chunks, total, 1.f / (float)R,
-                       out_max, out_mean, argmax, inner, out_ld);
-    SVNET_CHECK_LAUNCH("pool_maxmean_finish_kernel");
-    return SVNET_OK;
+    return split_maxmean_finish(ws.keys, ws.part, pl.chunks, total, R, out_max, out_mean, argmax, inner, out_ld, st);
 }
 
 /* BatchNorm (+ activation) of y [outer*R, inner] with the given statistics, pooled [max | mean] over R in the same pass (the activated
@@ -500,30 +328,23 @@ extern "C" int svnet_bn_pool_fwd_f32(const float* y, const float* mean, const fl
                                      int64_t outer, int64_t R, int64_t inner, int act, float slope, float* out_max, float* out_mean,
                                      int64_t out_ld, int32_t* argmax, void* workspace, size_t workspace_bytes, int workspace_zeroed,
                                      void* stream) {
-    SVNET_REQUIRE(y && mean && invstd && gamma && beta && out_max && out_mean && argmax && outer > 0 && R >= 256 && inner > 0 &&
+    SVNET_REQUIRE(y && mean && invstd && gamma && beta && out_max && out_mean && argmax && outer > 0 && R >= SPLIT_MIN_ROWS && inner > 0 &&
                       out_ld >= inner, SVNET_E_ARG, "svnet_bn_pool_fwd_f32: bad arguments (R >= 256)");
+    SVNET_REQUIRE(split_eligible(outer, R, inner), SVNET_E_UNSUPPORTED, "svnet_bn_pool_fwd_f32: too many outputs");
     const int64_t total = outer * inner;
-    SVNET_REQUIRE(total < (1 << 20) && outer <= 65535, SVNET_E_UNSUPPORTED, "svnet_bn_pool_fwd_f32: too many outputs");
-    int64_t chunks = pool_split_chunks(outer, R);
-    const int64_t rpc = svnet_cdiv(R, chunks);
-    chunks = svnet_cdiv(R, rpc);
-    const size_t key_bytes = (size_t)total * 8;
-    SVNET_REQUIRE(workspace && workspace_bytes >= key_bytes + (size_t)(chunks * total) * sizeof(float), SVNET_E_ARG,
+    const SplitPlan pl = pool_fwd_plan(outer, R);
+    SVNET_REQUIRE(workspace && workspace_bytes >= split_workspace_bytes(total, pl.chunks, true, true), SVNET_E_ARG,
                   "svnet_bn_pool_fwd_f32: workspace too small");
     hipStream_t st = (hipStream_t)stream;
-    unsigned long long* keys = (unsigned long long*)workspace;
-    float* part = (float*)((char*)workspace + key_bytes);
+    const SplitWorkspace ws = split_workspace_carve(workspace, total, true, true);
     if (!workspace_zeroed) {      // (a caller that hands over zero-filled memory - one fill per step for everything - saves this launch)
-        hipError_t e = hipMemsetAsync(keys, 0, key_bytes, st);
+        hipError_t e = hipMemsetAsync(ws.keys, 0, split_workspace_bytes(total, 0, true, false), st);
         SVNET_REQUIRE(e == hipSuccess, SVNET_E_LAUNCH, "svnet_bn_pool_fwd_f32: memset failed");
     }
-    hipLaunchKernelGGL(bn_pool_split_kernel, dim3((unsigned)chunks, (unsigned)outer), dim3(pool_col_block(inner)), 0, st, y, mean, invstd, gamma, beta, act,
-                       slope, R, inner, rpc, keys, part, total);
+    hipLaunchKernelGGL(bn_pool_split_kernel, dim3((unsigned)pl.chunks, (unsigned)outer), dim3(pool_col_block(inner)), 0, st, y, mean, invstd, gamma, beta, act,
+                       slope, R, inner, pl.rows, ws.keys, ws.part, total);
     SVNET_CHECK_LAUNCH("bn_pool_split_kernel");
-    hipLaunchKernelGGL(pool_maxmean_finish_kernel, dim3(svnet_grid(total, 256)), dim3(256), 0, st, keys, part, chunks, total, 1.f / (float)R,
-                       out_max, out_mean, argmax, inner, out_ld);
-    SVNET_CHECK_LAUNCH("pool_maxmean_finish_kernel");
-    return SVNET_OK;
+    return split_maxmean_finish(ws.keys, ws.part, pl.chunks, total, R, out_max, out_mean, argmax, inner, out_ld, st);
 }
 
 /* Backward of svnet_bn_pool_fwd_f32 from the POOLED gradients (gmax / gmean rows of stride g_ld): red [2*inner] (caller zero-fills)
@@ -536,22 +357,14 @@ extern "C" int svnet_bn_pool_bwd_f32(const float* gmax, const float* gmean, int6
     hipStream_t st = (hipStream_t)stream;
     // reduce: ~512 workgroups in all (every one ends in an atomic per column onto the same 2*inner addresses: thousands of adders
     // per cache line serialise at the memory side); apply: ~2048 (it streams two tensors and has nothing to combine)
-    auto split = [&](int64_t target, int64_t& chunks, int64_t& rpc) {
-        chunks = svnet_cdiv(target, outer);
-        if (chunks > svnet_cdiv(R, 8)) chunks = svnet_cdiv(R, 8);
-        if (chunks < 1) chunks = 1;
-        rpc = svnet_cdiv(R, chunks);
-        chunks = svnet_cdiv(R, rpc);
-    };
-    int64_t chunks, rpc;
-    split(512, chunks, rpc);
-    hipLaunchKernelGGL(bn_pool_bwd_reduce_kernel, dim3((unsigned)chunks, (unsigned)outer), dim3(pool_col_block(inner)), 0, st, gmax, gmean, g_ld, argmax, y, mean,
-                       invstd, gamma, beta, act, slope, R, inner, rpc, red);
+    SplitPlan pl = split_plan(outer, R, 512, 8);
+    hipLaunchKernelGGL(bn_pool_bwd_reduce_kernel, dim3((unsigned)pl.chunks, (unsigned)outer), dim3(pool_col_block(inner)), 0, st, gmax, gmean, g_ld, argmax, y, mean,
+                       invstd, gamma, beta, act, slope, R, inner, pl.rows, red);
     SVNET_CHECK_LAUNCH("bn_pool_bwd_reduce_kernel");
     if (dy) {
-        split(2048, chunks, rpc);
-        hipLaunchKernelGGL(bn_pool_bwd_apply_kernel, dim3((unsigned)chunks, (unsigned)outer), dim3(pool_col_block(inner)), 0, st, gmax, gmean, g_ld, argmax, y, mean,
-                           invstd, gamma, beta, red, act, slope, train_stats, outer, R, inner, rpc, dy);
+        pl = split_plan(outer, R, 2048, 8);
+        hipLaunchKernelGGL(bn_pool_bwd_apply_kernel, dim3((unsigned)pl.chunks, (unsigned)outer), dim3(pool_col_block(inner)), 0, st, gmax, gmean, g_ld, argmax, y, mean,
+                           invstd, gamma, beta, red, act, slope, train_stats, outer, R, inner, pl.rows, dy);
         SVNET_CHECK_LAUNCH("bn_pool_bwd_apply_kernel");
     } else {
         return svnet_slices_sum_f32(red, 2 * inner, stream);          // (no apply pass: the totals by a kernel of their own)
@@ -566,12 +379,9 @@ extern "C" int svnet_pool_bwd_f32(const float* g, const int32_t* argmax, int64_t
     if (outer <= 65535 && inner >= 128) {
         // rows streamed by a thread per column (pool_maxmean_bwd_kernel with one of its two parts): the flat kernel below spends three
         // 64-bit divisions on every element
-        int64_t chunks = svnet_cdiv(256 * 16, outer);
-        if (chunks > R) chunks = R;
-        const int64_t rpc = svnet_cdiv(R, chunks);
-        chunks = svnet_cdiv(R, rpc);
-        hipLaunchKernelGGL(pool_maxmean_bwd_kernel, dim3((unsigned)chunks, (unsigned)outer), dim3(256), 0, (hipStream_t)stream,
-                           mode == 0 ? g : nullptr, mode == 1 ? g : nullptr, inner, argmax, R, inner, rpc, dx);
+        const SplitPlan pl = split_plan(outer, R, 256 * 16, 1);
+        hipLaunchKernelGGL(pool_maxmean_bwd_kernel, dim3((unsigned)pl.chunks, (unsigned)outer), dim3(256), 0, (hipStream_t)stream,
+                           mode == 0 ? g : nullptr, mode == 1 ? g : nullptr, inner, argmax, R, inner, pl.rows, dx);
         SVNET_CHECK_LAUNCH("pool_maxmean_bwd_kernel");
         return SVNET_OK;
     }
@@ -586,13 +396,9 @@ extern "C" int svnet_pool_mean_bwd_add_f32(const float* gmean, const float* add,
     SVNET_REQUIRE(gmean && add && dx && outer >= 0 && R > 0 && inner > 0 && add_ld >= inner && outer <= 65535, SVNET_E_ARG,
                   "svnet_pool_mean_bwd_add_f32: bad arguments");
     if (outer == 0) return SVNET_OK;
-    int64_t chunks = svnet_cdiv(256 * 8, outer);
-    if (chunks > svnet_cdiv(R, 8)) chunks = svnet_cdiv(R, 8);
-    if (chunks < 1) chunks = 1;
-    const int64_t rpc = svnet_cdiv(R, chunks);
-    chunks = svnet_cdiv(R, rpc);
-    hipLaunchKernelGGL(pool_mean_bwd_add_kernel, dim3((unsigned)chunks, (unsigned)outer), dim3(pool_col_block(inner)), 0, (hipStream_t)stream, gmean, add, add_ld,
-                       R, inner, rpc, dx);
+    const SplitPlan pl = split_plan(outer, R, 256 * 8, 8);
+    hipLaunchKernelGGL(pool_mean_bwd_add_kernel, dim3((unsigned)pl.chunks, (unsigned)outer), dim3(pool_col_block(inner)), 0, (hipStream_t)stream, gmean, add, add_ld,
+                       R, inner, pl.rows, dx);
     SVNET_CHECK_LAUNCH("pool_mean_bwd_add_kernel");
     return SVNET_OK;
 }
@@ -603,12 +409,9 @@ extern "C" int svnet_pool_maxmean_bwd_f32(const float* gmax, const float* gmean,
                   "svnet_pool_maxmean_bwd_f32: bad arguments");
     SVNET_REQUIRE(outer <= 65535, SVNET_E_UNSUPPORTED, "svnet_pool_maxmean_bwd_f32: outer > 65535");
     if (outer == 0) return SVNET_OK;
-    int64_t chunks = svnet_cdiv(256 * 16, outer);
-    if (chunks > R) chunks = R;
-    const int64_t rpc = svnet_cdiv(R, chunks);
-    chunks = svnet_cdiv(R, rpc);
-    hipLaunchKernelGGL(pool_maxmean_bwd_kernel, dim3((unsigned)chunks, (unsigned)outer), dim3(256), 0, (hipStream_t)stream, gmax, gmean,
-                       g_ld, argmax, R, inner, rpc, dx);
+    const SplitPlan pl = split_plan(outer, R, 256 * 16, 1);
+    hipLaunchKernelGGL(pool_maxmean_bwd_kernel, dim3((unsigned)pl.chunks, (unsigned)outer), dim3(256), 0, (hipStream_t)stream, gmax, gmean,
+                       g_ld, argmax, R, inner, pl.rows, dx);
     SVNET_CHECK_LAUNCH("pool_maxmean_bwd_kernel");
     return SVNET_OK;
 }

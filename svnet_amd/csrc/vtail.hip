@@ -15,6 +15,7 @@
 // to the three axes) and other contractions: values agree with the layer-wise chain to rounding (2e-5 of a tensor's largest element,
 // arg-max equal but for near-ties: tests/test_hip_fused.py), not bit for bit.
 #include "common.h"
+#include "split_reduce.h"
 
 namespace {
 
@@ -221,35 +222,6 @@ __global__ __launch_bounds__(256) void vtail_fwd_kernel(const float* __restrict_
     }
 }
 
-// unpack of the keys + ordered finish of the mean (pool.hip pool_maxmean_finish_kernel)
-__global__ __launch_bounds__(256) void vtail_finish_kernel(const unsigned long long* __restrict__ keys, const float* __restrict__ part,
-                                                           int64_t chunks, int64_t total, float invR, float* __restrict__ out_max,
-                                                           float* __restrict__ out_mean, int32_t* __restrict__ argmax, int64_t inner,
-                                                           int64_t out_ld) {
-    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
-        const unsigned long long kk = keys[e];
-        uint32_t u = (uint32_t)(kk >> 32);
-        u = (u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u;
-        // (the chunks' partial sums in order - bit-reproducible - with eight loads in flight: one dependent L2 round trip per chunk made
-        //  this 16 K-element kernel 8 - 10 us long; 32-bit division: total < 2^20)
-        float s = 0.f;
-        int64_t c = 0;
-        for (; c + 7 < chunks; c += 8) {
-            float t[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) t[u] = part[(c + u) * total + e];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) s += t[u];
-        }
-        for (; c < chunks; ++c) s += part[c * total + e];
-        const uint32_t o32 = (uint32_t)e / (uint32_t)inner;
-        const int64_t o = o32, i = e - o * inner;
-        out_max[o * out_ld + i] = __uint_as_float(u);
-        out_mean[o * out_ld + i] = s * invR;
-        argmax[e] = (int32_t)(0xFFFFFFFFu - (uint32_t)(kk & 0xFFFFFFFFull));
-    }
-}
-
 // ---- backward.  APPLY = false, first pass: everything up to VectorBN's batch sums (+ optionally g5 = dL/dv5 for vbn_bwd_apply_kernel).
 // APPLY = true, second pass: the SAME per-point recomputation of dL/dv5 (one read of the product instead of reading it and a stored g5),
 // then VectorBN's apply pass on it (vbn_bwd_apply_kernel's expressions) with the totals of the first pass's sums -> dv.
@@ -421,21 +393,15 @@ __global__ __launch_bounds__(256) void vtail_bwd_kernel(const float* __restrict_
     }
 }
 
-inline void vtail_chunks(int64_t B, int64_t N, int64_t& chunks, int64_t& rpc) {
-    chunks = svnet_cdiv(256 * 3, B);                      // ~3 workgroups per CU: a workgroup's set-up (the channels' statistics and
-    if (chunks > svnet_cdiv(N, 32)) chunks = svnet_cdiv(N, 32);   // constants, its final LDS combine + atomics) is paid per workgroup
-    if (chunks < 1) chunks = 1;
-    rpc = svnet_cdiv(svnet_cdiv(N, chunks), 8) * 8;       // (two points per wave and loop trip)
-    chunks = svnet_cdiv(N, rpc);
-}
+// ~3 workgroups per CU: a workgroup's set-up (the channels' statistics and constants, its final LDS combine + atomics) is paid per
+// workgroup; rows per chunk a multiple of 8 (two points per wave and loop trip)
+inline SplitPlan vtail_plan(int64_t B, int64_t N) { return split_plan(B, N, 256 * 3, 32, 8); }
 
 }  // namespace
 
 extern "C" size_t svnet_vtail_workspace_bytes(int64_t B, int64_t N, int64_t C) {
     if (B <= 0 || N <= 0 || C <= 0) return 0;
-    int64_t chunks, rpc;
-    vtail_chunks(B, N, chunks, rpc);
-    return (size_t)(B * 3 * C) * 8 + (size_t)(chunks * B * 3 * C) * sizeof(float);
+    return split_workspace_bytes(B * 3 * C, vtail_plan(B, N).chunks, true, true);
 }
 
 extern "C" int svnet_vtail_fwd_f32(const float* v, const double* sums, float eps, float momentum, float* mean, float* invstd,
@@ -449,27 +415,22 @@ extern "C" int svnet_vtail_fwd_f32(const float* v, const double* sums, float eps
     SVNET_REQUIRE(C <= 192, SVNET_E_UNSUPPORTED, "svnet_vtail_fwd_f32: C=%lld > 192 vector channels", (long long)C);
     SVNET_REQUIRE(workspace_bytes >= svnet_vtail_workspace_bytes(B, N, C), SVNET_E_ARG, "svnet_vtail_fwd_f32: workspace too small");
     hipStream_t st = (hipStream_t)stream;
-    int64_t chunks, rpc;
-    vtail_chunks(B, N, chunks, rpc);
-    const int64_t total = B * 3 * C;
-    unsigned long long* keys = (unsigned long long*)workspace;
-    float* part = (float*)((char*)workspace + (size_t)total * 8);
+    const SplitPlan pl = vtail_plan(B, N);
+    const int64_t total = B * 3 * C, rpc = pl.rows;
+    const SplitWorkspace ws = split_workspace_carve(workspace, total, true, true);
     if (!workspace_zeroed) {
-        hipError_t e = hipMemsetAsync(keys, 0, (size_t)total * 8, st);
+        hipError_t e = hipMemsetAsync(ws.keys, 0, split_workspace_bytes(total, 0, true, false), st);
         SVNET_REQUIRE(e == hipSuccess, SVNET_E_LAUNCH, "svnet_vtail_fwd_f32: memset failed");
     }
     VtStats s{};
     s.sums = sums; s.mean_out = mean; s.invstd_out = invstd; s.rmean = running_mean; s.rvar = running_var; s.nbt = nbt;
     s.mean_in = mean; s.invstd_in = invstd; s.eps = eps; s.momentum = momentum;
-    const dim3 grid((unsigned)chunks, (unsigned)B);
-    if (C <= 64) hipLaunchKernelGGL((vtail_fwd_kernel<1>), grid, dim3(256), 0, st, v, s, gamma, beta, gate, w_eff, (int)N, (int)C, (int)rpc, keys, part, total);
-    else if (C <= 128) hipLaunchKernelGGL((vtail_fwd_kernel<2>), grid, dim3(256), 0, st, v, s, gamma, beta, gate, w_eff, (int)N, (int)C, (int)rpc, keys, part, total);
-    else hipLaunchKernelGGL((vtail_fwd_kernel<3>), grid, dim3(256), 0, st, v, s, gamma, beta, gate, w_eff, (int)N, (int)C, (int)rpc, keys, part, total);
+    const dim3 grid((unsigned)pl.chunks, (unsigned)B);
+    if (C <= 64) hipLaunchKernelGGL((vtail_fwd_kernel<1>), grid, dim3(256), 0, st, v, s, gamma, beta, gate, w_eff, (int)N, (int)C, (int)rpc, ws.keys, ws.part, total);
+    else if (C <= 128) hipLaunchKernelGGL((vtail_fwd_kernel<2>), grid, dim3(256), 0, st, v, s, gamma, beta, gate, w_eff, (int)N, (int)C, (int)rpc, ws.keys, ws.part, total);
+    else hipLaunchKernelGGL((vtail_fwd_kernel<3>), grid, dim3(256), 0, st, v, s, gamma, beta, gate, w_eff, (int)N, (int)C, (int)rpc, ws.keys, ws.part, total);
     SVNET_CHECK_LAUNCH("vtail_fwd_kernel");
-    hipLaunchKernelGGL(vtail_finish_kernel, dim3(svnet_grid(total, 256)), dim3(256), 0, st, keys, part, chunks, total, 1.f / (float)N, out_max,
-                       out_mean, argmax, 3 * C, out_ld);
-    SVNET_CHECK_LAUNCH("vtail_finish_kernel");
-    return SVNET_OK;
+    return split_maxmean_finish(ws.keys, ws.part, pl.chunks, total, N, out_max, out_mean, argmax, 3 * C, out_ld, st);
 }
 
 extern "C" int svnet_vtail_bwd_f32(const float* v, const float* mean, const float* invstd, const float* gamma, const float* beta,
@@ -482,9 +443,9 @@ extern "C" int svnet_vtail_bwd_f32(const float* v, const float* mean, const floa
                   "svnet_vtail_bwd_f32: bad sizes");
     SVNET_REQUIRE(C <= 192, SVNET_E_UNSUPPORTED, "svnet_vtail_bwd_f32: C=%lld > 192 vector channels", (long long)C);
     hipStream_t st = (hipStream_t)stream;
-    int64_t chunks, rpc;
-    vtail_chunks(B, N, chunks, rpc);
-    const dim3 grid((unsigned)chunks, (unsigned)B);
+    const SplitPlan pl = vtail_plan(B, N);
+    const int64_t rpc = pl.rows;
+    const dim3 grid((unsigned)pl.chunks, (unsigned)B);
 #define SVNET_VT_BWD(CPL_) hipLaunchKernelGGL((vtail_bwd_kernel<CPL_, false>), grid, dim3(256), 0, st, v, mean, invstd, gamma, beta, gate, w_eff, gmax, gmean, g_ld, \
                                               argmax, (int)N, (int)C, (int)rpc, red, dgate, GX, g5, 0, (float*)nullptr)
     if (C <= 64) SVNET_VT_BWD(1);
@@ -504,9 +465,9 @@ extern "C" int svnet_vtail_bwd_apply_f32(const float* v, const float* mean, cons
     SVNET_REQUIRE(B > 0 && B <= 65535 && N > 0 && N < (1 << 30) && C > 0 && g_ld >= 3 * C, SVNET_E_ARG, "svnet_vtail_bwd_apply_f32: bad sizes");
     SVNET_REQUIRE(C <= 192, SVNET_E_UNSUPPORTED, "svnet_vtail_bwd_apply_f32: C=%lld > 192 vector channels", (long long)C);
     hipStream_t st = (hipStream_t)stream;
-    int64_t chunks, rpc;
-    vtail_chunks(B, N, chunks, rpc);
-    const dim3 grid((unsigned)chunks, (unsigned)B);
+    const SplitPlan pl = vtail_plan(B, N);
+    const int64_t rpc = pl.rows;
+    const dim3 grid((unsigned)pl.chunks, (unsigned)B);
 #define SVNET_VT_APPLY(CPL_) hipLaunchKernelGGL((vtail_bwd_kernel<CPL_, true>), grid, dim3(256), 0, st, v, mean, invstd, gamma, beta, gate, w_eff, gmax, gmean, \
                                                 g_ld, argmax, (int)N, (int)C, (int)rpc, red, (float*)nullptr, (float*)nullptr, (float*)nullptr, train_stats, dv)
     if (C <= 64) SVNET_VT_APPLY(1);

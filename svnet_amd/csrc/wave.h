@@ -141,7 +141,7 @@ __device__ __forceinline__ void argmax_group(float& v, int& i, int lane) {
 
 // ---- order-preserving keys.  ord_bits maps a float's bit pattern to a uint32 whose unsigned order is the float order; ord_key first
 // makes -0 a +0, so that equal floats have equal keys, and ord_val is its inverse.  pack_key is the 64-bit composite whose unsigned
-// maximum (atomicMax) is the largest value and, among equal values, the lowest row; it keeps the sign of a zero.
+// maximum (atomicMax) is the largest value and, among equal values, the lowest row; it keeps the sign of a zero.  unpack_key is its inverse.
 __device__ __forceinline__ uint32_t ord_bits(uint32_t u) { return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
 __device__ __forceinline__ uint32_t ord_key(float v) { return ord_bits(__float_as_uint(v + 0.f)); }
 __device__ __forceinline__ float ord_val(uint32_t key) {
@@ -149,6 +149,10 @@ __device__ __forceinline__ float ord_val(uint32_t key) {
 }
 __device__ __forceinline__ unsigned long long pack_key(float v, int64_t r) {
     return ((unsigned long long)ord_bits(__float_as_uint(v)) << 32) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)r);
+}
+__device__ __forceinline__ void unpack_key(unsigned long long key, float& v, int32_t& r) {
+    v = ord_val((uint32_t)(key >> 32));
+    r = (int32_t)(0xFFFFFFFFu - (uint32_t)key);
 }
 
 // ---- 32 x 32 bit-matrix transpose across 32 consecutive lanes (both halves of the wave at once): lane r of a half holds row r

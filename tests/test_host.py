@@ -100,6 +100,25 @@ def test_block_tail_asks_for_at_most_64_kib_of_lds():
                     assert lds(Os, Ov, table) <= 65536, (Os, Ov, table)
 
 
+def test_split_reduction_workspace_contract():
+    """The workspace of a reduction over a long axis split over workgroups (csrc/split_reduce.h): [arg-max keys: outer*inner x 8 B |
+    partial sums: chunks x outer*inner x 4 B] with chunks = ceil(R / ceil(R / min(ceil(target / outer), ceil(R / 32)))), target 2048
+    (pooling) or 768 with rows per chunk rounded up to 8 (vector tail); 0 = no split path (R < 256, outer*inner >= 2^20, outer not
+    in 1..65535).  The Python layer sizes its blocks and decides "split path available" by these bytes alone, and the launchers
+    carve what they are handed by the same rule: values worked out by hand from the rule."""
+    from svnet_amd import _lib
+    L = _lib.lib()
+    pool = {(3, 300, 70): (1680, 8400), (32, 1024, 512): (131072, 2097152), (3, 256, 127): (3048, 12192), (1, 4099, 3): (24, 1548),
+            (65535, 256, 1): (524280, 262140), (3, 255, 70): (0, 0), (65536, 256, 1): (0, 0), (1024, 256, 1024): (0, 0),
+            (0, 300, 70): (0, 0)}
+    for (outer, R, inner), want in pool.items():
+        got = (L.svnet_pool_workspace_bytes(outer, R, inner, 0), L.svnet_pool_workspace_bytes(outer, R, inner, 1))
+        assert got == want, ((outer, R, inner), got, want)
+    vtail = {(32, 1024, 170): 1566720, (2, 256, 32): 7680, (3, 300, 45): 19440, (4, 257, 100): 52800, (0, 5, 5): 0}
+    for (B, N, C), want in vtail.items():
+        assert L.svnet_vtail_workspace_bytes(B, N, C) == want, ((B, N, C), L.svnet_vtail_workspace_bytes(B, N, C), want)
+
+
 def test_product_path_has_no_cpu_fallback():
     from svnet_amd.models.utils.sv_util import knn, svpool
     from svnet_amd.models.sv_layers import Linear
