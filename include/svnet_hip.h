@@ -45,9 +45,9 @@ int svnet_slices_sum_f64(double* buf, int64_t L, void* stream);
 
 /* ABI version = 100 * round-of-change + serial.  It changes whenever an entry point gains / loses an argument or a caller-owned buffer
  * changes its required length (200: sliced accumulators, SVNET_SLICED_LEN; 400: this header; 401: the totals of a sliced accumulator are
- * written by its consumer, svnet_slices_sum_*; 402: GX of svnet_v2s_bwd_*, gw of svnet_xyzblock_bwd_f32 and col_sum of svnet_gemm_f32 are sliced accumulators; 403: svnet_binweight_grad_f32 takes sliced inputs; 421: svnet_three_nn_f32, svnet_three_interpolate_f32; 422: svnet_ball_query_f32, svnet_group_points_f32; 423: svnet_vlinear_stats_f32 is gone).  svnet_version() returns the value the
+ * written by its consumer, svnet_slices_sum_*; 402: GX of svnet_v2s_bwd_*, gw of svnet_xyzblock_bwd_f32 and col_sum of svnet_gemm_f32 are sliced accumulators; 403: svnet_binweight_grad_f32 takes sliced inputs; 421: svnet_three_nn_f32, svnet_three_interpolate_f32; 422: svnet_ball_query_f32, svnet_group_points_f32; 423: svnet_vlinear_stats_f32 is gone; 424: svnet_edgeblock_fwd_tier, svnet_edgeblock_bwd_tier, svnet_edgeblock_wgrad_tier, svnet_xyzblock_tier).  svnet_version() returns the value the
  * library was BUILT with: a caller compiled against another header must refuse to run (svnet_amd/_lib.py does).                   */
-#define SVNET_ABI_VERSION 423
+#define SVNET_ABI_VERSION 424
 int svnet_version(void);
 const char* svnet_last_error(void);
 
@@ -233,6 +233,12 @@ int svnet_edgeblock_prepare_f32(const float* W, const float* beta, int64_t Os, i
 int svnet_edgeblock_prepare_vec_f32(const float* W2, const float* scale2, const float* Wz, const float* scalez, int64_t Ov,
                                     int64_t Cv, float* wv, float* scv, void* stream);
 int svnet_edgeblock_fwd_f32(const svnet_edgeblock_desc* desc, void* stream);
+/* Which kernel instantiation svnet_edgeblock_fwd_f32 launches for these sizes (pure host function; the launch switches on it):
+ * SVNET_EDGE_FWD_TWO = the two-edges-per-iteration kernel (Cs <= 32, 2 Cv <= 32, Os <= 32, Ov <= 32 and 32-bit offsets into ut);
+ * else 100 + 10 * OP + NARROW = edgeblock_fwd_kernel<OP, NARROW> (OP = output channels per lane: 1 for Os <= 64, else 2; NARROW = Cs <= 32
+ * and 2 Cv <= 32).  -1 = outside the limits above (Cs <= 64, 2 Cv <= 64, Os <= 128, Ov <= 64).                                    */
+#define SVNET_EDGE_FWD_TWO 1
+int svnet_edgeblock_fwd_tier(int64_t Cs, int64_t Cv, int64_t Os, int64_t Ov, int64_t B, int64_t N);
 /* coef [4*Os + 4*Ov] = [A1 | B1 | mean_y | invstd_y | Av | Bv | mean_n' | invstd_n']: BatchNorm folded into
  * y = A1*n + B1 and q = Av + Bv/n'; training != 0 uses the batch sums (E = B*N*k edges) and updates running_*.   */
 int svnet_edgeblock_coeffs_f32(const int64_t* stat_n, const double* stat_v, int64_t E, int64_t Os, int64_t Ov,
@@ -334,6 +340,11 @@ int svnet_edgeblock_bwd_coeffs_f32(const float* red, const float* redv, const fl
                                    float* bcoef, float* dgamma1, float* dbeta1, float* dgamma2, float* dbeta2,
                                    const svnet_gate_bwd_job* gate_job /* may be NULL */, void* stream);
 int svnet_edgeblock_bwd_f32(const svnet_edgeblock_bwd_desc* desc, void* stream);
+/* Which instantiation of the 32-edge tile kernel svnet_edgeblock_bwd_f32 launches (pure host function; the launch switches on it):
+ * 100 * NKS + NC2 = edgeblock_bwd_kernel<0, NKS, NC2>.  NKS = 2 / 4 / 8 for Os <= 32 / 64 / 128 (16-row k-steps of phase B); NC2 = 20 / 24 /
+ * 44 / 48 = the eight-edges-per-wave form of phase C for Cv <= 10 / 12 / 21 / 24, taken when 3 <= Cv <= 24 and 3 Cv <= 2 Cs, else 0 = the
+ * one-edge form.  -1 = outside the backward's limits: Cs <= 64, 2 Cv <= 64, Os a power of two in 8 .. 128.                         */
+int svnet_edgeblock_bwd_tier(int64_t Cs, int64_t Cv, int64_t Os);
 /* Reverse neighbour lists of a kNN graph (idx [B*N,k], cloud-local ids): the edges e = i*k + t that point at j are
  * rev_edge[rev_range[2j] .. rev_range[2j+1]), their source points i (global ids) rev_src[..].  rev_range [2*B*N], rev_edge and
  * rev_src [B*N*k]; N <= 8192; ids outside [0,N) are skipped.  Optional (all three or none): lists longer than `chunk` entries
@@ -413,6 +424,10 @@ typedef struct svnet_xyzblock_bwd_desc {
     int64_t nc;        /* as in svnet_xyzblock_desc; gw = [dW1 (Os*6nc) | dW2 (Ov*nc) | dW0 (3nc) | dWz (3nc)], gconst [B,3nc]   */
 } svnet_xyzblock_bwd_desc;
 int svnet_xyzblock_bwd_f32(const svnet_xyzblock_bwd_desc* desc, void* stream);
+/* Which instantiation svnet_xyzblock_fwd_f32 and svnet_xyzblock_bwd_f32 launch (pure host function; both launches switch on it):
+ * 10 * NC + EPI = xyzblock_fwd_kernel<NC, EPI> / xyzblock_bwd_kernel<NC, EPI>; NC = 2 (nc 0 or 2) or 3; EPI = edges per wave iteration: 2 for
+ * Os <= 32 and Ov <= 32, else 1.  -1 = outside Os <= 64, Ov <= 64, nc in {0, 2, 3}.                                                 */
+int svnet_xyzblock_tier(int64_t Os, int64_t Ov, int64_t nc);
 
 /* Weight-gradient product of a fused edge layer: GX[o*320 + c] += sum_e dy[e,o] * x_b[e,c] over the E = B*N*k edge rows, with
  * dy[e,o] = dL/dy_pre RECOMPUTED from the forward's int16 sums: chc[o]*g - (chc[Os+o] + chc[2Os+o]*n16[e,o]), g = gy[p,o] when the
@@ -422,6 +437,14 @@ int svnet_xyzblock_bwd_f32(const svnet_xyzblock_bwd_desc* desc, void* stream);
 int svnet_edgeblock_wgrad_f32(const int16_t* n16, const uint8_t* slot_max, const uint8_t* slot_min, const float* gy,
                               const float* chc, const uint64_t* x_sign, const uint64_t* x_nz, int64_t E, int64_t k, int64_t Os,
                               float* GX, uint32_t q_tile_mask, void* stream);
+/* Which kernel svnet_edgeblock_wgrad_f32 launches (pure host function; the launch and the caller's choice of path switch on it):
+ * SVNET_WGRAD_AFF2 = one 128 x 320 output tile per workgroup (Os = 128, all ten 32-column tiles of q_tile_mask in use, E % 32 == 0);
+ * SVNET_WGRAD_TERN5 = the ternary TN kernel with five column tiles per wave, affine A operand.  -1 = not served (k < 8: a 16-row k-step
+ * would span more than two points; k > 64; E % k != 0; Os > 128; (E / k) * Os >= 2^29): the caller has the tile kernel write dn_out and
+ * runs svnet_gemm_f32 on the planes instead.                                                                                      */
+#define SVNET_WGRAD_TERN5 1
+#define SVNET_WGRAD_AFF2 2
+int svnet_edgeblock_wgrad_tier(int64_t E, int64_t k, int64_t Os, uint32_t q_tile_mask);
 
 /* ------------------------------------------------------------------ Vector2Scalar (sv_layers.py:104-129)
  * v: [M,3,C]; w_eff: [J,C] effective weights (scale*sign(W) or W); z[m,i,j] = sum_c v[m,i,c] w_eff[j,c];

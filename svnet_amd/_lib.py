@@ -10,7 +10,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SVNET_DIAG_LIB") or os.path.join(_HERE, "libsvnet_hip.so")    # (SVNET_DIAG_LIB: an ablation build, tools/ only)
 _lib = None
-ABI_VERSION = 423       # include/svnet_hip.h SVNET_ABI_VERSION: argument lists / buffer-length contracts this binding was written against
+ABI_VERSION = 424       # include/svnet_hip.h SVNET_ABI_VERSION: argument lists / buffer-length contracts this binding was written against
 
 c_p = ctypes.c_void_p
 c_i64 = ctypes.c_int64
@@ -201,6 +201,7 @@ SIGNATURES = {
     "svnet_edgeblock_bwd_params_f32": (c_int, [c_p] * 8 + [c_i64] * 4 + [c_p] * 6 + [c_p]),
     "svnet_edgeblock_prepare_f32": (c_int, [c_p, c_p, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_p]),
     "svnet_edgeblock_fwd_f32": (c_int, [ctypes.POINTER(EdgeBlockDesc), c_p]),
+    "svnet_edgeblock_fwd_tier": (c_int, [c_i64] * 6),
     "svnet_edgeblock_coeffs_f32": (c_int, _block_coeffs([c_p])),
     "svnet_edgeblock_apply_f32": (c_int, _BLOCK_APPLY + [c_p]),
     "svnet_edgeblock_apply_knn_f32": (c_int, _BLOCK_APPLY + [c_p, c_sz, c_p]),
@@ -208,6 +209,8 @@ SIGNATURES = {
     "svnet_edgeblock_bwd_prelude_f32": (c_int, [c_p] * 9 + [c_i64, c_i64, c_i64, c_i64, c_f, c_p, c_p, c_p, c_p, c_p, c_i64, c_p, c_i64, c_p, c_p]),
     "svnet_edgeblock_bwd_coeffs_f32": (c_int, [c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_int, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
     "svnet_edgeblock_bwd_f32": (c_int, [ctypes.POINTER(EdgeBlockBwdDesc), c_p]),
+    "svnet_edgeblock_bwd_tier": (c_int, [c_i64] * 3),
+    "svnet_edgeblock_wgrad_tier": (c_int, [c_i64, c_i64, c_i64, ctypes.c_uint32]),
     "svnet_edgeblock_wgrad_f32": (c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_p, ctypes.c_uint32, c_p]),
     "svnet_xyzblock_fwd_f32": (c_int, [ctypes.POINTER(XyzBlockDesc), c_p]),
     "svnet_xyzblock_coeffs_f32": (c_int, _block_coeffs([])),
@@ -215,6 +218,7 @@ SIGNATURES = {
     "svnet_xyzblock_apply_knn_f32": (c_int, _BLOCK_APPLY + [c_p, c_sz, c_p]),
     "svnet_xyzblock_bwd_prelude_f32": (c_int, [c_p] * 8 + [c_i64, c_i64, c_i64, c_i64, c_f, c_p, c_p, c_p, c_p, c_p, c_i64, c_p, c_i64, c_p, c_p]),
     "svnet_xyzblock_bwd_f32": (c_int, [ctypes.POINTER(XyzBlockBwdDesc), c_p]),
+    "svnet_xyzblock_tier": (c_int, [c_i64] * 3),
     "svnet_binweight_i8_bytes": (c_sz, [c_i64, c_i64]),
     "svnet_binweight_pack_i8": (c_int, [c_p, c_i64, c_i64, c_p, c_p]),
     "svnet_binlinear_i8_fwd_f32": (c_int, [c_p, c_i64, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_p, c_p, c_p]),
@@ -287,6 +291,8 @@ SIGNATURES = {
 }
 
 
+EDGE_FWD_TWO = 1                     # SVNET_EDGE_FWD_TWO
+WGRAD_TERN5, WGRAD_AFF2 = 1, 2       # SVNET_WGRAD_TERN5 / SVNET_WGRAD_AFF2
 KD_ROWS, KD_CHANNEL_MAJOR = 0, 1     # SVNET_KD_ROWS / SVNET_KD_CHANNEL_MAJOR
 KD_WORKSPACE_FLOATS = 8192           # SVNET_KD_WORKSPACE_FLOATS
 

@@ -2142,7 +2142,12 @@ class EdgeBlock(torch.autograd.Function):
         coeffs_done = main.record_event()                                    # (what the vector path waits for)
 
         # ---- the edge pass
-        affine = k >= 8        # the weight-gradient GEMM recomputes dL/dy_pre from n16: the tile kernel then writes no fp32 [E,Os] tensor
+        used = 0                      # 32-column tiles of the 5 x 64 fused columns that hold features (the rest is padding)
+        for ct in range(10):
+            if ((Cs if ct < 4 else 2 * Cv) > 32 * (ct & 1)):
+                used |= 1 << ct
+        # the weight-gradient GEMM recomputes dL/dy_pre from n16 where it serves the shape (k >= 8): the tile kernel then writes no fp32 [E,Os] tensor
+        affine = _lib.lib().svnet_edgeblock_wgrad_tier(E, k, Os, used) >= 0
         dn_out = None if affine else torch.empty((E, Os), **f32)
         x_sign = torch.empty(((E + 63) // 64, 320), dtype=torch.int64, device=dev)
         x_nz = torch.empty(((E + 63) // 64, 320), dtype=torch.int64, device=dev)
@@ -2185,10 +2190,6 @@ class EdgeBlock(torch.autograd.Function):
         # linear1's weight-gradient product GXp = dy^T . x_b (MFMA, ternary planes, fused column order) only needs the tile
         # kernel's outputs: it keeps the main stream while the side stream (joined with main first) sums the messages
         side.wait_stream(main)
-        used = 0                      # 32-column tiles of the 5 x 64 fused columns that hold features (the rest is padding)
-        for ct in range(10):
-            if ((Cs if ct < 4 else 2 * Cv) > 32 * (ct & 1)):
-                used |= 1 << ct
 
         def wgrad1():
             if affine:

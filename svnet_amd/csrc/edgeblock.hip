@@ -701,6 +701,17 @@ extern "C" int svnet_edgeblock_prepare_f32(const float* W, const float* beta, in
     return SVNET_OK;
 }
 
+extern "C" int svnet_edgeblock_fwd_tier(int64_t Cs, int64_t Cv, int64_t Os, int64_t Ov, int64_t B, int64_t N) {
+    if (!(Cs > 0 && Cs <= 64 && Cv > 0 && 2 * Cv <= 64 && Os > 0 && Os <= 128 && Ov > 0 && Ov <= 64)) return -1;
+    const bool narrow = Cs <= 32 && 2 * Cv <= 32;
+    // two edges per wave iteration (32-bit element offsets: the largest table, ut, has B*N*6*Ov floats).  Measured at B=32,
+    // N=1024, k=20: Os = 32 (conv2) 196 -> 159 us; Os = 64 (conv3: two output channels per lane, so the popcount part does
+    // not shrink, and 72 B of spills at 4 waves per SIMD) 197 -> 195 us - conv3 stays on the one-edge kernel (OP2 = 1 is the
+    // only instantiation)
+    if (narrow && Ov <= 32 && Os <= 32 && B * N * 6 * Ov < ((int64_t)1 << 30)) return SVNET_EDGE_FWD_TWO;
+    return 100 + 10 * (Os <= 64 ? 1 : 2) + (narrow ? 1 : 0);
+}
+
 extern "C" int svnet_edgeblock_fwd_f32(const svnet_edgeblock_desc* desc, void* stream) {
     SVNET_REQUIRE(desc, SVNET_E_ARG, "svnet_edgeblock_fwd_f32: null descriptor");
     const svnet_edgeblock_desc& d = *desc;
@@ -710,8 +721,8 @@ extern "C" int svnet_edgeblock_fwd_f32(const svnet_edgeblock_desc* desc, void* s
     SVNET_REQUIRE((d.n16 == nullptr) == (d.planes == nullptr), SVNET_E_ARG, "svnet_edgeblock_fwd_f32: pass both n16 and planes or none");
     SVNET_REQUIRE(d.B >= 0 && d.N > 0 && d.k > 0, SVNET_E_ARG, "svnet_edgeblock_fwd_f32: bad sizes");
     SVNET_REQUIRE(d.k <= 64, SVNET_E_UNSUPPORTED, "svnet_edgeblock_fwd_f32: k=%lld > 64", (long long)d.k);
-    SVNET_REQUIRE(d.Cs > 0 && d.Cs <= 64 && d.Cv > 0 && 2 * d.Cv <= 64 && d.Os > 0 && d.Os <= 128 && d.Ov > 0 && d.Ov <= 64,
-                  SVNET_E_UNSUPPORTED, "svnet_edgeblock_fwd_f32: channel counts outside Cs<=64, 2Cv<=64, Os<=128, Ov<=64");
+    const int tier = svnet_edgeblock_fwd_tier(d.Cs, d.Cv, d.Os, d.Ov, d.B, d.N);
+    SVNET_REQUIRE(tier >= 0, SVNET_E_UNSUPPORTED, "svnet_edgeblock_fwd_f32: channel counts outside Cs<=64, 2Cv<=64, Os<=128, Ov<=64");
     if (d.B == 0) return SVNET_OK;
     FwdArgs fa;
     fa.d = d;
@@ -722,22 +733,15 @@ extern "C" int svnet_edgeblock_fwd_f32(const svnet_edgeblock_desc* desc, void* s
     fa.waves_per_cloud = (int)svnet_cdiv(d.N, fa.points_per_wave);
     const int64_t waves = d.B * fa.waves_per_cloud;
     const unsigned grid = (unsigned)svnet_cdiv(waves, 4);
-    const bool narrow = d.Cs <= 32 && 2 * d.Cv <= 32;
-    if (narrow && d.Ov <= 32 && d.Os <= 32 && d.B * d.N * 6 * (int64_t)d.Ov < ((int64_t)1 << 30)) {
-        // two edges per wave iteration (32-bit element offsets: the largest table, ut, has B*N*6*Ov floats).  Measured at B=32,
-        // N=1024, k=20: Os = 32 (conv2) 196 -> 159 us; Os = 64 (conv3: two output channels per lane, so the popcount part does
-        // not shrink, and 72 B of spills at 4 waves per SIMD) 197 -> 195 us - conv3 stays on the one-edge kernel (OP2 = 1 is the
-        // only instantiation)
-        hipLaunchKernelGGL((edgeblock_fwd2_kernel<1>), dim3(grid), dim3(256), 0, (hipStream_t)stream, fa);
-        SVNET_CHECK_LAUNCH("edgeblock_fwd2_kernel");
-        return SVNET_OK;
-    }
-    if (d.Os <= 64) {
-        if (narrow) hipLaunchKernelGGL((edgeblock_fwd_kernel<1, true>), dim3(grid), dim3(256), 0, (hipStream_t)stream, fa);
-        else hipLaunchKernelGGL((edgeblock_fwd_kernel<1, false>), dim3(grid), dim3(256), 0, (hipStream_t)stream, fa);
-    } else {
-        if (narrow) hipLaunchKernelGGL((edgeblock_fwd_kernel<2, true>), dim3(grid), dim3(256), 0, (hipStream_t)stream, fa);
-        else hipLaunchKernelGGL((edgeblock_fwd_kernel<2, false>), dim3(grid), dim3(256), 0, (hipStream_t)stream, fa);
+    switch (tier) {
+        case SVNET_EDGE_FWD_TWO:
+            hipLaunchKernelGGL((edgeblock_fwd2_kernel<1>), dim3(grid), dim3(256), 0, (hipStream_t)stream, fa);
+            SVNET_CHECK_LAUNCH("edgeblock_fwd2_kernel");
+            return SVNET_OK;
+        case 111: hipLaunchKernelGGL((edgeblock_fwd_kernel<1, true>), dim3(grid), dim3(256), 0, (hipStream_t)stream, fa); break;
+        case 110: hipLaunchKernelGGL((edgeblock_fwd_kernel<1, false>), dim3(grid), dim3(256), 0, (hipStream_t)stream, fa); break;
+        case 121: hipLaunchKernelGGL((edgeblock_fwd_kernel<2, true>), dim3(grid), dim3(256), 0, (hipStream_t)stream, fa); break;
+        default: hipLaunchKernelGGL((edgeblock_fwd_kernel<2, false>), dim3(grid), dim3(256), 0, (hipStream_t)stream, fa); break;   // 120
     }
     SVNET_CHECK_LAUNCH("edgeblock_fwd_kernel");
     return SVNET_OK;

@@ -538,7 +538,7 @@ __global__ __launch_bounds__(256, 4) void edgeblock_bwd_kernel(svnet_edgeblock_b
         const int o4_shift = __builtin_ctz((unsigned)O4);   // Os is a power of two (checked on the host): item / O4 is a shift
         const int k = (int)d.k;
         // per-channel constants [cs | alpha | beta | scale | pooled-is-max] from svnet_edgeblock_bwd_coeffs_f32.  256 is a multiple
-        // of Os/4 (Os in {32, 64, 128}: asserted on the host), so a thread's quads all sit on the same four channels
+        // of Os/4 (Os a power of two in 8 .. 128: svnet_edgeblock_bwd_tier, checked on the host), so a thread's quads all sit on the same four channels
         const float* chc = d.bcoef + ((3 * Os + 2 * d.Ov + 3) & ~3);
         const int o4c = (tid & (O4 - 1)) << 2;
         const float4 cs = *reinterpret_cast<const float4*>(chc + o4c);
@@ -1052,6 +1052,15 @@ extern "C" int svnet_edgeblock_bwd_coeffs_f32(const float* red, const float* red
     return SVNET_OK;
 }
 
+extern "C" int svnet_edgeblock_bwd_tier(int64_t Cs, int64_t Cv, int64_t Os) {
+    if (!(Cs > 0 && Cs <= 64 && Cv > 0 && 2 * Cv <= 64 && Os >= 8 && Os <= 128 && (Os & (Os - 1)) == 0)) return -1;
+    const int nks = Os <= 32 ? 2 : Os <= 64 ? 4 : 8;
+    // the eight-edges-per-wave form of phase C: a neighbour's [3][Cv] row in one or two 64-lane loads, a lane pair per (edge, axis)
+    // over the Cs scalar lanes (3 Cv <= 2 Cs); anything else takes the one-edge form
+    const bool c8 = Cv >= 3 && Cv <= 24 && 3 * Cv <= 2 * Cs && 3 * Cv <= 128;
+    return 100 * nks + (!c8 ? 0 : Cv <= 10 ? 20 : Cv <= 12 ? 24 : Cv <= 21 ? 44 : 48);
+}
+
 extern "C" int svnet_edgeblock_bwd_f32(const svnet_edgeblock_bwd_desc* desc, void* stream) {
     SVNET_REQUIRE(desc, SVNET_E_ARG, "svnet_edgeblock_bwd_f32: null descriptor");
     const svnet_edgeblock_bwd_desc& d = *desc;
@@ -1060,11 +1069,11 @@ extern "C" int svnet_edgeblock_bwd_f32(const svnet_edgeblock_bwd_desc* desc, voi
                       d.msg && d.dvc && d.dzc && d.dbeta_perm && d.ub_tab && d.ge_tab,
                   SVNET_E_ARG, "svnet_edgeblock_bwd_f32: null pointer");
     SVNET_REQUIRE(d.B >= 0 && d.N > 0 && d.k >= 2 && d.k <= 64, SVNET_E_ARG, "svnet_edgeblock_bwd_f32: bad sizes (2 <= k <= 64)");
-    SVNET_REQUIRE((d.Os & (d.Os - 1)) == 0, SVNET_E_UNSUPPORTED, "svnet_edgeblock_bwd_f32: Os must be a power of two (8..128)");
     SVNET_REQUIRE(d.B * d.N * 384 < ((int64_t)1 << 32), SVNET_E_UNSUPPORTED, "svnet_edgeblock_bwd_f32: more than 11 M points (32-bit row offsets)");
     SVNET_REQUIRE(d.B * d.N * d.k < ((int64_t)1 << 31), SVNET_E_UNSUPPORTED, "svnet_edgeblock_bwd_f32: more than 2^31 edge rows");
-    SVNET_REQUIRE(d.Cs > 0 && d.Cs <= 64 && d.Cv > 0 && 2 * d.Cv <= 64 && d.Os > 0 && d.Os <= 128 && d.Os % 8 == 0 && d.Ov > 0 &&
-                      d.Ov <= 64, SVNET_E_UNSUPPORTED, "svnet_edgeblock_bwd_f32: channel counts outside Cs<=64, 2Cv<=64, Os<=128 (mult of 8), Ov<=64");
+    const int tier = svnet_edgeblock_bwd_tier(d.Cs, d.Cv, d.Os);
+    SVNET_REQUIRE(tier >= 0 && d.Ov > 0 && d.Ov <= 64, SVNET_E_UNSUPPORTED,
+                  "svnet_edgeblock_bwd_f32: channel counts outside Cs<=64, 2Cv<=64, Os a power of two in 8..128, Ov<=64");
     const int64_t E = d.B * d.N * d.k;
     if (E == 0) return SVNET_OK;
     hipStream_t st = (hipStream_t)stream;
@@ -1099,29 +1108,25 @@ extern "C" int svnet_edgeblock_bwd_f32(const svnet_edgeblock_bwd_desc* desc, voi
     const int dx_floats = TE * dxs > dnf ? TE * dxs : dnf;              // the dL/dn planes alias dxl
     const size_t lds = (size_t)((dx_floats + 3) & ~3) * 4 + (size_t)3 * TE * NW * 8;
     const unsigned grid = (unsigned)svnet_cdiv(E, TE);
-#define SVNET_LAUNCH_BWD(MODE)                                                                                              \
+#define SVNET_LAUNCH_BWD(MODE, NC2_)                                                                                        \
     do {                                                                                                                    \
-        if (d.Os <= 32) hipLaunchKernelGGL((edgeblock_bwd_kernel<MODE, 2>), dim3(grid), dim3(256), lds, st, d);             \
-        else if (d.Os <= 64) hipLaunchKernelGGL((edgeblock_bwd_kernel<MODE, 4>), dim3(grid), dim3(256), lds, st, d);        \
-        else hipLaunchKernelGGL((edgeblock_bwd_kernel<MODE, 8>), dim3(grid), dim3(256), lds, st, d);                        \
-    } while (0)
-#define SVNET_LAUNCH_BWD_C(NKS_)                                                                                            \
-    do {                                                                                                                    \
-        if (d.Cv <= 10) hipLaunchKernelGGL((edgeblock_bwd_kernel<0, NKS_, 20>), dim3(grid), dim3(256), lds, st, d);         \
-        else if (d.Cv <= 12) hipLaunchKernelGGL((edgeblock_bwd_kernel<0, NKS_, 24>), dim3(grid), dim3(256), lds, st, d);    \
-        else if (d.Cv <= 21) hipLaunchKernelGGL((edgeblock_bwd_kernel<0, NKS_, 44>), dim3(grid), dim3(256), lds, st, d);    \
-        else hipLaunchKernelGGL((edgeblock_bwd_kernel<0, NKS_, 48>), dim3(grid), dim3(256), lds, st, d);                    \
+        if (nks == 2) hipLaunchKernelGGL((edgeblock_bwd_kernel<MODE, 2, NC2_>), dim3(grid), dim3(256), lds, st, d);         \
+        else if (nks == 4) hipLaunchKernelGGL((edgeblock_bwd_kernel<MODE, 4, NC2_>), dim3(grid), dim3(256), lds, st, d);    \
+        else hipLaunchKernelGGL((edgeblock_bwd_kernel<MODE, 8, NC2_>), dim3(grid), dim3(256), lds, st, d);                  \
     } while (0)
     static const bool c_old = getenv("SVNET_BWD_C_OLD") != nullptr;      // (diagnostic: the one-edge-per-iteration phase C)
-    if (mode == 0 && !c_old && d.Cv >= 3 && d.Cv <= 24 && 3 * d.Cv <= 2 * d.Cs && 3 * d.Cv <= 128) {     // (else the one-edge form)
-        if (d.Os <= 32) SVNET_LAUNCH_BWD_C(2); else if (d.Os <= 64) SVNET_LAUNCH_BWD_C(4); else SVNET_LAUNCH_BWD_C(8);
-    }
+    const int nks = tier / 100, nc2 = (mode != 0 || c_old) ? 0 : tier % 100;
 #ifdef SVNET_BWD_MODES
-    else if (mode == 1) SVNET_LAUNCH_BWD(1); else if (mode == 2) SVNET_LAUNCH_BWD(2); else if (mode == 3) SVNET_LAUNCH_BWD(3);
+    if (mode == 1) SVNET_LAUNCH_BWD(1, 0); else if (mode == 2) SVNET_LAUNCH_BWD(2, 0); else if (mode == 3) SVNET_LAUNCH_BWD(3, 0); else
 #endif
-    else SVNET_LAUNCH_BWD(0);
+    switch (nc2) {
+        case 20: SVNET_LAUNCH_BWD(0, 20); break;
+        case 24: SVNET_LAUNCH_BWD(0, 24); break;
+        case 44: SVNET_LAUNCH_BWD(0, 44); break;
+        case 48: SVNET_LAUNCH_BWD(0, 48); break;
+        default: SVNET_LAUNCH_BWD(0, 0); break;
+    }
 #undef SVNET_LAUNCH_BWD
-#undef SVNET_LAUNCH_BWD_C
     SVNET_CHECK_LAUNCH("edgeblock_bwd_kernel");
     return SVNET_OK;
 }

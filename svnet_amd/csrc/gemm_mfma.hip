@@ -1407,6 +1407,15 @@ int svnet_mfma_tn(const float* A, int64_t lda, const float* B, int64_t ldb, cons
     return SVNET_OK;
 }
 
+extern "C" int svnet_edgeblock_wgrad_tier(int64_t E, int64_t k, int64_t Os, uint32_t q_tile_mask) {
+    // k >= 8: a 16-row k-step (and an 8-row group of the aff2 kernel) then spans at most two points
+    if (!(E > 0 && k >= 8 && k <= 64 && E % k == 0 && Os > 0 && Os <= 128)) return -1;
+    if ((E / k) * Os >= ((int64_t)1 << 29)) return -1;                  // 32-bit offsets into the point-channel tables
+    const uint32_t qmask = q_tile_mask ? q_tile_mask : 0xFFFFFFFFu;
+    // wide layer, all ten column tiles in use, whole 32-row slabs: one output tile per workgroup
+    return (Os == 128 && (qmask & 0x3FFu) == 0x3FFu && (E & 31) == 0) ? SVNET_WGRAD_AFF2 : SVNET_WGRAD_TERN5;
+}
+
 // Weight-gradient product of a FUSED edge layer:  GX[p, q] += sum over the E edge rows of dy[e, p] * x_b[e, q]  (p < Os output
 // channels, q < 320 fused feature columns), with dy = dL/dy_pre recomputed inside the GEMM from the int16 sums the forward kept
 // (TnArgs "AFFINE A") instead of read from an fp32 [E, Os] tensor that the tile kernel would have to write first.
@@ -1414,9 +1423,10 @@ extern "C" int svnet_edgeblock_wgrad_f32(const int16_t* n16, const uint8_t* slot
                                          const float* chc, const uint64_t* x_sign, const uint64_t* x_nz, int64_t E, int64_t k, int64_t Os,
                                          float* GX, uint32_t q_tile_mask, void* stream) {
     SVNET_REQUIRE(n16 && slot_max && slot_min && gy && chc && x_sign && x_nz && GX, SVNET_E_ARG, "svnet_edgeblock_wgrad_f32: null pointer");
-    SVNET_REQUIRE(E > 0 && k >= 8 && k <= 64 && E % k == 0 && Os > 0 && Os <= 128, SVNET_E_UNSUPPORTED,
-                  "svnet_edgeblock_wgrad_f32: needs 8 <= k <= 64, Os <= 128 (got k=%lld, Os=%lld)", (long long)k, (long long)Os);
-    SVNET_REQUIRE((E / k) * Os < ((int64_t)1 << 29), SVNET_E_UNSUPPORTED, "svnet_edgeblock_wgrad_f32: more than 2^29 point-channels (32-bit offsets)");
+    const int tier = svnet_edgeblock_wgrad_tier(E, k, Os, q_tile_mask);
+    SVNET_REQUIRE(tier >= 0, SVNET_E_UNSUPPORTED,
+                  "svnet_edgeblock_wgrad_f32: needs 8 <= k <= 64, E %% k == 0, Os <= 128, fewer than 2^29 point-channels (got E=%lld, k=%lld, Os=%lld)",
+                  (long long)E, (long long)k, (long long)Os);
     hipStream_t st = (hipStream_t)stream;
     TnArgs a;
     a.A = nullptr; a.lda = Os; a.B = nullptr; a.ldb = 0; a.b_sign = x_sign; a.b_nz = x_nz;
@@ -1425,7 +1435,7 @@ extern "C" int svnet_edgeblock_wgrad_f32(const int16_t* n16, const uint8_t* slot
     a.n16 = n16; a.gy = gy; a.smax = slot_max; a.smin = slot_min; a.chc = chc;
     a.kk = (int)k; a.kmagic = (uint32_t)((65536 + k - 1) / k); a.npts = E / k;
     static const bool aff2_off = getenv("SVNET_AFF2_OFF") != nullptr;   // (diagnostic switch: the one-p-tile-per-wave kernel for every width)
-    if (Os == 128 && (a.qmask & 0x3FFu) == 0x3FFu && (E & 31) == 0 && !aff2_off) {       // wide layer, all ten column tiles in use: one output tile per workgroup
+    if (tier == SVNET_WGRAD_AFF2 && !aff2_off) {
         // (one 8-wave workgroup per CU: 126 KB of LDS.  256 workgroups - one round, every CU held for the whole launch - measured 4.356 /
         //  4.370 / 4.366 ms per step against 4.339 / 4.338 / 4.349 with 384: the shorter workgroups hand their CUs back to the gather on the main
         //  stream half-way; 320: 4.351, 448: 4.361, 512: 4.406, 128: 4.417; profiles/r04_ab_aff2_target.log)

@@ -570,6 +570,11 @@ inline void wave_geometry(int64_t B, int64_t N, int& wpc, int& ppw) {
 
 }  // namespace
 
+extern "C" int svnet_xyzblock_tier(int64_t Os, int64_t Ov, int64_t nc) {
+    if (!(Os > 0 && Os <= 64 && Ov > 0 && Ov <= 64 && (nc == 0 || nc == 2 || nc == 3))) return -1;
+    return 10 * (nc == 3 ? 3 : 2) + (Os <= 32 && Ov <= 32 ? 2 : 1);      // two edges per wave iteration while both widths fit half a wave
+}
+
 extern "C" int svnet_xyzblock_fwd_f32(const svnet_xyzblock_desc* desc, void* stream) {
     SVNET_REQUIRE(desc, SVNET_E_ARG, "svnet_xyzblock_fwd_f32: null descriptor");
     const svnet_xyzblock_desc& d = *desc;
@@ -584,13 +589,11 @@ extern "C" int svnet_xyzblock_fwd_f32(const svnet_xyzblock_desc* desc, void* str
     wave_geometry(d.B, d.N, fa.waves_per_cloud, fa.points_per_wave);
     const unsigned grid = (unsigned)svnet_cdiv(d.B * fa.waves_per_cloud, 4);
     SVNET_REQUIRE(d.nc == 0 || d.nc == 2 || d.nc == 3, SVNET_E_UNSUPPORTED, "svnet_xyzblock_fwd_f32: nc must be 2 (plain) or 3 (cross)");
-    const bool two = d.Os <= 32 && d.Ov <= 32;                  // two edges per wave iteration
-    if (d.nc == 3) {
-        if (two) hipLaunchKernelGGL((xyzblock_fwd_kernel<3, 2>), dim3(grid), dim3(256), 0, (hipStream_t)stream, fa);
-        else hipLaunchKernelGGL((xyzblock_fwd_kernel<3, 1>), dim3(grid), dim3(256), 0, (hipStream_t)stream, fa);
-    } else {
-        if (two) hipLaunchKernelGGL((xyzblock_fwd_kernel<2, 2>), dim3(grid), dim3(256), 0, (hipStream_t)stream, fa);
-        else hipLaunchKernelGGL((xyzblock_fwd_kernel<2, 1>), dim3(grid), dim3(256), 0, (hipStream_t)stream, fa);
+    switch (svnet_xyzblock_tier(d.Os, d.Ov, d.nc)) {
+        case 32: hipLaunchKernelGGL((xyzblock_fwd_kernel<3, 2>), dim3(grid), dim3(256), 0, (hipStream_t)stream, fa); break;
+        case 31: hipLaunchKernelGGL((xyzblock_fwd_kernel<3, 1>), dim3(grid), dim3(256), 0, (hipStream_t)stream, fa); break;
+        case 22: hipLaunchKernelGGL((xyzblock_fwd_kernel<2, 2>), dim3(grid), dim3(256), 0, (hipStream_t)stream, fa); break;
+        default: hipLaunchKernelGGL((xyzblock_fwd_kernel<2, 1>), dim3(grid), dim3(256), 0, (hipStream_t)stream, fa); break;    // 21
     }
     SVNET_CHECK_LAUNCH("xyzblock_fwd_kernel");
     return SVNET_OK;
@@ -663,13 +666,11 @@ extern "C" int svnet_xyzblock_bwd_f32(const svnet_xyzblock_bwd_desc* desc, void*
     wpc = (int)svnet_cdiv(d.N, ppw);
     const unsigned grid = (unsigned)svnet_cdiv(d.B * wpc, 4);
     SVNET_REQUIRE(d.nc == 0 || d.nc == 2 || d.nc == 3, SVNET_E_UNSUPPORTED, "svnet_xyzblock_bwd_f32: nc must be 2 (plain) or 3 (cross)");
-    const bool two = d.Os <= 32 && d.Ov <= 32;
-    if (d.nc == 3) {
-        if (two) hipLaunchKernelGGL((xyzblock_bwd_kernel<3, 2>), dim3(grid), dim3(256), 0, (hipStream_t)stream, d, wpc, ppw);
-        else hipLaunchKernelGGL((xyzblock_bwd_kernel<3, 1>), dim3(grid), dim3(256), 0, (hipStream_t)stream, d, wpc, ppw);
-    } else {
-        if (two) hipLaunchKernelGGL((xyzblock_bwd_kernel<2, 2>), dim3(grid), dim3(256), 0, (hipStream_t)stream, d, wpc, ppw);
-        else hipLaunchKernelGGL((xyzblock_bwd_kernel<2, 1>), dim3(grid), dim3(256), 0, (hipStream_t)stream, d, wpc, ppw);
+    switch (svnet_xyzblock_tier(d.Os, d.Ov, d.nc)) {
+        case 32: hipLaunchKernelGGL((xyzblock_bwd_kernel<3, 2>), dim3(grid), dim3(256), 0, (hipStream_t)stream, d, wpc, ppw); break;
+        case 31: hipLaunchKernelGGL((xyzblock_bwd_kernel<3, 1>), dim3(grid), dim3(256), 0, (hipStream_t)stream, d, wpc, ppw); break;
+        case 22: hipLaunchKernelGGL((xyzblock_bwd_kernel<2, 2>), dim3(grid), dim3(256), 0, (hipStream_t)stream, d, wpc, ppw); break;
+        default: hipLaunchKernelGGL((xyzblock_bwd_kernel<2, 1>), dim3(grid), dim3(256), 0, (hipStream_t)stream, d, wpc, ppw); break;   // 21
     }
     SVNET_CHECK_LAUNCH("xyzblock_bwd_kernel");
     return SVNET_OK;

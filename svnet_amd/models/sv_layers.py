@@ -256,6 +256,19 @@ class PendingEdgeBlock:
         return 2
 
 
+def edge_block_shape_ok(Cs, Cv, Os, Ov, k, N):
+    """The shapes the fused binarized edge block serves (plain integers: point-table widths (Cs, Cv) -> (Os, Ov), k neighbours, N points per
+    cloud) - what svnet_edgeblock_fwd_tier and svnet_edgeblock_bwd_tier admit, the k of the backward and the N of the reverse lists.
+    Anything else runs layer-wise."""
+    return (1 <= Cs <= 64 and 1 <= Cv and 2 * Cv <= 64 and Os in (8, 16, 32, 64, 128) and 1 <= Ov <= 64 and 2 <= k <= 64
+            and 1 <= N <= 8192)
+
+
+def xyz_block_shape_ok(Os, Ov, k):
+    """The shapes the fused full-precision first layer serves (svnet_xyzblock_tier's widths, k of the slot bytes)."""
+    return 1 <= Os <= 64 and 1 <= Ov <= 64 and 1 <= k <= 64
+
+
 class SVBlock(nn.Module):
     """One scalar/vector layer: gate from the mean scalar, invariant scalars from the vectors, (binarized)
     scalar linear + BN + LeakyReLU, (sign-weight) vector linear + VectorBN, vectors scaled by the gate."""
@@ -296,9 +309,8 @@ class SVBlock(nn.Module):
         if not (lin1.bw and lin1.ba and lin2.bw and self.v2s.linear.bw) or edges.idx_is_global:
             return False
         Cs, Cv = edges.s.shape[-1], edges.v.shape[-1]
-        return (Cs <= 64 and 2 * Cv <= 64 and lin1.out_features <= 128 and lin2.out_features <= 64 and 2 <= edges.k <= 64
-                and edges.s.shape[1] <= 8192 and lin1.out_features in (8, 16, 32, 64, 128) and lin1.in_features == 2 * Cs + 6 * Cv
-                and self._default_bn())
+        return (edge_block_shape_ok(Cs, Cv, lin1.out_features, lin2.out_features, edges.k, edges.s.shape[1])
+                and lin1.in_features == 2 * Cs + 6 * Cv and self._default_bn())
 
     def _default_bn(self):
         """The fused kernels take nn.BatchNorm1d's default eps / momentum (what every SV model uses); anything else runs layer-wise."""
@@ -315,8 +327,8 @@ class SVBlock(nn.Module):
             s, v = x
             lin1, lin2 = self.linear1, self.linear2
             if (isinstance(s, LazyInitScalar) and s.edges is v and not (lin1.bw or lin1.ba or lin2.bw or self.v2s.linear.bw)
-                    and lin1.in_features == 6 * v.nc and lin2.in_features == v.nc and lin1.out_features <= 64 and lin2.out_features <= 64
-                    and v.k <= 64 and self._default_bn()
+                    and lin1.in_features == 6 * v.nc and lin2.in_features == v.nc
+                    and xyz_block_shape_ok(lin1.out_features, lin2.out_features, v.k) and self._default_bn()
                     and (self.training or not torch.is_grad_enabled()
                          or not any(p.requires_grad for p in self.parameters()))):
                 return PendingXyzBlock(self, s, v)
