@@ -5,300 +5,93 @@ raises.  `build()` compiles the library in-tree with hipcc (gfx950 cross-compile
 """
 import ctypes
 import os
+import re
 import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SVNET_DIAG_LIB") or os.path.join(_HERE, "libsvnet_hip.so")    # (SVNET_DIAG_LIB: an ablation build, tools/ only)
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "svnet_hip.h")
 _lib = None
-ABI_VERSION = 424       # include/svnet_hip.h SVNET_ABI_VERSION: argument lists / buffer-length contracts this binding was written against
 
 c_p = ctypes.c_void_p
 c_i64 = ctypes.c_int64
 c_int = ctypes.c_int
 c_f = ctypes.c_float
 c_sz = ctypes.c_size_t
-
-
-class GemmDesc(ctypes.Structure):
-    """struct svnet_gemm_desc (include/svnet_hip.h)."""
-    _fields_ = [
-        ("M", c_i64), ("N", c_i64), ("K", c_i64),
-        ("A", c_p), ("a_rs", c_i64), ("a_cs", c_i64),
-        ("a_scale", c_p),
-        ("a_sign", c_p), ("a_nz", c_p),
-        ("B", c_p), ("b_rs", c_i64), ("b_cs", c_i64),
-        ("b_exact", c_int),
-        ("C", c_p), ("ldc", c_i64), ("c_cs", c_i64),
-        ("alpha", c_f),
-        ("col_scale", c_p),
-        ("bias", c_p),
-        ("mask", c_p),
-        ("col_sum", c_p),
-        ("split_k", c_int),
-        ("accumulate", c_int),
-        ("tern_tile_mask", ctypes.c_uint32),
-        ("workspace", c_p),
-        ("workspace_bytes", ctypes.c_size_t),
-    ]
-
-
-class GateFwdJob(ctypes.Structure):
-    """struct svnet_gate_fwd_job (include/svnet_hip.h): a gate MLP run beside a coefficient launch."""
-    _fields_ = [("gin", c_p), ("gin_f64", c_p), ("gin_out", c_p), ("in_scale", c_f), ("W0", c_p), ("W2", c_p),
-                ("B", c_i64), ("Cin", c_i64), ("H", c_i64), ("Ov", c_i64), ("h", c_p), ("gate", c_p), ("rows", c_p), ("R", c_i64)]
-
-
-class BlockTailDesc(ctypes.Structure):
-    """struct svnet_block_tail_desc (include/svnet_hip.h): coefficients + gate MLP + apply (+ k-NN table) of a fused level in one launch."""
-    _fields_ = [("stat1", c_p), ("stat_v", c_p), ("E", c_i64), ("Os", c_i64), ("Ov", c_i64), ("scale1", c_p),
-                ("gamma1", c_p), ("beta1", c_p), ("running_mean1", c_p), ("running_var1", c_p),
-                ("gamma2", c_p), ("beta2", c_p), ("running_mean2", c_p), ("running_var2", c_p),
-                ("training", c_int), ("eps", c_f), ("momentum", c_f),
-                ("coef", c_p), ("num_batches_tracked1", c_p), ("num_batches_tracked2", c_p),
-                ("gate", GateFwdJob),
-                ("hi", c_p), ("lo", c_p), ("mv", c_p), ("mvn", c_p), ("P", c_i64), ("N", c_i64), ("slope", c_f),
-                ("s_out", c_p), ("v_out", c_p), ("s_cat", c_p), ("s_ld", c_i64), ("v_cat", c_p), ("v_ld", c_i64),
-                ("knn_workspace", c_p), ("knn_workspace_bytes", c_sz)]
-
-
-class GateBwdJob(ctypes.Structure):
-    """struct svnet_gate_bwd_job (include/svnet_hip.h)."""
-    _fields_ = [("dgate", c_p), ("gate", c_p), ("h", c_p), ("gin", c_p), ("in_scale", c_f), ("W0", c_p), ("W2", c_p),
-                ("B", c_i64), ("Cin", c_i64), ("H", c_i64), ("Ov", c_i64), ("out_scale", c_f), ("dgin", c_p), ("dW0", c_p), ("dW2", c_p)]
-
-
-class EdgeBlockDesc(ctypes.Structure):
-    """struct svnet_edgeblock_desc (include/svnet_hip.h)."""
-    _fields_ = [
-        ("B", c_i64), ("N", c_i64), ("k", c_i64),
-        ("Cs", c_int), ("Cv", c_int), ("Os", c_int), ("Ov", c_int),
-        ("s", c_p), ("v", c_p), ("idx", c_p),
-        ("zz", c_p), ("ut", c_p),
-        ("w_sign", c_p), ("w_nz", c_p), ("beta_perm", c_p),
-        ("n_max", c_p), ("n_min", c_p), ("slot_max", c_p), ("slot_min", c_p),
-        ("mv", c_p), ("mvn", c_p),
-        ("stat_n", c_p), ("stat_v", c_p), ("gate_sum", c_p),
-        ("n16", c_p), ("planes", c_p),
-        ("w_dense", c_p),
-    ]
-
-
-class EdgeBlockBwdDesc(ctypes.Structure):
-    """struct svnet_edgeblock_bwd_desc (include/svnet_hip.h)."""
-    _fields_ = [
-        ("B", c_i64), ("N", c_i64), ("k", c_i64),
-        ("Cs", c_int), ("Cv", c_int), ("Os", c_int), ("Ov", c_int),
-        ("v", c_p), ("idx", c_p), ("zz", c_p), ("ut", c_p),
-        ("n16", c_p), ("planes", c_p),
-        ("w1bt", c_p),
-        ("scale1", c_p),
-        ("slot_max", c_p), ("slot_min", c_p),
-        ("coef", c_p), ("gate", c_p), ("gy", c_p), ("bcoef", c_p), ("gv", c_p), ("gconst", c_p),
-        ("dn_out", c_p), ("x_sign32", c_p), ("x_nz32", c_p),
-        ("msg", c_p),
-        ("ub_tab", c_p), ("ge_tab", c_p),
-        ("ds_acc", c_p), ("dv_acc", c_p), ("dvc", c_p), ("dzc", c_p), ("dbeta_perm", c_p),
-        ("debug", c_p),
-        ("parts", c_int),
-    ]
-
-
-class XyzBlockDesc(ctypes.Structure):
-    """struct svnet_xyzblock_desc (include/svnet_hip.h)."""
-    _fields_ = [
-        ("B", c_i64), ("N", c_i64), ("k", c_i64),
-        ("Os", c_int), ("Ov", c_int),
-        ("x", c_p), ("idx", c_p),
-        ("w0", c_p), ("wz", c_p), ("w1", c_p), ("w2", c_p),
-        ("y_max", c_p), ("y_min", c_p), ("slot_max", c_p), ("slot_min", c_p),
-        ("mv", c_p), ("mvn", c_p),
-        ("stat_y", c_p), ("stat_v", c_p), ("gate_sum", c_p),
-        ("nc", c_i64),
-    ]
-
-
-class XyzBlockBwdDesc(ctypes.Structure):
-    """struct svnet_xyzblock_bwd_desc (include/svnet_hip.h)."""
-    _fields_ = [
-        ("B", c_i64), ("N", c_i64), ("k", c_i64),
-        ("Os", c_int), ("Ov", c_int),
-        ("x", c_p), ("idx", c_p),
-        ("w0", c_p), ("wz", c_p), ("w1", c_p), ("w2", c_p),
-        ("slot_max", c_p), ("slot_min", c_p),
-        ("coef", c_p), ("bcoef", c_p), ("gate", c_p), ("gy", c_p), ("gv", c_p), ("gconst", c_p),
-        ("gw", c_p),
-        ("nc", c_i64),
-    ]
-
-
-class BinHeadDesc(ctypes.Structure):
-    """struct svnet_binhead_desc (include/svnet_hip.h)."""
-    _fields_ = [
-        ("M", c_i64), ("K", c_i64), ("O", c_i64),
-        ("W", c_p), ("w_sign", c_p), ("w_nz", c_p), ("wld", c_i64), ("w_b", c_p),
-        ("scale", c_p), ("gamma", c_p), ("bn_beta", c_p),
-        ("running_mean", c_p), ("running_var", c_p), ("nbt", c_p),
-        ("training", c_int), ("eps", c_f), ("momentum", c_f), ("act", c_int), ("slope", c_f),
-        ("x_sign", c_p), ("x_nz", c_p), ("x_ste", c_p), ("xc_sign", c_p), ("xc_nz", c_p),
-        ("y", c_p), ("mean", c_p), ("invstd", c_p), ("out", c_p),
-        ("g", c_p), ("dnT", c_p), ("dW", c_p), ("dscale", c_p), ("dgamma", c_p), ("dbn_beta", c_p),
-        ("dx", c_p), ("dbeta_in", c_p),
-    ]
-
-
-class BatchDesc(ctypes.Structure):
-    """struct svnet_batch_desc (include/svnet_hip.h)."""
-    _fields_ = [
-        ("data", c_p), ("label", c_p), ("seg", c_p), ("order", c_p),
-        ("M", c_i64), ("P", c_i64), ("L", c_i64),
-        ("B", c_i64), ("N", c_i64),
-        ("first", c_i64), ("count", c_i64),
-        ("seed", c_i64), ("epoch", c_i64),
-        ("select_mode", c_int), ("scale_shift", c_int), ("rotate", c_int),
-        ("num_cat", c_i64),
-        ("x", c_p), ("y", c_p), ("seg_out", c_p), ("onehot", c_p), ("params", c_p),
-    ]
-
-
-# The post-pool stage of a fused level has one entry point per block (edge / xyz) and one argument list for both (csrc/block_post.h):
-#   coeffs: stat1, stat_v, E, Os, Ov, [the edge block's scale1,] gamma1 .. running_var2, training, eps, momentum, coef, nbt1, nbt2, gate job, stream
-#   apply:  hi, lo, mv, mvn, coef, gate, P, N, Os, Ov, slope, s_out, v_out, s_cat, s_ld, v_cat, v_ld  (+ stream / + k-NN workspace, bytes, stream)
-#   tail:   descriptor, stream
-def _block_coeffs(scale1):
-    return [c_p, c_p, c_i64, c_i64, c_i64] + scale1 + [c_p] * 8 + [c_int, c_f, c_f] + [c_p] * 5
-
-
-_BLOCK_APPLY = [c_p] * 6 + [c_i64] * 4 + [c_f, c_p, c_p, c_p, c_i64, c_p, c_i64]
-_BLOCK_TAIL = [c_p, c_p]
-
-# name -> (restype, argtypes); every symbol include/svnet_hip.h declares
-SIGNATURES = {
-    "svnet_version": (c_int, []),
-    "svnet_stamp_u64": (c_int, [c_p, c_p]),
-    "svnet_slices_sum_f32": (c_int, [c_p, c_i64, c_p]),
-    "svnet_slices_sum_f64": (c_int, [c_p, c_i64, c_p]),
-    "svnet_last_error": (ctypes.c_char_p, []),
-    "svnet_knn_workspace_bytes": (c_sz, [c_i64, c_i64, c_i64]),
-    "svnet_knn_f32": (c_int, [c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_int, c_int, c_p, c_p, c_sz, c_p]),
-    "svnet_knn_sv_f32": (c_int, [c_p, c_i64, c_p, c_i64, c_i64, c_i64, c_int, c_p, c_p, c_sz, c_p]),
-    "svnet_knn_table_fusable": (c_int, [c_i64, c_i64, c_i64]),
-    "svnet_block_tail_supported": (c_int, [c_i64, c_i64, c_i64, c_i64, c_int]),
-    "svnet_edgeblock_tail_f32": (c_int, _BLOCK_TAIL),
-    "svnet_xyzblock_tail_f32": (c_int, _BLOCK_TAIL),
-    "svnet_knn_from_table_f32": (c_int, [c_p, c_sz, c_i64, c_i64, c_i64, c_int, c_p, c_p]),
-    "svnet_edge_xyz_f32": (c_int, [c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_int, c_p, c_p]),
-    "svnet_edge_diffcat_fwd_f32": (c_int, [c_p, c_p, c_int, c_i64, c_i64, c_i64, c_i64, c_i64, c_p, c_p]),
-    "svnet_edge_diffcat_bwd_f32": (c_int, [c_p, c_p, c_int, c_i64, c_i64, c_i64, c_i64, c_i64, c_p, c_p]),
-    "svnet_gemm_workspace_bytes": (ctypes.c_size_t, [c_i64, c_i64]),
-    "svnet_gemm_f32": (c_int, [ctypes.POINTER(GemmDesc), c_p]),
-    "svnet_binweight_prepare_f32": (c_int, [c_p, c_p, c_i64, c_i64, c_p, c_p, c_p, c_p, c_p]),
-    "svnet_binlinear_fwd_f32": (c_int, [c_p, c_i64, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_p, c_p]),
-    "svnet_binweight_grad_f32": (c_int, [c_p, c_p, c_p, c_i64, c_i64, c_p, c_p, c_int, c_int, c_p, c_i64, c_p]),
-    "svnet_edgeblock_prepare_vec_f32": (c_int, [c_p, c_p, c_p, c_p, c_i64, c_i64, c_p, c_p, c_p]),
-    "svnet_knn_reverse_i32": (c_int, [c_p, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_i64, c_p, c_p, c_p]),
-    "svnet_edgeblock_msg_stride": (c_i64, [c_i64, c_i64, c_i64]),
-    "svnet_edgeblock_bwd_gather_f32": (c_int, [c_p] * 9 + [c_i64] + [c_p, c_p] + [c_i64] * 5 + [c_p, c_i64, c_p, c_p, c_p, c_p, c_i64, c_p, c_p, c_p]),
-    "svnet_edgeblock_bwd_params_f32": (c_int, [c_p] * 8 + [c_i64] * 4 + [c_p] * 6 + [c_p]),
-    "svnet_edgeblock_prepare_f32": (c_int, [c_p, c_p, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_p]),
-    "svnet_edgeblock_fwd_f32": (c_int, [ctypes.POINTER(EdgeBlockDesc), c_p]),
-    "svnet_edgeblock_fwd_tier": (c_int, [c_i64] * 6),
-    "svnet_edgeblock_coeffs_f32": (c_int, _block_coeffs([c_p])),
-    "svnet_edgeblock_apply_f32": (c_int, _BLOCK_APPLY + [c_p]),
-    "svnet_edgeblock_apply_knn_f32": (c_int, _BLOCK_APPLY + [c_p, c_sz, c_p]),
-    "svnet_edgeblock_wbt_bf16": (c_int, [c_p, c_p, c_i64, c_i64, c_i64, c_p, c_p, c_p]),
-    "svnet_edgeblock_bwd_prelude_f32": (c_int, [c_p] * 9 + [c_i64, c_i64, c_i64, c_i64, c_f, c_p, c_p, c_p, c_p, c_p, c_i64, c_p, c_i64, c_p, c_p]),
-    "svnet_edgeblock_bwd_coeffs_f32": (c_int, [c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_int, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
-    "svnet_edgeblock_bwd_f32": (c_int, [ctypes.POINTER(EdgeBlockBwdDesc), c_p]),
-    "svnet_edgeblock_bwd_tier": (c_int, [c_i64] * 3),
-    "svnet_edgeblock_wgrad_tier": (c_int, [c_i64, c_i64, c_i64, ctypes.c_uint32]),
-    "svnet_edgeblock_wgrad_f32": (c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_p, ctypes.c_uint32, c_p]),
-    "svnet_xyzblock_fwd_f32": (c_int, [ctypes.POINTER(XyzBlockDesc), c_p]),
-    "svnet_xyzblock_coeffs_f32": (c_int, _block_coeffs([])),
-    "svnet_xyzblock_apply_f32": (c_int, _BLOCK_APPLY + [c_p]),
-    "svnet_xyzblock_apply_knn_f32": (c_int, _BLOCK_APPLY + [c_p, c_sz, c_p]),
-    "svnet_xyzblock_bwd_prelude_f32": (c_int, [c_p] * 8 + [c_i64, c_i64, c_i64, c_i64, c_f, c_p, c_p, c_p, c_p, c_p, c_i64, c_p, c_i64, c_p, c_p]),
-    "svnet_xyzblock_bwd_f32": (c_int, [ctypes.POINTER(XyzBlockBwdDesc), c_p]),
-    "svnet_xyzblock_tier": (c_int, [c_i64] * 3),
-    "svnet_binweight_i8_bytes": (c_sz, [c_i64, c_i64]),
-    "svnet_binweight_pack_i8": (c_int, [c_p, c_i64, c_i64, c_p, c_p]),
-    "svnet_binlinear_i8_fwd_f32": (c_int, [c_p, c_i64, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_p, c_p, c_p]),
-    "svnet_binlinear_i8_cloud_fwd_f32": (c_int, [c_p, c_i64, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_p]),
-    "svnet_v2s_fwd_f32": (c_int, [c_p, c_p, c_i64, c_i64, c_i64, c_p, c_p, c_p]),
-    "svnet_v2s_bwd_f32": (c_int, [c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_p, c_p, c_p]),
-    "svnet_v2s_cat_fwd_f32": (c_int, [c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_p, c_i64, c_p]),
-    "svnet_v2s_cat_sum_supported": (c_int, [c_i64, c_i64, c_i64, c_i64]),
-    "svnet_v2s_cat_sum_fwd_f32": (c_int, [c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_p, c_i64, c_p, c_i64, c_p]),
-    "svnet_v2s_bwd_ld_f32": (c_int, [c_p, c_p, c_p, c_i64, c_p, c_i64, c_i64, c_i64, c_p, c_p, c_p]),
-    "svnet_vproject_fwd_f32": (c_int, [c_p, c_p, c_i64, c_i64, c_i64, c_p, c_p]),
-    "svnet_vproject_bwd_f32": (c_int, [c_p, c_p, c_p, c_i64, c_i64, c_i64, c_p, c_p, c_p]),
-    "svnet_colstats_f64": (c_int, [c_p, c_i64, c_i64, c_int, c_p, c_p]),
-    "svnet_bn_finalize_f32": (c_int, [c_p, c_i64, c_i64, c_f, c_f, c_p, c_p, c_p, c_p, c_p, c_p]),
-    "svnet_bn_eval_stats_f32": (c_int, [c_p, c_p, c_i64, c_f, c_p, c_p, c_p]),
-    "svnet_bn_act_fwd_f32": (c_int, [c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_int, c_f, c_p, c_p]),
-    "svnet_bn_act_bwd_reduce_f32": (c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_int, c_f, c_p, c_p]),
-    "svnet_bn_act_bwd_apply_f32": (c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_int, c_f, c_int, c_p, c_p]),
-    "svnet_vbn_fwd_f32": (c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_p, c_p]),
-    "svnet_vbn_fwd_stats_f32": (c_int, [c_p, c_p, c_f, c_f, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_p, c_p]),
-    "svnet_vbn_bwd_reduce_f32": (c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_p, c_p, c_p]),
-    "svnet_vbn_bwd_apply_f32": (c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_int, c_p, c_p]),
-    "svnet_pool_workspace_bytes": (c_sz, [c_i64, c_i64, c_i64, c_int]),
-    "svnet_pool_fwd_f32": (c_int, [c_p, c_i64, c_i64, c_i64, c_int, c_p, c_i64, c_p, c_p, c_sz, c_p]),
-    "svnet_pool_maxmean_fwd_f32": (c_int, [c_p, c_i64, c_i64, c_i64, c_p, c_p, c_i64, c_p, c_p, c_sz, c_p]),
-    "svnet_bn_pool_fwd_f32": (c_int, [c_p] * 5 + [c_i64] * 3 + [c_int, c_f, c_p, c_p, c_i64, c_p, c_p, c_sz, c_int, c_p]),
-    "svnet_bn_pool_bwd_f32": (c_int, [c_p, c_p, c_i64] + [c_p] * 6 + [c_i64] * 3 + [c_int, c_f, c_int, c_p, c_p, c_p]),
-    "svnet_pool_bwd_f32": (c_int, [c_p, c_p, c_i64, c_i64, c_i64, c_int, c_p, c_p]),
-    "svnet_pool_mean_bwd_add_f32": (c_int, [c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_p, c_p]),
-    "svnet_pool_maxmean_bwd_f32": (c_int, [c_p, c_p, c_i64, c_p, c_i64, c_i64, c_i64, c_p, c_p]),
-    "svnet_vtail_workspace_bytes": (c_sz, [c_i64, c_i64, c_i64]),
-    "svnet_vtail_fwd_f32": (c_int, [c_p, c_p, c_f, c_f] + [c_p] * 9 + [c_i64] * 3 + [c_p, c_p, c_i64, c_p, c_p, c_sz, c_int, c_p]),
-    "svnet_vtail_bwd_f32": (c_int, [c_p] * 9 + [c_i64, c_p] + [c_i64] * 3 + [c_p] * 5),
-    "svnet_vtail_bwd_apply_f32": (c_int, [c_p] * 9 + [c_i64, c_p] + [c_i64] * 3 + [c_p, c_int, c_p, c_p]),
-    "svnet_act_fwd_f32": (c_int, [c_p, c_i64, c_int, c_p, c_p]),
-    "svnet_act_bwd_f32": (c_int, [c_p, c_p, c_i64, c_int, c_p, c_p]),
-    "svnet_gate_mlp_fwd_f32": (c_int, [c_p, c_p, c_p, c_f, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_i64, c_p]),
-    "svnet_gate_mlp_bwd_f32": (c_int, [c_p, c_p, c_p, c_p, c_f, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_f, c_p, c_p, c_p, c_p]),
-    "svnet_adam_step_f32": (c_int, [c_p, c_p, c_p, c_p, c_i64, c_f, c_f, c_f, c_f, c_f, c_i64, c_p]),
-    "svnet_sgd_step_f32": (c_int, [c_p, c_p, c_p, c_i64, c_f, c_f, c_f, c_int, c_p]),
-    "svnet_adam_step_dev_f32": (c_int, [c_p, c_p, c_p, c_p, c_i64, c_p, c_p]),
-    "svnet_sgd_step_dev_f32": (c_int, [c_p, c_p, c_p, c_i64, c_p, c_p]),
-    "svnet_smooth_ce_f32": (c_int, [c_p, c_p, c_i64, c_i64, c_f, c_p, c_p, c_p, c_i64, c_p]),
-    "svnet_kd_supported": (c_int, [c_int, c_i64, c_i64, c_i64]),
-    "svnet_kd_tier": (c_int, [c_int, c_i64, c_i64, c_i64]),
-    "svnet_kd_loss_f32": (c_int, [c_int, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_f, c_f, c_f, c_p, c_p, c_p, c_i64, c_p]),
-    "svnet_binhead_pack_f32": (c_int, [c_p, c_p, c_i64, c_i64, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
-    "svnet_binhead_fwd_f32": (c_int, [ctypes.POINTER(BinHeadDesc), c_p]),
-    "svnet_binhead_bwd_f32": (c_int, [ctypes.POINTER(BinHeadDesc), c_p]),
-    "svnet_fplinear_small_bwd_f32": (c_int, [c_p, c_p, c_p, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_p]),
-    "svnet_batch_supported": (c_int, [c_i64, c_i64, c_int]),
-    "svnet_batch_assemble_f32": (c_int, [ctypes.POINTER(BatchDesc), c_p]),
-    "svnet_fps_supported": (c_int, [c_i64, c_i64]),
-    "svnet_fps_tier": (c_int, [c_i64]),
-    "svnet_fps_f32": (c_int, [c_p, c_i64, c_i64, c_i64, c_p, c_p, c_p]),
-    "svnet_pool_gather_f32": (c_int, [c_p, c_p, c_p, c_i64, c_i64, c_i64, c_int, c_p, c_p, c_p]),
-    "svnet_propagate_supported": (c_int, [c_i64, c_i64, c_i64]),
-    "svnet_propagate_tile": (c_int, []),
-    "svnet_three_nn_f32": (c_int, [c_p, c_p, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_p]),
-    "svnet_three_interpolate_f32": (c_int, [c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_p, c_p]),
-    "svnet_group_supported": (c_int, [c_i64, c_i64, c_i64, c_i64]),
-    "svnet_ball_query_tile": (c_int, []),
-    "svnet_ball_query_f32": (c_int, [c_p, c_p, c_i64, c_i64, c_i64, c_f, c_i64, c_p, c_p, c_p]),
-    "svnet_group_points_f32": (c_int, [c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_p, c_p]),
-    "svnet_metrics_state_bytes": (c_sz, [c_i64]),
-    "svnet_metrics_workspace_bytes": (c_sz, [c_i64, c_i64, c_i64]),
-    "svnet_metrics_reset": (c_int, [c_p, c_i64, c_p, c_p, c_i64, c_p]),
-    "svnet_metrics_cls_f32": (c_int, [c_p, c_p, c_i64, c_i64, c_i64, c_f, c_p, c_p, c_sz, c_p]),
-    "svnet_metrics_seg_f32": (c_int, [c_p, c_p, c_p, c_i64, c_i64, c_i64, c_p, c_p, c_i64, c_i64, c_i64, c_f, c_p, c_p, c_p, c_i64, c_p, c_sz, c_p]),
-}
-
-
-EDGE_FWD_TWO = 1                     # SVNET_EDGE_FWD_TWO
-WGRAD_TERN5, WGRAD_AFF2 = 1, 2       # SVNET_WGRAD_TERN5 / SVNET_WGRAD_AFF2
-KD_ROWS, KD_CHANNEL_MAJOR = 0, 1     # SVNET_KD_ROWS / SVNET_KD_CHANNEL_MAJOR
-KD_WORKSPACE_FLOATS = 8192           # SVNET_KD_WORKSPACE_FLOATS
+SCALARS = {"int": c_int, "int64_t": c_i64, "float": c_f, "size_t": c_sz, "uint32_t": ctypes.c_uint32}     # every by-value type the header uses
 
 
 class SvnetHipError(RuntimeError):
     pass
+
+
+def _declare(text, structs, param):
+    """[(name, ctype)] of one declaration `TYPE a, *b`.  A pointer is a c_void_p, or POINTER(struct) for a parameter that points at a
+    parsed struct; a struct by value is a field only; anything else is a SCALARS entry or refused."""
+    m = re.fullmatch(r"\s*(?:const\s+)?(\w+(?: \w+)*?)\s*(\*?\s*\b\w+(?:\s*,\s*\*?\s*\w+)*)\s*", text)
+    if not m:
+        raise SvnetHipError("svnet_hip.h: cannot parse the declaration %r" % text.strip())
+    base, out = m.group(1), []
+    for star, name in re.findall(r"(\*?)\s*(\w+)", m.group(2)):
+        if star:
+            out.append((name, ctypes.POINTER(structs[base]) if param and base in structs else c_p))
+        elif base in SCALARS or (base in structs and not param):
+            out.append((name, SCALARS.get(base) or structs[base]))
+        else:
+            raise SvnetHipError("svnet_hip.h: no ctypes type for %r in %r" % (base, text.strip()))
+    return out
+
+
+def parse_header(text):
+    """(structs, signatures, defines) of a header in the dialect of include/svnet_hip.h: `typedef struct NAME { fields } NAME;`,
+    `RET svnet_name(ARGS);` and `#define NAME integer`.  It is no C parser: whatever else it meets it refuses, quoting the text."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    text = re.sub(r"#ifdef __cplusplus.*?#endif", " ", text, flags=re.S)
+    structs, signatures, defines = {}, {}, {}
+    for name, params, value in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(\w+)(\(?)[ \t]*(.*?)[ \t]*$", text, flags=re.M):
+        if value and not params:                                # (the include guard has no value, SVNET_SLICED_LEN(L) takes a parameter)
+            if not re.fullmatch(r"\d+|\(-\d+\)", value):
+                raise SvnetHipError("svnet_hip.h: #define %s %s is not an integer" % (name, value))
+            defines[name] = int(value.strip("()"))
+    text = re.sub(r"^[ \t]*#.*$", " ", text, flags=re.M)
+
+    def struct(m):
+        if m.group(1) != m.group(3) or re.search(r"[{\[(:]|\bunion\b", m.group(2)):
+            raise SvnetHipError("svnet_hip.h: cannot parse the struct %r" % m.group(0))
+        fields = [f for decl in m.group(2).split(";") if decl.strip() for f in _declare(decl, structs, False)]
+        structs[m.group(1)] = type(m.group(1), (ctypes.Structure,), {"_fields_": fields})
+        return " "
+
+    text = re.sub(r"\btypedef\s+struct\s+(\w+)\s*\{(.*?)\}\s*(\w+)\s*;", struct, text, flags=re.S)
+    for decl in filter(str.strip, text.split(";")):
+        m = re.fullmatch(r"\s*(?:(const\s+char\s*\*)|(\w+)\s)\s*(svnet_\w+)\s*\(([^()\[\]]*)\)\s*", decl)
+        if not m or not (m.group(1) or m.group(2) in SCALARS):
+            raise SvnetHipError("svnet_hip.h: cannot parse the declaration %r" % decl.strip())
+        args = [] if m.group(4).strip() == "void" else [_declare(a, structs, True)[0][1] for a in m.group(4).split(",")]
+        signatures[m.group(3)] = (ctypes.c_char_p if m.group(1) else SCALARS[m.group(2)], args)
+    return structs, signatures, defines
+
+
+# The header is the one statement of the ABI: struct layouts, name -> (restype, argtypes) of every entry point, and the constants.
+with open(HEADER_PATH) as _f:
+    STRUCTS, SIGNATURES, DEFINES = parse_header(_f.read())
+
+GemmDesc = STRUCTS["svnet_gemm_desc"]
+GateFwdJob = STRUCTS["svnet_gate_fwd_job"]
+GateBwdJob = STRUCTS["svnet_gate_bwd_job"]
+BlockTailDesc = STRUCTS["svnet_block_tail_desc"]
+EdgeBlockDesc = STRUCTS["svnet_edgeblock_desc"]
+EdgeBlockBwdDesc = STRUCTS["svnet_edgeblock_bwd_desc"]
+XyzBlockDesc = STRUCTS["svnet_xyzblock_desc"]
+XyzBlockBwdDesc = STRUCTS["svnet_xyzblock_bwd_desc"]
+BinHeadDesc = STRUCTS["svnet_binhead_desc"]
+BatchDesc = STRUCTS["svnet_batch_desc"]
+
+ABI_VERSION = DEFINES["SVNET_ABI_VERSION"]      # argument lists / buffer-length contracts of the header; lib() refuses a library built for another
+EDGE_FWD_TWO = DEFINES["SVNET_EDGE_FWD_TWO"]
+WGRAD_TERN5, WGRAD_AFF2 = DEFINES["SVNET_WGRAD_TERN5"], DEFINES["SVNET_WGRAD_AFF2"]
+KD_ROWS, KD_CHANNEL_MAJOR = DEFINES["SVNET_KD_ROWS"], DEFINES["SVNET_KD_CHANNEL_MAJOR"]
+KD_WORKSPACE_FLOATS = DEFINES["SVNET_KD_WORKSPACE_FLOATS"]
 
 
 def build(force=False, verbose=False):
@@ -321,13 +114,13 @@ def lib():
                 "%s is missing: run `python -c 'import __graft_entry__ as g; g.build()'` (or make -C svnet_amd/csrc). "
                 "svnet_amd has no CPU fallback." % LIB_PATH)
         handle = ctypes.CDLL(LIB_PATH)
+        if handle.svnet_version() != ABI_VERSION:               # a stale library: its entry points need not match the header's
+            raise SvnetHipError("%s was built for ABI %d, include/svnet_hip.h declares %d (SVNET_ABI_VERSION): rebuild it"
+                                % (LIB_PATH, handle.svnet_version(), ABI_VERSION))
         for name, (res, args) in SIGNATURES.items():
             fn = getattr(handle, name)
             fn.restype = res
             fn.argtypes = args
-        if handle.svnet_version() != ABI_VERSION:
-            raise SvnetHipError("%s was built for ABI %d, this binding speaks %d (include/svnet_hip.h SVNET_ABI_VERSION): rebuild it"
-                                % (LIB_PATH, handle.svnet_version(), ABI_VERSION))
         _lib = handle
     return _lib
 
@@ -401,6 +194,4 @@ def call(name, *args):
             t.pairs.append((a, b))
     else:
         rc = fn(*args)
-    if rc != 0:
-        msg = lib().svnet_last_error()
-        raise SvnetHipError("%s failed (%d): %s" % (name, rc, msg.decode() if msg else "?"))
+    check(rc, name)

@@ -12,7 +12,7 @@ from . import _lib, config
 from ._lib import BinHeadDesc, GemmDesc, call
 
 BN_EPS = 1e-5
-RED_SLICES = 16          # SVNET_RED_SLICES (include/svnet_hip.h): slices of the fused backward preludes' batch sums
+RED_SLICES = _lib.DEFINES["SVNET_RED_SLICES"]          # slices of the fused backward preludes' batch sums
 BN_MOMENTUM = 0.1
 
 # Test instrumentation (None in production): a dict {"knn": [], "signs": [], "pools": []} that records the DISCRETE decisions of a
@@ -2105,7 +2105,7 @@ class EdgeBlock(torch.autograd.Function):
         # every accumulator of this backward from ONE zero fill
         (red, redv, dgate, dWg0, dWg2, ds_acc, dv_acc, dzc, dbeta_perm, GXp, GXc, ovf_count) = _zeros_pool(
             dev, ((RED_SLICES * 2 * Os,), F), ((RED_SLICES * 2 * Ov,), F), ((B, Ov), F), ((H, 2 * Cs), F), ((Ov, H), F), ((P, Cs), F), ((P, 3, Cv), F),
-            ((P, 3, 3), F), ((64, 320), F), ((Os, 320), F), ((R, Cv), F), ((1,), torch.int32))        # dbeta_perm: SVNET_DBETA_SLICES x 320
+            ((P, 3, 3), F), ((_lib.DEFINES["SVNET_DBETA_SLICES"], 320), F), ((Os, 320), F), ((R, Cv), F), ((1,), torch.int32))
 
         # Two streams (forked / joined with events, so the pattern is captured into the hipGraph as parallel branches): the side
         # stream builds the reverse neighbour lists while the main stream runs the point-level prelude

@@ -65,8 +65,8 @@ import torch
 
 from . import _lib, _ops, _pointset, synth
 
-SELECT_MODES = {"first_shuffled": 0, "subset": 1, "first_ordered": 2}      # SVNET_BATCH_* (include/svnet_hip.h)
-ROTATE_MODES = {"none": 0, None: 0, "z": 1, "so3": 2}                      # SVNET_BATCH_ROTATE_*
+SELECT_MODES = {m: _lib.DEFINES["SVNET_BATCH_" + m.upper()] for m in ("first_shuffled", "subset", "first_ordered")}
+ROTATE_MODES = {m: _lib.DEFINES["SVNET_BATCH_ROTATE_" + (m or "none").upper()] for m in ("none", None, "z", "so3")}
 
 _U64 = np.uint64
 

@@ -24,7 +24,7 @@ from . import _lib, _ops
 SHAPENET_PARTS = ((0, 4, 6, 8, 12, 16, 19, 22, 24, 28, 30, 36, 38, 41, 44, 47),
                   (4, 2, 2, 4, 4, 3, 3, 2, 4, 2, 6, 2, 3, 3, 3, 3))
 
-CAT_EMPTY, CAT_INVALID = -1, -2        # SVNET_METRICS_CAT_* (include/svnet_hip.h)
+CAT_EMPTY, CAT_INVALID = _lib.DEFINES["SVNET_METRICS_CAT_EMPTY"], _lib.DEFINES["SVNET_METRICS_CAT_INVALID"]
 SMOOTHING_EPS = 0.2                    # utils.py:39
 
 

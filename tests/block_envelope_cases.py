@@ -16,10 +16,11 @@ from collections import OrderedDict
 import torch
 
 from oracle import sv_ref
+from svnet_amd._lib import DEFINES
 from tests.golden import cases as C
 from tests.golden import harness as H
 
-TWO = 1                 # SVNET_EDGE_FWD_TWO
+TWO = DEFINES["SVNET_EDGE_FWD_TWO"]
 OUT_RTOL = 1e-4         # outputs and running statistics (tests/common.py compare_case scaling)
 GRAD_RTOL = 1e-3        # gradients: the project's north-star tolerance (tests/test_hip_train_parity.py)
 MAX_EDGES = 25000       # every case stays at E = B*N*k below this: a few seconds at the most, float64 oracle included

@@ -32,7 +32,7 @@ def _knn(L, B, N, Cc, k, ws_bytes=None):
 def test_abi_refuses_past_the_extended_limits():
     from svnet_amd import _lib
     L = _lib.lib()
-    E_UNSUPPORTED = -2                       # (include/svnet_hip.h)
+    E_UNSUPPORTED = _lib.DEFINES["SVNET_E_UNSUPPORTED"]
     assert _knn(L, 1, 32769, 3, 20) == E_UNSUPPORTED
     msg = L.svnet_last_error().decode()
     assert "32768" in msg and "128" in msg
