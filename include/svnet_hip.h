@@ -45,9 +45,9 @@ int svnet_slices_sum_f64(double* buf, int64_t L, void* stream);
 
 /* ABI version = 100 * round-of-change + serial.  It changes whenever an entry point gains / loses an argument or a caller-owned buffer
  * changes its required length (200: sliced accumulators, SVNET_SLICED_LEN; 400: this header; 401: the totals of a sliced accumulator are
- * written by its consumer, svnet_slices_sum_*; 402: GX of svnet_v2s_bwd_*, gw of svnet_xyzblock_bwd_f32 and col_sum of svnet_gemm_f32 are sliced accumulators; 403: svnet_binweight_grad_f32 takes sliced inputs; 421: svnet_three_nn_f32, svnet_three_interpolate_f32; 422: svnet_ball_query_f32, svnet_group_points_f32; 423: svnet_vlinear_stats_f32 is gone; 424: svnet_edgeblock_fwd_tier, svnet_edgeblock_bwd_tier, svnet_edgeblock_wgrad_tier, svnet_xyzblock_tier).  svnet_version() returns the value the
+ * written by its consumer, svnet_slices_sum_*; 402: GX of svnet_v2s_bwd_*, gw of svnet_xyzblock_bwd_f32 and col_sum of svnet_gemm_f32 are sliced accumulators; 403: svnet_binweight_grad_f32 takes sliced inputs; 421: svnet_three_nn_f32, svnet_three_interpolate_f32; 422: svnet_ball_query_f32, svnet_group_points_f32; 423: svnet_vlinear_stats_f32 is gone; 424: svnet_edgeblock_fwd_tier, svnet_edgeblock_bwd_tier, svnet_edgeblock_wgrad_tier, svnet_xyzblock_tier; 425: svnet_pointset_reverse_i32, svnet_three_interpolate_bwd_f32, svnet_group_points_bwd_f32).  svnet_version() returns the value the
  * library was BUILT with: a caller compiled against another header must refuse to run (svnet_amd/_lib.py does).                   */
-#define SVNET_ABI_VERSION 424
+#define SVNET_ABI_VERSION 425
 int svnet_version(void);
 const char* svnet_last_error(void);
 
@@ -770,7 +770,7 @@ int svnet_pool_gather_f32(const float* data, const int64_t* seg, const int64_t* 
 
 /* ------------------------------------------------------------------ feature propagation: sampled points -> dense cloud
  * (models/utils/pointnet_util.py:281-308 PointNetFeaturePropagation.forward without its MLP: three nearest sampled points,
- * inverse-squared-distance weights, weighted sum).  Forward only.  Per cloud, query [P,3], ref [N,3], feat [D,N] (channel-first), fp32,
+ * inverse-squared-distance weights, weighted sum).  The gradient with respect to feat: svnet_three_interpolate_bwd_f32 below.  Per cloud, query [P,3], ref [N,3], feat [D,N] (channel-first), fp32,
  * every operation rounded once and never contracted into an fma, both divisions correctly rounded:
  *     d_c = fl(query[p,c] - ref[n,c]),  dist[p,n] = fl(fl(fl(d_0 d_0) + fl(d_1 d_1)) + fl(d_2 d_2))    (the difference form of svnet_fps_f32:
  *         never negative, exactly 0 at a coincident point; the reference's expanded form -2 q.r + |q|^2 + |r|^2 is NOT used)
@@ -793,7 +793,7 @@ int svnet_three_interpolate_f32(const float* feat, const int64_t* idx, const flo
                                 float* out, void* stream);
 
 /* ------------------------------------------------------------------ ball query and neighbourhood grouping: centres -> local groups
- * (models/utils/pointnet_util.py:87-107 query_ball_point, 110-143 sample_and_group without its sampling).  Forward only.  Per cloud,
+ * (models/utils/pointnet_util.py:87-107 query_ball_point, 110-143 sample_and_group without its sampling).  The gradient with respect to points: svnet_group_points_bwd_f32 below.  Per cloud,
  * xyz [N,3], new_xyz [S,3], points [N,D] (channel-last, or NULL with D = 0), fp32, every operation rounded once and never contracted:
  *     d_c = fl(new_xyz[s,c] - xyz[n,c]),  dist[s,n] = fl(fl(fl(d_0 d_0) + fl(d_1 d_1)) + fl(d_2 d_2))    (the difference form of svnet_fps_f32;
  *         the reference's expanded form -2 a.b + |a|^2 + |b|^2 is NOT used)
@@ -814,6 +814,35 @@ int svnet_ball_query_f32(const float* xyz, const float* new_xyz, int64_t B, int6
                          int* count, void* stream);
 int svnet_group_points_f32(const float* xyz, const float* new_xyz, const float* points, const int64_t* idx, int64_t B, int64_t N, int64_t S,
                            int64_t nsample, int64_t D, float* out, void* stream);
+
+/* ------------------------------------------------------------------ gradients of grouping and interpolation (autograd supplies them in the
+ * reference: models/utils/pointnet_util.py:166-207, 270-320).  Both are scatters; here each is a reverse list per destination and a
+ * per-destination sum in a fixed order.  No float atomic: two runs give the same bits.  Per cloud:
+ * svnet_pointset_reverse_i32: idx [R,K] int64 -> rev_start [N+1], rev_edge [R*K] int32.  Edge e = r K + j points to
+ *     n = idx[r,j] clamped into 0 .. N-1 (the clamp svnet_three_interpolate_f32 and svnet_group_points_f32 follow); nothing is skipped.
+ *     List n = rev_edge[rev_start[n] .. rev_start[n+1]) holds every edge that points to n exactly once, in ASCENDING e.  One launch,
+ *     no workspace, no atomics.  1 <= N <= 32768, 1 <= R * K <= 2^31 - 1, B * ceil(N / tile) <= 2^31 - 1; past that
+ *     SVNET_E_UNSUPPORTED.  svnet_pointset_reverse_supported (1 / 0, without the B term), svnet_pointset_reverse_tile (the
+ *     destinations one workgroup owns, a quarter of them per wave: the N at which a cloud takes a second workgroup) and
+ *     svnet_pointset_reverse_chunk (the edges per LDS chunk: the R * K at which the edge loop takes a second chunk) are pure host
+ *     functions.
+ * With the edges of list n e_1 < e_2 < ... and the terms t_i below: grad[n] = fl(fl(fl(t_1 + t_2) + t_3) + ...); one term gives t_1, an
+ * empty list +0.0, which is written.  Every product and sum is rounded once and never contracted.
+ * svnet_three_interpolate_bwd_f32: dout [B,D,P], weight [B,P,3], the reverse lists of idx [B,P,3] -> dfeat [B,D,N];
+ *     e_i = 3 p_i + j_i, t_i = fl(dout[d,p_i] weight[p_i,j_i]).  Slots past min(3, N) are ordinary edges (to point 0, weight 0).
+ *     No gradient goes to weight or to the coordinates.  1 <= D <= 524280.
+ * svnet_group_points_bwd_f32: dgrouped [B,S,nsample,3+D], the reverse lists of idx [B,S,nsample] -> dpoints [B,N,D];
+ *     t_i = dgrouped[s_i,j_i,3+c].  Padded slots and the slots of an empty group are ordinary edges.  Columns 0..2 (the gradients of
+ *     the coordinates) are not produced.  D >= 1.                                                                                   */
+int svnet_pointset_reverse_supported(int64_t R, int64_t K, int64_t N);
+int svnet_pointset_reverse_tile(void);
+int svnet_pointset_reverse_chunk(void);
+int svnet_pointset_reverse_i32(const int64_t* idx, int64_t B, int64_t R, int64_t K, int64_t N, int32_t* rev_start, int32_t* rev_edge,
+                               void* stream);
+int svnet_three_interpolate_bwd_f32(const float* dout, const float* weight, const int32_t* rev_start, const int32_t* rev_edge, int64_t B,
+                                    int64_t D, int64_t N, int64_t P, float* dfeat, void* stream);
+int svnet_group_points_bwd_f32(const float* dgrouped, const int32_t* rev_start, const int32_t* rev_edge, int64_t B, int64_t N, int64_t S,
+                               int64_t nsample, int64_t D, float* dpoints, void* stream);
 
 /* ------------------------------------------------------------------ epoch metrics (main_cls_dgcnn.py:187-251, main_partseg_dgcnn.py:185-279,
  * utils.py:68-91 calculate_shape_IoU; the accuracy scores of sklearn.metrics are functions of the confusion matrix)

@@ -3,7 +3,8 @@ propagation (svnet_amd/propagate.py), ball query and grouping (svnet_amd/group.p
 The device side of the same contract - the distance all three use, the LDS tile, the launch geometry - is svnet_amd/csrc/pointset.h.
 
 Here: the argument checks in the order every entry point applies them (tensors, then shapes, then - by _ops._hip - the HIP device,
-then the kernels' limits), the device refusal of the classes that allocate, the row gather, and the one launch of the sampler.
+then the kernels' limits), the device refusal of the classes that allocate, the row gather, the one launch of the sampler, and the
+reverse lists both backwards sum over (svnet_amd/csrc/pointset_grad.hip).
 """
 import torch
 
@@ -12,9 +13,11 @@ from . import _lib, _ops
 MAX_N = 32768       # SVNET_KNN_MAX_N (svnet_amd/csrc/common.h), for the messages: the library's *_supported queries are the check
 
 
-def check_tensors(name, tensors, dtypes, what):
-    """tensors: {argument name: tensor}; the type, dtype, device-match, contiguity and no-gradient checks shared by the entry points
-    (the HIP device itself is checked after the shapes, by _ops._hip).  `what` names the operation: "the grouping"."""
+def check_tensors(name, tensors, dtypes, what, grad=()):
+    """tensors: {argument name: tensor}; the type, dtype, device-match, contiguity and gradient checks shared by the entry points
+    (the HIP device itself is checked after the shapes, by _ops._hip).  `what` names the operation: "the grouping".  `grad` names
+    the arguments that may require grad - the data tensors whose backward exists, on a HIP device; coordinates, weights and indices
+    never may.  Returns whether one of them does."""
     for k, t in tensors.items():
         if not isinstance(t, torch.Tensor):
             raise TypeError("%s: %s must be a tensor, got %s" % (name, k, type(t).__name__))
@@ -27,8 +30,11 @@ def check_tensors(name, tensors, dtypes, what):
             raise ValueError("%s: %s on %s, %s on %s" % (name, next(iter(tensors)), first.device, k, t.device))
         if not t.is_contiguous():
             raise ValueError("%s: %s must be contiguous" % (name, k))
-        if t.requires_grad:
-            raise ValueError("%s: %s requires grad - %s is forward only" % (name, k, what))
+        if t.requires_grad and k not in grad:
+            raise ValueError("%s: %s requires grad - %s is forward only in %s" % (name, k, what, k))
+        if t.requires_grad and t.device.type != "cuda":
+            raise ValueError("%s: %s requires grad on %s - off a HIP device %s is forward only" % (name, k, t.device, what))
+    return any(tensors[k].requires_grad for k in grad if k in tensors)
 
 
 def check_cloud(name, arg, t, letter):
@@ -78,3 +84,34 @@ def fps_launch(xyz, B, P, npoint, start, idx):
     A start outside 0 .. P-1 is clamped into the cloud by the kernel; callers that refuse it check before."""
     with torch.cuda.device(xyz.device):
         _lib.call("svnet_fps_f32", _ops._p(xyz), B, P, npoint, _ops._p(start), _ops._p(idx), _ops._stream())
+
+
+def reverse_supported(name, R, K, N):
+    if not _lib.lib().svnet_pointset_reverse_supported(R, K, N):
+        raise _lib.SvnetHipError("%s: a [%d,%d] index table into N = %d points is not supported (1 <= N <= %d, 1 <= R * K <= 2^31 - 1)"
+                                 % (name, R, K, N, MAX_N))
+
+
+def reverse_tile():
+    """Destinations one workgroup of the reverse-list builder owns (a quarter of them per wave): the N past which a cloud takes a
+    second workgroup."""
+    return int(_lib.lib().svnet_pointset_reverse_tile())
+
+
+def reverse_chunk():
+    """Edges per LDS chunk of the reverse-list builder: the R * K past which its edge loop takes a second chunk."""
+    return int(_lib.lib().svnet_pointset_reverse_chunk())
+
+
+def reverse_lists(idx, N):
+    """idx [B,R,K] int64 on a HIP device with targets in [0, N) (clamped into it, as the forward kernels do) -> (rev_start [B,N+1],
+    rev_edge [B,R*K]) int32: per cloud, rev_edge[rev_start[n] : rev_start[n+1]] are the edges e = r K + j that point to n, in
+    ascending e; nothing is skipped.  One launch on the current stream, no host read: capturable."""
+    B, R, K = (int(v) for v in idx.shape)
+    N = int(N)
+    reverse_supported("reverse_lists", R, K, N)
+    rev_start = torch.empty(B, N + 1, dtype=torch.int32, device=idx.device)
+    rev_edge = torch.empty(B, R * K, dtype=torch.int32, device=idx.device)
+    with torch.cuda.device(idx.device):
+        _lib.call("svnet_pointset_reverse_i32", _ops._p(idx), B, R, K, N, _ops._p(rev_start), _ops._p(rev_edge), _ops._stream())
+    return rev_start, rev_edge

@@ -36,8 +36,18 @@ rounding to fp32.
 On lattice coordinates the whole contract equals the reference's CPU result bit for bit (tests/golden/group.npz; tests/group_ref.py
 restates the contract in numpy).
 
-Forward only: the first set-abstraction level groups data, not activations; the functions take no gradient and build no autograd
-graph.  There is no CPU fallback: tensors that are not on a HIP device raise.  Limits: 1 <= nsample <= N <= 32768 (the reference
+Gradients: `points` may require grad in group_points(), sample_and_group() and sample_and_group_all() - a second set-abstraction
+level groups activations.  The grouping then goes through a torch.autograd.Function whose backward is group_points_backward()
+(svnet_amd/csrc/pointset_grad.hip):
+
+    backward    with the edges e = s nsample + j that point to n (idx clamped as the forward clamps it) in ascending e,
+                e_1 < e_2 < ..., and t_i = dgrouped[s_i,j_i,3+c]:   dpoints[n,c] = fl(fl(fl(t_1 + t_2) + t_3) + ...); one term gives
+                t_1, no term +0.  Padded slots and the slots of an empty group are edges like any other.  A fixed order and no
+                float atomic: two runs give the same bits (tests/pointset_grad_ref.py restates it).
+
+Coordinates are data: columns 0..2 of the upstream gradient go nowhere, and xyz, new_xyz or idx that require grad are refused, as is
+`out=` beside points that require grad.  `Grouper` stays forward only.  There is no CPU fallback: tensors that are not on a HIP
+device raise.  Limits: 1 <= nsample <= N <= 32768 (the reference
 silently returns N columns when nsample > N; here it is refused), S >= 1, D >= 0, B * ceil(S / 32) <= 2^31 - 1 for the query and
 B * S * nsample <= 2^31 - 1 for the grouping; `sample_and_group` also has farthest point sampling's N <= 16384.
 """
@@ -109,9 +119,29 @@ def query_ball_point(radius, nsample, xyz, new_xyz, return_count=False):
     return (idx, count) if return_count else idx
 
 
+class _Group(torch.autograd.Function):
+    """The grouping launch for points that require grad, and group_points_backward as its backward (current stream, no host read:
+    capturable).  xyz, new_xyz and idx get no gradient."""
+
+    @staticmethod
+    def forward(ctx, points, xyz, new_xyz, idx):
+        (B, N, D), S, nsample = points.shape, idx.shape[1], idx.shape[2]
+        out = torch.empty(B, S, nsample, 3 + D, dtype=torch.float32, device=xyz.device)
+        _group_launch(xyz, new_xyz, points, idx, B, N, S, nsample, D, out)
+        ctx.save_for_backward(idx)
+        ctx.N = N
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dgrouped):
+        idx, = ctx.saved_tensors
+        return group_points_backward(dgrouped.contiguous(), idx, ctx.N), None, None, None
+
+
 def _group_args(name, xyz, new_xyz, idx, points):
     tensors, dtypes = _with_points({"xyz": xyz, "new_xyz": new_xyz, "idx": idx}, [torch.float32, torch.float32, torch.int64], points)
-    _pointset.check_tensors(name, tensors, dtypes, _WHAT)
+    _pointset.check_tensors(name, tensors, dtypes, _WHAT, grad=("points",))
     B, N, S = _cloud_shapes(name, xyz, new_xyz)
     if idx.dim() != 3 or idx.shape[0] != B or idx.shape[1] != S:
         raise ValueError("%s: idx must be [B,S,nsample] with B = %d, S = %d, got %s" % (name, B, S, tuple(idx.shape)))
@@ -122,15 +152,41 @@ def _group_args(name, xyz, new_xyz, idx, points):
 def group_points(xyz, new_xyz, idx, points=None, out=None):
     """xyz [B,N,3], new_xyz [B,S,3], idx [B,S,nsample] int64, points [B,N,D] or None -> [B,S,nsample,3+D]: the centred coordinates
     of every group's points followed by their attributes (module docstring).  An index outside [0, N) is clamped into it.  One
-    launch, no host read; `out` lets a caller keep a fixed buffer.  No gradient."""
+    launch, no host read; `out` lets a caller keep a fixed buffer.  points may require grad (module docstring); the rest may not."""
     B, N, S, nsample, D = _group_args("group_points", xyz, new_xyz, idx, points)
     _ops._hip(xyz, new_xyz, idx, points)
     _supported("group_points", N, S, nsample, D)
+    if D and points.requires_grad:
+        if out is not None:
+            raise ValueError("group_points: out= beside points that require grad - autograd owns the result of a differentiable call")
+        return _Group.apply(points, xyz, new_xyz, idx)
     if out is None:
         out = torch.empty(B, S, nsample, 3 + D, dtype=torch.float32, device=xyz.device)
     else:
         _pointset.check_out("group_points", {"xyz": xyz}, out, "[B,S,nsample,3+D]", (B, S, nsample, 3 + D), _WHAT)
     _group_launch(xyz, new_xyz, points, idx, B, N, S, nsample, D, out)
+    return out
+
+
+def group_points_backward(dgrouped, idx, N, out=None):
+    """The gradient of group_points with respect to points: dgrouped [B,S,nsample,3+D] float32 (D >= 1), idx [B,S,nsample] int64 ->
+    dpoints [B,N,D], the ordered sums of the module docstring.  Two launches on the current stream (the reverse lists of idx, the
+    sums), no host read; `out` lets a caller keep a fixed buffer.  Every element of dpoints is written, an empty list as +0."""
+    _pointset.check_tensors("group_points_backward", {"dgrouped": dgrouped, "idx": idx}, (torch.float32, torch.int64), _WHAT)
+    if idx.dim() != 3 or idx.shape[0] < 1 or dgrouped.dim() != 4 or tuple(dgrouped.shape[:3]) != tuple(idx.shape) or dgrouped.shape[3] < 4:
+        raise ValueError("group_points_backward: dgrouped must be [B,S,nsample,3+D] with D >= 1 and idx [B,S,nsample], got %s and %s"
+                         % (tuple(dgrouped.shape), tuple(idx.shape)))
+    B, S, nsample, D, N = int(idx.shape[0]), int(idx.shape[1]), int(idx.shape[2]), int(dgrouped.shape[3]) - 3, int(N)
+    _ops._hip(dgrouped, idx)
+    _pointset.reverse_supported("group_points_backward", S, nsample, N)
+    if out is None:
+        out = torch.empty(B, N, D, dtype=torch.float32, device=dgrouped.device)
+    else:
+        _pointset.check_out("group_points_backward", {"dgrouped": dgrouped}, out, "[B,N,D]", (B, N, D), _WHAT)
+    rev_start, rev_edge = _pointset.reverse_lists(idx, N)
+    with torch.cuda.device(dgrouped.device):
+        _lib.call("svnet_group_points_bwd_f32", _ops._p(dgrouped), _ops._p(rev_start), _ops._p(rev_edge), B, N, S, nsample, D, _ops._p(out),
+                  _ops._stream())
     return out
 
 
@@ -140,12 +196,12 @@ def sample_and_group(npoint, radius, nsample, xyz, points, returnfps=False, star
     Farthest point sampling -> gather of the centres -> ball query -> grouping, on the current stream with no host read between them.
     The reference's torch.randint start is an input, as in data.farthest_point_sample: `start` [B] int64 (a start outside 0 .. N-1 is
     clamped into the cloud by the sampling kernel), or None for data.fps_start(seed, B, N), which is copied from the host: a caller
-    that captures the call into a HIP graph passes a device tensor.  No gradient."""
+    that captures the call into a HIP graph passes a device tensor.  points may require grad (module docstring); xyz may not."""
     tensors, dtypes = _with_points({"xyz": xyz}, [torch.float32], points)
     if start is not None and isinstance(start, torch.Tensor):
         tensors["start"] = start
         dtypes.append(torch.int64)
-    _pointset.check_tensors("sample_and_group", tensors, dtypes, _WHAT)
+    _pointset.check_tensors("sample_and_group", tensors, dtypes, _WHAT, grad=("points",))
     B, N = _pointset.check_cloud("sample_and_group", "xyz", xyz, "N")
     S, nsample = int(npoint), int(nsample)
     D = 0 if points is None else _points_shape("sample_and_group", points, B, N)
@@ -164,9 +220,12 @@ def sample_and_group(npoint, radius, nsample, xyz, points, returnfps=False, star
     new_xyz = _pointset.gather_rows(xyz, fps_idx).contiguous()
     idx = torch.empty(B, S, nsample, dtype=torch.int64, device=dev)
     count = torch.empty(B, S, dtype=torch.int32, device=dev)
-    new_points = torch.empty(B, S, nsample, 3 + D, dtype=torch.float32, device=dev)
     _query_launch(xyz, new_xyz, B, N, S, _r2(radius), nsample, idx, count)
-    _group_launch(xyz, new_xyz, points, idx, B, N, S, nsample, D, new_points)
+    if D and points.requires_grad:
+        new_points = _Group.apply(points, xyz, new_xyz, idx)
+    else:
+        new_points = torch.empty(B, S, nsample, 3 + D, dtype=torch.float32, device=dev)
+        _group_launch(xyz, new_xyz, points, idx, B, N, S, nsample, D, new_points)
     if not returnfps:
         return new_xyz, new_points
     grouped_xyz = _pointset.gather_rows(xyz, idx.view(B, S * nsample)).view(B, S, nsample, 3)
@@ -175,8 +234,9 @@ def sample_and_group(npoint, radius, nsample, xyz, points, returnfps=False, star
 
 def sample_and_group_all(xyz, points):
     """The reference's trivial form: one group of all N points around centre 0, in order.  xyz [B,N,3], points [B,N,D] or None ->
-    (new_xyz [B,1,3] of zeros, new_points [B,1,N,3+D]).  torch views and one cat."""
-    _pointset.check_tensors("sample_and_group_all", *_with_points({"xyz": xyz}, [torch.float32], points), _WHAT)
+    (new_xyz [B,1,3] of zeros, new_points [B,1,N,3+D]).  torch views and one cat, so torch's own autograd carries the gradient of
+    points, which may require grad; xyz may not."""
+    _pointset.check_tensors("sample_and_group_all", *_with_points({"xyz": xyz}, [torch.float32], points), _WHAT, grad=("points",))
     B, N = _pointset.check_cloud("sample_and_group_all", "xyz", xyz, "N")
     if points is not None:
         _points_shape("sample_and_group_all", points, B, N)

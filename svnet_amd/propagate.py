@@ -30,7 +30,15 @@ The contract, for one cloud: queries q [P,3], sampled points r [N,3], features f
 On coordinates whose squares and products are exact in fp32 the two distance forms agree bit for bit, and there the whole contract
 equals the reference's CPU result bit for bit (tests/golden/propagate.npz; tests/propagate_ref.py restates the contract in numpy).
 
-Forward only: the functions take no gradient and build no autograd graph.  There is no CPU fallback: tensors that are not on a
+Gradients: `feat` may require grad in three_interpolate() and propagate(); the call then goes through a torch.autograd.Function
+whose backward is three_interpolate_backward() (svnet_amd/csrc/pointset_grad.hip), the adjoint of `values` above:
+
+    backward    with the edges e = 3 p + j that point to n (idx clamped as the forward clamps it) in ascending e, e_1 < e_2 < ...,
+                and t_i = fl(dout[d,p_i] w[p_i,j_i]):   dfeat[d,n] = fl(fl(fl(t_1 + t_2) + t_3) + ...); one term gives t_1, no term
+                +0.  A fixed order and no float atomic: two runs give the same bits (tests/pointset_grad_ref.py restates it).
+
+Coordinates are data: no gradient goes to query, ref or weight, and a coordinate, weight or index that requires grad is refused, as
+is `out=` beside a feat that requires grad.  The classes stay forward only.  There is no CPU fallback: tensors that are not on a
 HIP device raise.  Limits: 1 <= N <= 32768 (the k-NN's limit), P >= 1, D >= 1, B * ceil(P / 256) <= 2^31 - 1.
 """
 import torch
@@ -94,34 +102,93 @@ def _out_buffer(name, out, feat, B, D, P):
     return out
 
 
+def _no_out_with_grad(name, arg, out):
+    if out is not None:
+        raise ValueError("%s: out= beside a %s that requires grad - autograd owns the result of a differentiable call" % (name, arg))
+
+
+class _Interpolate(torch.autograd.Function):
+    """three_interpolate for a feat that requires grad: the forward launch, and three_interpolate_backward as its backward (current
+    stream, no host read: capturable).  idx and weight get no gradient."""
+
+    @staticmethod
+    def forward(ctx, feat, idx, weight):
+        B, D, N, P = _interp_shapes("three_interpolate", feat, idx, weight)
+        out = torch.empty(B, D, P, dtype=torch.float32, device=feat.device)
+        _interp_launch(feat, idx, weight, B, D, N, P, out)
+        ctx.save_for_backward(idx, weight)
+        ctx.N = N
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dout):
+        idx, weight = ctx.saved_tensors
+        return three_interpolate_backward(dout.contiguous(), idx, weight, ctx.N), None, None
+
+
 def three_interpolate(feat, idx, weight, out=None):
     """feat [B,D,N] float32, idx [B,P,3] int64, weight [B,P,3] float32 -> [B,D,P]: out[b,d,p] = sum_j feat[b,d,idx[b,p,j]] weight[b,p,j]
-    in the contract's order.  An index outside [0, N) is clamped into it.  One launch, no host read; no gradient."""
-    _pointset.check_tensors("three_interpolate", {"feat": feat, "idx": idx, "weight": weight}, (torch.float32, torch.int64, torch.float32), _WHAT)
+    in the contract's order.  An index outside [0, N) is clamped into it.  One launch, no host read.  feat may require grad (module
+    docstring); idx and weight may not."""
+    grad = _pointset.check_tensors("three_interpolate", {"feat": feat, "idx": idx, "weight": weight},
+                                   (torch.float32, torch.int64, torch.float32), _WHAT, grad=("feat",))
     B, D, N, P = _interp_shapes("three_interpolate", feat, idx, weight)
     _ops._hip(feat, idx, weight)
     _supported("three_interpolate", P, N, D)
+    if grad:
+        _no_out_with_grad("three_interpolate", "feat", out)
+        return _Interpolate.apply(feat, idx, weight)
     out = _out_buffer("three_interpolate", out, feat, B, D, P)
     _interp_launch(feat, idx, weight, B, D, N, P, out)
+    return out
+
+
+def three_interpolate_backward(dout, idx, weight, N, out=None):
+    """The gradient of three_interpolate with respect to feat: dout [B,D,P] float32, idx [B,P,3] int64, weight [B,P,3] float32 ->
+    dfeat [B,D,N], the ordered sums of the module docstring.  Two launches on the current stream (the reverse lists of idx, the
+    sums), no host read; `out` lets a caller keep a fixed buffer.  Every element of dfeat is written, an empty list as +0."""
+    _pointset.check_tensors("three_interpolate_backward", {"dout": dout, "idx": idx, "weight": weight},
+                            (torch.float32, torch.int64, torch.float32), _WHAT)
+    B, D, P, _ = _interp_shapes("three_interpolate_backward", dout, idx, weight)
+    N = int(N)
+    if idx.shape[1] != P:
+        raise ValueError("three_interpolate_backward: dout must be [B,D,P] with P = %d, got %s" % (idx.shape[1], tuple(dout.shape)))
+    _ops._hip(dout, idx, weight)
+    _supported("three_interpolate_backward", P, N, D)
+    _pointset.reverse_supported("three_interpolate_backward", P, 3, N)
+    if out is None:
+        out = torch.empty(B, D, N, dtype=torch.float32, device=dout.device)
+    else:
+        _pointset.check_out("three_interpolate_backward", {"dout": dout}, out, "[B,D,N]", (B, D, N), _WHAT)
+    rev_start, rev_edge = _pointset.reverse_lists(idx, N)
+    with torch.cuda.device(dout.device):
+        _lib.call("svnet_three_interpolate_bwd_f32", _ops._p(dout), _ops._p(weight), _ops._p(rev_start), _ops._p(rev_edge), B, D, N, P,
+                  _ops._p(out), _ops._stream())
     return out
 
 
 def propagate(query, ref, feat, out=None):
     """three_nn(query, ref) then three_interpolate(feat, ...): feat [B,D,N] at the points ref [B,N,3] -> [B,D,P] at query [B,P,3].
     Two launches on the current stream, no host read and no synchronisation, so it can be captured in a HIP graph; `out` lets a
-    caller keep a fixed buffer.  No gradient."""
-    _pointset.check_tensors("propagate", {"query": query, "ref": ref, "feat": feat}, (torch.float32,) * 3, _WHAT)
+    caller keep a fixed buffer.  feat may require grad (module docstring); query and ref may not."""
+    grad = _pointset.check_tensors("propagate", {"query": query, "ref": ref, "feat": feat}, (torch.float32,) * 3, _WHAT, grad=("feat",))
     B, P, N = _nn_shapes("propagate", query, ref)
     if feat.dim() != 3 or feat.shape[0] != B or feat.shape[2] != N:
         raise ValueError("propagate: feat must be [B,D,N] with B = %d, N = %d, got %s" % (B, N, tuple(feat.shape)))
     D = int(feat.shape[1])
     _ops._hip(query, ref, feat)
     _supported("propagate", P, N, D)
-    out = _out_buffer("propagate", out, feat, B, D, P)
+    if grad:
+        _no_out_with_grad("propagate", "feat", out)
+    else:
+        out = _out_buffer("propagate", out, feat, B, D, P)
     idx = torch.empty(B, P, 3, dtype=torch.int64, device=query.device)
     dist3 = torch.empty(B, P, 3, dtype=torch.float32, device=query.device)
     weight = torch.empty(B, P, 3, dtype=torch.float32, device=query.device)
     _nn_launch(query, ref, B, P, N, idx, dist3, weight)
+    if grad:
+        return _Interpolate.apply(feat, idx, weight)
     _interp_launch(feat, idx, weight, B, D, N, P, out)
     return out
 
