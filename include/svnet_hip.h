@@ -45,9 +45,9 @@ int svnet_slices_sum_f64(double* buf, int64_t L, void* stream);
 
 /* ABI version = 100 * round-of-change + serial.  It changes whenever an entry point gains / loses an argument or a caller-owned buffer
  * changes its required length (200: sliced accumulators, SVNET_SLICED_LEN; 400: this header; 401: the totals of a sliced accumulator are
- * written by its consumer, svnet_slices_sum_*; 402: GX of svnet_v2s_bwd_*, gw of svnet_xyzblock_bwd_f32 and col_sum of svnet_gemm_f32 are sliced accumulators; 403: svnet_binweight_grad_f32 takes sliced inputs; 421: svnet_three_nn_f32, svnet_three_interpolate_f32; 422: svnet_ball_query_f32, svnet_group_points_f32; 423: svnet_vlinear_stats_f32 is gone; 424: svnet_edgeblock_fwd_tier, svnet_edgeblock_bwd_tier, svnet_edgeblock_wgrad_tier, svnet_xyzblock_tier; 425: svnet_pointset_reverse_i32, svnet_three_interpolate_bwd_f32, svnet_group_points_bwd_f32).  svnet_version() returns the value the
+ * written by its consumer, svnet_slices_sum_*; 402: GX of svnet_v2s_bwd_*, gw of svnet_xyzblock_bwd_f32 and col_sum of svnet_gemm_f32 are sliced accumulators; 403: svnet_binweight_grad_f32 takes sliced inputs; 421: svnet_three_nn_f32, svnet_three_interpolate_f32; 422: svnet_ball_query_f32, svnet_group_points_f32; 423: svnet_vlinear_stats_f32 is gone; 424: svnet_edgeblock_fwd_tier, svnet_edgeblock_bwd_tier, svnet_edgeblock_wgrad_tier, svnet_xyzblock_tier; 425: svnet_pointset_reverse_i32, svnet_three_interpolate_bwd_f32, svnet_group_points_bwd_f32; 426: wbt of svnet_edgeblock_wbt_bf16 is 512 values longer, the all-zero fragment).  svnet_version() returns the value the
  * library was BUILT with: a caller compiled against another header must refuse to run (svnet_amd/_lib.py does).                   */
-#define SVNET_ABI_VERSION 425
+#define SVNET_ABI_VERSION 426
 int svnet_version(void);
 const char* svnet_last_error(void);
 
@@ -297,7 +297,7 @@ typedef struct svnet_edgeblock_bwd_desc {
     int Cs, Cv, Os, Ov;
     const float* v; const int64_t* idx; const float* zz; const float* ut;
     const int16_t* n16; const uint64_t* planes;   /* kept by svnet_edgeblock_fwd_f32 */
-    const uint16_t* w1bt;        /* svnet_edgeblock_wbt_bf16: sign(W1) as bf16 MFMA fragments, 320 * 16*ceil(Os/16) values */
+    const uint16_t* w1bt;        /* svnet_edgeblock_wbt_bf16: sign(W1) as bf16 MFMA fragments, 320 * 16*ceil(Os/16) + 512 values */
     const float* scale1;
     const uint8_t* slot_max; const uint8_t* slot_min;
     const float* coef;           /* from svnet_edgeblock_coeffs_f32 */
@@ -314,7 +314,8 @@ typedef struct svnet_edgeblock_bwd_desc {
     int parts;                   /* 0 or 3: both kernels; 1: vector path only (dvc, ub_tab, ge_tab); 2: scalar/tile path only.  The two
                                     are independent, so a caller may issue them on two streams                                   */
 } svnet_edgeblock_bwd_desc;
-/* wbt: 320 * 16*ceil(Os/16) bf16 values, [column tile (10)][k-step][lane (64)][8] (the tile kernel's B-fragment order) */
+/* wbt: 320 * 16*ceil(Os/16) + 512 bf16 values, [column tile (10)][k-step][lane (64)][8] (the tile kernel's B-fragment order), then ONE
+ * all-zero fragment [lane (64)][8]: what a wave without a column tile, and the second k-step of Os = 8 / 16, read                          */
 /* w_dense (may be NULL; then Cs / Cv are unused): one uint32, set to 1 when the planes show no zero weight among the columns in use
  * (Cs bits of words 0 - 1, 2 Cv bits of words 2 - 4), else 0 - see svnet_edgeblock_desc                                                   */
 int svnet_edgeblock_wbt_bf16(const uint64_t* w_sign, const uint64_t* w_nz, int64_t Os, int64_t Cs, int64_t Cv, uint16_t* wbt,

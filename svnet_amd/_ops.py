@@ -2006,7 +2006,7 @@ class EdgeBlock(torch.autograd.Function):
         def build():
             out = {"wv": torch.empty((2 * Ov + 6, Cv), **f32), "scv": torch.empty((2 * Ov + 6,), **f32),
                    "w_sign": torch.empty((Os, 5), dtype=torch.int64, device=dev), "w_nz": torch.empty((Os, 5), dtype=torch.int64, device=dev),
-                   "beta_perm": torch.empty((5 * 64,), **f32), "wbt": torch.empty((320 * ((Os + 15) // 16 * 16),), dtype=torch.int16, device=dev),
+                   "beta_perm": torch.empty((5 * 64,), **f32), "wbt": torch.empty((320 * ((Os + 15) // 16 * 16) + 512,), dtype=torch.int16, device=dev),
                    "w_dense": torch.zeros((1,), dtype=torch.int32, device=dev)}       # 1 = no exact zero in W1 (svnet_edgeblock_wbt_bf16 sets it from the planes)
 
             def rebuild():                       # (holds the parameters weakly: a dead model's entry is dropped by _PlaneCache._stale())

@@ -10,10 +10,13 @@
 //   edgeblock_bwd_vec_kernel (wave per point): the whole vector path; dv' scattered to dU with float atomics (contiguous
 //            row segments), the centre sums written once per point;
 //   edgeblock_bwd_kernel (workgroup = 4 waves = one tile of 32 consecutive edge rows):
+//     requests: everything phase A reads goes out first, from wave-uniform bases + 32-bit lane offsets, ahead of the tile's position
+//              arithmetic;
 //     phase A (elementwise, coalesced): dL/dy_pre from n -> HBM (operand of the weight-gradient GEMM) and LDS; planes -> LDS
 //              -> row-sliced 32-bit halves in HBM (the other operand);
 //     phase B (MFMA): dx_b[32 x 320] = dy[32 x Os] . sign(W1)[Os x 320] on v_mfma_f32_32x32x16_bf16, exact 3-way split
-//              of dy, STE mask applied from the LDS planes, result to LDS;
+//              of dy, STE mask applied from the LDS planes, result to LDS; the weight fragments come through unconditional loads
+//              (an all-zero fragment stands in for a column tile a wave does not have), two or three tile slots per wave;
 //     phase C (lanes = channels): beta / s / v2s backward, scatter-add to the point tables.
 // The weight gradient GX = dy^T . x_b is left to mfma_tn_kernel (gemm_mfma.hip) on the dn_out + planes this kernel
 // writes (4 B + 0.25 B per edge-channel instead of the 4 B fp32 input the layer-wise path keeps).
@@ -50,6 +53,13 @@ namespace {
 #endif
 
 typedef __attribute__((ext_vector_type(16))) float f32x16;
+
+// common.h's ld_f32_sbase for any element type (8- and 16-byte vectors included): wave-uniform `base` + per-lane BYTE offset,
+// loaded with the SGPR-base addressing mode
+template <typename T>
+__device__ __forceinline__ T ld_sbase(const void* base, uint32_t byte_off) {
+    return *reinterpret_cast<const T*>(reinterpret_cast<const char*>(base) + keep_here(byte_off));
+}
 
 // bf16 pieces of dL/dn that phase B of the tile kernel multiplies: 3 = the exact split (fp32-exact products); 2 = hi + mid only (a relative
 // 2^-16 cut of every dL/dn entry: measured this round as an A/B build)
@@ -99,14 +109,14 @@ __global__ void edgeblock_wbt_kernel(const uint64_t* __restrict__ w_sign, const 
         if (threadIdx.x == 0) *w_dense = bad == 0ull ? 1u : 0u;
     }
     const int nks = (Os + 15) >> 4;
-    const int total = (NCOL / 32) * nks * 512;
+    const int total = (NCOL / 32 * nks + 1) * 512;          // (+ the all-zero fragment behind the ten column tiles)
     for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < total; e += gridDim.x * blockDim.x) {
         const int j = e & 7, ln = (e >> 3) & 63, rest = e >> 9;
         const int ct = rest / nks, ks = rest - ct * nks;
         const int col = ct * 32 + (ln & 31), o = ks * 16 + 8 * (ln >> 5) + j;
         const int w = col >> 6, b = col & 63;
         uint16_t val = 0;
-        if (o < Os) {
+        if (o < Os && ct < NCOL / 32) {
             const uint64_t nz = w_nz[o * NW + w], sg = w_sign[o * NW + w];
             val = ((nz >> b) & 1ull) ? (((sg >> b) & 1ull) ? 0x3F80 : 0xBF80) : 0;
         }
@@ -427,8 +437,15 @@ _Pragma("unroll") \
 //  prologue lie under the next tile's phase A - was built this round and not kept: whatever form the loop took (by-value descriptor,
 //  descriptor re-read through an opaque kernarg offset) the allocator kept 56 .. 382 registers live across the back edge and spilled
 //  them; as a non-inlined function the callee-saved registers went to scratch twice per tile.)
+// Waves per SIMD the tile kernel is compiled for.  The kernel is a latency chain, so tiles in flight are what shortens it.  With two
+// column-tile slots per wave (NC2 = 20 / 24, see NQ below) the Os <= 32 form needs 68 registers and the Os = 64 form 94 - 95, without
+// scratch, and their 19.8 KB of LDS leave room for eight workgroups per CU: the bounds hold them at six and five waves (a forced bound
+// on the three-slot kernel spilled 24 / 92 bytes per lane and lost 0.02 / 0.13 ms of the step).  Everything else stays at four: Os = 128
+// is at four by its 36.5 KB of LDS as well.
+constexpr int tile_waves(int NKS, int NC2) { return (NC2 != 20 && NC2 != 24) ? 4 : NKS == 2 ? 6 : NKS == 4 ? 5 : 4; }
+
 template <int MODE, int NKS, int NC2 = 0>
-__global__ __launch_bounds__(256, 4) void edgeblock_bwd_kernel(svnet_edgeblock_bwd_desc d) {
+__global__ __launch_bounds__(256, tile_waves(NKS, NC2)) void edgeblock_bwd_kernel(svnet_edgeblock_bwd_desc d) {
     const uint32_t tile_lin = blockIdx.x;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int Cs = d.Cs, Cv = d.Cv, Os = d.Os;
@@ -457,6 +474,50 @@ __global__ __launch_bounds__(256, 4) void edgeblock_bwd_kernel(svnet_edgeblock_b
     }
     const int64_t e0 = (int64_t)tile * TE;
     const int64_t ew = e0 + wave * (TE / 4);                          // first edge row of this wave
+    const int rows_in = (int)min((int64_t)TE, E - e0);                // the tile's rows below E (>= 1: the grid is ceil(E / 32) tiles)
+
+    // ---- requests first.  What phase A reads depends only on the tile, the thread and the descriptor, and a tile's rows are contiguous
+    // in every per-edge array: each load is a wave-uniform base (SGPRs) plus a 32-bit lane offset, and the ones that need no position
+    // arithmetic go out before it (three divisions, the deal of the column tiles) - the longest single item of a workgroup's life is the
+    // time until the first of these is back.  Rows past E read the tile's last row and are masked where they are consumed.
+    // neighbour ids of this wave's 8 edge rows for phase C2 (lane rr holds idx[ew + rr]), consumed through v_readlane, so the row
+    // gathers of phase C2 never wait on a load of their own index
+    // (the LOW dword of the int64 id only: with a 64-bit load the allocator recycled the dead high register at once, and the write-after-
+    //  write hazard cost a full `s_waitcnt vmcnt(0)` - an HBM round trip - before any other load of the tile had been issued)
+    const int jv8 = ld_sbase<int>(d.idx + e0, 8u * (uint32_t)min(8 * wave + (lane & 7), rows_in - 1));
+    // ternary / STE planes of the tile: [e][plane][word] in HBM -> [plane][row][word] in LDS.  REQUESTED here (two words per thread),
+    // stored behind the other requests of phase A: as a load -> store loop the second word was requested after the first had arrived
+    static_assert(TE * 3 * NW <= 512, "two plane words per thread");
+    uint64_t plw[2];
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+        const int item = min(tid + 256 * u, TE * 3 * NW - 1);
+        const int r = item / (3 * NW);
+        plw[u] = ld_sbase<uint64_t>(d.planes + e0 * (3 * NW), 8u * (uint32_t)(min(r, rows_in - 1) * (3 * NW) + (item - r * (3 * NW))));
+    }
+    // this thread's edge-channel quads (<= 4: Os <= 128) and the per-channel constants [cs | alpha | beta | scale | pooled-is-max] from
+    // svnet_edgeblock_bwd_coeffs_f32.  256 is a multiple of Os/4 (Os a power of two in 8 .. 128: svnet_edgeblock_bwd_tier, checked on
+    // the host), so a thread's quads all sit on the same four channels
+    const int O4 = Os >> 2;
+    const int o4_shift = __builtin_ctz((unsigned)O4);   // Os is a power of two (checked on the host): item / O4 is a shift
+    constexpr int NI = NKS / 2;       // TE * (Os / 4) / 256 quads per thread
+    // (n and the pooled slots stay PACKED until they are used: as short4 / uchar4 they were unpacked right behind their loads - a
+    //  wait per quad, four dependent round trips per tile - profiles/r04_tile_phases.txt)
+    uint2 n4[NI]; float4 gy4[NI]; uint32_t smx[NI], smn[NI]; int tt[NI];
+#pragma unroll
+    for (int it = 0; it < NI; ++it) {
+        const int item = it * 256 + tid;
+        const int rc = min(item >> o4_shift, rows_in - 1), o4 = (item & (O4 - 1)) << 2;
+        n4[it] = ld_sbase<uint2>(d.n16 + e0 * Os, 2u * (uint32_t)(rc * Os + o4));
+    }
+    const float* chc = d.bcoef + ((3 * Os + 2 * d.Ov + 3) & ~3);
+    const uint32_t o4c = 16u * (uint32_t)(tid & (O4 - 1));          // byte offset of the thread's four channels
+    const float4 cs = ld_sbase<float4>(chc, o4c);
+    const float4 al = ld_sbase<float4>(chc + Os, o4c);
+    const float4 be = ld_sbase<float4>(chc + 2 * Os, o4c);
+    const float4 sc = ld_sbase<float4>(chc + 3 * Os, o4c);
+    const float4 ps = ld_sbase<float4>(chc + 4 * Os, o4c);
+    __builtin_amdgcn_sched_barrier(0);       // (the requests above stay above the divisions)
     TilePos tp;
     {
         const uint32_t ku = (uint32_t)d.k, Nu = (uint32_t)d.N, e0u = tile * (uint32_t)TE;
@@ -466,14 +527,21 @@ __global__ __launch_bounds__(256, 4) void edgeblock_bwd_kernel(svnet_edgeblock_b
         tp.pin0 = (int)(tp.gp0 - tp.b0 * Nu);
         tp.kmagic = (65536u + ku - 1u) / ku;
     }
+    // the per-point operands of the quads (the rows of the tile's points follow the row of its first point gp0)
+#pragma unroll
+    for (int it = 0; it < NI; ++it) {
+        const int item = it * 256 + tid;
+        const int r = item >> o4_shift, rc = min(r, rows_in - 1), o4 = (item & (O4 - 1)) << 2;
+        const uint32_t n_ = (uint32_t)(tp.t0 + rc), dq_ = small_div(n_, tp.kmagic);
+        tt[it] = (item < TE * O4 && r < rows_in) ? (int)(n_ - dq_ * (uint32_t)d.k) : -1;
+        const uint32_t po = dq_ * (uint32_t)Os + (uint32_t)o4;
+        gy4[it] = ld_sbase<float4>(d.gy + (int64_t)tp.gp0 * Os, 4u * po);
+        smx[it] = ld_sbase<uint32_t>(d.slot_max + (int64_t)tp.gp0 * Os, po);
+        smn[it] = ld_sbase<uint32_t>(d.slot_min + (int64_t)tp.gp0 * Os, po);
+    }
 
     const bool v2_lane = lane < 2 * Cv, diff_lane = lane < Cv;
     const int cm = diff_lane ? lane : lane - Cv;
-    // neighbour ids of this wave's 8 edge rows for phase C2 (lane rr holds idx[ew + rr]): requested now, consumed through
-    // v_readlane, so the row gathers of phase C2 never wait on a load of their own index
-    // (the LOW dword of the int64 id only: with a 64-bit load the allocator recycled the dead high register at once, and the write-after-
-    //  write hazard cost a full `s_waitcnt vmcnt(0)` - an HBM round trip - before any other load of the tile had been issued)
-    const int jv8 = reinterpret_cast<const int*>(d.idx)[2 * min(ew + (lane & 7), E - 1)];
 
     // The 320 fused columns are 5 words x 64, of which only Cs / Cs / 2Cv / 2Cv / 2Cv are in use: 32-column tiles that lie
     // entirely in the padding (5 of 10 for the Cs = 32, Cv = 10 layers) are skipped by phase B, and the used ones are dealt
@@ -484,31 +552,36 @@ __global__ __launch_bounds__(256, 4) void edgeblock_bwd_kernel(svnet_edgeblock_b
         const int width = (ct >> 1) < 2 ? Cs : 2 * Cv;
         if (width > 32 * (ct & 1)) used_tiles |= 1u << ct;
     }
-    int cts[3];
+    // (NQ slots per wave: with 2 Cv <= 24 - the NC2 = 20 / 24 forms - words 2 .. 4 hold one tile each, at most 7 tiles are in use and two
+    //  slots reach all of them; the third slot's accumulator and fragments were 24 - 32 registers held for nothing)
+    constexpr int NQ = (NC2 == 20 || NC2 == 24) ? 2 : 3;
+    int cts[NQ];
 #pragma unroll
-    for (int q = 0; q < 3; ++q) cts[q] = __builtin_amdgcn_readfirstlane(nth_set_bit10(used_tiles, wave + 4 * q));
+    for (int q = 0; q < NQ; ++q) cts[q] = __builtin_amdgcn_readfirstlane(nth_set_bit10(used_tiles, wave + 4 * q));
 
-    // sign(W1) fragments of this wave's column tiles for phase B (NKS k-steps x 3 tiles x 4 VGPRs).  Up to Os = 64 they are
-    // requested before anything else, so that their L2 latency is hidden behind phase A (at Os = 128 the 96 registers would
-    // spill across phase A: loaded at the start of phase B instead)
+    // sign(W1) fragments of this wave's column tiles for phase B (NKS k-steps x NQ tiles x 4 VGPRs).  Up to Os = 64 they are
+    // requested right behind phase A's own requests, so that their L2 latency is hidden behind phase A (at Os = 128 the 96 registers
+    // would spill across phase A: four k-steps are requested at the end of phase A, the other four while the MFMAs run)
     const int nks = (Os + 15) >> 4;
     constexpr int NKB = NKS < 4 ? NKS : 4;          // k-steps whose fragments are in registers at a time
-    bf16x8 bfr[NKB][3];
-#define SVNET_LOAD_BFR(KS0)                                                                                    \
+    bf16x8 bfr[NKB][NQ];
+    // The fragments of k-step KS into slot KB: NQ unconditional 16-byte loads from a wave-uniform base.  A wave without a q-th column
+    // tile, and the k-step past nks of Os = 8 / 16, read the table's all-zero fragment (index 10 nks) instead: with a branch around the
+    // load and a register fill on its other arm, the two arms merged into one register set and every load was waited for right behind
+    // its own issue (at Os = 128: a branch per fragment, two exposed round trips per tile).
+    const int zfrag = (NCOL / 32) * nks;
+#define SVNET_LOAD_BFR(KB, KS)                                                                                 \
     do {                                                                                                       \
-        const bf16x8* wbt_ = reinterpret_cast<const bf16x8*>(d.w1bt); /* [ct][ks][lane] fragments */           \
-        _Pragma("unroll") for (int kb = 0; kb < NKB; ++kb)                                                     \
-            _Pragma("unroll") for (int q = 0; q < 3; ++q) {                                                    \
-                const int ct = cts[q], ks_ = (KS0) + kb;                                                       \
-                if (ks_ < nks && ct >= 0) {                                                                    \
-                    bfr[kb][q] = wbt_[(ct * nks + ks_) * 64 + lane];                                           \
-                } else {                                                                                       \
-                    _Pragma("unroll") for (int j = 0; j < 8; ++j) bfr[kb][q][j] = bf16_from_bits(0);           \
-                }                                                                                              \
-            }                                                                                                  \
+        _Pragma("unroll") for (int q = 0; q < NQ; ++q) {                                                       \
+            const int fi_ = (cts[q] >= 0 && (NKS > 2 || (KS) < nks)) ? cts[q] * nks + (KS) : zfrag;            \
+            bfr[KB][q] = ld_sbase<bf16x8>(d.w1bt + (uint32_t)fi_ * 512u, 16u * (uint32_t)lane);                \
+        }                                                                                                      \
     } while (0)
     constexpr bool HOIST_B = NKS <= 4;
-    if (HOIST_B) SVNET_LOAD_BFR(0);
+    if (HOIST_B) {
+#pragma unroll
+        for (int kb = 0; kb < NKB; ++kb) SVNET_LOAD_BFR(kb, kb);
+    }
     // the gate path's per-cloud constants of phase C's scalar pass (lane = scalar channel): requested HERE.  Loaded where they are used
     // - first thing in pass 1, behind the ~20 gather requests of phase C that are still in flight (vmcnt retires in order) - they made
     // that pass wait out the whole gather: 19 % (conv4) to 42 % (conv2) of a workgroup's time (phase clocks, profiles/r04_tile_phases.txt)
@@ -523,49 +596,6 @@ __global__ __launch_bounds__(256, 4) void edgeblock_bwd_kernel(svnet_edgeblock_b
     //   dy_pre = cs*(g - m1 - xhat*m2), xhat = (scale*n - mean)*invstd, g = gy[p,o] on the pooled edge, else 0
     //          = cs*g - (alpha + beta*n)
     {
-        // ternary / STE planes of the tile: [e][plane][word] in HBM -> [plane][row][word] in LDS.  REQUESTED here (two words per thread),
-        // stored behind the other requests of phase A: as a load -> store loop the second word was requested after the first had arrived
-        static_assert(TE * 3 * NW <= 512, "two plane words per thread");
-        uint64_t plw[2];
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            const int item = min(tid + 256 * u, TE * 3 * NW - 1);
-            const int r = item / (3 * NW);
-            plw[u] = d.planes[min(e0 + r, E - 1) * (3 * NW) + (item - r * (3 * NW))];
-        }
-        // this thread's edge-channel quads (<= 4: Os <= 128): their loads go out before the barrier, with the constants'
-        const int O4 = Os >> 2;
-        const int o4_shift = __builtin_ctz((unsigned)O4);   // Os is a power of two (checked on the host): item / O4 is a shift
-        const int k = (int)d.k;
-        // per-channel constants [cs | alpha | beta | scale | pooled-is-max] from svnet_edgeblock_bwd_coeffs_f32.  256 is a multiple
-        // of Os/4 (Os a power of two in 8 .. 128: svnet_edgeblock_bwd_tier, checked on the host), so a thread's quads all sit on the same four channels
-        const float* chc = d.bcoef + ((3 * Os + 2 * d.Ov + 3) & ~3);
-        const int o4c = (tid & (O4 - 1)) << 2;
-        const float4 cs = *reinterpret_cast<const float4*>(chc + o4c);
-        const float4 al = *reinterpret_cast<const float4*>(chc + Os + o4c);
-        const float4 be = *reinterpret_cast<const float4*>(chc + 2 * Os + o4c);
-        const float4 sc = *reinterpret_cast<const float4*>(chc + 3 * Os + o4c);
-        const float4 ps = *reinterpret_cast<const float4*>(chc + 4 * Os + o4c);
-        constexpr int NI = NKS / 2;       // TE * (Os / 4) / 256 quads per thread
-        // (n and the pooled slots stay PACKED until they are used: as short4 / uchar4 they were unpacked right behind their loads - a
-        //  wait per quad, four dependent round trips per tile - profiles/r04_tile_phases.txt)
-        uint2 n4[NI]; float4 gy4[NI]; uint32_t smx[NI], smn[NI]; int tt[NI];
-#pragma unroll
-        for (int it = 0; it < NI; ++it) {
-            const int item = it * 256 + tid;
-            const int r = item >> o4_shift, o4 = (item & (O4 - 1)) << 2;
-            const int64_t e = e0 + r;
-            tt[it] = -1;
-            if (item < TE * O4 && e < E) {
-                const uint32_t n_ = (uint32_t)(tp.t0 + r), dq_ = small_div(n_, tp.kmagic);
-                const int64_t gp = (int64_t)(tp.gp0 + dq_);
-                tt[it] = (int)(n_ - dq_ * (uint32_t)k);
-                n4[it] = *reinterpret_cast<const uint2*>(d.n16 + e * Os + o4);
-                gy4[it] = *reinterpret_cast<const float4*>(d.gy + gp * Os + o4);
-                smx[it] = *reinterpret_cast<const uint32_t*>(d.slot_max + gp * Os + o4);
-                smn[it] = *reinterpret_cast<const uint32_t*>(d.slot_min + gp * Os + o4);
-            }
-        }
         __builtin_amdgcn_sched_barrier(0);       // every request of phase A is out before the first wait
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
@@ -573,7 +603,7 @@ __global__ __launch_bounds__(256, 4) void edgeblock_bwd_kernel(svnet_edgeblock_b
             if (item < TE * 3 * NW) {
                 const int r = item / (3 * NW), q = item - r * (3 * NW);
                 const int plane = q / NW, w = q - plane * NW;
-                pl[(plane * TE + r) * NW + w] = (e0 + r < E) ? plw[u] : 0ull;
+                pl[(plane * TE + r) * NW + w] = r < rows_in ? plw[u] : 0ull;
             }
         }
         PHASE_MARK(11);   // phase A: requests issued
@@ -584,7 +614,6 @@ __global__ __launch_bounds__(256, 4) void edgeblock_bwd_kernel(svnet_edgeblock_b
             const int item = it * 256 + tid;
             if (item >= TE * O4) break;
             const int r = item >> o4_shift, o4 = (item & (O4 - 1)) << 2;
-            const int64_t e = e0 + r;
             const int t = tt[it];
             float4 dn = make_float4(0.f, 0.f, 0.f, 0.f);
             if (Os == 8 && o4 == 0) {   // the k-step reads 16 columns: zero the 8 padding columns of the row (anything times a zero weight must be 0)
@@ -604,7 +633,8 @@ __global__ __launch_bounds__(256, 4) void edgeblock_bwd_kernel(svnet_edgeblock_b
                 dy.y = cs.y * g1 - (al.y + be.y * n1);
                 dy.z = cs.z * g2 - (al.z + be.z * n2);
                 dy.w = cs.w * g3 - (al.w + be.w * n3);
-                if (d.dn_out) *reinterpret_cast<float4*>(d.dn_out + e * Os + o4) = dy;   // (optional: svnet_edgeblock_wgrad_f32 recomputes it)
+                // (optional: svnet_edgeblock_wgrad_f32 recomputes it; the tile's 32 x Os block is contiguous: quad `item` at 16 item bytes)
+                if (d.dn_out) *reinterpret_cast<float4*>(reinterpret_cast<char*>(d.dn_out + e0 * Os) + keep_here(16u * (uint32_t)item)) = dy;
                 dn = make_float4(dy.x * sc.x, dy.y * sc.y, dy.z * sc.z, dy.w * sc.w);
             }
             uint32_t h0, m0, l0, h1, m1, l1;
@@ -622,6 +652,12 @@ __global__ __launch_bounds__(256, 4) void edgeblock_bwd_kernel(svnet_edgeblock_b
     PHASE_MARK(0);   // phase A
     if (MODE == 2) { PHASE_FLUSH(); return; }
 
+    // Os = 128: the fragments of the first four k-steps are requested HERE, in front of the plane transposition (their 48 registers are
+    // free again: phase A's operands are dead), the other four one by one into the slots phase B's MFMAs have consumed
+    if (!HOIST_B) {
+#pragma unroll
+        for (int kb = 0; kb < NKB; ++kb) SVNET_LOAD_BFR(kb, kb);
+    }
     // ---- ternary planes of this tile -> row-sliced 32-bit halves (rows = the tile's 32 edges)
     {
         const int64_t word_row = e0 >> 6;
@@ -656,25 +692,24 @@ __global__ __launch_bounds__(256, 4) void edgeblock_bwd_kernel(svnet_edgeblock_b
     // ================= phase B: dx_b = dnl . sign(W1), masked by the STE plane =================
     {
         const int r = lane & 31, h = lane >> 5;
-        f32x16 acc[3];
+        f32x16 acc[NQ];
 #pragma unroll
-        for (int q = 0; q < 3; ++q)
+        for (int q = 0; q < NQ; ++q)
 #pragma unroll
             for (int i = 0; i < 16; ++i) acc[q][i] = 0.f;
 #pragma unroll
-        for (int ks0 = 0; ks0 < NKS; ks0 += NKB) {
-            if (!HOIST_B) SVNET_LOAD_BFR(ks0);       // Os = 128: two groups of four k-steps (96 fragment registers would cost a wave per SIMD)
+        for (int ks0 = 0; ks0 < NKS; ks0 += NKB) {      // Os = 128: two groups of four k-steps (96 fragment registers would cost a wave per SIMD)
 #pragma unroll
             for (int kb = 0; kb < NKB; ++kb) {
                 const int ks = ks0 + kb;
-                if (ks < nks) {
+                if (NKS > 2 || ks < nks) {             // (nks == NKS but for Os = 8 / 16, which run one k-step of NKS = 2)
                     const uint16_t* a_ = dnb + r * DNB + ks * 16 + 8 * h;                          // 16-byte aligned: DNB % 8 == 0
                     const bf16x8 fh = *reinterpret_cast<const bf16x8*>(a_), fm = *reinterpret_cast<const bf16x8*>(a_ + TE * DNB);
 #if SVNET_DN_PIECES >= 3
                     const bf16x8 fl = *reinterpret_cast<const bf16x8*>(a_ + 2 * TE * DNB);
 #endif
 #pragma unroll
-                    for (int q = 0; q < 3; ++q) {
+                    for (int q = 0; q < NQ; ++q) {
                         if (cts[q] >= 0) {  // wave-uniform
                             acc[q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fh, bfr[kb][q], acc[q], 0, 0, 0);
                             acc[q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fm, bfr[kb][q], acc[q], 0, 0, 0);
@@ -684,6 +719,7 @@ __global__ __launch_bounds__(256, 4) void edgeblock_bwd_kernel(svnet_edgeblock_b
                         }
                     }
                 }
+                if (ks + NKB < NKS) SVNET_LOAD_BFR(kb, ks + NKB);      // the slot is consumed: its next k-step travels under the MFMAs of the other three
             }
         }
         // Phase C's operands are requested HERE for the wide layers, not at the start of phase C: its first two passes are ~100
@@ -694,8 +730,15 @@ __global__ __launch_bounds__(256, 4) void edgeblock_bwd_kernel(svnet_edgeblock_b
         if constexpr (NC2 > 0 && NKS >= 4) SVNET_PHASEC_REQUESTS();
         __syncthreads();   // every wave has consumed dnb: dxl may now overwrite the same LDS bytes
         PHASE_MARK(6);   // phase B: barrier behind the MFMAs
+        // Accumulator element i of a lane is row (i & 3) + 8 (i >> 2) + 4 h of the tile: the sixteen row offsets are wave-uniform values
+        // computed once, the lane's part of the address (its half's four rows and its column) once per column tile - the address of an
+        // element is then ONE add (it was a multiply by the run-time stride and a shift-add per element)
+        int roff[16];
 #pragma unroll
-        for (int q = 0; q < 3; ++q) {
+        for (int i = 0; i < 16; ++i) roff[i] = __builtin_amdgcn_readfirstlane(((i & 3) + 8 * (i >> 2)) * DXS);
+        const int hoff = 4 * h * DXS;
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) {
             const int ct = cts[q];
             if (ct >= 0) {
                 const int col = ct * 32 + r;
@@ -707,13 +750,18 @@ __global__ __launch_bounds__(256, 4) void edgeblock_bwd_kernel(svnet_edgeblock_b
                 const uint32_t roww = reinterpret_cast<const uint32_t*>(pl)[((2 * TE + r) * NW + wd) * 2 + (ct & 1)];
                 const int cmask = (int)(svnet_bit_transpose32(roww, lane) >> (4 * h));
                 float csum = 0.f;                       // dL/dbeta of this column: sum over the tile's rows (rows past E are zero)
+                float mv[16];
 #pragma unroll
                 for (int i = 0; i < 16; ++i) {
-                    const int rb = (i & 3) + 8 * (i >> 2), row = rb + 4 * h;
+                    const int rb = (i & 3) + 8 * (i >> 2);
                     const uint32_t keep = (uint32_t)__builtin_amdgcn_sbfe(cmask, rb, 1);            // 0 or ~0
-                    const float v = __uint_as_float(__float_as_uint(acc[q][i]) & keep);
-                    if (in_use) dxl[row * DXS + ccol] = v;
-                    csum += v;
+                    mv[i] = __uint_as_float(__float_as_uint(acc[q][i]) & keep);
+                    csum += mv[i];
+                }
+                if (in_use) {                           // (one exec region for the sixteen stores)
+                    float* const dcol = dxl + hoff + ccol;
+#pragma unroll
+                    for (int i = 0; i < 16; ++i) dcol[roff[i]] = mv[i];
                 }
                 const float other = lane_half_swap(csum);
                 if (h == 0 && in_use) { const float t = csum + other; if (t != 0.f) ATOMIC_ADD(&d.dbeta_perm[(tile_lin & (SVNET_DBETA_SLICES - 1)) * NCOL + col], t); }
@@ -1009,7 +1057,7 @@ extern "C" int svnet_edgeblock_wbt_bf16(const uint64_t* w_sign, const uint64_t* 
                                         uint32_t* w_dense, void* stream) {
     SVNET_REQUIRE(w_sign && w_nz && wbt && Os > 0 && Os % 8 == 0, SVNET_E_ARG, "svnet_edgeblock_wbt_bf16: bad arguments (Os must be a multiple of 8)");
     SVNET_REQUIRE(!w_dense || (Cs > 0 && Cs <= 64 && Cv > 0 && 2 * Cv <= 64), SVNET_E_ARG, "svnet_edgeblock_wbt_bf16: w_dense needs the layer's Cs <= 64, 2 Cv <= 64");
-    hipLaunchKernelGGL(edgeblock_wbt_kernel, dim3((unsigned)svnet_cdiv(NCOL * ((Os + 15) / 16 * 16), 256)), dim3(256), 0, (hipStream_t)stream, w_sign, w_nz,
+    hipLaunchKernelGGL(edgeblock_wbt_kernel, dim3((unsigned)svnet_cdiv(NCOL * ((Os + 15) / 16 * 16) + 512, 256)), dim3(256), 0, (hipStream_t)stream, w_sign, w_nz,
                        (int)Os, (int)Cs, (int)Cv, wbt, w_dense);
     SVNET_CHECK_LAUNCH("edgeblock_wbt_kernel");
     return SVNET_OK;
