@@ -150,11 +150,22 @@ __device__ __forceinline__ uint32_t keep_here(uint32_t x) { asm volatile("" : "+
 __device__ __forceinline__ float ld_f32_sbase(const float* base, uint32_t byte_off) {
     return *reinterpret_cast<const float*>(reinterpret_cast<const char*>(base) + keep_here(byte_off));
 }
+// The same for a lane offset that is formed inside the loop (nothing to hoist): without keep_here, whose "+v" costs a v_mov_b32 per load
+// whenever its operand lives on.
+__device__ __forceinline__ float ld_f32_sbase_fresh(const float* base, uint32_t byte_off) {
+    return *reinterpret_cast<const float*>(reinterpret_cast<const char*>(base) + byte_off);
+}
 __device__ __forceinline__ int16_t ld_i16_sbase(const int16_t* base, uint32_t byte_off) {
     return *reinterpret_cast<const int16_t*>(reinterpret_cast<const char*>(base) + keep_here(byte_off));
 }
 __device__ __forceinline__ void st_f32_sbase(float* base, uint32_t byte_off, float v) {
     *reinterpret_cast<float*>(reinterpret_cast<char*>(base) + keep_here(byte_off)) = v;
+}
+__device__ __forceinline__ void st_i16_sbase_fresh(int16_t* base, uint32_t byte_off, int16_t v) {
+    *reinterpret_cast<int16_t*>(reinterpret_cast<char*>(base) + byte_off) = v;
+}
+__device__ __forceinline__ void st_u64_sbase_fresh(uint64_t* base, uint32_t byte_off, uint64_t v) {
+    *reinterpret_cast<uint64_t*>(reinterpret_cast<char*>(base) + byte_off) = v;
 }
 
 #endif

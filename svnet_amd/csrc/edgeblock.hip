@@ -68,10 +68,19 @@ __device__ __forceinline__ bool edge_weights_dense(const uint32_t* __restrict__ 
     return w_dense && *w_dense == 1u;
 }
 
+// a table row at a wave-uniform byte offset (32-bit: zero-extended, one s_add_u32 / s_addc_u32 on the table base)
+__device__ __forceinline__ const float* row_at(const float* table, uint32_t byte_off) {
+    return reinterpret_cast<const float*>(reinterpret_cast<const char*>(table) + byte_off);
+}
+__device__ __forceinline__ const float* row_at(const float* table, int64_t byte_off) {
+    return reinterpret_cast<const float*>(reinterpret_cast<const char*>(table) + byte_off);
+}
+
 // NARROW: every word has at most 32 columns in use (Cs <= 32 and 2 Cv <= 32): the popcount products run on the low halves only
 // The kernel proper.  Every table comes in as a __restrict__ parameter (the kernel below just unpacks the descriptor): with
 // the aliasing question settled, the wave-uniform reads (the zz rows) become scalar loads instead of vector loads + readlanes.
-template <int OP, bool NARROW, bool DENSE>
+// ROWS32: the neighbour rows' byte offsets fit 32 bits (edge_rows_fit_32, decided by the launch)
+template <int OP, bool NARROW, bool DENSE, bool SAVE, bool ROWS32>
 __device__ __forceinline__ void edgeblock_fwd_body(const FwdArgs& fa, const float* __restrict__ ts, const float* __restrict__ tv,
                                                    const int64_t* __restrict__ tidx, const float* __restrict__ tzz,
                                                    const float* __restrict__ tut, int16_t* __restrict__ o_n16,
@@ -95,6 +104,8 @@ __device__ __forceinline__ void edgeblock_fwd_body(const FwdArgs& fa, const floa
     const int p_begin = wi * fa.points_per_wave;
     const int p_end = bq < d.B ? min((int)d.N, p_begin + fa.points_per_wave) : p_begin;
     const int Cs = d.Cs, Cv = d.Cv, Os = d.Os, Ov = d.Ov, k = (int)d.k;
+    typedef typename std::conditional<ROWS32, uint32_t, int64_t>::type row_t;
+    const row_t cloud0 = (row_t)(b * d.N), row_s = (row_t)(4 * Cs), row_v = (row_t)(12 * Cv), row_u = (row_t)(24 * Ov), row_z = (row_t)72;
 
     // my output channels' weight words
     word_t wsg[OP][NW], wnz[OP][NW];
@@ -117,8 +128,13 @@ __device__ __forceinline__ void edgeblock_fwd_body(const FwdArgs& fa, const floa
     const bool diff_lane = lane < Cv;
     const int cm = diff_lane ? lane : lane - Cv;
     const bool o_lane = lane < Ov;
+    // the lane predicates as wave-uniform words (wave_ballot_masked; every ballot below sits in wave-uniform control flow, all lanes active)
+    const uint64_t m_s = __builtin_amdgcn_ballot_w64(s_lane), m_v2 = __builtin_amdgcn_ballot_w64(v2_lane);
 
-    const bool save = o_planes != nullptr;   // training: keep n and the ternary / STE planes of every edge for the backward
+    // SAVE (training: keep n and the ternary / STE planes of every edge for the backward) is the launch's d.planes != nullptr.  As a run-time
+    // flag it put a uniform branch around each STE ballot, the v_writelane block and the n16 store: eight basic blocks per edge, across
+    // which no load, popcount or v_writelane could be scheduled.
+    constexpr bool save = SAVE;
 
     long long sn[OP], sn2[OP];
 #pragma unroll
@@ -155,8 +171,8 @@ __device__ __forceinline__ void edgeblock_fwd_body(const FwdArgs& fa, const floa
         const float s_i = s_lane ? s_raw : 0.f;
         gs_cen += s_i;
         const float tc = s_i + bc;
-        const uint64_t csg = __ballot(s_lane && tc > 0.f), cnz = __ballot(s_lane && tc != 0.f);
-        const uint64_t cst = save ? __ballot(s_lane && fabsf(tc) <= 1.2f) : 0ull;
+        const uint64_t csg = wave_ballot_masked(tc > 0.f, m_s), cnz = wave_ballot_masked(tc != 0.f, m_s);
+        const uint64_t cst = save ? wave_ballot_masked(fabsf(tc) <= 1.2f, m_s) : 0ull;
         int base[OP];
 #pragma unroll
         for (int op = 0; op < OP; ++op) base[op] = tdot((word_t)csg, (word_t)cnz, wsg[op][1], wnz[op][1]);
@@ -183,20 +199,34 @@ __device__ __forceinline__ void edgeblock_fwd_body(const FwdArgs& fa, const floa
                        bo0 = 4u * (uint32_t)lo, bo1 = 4u * (uint32_t)(lo + 2 * Ov), bo2 = 4u * (uint32_t)(lo + 4 * Ov);
         struct Nbr { float sj, vj0, vj1, vj2, u0, u1, u2, z[9]; };
         Nbr na = {}, nb = {};
+        // the point's rows of the per-edge records (wave-uniform) as SGPR bases: edge t stores at the 32-bit byte offset t * row + lane's
+        // (per-lane 64-bit addresses cost a v_mad_u64_u32 per edge and output)
+        int16_t* const n16_pt = save ? o_n16 + gp * k * Os : nullptr;
+        uint64_t* const pl_pt = save ? o_planes + gp * k * (3 * NW) : nullptr;
+        // Row bases: byte offset of the neighbour's row = (first point of the cloud + its id) * bytes per row, in row_t.  As 64-bit
+        // products of 64-bit factors these were half of the loop's scalar instructions (s_mul_i32 x3 + s_mul_hi_u32 + adds per table);
+        // ROWS32 (edge_rows_fit_32: every table below 2^32 bytes) forms them with one s_mul_i32 each.
 #define SVNET_LOAD_NBR(N_, T)                                                               \
     do {                                                                                    \
-        const int64_t gj_ = b * d.N + __builtin_amdgcn_readlane(jv, (T));                   \
-        const float* ps_ = ts + gj_ * Cs;        /* wave-uniform row bases + 32-bit lane byte offsets: SGPR-base loads */ \
-        const float* pv_ = tv + gj_ * 3 * Cv;                                               \
-        const float* pu_ = tut + gj_ * 6 * Ov;                                              \
-        N_.sj = ld_f32_sbase(ps_, bs0);                                                     \
-        N_.vj0 = ld_f32_sbase(pv_, bd0); N_.vj1 = ld_f32_sbase(pv_, bd1); N_.vj2 = ld_f32_sbase(pv_, bd2); \
-        N_.u0 = ld_f32_sbase(pu_, bo0); N_.u1 = ld_f32_sbase(pu_, bo1); N_.u2 = ld_f32_sbase(pu_, bo2); \
-        const float* zr_ = tzz + gj_ * 18 + opaque0;                                        \
-        N_.z[0] = zr_[0]; N_.z[1] = zr_[1]; N_.z[2] = zr_[2]; N_.z[3] = zr_[6]; N_.z[4] = zr_[7]; N_.z[5] = zr_[8];        \
+        const row_t gj_ = cloud0 + (row_t)(uint32_t)__builtin_amdgcn_readlane(jv, (T));     \
+        if constexpr (ROWS32) { /* the table itself as SGPR base; row + lane byte offset: one v_add_u32 of an SGPR per load */ \
+            const uint32_t rs_ = gj_ * row_s, rv_ = gj_ * row_v, ru_ = gj_ * row_u;         \
+            N_.sj = ld_f32_sbase_fresh(ts, rs_ + bs0);                                      \
+            N_.vj0 = ld_f32_sbase_fresh(tv, rv_ + bd0); N_.vj1 = ld_f32_sbase_fresh(tv, rv_ + bd1); N_.vj2 = ld_f32_sbase_fresh(tv, rv_ + bd2); \
+            N_.u0 = ld_f32_sbase_fresh(tut, ru_ + bo0); N_.u1 = ld_f32_sbase_fresh(tut, ru_ + bo1); N_.u2 = ld_f32_sbase_fresh(tut, ru_ + bo2); \
+        } else {               /* wave-uniform 64-bit row bases + 32-bit lane byte offsets */ \
+            const float* ps_ = row_at(ts, gj_ * row_s);                                     \
+            const float* pv_ = row_at(tv, gj_ * row_v);                                     \
+            const float* pu_ = row_at(tut, gj_ * row_u);                                    \
+            N_.sj = ld_f32_sbase(ps_, bs0);                                                 \
+            N_.vj0 = ld_f32_sbase(pv_, bd0); N_.vj1 = ld_f32_sbase(pv_, bd1); N_.vj2 = ld_f32_sbase(pv_, bd2); \
+            N_.u0 = ld_f32_sbase(pu_, bo0); N_.u1 = ld_f32_sbase(pu_, bo1); N_.u2 = ld_f32_sbase(pu_, bo2); \
+        }                                                                                   \
+        const float* zr_ = row_at(tzz, gj_ * row_z) + opaque0;                              \
+        N_.z[0] = zr_[0]; N_.z[1] = zr_[1]; N_.z[2] = zr_[2]; N_.z[3] = zr_[6]; N_.z[4] = zr_[7]; N_.z[5] = zr_[8]; \
         N_.z[6] = zr_[12]; N_.z[7] = zr_[13]; N_.z[8] = zr_[14];                            \
     } while (0)
-#define SVNET_WL(W, L)                                                                                           \
+#define SVNET_WL(W, L)                                                                                               \
     do {                                                                                                             \
         asm("v_writelane_b32 %0, %1, " #L : "+v"(vlo) : "s"((int)(uint32_t)(W)));                                    \
         if (!NARROW) asm("v_writelane_b32 %0, %1, " #L : "+v"(vhi) : "s"((int)(uint32_t)((W) >> 32)));               \
@@ -209,7 +239,7 @@ __device__ __forceinline__ void edgeblock_fwd_body(const FwdArgs& fa, const floa
         const float sd = s_lane ? (CUR.sj - s_i) : 0.f;                                                                      \
         gs_diff += sd;                                                                                                       \
         const float td = sd + bd;                                                                                            \
-        const uint64_t dsg = __ballot(s_lane && td > 0.f), dnz = __ballot(s_lane && td != 0.f);                              \
+        const uint64_t dsg = wave_ballot_masked(td > 0.f, m_s), dnz = wave_ballot_masked(td != 0.f, m_s);                    \
         float ve[3], z[3][3];                                                                                                \
         ve[0] = diff_lane ? (CUR.vj0 - vi[0]) : vi[0];                                                                       \
         ve[1] = diff_lane ? (CUR.vj1 - vi[1]) : vi[1];                                                                       \
@@ -219,19 +249,18 @@ __device__ __forceinline__ void edgeblock_fwd_body(const FwdArgs& fa, const floa
         uint64_t vsg[3], vnz[3], vst[3];                                                                                     \
         _Pragma("unroll") for (int jz = 0; jz < 3; ++jz) {                                                                   \
             const float tvv = ve[0] * z[0][jz] + ve[1] * z[1][jz] + ve[2] * z[2][jz] + bv[jz];                               \
-            vsg[jz] = __ballot(v2_lane && tvv > 0.f);                                                                        \
-            vnz[jz] = __ballot(v2_lane && tvv != 0.f);                                                                       \
-            vst[jz] = save ? __ballot(v2_lane && fabsf(tvv) <= 1.2f) : 0ull;                                                 \
+            vsg[jz] = wave_ballot_masked(tvv > 0.f, m_v2);                                                                   \
+            vnz[jz] = wave_ballot_masked(tvv != 0.f, m_v2);                                                                  \
+            vst[jz] = save ? wave_ballot_masked(fabsf(tvv) <= 1.2f, m_v2) : 0ull;                                            \
         }                                                                                                                    \
-        const int64_t e = gp * k + t;                                                                                        \
-        if (save) { /* wave-uniform.  planes[e][plane][word]: lane 5*plane + word holds one 64-bit word of the edge row */  \
-            const uint64_t dst = __ballot(s_lane && fabsf(td) <= 1.2f);                                                      \
-            /* v_writelane drops each (wave-uniform) ballot word straight into its lane: no lane masks, no selects */       \
+        if (save) { /* wave-uniform.  planes[e][plane][word]: lane 5*plane + word holds one 64-bit word of the edge row */   \
+            const uint64_t dst = wave_ballot_masked(fabsf(td) <= 1.2f, m_s);                                                 \
+            /* v_writelane drops each (wave-uniform) ballot word straight into its lane: no lane masks, no selects */        \
             int vlo = 0, vhi = 0;                                                                                            \
             SVNET_WL(dsg, 0);  SVNET_WL(csg, 1);  SVNET_WL(vsg[0], 2);  SVNET_WL(vsg[1], 3);  SVNET_WL(vsg[2], 4);           \
             SVNET_WL(dnz, 5);  SVNET_WL(cnz, 6);  SVNET_WL(vnz[0], 7);  SVNET_WL(vnz[1], 8);  SVNET_WL(vnz[2], 9);           \
             SVNET_WL(dst, 10); SVNET_WL(cst, 11); SVNET_WL(vst[0], 12); SVNET_WL(vst[1], 13); SVNET_WL(vst[2], 14);          \
-            if (lane < 3 * NW) o_planes[e * (3 * NW) + lane] = ((uint64_t)(uint32_t)vhi << 32) | (uint32_t)vlo;             \
+            if (lane < 3 * NW) st_u64_sbase_fresh(pl_pt, (uint32_t)t * (24u * NW) + 8u * (uint32_t)lane, ((uint64_t)(uint32_t)vhi << 32) | (uint32_t)vlo); \
         }                                                                                                                    \
         /* (DENSE: the edge's own count of non-zero features - wave-uniform, on the scalar unit) */                          \
         const int pme = DENSE ? (int)(__popcll((uint64_t)(word_t)dnz) + __popcll((uint64_t)(word_t)vnz[0]) + __popcll((uint64_t)(word_t)vnz[1]) + \
@@ -250,7 +279,7 @@ __device__ __forceinline__ void edgeblock_fwd_body(const FwdArgs& fa, const floa
             if (n < nmin[op]) { nmin[op] = n; smin[op] = t; }                                                                \
             sn[op] += n;                                                                                                     \
             sn2[op] += n * n;                                                                                                \
-            if (save && lane + 64 * op < Os) o_n16[e * Os + lane + 64 * op] = (int16_t)n;   /* |n| <= 320 */                 \
+            if (save && lane + 64 * op < Os) st_i16_sbase_fresh(n16_pt, (uint32_t)t * (2u * (uint32_t)Os) + 2u * (uint32_t)(lane + 64 * op), (int16_t)n);   /* |n| <= 320 */ \
         }                                                                                                                    \
         if (o_lane) {                                                                                                        \
             const float vp0 = CUR.u0 + ub[0], vp1 = CUR.u1 + ub[1], vp2 = CUR.u2 + ub[2];                                    \
@@ -330,14 +359,14 @@ __device__ __forceinline__ void edgeblock_fwd_body(const FwdArgs& fa, const floa
 }
 
 // register budget: 4 waves per SIMD (<= 128 VGPRs) up to Os = 64, 3 (<= 168) above: the kernel sat 1 and 3 registers over
-template <int OP, bool NARROW>
+template <int OP, bool NARROW, bool SAVE, bool ROWS32>
 __global__ __launch_bounds__(256, (OP == 1 ? 4 : 3)) void edgeblock_fwd_kernel(FwdArgs fa) {
     const svnet_edgeblock_desc& d = fa.d;
     // (a wave-uniform branch between the two instantiations: the weights of a layer hold no exact zero in practice)
     if (edge_weights_dense(d.w_dense))
-        edgeblock_fwd_body<OP, NARROW, true>(fa, d.s, d.v, d.idx, d.zz, d.ut, d.n16, d.planes, d.n_max, d.n_min, d.slot_max, d.slot_min, d.mv, d.mvn);
+        edgeblock_fwd_body<OP, NARROW, true, SAVE, ROWS32>(fa, d.s, d.v, d.idx, d.zz, d.ut, d.n16, d.planes, d.n_max, d.n_min, d.slot_max, d.slot_min, d.mv, d.mvn);
     else
-        edgeblock_fwd_body<OP, NARROW, false>(fa, d.s, d.v, d.idx, d.zz, d.ut, d.n16, d.planes, d.n_max, d.n_min, d.slot_max, d.slot_min, d.mv, d.mvn);
+        edgeblock_fwd_body<OP, NARROW, false, SAVE, ROWS32>(fa, d.s, d.v, d.idx, d.zz, d.ut, d.n16, d.planes, d.n_max, d.n_min, d.slot_max, d.slot_min, d.mv, d.mvn);
 }
 
 // ---------------------------------------------------------------------------------------------- two edges per wave iteration
@@ -347,7 +376,7 @@ __global__ __launch_bounds__(256, (OP == 1 ? 4 : 3)) void edgeblock_fwd_kernel(F
 // once per point (arg-max / arg-min with the lower slot winning ties, sums added).  Lane l of either half owns the output channels
 // l + 32*q (q < OP2), the scalar channel l, the vector channel l and the v2s channel l.  Same arithmetic per edge as the kernel
 // above (bit-identical results).
-template <int OP2, bool DENSE>
+template <int OP2, bool DENSE, bool SAVE>
 __device__ __forceinline__ void edgeblock_fwd2_body(const FwdArgs& fa) {
     const svnet_edgeblock_desc& d = fa.d;
     const float* __restrict__ ts = d.s; const float* __restrict__ tv = d.v; const int64_t* __restrict__ tidx = d.idx;
@@ -385,7 +414,9 @@ __device__ __forceinline__ void edgeblock_fwd2_body(const FwdArgs& fa) {
 
     const bool s_lane = l < Cs, v2_lane = l < 2 * Cv, diff_lane = l < Cv, o_lane = l < Ov;
     const int cm = diff_lane ? l : l - Cv;
-    const bool save = o_planes != nullptr;
+    // (the lane predicates of BOTH halves as wave-uniform words: wave_ballot_masked, as above)
+    const uint64_t m_s = __builtin_amdgcn_ballot_w64(s_lane), m_v2 = __builtin_amdgcn_ballot_w64(v2_lane);
+    constexpr bool save = SAVE;      // (see edgeblock_fwd_body)
 
     long long sn[OP2], sn2[OP2];
 #pragma unroll
@@ -422,8 +453,8 @@ __device__ __forceinline__ void edgeblock_fwd2_body(const FwdArgs& fa) {
         const float s_i = s_lane ? s_raw : 0.f;
         if (!hi) gs_cen += s_i;
         const float tc = s_i + bc;
-        const uint64_t csg = __ballot(s_lane && tc > 0.f), cnz = __ballot(s_lane && tc != 0.f);     // both halves identical
-        const uint64_t cst = save ? __ballot(s_lane && fabsf(tc) <= 1.2f) : 0ull;
+        const uint64_t csg = wave_ballot_masked(tc > 0.f, m_s), cnz = wave_ballot_masked(tc != 0.f, m_s);     // both halves identical
+        const uint64_t cst = save ? wave_ballot_masked(fabsf(tc) <= 1.2f, m_s) : 0ull;
         int base[OP2];
 #pragma unroll
         for (int q = 0; q < OP2; ++q) base[q] = tdot((uint32_t)csg, (uint32_t)cnz, wsg[q][1], wnz[q][1]);
@@ -445,6 +476,9 @@ __device__ __forceinline__ void edgeblock_fwd2_body(const FwdArgs& fa) {
         // rows are requested one pair ahead into two alternating register sets; 32-bit element offsets from SGPR table bases
         struct Nbr { float sj, vj0, vj1, vj2, u0, u1, u2, z[9]; };
         Nbr na = {}, nb = {};
+        int16_t* const n16_pt = save ? o_n16 + gp * k * Os : nullptr;             // (the point's rows of the per-edge records, as above)
+        uint64_t* const pl_pt = save ? o_planes + gp * k * (3 * NW) : nullptr;
+        const uint32_t n16_l = 2u * (uint32_t)((hi ? Os : 0) + l);                 // (byte offset of this half's channel l in the pair's two rows)
 #define SVNET_LOAD_NBR2(N_, I)                                                                               \
     do {                                                                                                     \
         const int ta_ = min(2 * (I), k - 1), tb_ = min(2 * (I) + 1, k - 1);                                  \
@@ -452,12 +486,12 @@ __device__ __forceinline__ void edgeblock_fwd2_body(const FwdArgs& fa) {
         const uint32_t gj_ = cloud0 + (uint32_t)(hi ? jb_ : ja_);                                            \
         const uint32_t os_ = 4u * (gj_ * uCs + ls), ov_ = 4u * (gj_ * 3u * uCv + ldv), ou_ = 4u * (gj_ * 6u * uOv + lo), \
                        oz_ = 4u * (gj_ * 18u);                                                               \
-        N_.sj = ld_f32_sbase(ts, os_);                                                                       \
-        N_.vj0 = ld_f32_sbase(tv, ov_); N_.vj1 = ld_f32_sbase(tv, ov_ + 4u * uCv); N_.vj2 = ld_f32_sbase(tv, ov_ + 8u * uCv); \
-        N_.u0 = ld_f32_sbase(tut, ou_); N_.u1 = ld_f32_sbase(tut, ou_ + 8u * uOv); N_.u2 = ld_f32_sbase(tut, ou_ + 16u * uOv); \
-        N_.z[0] = ld_f32_sbase(tzz, oz_); N_.z[1] = ld_f32_sbase(tzz, oz_ + 4u); N_.z[2] = ld_f32_sbase(tzz, oz_ + 8u);        \
-        N_.z[3] = ld_f32_sbase(tzz, oz_ + 24u); N_.z[4] = ld_f32_sbase(tzz, oz_ + 28u); N_.z[5] = ld_f32_sbase(tzz, oz_ + 32u); \
-        N_.z[6] = ld_f32_sbase(tzz, oz_ + 48u); N_.z[7] = ld_f32_sbase(tzz, oz_ + 52u); N_.z[8] = ld_f32_sbase(tzz, oz_ + 56u); \
+        N_.sj = ld_f32_sbase_fresh(ts, os_);                                                                 \
+        N_.vj0 = ld_f32_sbase_fresh(tv, ov_); N_.vj1 = ld_f32_sbase_fresh(tv, ov_ + 4u * uCv); N_.vj2 = ld_f32_sbase_fresh(tv, ov_ + 8u * uCv); \
+        N_.u0 = ld_f32_sbase_fresh(tut, ou_); N_.u1 = ld_f32_sbase_fresh(tut, ou_ + 8u * uOv); N_.u2 = ld_f32_sbase_fresh(tut, ou_ + 16u * uOv); \
+        N_.z[0] = ld_f32_sbase_fresh(tzz, oz_); N_.z[1] = ld_f32_sbase_fresh(tzz, oz_ + 4u); N_.z[2] = ld_f32_sbase_fresh(tzz, oz_ + 8u); \
+        N_.z[3] = ld_f32_sbase_fresh(tzz, oz_ + 24u); N_.z[4] = ld_f32_sbase_fresh(tzz, oz_ + 28u); N_.z[5] = ld_f32_sbase_fresh(tzz, oz_ + 32u); \
+        N_.z[6] = ld_f32_sbase_fresh(tzz, oz_ + 48u); N_.z[7] = ld_f32_sbase_fresh(tzz, oz_ + 52u); N_.z[8] = ld_f32_sbase_fresh(tzz, oz_ + 56u); \
     } while (0)
 #define SVNET_HALF(W) (hi ? (uint32_t)((W) >> 32) : (uint32_t)(W))
 #define SVNET_WL2(W, L)                                                                                      \
@@ -474,7 +508,7 @@ __device__ __forceinline__ void edgeblock_fwd2_body(const FwdArgs& fa) {
         const float sd = s_lane ? (CUR.sj - s_i) : 0.f;                                                      \
         gs_diff += ok ? sd : 0.f;                                                                            \
         const float td = sd + bd;                                                                            \
-        const uint64_t dsg = __ballot(s_lane && td > 0.f), dnz = __ballot(s_lane && td != 0.f);              \
+        const uint64_t dsg = wave_ballot_masked(td > 0.f, m_s), dnz = wave_ballot_masked(td != 0.f, m_s);    \
         float ve[3], z[3][3];                                                                                \
         ve[0] = diff_lane ? (CUR.vj0 - vi[0]) : vi[0];                                                       \
         ve[1] = diff_lane ? (CUR.vj1 - vi[1]) : vi[1];                                                       \
@@ -484,24 +518,24 @@ __device__ __forceinline__ void edgeblock_fwd2_body(const FwdArgs& fa) {
         uint64_t vsg[3], vnz[3], vst[3];                                                                     \
         _Pragma("unroll") for (int jz = 0; jz < 3; ++jz) {                                                   \
             const float tvv = ve[0] * z[0][jz] + ve[1] * z[1][jz] + ve[2] * z[2][jz] + bv[jz];               \
-            vsg[jz] = __ballot(v2_lane && tvv > 0.f);                                                        \
-            vnz[jz] = __ballot(v2_lane && tvv != 0.f);                                                       \
-            vst[jz] = save ? __ballot(v2_lane && fabsf(tvv) <= 1.2f) : 0ull;                                 \
+            vsg[jz] = wave_ballot_masked(tvv > 0.f, m_v2);                                                   \
+            vnz[jz] = wave_ballot_masked(tvv != 0.f, m_v2);                                                  \
+            vst[jz] = save ? wave_ballot_masked(fabsf(tvv) <= 1.2f, m_v2) : 0ull;                            \
         }                                                                                                    \
-        const int64_t e0 = gp * k + 2 * i_;                  /* edge row of the low half; the high half's is e0 + 1 */ \
         if (save) { /* planes[e][plane][word]: lanes 0..14 hold the low half's 15 words, lanes 15..29 the high half's */ \
-            const uint64_t dst = __ballot(s_lane && fabsf(td) <= 1.2f);                                      \
+            const uint64_t dst = wave_ballot_masked(fabsf(td) <= 1.2f, m_s);                                 \
             int vlo = 0;                                                                                     \
-            SVNET_WL2(dsg, 0);  SVNET_WL2(csg, 1);  SVNET_WL2(vsg[0], 2);  SVNET_WL2(vsg[1], 3);  SVNET_WL2(vsg[2], 4);      \
-            SVNET_WL2(dnz, 5);  SVNET_WL2(cnz, 6);  SVNET_WL2(vnz[0], 7);  SVNET_WL2(vnz[1], 8);  SVNET_WL2(vnz[2], 9);      \
-            SVNET_WL2(dst, 10); SVNET_WL2(cst, 11); SVNET_WL2(vst[0], 12); SVNET_WL2(vst[1], 13); SVNET_WL2(vst[2], 14);     \
-            if (lane < ((2 * i_ + 1 < k) ? 30 : 15)) o_planes[e0 * (3 * NW) + lane] = (uint64_t)(uint32_t)vlo; \
+            SVNET_WL2(dsg, 0);  SVNET_WL2(csg, 1);  SVNET_WL2(vsg[0], 2);  SVNET_WL2(vsg[1], 3);  SVNET_WL2(vsg[2], 4); \
+            SVNET_WL2(dnz, 5);  SVNET_WL2(cnz, 6);  SVNET_WL2(vnz[0], 7);  SVNET_WL2(vnz[1], 8);  SVNET_WL2(vnz[2], 9); \
+            SVNET_WL2(dst, 10); SVNET_WL2(cst, 11); SVNET_WL2(vst[0], 12); SVNET_WL2(vst[1], 13); SVNET_WL2(vst[2], 14); \
+            /* edge row 2 i_ of the point is the low half's; the high half's is the next one */              \
+            if (lane < ((2 * i_ + 1 < k) ? 30 : 15)) st_u64_sbase_fresh(pl_pt, (uint32_t)i_ * (48u * NW) + 8u * (uint32_t)lane, (uint64_t)(uint32_t)vlo); \
         }                                                                                                    \
-        const uint32_t m_dsg = SVNET_HALF(dsg), m_dnz = SVNET_HALF(dnz);                                      \
+        const uint32_t m_dsg = SVNET_HALF(dsg), m_dnz = SVNET_HALF(dnz);                                     \
         uint32_t m_vsg[3], m_vnz[3];                                                                         \
         _Pragma("unroll") for (int jz = 0; jz < 3; ++jz) { m_vsg[jz] = SVNET_HALF(vsg[jz]); m_vnz[jz] = SVNET_HALF(vnz[jz]); } \
         /* (DENSE weights: the half's own count of non-zero features, once per edge instead of an and + bcnt per word and channel) */ \
-        const int pme = DENSE ? (__popc(m_dnz) + __popc(m_vnz[0]) + __popc(m_vnz[1]) + __popc(m_vnz[2])) : 0;   \
+        const int pme = DENSE ? (__popc(m_dnz) + __popc(m_vnz[0]) + __popc(m_vnz[1]) + __popc(m_vnz[2])) : 0; \
         _Pragma("unroll") for (int q = 0; q < OP2; ++q) {                                                    \
             int pm_ = base[q] + pme, pd_ = 0;                                                                \
             if (DENSE) {                                                                                     \
@@ -517,7 +551,7 @@ __device__ __forceinline__ void edgeblock_fwd2_body(const FwdArgs& fa) {
                 if (n < nmin[q]) { nmin[q] = n; smin[q] = t; }                                               \
                 sn[q] += n;                                                                                  \
                 sn2[q] += n * n;                                                                             \
-                if (save && l + 32 * q < Os) o_n16[(e0 + (hi ? 1 : 0)) * Os + l + 32 * q] = (int16_t)n;      \
+                if (save && l + 32 * q < Os) st_i16_sbase_fresh(n16_pt, (uint32_t)i_ * (4u * (uint32_t)Os) + n16_l + 64u * q, (int16_t)n); \
             }                                                                                                \
         }                                                                                                    \
         if (o_lane && ok) {                                                                                  \
@@ -599,10 +633,22 @@ __device__ __forceinline__ void edgeblock_fwd2_body(const FwdArgs& fa) {
     }
 }
 
-template <int OP2>
+template <int OP2, bool SAVE>
 __global__ __launch_bounds__(256, 4) void edgeblock_fwd2_kernel(FwdArgs fa) {
-    if (edge_weights_dense(fa.d.w_dense)) edgeblock_fwd2_body<OP2, true>(fa);      // (wave-uniform: see edgeblock_fwd_kernel)
-    else edgeblock_fwd2_body<OP2, false>(fa);
+    if (edge_weights_dense(fa.d.w_dense)) edgeblock_fwd2_body<OP2, true, SAVE>(fa);      // (wave-uniform: see edgeblock_fwd_kernel)
+    else edgeblock_fwd2_body<OP2, false, SAVE>(fa);
+}
+
+// the kernel of a forward tier (svnet_edgeblock_fwd_tier), with or without the backward's per-edge records
+template <bool SAVE, bool ROWS32>
+void edge_fwd_launch(int tier, unsigned grid, const FwdArgs& fa, hipStream_t stream) {
+    switch (tier) {
+        case SVNET_EDGE_FWD_TWO: hipLaunchKernelGGL((edgeblock_fwd2_kernel<1, SAVE>), dim3(grid), dim3(256), 0, stream, fa); break;
+        case 111: hipLaunchKernelGGL((edgeblock_fwd_kernel<1, true, SAVE, ROWS32>), dim3(grid), dim3(256), 0, stream, fa); break;
+        case 110: hipLaunchKernelGGL((edgeblock_fwd_kernel<1, false, SAVE, ROWS32>), dim3(grid), dim3(256), 0, stream, fa); break;
+        case 121: hipLaunchKernelGGL((edgeblock_fwd_kernel<2, true, SAVE, ROWS32>), dim3(grid), dim3(256), 0, stream, fa); break;
+        default: hipLaunchKernelGGL((edgeblock_fwd_kernel<2, false, SAVE, ROWS32>), dim3(grid), dim3(256), 0, stream, fa); break;   // 120
+    }
 }
 
 // Per-channel affine forms from the batch (or running) statistics.
@@ -701,14 +747,26 @@ extern "C" int svnet_edgeblock_prepare_f32(const float* W, const float* beta, in
     return SVNET_OK;
 }
 
+// The forward kernels' 32-bit neighbour row offsets are BYTE offsets into the point tables s [B N Cs], v [B N 3 Cv], ut [B N 6 Ov] and
+// zz [B N 18]: every one of them must stay below 2^32 bytes = 2^30 floats.  (ut is the widest table of the model's layers; a layer with
+// Ov < 3 or Cs > 6 Ov has a wider one.)  Past the bound the one-edge kernels run their 64-bit instantiation and the two-edge kernel,
+// which has none, is not chosen.
+static bool edge_rows_fit_32(int64_t Cs, int64_t Cv, int64_t Ov, int64_t B, int64_t N) {
+    int64_t widest = 18;
+    if (Cs > widest) widest = Cs;
+    if (3 * Cv > widest) widest = 3 * Cv;
+    if (6 * Ov > widest) widest = 6 * Ov;
+    return B >= 0 && N >= 0 && (B == 0 || N <= (((int64_t)1 << 30) - 1) / widest / B);      // B*N*widest < 2^30, without overflow
+}
+
 extern "C" int svnet_edgeblock_fwd_tier(int64_t Cs, int64_t Cv, int64_t Os, int64_t Ov, int64_t B, int64_t N) {
     if (!(Cs > 0 && Cs <= 64 && Cv > 0 && 2 * Cv <= 64 && Os > 0 && Os <= 128 && Ov > 0 && Ov <= 64)) return -1;
     const bool narrow = Cs <= 32 && 2 * Cv <= 32;
-    // two edges per wave iteration (32-bit element offsets: the largest table, ut, has B*N*6*Ov floats).  Measured at B=32,
+    // two edges per wave iteration (32-bit row offsets: edge_rows_fit_32).  Measured at B=32,
     // N=1024, k=20: Os = 32 (conv2) 196 -> 159 us; Os = 64 (conv3: two output channels per lane, so the popcount part does
     // not shrink, and 72 B of spills at 4 waves per SIMD) 197 -> 195 us - conv3 stays on the one-edge kernel (OP2 = 1 is the
     // only instantiation)
-    if (narrow && Ov <= 32 && Os <= 32 && B * N * 6 * Ov < ((int64_t)1 << 30)) return SVNET_EDGE_FWD_TWO;
+    if (narrow && Ov <= 32 && Os <= 32 && edge_rows_fit_32(Cs, Cv, Ov, B, N)) return SVNET_EDGE_FWD_TWO;
     return 100 + 10 * (Os <= 64 ? 1 : 2) + (narrow ? 1 : 0);
 }
 
@@ -733,17 +791,15 @@ extern "C" int svnet_edgeblock_fwd_f32(const svnet_edgeblock_desc* desc, void* s
     fa.waves_per_cloud = (int)svnet_cdiv(d.N, fa.points_per_wave);
     const int64_t waves = d.B * fa.waves_per_cloud;
     const unsigned grid = (unsigned)svnet_cdiv(waves, 4);
-    switch (tier) {
-        case SVNET_EDGE_FWD_TWO:
-            hipLaunchKernelGGL((edgeblock_fwd2_kernel<1>), dim3(grid), dim3(256), 0, (hipStream_t)stream, fa);
-            SVNET_CHECK_LAUNCH("edgeblock_fwd2_kernel");
-            return SVNET_OK;
-        case 111: hipLaunchKernelGGL((edgeblock_fwd_kernel<1, true>), dim3(grid), dim3(256), 0, (hipStream_t)stream, fa); break;
-        case 110: hipLaunchKernelGGL((edgeblock_fwd_kernel<1, false>), dim3(grid), dim3(256), 0, (hipStream_t)stream, fa); break;
-        case 121: hipLaunchKernelGGL((edgeblock_fwd_kernel<2, true>), dim3(grid), dim3(256), 0, (hipStream_t)stream, fa); break;
-        default: hipLaunchKernelGGL((edgeblock_fwd_kernel<2, false>), dim3(grid), dim3(256), 0, (hipStream_t)stream, fa); break;   // 120
+    const bool save = d.planes != nullptr;      // training: the instantiations that keep n16 and the planes
+    if (edge_rows_fit_32(d.Cs, d.Cv, d.Ov, d.B, d.N)) {
+        if (save) edge_fwd_launch<true, true>(tier, grid, fa, (hipStream_t)stream);
+        else edge_fwd_launch<false, true>(tier, grid, fa, (hipStream_t)stream);
+    } else {                                    // (never the two-edge kernel: svnet_edgeblock_fwd_tier)
+        if (save) edge_fwd_launch<true, false>(tier, grid, fa, (hipStream_t)stream);
+        else edge_fwd_launch<false, false>(tier, grid, fa, (hipStream_t)stream);
     }
-    SVNET_CHECK_LAUNCH("edgeblock_fwd_kernel");
+    SVNET_CHECK_LAUNCH(tier == SVNET_EDGE_FWD_TWO ? "edgeblock_fwd2_kernel" : "edgeblock_fwd_kernel");
     return SVNET_OK;
 }
 

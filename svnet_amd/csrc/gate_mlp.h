@@ -103,9 +103,13 @@ static inline int svnet_gate_bwd_chunks(int64_t Cin, int64_t H, int64_t Ov) {
     if (chunks < 1) chunks = 1;
     return (int)chunks;
 }
+// H = 0 (the gate of an SVBlock with one output vector channel: its hidden layer has Ov / 2 = 0 units, gate = sigmoid(0)) is a job whose
+// H-sized arrays are empty and may be null: every loop over H above runs zero times and nothing of them is read or written.
 static inline bool svnet_gate_fwd_job_ok(const svnet_gate_fwd_job* j) {
-    return j && (j->gin || (j->gin_f64 && j->gin_out) || (j->rows && j->gin_out && j->R > 0 && j->Cin <= 256)) && j->W0 && j->W2 && j->h && j->gate && j->B >= 0 && j->Cin > 0 && j->H > 0 && j->Ov > 0 && j->H <= 256 && j->Ov <= 256;
+    return j && (j->gin || (j->gin_f64 && j->gin_out) || (j->rows && j->gin_out && j->R > 0 && j->Cin <= 256)) &&
+           (j->H == 0 || (j->W0 && j->W2 && j->h)) && j->gate && j->B >= 0 && j->Cin > 0 && j->H >= 0 && j->Ov > 0 && j->H <= 256 && j->Ov <= 256;
 }
 static inline bool svnet_gate_bwd_job_ok(const svnet_gate_bwd_job* j) {
-    return j && j->dgate && j->gate && j->h && j->gin && j->W0 && j->W2 && j->dW0 && j->dW2 && j->B >= 0 && j->Cin > 0 && j->H > 0 && j->Ov > 0 && j->H <= 256 && j->Ov <= 256;
+    return j && j->dgate && j->gate && j->gin && (j->H == 0 || (j->h && j->W0 && j->W2 && j->dW0 && j->dW2)) && j->B >= 0 && j->Cin > 0 && j->H >= 0 &&
+           j->Ov > 0 && j->H <= 256 && j->Ov <= 256;
 }

@@ -110,6 +110,14 @@ __device__ __forceinline__ int lanes_below(unsigned long long mask) {
     return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
 }
 
+// ---- ballot of a comparison over the lanes of `lane_mask` (a wave-uniform word, taken once per kernel as the ballot of the lane
+// predicate: never as (1ull << n) - 1, which is undefined at n = 64).  __ballot(in_lane && cmp) materialises its predicate: v_cmp,
+// s_and_b64 with the lane predicate's mask, then v_cndmask_b32 v, 0, 1 and v_cmp_ne_u32 0, v to turn the bool back into a mask - two
+// VALU instructions per ballot for nothing.  The ballot of the raw comparison is the v_cmp's own result, and the AND runs on the
+// scalar unit.  Equal to __ballot(in_lane && cmp) only where every lane of the wave is active: call it in wave-uniform control flow
+// with a full exec mask (an inactive lane contributes 0 to a ballot, but its bit of lane_mask was taken when it was active).
+__device__ __forceinline__ uint64_t wave_ballot_masked(bool cmp, uint64_t lane_mask) { return __builtin_amdgcn_ballot_w64(cmp) & lane_mask; }
+
 // ---- (value, index) ranking: "a ranks before b" = larger value first, equal values -> smaller index first
 __device__ __forceinline__ bool ranks_before(float va, int ja, float vb, int jb) { return (va > vb) | ((va == vb) & (ja < jb)); }   // (bitwise: selects, not branches)
 // the same for values that may be NaN (torch.argmax: a NaN is the maximum, the first one wins).  Its own name, not an overload: a
