@@ -45,9 +45,9 @@ int svnet_slices_sum_f64(double* buf, int64_t L, void* stream);
 
 /* ABI version = 100 * round-of-change + serial.  It changes whenever an entry point gains / loses an argument or a caller-owned buffer
  * changes its required length (200: sliced accumulators, SVNET_SLICED_LEN; 400: this header; 401: the totals of a sliced accumulator are
- * written by its consumer, svnet_slices_sum_*; 402: GX of svnet_v2s_bwd_*, gw of svnet_xyzblock_bwd_f32 and col_sum of svnet_gemm_f32 are sliced accumulators; 403: svnet_binweight_grad_f32 takes sliced inputs; 421: svnet_three_nn_f32, svnet_three_interpolate_f32; 422: svnet_ball_query_f32, svnet_group_points_f32; 423: svnet_vlinear_stats_f32 is gone; 424: svnet_edgeblock_fwd_tier, svnet_edgeblock_bwd_tier, svnet_edgeblock_wgrad_tier, svnet_xyzblock_tier; 425: svnet_pointset_reverse_i32, svnet_three_interpolate_bwd_f32, svnet_group_points_bwd_f32; 426: wbt of svnet_edgeblock_wbt_bf16 is 512 values longer, the all-zero fragment).  svnet_version() returns the value the
+ * written by its consumer, svnet_slices_sum_*; 402: GX of svnet_v2s_bwd_*, gw of svnet_xyzblock_bwd_f32 and col_sum of svnet_gemm_f32 are sliced accumulators; 403: svnet_binweight_grad_f32 takes sliced inputs; 421: svnet_three_nn_f32, svnet_three_interpolate_f32; 422: svnet_ball_query_f32, svnet_group_points_f32; 423: svnet_vlinear_stats_f32 is gone; 424: svnet_edgeblock_fwd_tier, svnet_edgeblock_bwd_tier, svnet_edgeblock_wgrad_tier, svnet_xyzblock_tier; 425: svnet_pointset_reverse_i32, svnet_three_interpolate_bwd_f32, svnet_group_points_bwd_f32; 426: wbt of svnet_edgeblock_wbt_bf16 is 512 values longer, the all-zero fragment; 427: svnet_ball_query_msg_f32, svnet_group_points_msg_f32, svnet_group_points_msg_bwd_f32).  svnet_version() returns the value the
  * library was BUILT with: a caller compiled against another header must refuse to run (svnet_amd/_lib.py does).                   */
-#define SVNET_ABI_VERSION 426
+#define SVNET_ABI_VERSION 427
 int svnet_version(void);
 const char* svnet_last_error(void);
 
@@ -844,6 +844,35 @@ int svnet_three_interpolate_bwd_f32(const float* dout, const float* weight, cons
                                     int64_t D, int64_t N, int64_t P, float* dfeat, void* stream);
 int svnet_group_points_bwd_f32(const float* dgrouped, const int32_t* rev_start, const int32_t* rev_edge, int64_t B, int64_t N, int64_t S,
                                int64_t nsample, int64_t D, float* dpoints, void* stream);
+
+/* ------------------------------------------------------------------ multi-scale grouping: one pass over the cloud for R radii
+ * (models/utils/pointnet_util.py:210-267 PointNetSetAbstractionMsg).  `scales` = R, 1 .. SVNET_MSG_MAX_SCALES; r2 [R] fp32 and
+ * nsample [R] int64 are HOST arrays, read during the call and handed to the kernels by value: no device copy, no host read of device
+ * memory, so every call below can be captured.  Ktot = sum nsample[i], off_i = nsample[0] + .. + nsample[i-1].  Radii need not be
+ * ascending and may repeat.  Distance, membership, order, padding, the empty group and the clamp are those of the block above.
+ * svnet_ball_query_msg_f32: xyz [B,N,3], new_xyz [B,S,3] -> idx [B,S,Ktot] int64, count [B,S,R] int32.  A centre's row is the R lists
+ *     end to end: columns off_i .. off_i + nsample[i] - 1 and count[..,i] are exactly what svnet_ball_query_f32 gives for
+ *     (r2[i], nsample[i]).  One launch: a candidate's distance is computed once, every scale that is not yet full takes its own
+ *     ballot, the wave leaves a centre when all its scales are full.  Every index written lies in 0 .. N-1.
+ * svnet_group_points_msg_f32: one launch over idx [B,S,Ktot] -> R separate contiguous outputs out_i [B,S,nsample[i],D+3] (out0 .. out3,
+ *     the ones past `scales` ignored).  ATTRIBUTES FIRST: columns 0..D-1 = points[idx,:] bit for bit, columns D..D+2 =
+ *     fl(xyz[idx,c] - new_xyz[s,c]); D = 0 gives [..,3].  An index outside 0 .. N-1 is clamped into it, never followed.
+ * svnet_group_points_msg_bwd_f32: the R upstream gradients dg_i [B,S,nsample[i],D+3] (dg0 .. dg3) and the reverse lists of the
+ *     concatenated idx (svnet_pointset_reverse_i32 with R = S, K = Ktot) -> dpoints [B,N,D] by the ordered sum of the block above:
+ *     ascending edge e = s Ktot + j, that is per centre scale 0's slots, then scale 1's, ...; t_i = column c (the attributes come
+ *     first) of the gradient of the scale slot j lies in.  No float atomic: two runs give the same bits.  D >= 1.
+ * 1 <= scales <= 4, every 1 <= nsample[i] <= N <= 32768, S >= 1, D >= 0 (svnet_group_msg_supported: 1 / 0, a pure host function);
+ * B * ceil(S / 32) <= 2^31 - 1 workgroups and B * S * Ktot <= 2^31 - 1 are refused in the calls with SVNET_E_UNSUPPORTED.          */
+#define SVNET_MSG_MAX_SCALES 4
+int svnet_group_msg_supported(int64_t N, int64_t S, int64_t scales, const int64_t* nsample, int64_t D);
+int svnet_ball_query_msg_f32(const float* xyz, const float* new_xyz, int64_t B, int64_t N, int64_t S, int64_t scales, const float* r2,
+                             const int64_t* nsample, int64_t* idx, int* count, void* stream);
+int svnet_group_points_msg_f32(const float* xyz, const float* new_xyz, const float* points, const int64_t* idx, int64_t B, int64_t N, int64_t S,
+                               int64_t scales, const int64_t* nsample, int64_t D, float* out0, float* out1, float* out2, float* out3,
+                               void* stream);
+int svnet_group_points_msg_bwd_f32(const float* dg0, const float* dg1, const float* dg2, const float* dg3, const int32_t* rev_start,
+                                   const int32_t* rev_edge, int64_t B, int64_t N, int64_t S, int64_t scales, const int64_t* nsample, int64_t D,
+                                   float* dpoints, void* stream);
 
 /* ------------------------------------------------------------------ epoch metrics (main_cls_dgcnn.py:187-251, main_partseg_dgcnn.py:185-279,
  * utils.py:68-91 calculate_shape_IoU; the accuracy scores of sklearn.metrics are functions of the confusion matrix)

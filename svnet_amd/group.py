@@ -50,6 +50,29 @@ Coordinates are data: columns 0..2 of the upstream gradient go nowhere, and xyz,
 device raise.  Limits: 1 <= nsample <= N <= 32768 (the reference
 silently returns N columns when nsample > N; here it is refused), S >= 1, D >= 0, B * ceil(S / 32) <= 2^31 - 1 for the query and
 B * S * nsample <= 2^31 - 1 for the grouping; `sample_and_group` also has farthest point sampling's N <= 16384.
+
+Multi-scale grouping (the reference's PointNetSetAbstractionMsg.forward, lines 229-267: the same centres grouped at R radii):
+
+    idx_cat, count = query_ball_point_msg((0.1, 0.2, 0.4), (16, 32, 128), xyz, new_xyz, return_count=True)   # [B,S,176], [B,S,3]
+    grouped = group_points_msg(xyz, new_xyz, idx_cat, (16, 32, 128), points)        # R tensors [B,S,nsample_i,D+3]
+    new_xyz, grouped = sample_and_group_msg(512, (0.1, 0.2, 0.4), (16, 32, 128), xyz, points)
+
+    query       ONE pass over the cloud for all R radii: a candidate's distance is computed once, every scale that is not yet full
+                tests it against its own r2_i = fp32(radius_i * radius_i) and keeps its own list.  idx_cat [S,Ktot] int64 with
+                Ktot = sum nsample_i: a centre's row is its R lists end to end, list i at columns off_i .. off_i + nsample_i - 1,
+                off_i = nsample_0 + .. + nsample_(i-1) (`split_scales` gives the views); count [S,R] int32.  List i and
+                count[:,i] are EXACTLY what query_ball_point(radius_i, nsample_i, ...) returns: the same distance, `<=`, order,
+                padding and empty-group rule.  Radii need not be ascending and may repeat (the shorter list of two equal radii is
+                then a prefix of the longer).
+    grouping    one launch over idx_cat, R separate contiguous tensors [S,nsample_i,D+3] in the reference's Msg order - ATTRIBUTES
+                FIRST: columns 0..D-1 = points[i,:] copied bit for bit, columns D..D+2 = fl(xyz[i,c] - new_xyz[s,c]); points=None
+                gives [S,nsample_i,3].  (`sample_and_group` writes [xyz | attributes]; the Msg module of the reference does not.)
+    backward    group_points_msg_backward: the reverse lists of idx_cat, edges e = s Ktot + j in ascending e - per centre, scale
+                0's slots, then scale 1's, ... - and t_i = column c of the upstream gradient of the scale that slot j falls in;
+                dpoints[n,c] by the ordered sum above.  No float atomic: two runs give the same bits.
+    limits      1 <= R <= 4 (SVNET_MSG_MAX_SCALES), every 1 <= nsample_i <= N <= 32768, S >= 1, D >= 0, B * ceil(S / 32) <= 2^31 - 1
+                and B * S * Ktot <= 2^31 - 1; `sample_and_group_msg` also has farthest point sampling's N <= 16384.  The radii and
+                nsample travel to the kernels by value: no device copy, no host read, so the calls can be captured.
 """
 import numpy as np
 import torch
@@ -230,6 +253,180 @@ def sample_and_group(npoint, radius, nsample, xyz, points, returnfps=False, star
         return new_xyz, new_points
     grouped_xyz = _pointset.gather_rows(xyz, idx.view(B, S * nsample)).view(B, S, nsample, 3)
     return new_xyz, new_points, grouped_xyz, fps_idx
+
+
+# ---- multi-scale grouping (module docstring: "Multi-scale grouping")
+MAX_SCALES = _lib.DEFINES["SVNET_MSG_MAX_SCALES"]
+
+
+def _scales(name, radius_list, nsample_list):
+    """(R, r2 as a C float array or None, nsample as a C int64 array, the nsample tuple) of a call's scales; radius_list=None where
+    no radius enters.  The C arrays are host memory the entry points read during the call."""
+    nsamples = tuple(int(k) for k in nsample_list)
+    R = len(nsamples)
+    if radius_list is not None and len(radius_list) != R:
+        raise ValueError("%s: %d radii for %d nsample" % (name, len(radius_list), R))
+    if not 1 <= R <= MAX_SCALES:
+        raise ValueError("%s: %d scales, needs 1 .. %d" % (name, R, MAX_SCALES))
+    r2 = None if radius_list is None else (_lib.c_f * R)(*(_r2(r) for r in radius_list))
+    return R, r2, (_lib.c_i64 * R)(*nsamples), nsamples
+
+
+def _supported_msg(name, N, S, R, c_nsample, nsamples, D):
+    if not _lib.lib().svnet_group_msg_supported(N, S, R, c_nsample, D):
+        raise _lib.SvnetHipError("%s: N = %d, S = %d, nsample = %s, D = %d is not supported (1 .. %d scales, every 1 <= nsample <= N <= %d, "
+                                 "S >= 1, D >= 0)" % (name, N, S, list(nsamples), D, MAX_SCALES, _pointset.MAX_N))
+
+
+def _four(tensors):
+    """The pointers of up to four tensors, None past them: the out0 .. out3 / dg0 .. dg3 arguments of the C entry points."""
+    return [_ops._p(t) for t in tensors] + [None] * (MAX_SCALES - len(tensors))
+
+
+def _query_msg_launch(xyz, new_xyz, B, N, S, R, c_r2, c_nsample, idx, count):
+    with torch.cuda.device(xyz.device):
+        _lib.call("svnet_ball_query_msg_f32", _ops._p(xyz), _ops._p(new_xyz), B, N, S, R, c_r2, c_nsample, _ops._p(idx), _ops._p(count),
+                  _ops._stream())
+
+
+def _group_msg_launch(xyz, new_xyz, points, idx_cat, B, N, S, R, c_nsample, nsamples, D, outs=None):
+    """-> the R outputs, allocated here unless `outs` (contiguous [B,S,nsample_i,D+3] float32, unchecked: tools/ only) is given."""
+    if outs is None:
+        outs = [torch.empty(B, S, k, D + 3, dtype=torch.float32, device=xyz.device) for k in nsamples]
+    with torch.cuda.device(xyz.device):
+        _lib.call("svnet_group_points_msg_f32", _ops._p(xyz), _ops._p(new_xyz), _ops._p(points if D else None), _ops._p(idx_cat), B, N, S, R,
+                  c_nsample, D, *_four(outs), _ops._stream())
+    return tuple(outs)
+
+
+def query_ball_point_msg(radius_list, nsample_list, xyz, new_xyz, return_count=False):
+    """query_ball_point for R radii in one pass over the cloud: xyz [B,N,3], new_xyz [B,S,3] -> idx_cat [B,S,Ktot] int64, the R lists
+    of a centre end to end (split_scales gives the views), list i exactly query_ball_point(radius_list[i], nsample_list[i], ...);
+    with return_count also count [B,S,R] int32.  One launch, no host read; no gradient."""
+    _pointset.check_tensors("query_ball_point_msg", {"xyz": xyz, "new_xyz": new_xyz}, (torch.float32, torch.float32), _WHAT)
+    B, N, S = _cloud_shapes("query_ball_point_msg", xyz, new_xyz)
+    R, c_r2, c_nsample, nsamples = _scales("query_ball_point_msg", radius_list, nsample_list)
+    _ops._hip(xyz, new_xyz)
+    _supported_msg("query_ball_point_msg", N, S, R, c_nsample, nsamples, 0)
+    idx = torch.empty(B, S, sum(nsamples), dtype=torch.int64, device=xyz.device)
+    count = torch.empty(B, S, R, dtype=torch.int32, device=xyz.device)
+    _query_msg_launch(xyz, new_xyz, B, N, S, R, c_r2, c_nsample, idx, count)
+    return (idx, count) if return_count else idx
+
+
+def split_scales(idx_cat, nsample_list):
+    """idx_cat [B,S,Ktot] -> the R views [B,S,nsample_i] of its scales (not contiguous: .contiguous() for the single-scale calls)."""
+    nsamples = [int(k) for k in nsample_list]
+    if idx_cat.dim() != 3 or idx_cat.shape[2] != sum(nsamples):
+        raise ValueError("split_scales: idx_cat must be [B,S,%d] for nsample %s, got %s" % (sum(nsamples), nsamples, tuple(idx_cat.shape)))
+    return torch.split(idx_cat, nsamples, dim=2)
+
+
+class _GroupMsg(torch.autograd.Function):
+    """The one-launch multi-scale grouping for points that require grad: R outputs, group_points_msg_backward as the backward
+    (current stream, no host read: capturable).  xyz, new_xyz and idx_cat get no gradient."""
+
+    @staticmethod
+    def forward(ctx, points, xyz, new_xyz, idx_cat, nsamples):
+        (B, N, D), S = points.shape, idx_cat.shape[1]
+        R, _, c_nsample, _ = _scales("group_points_msg", None, nsamples)
+        ctx.save_for_backward(idx_cat)
+        ctx.N, ctx.nsamples = N, nsamples
+        return _group_msg_launch(xyz, new_xyz, points, idx_cat, B, N, S, R, c_nsample, nsamples, D)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *dgrouped):
+        idx_cat, = ctx.saved_tensors
+        return group_points_msg_backward([g.contiguous() for g in dgrouped], idx_cat, ctx.nsamples, ctx.N), None, None, None, None
+
+
+def _group_msg_args(name, xyz, new_xyz, idx_cat, nsample_list, points):
+    tensors, dtypes = _with_points({"xyz": xyz, "new_xyz": new_xyz, "idx_cat": idx_cat}, [torch.float32, torch.float32, torch.int64], points)
+    _pointset.check_tensors(name, tensors, dtypes, _WHAT, grad=("points",))
+    B, N, S = _cloud_shapes(name, xyz, new_xyz)
+    R, _, c_nsample, nsamples = _scales(name, None, nsample_list)
+    if idx_cat.dim() != 3 or idx_cat.shape[0] != B or idx_cat.shape[1] != S or idx_cat.shape[2] != sum(nsamples):
+        raise ValueError("%s: idx_cat must be [B,S,Ktot] with B = %d, S = %d, Ktot = %d, got %s" % (name, B, S, sum(nsamples), tuple(idx_cat.shape)))
+    D = 0 if points is None else _points_shape(name, points, B, N)
+    return B, N, S, R, c_nsample, nsamples, D
+
+
+def group_points_msg(xyz, new_xyz, idx_cat, nsample_list, points=None):
+    """xyz [B,N,3], new_xyz [B,S,3], idx_cat [B,S,Ktot] int64, points [B,N,D] or None -> a tuple of R tensors [B,S,nsample_i,D+3]:
+    per scale the attributes of every group's points FOLLOWED BY their centred coordinates (module docstring).  An index outside
+    [0, N) is clamped into it.  One launch for all scales, no host read.  points may require grad; the rest may not."""
+    B, N, S, R, c_nsample, nsamples, D = _group_msg_args("group_points_msg", xyz, new_xyz, idx_cat, nsample_list, points)
+    _ops._hip(xyz, new_xyz, idx_cat, points)
+    _supported_msg("group_points_msg", N, S, R, c_nsample, nsamples, D)
+    if D and points.requires_grad:
+        return _GroupMsg.apply(points, xyz, new_xyz, idx_cat, nsamples)
+    return _group_msg_launch(xyz, new_xyz, points, idx_cat, B, N, S, R, c_nsample, nsamples, D)
+
+
+def group_points_msg_backward(dgrouped_list, idx_cat, nsample_list, N, out=None):
+    """The gradient of group_points_msg with respect to points: dgrouped_list, R tensors [B,S,nsample_i,D+3] float32 (D >= 1), and
+    idx_cat [B,S,Ktot] int64 -> dpoints [B,N,D], the ordered sums of the module docstring.  Two launches on the current stream (the
+    reverse lists of idx_cat, the sums), no host read; `out` lets a caller keep a fixed buffer.  Every element is written."""
+    dgrouped_list = list(dgrouped_list)
+    R, _, c_nsample, nsamples = _scales("group_points_msg_backward", None, nsample_list)
+    if len(dgrouped_list) != R:
+        raise ValueError("group_points_msg_backward: %d gradients for %d nsample" % (len(dgrouped_list), R))
+    tensors = dict({"dgrouped_%d" % i: g for i, g in enumerate(dgrouped_list)}, idx_cat=idx_cat)
+    _pointset.check_tensors("group_points_msg_backward", tensors, [torch.float32] * R + [torch.int64], _WHAT)
+    W = int(dgrouped_list[0].shape[-1]) if dgrouped_list[0].dim() == 4 else 0
+    if idx_cat.dim() != 3 or idx_cat.shape[0] < 1 or idx_cat.shape[2] != sum(nsamples) or W < 4 or any(
+            tuple(g.shape) != (idx_cat.shape[0], idx_cat.shape[1], k, W) for g, k in zip(dgrouped_list, nsamples)):
+        raise ValueError("group_points_msg_backward: dgrouped_list must be [B,S,nsample_i,D+3] with D >= 1 for nsample %s and idx_cat "
+                         "[B,S,%d], got %s and %s" % (list(nsamples), sum(nsamples), [tuple(g.shape) for g in dgrouped_list], tuple(idx_cat.shape)))
+    B, S, D, N = int(idx_cat.shape[0]), int(idx_cat.shape[1]), W - 3, int(N)
+    _ops._hip(idx_cat, *dgrouped_list)
+    _supported_msg("group_points_msg_backward", N, S, R, c_nsample, nsamples, D)
+    _pointset.reverse_supported("group_points_msg_backward", S, sum(nsamples), N)
+    if out is None:
+        out = torch.empty(B, N, D, dtype=torch.float32, device=idx_cat.device)
+    else:
+        _pointset.check_out("group_points_msg_backward", {"dgrouped_0": dgrouped_list[0]}, out, "[B,N,D]", (B, N, D), _WHAT)
+    rev_start, rev_edge = _pointset.reverse_lists(idx_cat, N)
+    with torch.cuda.device(idx_cat.device):
+        _lib.call("svnet_group_points_msg_bwd_f32", *_four(dgrouped_list), _ops._p(rev_start), _ops._p(rev_edge), B, N, S, R, c_nsample, D,
+                  _ops._p(out), _ops._stream())
+    return out
+
+
+def sample_and_group_msg(npoint, radius_list, nsample_list, xyz, points, start=None, seed=0):
+    """The sampling and grouping of the reference's PointNetSetAbstractionMsg.forward: xyz [B,N,3], points [B,N,D] or None ->
+    (new_xyz [B,npoint,3], a tuple of R tensors [B,npoint,nsample_i,D+3]).  Farthest point sampling -> gather of the centres -> the
+    one-pass query -> the one-launch grouping, on the current stream with no host read between them.  `start` and `seed` as in
+    sample_and_group: a caller that captures the call passes a device tensor.  points may require grad; xyz may not."""
+    tensors, dtypes = _with_points({"xyz": xyz}, [torch.float32], points)
+    if start is not None and isinstance(start, torch.Tensor):
+        tensors["start"] = start
+        dtypes.append(torch.int64)
+    _pointset.check_tensors("sample_and_group_msg", tensors, dtypes, _WHAT, grad=("points",))
+    B, N = _pointset.check_cloud("sample_and_group_msg", "xyz", xyz, "N")
+    S = int(npoint)
+    R, c_r2, c_nsample, nsamples = _scales("sample_and_group_msg", radius_list, nsample_list)
+    D = 0 if points is None else _points_shape("sample_and_group_msg", points, B, N)
+    _ops._hip(xyz, points)
+    _pointset.fps_supported("sample_and_group_msg", "N", N, S)
+    _supported_msg("sample_and_group_msg", N, S, R, c_nsample, nsamples, D)
+    if start is None:
+        start = torch.from_numpy(fps_start(seed, B, N)).to(xyz.device)
+    elif not isinstance(start, torch.Tensor):
+        start = torch.from_numpy(np.ascontiguousarray(start, dtype=np.int64)).to(xyz.device)
+    if tuple(start.shape) != (B,):
+        raise ValueError("sample_and_group_msg: start must be [B] = [%d], got %s" % (B, tuple(start.shape)))
+    dev = xyz.device
+    fps_idx = torch.empty(B, S, dtype=torch.int64, device=dev)
+    _pointset.fps_launch(xyz, B, N, S, start, fps_idx)
+    new_xyz = _pointset.gather_rows(xyz, fps_idx).contiguous()
+    idx = torch.empty(B, S, sum(nsamples), dtype=torch.int64, device=dev)
+    count = torch.empty(B, S, R, dtype=torch.int32, device=dev)
+    _query_msg_launch(xyz, new_xyz, B, N, S, R, c_r2, c_nsample, idx, count)
+    if D and points.requires_grad:
+        return new_xyz, _GroupMsg.apply(points, xyz, new_xyz, idx, nsamples)
+    return new_xyz, _group_msg_launch(xyz, new_xyz, points, idx, B, N, S, R, c_nsample, nsamples, D)
 
 
 def sample_and_group_all(xyz, points):

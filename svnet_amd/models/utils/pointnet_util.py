@@ -13,7 +13,7 @@ Coordinates are data and get no gradient.
 
 Stated divergences from the reference, the ones the helpers have: the difference-form distance (svnet_amd/csrc/pointset.h); the
 start of the sampling is an input - forward(xyz, points, start=None), the default being data.fps_start(self.seed, B, N), uploaded
-once per (B, N, device) and kept; nsample > N is refused; an empty group takes point 0.  `PointNetSetAbstractionMsg` is not here.
+once per (B, N, device) and kept; nsample > N is refused; an empty group takes point 0.  `PointNetSetAbstractionMsg` is in pointnet_msg.py, beside this file.
 There is no CPU fallback: tensors that are not on a HIP device raise.
 """
 import torch
