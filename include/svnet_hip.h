@@ -45,9 +45,9 @@ int svnet_slices_sum_f64(double* buf, int64_t L, void* stream);
 
 /* ABI version = 100 * round-of-change + serial.  It changes whenever an entry point gains / loses an argument or a caller-owned buffer
  * changes its required length (200: sliced accumulators, SVNET_SLICED_LEN; 400: this header; 401: the totals of a sliced accumulator are
- * written by its consumer, svnet_slices_sum_*; 402: GX of svnet_v2s_bwd_*, gw of svnet_xyzblock_bwd_f32 and col_sum of svnet_gemm_f32 are sliced accumulators; 403: svnet_binweight_grad_f32 takes sliced inputs; 421: svnet_three_nn_f32, svnet_three_interpolate_f32; 422: svnet_ball_query_f32, svnet_group_points_f32; 423: svnet_vlinear_stats_f32 is gone; 424: svnet_edgeblock_fwd_tier, svnet_edgeblock_bwd_tier, svnet_edgeblock_wgrad_tier, svnet_xyzblock_tier; 425: svnet_pointset_reverse_i32, svnet_three_interpolate_bwd_f32, svnet_group_points_bwd_f32; 426: wbt of svnet_edgeblock_wbt_bf16 is 512 values longer, the all-zero fragment; 427: svnet_ball_query_msg_f32, svnet_group_points_msg_f32, svnet_group_points_msg_bwd_f32).  svnet_version() returns the value the
+ * written by its consumer, svnet_slices_sum_*; 402: GX of svnet_v2s_bwd_*, gw of svnet_xyzblock_bwd_f32 and col_sum of svnet_gemm_f32 are sliced accumulators; 403: svnet_binweight_grad_f32 takes sliced inputs; 421: svnet_three_nn_f32, svnet_three_interpolate_f32; 422: svnet_ball_query_f32, svnet_group_points_f32; 423: svnet_vlinear_stats_f32 is gone; 424: svnet_edgeblock_fwd_tier, svnet_edgeblock_bwd_tier, svnet_edgeblock_wgrad_tier, svnet_xyzblock_tier; 425: svnet_pointset_reverse_i32, svnet_three_interpolate_bwd_f32, svnet_group_points_bwd_f32; 426: wbt of svnet_edgeblock_wbt_bf16 is 512 values longer, the all-zero fragment; 427: svnet_ball_query_msg_f32, svnet_group_points_msg_f32, svnet_group_points_msg_bwd_f32; 428: svnet_sa_fold_f32, svnet_sa_fused_f32).  svnet_version() returns the value the
  * library was BUILT with: a caller compiled against another header must refuse to run (svnet_amd/_lib.py does).                   */
-#define SVNET_ABI_VERSION 427
+#define SVNET_ABI_VERSION 428
 int svnet_version(void);
 const char* svnet_last_error(void);
 
@@ -873,6 +873,39 @@ int svnet_group_points_msg_f32(const float* xyz, const float* new_xyz, const flo
 int svnet_group_points_msg_bwd_f32(const float* dg0, const float* dg1, const float* dg2, const float* dg3, const int32_t* rev_start,
                                    const int32_t* rev_edge, int64_t B, int64_t N, int64_t S, int64_t scales, const int64_t* nsample, int64_t D,
                                    float* dpoints, void* stream);
+
+/* ------------------------------------------------------------------ fused set-abstraction level for inference: group, shared MLP, max
+ * (models/utils/pointnet_util.py:166-267, the eval-mode forward of PointNetSetAbstraction / PointNetSetAbstractionMsg after the query).
+ * A level has L layers, 1 <= L <= SVNET_SA_MAX_LAYERS, of 1x1 convolution + BatchNorm (running statistics) + ReLU; its input width is
+ * C0 = 3 + D, its layer widths C1 .. CL.  fl() is rounding to fp32; every operation is rounded once.
+ * svnet_sa_fold_f32: one layer's convolution W [O,C], b [O] and BatchNorm gamma, beta, running_mean, running_var [O] -> Wf [O,C], bf [O]
+ *     (plain, unpadded, caller-owned).  One launch, no host read: it can be captured and repeated after the parameters change.
+ *         invstd[o] = fl(1 / fl(sqrt(fl(var[o] + eps))))     (svnet_bn_eval_stats_f32's; division and square root correctly rounded)
+ *         s[o] = fl(gamma[o] invstd[o]);   Wf[o,c] = fl(W[o,c] s[o]);   bf[o] = fl(fl(fl(b[o] - mean[o]) s[o]) + beta[o])
+ *     never contracted.  1 <= O, 1 <= C, O * C <= 2^31 - 1.
+ * svnet_sa_fused_f32: per cloud xyz [N,3], new_xyz [S,3], points [N,D] (NULL when D = 0), idx [S,K] int64 with row stride idx_ld >= K
+ *     (a scale's columns of a concatenated table are used where they lie), count [S] int32 with element stride count_ld or NULL;
+ *     wf and bf are HOST arrays of L device pointers (the folded layers) and widths a HOST array of the L widths C1 .. CL, read during the
+ *     call and handed to the kernel by value: no device copy, no workspace, one launch.
+ *         row j of centre s: n = idx[s,j] clamped into 0 .. N-1 (svnet_group_points_f32's clamp); h0 = [fl(xyz[n,c] - new_xyz[s,c]) c = 0..2 |
+ *         points[n,:] bit for bit] with xyz_last = 0, [points[n,:] | the three differences] with xyz_last = 1 (the multi-scale order).
+ *         per layer and output o: acc = bf[o]; for c ascending acc = fmaf(h[c], Wf[o,c], acc); h'[o] = acc > 0 ? acc : +0.
+ *         out[b, c_off + o, s] = max_j hL_j[o], channel-first into out [B,C_total,S]; the other channels are left as they are.
+ *     The products run on v_mfma_f32_16x16x4_f32, bit for bit that fmaf chain; K is never split, so a value does not depend on how rows,
+ *     columns or centres are tiled, and the zero padding of K adds exact zeros.  With count, the slots >= max(count[s], 1) are skipped:
+ *     they repeat slot 0 (svnet_ball_query_f32's padding and empty group), so the maximum is that of all slots.  Inputs are assumed
+ *     finite.  svnet_sa_fused_supported (1 / 0, a pure host function): 1 <= K <= N <= 32768, S >= 1, 0 <= D <= 321 (C0 <= 324),
+ *     1 <= L <= 4, every 1 <= width <= 256.  B * ceil(S / centres per workgroup) <= 2^31 - 1 and B * S * idx_ld <= 2^31 - 1 are refused in
+ *     the call with SVNET_E_UNSUPPORTED.  svnet_sa_fused_rows_tile: the grouped rows one workgroup multiplies at a time - a group of
+ *     more slots than that takes further tiles, a smaller one shares its tile with the next centres.                                 */
+#define SVNET_SA_MAX_LAYERS 4
+int svnet_sa_fold_f32(const float* W, const float* b, const float* gamma, const float* beta, const float* running_mean,
+                      const float* running_var, int64_t O, int64_t C, float eps, float* Wf, float* bf, void* stream);
+int svnet_sa_fused_supported(int64_t N, int64_t S, int64_t K, int64_t D, int64_t L, const int64_t* widths);
+int svnet_sa_fused_rows_tile(void);
+int svnet_sa_fused_f32(const float* xyz, const float* new_xyz, const float* points, const int64_t* idx, int64_t idx_ld, const int* count,
+                       int64_t count_ld, int64_t B, int64_t N, int64_t S, int64_t K, int64_t D, int64_t L, const int64_t* widths,
+                       const void* wf, const void* bf, int xyz_last, float* out, int64_t C_total, int64_t c_off, void* stream);
 
 /* ------------------------------------------------------------------ epoch metrics (main_cls_dgcnn.py:187-251, main_partseg_dgcnn.py:185-279,
  * utils.py:68-91 calculate_shape_IoU; the accuracy scores of sklearn.metrics are functions of the confusion matrix)

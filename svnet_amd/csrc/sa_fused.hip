@@ -1,0 +1,329 @@
+// Fused set-abstraction level for inference: the eval-mode forward of PointNetSetAbstraction / PointNetSetAbstractionMsg after the
+// query (models/utils/pointnet_util.py:166-267) - grouping, the stack of 1x1 convolution + BatchNorm + ReLU and the max over a group -
+// as ONE launch that writes C_out floats per centre and nothing else.  The contract is in include/svnet_hip.h ("fused set-abstraction
+// level") and svnet_amd/sa_fused.py; tests/sa_fused_ref.py restates it.  Two kernels:
+//   sa_fold_kernel   BatchNorm's running statistics folded into a layer's weights and bias, every operation rounded once.
+//   sa_fused_kernel  a workgroup takes a tile of SF_ROWS grouped rows - whole centres when a group has at most SF_ROWS slots, else the
+//                    tiles of one centre one after the other - gathers them into LDS and runs the layers on v_mfma_f32_16x16x4_f32
+//                    (bit for bit a c-ascending fmaf chain that starts at the bias; a wave owns 16-column tiles over the full K, so no
+//                    value depends on the tiling).  Activations ping-pong between two LDS buffers, weights come from global memory
+//                    (L2-resident) into registers, 8 k-steps ahead.  The last layer is not stored: its ReLU output, >= +0, goes into a per-centre column maximum by an
+//                    integer LDS maximum on the bit patterns, which is order-free.
+// Built with -ffp-contract=off (Makefile, NO_CONTRACT).
+#include "pointset.h"
+
+namespace {
+
+typedef __attribute__((ext_vector_type(4))) float f32x4;
+
+constexpr int SF_THREADS = 256, SF_WAVES = SF_THREADS / SVNET_WAVE;
+constexpr int SF_ROWS = 64;                                      // grouped rows per tile: four 16-row MFMA tiles
+constexpr int SF_MAX_C0 = 324, SF_MAX_WIDTH = 256;               // the envelope (svnet_sa_fused_supported)
+constexpr int SF_MAX_FLOATS = 2048;                              // the running maxima: centres per workgroup x padded last width, at most
+constexpr int SF_LDS_MAX = 160 * 1024;
+constexpr int SF_U = 8;                                          // k-steps whose weights a lane holds at a time: 32 channels
+constexpr int SF_HEAD = SF_ROWS * 8 + SF_ROWS * 4 + (SF_ROWS + 4) * 4 + SF_ROWS * 4;      // s_src | s_ctr | s_start (+ total) | s_lim
+static_assert(SF_HEAD % 16 == 0, "the float regions behind the row tables stay 16-byte aligned");
+
+inline int pad_to(int64_t v, int m) { return (int)((v + m - 1) / m * m); }
+
+// The folded layers and widths of a call handed to the kernel by value: no device copy.  C[0] = 3 + D, C[l] = width of layer l.
+struct SaLevel {
+    const float* w[SVNET_SA_MAX_LAYERS];
+    const float* b[SVNET_SA_MAX_LAYERS];
+    int C[SVNET_SA_MAX_LAYERS + 1];
+    int L;
+};
+// cpw: centres per workgroup; stride[p]: row stride of the activation buffer p (layer l reads buffer l & 1 and writes the other one),
+// 4 times an odd number: the 16 rows x 4 channels of an A fragment, and the 16 columns x 4 row quads of a result, then fall into 64
+// different banks; opad: the last width padded to whole column tiles.
+struct SaPlan { int cpw, stride[2], opad, lds; };
+
+inline bool sa_plan(int64_t N, int64_t S, int64_t K, int64_t D, int64_t L, const int64_t* widths, SaPlan& pl) {
+    if (!widths || L < 1 || L > SVNET_SA_MAX_LAYERS || !svnet_group_supported(N, S, K, D) || 3 + D > SF_MAX_C0) return false;
+    for (int64_t l = 0; l < L; ++l)
+        if (widths[l] < 1 || widths[l] > SF_MAX_WIDTH) return false;
+    pl = SaPlan{};
+    pl.opad = pad_to(widths[L - 1], 16);
+    for (int64_t l = 0; l < L; ++l) {
+        const int c = pad_to(l ? widths[l - 1] : 3 + D, 4), s = c % 8 ? c : c + 4;
+        if (s > pl.stride[l & 1]) pl.stride[l & 1] = s;
+    }
+    const int fixed = SF_HEAD + 4 * SF_ROWS * (pl.stride[0] + pl.stride[1]);
+    int64_t room = (SF_LDS_MAX - fixed) / 4;                     // floats left for the maxima
+    if (room > SF_MAX_FLOATS) room = SF_MAX_FLOATS;
+    const int64_t fit = room / pl.opad, whole = SF_ROWS / K;
+    if (fit < 1) return false;                                   // (not inside the envelope: 324 and 256 columns leave room for 3000)
+    pl.cpw = (int)(whole < 1 ? 1 : whole < fit ? whole : fit);
+    pl.lds = fixed + 4 * pl.cpw * pl.opad;
+    return true;
+}
+
+__global__ __launch_bounds__(SF_THREADS) void sa_fold_kernel(const float* __restrict__ W, const float* __restrict__ b, const float* __restrict__ gamma,
+                                                             const float* __restrict__ beta, const float* __restrict__ rmean,
+                                                             const float* __restrict__ rvar, int64_t OC, int C, float eps,
+                                                             float* __restrict__ Wf, float* __restrict__ bf) {
+    const int64_t e = (int64_t)blockIdx.x * SF_THREADS + threadIdx.x;
+    if (e >= OC) return;
+    const int64_t o = e / C;
+    const float invstd = 1.f / sqrtf(rvar[o] + eps);             // bn_eval_stats_kernel's (norm.hip)
+    const float s = gamma[o] * invstd;
+    Wf[e] = W[e] * s;
+    if (e == o * C) bf[o] = (b[o] - rmean[o]) * s + beta[o];
+}
+
+// The B operands of one lane for SF_U k-steps from channel c on, step u at channel c + 4 u: Wf[o][c + 4 u] of the lane's column o.  A
+// channel past the row is an exact zero; its load reads the row's last weight instead, so that no load needs a branch.
+// (W is wave-uniform and row = o Cin a 32-bit lane offset: the loads take the SGPR-base form and keep no 64-bit address per load.)
+__device__ __forceinline__ void sa_weights(const float* __restrict__ W, int row, int Cin, int c, float (&w)[SF_U]) {
+#pragma unroll
+    for (int u = 0; u < SF_U; ++u) {
+        const int cu = c + 4 * u;
+        const float x = ld_f32_sbase_fresh(W, (uint32_t)(row + (cu < Cin ? cu : Cin - 1)) * 4u);
+        w[u] = cu < Cin ? x : 0.f;
+    }
+}
+
+// One layer over the NRT 16-row tiles of the workgroup's rows.  A wave takes the column tiles wave, wave + 4, ...  A lane holds the B
+// operands of its column o = 16 ct + lane % 16 for SF_U k-steps (channels k0 + lane / 16 + 4 u) in registers, straight from global
+// memory, and the next SF_U - of this tile or, at its end, of the wave's next tile - are under way while these multiply.  More steps
+// in flight, or the activations read ahead of their products, cost registers, and a fourth wave per SIMD was worth more than either
+// (DESIGN.md 4.20).  The A operands (row 16 rt + lane % 16, channel k0 + lane / 16) come from the activation buffer and feed NRT
+// independent accumulators that started at the bias.  A lane of a result holds column lane % 16 of rows 4 (lane / 16) + 0..3.  LAST: the ReLU
+// outputs go into the centres' maxima instead of LDS.
+template <int NRT, bool LAST>
+__device__ __forceinline__ void sa_layer(const float* __restrict__ W, const float* __restrict__ bias, int Cin, int O, const float* in, int sin,
+                                         float* outb, int sout, const int* s_ctr, unsigned* smax, int opad, int wave, int lane) {
+    const int r16 = lane & 15, q = lane >> 4;
+    const int Kp = (Cin + 3) & ~3, Op = (O + 3) & ~3, nct = (O + 15) >> 4;
+    const float* arow = in + r16 * sin + q;
+    float wc[SF_U], wn[SF_U];
+    if (wave < nct) {
+        const int o = wave * 16 + r16;
+        sa_weights(W, (o < O ? o : O - 1) * Cin, Cin, q, wc);
+    }
+    for (int ct = wave; ct < nct; ct += SF_WAVES) {
+        const int o = ct * 16 + r16, on = o + 16 * SF_WAVES;
+        const bool ov = o < O;
+        const int wrow = (ov ? o : O - 1) * Cin, wnext = (on < O ? on : O - 1) * Cin;      // (past the last tile: loaded, never used)
+        const float b0 = ov ? bias[o] : 0.f;
+        f32x4 acc[NRT];
+#pragma unroll
+        for (int rt = 0; rt < NRT; ++rt) acc[rt] = f32x4{b0, b0, b0, b0};
+        for (int k0 = 0; k0 < Kp; k0 += 4 * SF_U) {
+            if (k0 + 4 * SF_U < Kp) sa_weights(W, wrow, Cin, k0 + 4 * SF_U + q, wn);
+            else sa_weights(W, wnext, Cin, q, wn);
+#pragma unroll
+            for (int u = 0; u < SF_U; ++u) {
+                if (k0 + 4 * u >= Kp) break;                     // (wave-uniform)
+#pragma unroll
+                for (int rt = 0; rt < NRT; ++rt)
+                    acc[rt] = __builtin_amdgcn_mfma_f32_16x16x4f32(arow[rt * 16 * sin + k0 + 4 * u], wc[u], acc[rt], 0, 0, 0);
+            }
+#pragma unroll
+            for (int u = 0; u < SF_U; ++u) wc[u] = wn[u];
+        }
+#pragma unroll
+        for (int rt = 0; rt < NRT; ++rt) {
+            const int row = rt * 16 + q * 4;
+            float v[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) v[i] = ov && acc[rt][i] > 0.f ? acc[rt][i] : 0.f;      // a column past the layer's: zero
+            if (!LAST) {
+                if (o < Op) {                                    // up to the next layer's padded K: zeros
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) outb[(row + i) * sout + o] = v[i];
+                }
+            } else if (ov) {
+                // rows ascend, so a centre's rows are adjacent: one maximum per run of equal centres; -1 marks a row past the tile's
+                const int4 cv = *reinterpret_cast<const int4*>(s_ctr + row);
+                const int ctr[4] = {cv.x, cv.y, cv.z, cv.w};
+                int cur = ctr[0];
+                float m = v[0];
+#pragma unroll
+                for (int i = 1; i < 4; ++i) {
+                    if (ctr[i] != cur) {
+                        if (cur >= 0) atomicMax(smax + cur * opad + o, __float_as_uint(m));
+                        cur = ctr[i];
+                        m = v[i];
+                    } else {
+                        m = m > v[i] ? m : v[i];
+                    }
+                }
+                if (cur >= 0) atomicMax(smax + cur * opad + o, __float_as_uint(m));
+            }
+        }
+    }
+}
+
+template <bool LAST>
+__device__ __forceinline__ void sa_layer_rt(int nrt, const float* W, const float* bias, int Cin, int O, const float* in, int sin, float* outb,
+                                            int sout, const int* s_ctr, unsigned* smax, int opad, int wave, int lane) {
+    switch (nrt) {
+        case 1: sa_layer<1, LAST>(W, bias, Cin, O, in, sin, outb, sout, s_ctr, smax, opad, wave, lane); break;
+        case 2: sa_layer<2, LAST>(W, bias, Cin, O, in, sin, outb, sout, s_ctr, smax, opad, wave, lane); break;
+        case 3: sa_layer<3, LAST>(W, bias, Cin, O, in, sin, outb, sout, s_ctr, smax, opad, wave, lane); break;
+        default: sa_layer<4, LAST>(W, bias, Cin, O, in, sin, outb, sout, s_ctr, smax, opad, wave, lane); break;
+    }
+}
+
+__global__ __launch_bounds__(SF_THREADS) __attribute__((amdgpu_waves_per_eu(4, 4))) void sa_fused_kernel(const float* __restrict__ xyz, const float* __restrict__ new_xyz,
+                                                              const float* __restrict__ points, const int64_t* __restrict__ idx, int64_t idx_ld,
+                                                              const int* __restrict__ count, int64_t count_ld, int64_t N, int64_t S, int K,
+                                                              int D, int64_t chunks, SaLevel lv, SaPlan pl, int xyz_last,
+                                                              float* __restrict__ out, int64_t C_total, int64_t c_off) {
+    extern __shared__ __align__(16) unsigned char sf_lds[];
+    int64_t* s_src = reinterpret_cast<int64_t*>(sf_lds);                        // [SF_ROWS] b * N + the row's point
+    int* s_ctr = reinterpret_cast<int*>(sf_lds + SF_ROWS * 8);                  // [SF_ROWS] the row's centre in the workgroup, -1: no row
+    int* s_start = s_ctr + SF_ROWS;                                             // [SF_ROWS + 4] a centre's first row; [SF_ROWS]: all rows
+    int* s_lim = s_start + SF_ROWS + 4;                                         // [SF_ROWS] a centre's rows
+    unsigned* smax = reinterpret_cast<unsigned*>(sf_lds + SF_HEAD);             // [cpw][opad] bit patterns of the maxima, all >= +0
+    float* buf0 = reinterpret_cast<float*>(smax + pl.cpw * pl.opad);
+    float* buf1 = buf0 + SF_ROWS * pl.stride[0];
+
+    const int t = threadIdx.x, lane = lane_id();
+    const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
+    const int64_t b = blockIdx.x / chunks;
+    const int64_t s0 = (blockIdx.x % chunks) * pl.cpw;                          // this workgroup's first centre
+    const int ncen = (int)(S - s0 < pl.cpw ? S - s0 : pl.cpw);
+    const int C0 = 3 + D, C0p = (C0 + 3) & ~3, OL = lv.C[lv.L];
+
+    if (wave == 0) {                                                            // the centres' row counts and their running sum
+        int lim = 0;
+        if (lane < ncen) {
+            lim = K;
+            if (count) {
+                const int c = count[(b * S + s0 + lane) * count_ld];
+                lim = c < 1 ? 1 : c < K ? c : K;
+            }
+        }
+        int inc = lim;
+#pragma unroll
+        for (int o = 1; o < SVNET_WAVE; o <<= 1) {
+            const int v = __shfl_up(inc, o, SVNET_WAVE);
+            if (lane >= o) inc += v;
+        }
+        s_lim[lane] = lim;
+        s_start[lane] = inc - lim;
+        if (lane == SVNET_WAVE - 1) s_start[SF_ROWS] = inc;
+    }
+    for (int e = t; e < ncen * pl.opad; e += SF_THREADS) smax[e] = 0u;
+    __syncthreads();
+    const int total = __builtin_amdgcn_readfirstlane(s_start[SF_ROWS]);        // >= 1; at most SF_ROWS unless cpw = 1
+
+    for (int base = 0; base < total; base += SF_ROWS) {
+        const int nrows = total - base < SF_ROWS ? total - base : SF_ROWS;
+        const int nrt = (nrows + 15) >> 4;
+        if (wave == 0) {                                                        // the rows' points: one wave, its LDS writes keep their order
+            s_ctr[lane] = -1;
+            int c = 0, j = base + lane;                                         // one centre, tile by tile
+            bool on = lane < nrows;
+            if (K < SF_ROWS) {                                                  // whole centres: lane = centre * K + slot
+                c = lane / K;
+                j = lane - c * K;
+                on = c < ncen && j < s_lim[c];
+            }
+            if (on) {
+                const int r = K < SF_ROWS ? s_start[c] + j : lane;
+                s_src[r] = b * N + clamp_index(idx[(b * S + s0 + c) * idx_ld + j], N);
+                s_ctr[r] = c;
+            }
+        }
+        __syncthreads();
+        {                                                                       // the centred rows, zero where there is no row or column
+            const int totalE = nrt * 16 * C0p;
+            const int qstep = SF_THREADS / C0p, rstep = SF_THREADS % C0p;
+            int row = t / C0p, col = t % C0p;
+            for (int e = t; e < totalE; e += SF_THREADS) {
+                const int c = s_ctr[row];
+                float v = 0.f;
+                if (c >= 0 && col < C0) {
+                    const int64_t src = s_src[row];
+                    const int x = xyz_last ? col - D : col;                     // the coordinate, where 0 <= x < 3
+                    if (x >= 0 && x < 3) v = xyz[src * 3 + x] - new_xyz[(b * S + s0 + c) * 3 + x];
+                    else v = points[src * D + (xyz_last ? col : col - 3)];
+                }
+                buf0[row * pl.stride[0] + col] = v;
+                col += rstep; row += qstep;
+                if (col >= C0p) { col -= C0p; ++row; }
+            }
+        }
+        __syncthreads();
+        for (int l = 0; l < lv.L; ++l) {
+            const float* in = l & 1 ? buf1 : buf0;
+            float* outb = l & 1 ? buf0 : buf1;
+            const int sin = pl.stride[l & 1], sout = pl.stride[(l & 1) ^ 1];
+            if (l + 1 < lv.L) sa_layer_rt<false>(nrt, lv.w[l], lv.b[l], lv.C[l], lv.C[l + 1], in, sin, outb, sout, s_ctr, smax, pl.opad, wave, lane);
+            else sa_layer_rt<true>(nrt, lv.w[l], lv.b[l], lv.C[l], lv.C[l + 1], in, sin, outb, sout, s_ctr, smax, pl.opad, wave, lane);
+            __syncthreads();
+        }
+    }
+    // channel-first: the workgroup's centres of a channel lie side by side
+    float* dst = out + (b * C_total + c_off) * S + s0;
+    for (int e = t; e < ncen * OL; e += SF_THREADS) {
+        const int o = e / ncen, sl = e - o * ncen;
+        dst[(int64_t)o * S + sl] = __uint_as_float(smax[sl * pl.opad + o]);
+    }
+}
+
+}  // namespace
+
+extern "C" int svnet_sa_fused_rows_tile(void) { return SF_ROWS; }
+
+extern "C" int svnet_sa_fused_supported(int64_t N, int64_t S, int64_t K, int64_t D, int64_t L, const int64_t* widths) {
+    SaPlan pl;
+    return sa_plan(N, S, K, D, L, widths, pl) ? 1 : 0;
+}
+
+extern "C" int svnet_sa_fold_f32(const float* W, const float* b, const float* gamma, const float* beta, const float* running_mean,
+                                 const float* running_var, int64_t O, int64_t C, float eps, float* Wf, float* bf, void* stream) {
+    SVNET_REQUIRE(W && b && gamma && beta && running_mean && running_var && Wf && bf, SVNET_E_ARG,
+                  "svnet_sa_fold_f32: null W / b / gamma / beta / running_mean / running_var / Wf / bf");
+    SVNET_REQUIRE(O >= 1 && C >= 1, SVNET_E_ARG, "svnet_sa_fold_f32: O %lld and C %lld must be positive", (long long)O, (long long)C);
+    SVNET_REQUIRE(O <= 0x7fffffffll / C, SVNET_E_UNSUPPORTED, "svnet_sa_fold_f32: O %lld x C %lld weights > 2^31 - 1", (long long)O, (long long)C);
+    hipLaunchKernelGGL(sa_fold_kernel, dim3((unsigned)svnet_cdiv(O * C, SF_THREADS)), dim3(SF_THREADS), 0, (hipStream_t)stream, W, b, gamma, beta,
+                       running_mean, running_var, O * C, (int)C, eps, Wf, bf);
+    SVNET_CHECK_LAUNCH("sa_fold_kernel");
+    return SVNET_OK;
+}
+
+extern "C" int svnet_sa_fused_f32(const float* xyz, const float* new_xyz, const float* points, const int64_t* idx, int64_t idx_ld, const int* count,
+                                  int64_t count_ld, int64_t B, int64_t N, int64_t S, int64_t K, int64_t D, int64_t L, const int64_t* widths,
+                                  const void* wf, const void* bf, int xyz_last, float* out, int64_t C_total, int64_t c_off, void* stream) {
+    SVNET_REQUIRE(xyz && new_xyz && idx && widths && wf && bf && out, SVNET_E_ARG, "svnet_sa_fused_f32: null xyz / new_xyz / idx / widths / wf / bf / out");
+    SVNET_REQUIRE(points || D == 0, SVNET_E_ARG, "svnet_sa_fused_f32: null points with D %lld > 0", (long long)D);
+    SVNET_REQUIRE(B >= 1, SVNET_E_ARG, "svnet_sa_fused_f32: B %lld must be positive", (long long)B);
+    SaPlan pl;
+    SVNET_REQUIRE(sa_plan(N, S, K, D, L, widths, pl), SVNET_E_UNSUPPORTED,
+                  "svnet_sa_fused_f32: N %lld, S %lld, K %lld, D %lld, L %lld: needs 1 <= K <= N <= %lld, S >= 1, 0 <= D <= %d, 1 <= L <= %d, every 1 <= width <= %d",
+                  (long long)N, (long long)S, (long long)K, (long long)D, (long long)L, (long long)SVNET_KNN_MAX_N, SF_MAX_C0 - 3,
+                  SVNET_SA_MAX_LAYERS, SF_MAX_WIDTH);
+    SVNET_REQUIRE(idx_ld >= K && (!count || count_ld >= 1), SVNET_E_ARG, "svnet_sa_fused_f32: idx_ld %lld < K %lld, or count_ld %lld < 1",
+                  (long long)idx_ld, (long long)K, (long long)count_ld);
+    SVNET_REQUIRE(c_off >= 0 && c_off + widths[L - 1] <= C_total, SVNET_E_ARG, "svnet_sa_fused_f32: channels %lld .. %lld outside C_total %lld",
+                  (long long)c_off, (long long)(c_off + widths[L - 1]), (long long)C_total);
+    SVNET_REQUIRE(B <= 0x7fffffffll / S / idx_ld, SVNET_E_UNSUPPORTED, "svnet_sa_fused_f32: B %lld x S %lld x idx_ld %lld indices > 2^31 - 1",
+                  (long long)B, (long long)S, (long long)idx_ld);
+    SaLevel lv = {};
+    lv.L = (int)L;
+    lv.C[0] = (int)(3 + D);
+    const float* const* w = static_cast<const float* const*>(wf);
+    const float* const* bb = static_cast<const float* const*>(bf);
+    for (int l = 0; l < lv.L; ++l) {
+        SVNET_REQUIRE(w[l] && bb[l], SVNET_E_ARG, "svnet_sa_fused_f32: null wf[%d] / bf[%d]", l, l);
+        lv.w[l] = w[l];
+        lv.b[l] = bb[l];
+        lv.C[l + 1] = (int)widths[l];
+    }
+    const CloudGrid grid = cloud_grid(B, S, pl.cpw);
+    SVNET_REQUIRE(grid.blocks > 0, SVNET_E_UNSUPPORTED, "svnet_sa_fused_f32: B %lld x ceil(S %lld / %d) workgroups > 2^31 - 1", (long long)B,
+                  (long long)S, pl.cpw);
+    bool ok = true;
+    if (pl.lds > 64 * 1024) SVNET_LDS_OPTIN(ok, SF_LDS_MAX, "svnet_sa_fused_f32", reinterpret_cast<const void*>(&sa_fused_kernel));
+    if (!ok) return SVNET_E_LAUNCH;
+    if (!points) points = xyz;                                   // D = 0: never read
+    hipLaunchKernelGGL(sa_fused_kernel, dim3((unsigned)grid.blocks), dim3(SF_THREADS), (size_t)pl.lds, (hipStream_t)stream, xyz, new_xyz, points, idx,
+                       idx_ld, count, count_ld, N, S, (int)K, (int)D, grid.chunks, lv, pl, xyz_last, out, C_total, c_off);
+    SVNET_CHECK_LAUNCH("sa_fused_kernel");
+    return SVNET_OK;
+}
