@@ -45,9 +45,9 @@ int svnet_slices_sum_f64(double* buf, int64_t L, void* stream);
 
 /* ABI version = 100 * round-of-change + serial.  It changes whenever an entry point gains / loses an argument or a caller-owned buffer
  * changes its required length (200: sliced accumulators, SVNET_SLICED_LEN; 400: this header; 401: the totals of a sliced accumulator are
- * written by its consumer, svnet_slices_sum_*; 402: GX of svnet_v2s_bwd_*, gw of svnet_xyzblock_bwd_f32 and col_sum of svnet_gemm_f32 are sliced accumulators; 403: svnet_binweight_grad_f32 takes sliced inputs; 421: svnet_three_nn_f32, svnet_three_interpolate_f32; 422: svnet_ball_query_f32, svnet_group_points_f32; 423: svnet_vlinear_stats_f32 is gone; 424: svnet_edgeblock_fwd_tier, svnet_edgeblock_bwd_tier, svnet_edgeblock_wgrad_tier, svnet_xyzblock_tier; 425: svnet_pointset_reverse_i32, svnet_three_interpolate_bwd_f32, svnet_group_points_bwd_f32; 426: wbt of svnet_edgeblock_wbt_bf16 is 512 values longer, the all-zero fragment; 427: svnet_ball_query_msg_f32, svnet_group_points_msg_f32, svnet_group_points_msg_bwd_f32; 428: svnet_sa_fold_f32, svnet_sa_fused_f32).  svnet_version() returns the value the
+ * written by its consumer, svnet_slices_sum_*; 402: GX of svnet_v2s_bwd_*, gw of svnet_xyzblock_bwd_f32 and col_sum of svnet_gemm_f32 are sliced accumulators; 403: svnet_binweight_grad_f32 takes sliced inputs; 421: svnet_three_nn_f32, svnet_three_interpolate_f32; 422: svnet_ball_query_f32, svnet_group_points_f32; 423: svnet_vlinear_stats_f32 is gone; 424: svnet_edgeblock_fwd_tier, svnet_edgeblock_bwd_tier, svnet_edgeblock_wgrad_tier, svnet_xyzblock_tier; 425: svnet_pointset_reverse_i32, svnet_three_interpolate_bwd_f32, svnet_group_points_bwd_f32; 426: wbt of svnet_edgeblock_wbt_bf16 is 512 values longer, the all-zero fragment; 427: svnet_ball_query_msg_f32, svnet_group_points_msg_f32, svnet_group_points_msg_bwd_f32; 428: svnet_sa_fold_f32, svnet_sa_fused_f32; 429: svnet_fp_fused_f32, svnet_fp_fused_supported, svnet_fp_fused_rows_tile).  svnet_version() returns the value the
  * library was BUILT with: a caller compiled against another header must refuse to run (svnet_amd/_lib.py does).                   */
-#define SVNET_ABI_VERSION 428
+#define SVNET_ABI_VERSION 429
 int svnet_version(void);
 const char* svnet_last_error(void);
 
@@ -906,6 +906,32 @@ int svnet_sa_fused_rows_tile(void);
 int svnet_sa_fused_f32(const float* xyz, const float* new_xyz, const float* points, const int64_t* idx, int64_t idx_ld, const int* count,
                        int64_t count_ld, int64_t B, int64_t N, int64_t S, int64_t K, int64_t D, int64_t L, const int64_t* widths,
                        const void* wf, const void* bf, int xyz_last, float* out, int64_t C_total, int64_t c_off, void* stream);
+
+/* ------------------------------------------------------------------ fused feature-propagation level for inference: interpolate, skip, MLP
+ * (models/utils/pointnet_util.py:84-92, the eval-mode forward of PointNetFeaturePropagation behind svnet_three_nn_f32).  A level has L
+ * layers, 1 <= L <= SVNET_SA_MAX_LAYERS, of 1x1 convolution + BatchNorm (running statistics) + ReLU, folded by svnet_sa_fold_f32 (a
+ * Conv1d weight [O,C,1] is a [O,C] matrix); its input width is C0 = D1 + D2.  fl() is rounding to fp32; every operation is rounded once.
+ * svnet_fp_fused_f32: per cloud idx [N,3] int64 and weight [N,3], exactly as svnet_three_nn_f32 writes them; points2 [D2,S], the sampled
+ *     level's features, channel-first (svnet_three_interpolate_f32's feat); points1 [D1,N], the skip features, channel-first, or NULL
+ *     with D1 = 0; wf, bf, widths as in svnet_sa_fused_f32: HOST arrays read during the call, handed to the kernel by value.  No
+ *     device copy, no workspace, one launch.
+ *         input row of point p: h0 = [ points1[0..D1-1, p] bit for bit | y[0..D2-1] ], the order of cat([points1, interpolated]), with
+ *             y[d] = fl(fl(fl(f[d,i0] w0) + fl(f[d,i1] w1)) + fl(f[d,i2] w2)),  f = points2, w_j = weight[p,j],
+ *             i_j = idx[p,j] clamped into 0 .. S-1: svnet_three_interpolate_f32's arithmetic word for word, S < 3 included, where the
+ *             empty slots are index 0 with weight 0.
+ *         per layer and output o: acc = bf[o]; for c ascending acc = fmaf(h[c], Wf[o,c], acc); h'[o] = acc > 0 ? acc : +0.
+ *         out[b, c_off + o, p] = hL_p[o], channel-first into out [B,C_total,N]; the other channels are left as they are.
+ *     The products run on v_mfma_f32_16x16x4_f32, bit for bit that fmaf chain; K is never split, so a value does not depend on how rows
+ *     or columns are tiled, and the zero padding of K adds exact zeros.  Inputs are assumed finite.
+ *     svnet_fp_fused_supported (1 / 0, a pure host function): N >= 1, 1 <= S <= 32768, D1 >= 0, D2 >= 1, D1 + D2 <= 1536, 1 <= L <= 4,
+ *     every 1 <= width <= 256, ceil(N / rows) <= 2^31 - 1.  B * ceil(N / rows) > 2^31 - 1 is refused in the call with
+ *     SVNET_E_UNSUPPORTED.  svnet_fp_fused_rows_tile: the consecutive points one workgroup takes - the largest of 64, 32 and 16 whose two
+ *     activation buffers fit in 160 KB of LDS; 0 outside the limits on D1, D2, L and the widths.                                      */
+int svnet_fp_fused_supported(int64_t N, int64_t S, int64_t D1, int64_t D2, int64_t L, const int64_t* widths);
+int svnet_fp_fused_rows_tile(int64_t D1, int64_t D2, int64_t L, const int64_t* widths);
+int svnet_fp_fused_f32(const int64_t* idx, const float* weight, const float* points2, const float* points1, int64_t B, int64_t N, int64_t S,
+                       int64_t D1, int64_t D2, int64_t L, const int64_t* widths, const void* wf, const void* bf, float* out, int64_t C_total,
+                       int64_t c_off, void* stream);
 
 /* ------------------------------------------------------------------ epoch metrics (main_cls_dgcnn.py:187-251, main_partseg_dgcnn.py:185-279,
  * utils.py:68-91 calculate_shape_IoU; the accuracy scores of sklearn.metrics are functions of the confusion matrix)

@@ -4,51 +4,32 @@
 // level") and svnet_amd/sa_fused.py; tests/sa_fused_ref.py restates it.  Two kernels:
 //   sa_fold_kernel   BatchNorm's running statistics folded into a layer's weights and bias, every operation rounded once.
 //   sa_fused_kernel  a workgroup takes a tile of SF_ROWS grouped rows - whole centres when a group has at most SF_ROWS slots, else the
-//                    tiles of one centre one after the other - gathers them into LDS and runs the layers on v_mfma_f32_16x16x4_f32
-//                    (bit for bit a c-ascending fmaf chain that starts at the bias; a wave owns 16-column tiles over the full K, so no
-//                    value depends on the tiling).  Activations ping-pong between two LDS buffers, weights come from global memory
-//                    (L2-resident) into registers, 8 k-steps ahead.  The last layer is not stored: its ReLU output, >= +0, goes into a per-centre column maximum by an
-//                    integer LDS maximum on the bit patterns, which is order-free.
+//                    tiles of one centre one after the other - gathers them into LDS and runs the layers through the layer engine
+//                    of mlp_tile.h (v_mfma_f32_16x16x4_f32, bit for bit a c-ascending fmaf chain that starts at the bias; the engine
+//                    is shared with fp_fused.hip).  The last layer is not stored: its ReLU output, >= +0, goes into a per-centre
+//                    column maximum by an integer LDS maximum on the bit patterns, which is order-free (the epilogue policy SaMax).
 // Built with -ffp-contract=off (Makefile, NO_CONTRACT).
-#include "pointset.h"
+#include "mlp_tile.h"
 
 namespace {
 
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-
-constexpr int SF_THREADS = 256, SF_WAVES = SF_THREADS / SVNET_WAVE;
+constexpr int SF_THREADS = MLP_THREADS;
 constexpr int SF_ROWS = 64;                                      // grouped rows per tile: four 16-row MFMA tiles
-constexpr int SF_MAX_C0 = 324, SF_MAX_WIDTH = 256;               // the envelope (svnet_sa_fused_supported)
+constexpr int SF_MAX_C0 = 324, SF_MAX_WIDTH = MLP_MAX_WIDTH;     // the envelope (svnet_sa_fused_supported)
 constexpr int SF_MAX_FLOATS = 2048;                              // the running maxima: centres per workgroup x padded last width, at most
-constexpr int SF_LDS_MAX = 160 * 1024;
-constexpr int SF_U = 8;                                          // k-steps whose weights a lane holds at a time: 32 channels
+constexpr int SF_LDS_MAX = MLP_LDS_MAX;
 constexpr int SF_HEAD = SF_ROWS * 8 + SF_ROWS * 4 + (SF_ROWS + 4) * 4 + SF_ROWS * 4;      // s_src | s_ctr | s_start (+ total) | s_lim
 static_assert(SF_HEAD % 16 == 0, "the float regions behind the row tables stay 16-byte aligned");
 
-inline int pad_to(int64_t v, int m) { return (int)((v + m - 1) / m * m); }
-
-// The folded layers and widths of a call handed to the kernel by value: no device copy.  C[0] = 3 + D, C[l] = width of layer l.
-struct SaLevel {
-    const float* w[SVNET_SA_MAX_LAYERS];
-    const float* b[SVNET_SA_MAX_LAYERS];
-    int C[SVNET_SA_MAX_LAYERS + 1];
-    int L;
-};
-// cpw: centres per workgroup; stride[p]: row stride of the activation buffer p (layer l reads buffer l & 1 and writes the other one),
-// 4 times an odd number: the 16 rows x 4 channels of an A fragment, and the 16 columns x 4 row quads of a result, then fall into 64
-// different banks; opad: the last width padded to whole column tiles.
+// cpw: centres per workgroup; stride[p]: row stride of the activation buffer p (mlp_tile.h: mlp_strides); opad: the last width padded
+// to whole column tiles.
 struct SaPlan { int cpw, stride[2], opad, lds; };
 
 inline bool sa_plan(int64_t N, int64_t S, int64_t K, int64_t D, int64_t L, const int64_t* widths, SaPlan& pl) {
-    if (!widths || L < 1 || L > SVNET_SA_MAX_LAYERS || !svnet_group_supported(N, S, K, D) || 3 + D > SF_MAX_C0) return false;
-    for (int64_t l = 0; l < L; ++l)
-        if (widths[l] < 1 || widths[l] > SF_MAX_WIDTH) return false;
+    if (!mlp_widths_ok(L, widths) || !svnet_group_supported(N, S, K, D) || 3 + D > SF_MAX_C0) return false;
     pl = SaPlan{};
     pl.opad = pad_to(widths[L - 1], 16);
-    for (int64_t l = 0; l < L; ++l) {
-        const int c = pad_to(l ? widths[l - 1] : 3 + D, 4), s = c % 8 ? c : c + 4;
-        if (s > pl.stride[l & 1]) pl.stride[l & 1] = s;
-    }
+    mlp_strides(3 + D, L, widths, pl.stride);
     const int fixed = SF_HEAD + 4 * SF_ROWS * (pl.stride[0] + pl.stride[1]);
     int64_t room = (SF_LDS_MAX - fixed) / 4;                     // floats left for the maxima
     if (room > SF_MAX_FLOATS) room = SF_MAX_FLOATS;
@@ -72,105 +53,36 @@ __global__ __launch_bounds__(SF_THREADS) void sa_fold_kernel(const float* __rest
     if (e == o * C) bf[o] = (b[o] - rmean[o]) * s + beta[o];
 }
 
-// The B operands of one lane for SF_U k-steps from channel c on, step u at channel c + 4 u: Wf[o][c + 4 u] of the lane's column o.  A
-// channel past the row is an exact zero; its load reads the row's last weight instead, so that no load needs a branch.
-// (W is wave-uniform and row = o Cin a 32-bit lane offset: the loads take the SGPR-base form and keep no 64-bit address per load.)
-__device__ __forceinline__ void sa_weights(const float* __restrict__ W, int row, int Cin, int c, float (&w)[SF_U]) {
+// The last layer's epilogue (mlp_tile.h): the ReLU outputs, >= +0, of column o and rows row .. row + 3 go into the centres' maxima.
+// Rows ascend, so a centre's rows are adjacent: one maximum per run of equal centres; -1 marks a row past the tile's.
+struct SaMax {
+    static constexpr bool LAST = true;
+    const int* s_ctr;
+    unsigned* smax;
+    int opad;
+    __device__ __forceinline__ void operator()(int row, int o, const float (&v)[4]) const {
+        const int4 cv = *reinterpret_cast<const int4*>(s_ctr + row);
+        const int ctr[4] = {cv.x, cv.y, cv.z, cv.w};
+        int cur = ctr[0];
+        float m = v[0];
 #pragma unroll
-    for (int u = 0; u < SF_U; ++u) {
-        const int cu = c + 4 * u;
-        const float x = ld_f32_sbase_fresh(W, (uint32_t)(row + (cu < Cin ? cu : Cin - 1)) * 4u);
-        w[u] = cu < Cin ? x : 0.f;
-    }
-}
-
-// One layer over the NRT 16-row tiles of the workgroup's rows.  A wave takes the column tiles wave, wave + 4, ...  A lane holds the B
-// operands of its column o = 16 ct + lane % 16 for SF_U k-steps (channels k0 + lane / 16 + 4 u) in registers, straight from global
-// memory, and the next SF_U - of this tile or, at its end, of the wave's next tile - are under way while these multiply.  More steps
-// in flight, or the activations read ahead of their products, cost registers, and a fourth wave per SIMD was worth more than either
-// (DESIGN.md 4.20).  The A operands (row 16 rt + lane % 16, channel k0 + lane / 16) come from the activation buffer and feed NRT
-// independent accumulators that started at the bias.  A lane of a result holds column lane % 16 of rows 4 (lane / 16) + 0..3.  LAST: the ReLU
-// outputs go into the centres' maxima instead of LDS.
-template <int NRT, bool LAST>
-__device__ __forceinline__ void sa_layer(const float* __restrict__ W, const float* __restrict__ bias, int Cin, int O, const float* in, int sin,
-                                         float* outb, int sout, const int* s_ctr, unsigned* smax, int opad, int wave, int lane) {
-    const int r16 = lane & 15, q = lane >> 4;
-    const int Kp = (Cin + 3) & ~3, Op = (O + 3) & ~3, nct = (O + 15) >> 4;
-    const float* arow = in + r16 * sin + q;
-    float wc[SF_U], wn[SF_U];
-    if (wave < nct) {
-        const int o = wave * 16 + r16;
-        sa_weights(W, (o < O ? o : O - 1) * Cin, Cin, q, wc);
-    }
-    for (int ct = wave; ct < nct; ct += SF_WAVES) {
-        const int o = ct * 16 + r16, on = o + 16 * SF_WAVES;
-        const bool ov = o < O;
-        const int wrow = (ov ? o : O - 1) * Cin, wnext = (on < O ? on : O - 1) * Cin;      // (past the last tile: loaded, never used)
-        const float b0 = ov ? bias[o] : 0.f;
-        f32x4 acc[NRT];
-#pragma unroll
-        for (int rt = 0; rt < NRT; ++rt) acc[rt] = f32x4{b0, b0, b0, b0};
-        for (int k0 = 0; k0 < Kp; k0 += 4 * SF_U) {
-            if (k0 + 4 * SF_U < Kp) sa_weights(W, wrow, Cin, k0 + 4 * SF_U + q, wn);
-            else sa_weights(W, wnext, Cin, q, wn);
-#pragma unroll
-            for (int u = 0; u < SF_U; ++u) {
-                if (k0 + 4 * u >= Kp) break;                     // (wave-uniform)
-#pragma unroll
-                for (int rt = 0; rt < NRT; ++rt)
-                    acc[rt] = __builtin_amdgcn_mfma_f32_16x16x4f32(arow[rt * 16 * sin + k0 + 4 * u], wc[u], acc[rt], 0, 0, 0);
-            }
-#pragma unroll
-            for (int u = 0; u < SF_U; ++u) wc[u] = wn[u];
-        }
-#pragma unroll
-        for (int rt = 0; rt < NRT; ++rt) {
-            const int row = rt * 16 + q * 4;
-            float v[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) v[i] = ov && acc[rt][i] > 0.f ? acc[rt][i] : 0.f;      // a column past the layer's: zero
-            if (!LAST) {
-                if (o < Op) {                                    // up to the next layer's padded K: zeros
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) outb[(row + i) * sout + o] = v[i];
-                }
-            } else if (ov) {
-                // rows ascend, so a centre's rows are adjacent: one maximum per run of equal centres; -1 marks a row past the tile's
-                const int4 cv = *reinterpret_cast<const int4*>(s_ctr + row);
-                const int ctr[4] = {cv.x, cv.y, cv.z, cv.w};
-                int cur = ctr[0];
-                float m = v[0];
-#pragma unroll
-                for (int i = 1; i < 4; ++i) {
-                    if (ctr[i] != cur) {
-                        if (cur >= 0) atomicMax(smax + cur * opad + o, __float_as_uint(m));
-                        cur = ctr[i];
-                        m = v[i];
-                    } else {
-                        m = m > v[i] ? m : v[i];
-                    }
-                }
+        for (int i = 1; i < 4; ++i) {
+            if (ctr[i] != cur) {
                 if (cur >= 0) atomicMax(smax + cur * opad + o, __float_as_uint(m));
+                cur = ctr[i];
+                m = v[i];
+            } else {
+                m = m > v[i] ? m : v[i];
             }
         }
+        if (cur >= 0) atomicMax(smax + cur * opad + o, __float_as_uint(m));
     }
-}
-
-template <bool LAST>
-__device__ __forceinline__ void sa_layer_rt(int nrt, const float* W, const float* bias, int Cin, int O, const float* in, int sin, float* outb,
-                                            int sout, const int* s_ctr, unsigned* smax, int opad, int wave, int lane) {
-    switch (nrt) {
-        case 1: sa_layer<1, LAST>(W, bias, Cin, O, in, sin, outb, sout, s_ctr, smax, opad, wave, lane); break;
-        case 2: sa_layer<2, LAST>(W, bias, Cin, O, in, sin, outb, sout, s_ctr, smax, opad, wave, lane); break;
-        case 3: sa_layer<3, LAST>(W, bias, Cin, O, in, sin, outb, sout, s_ctr, smax, opad, wave, lane); break;
-        default: sa_layer<4, LAST>(W, bias, Cin, O, in, sin, outb, sout, s_ctr, smax, opad, wave, lane); break;
-    }
-}
+};
 
 __global__ __launch_bounds__(SF_THREADS) __attribute__((amdgpu_waves_per_eu(4, 4))) void sa_fused_kernel(const float* __restrict__ xyz, const float* __restrict__ new_xyz,
                                                               const float* __restrict__ points, const int64_t* __restrict__ idx, int64_t idx_ld,
                                                               const int* __restrict__ count, int64_t count_ld, int64_t N, int64_t S, int K,
-                                                              int D, int64_t chunks, SaLevel lv, SaPlan pl, int xyz_last,
+                                                              int D, int64_t chunks, MlpLevel lv, SaPlan pl, int xyz_last,
                                                               float* __restrict__ out, int64_t C_total, int64_t c_off) {
     extern __shared__ __align__(16) unsigned char sf_lds[];
     int64_t* s_src = reinterpret_cast<int64_t*>(sf_lds);                        // [SF_ROWS] b * N + the row's point
@@ -253,8 +165,8 @@ __global__ __launch_bounds__(SF_THREADS) __attribute__((amdgpu_waves_per_eu(4, 4
             const float* in = l & 1 ? buf1 : buf0;
             float* outb = l & 1 ? buf0 : buf1;
             const int sin = pl.stride[l & 1], sout = pl.stride[(l & 1) ^ 1];
-            if (l + 1 < lv.L) sa_layer_rt<false>(nrt, lv.w[l], lv.b[l], lv.C[l], lv.C[l + 1], in, sin, outb, sout, s_ctr, smax, pl.opad, wave, lane);
-            else sa_layer_rt<true>(nrt, lv.w[l], lv.b[l], lv.C[l], lv.C[l + 1], in, sin, outb, sout, s_ctr, smax, pl.opad, wave, lane);
+            if (l + 1 < lv.L) mlp_layer_rt(nrt, lv.w[l], lv.b[l], lv.C[l], lv.C[l + 1], in, sin, outb, sout, MlpToLds{}, wave, lane);
+            else mlp_layer_rt(nrt, lv.w[l], lv.b[l], lv.C[l], lv.C[l + 1], in, sin, outb, sout, SaMax{s_ctr, smax, pl.opad}, wave, lane);
             __syncthreads();
         }
     }
@@ -304,7 +216,7 @@ extern "C" int svnet_sa_fused_f32(const float* xyz, const float* new_xyz, const 
                   (long long)c_off, (long long)(c_off + widths[L - 1]), (long long)C_total);
     SVNET_REQUIRE(B <= 0x7fffffffll / S / idx_ld, SVNET_E_UNSUPPORTED, "svnet_sa_fused_f32: B %lld x S %lld x idx_ld %lld indices > 2^31 - 1",
                   (long long)B, (long long)S, (long long)idx_ld);
-    SaLevel lv = {};
+    MlpLevel lv = {};
     lv.L = (int)L;
     lv.C[0] = (int)(3 + D);
     const float* const* w = static_cast<const float* const*>(wf);
