@@ -849,7 +849,9 @@ int svnet_group_points_bwd_f32(const float* dgrouped, const int32_t* rev_start, 
  * (models/utils/pointnet_util.py:210-267 PointNetSetAbstractionMsg).  `scales` = R, 1 .. SVNET_MSG_MAX_SCALES; r2 [R] fp32 and
  * nsample [R] int64 are HOST arrays, read during the call and handed to the kernels by value: no device copy, no host read of device
  * memory, so every call below can be captured.  Ktot = sum nsample[i], off_i = nsample[0] + .. + nsample[i-1].  Radii need not be
- * ascending and may repeat.  Distance, membership, order, padding, the empty group and the clamp are those of the block above.
+ * ascending and may repeat.  Distance, membership, order, padding, the empty group and the clamp are those of the block above:
+ * the query and the grouping kernel are the same ones (csrc/group.hip states each once for 1 .. R scales; the single-scale calls
+ * launch the one-scale form).
  * svnet_ball_query_msg_f32: xyz [B,N,3], new_xyz [B,S,3] -> idx [B,S,Ktot] int64, count [B,S,R] int32.  A centre's row is the R lists
  *     end to end: columns off_i .. off_i + nsample[i] - 1 and count[..,i] are exactly what svnet_ball_query_f32 gives for
  *     (r2[i], nsample[i]).  One launch: a candidate's distance is computed once, every scale that is not yet full takes its own

@@ -68,6 +68,11 @@ def hip_device(who, device):
     return device
 
 
+def rows(t):
+    """[B,C,N] channel-first, as the modules take clouds and features -> [B,N,C] contiguous, as the kernels do (autograd follows)."""
+    return t.permute(0, 2, 1).contiguous()
+
+
 def gather_rows(x, idx):
     """x [B,N,3], idx [B,S] int64 -> [B,S,3]: x[b, idx[b,s], :]."""
     return torch.gather(x, 1, idx.unsqueeze(2).expand(-1, -1, 3))

@@ -110,10 +110,6 @@ def interp_mlp(idx, weight, points2, points1, level, out=None, c_off=0):
     return out
 
 
-def _rows(t):
-    return t.permute(0, 2, 1).contiguous()
-
-
 class FusedFeaturePropagation:
     """The eval-mode forward of a PointNetFeaturePropagation on a HIP device, with the module's signature and result:
 
@@ -171,7 +167,7 @@ class FusedFeaturePropagation:
         idx = torch.empty(B, N, 3, dtype=torch.int64, device=dev)
         dist3 = torch.empty(B, N, 3, dtype=torch.float32, device=dev)
         weight = torch.empty(B, N, 3, dtype=torch.float32, device=dev)
-        _nn_launch(_rows(xyz1), _rows(xyz2), B, N, S, idx, dist3, weight)
+        _nn_launch(_pointset.rows(xyz1), _pointset.rows(xyz2), B, N, S, idx, dist3, weight)
         out = torch.empty(B, self.channels, N, dtype=torch.float32, device=dev)
         _launch(idx, weight, points2.contiguous(), None if points1 is None else points1.contiguous(), self.level, out, 0, B, N, S, D1, D2)
         return out

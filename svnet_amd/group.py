@@ -127,6 +127,31 @@ def _group_launch(xyz, new_xyz, points, idx, B, N, S, nsample, D, out):
                   _ops._p(out), _ops._stream())
 
 
+def _sample_centres(name, xyz, B, N, S, start, seed=0):
+    """What every sampling front end does between its argument checks and its query: resolve `start` (None: data.fps_start(seed, B, N),
+    copied from the host; a host array: copied; a device tensor: taken) and check it is [B], farthest point sampling, the gather of
+    the centres.  xyz [B,N,3] -> (new_xyz [B,S,3] contiguous, fps_idx [B,S] int64); two launches on the current stream, no host read
+    when start is a device tensor.  Errors are raised under the caller's `name`."""
+    if start is None:
+        start = torch.from_numpy(fps_start(seed, B, N)).to(xyz.device)
+    elif not isinstance(start, torch.Tensor):
+        start = torch.from_numpy(np.ascontiguousarray(start, dtype=np.int64)).to(xyz.device)
+    if tuple(start.shape) != (B,):
+        raise ValueError("%s: start must be [B] = [%d], got %s" % (name, B, tuple(start.shape)))
+    fps_idx = torch.empty(B, S, dtype=torch.int64, device=xyz.device)
+    _pointset.fps_launch(xyz, B, N, S, start, fps_idx)
+    return _pointset.gather_rows(xyz, fps_idx).contiguous(), fps_idx
+
+
+def _cached_start(cache, seed, B, N, device):
+    """The default sampling start of a set-abstraction module, data.fps_start(seed, B, N), uploaded once per (seed, B, N, device) and
+    kept in the module's `cache` dict."""
+    key = (int(seed), B, N, device)
+    if key not in cache:
+        cache[key] = torch.from_numpy(fps_start(seed, B, N)).to(device)
+    return cache[key]
+
+
 def query_ball_point(radius, nsample, xyz, new_xyz, return_count=False):
     """The reference's name and argument order: xyz [B,N,3], new_xyz [B,S,3] float32 on a HIP device -> idx [B,S,nsample] int64, the
     first nsample points within `radius` of every centre in ascending index, padded with the first (module docstring); with
@@ -231,16 +256,8 @@ def sample_and_group(npoint, radius, nsample, xyz, points, returnfps=False, star
     _ops._hip(xyz, points)
     _pointset.fps_supported("sample_and_group", "N", N, S)
     _supported("sample_and_group", N, S, nsample, D)
-    if start is None:
-        start = torch.from_numpy(fps_start(seed, B, N)).to(xyz.device)
-    elif not isinstance(start, torch.Tensor):
-        start = torch.from_numpy(np.ascontiguousarray(start, dtype=np.int64)).to(xyz.device)
-    if tuple(start.shape) != (B,):
-        raise ValueError("sample_and_group: start must be [B] = [%d], got %s" % (B, tuple(start.shape)))
+    new_xyz, fps_idx = _sample_centres("sample_and_group", xyz, B, N, S, start, seed)
     dev = xyz.device
-    fps_idx = torch.empty(B, S, dtype=torch.int64, device=dev)
-    _pointset.fps_launch(xyz, B, N, S, start, fps_idx)
-    new_xyz = _pointset.gather_rows(xyz, fps_idx).contiguous()
     idx = torch.empty(B, S, nsample, dtype=torch.int64, device=dev)
     count = torch.empty(B, S, dtype=torch.int32, device=dev)
     _query_launch(xyz, new_xyz, B, N, S, _r2(radius), nsample, idx, count)
@@ -411,16 +428,8 @@ def sample_and_group_msg(npoint, radius_list, nsample_list, xyz, points, start=N
     _ops._hip(xyz, points)
     _pointset.fps_supported("sample_and_group_msg", "N", N, S)
     _supported_msg("sample_and_group_msg", N, S, R, c_nsample, nsamples, D)
-    if start is None:
-        start = torch.from_numpy(fps_start(seed, B, N)).to(xyz.device)
-    elif not isinstance(start, torch.Tensor):
-        start = torch.from_numpy(np.ascontiguousarray(start, dtype=np.int64)).to(xyz.device)
-    if tuple(start.shape) != (B,):
-        raise ValueError("sample_and_group_msg: start must be [B] = [%d], got %s" % (B, tuple(start.shape)))
+    new_xyz, _ = _sample_centres("sample_and_group_msg", xyz, B, N, S, start, seed)
     dev = xyz.device
-    fps_idx = torch.empty(B, S, dtype=torch.int64, device=dev)
-    _pointset.fps_launch(xyz, B, N, S, start, fps_idx)
-    new_xyz = _pointset.gather_rows(xyz, fps_idx).contiguous()
     idx = torch.empty(B, S, sum(nsamples), dtype=torch.int64, device=dev)
     count = torch.empty(B, S, R, dtype=torch.int32, device=dev)
     _query_msg_launch(xyz, new_xyz, B, N, S, R, c_r2, c_nsample, idx, count)

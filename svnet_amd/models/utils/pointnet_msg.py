@@ -6,7 +6,7 @@ and state_dict keys (`conv_blocks.i.j.*`, `bn_blocks.i.j.*`, Conv2d / BatchNorm2
 It lives beside svnet_amd/models/utils/pointnet_util.py, which holds the single-scale level and the propagation and is left as it is.
 
 The data path is the device's: farthest point sampling -> gather of the centres -> ONE ball-query pass for all radii -> ONE grouping
-launch (svnet_amd/group.py, "Multi-scale grouping"; svnet_amd/csrc/group_msg.hip); the 1x1 convolution + BatchNorm + ReLU stacks, the
+launch (svnet_amd/group.py, "Multi-scale grouping"; svnet_amd/csrc/group.hip); the 1x1 convolution + BatchNorm + ReLU stacks, the
 max over a group and the cat of the scales on the channel axis are torch modules.  The attributes carry gradients (the ordered sums of
 group_points_msg_backward, bit-reproducible); coordinates are data and get no gradient.
 
@@ -18,15 +18,10 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from ...data import fps_start
-from ...group import query_ball_point_msg, sample_and_group_msg                                # noqa: F401  (re-exported)
+from ..._pointset import rows as _rows
+from ...group import _cached_start, query_ball_point_msg, sample_and_group_msg                 # noqa: F401  (re-exported)
 
 __all__ = ["PointNetSetAbstractionMsg", "query_ball_point_msg", "sample_and_group_msg"]
-
-
-def _rows(t):
-    """[B,C,N] channel-first -> [B,N,C] contiguous (autograd follows)."""
-    return t.permute(0, 2, 1).contiguous()
 
 
 class PointNetSetAbstractionMsg(nn.Module):
@@ -47,10 +42,7 @@ class PointNetSetAbstractionMsg(nn.Module):
         self._starts = {}
 
     def _start(self, B, N, device):
-        key = (int(self.seed), B, N, device)
-        if key not in self._starts:
-            self._starts[key] = torch.from_numpy(fps_start(self.seed, B, N)).to(device)
-        return self._starts[key]
+        return _cached_start(self._starts, self.seed, B, N, device)
 
     def forward(self, xyz, points, start=None):
         """xyz [B,3,N], points [B,D,N] or None, start [B] int64 or None -> (new_xyz [B,3,S], new_points [B,sum of mlp[-1],S]): the

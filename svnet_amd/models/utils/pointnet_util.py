@@ -21,16 +21,12 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ...data import farthest_point_sample, fps_start                                          # noqa: F401  (re-exported)
-from ...group import query_ball_point, sample_and_group, sample_and_group_all                 # noqa: F401  (re-exported)
+from ..._pointset import rows as _rows
+from ...group import _cached_start, query_ball_point, sample_and_group, sample_and_group_all  # noqa: F401  (re-exported)
 from ...propagate import propagate, three_interpolate, three_nn                               # noqa: F401  (re-exported)
 
 __all__ = ["PointNetSetAbstraction", "PointNetFeaturePropagation", "farthest_point_sample", "query_ball_point", "sample_and_group",
            "sample_and_group_all", "three_nn", "three_interpolate"]
-
-
-def _rows(t):
-    """[B,C,N] channel-first -> [B,N,C] contiguous (autograd follows)."""
-    return t.permute(0, 2, 1).contiguous()
 
 
 class PointNetSetAbstraction(nn.Module):
@@ -48,10 +44,7 @@ class PointNetSetAbstraction(nn.Module):
         self._starts = {}
 
     def _start(self, B, N, device):
-        key = (int(self.seed), B, N, device)
-        if key not in self._starts:
-            self._starts[key] = torch.from_numpy(fps_start(self.seed, B, N)).to(device)
-        return self._starts[key]
+        return _cached_start(self._starts, self.seed, B, N, device)
 
     def forward(self, xyz, points, start=None):
         """xyz [B,3,N], points [B,D,N] or None, start [B] int64 or None -> (new_xyz [B,3,S], new_points [B,mlp[-1],S])."""

@@ -34,7 +34,7 @@ require grad.  There is no CPU fallback: tensors that are not on a HIP device ra
 import torch
 
 from . import _lib, _ops, _pointset
-from .group import _query_msg_launch, _scales
+from .group import _query_msg_launch, _sample_centres, _scales
 
 __all__ = ["FoldedLevel", "fold_level", "group_mlp_max", "supported", "rows_tile", "FusedSetAbstraction"]
 
@@ -181,10 +181,6 @@ def group_mlp_max(xyz, new_xyz, idx, points, level, count=None, xyz_last=False, 
     return out
 
 
-def _rows(t):
-    return t.permute(0, 2, 1).contiguous()
-
-
 class FusedSetAbstraction:
     """The eval-mode forward of a PointNetSetAbstraction (group_all=False) or a PointNetSetAbstractionMsg on a HIP device, with the
     module's signature, default start and results:
@@ -251,14 +247,10 @@ class FusedSetAbstraction:
             return self.module(xyz, points, start=start)
         if start is None:
             start = self.module._start(B, N, xyz.device)
-        if tuple(start.shape) != (B,):
-            raise ValueError("%s: start must be [B] = [%d], got %s" % (name, B, tuple(start.shape)))
         dev, S = xyz.device, self.npoint
-        rows, attrs = _rows(xyz), None if points is None else _rows(points)
+        rows, attrs = _pointset.rows(xyz), None if points is None else _pointset.rows(points)
         R, c_r2, c_nsample, nsamples = _scales(name, self.radii, self.nsamples)
-        fps_idx = torch.empty(B, S, dtype=torch.int64, device=dev)
-        _pointset.fps_launch(rows, B, N, S, start, fps_idx)
-        new_xyz = _pointset.gather_rows(rows, fps_idx).contiguous()
+        new_xyz, _ = _sample_centres(name, rows, B, N, S, start)
         Ktot = sum(nsamples)
         idx = torch.empty(B, S, Ktot, dtype=torch.int64, device=dev)
         count = torch.empty(B, S, R, dtype=torch.int32, device=dev)

@@ -1,4 +1,4 @@
-"""numpy restatement of the multi-scale grouping (svnet_amd/csrc/group_msg.hip), written from the contract in
+"""numpy restatement of the multi-scale grouping (svnet_amd/csrc/group.hip), written from the contract in
 svnet_amd/group.py's docstring ("Multi-scale grouping") and independent of the kernels.  It is built on the single-scale restatements:
 tests/group_ref.py's query_ball and distances, tests/pointset_grad_ref.py's reverse lists and ordered sum.
 

@@ -1,5 +1,5 @@
 """GPU tests (-m gpu) of the multi-scale grouping: svnet_ball_query_msg_f32, svnet_group_points_msg_f32 and
-svnet_group_points_msg_bwd_f32 (svnet_amd/csrc/group_msg.hip) through svnet_amd.group, and PointNetSetAbstractionMsg of
+svnet_group_points_msg_bwd_f32 (svnet_amd/csrc/group.hip) through svnet_amd.group, and PointNetSetAbstractionMsg of
 svnet_amd/models/utils/pointnet_msg.py, against the numpy restatement tests/msg_ref.py, the single-scale calls on the device and the
 reference's recorded results (tests/golden/msg.npz).  The contract is single-rounded fp32 with a fixed sum order, so indices and counts
 are compared as integers and everything else as BIT PATTERNS; the two tolerances there are, are derived where they are used.  Every
@@ -49,7 +49,11 @@ CASES = [(1, 1, (0.4,), (1,), 0),
          (T + 1, 3, (0.4, 0.05, 4.0), (65, 8, 64), 61),
          (2 * T + 5, 130, (0.05, 4.0, 0.5, 0.5), (8, 4, 200, 64), 64),
          (2 * T + 5, 5, (0.3, 0.05, 3.0), (150, 2, 6), 5),
-         (129, 1, (1.0,), (128,), 0)]
+         (129, 1, (1.0,), (128,), 0),
+         # one scale WITH attributes: the one-scale, attributes-first forms of the grouping and of its gradient
+         (65, 33, (0.9,), (5,), 1),                # float4 rows, one centre past a 32-centre workgroup
+         (T + 1, 3, (0.4,), (65,), 5),             # the second LDS tile, a list longer than a 64-candidate step
+         (64, 7, (1.5,), (64,), 61)]               # rows of 64 columns
 GRAD_CASES = [c for c in CASES if c[4] > 0]
 
 

@@ -1,6 +1,6 @@
 """CPU tests of the multi-scale grouping's host side: the numpy restatement tests/msg_ref.py against the reference's recorded results
 (tests/golden/msg.npz, written by tests/golden/make_msg_golden.py), the layout and sum order of the contract on constructed inputs,
-the new names in the parsed header, the pure-host refusals of svnet_amd/csrc/group_msg.hip, and the argument checks of
+the new names in the parsed header, the pure-host refusals of svnet_amd/csrc/group.hip, and the argument checks of
 svnet_amd/group.py."""
 import ctypes
 import inspect

@@ -1,4 +1,4 @@
-"""Times of the multi-scale grouping on the GPU (svnet_amd/group.py, csrc/group_msg.hip) against the single-scale
+"""Times of the multi-scale grouping on the GPU (svnet_amd/group.py, csrc/group.hip) against the single-scale
 calls it replaces, HIP events around repeated launches, at
 
     (B, N, S, radii, nsample, D) = (32, 1024, 512, 0.1/0.2/0.4, 16/32/128, 0), (32, 512, 128, 0.2/0.4/0.8, 32/64/128, 320) and
