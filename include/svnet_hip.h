@@ -45,9 +45,9 @@ int svnet_slices_sum_f64(double* buf, int64_t L, void* stream);
 
 /* ABI version = 100 * round-of-change + serial.  It changes whenever an entry point gains / loses an argument or a caller-owned buffer
  * changes its required length (200: sliced accumulators, SVNET_SLICED_LEN; 400: this header; 401: the totals of a sliced accumulator are
- * written by its consumer, svnet_slices_sum_*; 402: GX of svnet_v2s_bwd_*, gw of svnet_xyzblock_bwd_f32 and col_sum of svnet_gemm_f32 are sliced accumulators; 403: svnet_binweight_grad_f32 takes sliced inputs; 421: svnet_three_nn_f32, svnet_three_interpolate_f32; 422: svnet_ball_query_f32, svnet_group_points_f32; 423: svnet_vlinear_stats_f32 is gone; 424: svnet_edgeblock_fwd_tier, svnet_edgeblock_bwd_tier, svnet_edgeblock_wgrad_tier, svnet_xyzblock_tier; 425: svnet_pointset_reverse_i32, svnet_three_interpolate_bwd_f32, svnet_group_points_bwd_f32; 426: wbt of svnet_edgeblock_wbt_bf16 is 512 values longer, the all-zero fragment; 427: svnet_ball_query_msg_f32, svnet_group_points_msg_f32, svnet_group_points_msg_bwd_f32; 428: svnet_sa_fold_f32, svnet_sa_fused_f32; 429: svnet_fp_fused_f32, svnet_fp_fused_supported, svnet_fp_fused_rows_tile).  svnet_version() returns the value the
+ * written by its consumer, svnet_slices_sum_*; 402: GX of svnet_v2s_bwd_*, gw of svnet_xyzblock_bwd_f32 and col_sum of svnet_gemm_f32 are sliced accumulators; 403: svnet_binweight_grad_f32 takes sliced inputs; 421: svnet_three_nn_f32, svnet_three_interpolate_f32; 422: svnet_ball_query_f32, svnet_group_points_f32; 423: svnet_vlinear_stats_f32 is gone; 424: svnet_edgeblock_fwd_tier, svnet_edgeblock_bwd_tier, svnet_edgeblock_wgrad_tier, svnet_xyzblock_tier; 425: svnet_pointset_reverse_i32, svnet_three_interpolate_bwd_f32, svnet_group_points_bwd_f32; 426: wbt of svnet_edgeblock_wbt_bf16 is 512 values longer, the all-zero fragment; 427: svnet_ball_query_msg_f32, svnet_group_points_msg_f32, svnet_group_points_msg_bwd_f32; 428: svnet_sa_fold_f32, svnet_sa_fused_f32; 429: svnet_fp_fused_f32, svnet_fp_fused_supported, svnet_fp_fused_rows_tile; 430: svnet_sa_global_f32, svnet_sa_global_supported, svnet_sa_global_rows_tile).  svnet_version() returns the value the
  * library was BUILT with: a caller compiled against another header must refuse to run (svnet_amd/_lib.py does).                   */
-#define SVNET_ABI_VERSION 429
+#define SVNET_ABI_VERSION 430
 int svnet_version(void);
 const char* svnet_last_error(void);
 
@@ -934,6 +934,36 @@ int svnet_fp_fused_rows_tile(int64_t D1, int64_t D2, int64_t L, const int64_t* w
 int svnet_fp_fused_f32(const int64_t* idx, const float* weight, const float* points2, const float* points1, int64_t B, int64_t N, int64_t S,
                        int64_t D1, int64_t D2, int64_t L, const int64_t* widths, const void* wf, const void* bf, float* out, int64_t C_total,
                        int64_t c_off, void* stream);
+
+/* ------------------------------------------------------------------ fused global set-abstraction level for inference: all points, shared MLP, max
+ * (models/utils/pointnet_util.py:49-63 with group_all, the eval-mode forward of PointNetSetAbstraction behind sample_and_group_all: one
+ * group of all N points of a cloud, coordinates first and NOT centred - the reference subtracts nothing there).  A level has L layers,
+ * 1 <= L <= SVNET_SA_MAX_LAYERS, of 1x1 convolution + BatchNorm (running statistics) + ReLU, folded by svnet_sa_fold_f32; its input width
+ * is C0 = 3 + D.  fl() is rounding to fp32; every operation is rounded once, nothing is contracted but the stated fmaf.
+ * svnet_sa_global_f32: per cloud xyz [3,N] and points [D,N] (NULL with D = 0), channel-first as the module receives them: no transposed
+ *     copy is made; wf, bf, widths as in svnet_sa_fused_f32: HOST arrays read during the call, handed to the kernel by value.
+ *         row p, 0 <= p < N: h0 = [ xyz[0..2, p] | points[0..D-1, p] ], bit for bit.
+ *         per layer and output o: acc = bf[o]; for c ascending acc = fmaf(h[c], Wf[o,c], acc); h'[o] = acc > 0 ? acc : +0.
+ *         out[b, c_off + o] = max over p in [0, N) of hL_p[o], into out [B,C_total] (that is [B,C_total,1]); the other channels are left
+ *         as they are.
+ *     The products run on v_mfma_f32_16x16x4_f32, bit for bit that fmaf chain; K is never split, so no value depends on how rows, columns
+ *     or clouds are tiled, and the zero padding of K adds exact zeros.  A workgroup takes svnet_sa_global_rows_tile consecutive points
+ *     of a cloud; the rows of its tile past N never enter the maximum (a zero row is not neutral: its output is the ReLU of the bias
+ *     chain).  The workgroups of a cloud meet in out by an unsigned-integer maximum on the bit patterns - the values are >= +0, such
+ *     floats order as their bit patterns, and an integer maximum has no order: the bits are reproducible; there are no float atomics -
+ *     after a first small launch of the same call has set exactly the channels c_off .. c_off + C_L - 1 of every cloud to +0.  Two
+ *     launches on `stream`, no workspace, no host read: capturable.  Inputs are assumed finite.
+ *     svnet_sa_global_supported (1 / 0, a pure host function): 1 <= N <= 32768, 0 <= D <= 1024, 1 <= L <= 4, every 1 <= width <= 1024.
+ *     B * ceil(N / rows) > 2^31 - 1 is refused in the call with SVNET_E_UNSUPPORTED.
+ *     svnet_sa_global_rows_tile (a pure host function): rows = the largest of 64, 48, 32 and 16 with
+ *         4 rows (stride0 + stride1) + 4 pad16(C_L) <= 160 KB of LDS,
+ *     where buffer l & 1 holds layer l's input rows, stride_p is the widest row of buffer p padded to a multiple of 4 floats and, where
+ *     that is a multiple of 8, by 4 more (csrc/mlp_tile.h), and pad16 rounds up to a multiple of 16; 0 outside the limits on D, L and
+ *     the widths.  The whole envelope fits at 16 rows (D 1024, four layers of 1024: 16 x 2056 floats + 1024 maxima = 133 KB).           */
+int svnet_sa_global_supported(int64_t N, int64_t D, int64_t L, const int64_t* widths);
+int svnet_sa_global_rows_tile(int64_t D, int64_t L, const int64_t* widths);
+int svnet_sa_global_f32(const float* xyz, const float* points, int64_t B, int64_t N, int64_t D, int64_t L, const int64_t* widths,
+                        const void* wf, const void* bf, float* out, int64_t C_total, int64_t c_off, void* stream);
 
 /* ------------------------------------------------------------------ epoch metrics (main_cls_dgcnn.py:187-251, main_partseg_dgcnn.py:185-279,
  * utils.py:68-91 calculate_shape_IoU; the accuracy scores of sklearn.metrics are functions of the confusion matrix)

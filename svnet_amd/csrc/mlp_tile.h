@@ -1,4 +1,4 @@
-// The layer engine of the fused inference levels (sa_fused.hip, fp_fused.hip), stated once: a stack of folded 1x1 convolution +
+// The layer engine of the fused inference levels (sa_fused.hip, fp_fused.hip, sa_global.hip), stated once: a stack of folded 1x1 convolution +
 // BatchNorm + ReLU layers over a tile of rows that lie in LDS, on v_mfma_f32_16x16x4_f32.  Per layer and output o the value is
 //   acc = bf[o];  for c ascending acc = fmaf(h[c], Wf[o,c], acc);  h'[o] = acc > 0 ? acc : +0
 // bit for bit: the bias is the accumulator's start, a wave owns 16-column tiles over the full K, and K is never split, so no value
@@ -38,10 +38,11 @@ inline void mlp_strides(int64_t C0, int64_t L, const int64_t* widths, int (&stri
     }
 }
 
-inline bool mlp_widths_ok(int64_t L, const int64_t* widths) {
+// (max_width: the column-tile loop of mlp_layer takes any width; a kernel's envelope may be wider than MLP_MAX_WIDTH - sa_global.hip)
+inline bool mlp_widths_ok(int64_t L, const int64_t* widths, int64_t max_width = MLP_MAX_WIDTH) {
     if (!widths || L < 1 || L > SVNET_SA_MAX_LAYERS) return false;
     for (int64_t l = 0; l < L; ++l)
-        if (widths[l] < 1 || widths[l] > MLP_MAX_WIDTH) return false;
+        if (widths[l] < 1 || widths[l] > max_width) return false;
     return true;
 }
 

@@ -198,7 +198,7 @@ class FusedSetAbstraction:
         from .models.utils.pointnet_util import PointNetSetAbstraction
         if isinstance(module, PointNetSetAbstraction):
             if module.group_all:
-                raise ValueError("FusedSetAbstraction: a group_all level has no query to fuse behind - call the module")
+                raise ValueError("FusedSetAbstraction: a group_all level has no query to fuse behind - that level is sa_global.FusedGlobalAbstraction's")
             self.radii, self.nsamples, self.xyz_last = (module.radius,), (int(module.nsample),), False
             self.levels = [fold_level(module.mlp_convs, module.mlp_bns)]
         elif isinstance(module, PointNetSetAbstractionMsg):

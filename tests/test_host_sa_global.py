@@ -1,0 +1,165 @@
+"""CPU tests of the fused global set-abstraction level's yardstick and front end: the numpy restatement tests/sa_global_ref.py - its fp32
+chain against its float64 one, and against the reference's recorded eval outputs (tests/golden/sa_global.npz) - the host side of the
+library (svnet_sa_global_supported, svnet_sa_global_rows_tile, the ABI) and the argument checks of svnet_amd/sa_global.py.  The
+kernels themselves: tests/test_hip_sa_global.py."""
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+from svnet_amd import _lib, synth
+from tests import sa_fused_ref as R
+from tests import sa_global_ref as SG
+from tests.common import compare_case
+
+F32 = np.float32
+HERE = os.path.dirname(os.path.abspath(__file__))
+GOLDEN = np.load(os.path.join(HERE, "golden", "sa_global.npz"))
+
+
+def _random_level(seed, C0, widths):
+    layers, last = [], C0
+    for i, w in enumerate(widths):
+        W = (synth.normal(seed, 10 + 8 * i, (w, last)) / np.sqrt(F32(last))).astype(F32)
+        gamma = (synth.normal(seed, 11 + 8 * i, (w,)) + F32(0.25)).astype(F32)                 # both signs
+        layers.append(R.fold(W, synth.normal(seed, 12 + 8 * i, (w,)) * F32(0.1), gamma, synth.normal(seed, 13 + 8 * i, (w,)) * F32(0.2),
+                             synth.normal(seed, 14 + 8 * i, (w,)) * F32(0.1), (np.abs(synth.normal(seed, 15 + 8 * i, (w,))) + F32(0.5)).astype(F32), 1e-5))
+        last = w
+    return layers
+
+
+@pytest.mark.parametrize("N,D,widths", [(1, 0, (5,)), (17, 4, (12, 20)), (40, 64, (33, 8, 300)), (9, 131, (16, 16, 16, 7))])
+def test_fp32_chain_lies_within_the_running_bound_of_the_float64_chain(N, D, widths):
+    x = (synth.normal(18, 1, (3, N)) * F32(0.5)).astype(F32)
+    pts = synth.normal(18, 2, (D, N)) if D else None
+    layers = _random_level(18 + D, 3 + D, widths)
+    got = SG.level(x, pts, layers)
+    value, bound = SG.level_f64(x, pts, layers)
+    assert got.dtype == F32 and got.shape == value.shape == bound.shape == (widths[-1],)
+    err = np.abs(got.astype(np.float64) - value)
+    assert (err <= bound).all(), float((err / np.maximum(bound, 1e-300)).max())
+    assert float(got.max()) > 0 and (bound < 1e-2 * float(value.max())).all()
+    # the global level is the maximum over the rows [xyz[:, p] | points[:, p]] of the chain, stated without sa_fused_ref's grouping
+    h0 = x.T if pts is None else np.concatenate([x.T, pts.T], axis=1)
+    assert np.array_equal(R.mlp(h0, layers).max(axis=0).view(np.uint32), got.view(np.uint32))
+    batch = SG.level_batch(np.stack([x, x]), None if pts is None else np.stack([pts, pts]), layers)
+    assert batch.shape == (2, widths[-1], 1) and np.array_equal(batch[1, :, 0].view(np.uint32), got.view(np.uint32))
+
+
+def test_restatement_equals_the_recorded_eval_output():
+    seed, B, N, D, mlp = SG.GOLDEN_CASE
+    want = GOLDEN["ev_out:new_points"]
+    assert want.shape == (B, mlp[-1], 1) and GOLDEN["xyz"].shape == (B, 3, N) and GOLDEN["points"].shape == (B, D, N)
+    assert GOLDEN["ev_out:new_xyz"].shape == (B, 3, 1) and not GOLDEN["ev_out:new_xyz"].any()
+    x, pts = SG.golden_inputs()
+    assert np.array_equal(x, GOLDEN["xyz"]) and np.array_equal(pts, GOLDEN["points"]) and np.array_equal(x * 1024, np.round(x * 1024))
+    assert all(((GOLDEN["sd:mlp_bns.%d.weight" % i] > 0).any() and (GOLDEN["sd:mlp_bns.%d.weight" % i] < 0).any()) for i in range(len(mlp)))
+    assert os.path.getsize(os.path.join(HERE, "golden", "sa_global.npz")) < os.path.getsize(os.path.join(HERE, "golden", "msg.npz"))
+    state = {str(k): GOLDEN["sd:" + str(k)] for k in GOLDEN["keys"]}
+    got = SG.level_batch(x, pts, R.fold_state(state, R.single_prefixes(len(mlp))))
+    worst = compare_case({"out:new_points": got}, {"out:new_points": want}, 1e-3, "sa_global.npz")
+    print("worst relative error %.3e" % worst[0])
+
+
+# ---- the host side of the library
+def test_supported_is_the_stated_envelope_and_the_abi_names_the_entries():
+    from svnet_amd import sa_global as SGL
+    assert SGL.supported(128, 256, (256, 512, 1024)) and SGL.supported(128, 640, (256, 512, 1024)) and SGL.supported(1024, 0, (64,))
+    # both sides of every edge: N 0 / 1 / 32768 / 32769, D 1024 / 1025, width 1024 / 1025, L 0 / 4 / 5
+    assert not SGL.supported(0, 0, (8,)) and SGL.supported(1, 0, (8,)) and SGL.supported(32768, 0, (8,)) and not SGL.supported(32769, 0, (8,))
+    assert SGL.supported(16, 1024, (8,)) and not SGL.supported(16, 1025, (8,)) and not SGL.supported(16, -1, (8,))
+    assert SGL.supported(16, 0, (1024,)) and not SGL.supported(16, 0, (1025,)) and not SGL.supported(16, 0, (8, 0))
+    assert SGL.supported(16, 0, (8, 1024, 1, 1024)) and not SGL.supported(16, 0, (8, 1025, 8))
+    assert not SGL.supported(16, 0, ()) and SGL.supported(16, 1024, (1024,) * 4) and not SGL.supported(16, 0, (8,) * 5)
+    # rows_tile: the largest R of 64, 48, 32, 16 with 4 R (stride0 + stride1) + 4 pad16(C_L) <= 163840 bytes, where buffer l & 1 holds
+    # layer l's input and a stride is the widest such row padded to a multiple of 4, plus 4 where that is a multiple of 8 - by hand:
+    #   D 256, 256/512/1024: stride0 = max(260, 512 + 4) = 516, stride1 = 256 + 4 = 260: 64: 198656 + 4096 no; 48: 148992 + 4096 = 153088
+    #   D 640, 256/512/1024: stride0 = max(644, 516) = 644, stride1 = 260: 48: 173568 + 4096 no; 32: 115712 + 4096 = 119808
+    #   D 0, 64:             stride0 = 4, stride1 = 0: 64: 1024 + 256 = 1280
+    #   D 1024, 4 x 1024:    stride0 = stride1 = 1028: 32: 263168 + 4096 no; 16: 131584 + 4096 = 135680
+    assert SGL.rows_tile(256, (256, 512, 1024)) == 48 and SGL.rows_tile(640, (256, 512, 1024)) == 32
+    assert SGL.rows_tile(0, (64,)) == 64 and SGL.rows_tile(1024, (1024,) * 4) == 16
+    #   the tile-crossing cases of tests/test_hip_sa_global.py - D 700, (8,): stride0 = 704 + 4 = 708: 64: 181248 + 64 no; 48: 135936 + 64
+    #   D 1000, (8,): stride0 = 1004: 48: 192768 + 64 no; 32: 128512 + 64.  D 1000, (600, 8): stride1 = 600 + 4: 32: 205824 + 64 no; 16: 102912 + 64
+    assert SGL.rows_tile(700, (8,)) == 48 and SGL.rows_tile(1000, (8,)) == 32 and SGL.rows_tile(1000, (600, 8)) == 16 and SGL.rows_tile(0, (5,)) == 64
+    assert SGL.rows_tile(1025, (8,)) == 0 and SGL.rows_tile(0, (1025,)) == 0 and SGL.rows_tile(0, ()) == 0 and SGL.rows_tile(0, (8,) * 5) == 0
+    header = open(_lib.HEADER_PATH).read()
+    abi = int(re.search(r"#define SVNET_ABI_VERSION (\d+)", header).group(1))
+    assert _lib.lib().svnet_version() == _lib.ABI_VERSION == abi >= 430
+    assert "430: svnet_sa_global_f32, svnet_sa_global_supported, svnet_sa_global_rows_tile" in header
+    assert "fused global set-abstraction level" in header
+    for name in ("svnet_sa_global_f32", "svnet_sa_global_supported", "svnet_sa_global_rows_tile"):
+        assert name in _lib.SIGNATURES and hasattr(_lib.lib(), name)
+    assert _lib.SIGNATURES["svnet_sa_global_f32"][1][2] is _lib.c_i64 and len(_lib.SIGNATURES["svnet_sa_global_f32"][1]) == 13
+    L = _lib.lib()                                                    # refused before any launch: no device is touched
+    w = (_lib.c_i64 * 1)(8)
+    one = (_lib.c_p * 1)(64)
+    p = _lib.c_p(64)
+    assert L.svnet_sa_global_f32(None, None, 1, 16, 0, 1, w, one, one, p, 8, 0, None) == _lib.DEFINES["SVNET_E_ARG"]
+    assert L.svnet_sa_global_f32(p, None, 1, 16, 2, 1, w, one, one, p, 8, 0, None) == _lib.DEFINES["SVNET_E_ARG"]              # null points, D > 0
+    assert L.svnet_sa_global_f32(p, None, 0, 16, 0, 1, w, one, one, p, 8, 0, None) == _lib.DEFINES["SVNET_E_ARG"]              # B 0
+    assert L.svnet_sa_global_f32(p, None, 1, 32769, 0, 1, w, one, one, p, 8, 0, None) == _lib.DEFINES["SVNET_E_UNSUPPORTED"]
+    assert b"svnet_sa_global_f32" in L.svnet_last_error()
+    assert L.svnet_sa_global_f32(p, None, 1, 16, 0, 1, w, one, one, p, 8, 1, None) == _lib.DEFINES["SVNET_E_ARG"]              # c_off + 8 > 8
+    # B x ceil(N / rows) past a 32-bit grid: 2^27 clouds x 512 tiles of 64 rows
+    assert L.svnet_sa_global_f32(p, None, 1 << 27, 32768, 0, 1, w, one, one, p, 8, 0, None) == _lib.DEFINES["SVNET_E_UNSUPPORTED"]
+    assert b"workgroups" in L.svnet_last_error()
+
+
+# ---- the argument checks of the front end (no device needed: every refusal comes before the first launch)
+def _fake_level(c_in, widths):
+    from svnet_amd import sa_fused as SF
+    level = object.__new__(SF.FoldedLevel)
+    level.c_in, level.widths, level.device = c_in, tuple(widths), torch.device("cpu")
+    return level
+
+
+def test_global_mlp_max_refuses_bad_arguments():
+    from svnet_amd import sa_global as SGL
+    B, N, D = 2, 16, 2
+    xyz, pts, level = torch.zeros(B, 3, N), torch.zeros(B, D, N), _fake_level(3 + D, (8,))
+    with pytest.raises(TypeError, match="FoldedLevel"):
+        SGL.global_mlp_max(xyz, pts, object())
+    with pytest.raises(TypeError, match="xyz must be torch.float32"):
+        SGL.global_mlp_max(xyz.double(), pts, level)
+    with pytest.raises(TypeError, match="points must be a tensor"):
+        SGL.global_mlp_max(xyz, pts.numpy(), level)
+    for k in ("xyz", "points"):
+        args = dict(xyz=xyz, points=pts)
+        args[k] = args[k].clone().requires_grad_()
+        with pytest.raises(ValueError, match="%s requires grad" % k):
+            SGL.global_mlp_max(args["xyz"], args["points"], level)
+    with pytest.raises(ValueError, match="xyz must be contiguous"):
+        SGL.global_mlp_max(torch.zeros(B, N, 3).permute(0, 2, 1), pts, level)
+    with pytest.raises(ValueError, match=r"xyz must be \[B,3,N\]"):
+        SGL.global_mlp_max(torch.zeros(B, N, 3), pts, level)
+    with pytest.raises(ValueError, match=r"points must be \[B,D,N\]"):
+        SGL.global_mlp_max(xyz, torch.zeros(B, D, N - 1), level)
+    with pytest.raises(ValueError, match="the level takes 5 input columns"):
+        SGL.global_mlp_max(xyz, None, level)
+    with pytest.raises(ValueError, match="out must be"):
+        SGL.global_mlp_max(xyz, pts, level, out=torch.zeros(B, 10, 1), c_off=3)
+    with pytest.raises(ValueError, match="out must be"):
+        SGL.global_mlp_max(xyz, pts, level, out=torch.zeros(B, 10, 2))
+    with pytest.raises(ValueError, match="c_off = 2 without out"):
+        SGL.global_mlp_max(xyz, pts, level, c_off=2)
+    # everything in order but the device: there is no CPU fallback
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        SGL.global_mlp_max(xyz, pts, level, out=torch.zeros(B, 10, 1), c_off=2)
+
+
+def test_the_wrapper_refuses_what_it_cannot_take():
+    from svnet_amd import sa_fused as SF
+    from svnet_amd import sa_global as SGL
+    from svnet_amd.models.utils.pointnet_util import PointNetSetAbstraction
+    with pytest.raises(TypeError, match="PointNetSetAbstraction"):
+        SGL.FusedGlobalAbstraction(torch.nn.Linear(3, 3))
+    with pytest.raises(ValueError, match="FusedSetAbstraction"):
+        SGL.FusedGlobalAbstraction(PointNetSetAbstraction(4, 0.2, 4, 7, [8], False))
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        SGL.FusedGlobalAbstraction(PointNetSetAbstraction(None, None, None, 7, [8, 300], True))
+    # the local wrapper goes on refusing a group_all level, and names this one
+    with pytest.raises(ValueError, match="group_all.*FusedGlobalAbstraction"):
+        SF.FusedSetAbstraction(PointNetSetAbstraction(None, None, None, 7, [8], True))
