@@ -7,8 +7,9 @@
 //                    the skip features points1[c, p], coalesced along p, and the interpolated ones, three gathers inside one
 //                    4 S-byte row of points2 per channel with the row's indices and weights resolved once, in registers - in
 //                    three_interpolate_kernel's arithmetic (propagate.hip).  Rows past N are zero rows.  The layers run through the
-//                    layer engine of mlp_tile.h (shared with sa_fused.hip), one barrier per layer; the last layer's epilogue, the
-//                    policy FpStore, is a channel-first global store: a lane holds one column of four consecutive points, 16 bytes.
+//                    layer engine of mlp_tile.h (shared with sa_fused.hip and sa_global.hip), one barrier between layers; the last
+//                    layer's epilogue, the policy FpStore, is a channel-first global store: a lane holds one column of four
+//                    consecutive points, 16 bytes.
 // The folds are sa_fused.hip's (svnet_sa_fold_f32).  Built with -ffp-contract=off (Makefile, NO_CONTRACT).
 #include "mlp_tile.h"
 
@@ -16,6 +17,7 @@ namespace {
 
 constexpr int FP_THREADS = MLP_THREADS;
 constexpr int FP_MAX_C0 = 1536, FP_MAX_S = SVNET_KNN_MAX_N;      // the envelope (svnet_fp_fused_supported)
+constexpr int FP_ROWS[] = {64, 32, 16};                          // powers of two: a thread finds its row and column by mask and shift
 
 // rows: points per workgroup, 64, 32 or 16, and shift = log2(rows); stride[p]: row stride of the activation buffer p (mlp_tile.h:
 // mlp_strides); lds = 4 rows (stride[0] + stride[1]) bytes.
@@ -25,16 +27,9 @@ inline bool fp_plan(int64_t D1, int64_t D2, int64_t L, const int64_t* widths, Fp
     if (!mlp_widths_ok(L, widths) || D1 < 0 || D2 < 1 || D1 > FP_MAX_C0 || D2 > FP_MAX_C0 || D1 + D2 > FP_MAX_C0) return false;
     pl = FpPlan{};
     mlp_strides(D1 + D2, L, widths, pl.stride);
-    for (int shift = 6; shift >= 4; --shift) {
-        const int64_t lds = (int64_t)4 * (1 << shift) * (pl.stride[0] + pl.stride[1]);
-        if (lds <= MLP_LDS_MAX) {
-            pl.rows = 1 << shift;
-            pl.shift = shift;
-            pl.lds = (int)lds;
-            return true;
-        }
-    }
-    return false;                                                // (not inside the envelope: 16 rows of 1540 + 260 floats are 113 KB)
+    if (!mlp_rows(FP_ROWS, pl.stride, 0, pl.rows, pl.lds)) return false;      // (not inside the envelope: 16 rows of 1540 + 260 floats are 113 KB)
+    pl.shift = __builtin_ctz(pl.rows);
+    return true;
 }
 
 // The last layer's epilogue (mlp_tile.h): column o of the tile's rows row .. row + 3 - four consecutive points of channel c_off + o.
@@ -101,17 +96,7 @@ __global__ __launch_bounds__(FP_THREADS) __attribute__((amdgpu_waves_per_eu(4, 4
     }
     __syncthreads();
     const FpStore store = {out + (b * C_total + c_off) * N + p0, N, nrows, wide != 0};
-    for (int l = 0; l < lv.L; ++l) {
-        const float* in = l & 1 ? buf1 : buf0;
-        float* outb = l & 1 ? buf0 : buf1;
-        const int sin = pl.stride[l & 1], sout = pl.stride[(l & 1) ^ 1];
-        if (l + 1 < lv.L) {
-            mlp_layer_rt(nrt, lv.w[l], lv.b[l], lv.C[l], lv.C[l + 1], in, sin, outb, sout, MlpToLds{}, wave, lane);
-            __syncthreads();
-        } else {
-            mlp_layer_rt(nrt, lv.w[l], lv.b[l], lv.C[l], lv.C[l + 1], in, sin, outb, sout, store, wave, lane);
-        }
-    }
+    mlp_stack<false>(nrt, lv, pl.stride, buf0, buf1, store, wave, lane);       // (no barrier behind the global stores)
 }
 
 }  // namespace
@@ -138,29 +123,16 @@ extern "C" int svnet_fp_fused_f32(const int64_t* idx, const float* weight, const
                   "svnet_fp_fused_f32: N %lld, S %lld, D1 %lld, D2 %lld, L %lld: needs N >= 1, 1 <= S <= %lld, D1 >= 0, D2 >= 1, D1 + D2 <= %d, 1 <= L <= %d, every 1 <= width <= %d",
                   (long long)N, (long long)S, (long long)D1, (long long)D2, (long long)L, (long long)FP_MAX_S, FP_MAX_C0, SVNET_SA_MAX_LAYERS,
                   MLP_MAX_WIDTH);
-    SVNET_REQUIRE(c_off >= 0 && c_off + widths[L - 1] <= C_total, SVNET_E_ARG, "svnet_fp_fused_f32: channels %lld .. %lld outside C_total %lld",
-                  (long long)c_off, (long long)(c_off + widths[L - 1]), (long long)C_total);
-    MlpLevel lv = {};
-    lv.L = (int)L;
-    lv.C[0] = (int)(D1 + D2);
-    const float* const* w = static_cast<const float* const*>(wf);
-    const float* const* bb = static_cast<const float* const*>(bf);
-    for (int l = 0; l < lv.L; ++l) {
-        SVNET_REQUIRE(w[l] && bb[l], SVNET_E_ARG, "svnet_fp_fused_f32: null wf[%d] / bf[%d]", l, l);
-        lv.w[l] = w[l];
-        lv.b[l] = bb[l];
-        lv.C[l + 1] = (int)widths[l];
-    }
+    if (const int e = mlp_window("svnet_fp_fused_f32", c_off, widths[L - 1], C_total)) return e;
+    MlpLevel lv;
+    if (const int e = mlp_level("svnet_fp_fused_f32", D1 + D2, L, widths, wf, bf, lv)) return e;
     const CloudGrid grid = cloud_grid(B, N, pl.rows);
     SVNET_REQUIRE(grid.blocks > 0, SVNET_E_UNSUPPORTED, "svnet_fp_fused_f32: B %lld x ceil(N %lld / %d) workgroups > 2^31 - 1", (long long)B,
                   (long long)N, pl.rows);
-    bool ok = true;
-    if (pl.lds > 64 * 1024) SVNET_LDS_OPTIN(ok, MLP_LDS_MAX, "svnet_fp_fused_f32", reinterpret_cast<const void*>(&fp_fused_kernel));
-    if (!ok) return SVNET_E_LAUNCH;
-    if (!points1) points1 = points2;                             // D1 = 0: never read
+    if (const int e = mlp_lds_optin<&fp_fused_kernel>("svnet_fp_fused_f32", pl.lds)) return e;
     const int wide = N % 4 == 0 && reinterpret_cast<uintptr_t>(out) % 16 == 0;
     hipLaunchKernelGGL(fp_fused_kernel, dim3((unsigned)grid.blocks), dim3(FP_THREADS), (size_t)pl.lds, (hipStream_t)stream, idx, weight, points2,
-                       points1, N, (int)S, (int)D1, (int)D2, grid.chunks, lv, pl, out, C_total, c_off, wide);
+                       mlp_optional(points1, points2), N, (int)S, (int)D1, (int)D2, grid.chunks, lv, pl, out, C_total, c_off, wide);
     SVNET_CHECK_LAUNCH("fp_fused_kernel");
     return SVNET_OK;
 }

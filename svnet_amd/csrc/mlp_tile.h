@@ -4,7 +4,9 @@
 // bit for bit: the bias is the accumulator's start, a wave owns 16-column tiles over the full K, and K is never split, so no value
 // depends on how rows or columns are tiled.  Activations ping-pong between two LDS buffers, weights come from global
 // memory (L2-resident) into registers, MLP_U k-steps ahead.  What happens to the LAST layer's ReLU outputs is the caller's: an epilogue
-// policy (below).  Internal: not part of the C interface.  The files that include this are built with -ffp-contract=off (Makefile).
+// policy (below).  Around the engine, stated once too: the host's plan pieces (mlp_strides, mlp_opad, mlp_rows), its launch pieces
+// (mlp_level, mlp_window, mlp_optional, mlp_lds_optin) and the kernels' loop over the layers (mlp_stack); the gather into buffer 0, the
+// policy and sa_fused.hip's plan in centres are each level's own.  Internal: not part of the C interface.  Built with -ffp-contract=off.
 #pragma once
 #include "pointset.h"
 
@@ -38,12 +40,60 @@ inline void mlp_strides(int64_t C0, int64_t L, const int64_t* widths, int (&stri
     }
 }
 
+// The last width padded to whole column tiles: a row of a kernel's table of column maxima.
+inline int mlp_opad(int64_t L, const int64_t* widths) { return pad_to(widths[L - 1], 16); }
+
+// The row plan of a kernel whose workgroup takes `rows` consecutive rows: the first of `cands` (descending) whose two activation
+// buffers and `extra` more bytes fit in LDS, lds = 4 rows (stride[0] + stride[1]) + extra <= MLP_LDS_MAX; false when none does.
+template <int NC>
+inline bool mlp_rows(const int (&cands)[NC], const int (&stride)[2], int64_t extra, int& rows, int& lds) {
+    for (const int r : cands) {
+        const int64_t need = (int64_t)4 * r * (stride[0] + stride[1]) + extra;
+        if (need <= MLP_LDS_MAX) { rows = r; lds = (int)need; return true; }
+    }
+    return false;
+}
+
 // (max_width: the column-tile loop of mlp_layer takes any width; a kernel's envelope may be wider than MLP_MAX_WIDTH - sa_global.hip)
 inline bool mlp_widths_ok(int64_t L, const int64_t* widths, int64_t max_width = MLP_MAX_WIDTH) {
     if (!widths || L < 1 || L > SVNET_SA_MAX_LAYERS) return false;
     for (int64_t l = 0; l < L; ++l)
         if (widths[l] < 1 || widths[l] > max_width) return false;
     return true;
+}
+
+// ---- the launch pieces of an entry point `name` (svnet_*_f32): each returns SVNET_OK or, with svnet_last_error set, the error.
+// The level of a call from its arguments: C0 input columns, and per layer the width and the folded weights and bias.
+inline int mlp_level(const char* name, int64_t C0, int64_t L, const int64_t* widths, const void* wf, const void* bf, MlpLevel& lv) {
+    lv = MlpLevel{};
+    lv.L = (int)L;
+    lv.C[0] = (int)C0;
+    const auto w = static_cast<const float* const*>(wf), bb = static_cast<const float* const*>(bf);
+    for (int l = 0; l < lv.L; ++l) {
+        SVNET_REQUIRE(w[l] && bb[l], SVNET_E_ARG, "%s: null wf[%d] / bf[%d]", name, l, l);
+        lv.w[l] = w[l];
+        lv.b[l] = bb[l];
+        lv.C[l + 1] = (int)widths[l];
+    }
+    return SVNET_OK;
+}
+
+// The window of the result: the level's CL channels from c_off on lie inside the C_total of out.
+inline int mlp_window(const char* name, int64_t c_off, int64_t CL, int64_t C_total) {
+    SVNET_REQUIRE(c_off >= 0 && c_off + CL <= C_total, SVNET_E_ARG, "%s: channels %lld .. %lld outside C_total %lld", name, (long long)c_off,
+                  (long long)(c_off + CL), (long long)C_total);
+    return SVNET_OK;
+}
+
+// A feature matrix of zero columns may be null.  It is never read, but the kernels form addresses from it: any valid pointer serves.
+inline const float* mlp_optional(const float* p, const float* other) { return p ? p : other; }
+
+// The opt-in of KERNEL (one record of the devices done per kernel: common.h) to MLP_LDS_MAX bytes of dynamic LDS where the plan needs it.
+template <auto KERNEL>
+inline int mlp_lds_optin(const char* name, int lds) {
+    bool ok = true;
+    if (lds > 64 * 1024) SVNET_LDS_OPTIN(ok, MLP_LDS_MAX, name, reinterpret_cast<const void*>(KERNEL));
+    return ok ? SVNET_OK : SVNET_E_LAUNCH;
 }
 
 // The epilogue of a layer that is not the last: its outputs go to the other activation buffer (mlp_layer does that itself).
@@ -129,6 +179,22 @@ __device__ __forceinline__ void mlp_layer_rt(int nrt, const float* W, const floa
         case 2: mlp_layer<2>(W, bias, Cin, O, in, sin, outb, sout, epi, wave, lane); break;
         case 3: mlp_layer<3>(W, bias, Cin, O, in, sin, outb, sout, epi, wave, lane); break;
         default: mlp_layer<4>(W, bias, Cin, O, in, sin, outb, sout, epi, wave, lane); break;
+    }
+}
+
+// The layer stack over the NRT = nrt 16-row tiles in buffer 0: layer l reads buffer l & 1 and writes the other one, with a barrier
+// behind it; the last layer's ReLU outputs go to `last` instead - handed over by value, so a policy may keep state during the layer.
+// BARRIER_LAST: a barrier behind the last layer too, for a policy whose results the workgroup reads back from LDS.
+template <bool BARRIER_LAST, class Epi>
+__device__ __forceinline__ void mlp_stack(int nrt, const MlpLevel& lv, const int (&stride)[2], float* buf0, float* buf1, Epi last, int wave,
+                                          int lane) {
+    for (int l = 0; l < lv.L; ++l) {
+        const float* in = l & 1 ? buf1 : buf0;
+        float* outb = l & 1 ? buf0 : buf1;
+        const int sin = stride[l & 1], sout = stride[(l & 1) ^ 1];
+        if (l + 1 < lv.L) mlp_layer_rt(nrt, lv.w[l], lv.b[l], lv.C[l], lv.C[l + 1], in, sin, outb, sout, MlpToLds{}, wave, lane);
+        else mlp_layer_rt(nrt, lv.w[l], lv.b[l], lv.C[l], lv.C[l + 1], in, sin, outb, sout, last, wave, lane);
+        if (BARRIER_LAST || l + 1 < lv.L) __syncthreads();
     }
 }
 

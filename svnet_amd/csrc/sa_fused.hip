@@ -6,7 +6,7 @@
 //   sa_fused_kernel  a workgroup takes a tile of SF_ROWS grouped rows - whole centres when a group has at most SF_ROWS slots, else the
 //                    tiles of one centre one after the other - gathers them into LDS and runs the layers through the layer engine
 //                    of mlp_tile.h (v_mfma_f32_16x16x4_f32, bit for bit a c-ascending fmaf chain that starts at the bias; the engine
-//                    is shared with fp_fused.hip).  The last layer is not stored: its ReLU output, >= +0, goes into a per-centre
+//                    is shared with the other levels).  The last layer is not stored: its ReLU output, >= +0, goes into a per-centre
 //                    column maximum by an integer LDS maximum on the bit patterns, which is order-free (the epilogue policy SaMax).
 // Built with -ffp-contract=off (Makefile, NO_CONTRACT).
 #include "mlp_tile.h"
@@ -21,14 +21,14 @@ constexpr int SF_LDS_MAX = MLP_LDS_MAX;
 constexpr int SF_HEAD = SF_ROWS * 8 + SF_ROWS * 4 + (SF_ROWS + 4) * 4 + SF_ROWS * 4;      // s_src | s_ctr | s_start (+ total) | s_lim
 static_assert(SF_HEAD % 16 == 0, "the float regions behind the row tables stay 16-byte aligned");
 
-// cpw: centres per workgroup; stride[p]: row stride of the activation buffer p (mlp_tile.h: mlp_strides); opad: the last width padded
-// to whole column tiles.
+// cpw: centres per workgroup; stride[p]: row stride of the activation buffer p and opad: the last width padded to whole column tiles
+// (mlp_tile.h: mlp_strides, mlp_opad).
 struct SaPlan { int cpw, stride[2], opad, lds; };
 
 inline bool sa_plan(int64_t N, int64_t S, int64_t K, int64_t D, int64_t L, const int64_t* widths, SaPlan& pl) {
     if (!mlp_widths_ok(L, widths) || !svnet_group_supported(N, S, K, D) || 3 + D > SF_MAX_C0) return false;
     pl = SaPlan{};
-    pl.opad = pad_to(widths[L - 1], 16);
+    pl.opad = mlp_opad(L, widths);
     mlp_strides(3 + D, L, widths, pl.stride);
     const int fixed = SF_HEAD + 4 * SF_ROWS * (pl.stride[0] + pl.stride[1]);
     int64_t room = (SF_LDS_MAX - fixed) / 4;                     // floats left for the maxima
@@ -161,14 +161,7 @@ __global__ __launch_bounds__(SF_THREADS) __attribute__((amdgpu_waves_per_eu(4, 4
             }
         }
         __syncthreads();
-        for (int l = 0; l < lv.L; ++l) {
-            const float* in = l & 1 ? buf1 : buf0;
-            float* outb = l & 1 ? buf0 : buf1;
-            const int sin = pl.stride[l & 1], sout = pl.stride[(l & 1) ^ 1];
-            if (l + 1 < lv.L) mlp_layer_rt(nrt, lv.w[l], lv.b[l], lv.C[l], lv.C[l + 1], in, sin, outb, sout, MlpToLds{}, wave, lane);
-            else mlp_layer_rt(nrt, lv.w[l], lv.b[l], lv.C[l], lv.C[l + 1], in, sin, outb, sout, SaMax{s_ctr, smax, pl.opad}, wave, lane);
-            __syncthreads();
-        }
+        mlp_stack<true>(nrt, lv, pl.stride, buf0, buf1, SaMax{s_ctr, smax, pl.opad}, wave, lane);      // (the barrier: smax, and the next tile's tables)
     }
     // channel-first: the workgroup's centres of a channel lie side by side
     float* dst = out + (b * C_total + c_off) * S + s0;
@@ -212,30 +205,17 @@ extern "C" int svnet_sa_fused_f32(const float* xyz, const float* new_xyz, const 
                   SVNET_SA_MAX_LAYERS, SF_MAX_WIDTH);
     SVNET_REQUIRE(idx_ld >= K && (!count || count_ld >= 1), SVNET_E_ARG, "svnet_sa_fused_f32: idx_ld %lld < K %lld, or count_ld %lld < 1",
                   (long long)idx_ld, (long long)K, (long long)count_ld);
-    SVNET_REQUIRE(c_off >= 0 && c_off + widths[L - 1] <= C_total, SVNET_E_ARG, "svnet_sa_fused_f32: channels %lld .. %lld outside C_total %lld",
-                  (long long)c_off, (long long)(c_off + widths[L - 1]), (long long)C_total);
+    if (const int e = mlp_window("svnet_sa_fused_f32", c_off, widths[L - 1], C_total)) return e;
     SVNET_REQUIRE(B <= 0x7fffffffll / S / idx_ld, SVNET_E_UNSUPPORTED, "svnet_sa_fused_f32: B %lld x S %lld x idx_ld %lld indices > 2^31 - 1",
                   (long long)B, (long long)S, (long long)idx_ld);
-    MlpLevel lv = {};
-    lv.L = (int)L;
-    lv.C[0] = (int)(3 + D);
-    const float* const* w = static_cast<const float* const*>(wf);
-    const float* const* bb = static_cast<const float* const*>(bf);
-    for (int l = 0; l < lv.L; ++l) {
-        SVNET_REQUIRE(w[l] && bb[l], SVNET_E_ARG, "svnet_sa_fused_f32: null wf[%d] / bf[%d]", l, l);
-        lv.w[l] = w[l];
-        lv.b[l] = bb[l];
-        lv.C[l + 1] = (int)widths[l];
-    }
+    MlpLevel lv;
+    if (const int e = mlp_level("svnet_sa_fused_f32", 3 + D, L, widths, wf, bf, lv)) return e;
     const CloudGrid grid = cloud_grid(B, S, pl.cpw);
     SVNET_REQUIRE(grid.blocks > 0, SVNET_E_UNSUPPORTED, "svnet_sa_fused_f32: B %lld x ceil(S %lld / %d) workgroups > 2^31 - 1", (long long)B,
                   (long long)S, pl.cpw);
-    bool ok = true;
-    if (pl.lds > 64 * 1024) SVNET_LDS_OPTIN(ok, SF_LDS_MAX, "svnet_sa_fused_f32", reinterpret_cast<const void*>(&sa_fused_kernel));
-    if (!ok) return SVNET_E_LAUNCH;
-    if (!points) points = xyz;                                   // D = 0: never read
-    hipLaunchKernelGGL(sa_fused_kernel, dim3((unsigned)grid.blocks), dim3(SF_THREADS), (size_t)pl.lds, (hipStream_t)stream, xyz, new_xyz, points, idx,
-                       idx_ld, count, count_ld, N, S, (int)K, (int)D, grid.chunks, lv, pl, xyz_last, out, C_total, c_off);
+    if (const int e = mlp_lds_optin<&sa_fused_kernel>("svnet_sa_fused_f32", pl.lds)) return e;
+    hipLaunchKernelGGL(sa_fused_kernel, dim3((unsigned)grid.blocks), dim3(SF_THREADS), (size_t)pl.lds, (hipStream_t)stream, xyz, new_xyz,
+                       mlp_optional(points, xyz), idx, idx_ld, count, count_ld, N, S, (int)K, (int)D, grid.chunks, lv, pl, xyz_last, out, C_total, c_off);
     SVNET_CHECK_LAUNCH("sa_fused_kernel");
     return SVNET_OK;
 }

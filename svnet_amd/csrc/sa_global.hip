@@ -21,25 +21,18 @@ namespace {
 
 constexpr int SG_THREADS = MLP_THREADS;
 constexpr int SG_MAX_N = SVNET_KNN_MAX_N, SG_MAX_D = 1024, SG_MAX_WIDTH = 1024;      // the envelope (svnet_sa_global_supported)
+constexpr int SG_ROWS[] = {64, 48, 32, 16};                      // whole 16-row tiles
 
-// rows: points per workgroup; stride[p]: row stride of the activation buffer p (mlp_tile.h: mlp_strides); opad: the last width padded
-// to whole column tiles; lds = 4 rows (stride[0] + stride[1]) + 4 opad bytes.
+// rows: points per workgroup; stride[p]: row stride of the activation buffer p and opad: the last width padded to whole column tiles
+// (mlp_tile.h: mlp_strides, mlp_opad); lds = 4 rows (stride[0] + stride[1]) + 4 opad bytes.
 struct SgPlan { int rows, stride[2], opad, lds; };
 
 inline bool sg_plan(int64_t D, int64_t L, const int64_t* widths, SgPlan& pl) {
     if (!mlp_widths_ok(L, widths, SG_MAX_WIDTH) || D < 0 || D > SG_MAX_D) return false;
     pl = SgPlan{};
-    pl.opad = pad_to(widths[L - 1], 16);
+    pl.opad = mlp_opad(L, widths);
     mlp_strides(3 + D, L, widths, pl.stride);
-    for (int rows = 64; rows >= 16; rows -= 16) {
-        const int64_t lds = (int64_t)4 * rows * (pl.stride[0] + pl.stride[1]) + 4 * pl.opad;
-        if (lds <= MLP_LDS_MAX) {
-            pl.rows = rows;
-            pl.lds = (int)lds;
-            return true;
-        }
-    }
-    return false;                                                // (not inside the envelope: 16 rows of 1028 + 1028 floats and 1024 maxima are 133 KB)
+    return mlp_rows(SG_ROWS, pl.stride, 4 * pl.opad, pl.rows, pl.lds);      // (true inside the envelope: 16 rows of 1028 + 1028 floats and 1024 maxima are 133 KB)
 }
 
 __global__ __launch_bounds__(SG_THREADS) void sg_zero_kernel(float* __restrict__ out, int64_t total, int CL, int64_t C_total, int64_t c_off) {
@@ -104,14 +97,7 @@ __global__ __launch_bounds__(SG_THREADS) __attribute__((amdgpu_waves_per_eu(4, 4
         }
     }
     __syncthreads();
-    for (int l = 0; l < lv.L; ++l) {
-        const float* in = l & 1 ? buf1 : buf0;
-        float* outb = l & 1 ? buf0 : buf1;
-        const int sin = pl.stride[l & 1], sout = pl.stride[(l & 1) ^ 1];
-        if (l + 1 < lv.L) mlp_layer_rt(nrt, lv.w[l], lv.b[l], lv.C[l], lv.C[l + 1], in, sin, outb, sout, MlpToLds{}, wave, lane);
-        else mlp_layer_rt(nrt, lv.w[l], lv.b[l], lv.C[l], lv.C[l + 1], in, sin, outb, sout, SgMax{smax, nrows, r16 - 16, 0u}, wave, lane);
-        __syncthreads();
-    }
+    mlp_stack<true>(nrt, lv, pl.stride, buf0, buf1, SgMax{smax, nrows, r16 - 16, 0u}, wave, lane);      // (the barrier: smax is read below)
     // across the workgroups of a cloud: an integer maximum on the bit patterns of out, which sg_zero_kernel set to +0
     unsigned* dst = reinterpret_cast<unsigned*>(out + b * C_total + c_off);
     for (int o = t; o < OL; o += SG_THREADS) {
@@ -141,31 +127,18 @@ extern "C" int svnet_sa_global_f32(const float* xyz, const float* points, int64_
     SVNET_REQUIRE(svnet_sa_global_supported(N, D, L, widths) && sg_plan(D, L, widths, pl), SVNET_E_UNSUPPORTED,
                   "svnet_sa_global_f32: N %lld, D %lld, L %lld: needs 1 <= N <= %d, 0 <= D <= %d, 1 <= L <= %d, every 1 <= width <= %d",
                   (long long)N, (long long)D, (long long)L, SG_MAX_N, SG_MAX_D, SVNET_SA_MAX_LAYERS, SG_MAX_WIDTH);
-    SVNET_REQUIRE(c_off >= 0 && c_off + widths[L - 1] <= C_total, SVNET_E_ARG, "svnet_sa_global_f32: channels %lld .. %lld outside C_total %lld",
-                  (long long)c_off, (long long)(c_off + widths[L - 1]), (long long)C_total);
-    MlpLevel lv = {};
-    lv.L = (int)L;
-    lv.C[0] = (int)(3 + D);
-    const float* const* w = static_cast<const float* const*>(wf);
-    const float* const* bb = static_cast<const float* const*>(bf);
-    for (int l = 0; l < lv.L; ++l) {
-        SVNET_REQUIRE(w[l] && bb[l], SVNET_E_ARG, "svnet_sa_global_f32: null wf[%d] / bf[%d]", l, l);
-        lv.w[l] = w[l];
-        lv.b[l] = bb[l];
-        lv.C[l + 1] = (int)widths[l];
-    }
+    if (const int e = mlp_window("svnet_sa_global_f32", c_off, widths[L - 1], C_total)) return e;
+    MlpLevel lv;
+    if (const int e = mlp_level("svnet_sa_global_f32", 3 + D, L, widths, wf, bf, lv)) return e;
     const CloudGrid grid = cloud_grid(B, N, pl.rows);
     SVNET_REQUIRE(grid.blocks > 0, SVNET_E_UNSUPPORTED, "svnet_sa_global_f32: B %lld x ceil(N %lld / %d) workgroups > 2^31 - 1", (long long)B,
                   (long long)N, pl.rows);
-    bool ok = true;
-    if (pl.lds > 64 * 1024) SVNET_LDS_OPTIN(ok, MLP_LDS_MAX, "svnet_sa_global_f32", reinterpret_cast<const void*>(&sa_global_kernel));
-    if (!ok) return SVNET_E_LAUNCH;
-    if (!points) points = xyz;                                   // D = 0: never read
+    if (const int e = mlp_lds_optin<&sa_global_kernel>("svnet_sa_global_f32", pl.lds)) return e;
     const int CL = (int)widths[L - 1];
     hipLaunchKernelGGL(sg_zero_kernel, dim3(svnet_grid(B * CL, SG_THREADS)), dim3(SG_THREADS), 0, (hipStream_t)stream, out, B * CL, CL, C_total, c_off);
     SVNET_CHECK_LAUNCH("sg_zero_kernel");
-    hipLaunchKernelGGL(sa_global_kernel, dim3((unsigned)grid.blocks), dim3(SG_THREADS), (size_t)pl.lds, (hipStream_t)stream, xyz, points, N, (int)D,
-                       grid.chunks, lv, pl, out, C_total, c_off);
+    hipLaunchKernelGGL(sa_global_kernel, dim3((unsigned)grid.blocks), dim3(SG_THREADS), (size_t)pl.lds, (hipStream_t)stream, xyz, mlp_optional(points, xyz), N,
+                       (int)D, grid.chunks, lv, pl, out, C_total, c_off);
     SVNET_CHECK_LAUNCH("sa_global_kernel");
     return SVNET_OK;
 }

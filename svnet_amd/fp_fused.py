@@ -32,31 +32,25 @@ require grad.  There is no CPU fallback: tensors that are not on a HIP device ra
 """
 import torch
 
-from . import _lib, _ops, _pointset
+from . import _level, _lib, _ops, _pointset
+from ._level import MAX_LAYERS, fold_level
 from .propagate import _nn_launch
-from .sa_fused import MAX_LAYERS, FoldedLevel, fold_level
 
 __all__ = ["interp_mlp", "supported", "rows_tile", "FusedFeaturePropagation"]
 
 _WHAT = "the fused feature-propagation level"      # in the messages of _pointset.check_tensors
 MAX_C0 = 1536
-
-
-def _c_widths(widths):
-    widths = [int(w) for w in widths]
-    return len(widths), (_lib.c_i64 * max(len(widths), 1))(*widths)
+_F32 = torch.float32
 
 
 def rows_tile(D1, D2, widths):
     """Consecutive points one workgroup takes for this level: 64, 32 or 16; 0 outside the limits on D1, D2 and the widths."""
-    L, c = _c_widths(widths)
-    return int(_lib.lib().svnet_fp_fused_rows_tile(int(D1), int(D2), L, c))
+    return int(_lib.lib().svnet_fp_fused_rows_tile(int(D1), int(D2), *_level.c_widths(widths)))
 
 
 def supported(N, S, D1, D2, widths):
     """Whether the fused kernel takes this level (module docstring, limits)."""
-    L, c = _c_widths(widths)
-    return bool(_lib.lib().svnet_fp_fused_supported(int(N), int(S), int(D1), int(D2), L, c))
+    return bool(_lib.lib().svnet_fp_fused_supported(int(N), int(S), int(D1), int(D2), *_level.c_widths(widths)))
 
 
 def _launch(idx, weight, points2, points1, level, out, c_off, B, N, S, D1, D2):
@@ -70,16 +64,9 @@ def interp_mlp(idx, weight, points2, points1, level, out=None, c_off=0):
     for D1 + D2 input columns -> out [B,C_total,N] with channels c_off .. c_off + C_out - 1 written (module docstring); out=None
     allocates [B,C_out,N].  One launch on the current stream, no host read, no workspace.  No argument may require grad."""
     name = "interp_mlp"
-    if not isinstance(level, FoldedLevel):
-        raise TypeError("%s: level must be a FoldedLevel (sa_fused.fold_level), got %s" % (name, type(level).__name__))
-    tensors, dtypes = {"points2": points2, "idx": idx, "weight": weight}, [torch.float32, torch.int64, torch.float32]
-    if points1 is not None:
-        tensors["points1"] = points1
-        dtypes.append(torch.float32)
-    if out is not None:
-        tensors["out"] = out
-        dtypes.append(torch.float32)
-    _pointset.check_tensors(name, tensors, dtypes, _WHAT)
+    _level.check_is_level(name, level)
+    _level.check_args(name, _WHAT, {"points2": (points2, _F32), "idx": (idx, torch.int64), "weight": (weight, _F32)},
+                      {"points1": (points1, _F32), "out": (out, _F32)})
     if points2.dim() != 3 or points2.shape[0] < 1:
         raise ValueError("%s: points2 must be [B,D2,S], got %s" % (name, tuple(points2.shape)))
     B, D2, S = (int(v) for v in points2.shape)
@@ -90,27 +77,19 @@ def interp_mlp(idx, weight, points2, points1, level, out=None, c_off=0):
         if points1.dim() != 3 or points1.shape[0] != B or points1.shape[2] != N:
             raise ValueError("%s: points1 must be [B,D1,N] with B = %d, N = %d, got %s" % (name, B, N, tuple(points1.shape)))
         D1 = int(points1.shape[1])
-    if level.c_in != D1 + D2:
-        raise ValueError("%s: the level takes %d input columns, points1 and points2 give %d + %d" % (name, level.c_in, D1, D2))
-    c_off, C = int(c_off), level.widths[-1]
-    if out is not None and (out.dim() != 3 or out.shape[0] != B or out.shape[2] != N or c_off < 0 or c_off + C > out.shape[1]):
-        raise ValueError("%s: out must be [B,C_total,N] with B = %d, N = %d and channels %d .. %d inside it, got %s"
-                         % (name, B, N, c_off, c_off + C - 1, tuple(out.shape)))
-    if out is None and c_off:
-        raise ValueError("%s: c_off = %d without out" % (name, c_off))
+    _level.check_c_in(name, level, D1 + D2, "points1 and points2 give %d + %d" % (D1, D2))
+    c_off = _level.check_window(name, out, c_off, level, B, N, "N")
     _ops._hip(points2, idx, weight, points1, out)
-    if level.device != points2.device:
-        raise ValueError("%s: the level is on %s, points2 on %s" % (name, level.device, points2.device))
+    _level.check_device(name, level, "points2", points2)
     if not supported(N, S, D1, D2, level.widths):
         raise _lib.SvnetHipError("%s: N = %d, S = %d, D1 = %d, D2 = %d, widths %s is not supported (N >= 1, 1 <= S <= %d, D2 >= 1, D1 + D2 <= %d, "
                                  "1 .. %d layers of width 1 .. 256)" % (name, N, S, D1, D2, list(level.widths), _pointset.MAX_N, MAX_C0, MAX_LAYERS))
-    if out is None:
-        out = torch.empty(B, C, N, dtype=torch.float32, device=points2.device)
+    out = _level.result(out, level, B, N, points2.device)
     _launch(idx, weight, points2, points1, level, out, c_off, B, N, S, D1, D2)
     return out
 
 
-class FusedFeaturePropagation:
+class FusedFeaturePropagation(_level.FusedWrapper):
     """The eval-mode forward of a PointNetFeaturePropagation on a HIP device, with the module's signature and result:
 
         fused(xyz1 [B,3,N], xyz2 [B,3,S], points1 [B,D1,N] or None, points2 [B,D2,S]) -> [B,C,N]
@@ -126,11 +105,7 @@ class FusedFeaturePropagation:
             raise TypeError("FusedFeaturePropagation: needs a PointNetFeaturePropagation, got %s" % type(module).__name__)
         self.module = module
         self.level = fold_level(module.mlp_convs, module.mlp_bns)
-        self.channels = self.level.widths[-1]
-
-    def refresh(self):
-        self.level.refresh()
-        return self
+        self.levels, self.channels = [self.level], self.level.widths[-1]
 
     def supported(self, N, S, D1, D2):
         """Whether clouds of N points over S sampled ones with D1 + D2 columns take the fused path here; else __call__ runs the module."""
@@ -138,32 +113,13 @@ class FusedFeaturePropagation:
 
     @torch.no_grad()
     def __call__(self, xyz1, xyz2, points1, points2):
-        name = "FusedFeaturePropagation"
-        if self.module.training:
-            raise RuntimeError("%s: the module is in train mode - this is the eval-mode forward (module.eval())" % name)
-        tensors, dtypes = {"xyz1": xyz1, "xyz2": xyz2, "points2": points2}, [torch.float32] * 3
-        if points1 is not None:
-            tensors["points1"] = points1
-            dtypes.append(torch.float32)
-        # (the module takes views: they are made contiguous below, so contiguity is not asked for here)
-        _pointset.check_tensors(name, {k: t.contiguous() if isinstance(t, torch.Tensor) else t for k, t in tensors.items()}, dtypes, _WHAT)
-        if xyz1.dim() != 3 or xyz1.shape[1] != 3 or xyz1.shape[0] < 1:
-            raise ValueError("%s: xyz1 must be [B,3,N], got %s" % (name, tuple(xyz1.shape)))
-        B, N = int(xyz1.shape[0]), int(xyz1.shape[2])
-        if xyz2.dim() != 3 or xyz2.shape[0] != B or xyz2.shape[1] != 3:
-            raise ValueError("%s: xyz2 must be [B,3,S] with B = %d, got %s" % (name, B, tuple(xyz2.shape)))
-        S = int(xyz2.shape[2])
-        if points2.dim() != 3 or points2.shape[0] != B or points2.shape[2] != S:
-            raise ValueError("%s: points2 must be [B,D2,S] with B = %d, S = %d, got %s" % (name, B, S, tuple(points2.shape)))
-        if points1 is not None and (points1.dim() != 3 or points1.shape[0] != B or points1.shape[2] != N):
-            raise ValueError("%s: points1 must be [B,D1,N] with B = %d, N = %d, got %s" % (name, B, N, tuple(points1.shape)))
-        D1, D2 = 0 if points1 is None else int(points1.shape[1]), int(points2.shape[1])
+        name = self._begin(_WHAT, {"xyz1": (xyz1, _F32), "xyz2": (xyz2, _F32), "points2": (points2, _F32)}, {"points1": (points1, _F32)})
+        B, N, S, D1, D2 = _level.cloud_pair_shapes(name, xyz1, xyz2, points1, points2)
         _ops._hip(xyz1, xyz2, points1, points2)
         if not self.supported(N, S, D1, D2):
             return self.module(xyz1, xyz2, points1, points2)
         dev = xyz1.device
-        if self.level.device != dev:
-            raise ValueError("%s: the level is on %s, xyz1 on %s" % (name, self.level.device, dev))
+        _level.check_device(name, self.level, "xyz1", xyz1)
         idx = torch.empty(B, N, 3, dtype=torch.int64, device=dev)
         dist3 = torch.empty(B, N, 3, dtype=torch.float32, device=dev)
         weight = torch.empty(B, N, 3, dtype=torch.float32, device=dev)

@@ -33,13 +33,14 @@ require grad.  There is no CPU fallback: tensors that are not on a HIP device ra
 """
 import torch
 
-from . import _lib, _ops, _pointset
+from . import _level, _lib, _ops, _pointset
+from ._level import MAX_LAYERS, FoldedLevel, fold_level
 from .group import _query_msg_launch, _sample_centres, _scales
 
 __all__ = ["FoldedLevel", "fold_level", "group_mlp_max", "supported", "rows_tile", "FusedSetAbstraction"]
 
 _WHAT = "the fused set-abstraction level"          # in the messages of _pointset.check_tensors
-MAX_LAYERS = _lib.DEFINES["SVNET_SA_MAX_LAYERS"]
+_F32 = torch.float32
 
 
 def rows_tile():
@@ -49,60 +50,7 @@ def rows_tile():
 
 def supported(N, S, K, D, widths):
     """Whether the fused kernel takes this level (module docstring, limits)."""
-    widths = [int(w) for w in widths]
-    return bool(_lib.lib().svnet_sa_fused_supported(int(N), int(S), int(K), int(D), len(widths), (_lib.c_i64 * max(len(widths), 1))(*widths)))
-
-
-class FoldedLevel:
-    """The folded layers of one level: Wf_l [C_l, C_(l-1)] and bf_l [C_l] on the layers' device, allocated once.  refresh() runs the
-    folds again - after the parameters or the running statistics changed - on the current stream, one launch per layer."""
-
-    def __init__(self, convs, bns):
-        convs, bns = list(convs), list(bns)
-        if len(convs) != len(bns) or not 1 <= len(convs) <= MAX_LAYERS:
-            raise ValueError("fold_level: %d convolutions and %d BatchNorms, needs 1 .. %d pairs" % (len(convs), len(bns), MAX_LAYERS))
-        last = None
-        for i, (conv, bn) in enumerate(zip(convs, bns)):
-            w = conv.weight
-            if w.dim() < 2 or any(int(v) != 1 for v in w.shape[2:]) or conv.bias is None:
-                raise ValueError("fold_level: layer %d must be a 1x1 convolution with a bias, got a weight of %s" % (i, tuple(w.shape)))
-            if bn.running_mean is None or bn.running_var is None or bn.weight is None or bn.bias is None:
-                raise ValueError("fold_level: BatchNorm %d must be affine and track running statistics" % i)
-            if int(bn.num_features) != int(w.shape[0]) or (last is not None and int(w.shape[1]) != last):
-                raise ValueError("fold_level: layer %d is %s, BatchNorm over %d, behind a layer of width %s"
-                                 % (i, tuple(w.shape), bn.num_features, last))
-            tensors = {"weight": w, "bias": conv.bias, "bn.weight": bn.weight, "bn.bias": bn.bias, "running_mean": bn.running_mean,
-                       "running_var": bn.running_var}
-            for k, t in tensors.items():
-                if t.dtype != torch.float32 or not t.is_contiguous() or t.device != w.device:
-                    raise ValueError("fold_level: layer %d %s must be contiguous float32 on %s" % (i, k, w.device))
-            last = int(w.shape[0])
-        self.device = _pointset.hip_device("fold_level", convs[0].weight.device)
-        self.convs, self.bns = convs, bns
-        self.c_in = int(convs[0].weight.shape[1])
-        self.widths = tuple(int(c.weight.shape[0]) for c in convs)
-        self.wf = [torch.empty(int(c.weight.shape[0]), int(c.weight.shape[1]), dtype=torch.float32, device=self.device) for c in convs]
-        self.bf = [torch.empty(w, dtype=torch.float32, device=self.device) for w in self.widths]
-        L = len(convs)
-        self._c_widths = (_lib.c_i64 * L)(*self.widths)
-        self._c_wf = (_lib.c_p * L)(*(t.data_ptr() for t in self.wf))
-        self._c_bf = (_lib.c_p * L)(*(t.data_ptr() for t in self.bf))
-        self.refresh()
-
-    def refresh(self):
-        with torch.cuda.device(self.device):
-            for conv, bn, wf, bf in zip(self.convs, self.bns, self.wf, self.bf):
-                if conv.weight.device != self.device:
-                    raise ValueError("fold_level: the layers moved from %s to %s - fold them again" % (self.device, conv.weight.device))
-                _lib.call("svnet_sa_fold_f32", _ops._p(conv.weight.detach()), _ops._p(conv.bias.detach()), _ops._p(bn.weight.detach()),
-                          _ops._p(bn.bias.detach()), _ops._p(bn.running_mean), _ops._p(bn.running_var), wf.shape[0], wf.shape[1],
-                          float(bn.eps), _ops._p(wf), _ops._p(bf), _ops._stream())
-        return self
-
-
-def fold_level(convs, bns):
-    """The 1x1 convolutions (Conv2d or Conv1d with a bias) and BatchNorms of one level, on a HIP device -> FoldedLevel."""
-    return FoldedLevel(convs, bns)
+    return bool(_lib.lib().svnet_sa_fused_supported(int(N), int(S), int(K), int(D), *_level.c_widths(widths)))
 
 
 def _launch(xyz, new_xyz, idx, idx_ld, points, level, count, count_ld, xyz_last, out, c_off, B, N, S, K, D):
@@ -128,16 +76,8 @@ def group_mlp_max(xyz, new_xyz, idx, points, level, count=None, xyz_last=False, 
     count [B,S] int32 may be slices of the last axis of a contiguous tensor - a scale's columns of query_ball_point_msg's table and
     counts.  One launch on the current stream, no host read, no workspace.  No argument may require grad."""
     name = "group_mlp_max"
-    if not isinstance(level, FoldedLevel):
-        raise TypeError("%s: level must be a FoldedLevel (fold_level), got %s" % (name, type(level).__name__))
-    tensors, dtypes = {"xyz": xyz, "new_xyz": new_xyz}, [torch.float32, torch.float32]
-    if points is not None:
-        tensors["points"] = points
-        dtypes.append(torch.float32)
-    if out is not None:
-        tensors["out"] = out
-        dtypes.append(torch.float32)
-    _pointset.check_tensors(name, tensors, dtypes, _WHAT)
+    _level.check_is_level(name, level, "fold_level")
+    _level.check_args(name, _WHAT, {"xyz": (xyz, _F32), "new_xyz": (new_xyz, _F32)}, {"points": (points, _F32), "out": (out, _F32)})
     strided = {"idx": (idx, torch.int64)}
     if count is not None:
         strided["count"] = (count, torch.int32)
@@ -161,27 +101,19 @@ def group_mlp_max(xyz, new_xyz, idx, points, level, count=None, xyz_last=False, 
         if points.dim() != 3 or points.shape[0] != B or points.shape[1] != N:
             raise ValueError("%s: points must be [B,N,D] with B = %d, N = %d, got %s" % (name, B, N, tuple(points.shape)))
         D = int(points.shape[2])
-    if level.c_in != 3 + D:
-        raise ValueError("%s: the level takes %d input columns, xyz and points give 3 + %d" % (name, level.c_in, D))
-    c_off, C = int(c_off), level.widths[-1]
-    if out is not None and (out.dim() != 3 or out.shape[0] != B or out.shape[2] != S or c_off < 0 or c_off + C > out.shape[1]):
-        raise ValueError("%s: out must be [B,C_total,S] with B = %d, S = %d and channels %d .. %d inside it, got %s"
-                         % (name, B, S, c_off, c_off + C - 1, tuple(out.shape)))
-    if out is None and c_off:
-        raise ValueError("%s: c_off = %d without out" % (name, c_off))
+    _level.check_c_in(name, level, 3 + D, "xyz and points give 3 + %d" % D)
+    c_off = _level.check_window(name, out, c_off, level, B, S, "S")
     _ops._hip(xyz, new_xyz, idx, points, count, out)
-    if level.device != xyz.device:
-        raise ValueError("%s: the level is on %s, xyz on %s" % (name, level.device, xyz.device))
+    _level.check_device(name, level, "xyz", xyz)
     if not supported(N, S, K, D, level.widths):
         raise _lib.SvnetHipError("%s: N = %d, S = %d, K = %d, D = %d, widths %s is not supported (1 <= K <= N <= %d, S >= 1, D <= 321, 1 .. %d "
                                  "layers of width 1 .. 256)" % (name, N, S, K, D, list(level.widths), _pointset.MAX_N, MAX_LAYERS))
-    if out is None:
-        out = torch.empty(B, C, S, dtype=torch.float32, device=xyz.device)
+    out = _level.result(out, level, B, S, xyz.device)
     _launch(xyz, new_xyz, idx, idx_ld, points, level, count, count_ld, xyz_last, out, c_off, B, N, S, K, D)
     return out
 
 
-class FusedSetAbstraction:
+class FusedSetAbstraction(_level.FusedWrapper):
     """The eval-mode forward of a PointNetSetAbstraction (group_all=False) or a PointNetSetAbstractionMsg on a HIP device, with the
     module's signature, default start and results:
 
@@ -209,11 +141,6 @@ class FusedSetAbstraction:
         self.module, self.npoint = module, int(module.npoint)
         self.channels = sum(level.widths[-1] for level in self.levels)
 
-    def refresh(self):
-        for level in self.levels:
-            level.refresh()
-        return self
-
     def supported(self, N, D):
         """Whether clouds of N points with D attributes take the fused path here; else __call__ runs the module."""
         R, _, c_nsample, _ = _scales("FusedSetAbstraction", self.radii, self.nsamples)
@@ -224,24 +151,8 @@ class FusedSetAbstraction:
 
     @torch.no_grad()
     def __call__(self, xyz, points, start=None):
-        name = "FusedSetAbstraction"
-        if self.module.training:
-            raise RuntimeError("%s: the module is in train mode - this is the eval-mode forward (module.eval())" % name)
-        tensors, dtypes = {"xyz": xyz}, [torch.float32]
-        if points is not None:
-            tensors["points"] = points
-            dtypes.append(torch.float32)
-        if start is not None:
-            tensors["start"] = start
-            dtypes.append(torch.int64)
-        # (the module takes views: they are made contiguous row-major below, so contiguity is not asked for here)
-        _pointset.check_tensors(name, {k: t.contiguous() if isinstance(t, torch.Tensor) else t for k, t in tensors.items()}, dtypes, _WHAT)
-        if xyz.dim() != 3 or xyz.shape[1] != 3 or xyz.shape[0] < 1:
-            raise ValueError("%s: xyz must be [B,3,N], got %s" % (name, tuple(xyz.shape)))
-        B, N = int(xyz.shape[0]), int(xyz.shape[2])
-        if points is not None and (points.dim() != 3 or points.shape[0] != B or points.shape[2] != N):
-            raise ValueError("%s: points must be [B,D,N] with B = %d, N = %d, got %s" % (name, B, N, tuple(points.shape)))
-        D = 0 if points is None else int(points.shape[1])
+        name = self._begin(_WHAT, {"xyz": (xyz, _F32)}, {"points": (points, _F32), "start": (start, torch.int64)})
+        B, N, D = _level.cloud_shapes(name, xyz, points)
         _ops._hip(xyz, points, start)
         if not self.supported(N, D):
             return self.module(xyz, points, start=start)

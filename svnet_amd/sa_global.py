@@ -34,30 +34,24 @@ require grad.  There is no CPU fallback: tensors that are not on a HIP device ra
 """
 import torch
 
-from . import _lib, _ops, _pointset
-from .sa_fused import MAX_LAYERS, FoldedLevel, fold_level
+from . import _level, _lib, _ops, _pointset
+from ._level import MAX_LAYERS, fold_level
 
 __all__ = ["global_mlp_max", "supported", "rows_tile", "FusedGlobalAbstraction"]
 
 _WHAT = "the fused global set-abstraction level"   # in the messages of _pointset.check_tensors
 MAX_D = MAX_WIDTH = 1024
-
-
-def _c_widths(widths):
-    widths = [int(w) for w in widths]
-    return len(widths), (_lib.c_i64 * max(len(widths), 1))(*widths)
+_F32 = torch.float32
 
 
 def rows_tile(D, widths):
     """Consecutive points one workgroup takes for this level: 64, 48, 32 or 16; 0 outside the limits on D and the widths."""
-    L, c = _c_widths(widths)
-    return int(_lib.lib().svnet_sa_global_rows_tile(int(D), L, c))
+    return int(_lib.lib().svnet_sa_global_rows_tile(int(D), *_level.c_widths(widths)))
 
 
 def supported(N, D, widths):
     """Whether the fused kernel takes this level (module docstring, limits)."""
-    L, c = _c_widths(widths)
-    return bool(_lib.lib().svnet_sa_global_supported(int(N), int(D), L, c))
+    return bool(_lib.lib().svnet_sa_global_supported(int(N), int(D), *_level.c_widths(widths)))
 
 
 def _launch(xyz, points, level, out, c_off, B, N, D):
@@ -66,53 +60,27 @@ def _launch(xyz, points, level, out, c_off, B, N, D):
                   level._c_bf, _ops._p(out), int(out.shape[1]), c_off, _ops._stream())
 
 
-def _cloud_shapes(name, xyz, points):
-    """xyz [B,3,N] and points [B,D,N] or None -> (B, N, D)."""
-    if xyz.dim() != 3 or xyz.shape[1] != 3 or xyz.shape[0] < 1:
-        raise ValueError("%s: xyz must be [B,3,N], got %s" % (name, tuple(xyz.shape)))
-    B, N = int(xyz.shape[0]), int(xyz.shape[2])
-    if points is not None and (points.dim() != 3 or points.shape[0] != B or points.shape[2] != N):
-        raise ValueError("%s: points must be [B,D,N] with B = %d, N = %d, got %s" % (name, B, N, tuple(points.shape)))
-    return B, N, 0 if points is None else int(points.shape[1])
-
-
 def global_mlp_max(xyz, points, level, out=None, c_off=0):
     """xyz [B,3,N], points [B,D,N] or None - channel-first, as the module receives them - and level a FoldedLevel for 3 + D input
     columns -> out [B,C_total,1] with channels c_off .. c_off + C_out - 1 written (module docstring); out=None allocates [B,C_out,1].
     Two launches on the current stream, no host read, no workspace.  No argument may require grad."""
     name = "global_mlp_max"
-    if not isinstance(level, FoldedLevel):
-        raise TypeError("%s: level must be a FoldedLevel (sa_fused.fold_level), got %s" % (name, type(level).__name__))
-    tensors, dtypes = {"xyz": xyz}, [torch.float32]
-    if points is not None:
-        tensors["points"] = points
-        dtypes.append(torch.float32)
-    if out is not None:
-        tensors["out"] = out
-        dtypes.append(torch.float32)
-    _pointset.check_tensors(name, tensors, dtypes, _WHAT)
-    B, N, D = _cloud_shapes(name, xyz, points)
-    if level.c_in != 3 + D:
-        raise ValueError("%s: the level takes %d input columns, xyz and points give 3 + %d" % (name, level.c_in, D))
-    c_off, C = int(c_off), level.widths[-1]
-    if out is not None and (out.dim() != 3 or out.shape[0] != B or out.shape[2] != 1 or c_off < 0 or c_off + C > out.shape[1]):
-        raise ValueError("%s: out must be [B,C_total,1] with B = %d and channels %d .. %d inside it, got %s"
-                         % (name, B, c_off, c_off + C - 1, tuple(out.shape)))
-    if out is None and c_off:
-        raise ValueError("%s: c_off = %d without out" % (name, c_off))
+    _level.check_is_level(name, level)
+    _level.check_args(name, _WHAT, {"xyz": (xyz, _F32)}, {"points": (points, _F32), "out": (out, _F32)})
+    B, N, D = _level.cloud_shapes(name, xyz, points)
+    _level.check_c_in(name, level, 3 + D, "xyz and points give 3 + %d" % D)
+    c_off = _level.check_window(name, out, c_off, level, B, 1)
     _ops._hip(xyz, points, out)
-    if level.device != xyz.device:
-        raise ValueError("%s: the level is on %s, xyz on %s" % (name, level.device, xyz.device))
+    _level.check_device(name, level, "xyz", xyz)
     if not supported(N, D, level.widths):
         raise _lib.SvnetHipError("%s: N = %d, D = %d, widths %s is not supported (1 <= N <= %d, D <= %d, 1 .. %d layers of width 1 .. %d)"
                                  % (name, N, D, list(level.widths), _pointset.MAX_N, MAX_D, MAX_LAYERS, MAX_WIDTH))
-    if out is None:
-        out = torch.empty(B, C, 1, dtype=torch.float32, device=xyz.device)
+    out = _level.result(out, level, B, 1, xyz.device)
     _launch(xyz, points, level, out, c_off, B, N, D)
     return out
 
 
-class FusedGlobalAbstraction:
+class FusedGlobalAbstraction(_level.FusedWrapper):
     """The eval-mode forward of a PointNetSetAbstraction with group_all=True on a HIP device, with the module's signature and results:
 
         fused(xyz [B,3,N], points [B,D,N] or None, start=None) -> (new_xyz [B,3,1] of zeros, new_points [B,C,1])
@@ -131,11 +99,7 @@ class FusedGlobalAbstraction:
             raise ValueError("FusedGlobalAbstraction: the module has group_all=False - that level is FusedSetAbstraction's")
         self.module = module
         self.level = fold_level(module.mlp_convs, module.mlp_bns)
-        self.channels = self.level.widths[-1]
-
-    def refresh(self):
-        self.level.refresh()
-        return self
+        self.levels, self.channels = [self.level], self.level.widths[-1]
 
     def supported(self, N, D):
         """Whether clouds of N points with D attributes take the fused path here; else __call__ runs the module."""
@@ -143,22 +107,13 @@ class FusedGlobalAbstraction:
 
     @torch.no_grad()
     def __call__(self, xyz, points, start=None):
-        name = "FusedGlobalAbstraction"
-        if self.module.training:
-            raise RuntimeError("%s: the module is in train mode - this is the eval-mode forward (module.eval())" % name)
-        tensors, dtypes = {"xyz": xyz}, [torch.float32]
-        if points is not None:
-            tensors["points"] = points
-            dtypes.append(torch.float32)
-        # (the module takes views: they are made contiguous below, so contiguity is not asked for here)
-        _pointset.check_tensors(name, {k: t.contiguous() if isinstance(t, torch.Tensor) else t for k, t in tensors.items()}, dtypes, _WHAT)
-        B, N, D = _cloud_shapes(name, xyz, points)
+        name = self._begin(_WHAT, {"xyz": (xyz, _F32)}, {"points": (points, _F32)})
+        B, N, D = _level.cloud_shapes(name, xyz, points)
         _ops._hip(xyz, points)
         if not self.supported(N, D):
             return self.module(xyz, points, start=start)
         dev = xyz.device
-        if self.level.device != dev:
-            raise ValueError("%s: the level is on %s, xyz on %s" % (name, self.level.device, dev))
+        _level.check_device(name, self.level, "xyz", xyz)
         out = torch.empty(B, self.channels, 1, dtype=torch.float32, device=dev)
         _launch(xyz.contiguous(), None if points is None else points.contiguous(), self.level, out, 0, B, N, D)
         return torch.zeros(B, 3, 1, dtype=torch.float32, device=dev), out

@@ -20,9 +20,9 @@ three_nn is tests/propagate_ref.three_nn; the fold tests/sa_fused_ref.fold; resu
 import numpy as np
 
 from tests import propagate_ref as P
-from tests.sa_fused_ref import EPS24, fold, fold_state, fmaf, mlp, positive_zero, single_prefixes         # noqa: F401  (the tests reach them here)
+from tests.sa_fused_ref import fold, fold_state, fmaf, mlp, mlp_f64, positive_zero, single_prefixes        # noqa: F401  (the tests reach them here)
 
-F32, F64 = np.float32, np.float64
+F32 = np.float32
 
 
 def rows(idx, w, f2, f1=None):
@@ -40,14 +40,7 @@ def level(idx, w, f2, f1, layers):
 
 
 def level_f64(idx, w, f2, f1, layers):
-    h = rows(idx, w, f2, f1).astype(F64)
-    bound = np.zeros_like(h)
-    for Wf, bf in layers:
-        W, b0, n = Wf.astype(F64), bf.astype(F64), Wf.shape[1]
-        z = h @ W.T + b0
-        mag = (np.abs(h) + bound) @ np.abs(W).T + np.abs(b0)
-        bound = bound @ np.abs(W).T + (n + 2) * EPS24 * mag
-        h = np.maximum(z, 0.0)
+    h, bound = mlp_f64(rows(idx, w, f2, f1), layers)
     return np.ascontiguousarray(h.T), np.ascontiguousarray(bound.T)
 
 

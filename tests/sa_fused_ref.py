@@ -5,7 +5,7 @@ svnet_amd/sa_fused.py's docstring and include/svnet_hip.h and independent of the
     fmaf(a, b, c)                                    fl(a b + c) with ONE rounding, on float32 arrays
     rows(x, c, idx, pts, xyz_last)                   [S,K,3+D]: the centred coordinates and the attributes, indices clamped
     level(x, c, idx, pts, layers, xyz_last)          [C_out,S] float32: the chain of the contract, then the max over a group
-    level_f64(...)                                   (value, bound) [C_out,S] float64: the same layers in float64 on the same fp32 rows
+    mlp_f64(h, layers), level_f64(...)               (value, bound) [C_out,S] float64: the same layers in float64 on the same fp32 rows
                                                      and folded weights, and a running bound on what the fp32 chain may differ by
     *_batch                                          the same over a leading batch axis
 
@@ -83,9 +83,9 @@ def level(x, c, idx, pts, layers, xyz_last=False):
     return np.ascontiguousarray(mlp(rows(x, c, idx, pts, xyz_last), layers).max(axis=1).T)
 
 
-def level_f64(x, c, idx, pts, layers, xyz_last=False):
-    """(value, bound) [C_out,S] float64 (module docstring)."""
-    h = rows(x, c, idx, pts, xyz_last).astype(F64)
+def mlp_f64(h, layers):
+    """h [..., C0] float32 -> (value, bound) [..., CL] float64: the layers in float64 and the running bound (module docstring)."""
+    h = h.astype(F64)
     bound = np.zeros_like(h)
     for Wf, bf in layers:
         W, b0, n = Wf.astype(F64), bf.astype(F64), Wf.shape[1]
@@ -93,6 +93,12 @@ def level_f64(x, c, idx, pts, layers, xyz_last=False):
         mag = (np.abs(h) + bound) @ np.abs(W).T + np.abs(b0)
         bound = bound @ np.abs(W).T + (n + 2) * EPS24 * mag
         h = np.maximum(z, 0.0)
+    return h, bound
+
+
+def level_f64(x, c, idx, pts, layers, xyz_last=False):
+    """(value, bound) [C_out,S] float64 (module docstring)."""
+    h, bound = mlp_f64(rows(x, c, idx, pts, xyz_last), layers)
     return np.ascontiguousarray(h.max(axis=1).T), np.ascontiguousarray(bound.max(axis=1).T)
 
 

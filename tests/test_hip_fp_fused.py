@@ -12,15 +12,15 @@ import torch
 
 from svnet_amd import synth
 from tests import fp_fused_ref as R
+from tests import fused_level_cases as FL
 from tests import propagate_ref as P
 from tests.common import compare_case
 
 pytestmark = pytest.mark.gpu
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-F32 = np.float32
 B = 2
-_REF = {}
+_once = FL.cache()
 
 # (N, S, D1, D2, widths): every N in {1, 3, 63, 64, 65, 131} (a lone point, tile tails on both sides of one 64-point tile, three
 # tiles; all but 64 no multiple of 4, so the last layer's scalar stores run, at 64 the 16-byte ones), every S in {1, 2, 3, 40} (empty
@@ -39,66 +39,6 @@ CASES = [(1, 1, 0, 1, (5,)),
 ROWS = {(70, 40, 132, 256, (256, 128)): 32, (70, 40, 512, 1024, (256, 256)): 16}       # points per workgroup where they are not 64
 
 
-def _bits(a):
-    return R.positive_zero(a.cpu().numpy() if isinstance(a, torch.Tensor) else a)
-
-
-def _same_bits(got, want, tag):
-    g, w = _bits(got), _bits(want)
-    assert g.shape == w.shape, (tag, g.shape, w.shape)
-    bad = np.argwhere(g != w)
-    assert bad.size == 0, "%s: %d of %d differ, first at %r: got %r, want %r" % (
-        tag, len(bad), w.size, tuple(bad[0]), g[tuple(bad[0])].view(F32), w[tuple(bad[0])].view(F32))
-
-
-def _once(key, make):
-    if key not in _REF:
-        _REF[key] = make()
-    return _REF[key]
-
-
-def _dev(dev, *arrays):
-    return tuple(None if a is None else torch.from_numpy(np.array(a, order="C")).to(dev) for a in arrays)      # a copy: the references are shared
-
-
-def _state(seed, C0, widths):
-    """Per layer the Conv1d and BatchNorm1d arrays: weights ~ N(0, 1/C), BatchNorm weights of both signs, statistics away from
-    identity; and the restatement's folded layers."""
-    def make():
-        layers, last = [], C0
-        for i, w in enumerate(widths):
-            layers.append(dict(W=(synth.normal(seed, 10 + 8 * i, (w, last)) / np.sqrt(F32(last))).astype(F32), b=synth.normal(seed, 12 + 8 * i, (w,)) * F32(0.1),
-                               gamma=(synth.normal(seed, 11 + 8 * i, (w,)) + F32(0.25)).astype(F32), beta=synth.normal(seed, 13 + 8 * i, (w,)) * F32(0.2),
-                               mean=synth.normal(seed, 14 + 8 * i, (w,)) * F32(0.1),
-                               var=(np.abs(synth.normal(seed, 15 + 8 * i, (w,))) + F32(0.5)).astype(F32)))
-            last = w
-        return layers, [R.fold(s["W"], s["b"], s["gamma"], s["beta"], s["mean"], s["var"], 1e-5) for s in layers]
-    return _once(("state", seed, C0, widths), make)
-
-
-def _level(dev, seed, C0, widths):
-    """(FoldedLevel of Conv1d + BatchNorm1d layers on the device, the restatement's folded layers), the fold checked as bit patterns."""
-    from svnet_amd import sa_fused as SF
-    state, folded = _state(seed, C0, widths)
-    convs, bns = [], []
-    for s in state:
-        conv, bn = torch.nn.Conv1d(s["W"].shape[1], s["W"].shape[0], 1), torch.nn.BatchNorm1d(s["W"].shape[0])
-        with torch.no_grad():
-            conv.weight.copy_(torch.from_numpy(s["W"])[:, :, None])
-            conv.bias.copy_(torch.from_numpy(s["b"]))
-            bn.weight.copy_(torch.from_numpy(s["gamma"]))
-            bn.bias.copy_(torch.from_numpy(s["beta"]))
-            bn.running_mean.copy_(torch.from_numpy(s["mean"]))
-            bn.running_var.copy_(torch.from_numpy(s["var"]))
-        convs.append(conv.to(dev))
-        bns.append(bn.to(dev))
-    level = SF.fold_level(convs, bns)
-    for i, (Wf, bf) in enumerate(folded):
-        assert np.array_equal(level.wf[i].cpu().numpy().view(np.uint32), Wf.view(np.uint32)), "Wf of layer %d" % i
-        assert np.array_equal(level.bf[i].cpu().numpy().view(np.uint32), bf.view(np.uint32)), "bf of layer %d" % i
-    return level, folded
-
-
 def _inputs(N, S, D1, D2):
     """(idx [B,N,3], weight [B,N,3], points2 [B,D2,S], points1 [B,D1,N] or None): the neighbours and weights of the restated three_nn
     on Gaussian clouds, then two points' indices moved outside [0, S) - the kernel clamps them, the restatement too."""
@@ -115,7 +55,7 @@ def _inputs(N, S, D1, D2):
 def _want(N, S, D1, D2, widths):
     def make():
         idx, w, f2, f1 = _inputs(N, S, D1, D2)
-        return R.level_batch(idx, w, f2, f1, _state(9100 + D1 + D2, D1 + D2, widths)[1])
+        return R.level_batch(idx, w, f2, f1, FL.state(9100 + D1 + D2, D1 + D2, widths)[1])
     return _once(("want", N, S, D1, D2, widths), make)
 
 
@@ -126,27 +66,27 @@ def test_fused_level_equals_the_restatement_bit_for_bit(N, S, D1, D2, widths, hi
     assert FP.rows_tile(D1, D2, widths) == ROWS.get((N, S, D1, D2, widths), 64)
     idx, w, f2, f1 = _inputs(N, S, D1, D2)
     want = _want(N, S, D1, D2, widths)
-    level, _ = _level(dev, 9100 + D1 + D2, D1 + D2, widths)
+    level, _ = FL.level(dev, 9100 + D1 + D2, D1 + D2, widths, conv_dim=1)
     tag = "N %d S %d D1 %d D2 %d widths %s" % (N, S, D1, D2, widths)
-    ti, tw, t2, t1 = _dev(dev, idx, w, f2, f1)
+    ti, tw, t2, t1 = FL.dev(dev, idx, w, f2, f1)
     got = FP.interp_mlp(ti, tw, t2, t1, level)
     assert got.dtype == torch.float32 and tuple(got.shape) == (B, widths[-1], N) and got.is_contiguous()
-    _same_bits(got, want, tag)
+    FL.same_bits(got, want, tag)
     assert float(want.max()) > 0
     # the clamp: the same indices clamped on the host give the same bits; a second run too
-    _same_bits(FP.interp_mlp(ti.clamp(0, S - 1), tw, t2, t1, level), want, tag + ", clamped on the host")
-    _same_bits(FP.interp_mlp(ti, tw, t2, t1, level), want, tag + ", again")
+    FL.same_bits(FP.interp_mlp(ti.clamp(0, S - 1), tw, t2, t1, level), want, tag + ", clamped on the host")
+    FL.same_bits(FP.interp_mlp(ti, tw, t2, t1, level), want, tag + ", again")
     # into channels 3 .. of a NaN-filled [B,C_total,N]: the other channels stay NaN
     C = widths[-1]
     buf = torch.full((B, C + 5, N), float("nan"), dtype=torch.float32, device=dev)
     assert FP.interp_mlp(ti, tw, t2, t1, level, out=buf, c_off=3) is buf
-    _same_bits(buf[:, 3:3 + C].contiguous(), want, tag + ", c_off 3")
+    FL.same_bits(buf[:, 3:3 + C].contiguous(), want, tag + ", c_off 3")
     assert torch.isnan(buf[:, :3]).all() and torch.isnan(buf[:, 3 + C:]).all()
     # one point on its own (B 1, N 1) has the bits it has inside a tile
     b, p = B - 1, N // 2
     alone = FP.interp_mlp(ti[b:b + 1, p:p + 1].contiguous(), tw[b:b + 1, p:p + 1].contiguous(), t2[b:b + 1],
                           None if t1 is None else t1[b:b + 1, :, p:p + 1].contiguous(), level)
-    _same_bits(alone, want[b:b + 1, :, p:p + 1], tag + ", one point alone")
+    FL.same_bits(alone, want[b:b + 1, :, p:p + 1], tag + ", one point alone")
 
 
 def test_interp_mlp_follows_three_nn_on_the_device(hip_device):
@@ -159,12 +99,12 @@ def test_interp_mlp_follows_three_nn_on_the_device(hip_device):
             q, r, f2 = P.gauss_case(7300 + S, B, N, S, D2)
             f1 = np.ascontiguousarray(synth.normal(7300 + S, 9, (B, D1, N))) if D1 else None
             idx, _, w = P.three_nn_batch(q, r)
-            return q, r, f2, f1, R.level_batch(idx, w, f2, f1, _state(7300 + S, D1 + D2, widths)[1])
+            return q, r, f2, f1, R.level_batch(idx, w, f2, f1, FL.state(7300 + S, D1 + D2, widths)[1])
         q, r, f2, f1, want = _once(("nn", N, S, D1, D2, widths), make)
-        level, _ = _level(dev, 7300 + S, D1 + D2, widths)
-        tq, tr, t2, t1 = _dev(dev, q, r, f2, f1)
+        level, _ = FL.level(dev, 7300 + S, D1 + D2, widths, conv_dim=1)
+        tq, tr, t2, t1 = FL.dev(dev, q, r, f2, f1)
         idx, _, weight = PR.three_nn(tq, tr)
-        _same_bits(FP.interp_mlp(idx, weight, t2, t1, level), want, "S %d behind three_nn" % S)
+        FL.same_bits(FP.interp_mlp(idx, weight, t2, t1, level), want, "S %d behind three_nn" % S)
 
 
 # ---- the wrapper
@@ -175,7 +115,7 @@ def _golden_module(name, dev):
     seed, Bc, N, S, D1, D2, widths = R.GOLDEN_CASES[name]
     mod = PointNetFeaturePropagation(D1 + D2, list(widths))
     mod.load_state_dict({str(k): torch.from_numpy(G["%s_sd:%s" % (name, k)]) for k in G[name + "_keys"]}, strict=True)
-    xyz1, xyz2, f1, f2 = _dev(dev, G[name + "_xyz1"].transpose(0, 2, 1), G[name + "_xyz2"].transpose(0, 2, 1), G[name + "_points1"] if D1 else None,
+    xyz1, xyz2, f1, f2 = FL.dev(dev, G[name + "_xyz1"].transpose(0, 2, 1), G[name + "_xyz2"].transpose(0, 2, 1), G[name + "_points1"] if D1 else None,
                               G[name + "_points2"])
     return mod.to(dev).eval(), xyz1, xyz2, f1, f2, G[name + "_ev_out"]
 
@@ -196,7 +136,7 @@ def test_wrapper_equals_the_module_and_the_recorded_reference(name, hip_device):
     worst_ref = compare_case({"out:new_points": got.cpu().numpy()}, {"out:new_points": ref}, 1e-3, name + " against the recorded reference")
     print("%s: worst relative error %.3e against the module, %.3e against the reference" % (name, worst_mod[0], worst_ref[0]))
     G = np.load(os.path.join(HERE, "golden", "fp_fused.npz"))
-    _same_bits(got, _once(("golden", name), lambda: R.golden_restatement(G, name)), name + " against the restatement")
+    FL.same_bits(got, _once(("golden", name), lambda: R.golden_restatement(G, name)), name + " against the restatement")
     # new running statistics: stale until refresh()
     with torch.no_grad():
         for m in mod.modules():
@@ -246,7 +186,7 @@ def test_wrapper_in_a_captured_graph(hip_device):
     sets = []
     for seed in (90, 91):
         q, r, f2 = P.gauss_case(seed, B, N, S, D2)
-        sets.append(_dev(dev, q.transpose(0, 2, 1), r.transpose(0, 2, 1), synth.normal(seed, 7, (B, D1, N)), f2))
+        sets.append(FL.dev(dev, q.transpose(0, 2, 1), r.transpose(0, 2, 1), synth.normal(seed, 7, (B, D1, N)), f2))
     xyz1, xyz2, f1, f2 = (t.clone() for t in sets[0])
 
     def run():

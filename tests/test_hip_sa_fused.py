@@ -11,6 +11,7 @@ import pytest
 import torch
 
 from svnet_amd import synth
+from tests import fused_level_cases as FL
 from tests import group_ref as G
 from tests import msg_ref as M
 from tests import sa_fused_ref as R
@@ -23,7 +24,7 @@ MSG = np.load(os.path.join(HERE, "golden", "msg.npz"))
 GOLDEN = np.load(os.path.join(HERE, "golden", "sa_fused.npz"))
 F32 = np.float32
 B = 2
-_REF = {}
+_once = FL.cache()
 
 
 def _tile():
@@ -50,69 +51,6 @@ CASES = [(1, 1, 1, 0, (5,)),
          (64, 5, 16, 3, (256,))]
 
 
-def _bits(a):
-    return R.positive_zero(a.cpu().numpy() if isinstance(a, torch.Tensor) else a)
-
-
-def _same_bits(got, want, tag):
-    g, w = _bits(got), _bits(want)
-    assert g.shape == w.shape, (tag, g.shape, w.shape)
-    bad = np.argwhere(g != w)
-    assert bad.size == 0, "%s: %d of %d differ, first at %r: got %r, want %r" % (
-        tag, len(bad), w.size, tuple(bad[0]), g[tuple(bad[0])].view(F32), w[tuple(bad[0])].view(F32))
-
-
-def _once(key, make):
-    if key not in _REF:
-        _REF[key] = make()
-    return _REF[key]
-
-
-def _dev(dev, *arrays):
-    return tuple(None if a is None else torch.from_numpy(np.array(a, order="C")).to(dev) for a in arrays)      # a copy: the references are shared
-
-
-def _state(seed, C0, widths, negative_last=False):
-    """Per layer the convolution and BatchNorm arrays: weights ~ N(0, 1/C), BatchNorm weights of both signs, statistics away from
-    identity.  negative_last: the last BatchNorm has weight 0 and a negative bias - every output of the level is then exactly 0."""
-    def make():
-        layers, last = [], C0
-        for i, w in enumerate(widths):
-            s = dict(W=(synth.normal(seed, 10 + 8 * i, (w, last)) / np.sqrt(F32(last))).astype(F32), b=synth.normal(seed, 12 + 8 * i, (w,)) * F32(0.1),
-                     gamma=(synth.normal(seed, 11 + 8 * i, (w,)) + F32(0.25)).astype(F32), beta=synth.normal(seed, 13 + 8 * i, (w,)) * F32(0.2),
-                     mean=synth.normal(seed, 14 + 8 * i, (w,)) * F32(0.1), var=(np.abs(synth.normal(seed, 15 + 8 * i, (w,))) + F32(0.5)).astype(F32))
-            if negative_last and i == len(widths) - 1:
-                s["gamma"] = np.zeros_like(s["gamma"])
-                s["beta"] = (-np.abs(s["beta"]) - F32(0.125)).astype(F32)
-            layers.append(s)
-            last = w
-        return layers, [R.fold(s["W"], s["b"], s["gamma"], s["beta"], s["mean"], s["var"], 1e-5) for s in layers]
-    return _once(("state", seed, C0, widths, negative_last), make)
-
-
-def _level(dev, seed, C0, widths, negative_last=False):
-    """(FoldedLevel on the device, the restatement's folded layers); the fold's results are checked as bit patterns on the way."""
-    from svnet_amd import sa_fused as SF
-    state, folded = _state(seed, C0, widths, negative_last)
-    convs, bns = [], []
-    for s in state:
-        conv, bn = torch.nn.Conv2d(s["W"].shape[1], s["W"].shape[0], 1), torch.nn.BatchNorm2d(s["W"].shape[0])
-        with torch.no_grad():
-            conv.weight.copy_(torch.from_numpy(s["W"])[:, :, None, None])
-            conv.bias.copy_(torch.from_numpy(s["b"]))
-            bn.weight.copy_(torch.from_numpy(s["gamma"]))
-            bn.bias.copy_(torch.from_numpy(s["beta"]))
-            bn.running_mean.copy_(torch.from_numpy(s["mean"]))
-            bn.running_var.copy_(torch.from_numpy(s["var"]))
-        convs.append(conv.to(dev))
-        bns.append(bn.to(dev))
-    level = SF.fold_level(convs, bns)
-    for i, (Wf, bf) in enumerate(folded):
-        assert np.array_equal(level.wf[i].cpu().numpy().view(np.uint32), Wf.view(np.uint32)), "Wf of layer %d" % i
-        assert np.array_equal(level.bf[i].cpu().numpy().view(np.uint32), bf.view(np.uint32)), "bf of layer %d" % i
-    return level, folded
-
-
 def _inputs(N, S, K, D):
     def make():
         x, c, pts = G.gauss_case(8000 + N + S, B, N, S, D)
@@ -125,17 +63,17 @@ def _inputs(N, S, K, D):
 def _want(N, S, K, D, widths, xyz_last):
     def make():
         x, c, pts, idx = _inputs(N, S, K, D)
-        return R.level_batch(x, c, idx, pts, _state(9000 + 3 + D, 3 + D, widths)[1], xyz_last)
+        return R.level_batch(x, c, idx, pts, FL.state(9000 + 3 + D, 3 + D, widths)[1], xyz_last)
     return _once(("want", N, S, K, D, widths, xyz_last), make)
 
 
 def test_fold_equals_the_restatement_bit_for_bit(hip_device):
-    """Wf and bf of every layer (the comparison is in _level), widths 1 .. 256 and inputs 1 .. 324 that are multiples of nothing;
+    """Wf and bf of every layer (the comparison is in fused_level_cases.level), widths 1 .. 256 and inputs 1 .. 324 that are multiples of nothing;
     refresh() after the statistics changed folds the new ones."""
     for seed, C0, widths in [(1, 3, (5,)), (2, 324, (256, 1, 196)), (3, 131, (16, 16, 16, 7)), (4, 1, (3,))]:
-        _level(hip_device, seed, C0, widths)
-    level, folded = _level(hip_device, 5, 7, (12, 20))
-    state = _state(5, 7, (12, 20))[0]
+        FL.level(hip_device, seed, C0, widths)
+    level, folded = FL.level(hip_device, 5, 7, (12, 20))
+    state = FL.state(5, 7, (12, 20))[0]
     with torch.no_grad():
         level.bns[1].running_var.mul_(3.0)
     level.refresh()
@@ -152,34 +90,34 @@ def test_fused_level_equals_the_restatement_bit_for_bit(N, S, K, D, widths, xyz_
     dev = hip_device
     x, c, pts, idx = _inputs(N, S, K, D)
     want = _want(N, S, K, D, widths, xyz_last)
-    level, _ = _level(dev, 9000 + 3 + D, 3 + D, widths)
+    level, _ = FL.level(dev, 9000 + 3 + D, 3 + D, widths)
     tag = "N %d S %d K %d D %d widths %s xyz_last %s" % (N, S, K, D, widths, xyz_last)
-    tx, tc, tp, ti = _dev(dev, x, c, pts, idx)
+    tx, tc, tp, ti = FL.dev(dev, x, c, pts, idx)
     got = SF.group_mlp_max(tx, tc, ti, tp, level, xyz_last=xyz_last)
     assert got.dtype == torch.float32 and tuple(got.shape) == (B, widths[-1], S) and got.is_contiguous()
-    _same_bits(got, want, tag)
+    FL.same_bits(got, want, tag)
     assert float(want.max()) > 0
     # a second run; the indices as columns 3 .. 3 + K - 1 of a wider table (idx_ld = K + 5)
-    _same_bits(SF.group_mlp_max(tx, tc, ti, tp, level, xyz_last=xyz_last), want, tag + ", again")
+    FL.same_bits(SF.group_mlp_max(tx, tc, ti, tp, level, xyz_last=xyz_last), want, tag + ", again")
     wide = torch.full((B, S, K + 5), N + 11, dtype=torch.int64, device=dev)
     wide[:, :, 3:3 + K] = ti
     view = wide[:, :, 3:3 + K]
     assert not view.is_contiguous() or S == 1
-    _same_bits(SF.group_mlp_max(tx, tc, view, tp, level, xyz_last=xyz_last), want, tag + ", idx_ld > K")
+    FL.same_bits(SF.group_mlp_max(tx, tc, view, tp, level, xyz_last=xyz_last), want, tag + ", idx_ld > K")
     # into channels 3 .. of a NaN-filled [B,C_total,S]: the other channels stay NaN
     C = widths[-1]
     buf = torch.full((B, C + 5, S), float("nan"), dtype=torch.float32, device=dev)
     assert SF.group_mlp_max(tx, tc, ti, tp, level, xyz_last=xyz_last, out=buf, c_off=3) is buf
-    _same_bits(buf[:, 3:3 + C].contiguous(), want, tag + ", c_off 3")
+    FL.same_bits(buf[:, 3:3 + C].contiguous(), want, tag + ", c_off 3")
     assert torch.isnan(buf[:, :3]).all() and torch.isnan(buf[:, 3 + C:]).all()
     # permuting the slots of every group changes nothing: a maximum has no order
     perm = torch.from_numpy(np.argsort(synth.integers(77, K, (K,), 1 << 30), kind="stable")).to(dev)
-    _same_bits(SF.group_mlp_max(tx, tc, ti[:, :, perm].contiguous(), tp, level, xyz_last=xyz_last), want, tag + ", slots permuted")
+    FL.same_bits(SF.group_mlp_max(tx, tc, ti[:, :, perm].contiguous(), tp, level, xyz_last=xyz_last), want, tag + ", slots permuted")
     # one centre on its own (B 1, S 1) has the bits it has inside the batch
     b, s = B - 1, S // 2
     alone = SF.group_mlp_max(tx[b:b + 1], tc[b:b + 1, s:s + 1].contiguous(), ti[b:b + 1, s:s + 1].contiguous(), None if tp is None else tp[b:b + 1],
                              level, xyz_last=xyz_last)
-    _same_bits(alone, want[b:b + 1, :, s:s + 1], tag + ", one centre alone")
+    FL.same_bits(alone, want[b:b + 1, :, s:s + 1], tag + ", one centre alone")
 
 
 # (N, S, radius, K, D, widths): groups from the query's restatement - full, padded and (centre 1, planted far away) empty ones - below,
@@ -197,21 +135,21 @@ def test_padded_and_empty_groups_with_and_without_count(N, S, radius, K, D, widt
         c = np.ascontiguousarray(c)
         c[:, 1] = 9.0                                                        # no point within the radius: the empty group
         idx, count = G.query_ball_batch(x, c, G.r2_of(radius), K)
-        return x, c, pts, idx, count, R.level_batch(x, c, idx, pts, _state(8300 + K, 3 + D, widths)[1])
+        return x, c, pts, idx, count, R.level_batch(x, c, idx, pts, FL.state(8300 + K, 3 + D, widths)[1])
     x, c, pts, idx, count, want = _once(("count", N, S, radius, K, D, widths), make)
     assert (count[:, 1] == 0).all() and (idx[:, 1] == 0).all() and (count < K).any() and (count[:, 0] >= 1).all()
-    level, _ = _level(dev, 8300 + K, 3 + D, widths)
-    tx, tc, tp, ti, tn = _dev(dev, x, c, pts, idx, count)
+    level, _ = FL.level(dev, 8300 + K, 3 + D, widths)
+    tx, tc, tp, ti, tn = FL.dev(dev, x, c, pts, idx, count)
     tag = "N %d S %d K %d D %d" % (N, S, K, D)
-    _same_bits(SF.group_mlp_max(tx, tc, ti, tp, level), want, tag + ", all slots")
-    _same_bits(SF.group_mlp_max(tx, tc, ti, tp, level, count=tn), want, tag + ", with count")
+    FL.same_bits(SF.group_mlp_max(tx, tc, ti, tp, level), want, tag + ", all slots")
+    FL.same_bits(SF.group_mlp_max(tx, tc, ti, tp, level, count=tn), want, tag + ", with count")
     # count as a column of a [B,S,3] table (count_ld = 3), and the slots past count overwritten: with count they are never read
     table = torch.full((B, S, 3), K, dtype=torch.int32, device=dev)
     table[:, :, 1] = tn
     junk = ti.clone()
     slot = torch.arange(K, device=dev).view(1, 1, K)
     junk[slot.expand(B, S, K) >= tn.clamp(min=1).unsqueeze(2)] = N // 2
-    _same_bits(SF.group_mlp_max(tx, tc, junk, tp, level, count=table[:, :, 1]), want, tag + ", count_ld 3, junk past count")
+    FL.same_bits(SF.group_mlp_max(tx, tc, junk, tp, level, count=table[:, :, 1]), want, tag + ", count_ld 3, junk past count")
 
 
 def test_a_level_whose_last_layer_is_negative_everywhere_gives_exact_zeros(hip_device):
@@ -219,11 +157,11 @@ def test_a_level_whose_last_layer_is_negative_everywhere_gives_exact_zeros(hip_d
     dev = hip_device
     N, S, K, D, widths = 128, 33, 32, 0, (64, 64, 128)
     x, c, pts, idx = _inputs(N, S, K, D)
-    level, folded = _level(dev, 31, 3, widths, negative_last=True)
+    level, folded = FL.level(dev, 31, 3, widths, kind="negative_last")
     assert (folded[-1][1] < 0).all() and not folded[-1][0].any()
-    tx, tc, ti = _dev(dev, x, c, idx)
+    tx, tc, ti = FL.dev(dev, x, c, idx)
     got = SF.group_mlp_max(tx, tc, ti, None, level, out=torch.full((B, widths[-1], S), float("nan"), dtype=torch.float32, device=dev))
-    assert not _bits(got).any()
+    assert not FL.bits(got).any()
 
 
 # ---- the wrapper
@@ -243,7 +181,7 @@ def _golden_module(name, dev):
         mod.load_state_dict({str(k): torch.from_numpy(MSG["%s_sd:%s" % (name, k)]) for k in MSG[name + "_keys"]}, strict=True)
         x, pts, start = MSG[name + "_xyz"], MSG[name + "_points"] if D else None, MSG[name + "_start"]
         ref = {"out:new_xyz": MSG[name + "_ev_out:new_xyz"], "out:new_points": MSG[name + "_ev_out:new_points"]}
-    xyz, points, start = _dev(dev, x.transpose(0, 2, 1), None if pts is None else pts.transpose(0, 2, 1), start)
+    xyz, points, start = FL.dev(dev, x.transpose(0, 2, 1), None if pts is None else pts.transpose(0, 2, 1), start)
     return mod.to(dev).eval(), xyz, points, start, ref
 
 
@@ -297,7 +235,7 @@ def test_wrapper_refuses_train_mode_and_falls_back_outside_the_envelope(hip_devi
     torch.manual_seed(5)
     wide = PointNetSetAbstraction(8, 0.4, 8, 3, [16, 300], False).to(dev).eval()
     fused = SF.FusedSetAbstraction(wide)
-    x = _dev(dev, G.gauss_case(12, B, 64, 4, 0)[0].transpose(0, 2, 1))[0]
+    x = FL.dev(dev, G.gauss_case(12, B, 64, 4, 0)[0].transpose(0, 2, 1))[0]
     assert not fused.supported(64, 0) and SF.FusedSetAbstraction(mod).supported(256, 4)
     got, want = fused(x, None), wide(x, None)
     assert tuple(got[1].shape) == (B, 300, 8) and not got[1].requires_grad
@@ -317,7 +255,7 @@ def test_wrapper_in_a_captured_graph(hip_device):
     sets = []
     for seed in (90, 91):
         x, _, pts = G.gauss_case(seed, B, N, 4, D)
-        sets.append(_dev(dev, x.transpose(0, 2, 1), pts.transpose(0, 2, 1), np.array([seed % 7, 200 + seed % 5], dtype=np.int64)))
+        sets.append(FL.dev(dev, x.transpose(0, 2, 1), pts.transpose(0, 2, 1), np.array([seed % 7, 200 + seed % 5], dtype=np.int64)))
     x, pts, start = (t.clone() for t in sets[0])
 
     def run():

@@ -11,6 +11,7 @@ import pytest
 import torch
 
 from svnet_amd import synth
+from tests import fused_level_cases as FL
 from tests import sa_fused_ref as R
 from tests import sa_global_ref as SG
 from tests.common import compare_case
@@ -21,7 +22,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 GOLDEN = np.load(os.path.join(HERE, "golden", "sa_global.npz"))
 F32 = np.float32
 B = 2
-_REF = {}
+_once = FL.cache()
 
 # (N, D, widths): every N in {1, 15, 16, 17, 47, 49, 64, 65, 131} (below, at and past one 16-row MFMA tile, three tiles less and more
 # than a point, one workgroup's 64 rows and one more, three workgroups), every C0 = 3 + D in {3, 4, 7, 67, 134} (K of the first product
@@ -44,78 +45,6 @@ CASES = [(1, 0, (5,)),
 CROSSING = [(64, 65, 0, (5,)), (48, 49, 700, (8,)), (32, 33, 1000, (8,)), (16, 17, 1000, (600, 8))]
 
 
-def _bits(a):
-    return R.positive_zero(a.cpu().numpy() if isinstance(a, torch.Tensor) else a)
-
-
-def _same_bits(got, want, tag):
-    g, w = _bits(got), _bits(want)
-    assert g.shape == w.shape, (tag, g.shape, w.shape)
-    bad = np.argwhere(g != w)
-    assert bad.size == 0, "%s: %d of %d differ, first at %r: got %r, want %r" % (
-        tag, len(bad), w.size, tuple(bad[0]), g[tuple(bad[0])].view(F32), w[tuple(bad[0])].view(F32))
-
-
-def _once(key, make):
-    if key not in _REF:
-        _REF[key] = make()
-    return _REF[key]
-
-
-def _dev(dev, *arrays):
-    return tuple(None if a is None else torch.from_numpy(np.array(a, order="C")).to(dev) for a in arrays)      # a copy: the references are shared
-
-
-def _state(seed, C0, widths, kind="random"):
-    """Per layer the convolution and BatchNorm arrays: weights ~ N(0, 1/C), BatchNorm weights of both signs, statistics away from
-    identity.  kind "negative_last": the last BatchNorm has weight 0 and a negative bias - every output of the level is exactly 0.
-    "padding": the last layer has negative weights, a positive BatchNorm weight and the folded bias 8: on positive inputs every real
-    row lies below 8, the value of a zero row.  "positive": positive weights and BatchNorm weights - the outputs grow with the inputs."""
-    def make():
-        layers, last = [], C0
-        for i, w in enumerate(widths):
-            s = dict(W=(synth.normal(seed, 10 + 8 * i, (w, last)) / np.sqrt(F32(last))).astype(F32), b=synth.normal(seed, 12 + 8 * i, (w,)) * F32(0.1),
-                     gamma=(synth.normal(seed, 11 + 8 * i, (w,)) + F32(0.25)).astype(F32), beta=synth.normal(seed, 13 + 8 * i, (w,)) * F32(0.2),
-                     mean=synth.normal(seed, 14 + 8 * i, (w,)) * F32(0.1), var=(np.abs(synth.normal(seed, 15 + 8 * i, (w,))) + F32(0.5)).astype(F32))
-            if i == len(widths) - 1:
-                if kind == "negative_last":
-                    s["gamma"] = np.zeros_like(s["gamma"])
-                    s["beta"] = (-np.abs(s["beta"]) - F32(0.125)).astype(F32)
-                elif kind == "padding":
-                    s["W"] = (-np.abs(s["W"]) * F32(0.5)).astype(F32)
-                    s["gamma"] = (np.abs(s["gamma"]) + F32(0.5)).astype(F32)
-                    s["b"], s["mean"], s["beta"] = np.zeros_like(s["b"]), np.zeros_like(s["mean"]), np.full_like(s["beta"], 8.0)
-            if kind == "positive":
-                s["W"], s["gamma"] = np.abs(s["W"]), (np.abs(s["gamma"]) + F32(0.5)).astype(F32)
-            layers.append(s)
-            last = w
-        return layers, [R.fold(s["W"], s["b"], s["gamma"], s["beta"], s["mean"], s["var"], 1e-5) for s in layers]
-    return _once(("state", seed, C0, widths, kind), make)
-
-
-def _level(dev, seed, C0, widths, kind="random"):
-    """(FoldedLevel on the device, the restatement's folded layers); the fold's results are checked as bit patterns on the way."""
-    from svnet_amd import sa_fused as SF
-    state, folded = _state(seed, C0, widths, kind)
-    convs, bns = [], []
-    for s in state:
-        conv, bn = torch.nn.Conv2d(s["W"].shape[1], s["W"].shape[0], 1), torch.nn.BatchNorm2d(s["W"].shape[0])
-        with torch.no_grad():
-            conv.weight.copy_(torch.from_numpy(s["W"])[:, :, None, None])
-            conv.bias.copy_(torch.from_numpy(s["b"]))
-            bn.weight.copy_(torch.from_numpy(s["gamma"]))
-            bn.bias.copy_(torch.from_numpy(s["beta"]))
-            bn.running_mean.copy_(torch.from_numpy(s["mean"]))
-            bn.running_var.copy_(torch.from_numpy(s["var"]))
-        convs.append(conv.to(dev))
-        bns.append(bn.to(dev))
-    level = SF.fold_level(convs, bns)
-    for i, (Wf, bf) in enumerate(folded):
-        assert np.array_equal(level.wf[i].cpu().numpy().view(np.uint32), Wf.view(np.uint32)), "Wf of layer %d" % i
-        assert np.array_equal(level.bf[i].cpu().numpy().view(np.uint32), bf.view(np.uint32)), "bf of layer %d" % i
-    return level, folded
-
-
 def _inputs(N, D, positive=False):
     """(xyz [B,3,N], points [B,D,N] or None), channel-first."""
     def make():
@@ -130,7 +59,7 @@ def _inputs(N, D, positive=False):
 def _want(N, D, widths):
     def make():
         x, pts = _inputs(N, D)
-        return SG.level_batch(x, pts, _state(9100 + D, 3 + D, widths)[1])
+        return SG.level_batch(x, pts, FL.state(9100 + D, 3 + D, widths)[1])
     return _once(("want", N, D, widths), make)
 
 
@@ -141,26 +70,26 @@ def test_global_level_equals_the_restatement_bit_for_bit(N, D, widths, hip_devic
     dev = hip_device
     x, pts = _inputs(N, D)
     want = _want(N, D, widths)
-    level, _ = _level(dev, 9100 + D, 3 + D, widths)
+    level, _ = FL.level(dev, 9100 + D, 3 + D, widths)
     tag = "N %d D %d widths %s" % (N, D, widths)
-    tx, tp = _dev(dev, x, pts)
+    tx, tp = FL.dev(dev, x, pts)
     got = SGL.global_mlp_max(tx, tp, level)
     C = widths[-1]
     assert got.dtype == torch.float32 and tuple(got.shape) == (B, C, 1) and got.is_contiguous()
-    _same_bits(got, want, tag)
+    FL.same_bits(got, want, tag)
     assert float(want.max()) > 0
-    _same_bits(SGL.global_mlp_max(tx, tp, level), want, tag + ", again")
+    FL.same_bits(SGL.global_mlp_max(tx, tp, level), want, tag + ", again")
     # into channels 3 .. of a NaN-filled [B,C_total,1]: the other channels stay NaN
     buf = torch.full((B, C + 5, 1), float("nan"), dtype=torch.float32, device=dev)
     assert SGL.global_mlp_max(tx, tp, level, out=buf, c_off=3) is buf
-    _same_bits(buf[:, 3:3 + C].contiguous(), want, tag + ", c_off 3")
+    FL.same_bits(buf[:, 3:3 + C].contiguous(), want, tag + ", c_off 3")
     assert torch.isnan(buf[:, :3]).all() and torch.isnan(buf[:, 3 + C:]).all()
     # one cloud on its own (B 1) has the bits it has inside the batch
     alone = SGL.global_mlp_max(tx[B - 1:], None if tp is None else tp[B - 1:], level)
-    _same_bits(alone, want[B - 1:], tag + ", one cloud alone")
+    FL.same_bits(alone, want[B - 1:], tag + ", one cloud alone")
     # a maximum has no order: the points of a cloud permuted
     perm = torch.from_numpy(np.argsort(synth.integers(78, N, (N,), 1 << 30), kind="stable")).to(dev)
-    _same_bits(SGL.global_mlp_max(tx[:, :, perm].contiguous(), None if tp is None else tp[:, :, perm].contiguous(), level), want, tag + ", points permuted")
+    FL.same_bits(SGL.global_mlp_max(tx[:, :, perm].contiguous(), None if tp is None else tp[:, :, perm].contiguous(), level), want, tag + ", points permuted")
     # where the existing fused kernel admits the level too: one centre at 0 whose group is all points in order
     assert SF.supported(N, 1, N, D, widths) == (max(widths) <= 256)
     if max(widths) <= 256:
@@ -178,15 +107,15 @@ def test_two_workgroups_share_a_cloud_at_every_row_plan(rows, N, D, widths, hip_
     assert SGL.rows_tile(D, widths) == rows and N == rows + 1
     x, pts = _inputs(N, D)
     want = _want(N, D, widths)
-    level, _ = _level(dev, 9100 + D, 3 + D, widths)
-    tx, tp = _dev(dev, x, pts)
+    level, _ = FL.level(dev, 9100 + D, 3 + D, widths)
+    tx, tp = FL.dev(dev, x, pts)
     tag = "rows %d N %d D %d widths %s" % (rows, N, D, widths)
-    _same_bits(SGL.global_mlp_max(tx, tp, level), want, tag)
+    FL.same_bits(SGL.global_mlp_max(tx, tp, level), want, tag)
     assert float(want.max()) > 0
     # the first tile on its own: one workgroup per cloud
-    head = SG.level_batch(x[:, :, :rows], None if pts is None else pts[:, :, :rows], _state(9100 + D, 3 + D, widths)[1])
+    head = SG.level_batch(x[:, :, :rows], None if pts is None else pts[:, :, :rows], FL.state(9100 + D, 3 + D, widths)[1])
     assert (head <= want).all()
-    _same_bits(SGL.global_mlp_max(tx[:, :, :rows].contiguous(), None if tp is None else tp[:, :, :rows].contiguous(), level), head, tag + ", one tile")
+    FL.same_bits(SGL.global_mlp_max(tx[:, :, :rows].contiguous(), None if tp is None else tp[:, :, :rows].contiguous(), level), head, tag + ", one tile")
 
 
 @pytest.mark.parametrize("where", ["first_tile", "last_partial_tile"])
@@ -203,15 +132,15 @@ def test_the_maximum_is_found_wherever_it_lies(where, hip_device):
         x, pts = (a.copy() for a in _inputs(N, D))
         x, pts = (x * F32(2.0 ** -6)).astype(F32), (pts * F32(2.0 ** -6)).astype(F32)
         x[:, :, p], pts[:, :, p] = _inputs(N, D)[0][:, :, p] * F32(8), _inputs(N, D)[1][:, :, p] * F32(8)
-        layers = _state(9100 + D, 3 + D, widths)[1]
+        layers = FL.state(9100 + D, 3 + D, widths)[1]
         h = R.mlp(np.concatenate([x, pts], axis=1).transpose(0, 2, 1), layers)                  # [B,N,C]
         rest = np.delete(h, p, axis=1).max(axis=1)
         return x, pts, SG.level_batch(x, pts, layers), (h[:, p] > rest).mean()
     x, pts, want, share = _once(("planted", where), make)
     assert share > 0.25, share
-    level, _ = _level(dev, 9100 + D, 3 + D, widths)
-    tx, tp = _dev(dev, x, pts)
-    _same_bits(SGL.global_mlp_max(tx, tp, level), want, where)
+    level, _ = FL.level(dev, 9100 + D, 3 + D, widths)
+    tx, tp = FL.dev(dev, x, pts)
+    FL.same_bits(SGL.global_mlp_max(tx, tp, level), want, where)
 
 
 def test_rows_past_the_cloud_never_enter_the_maximum(hip_device):
@@ -221,12 +150,12 @@ def test_rows_past_the_cloud_never_enter_the_maximum(hip_device):
     dev = hip_device
     N, D, widths = 17, 4, (8,)
     x, pts = _inputs(N, D, positive=True)
-    level, folded = _level(dev, 41, 3 + D, widths, kind="padding")
+    level, folded = FL.level(dev, 41, 3 + D, widths, kind="padding")
     assert (folded[-1][0] < 0).all() and (folded[-1][1] == F32(8)).all() and x.min() > 0 and pts.min() > 0
     want = _once(("padding",), lambda: SG.level_batch(x, pts, folded))
     assert (want < 8).all() and (want > 0).all()
-    tx, tp = _dev(dev, x, pts)
-    _same_bits(SGL.global_mlp_max(tx, tp, level), want, "padding rows")
+    tx, tp = FL.dev(dev, x, pts)
+    FL.same_bits(SGL.global_mlp_max(tx, tp, level), want, "padding rows")
 
 
 def test_a_level_whose_last_layer_is_negative_everywhere_gives_exact_zeros(hip_device):
@@ -234,11 +163,11 @@ def test_a_level_whose_last_layer_is_negative_everywhere_gives_exact_zeros(hip_d
     dev = hip_device
     N, D, widths = 65, 1, (12, 20)
     x, pts = _inputs(N, D)
-    level, folded = _level(dev, 31, 3 + D, widths, kind="negative_last")
+    level, folded = FL.level(dev, 31, 3 + D, widths, kind="negative_last")
     assert (folded[-1][1] < 0).all() and not folded[-1][0].any()
-    tx, tp = _dev(dev, x, pts)
+    tx, tp = FL.dev(dev, x, pts)
     got = SGL.global_mlp_max(tx, tp, level, out=torch.full((B, widths[-1], 1), float("nan"), dtype=torch.float32, device=dev))
-    assert not _bits(got).any()
+    assert not FL.bits(got).any()
 
 
 def test_a_second_call_into_the_same_buffer_leaves_no_stale_maxima(hip_device):
@@ -248,13 +177,13 @@ def test_a_second_call_into_the_same_buffer_leaves_no_stale_maxima(hip_device):
     dev = hip_device
     N, D, widths = 65, 4, (20,)
     x, pts = _inputs(N, D, positive=True)
-    level, folded = _level(dev, 43, 3 + D, widths, kind="positive")
+    level, folded = FL.level(dev, 43, 3 + D, widths, kind="positive")
     x2, pts2 = (x * F32(0.5)).astype(F32), (pts * F32(0.5)).astype(F32)
     want1, want2 = _once(("stale",), lambda: (SG.level_batch(x, pts, folded), SG.level_batch(x2, pts2, folded)))
     assert (want2 < want1).all() and (want2 > 0).all()
     buf = torch.empty(B, widths[-1], 1, dtype=torch.float32, device=dev)
-    _same_bits(SGL.global_mlp_max(*_dev(dev, x, pts), level, out=buf), want1, "first call")
-    _same_bits(SGL.global_mlp_max(*_dev(dev, x2, pts2), level, out=buf), want2, "second call")
+    FL.same_bits(SGL.global_mlp_max(*FL.dev(dev, x, pts), level, out=buf), want1, "first call")
+    FL.same_bits(SGL.global_mlp_max(*FL.dev(dev, x2, pts2), level, out=buf), want2, "second call")
 
 
 # ---- the wrapper
@@ -264,7 +193,7 @@ def _golden_module(dev):
     seed, Bc, N, D, mlp = SG.GOLDEN_CASE
     mod = PointNetSetAbstraction(None, None, None, D + 3, list(mlp), True)
     mod.load_state_dict({str(k): torch.from_numpy(GOLDEN["sd:" + str(k)]) for k in GOLDEN["keys"]}, strict=True)
-    xyz, points = _dev(dev, GOLDEN["xyz"], GOLDEN["points"])
+    xyz, points = FL.dev(dev, GOLDEN["xyz"], GOLDEN["points"])
     return mod.to(dev).eval(), xyz, points, {"out:new_xyz": GOLDEN["ev_out:new_xyz"], "out:new_points": GOLDEN["ev_out:new_points"]}
 
 
@@ -286,7 +215,7 @@ def test_wrapper_equals_the_module_and_the_recorded_reference(hip_device):
     worst_ref = compare_case(got, ref, 1e-3, "against the recorded reference")
     print("worst relative error %.3e against the module, %.3e against the reference" % (worst_mod[0], worst_ref[0]))
     state = {str(k): GOLDEN["sd:" + str(k)] for k in GOLDEN["keys"]}
-    _same_bits(new_points, SG.level_batch(GOLDEN["xyz"], GOLDEN["points"], R.fold_state(state, R.single_prefixes(len(mlp)))), "the wrapper")
+    FL.same_bits(new_points, SG.level_batch(GOLDEN["xyz"], GOLDEN["points"], R.fold_state(state, R.single_prefixes(len(mlp)))), "the wrapper")
     # views, as a model hands them over, are taken
     wide = torch.cat([xyz, points], dim=1)
     again = fused(wide[:, :3], wide[:, 3:])[1]
@@ -319,7 +248,7 @@ def test_wrapper_refuses_train_mode_and_falls_back_outside_the_envelope(hip_devi
     torch.manual_seed(5)
     wide = PointNetSetAbstraction(None, None, None, 3, [16, 1100], True).to(dev).eval()
     fused = SGL.FusedGlobalAbstraction(wide)
-    x = _dev(dev, _inputs(49, 0)[0])[0]
+    x = FL.dev(dev, _inputs(49, 0)[0])[0]
     assert not fused.supported(49, 0)
     got, want = fused(x, None), wide(x, None)
     assert tuple(got[1].shape) == (B, 1100, 1) and not got[1].requires_grad
@@ -341,7 +270,7 @@ def test_wrapper_in_a_captured_graph(hip_device):
     fused = SGL.FusedGlobalAbstraction(mod)
     sets = []
     for seed in (90, 91):
-        sets.append(_dev(dev, synth.normal(seed, 1, (B, 3, N)) * F32(0.5), synth.normal(seed, 2, (B, D, N))))
+        sets.append(FL.dev(dev, synth.normal(seed, 1, (B, 3, N)) * F32(0.5), synth.normal(seed, 2, (B, D, N))))
     x, pts = (t.clone() for t in sets[0])
 
     def run():

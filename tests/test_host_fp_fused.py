@@ -11,6 +11,7 @@ import torch
 
 from svnet_amd import _lib, synth
 from tests import fp_fused_ref as R
+from tests import fused_level_cases as FL
 from tests import propagate_ref as P
 from tests.common import compare_case
 
@@ -34,23 +35,13 @@ def test_restatement_equals_the_recorded_eval_output(name):
     print("%s: worst relative error %.3e" % (name, worst[0]))
 
 
-def _random_level(seed, C0, widths):
-    layers, last = [], C0
-    for i, w in enumerate(widths):
-        layers.append(R.fold((synth.normal(seed, 10 + 8 * i, (w, last, 1)) / np.sqrt(F32(last))).astype(F32), synth.normal(seed, 12 + 8 * i, (w,)) * F32(0.1),
-                             (synth.normal(seed, 11 + 8 * i, (w,)) + F32(0.25)).astype(F32), synth.normal(seed, 13 + 8 * i, (w,)) * F32(0.2),
-                             synth.normal(seed, 14 + 8 * i, (w,)) * F32(0.1), (np.abs(synth.normal(seed, 15 + 8 * i, (w,))) + F32(0.5)).astype(F32), 1e-5))
-        last = w
-    return layers
-
-
 @pytest.mark.parametrize("S,D1,D2,widths", [(1, 0, 1, (5,)), (2, 3, 5, (12, 20)), (3, 6, 64, (33, 8, 196)), (40, 131, 1, (16, 16, 16, 7))])
 def test_fp32_chain_lies_within_the_running_bound_of_the_float64_chain(S, D1, D2, widths):
     N = 21
     q, r, f2 = (a[0] for a in P.gauss_case(70 + S, 1, N, S, D2))
     f1 = synth.normal(70 + S, 6, (D1, N)) if D1 else None
     idx, _, w = P.three_nn(q, r)
-    layers = _random_level(70 + D1, D1 + D2, widths)
+    layers = FL.random_level(70 + D1, D1 + D2, widths)
     h0 = R.rows(idx, w, f2, f1)
     assert h0.dtype == F32 and h0.shape == (N, D1 + D2)
     if D1:
@@ -115,18 +106,11 @@ def test_supported_and_rows_tile_are_the_stated_envelope_and_the_abi_names_the_e
 
 
 # ---- the argument checks of the front end (no device needed: every refusal comes before the first launch)
-def _fake_level(c_in, widths):
-    from svnet_amd import sa_fused as SF
-    level = object.__new__(SF.FoldedLevel)
-    level.c_in, level.widths, level.device = c_in, tuple(widths), torch.device("cpu")
-    return level
-
-
 def test_interp_mlp_refuses_bad_arguments():
     from svnet_amd import fp_fused as FP
     B, N, S, D1, D2 = 2, 16, 4, 2, 3
     idx, weight = torch.zeros(B, N, 3, dtype=torch.int64), torch.zeros(B, N, 3)
-    f2, f1, level = torch.zeros(B, D2, S), torch.zeros(B, D1, N), _fake_level(D1 + D2, (8,))
+    f2, f1, level = torch.zeros(B, D2, S), torch.zeros(B, D1, N), FL.fake_level(D1 + D2, (8,))
     with pytest.raises(TypeError, match="FoldedLevel"):
         FP.interp_mlp(idx, weight, f2, f1, object())
     with pytest.raises(TypeError, match="idx must be torch.int64"):

@@ -11,6 +11,7 @@ import pytest
 import torch
 
 from svnet_amd import _lib, synth
+from tests import fused_level_cases as FL
 from tests import msg_ref as M
 from tests import sa_fused_ref as R
 from tests.common import compare_case
@@ -67,19 +68,6 @@ def test_fmaf_is_right_where_float64_arithmetic_rounds_twice():
     assert np.array_equal(R.fmaf(a, b, c).view(np.uint32), want.view(np.uint32))
 
 
-def _random_level(seed, C0, widths):
-    layers, last = [], C0
-    for i, w in enumerate(widths):
-        W = (synth.normal(seed, 10 + 8 * i, (w, last)) / np.sqrt(F32(last))).astype(F32)
-        gamma = (synth.normal(seed, 11 + 8 * i, (w,)) + F32(0.25)).astype(F32)                 # both signs
-        state = dict(W=W, b=synth.normal(seed, 12 + 8 * i, (w,)) * F32(0.1), gamma=gamma, beta=synth.normal(seed, 13 + 8 * i, (w,)) * F32(0.2),
-                     mean=synth.normal(seed, 14 + 8 * i, (w,)) * F32(0.1),
-                     var=(np.abs(synth.normal(seed, 15 + 8 * i, (w,))) + F32(0.5)).astype(F32))
-        layers.append(state)
-        last = w
-    return layers
-
-
 @pytest.mark.parametrize("C0,widths,K,xyz_last", [(3, (5,), 1, False), (7, (12, 20), 9, True), (67, (33, 8, 196), 4, False),
                                                   (131, (16, 16, 16, 7), 3, True)])
 def test_fp32_chain_lies_within_the_running_bound_of_the_float64_chain(C0, widths, K, xyz_last):
@@ -88,7 +76,7 @@ def test_fp32_chain_lies_within_the_running_bound_of_the_float64_chain(C0, width
     c = np.ascontiguousarray(x[:S] + F32(0.01))
     pts = synth.normal(8, 2, (N, D)) if D else None
     idx = synth.integers(8, 3, (S, K), N).astype(np.int64)
-    layers = [R.fold(s["W"], s["b"], s["gamma"], s["beta"], s["mean"], s["var"], 1e-5) for s in _random_level(8 + C0, C0, widths)]
+    layers = FL.random_level(8 + C0, C0, widths)
     got = R.level(x, c, idx, pts, layers, xyz_last)
     value, bound = R.level_f64(x, c, idx, pts, layers, xyz_last)
     assert got.dtype == F32 and got.shape == value.shape == bound.shape == (widths[-1], S)
@@ -97,7 +85,7 @@ def test_fp32_chain_lies_within_the_running_bound_of_the_float64_chain(C0, width
     # the bound says something: it grows by sum |Wf| per layer, and after four layers is still under a hundredth of the largest output
     assert float(got.max()) > 0 and (bound < 1e-2 * float(value.max())).all()
     # the fold: against float64 arithmetic within four roundings, and the sign of a negative BatchNorm weight carried into Wf
-    s0 = _random_level(8 + C0, C0, widths)[0]
+    s0 = FL.layer_state(8 + C0, C0, widths)[0]
     scale = s0["gamma"].astype(np.float64) / np.sqrt(s0["var"].astype(np.float64) + 1e-5)
     Wf, bf = layers[0]
     assert np.allclose(Wf, s0["W"] * scale[:, None], rtol=4 * 2.0 ** -23, atol=0) and (s0["gamma"] < 0).any()
@@ -174,18 +162,11 @@ def test_supported_is_the_stated_envelope_and_the_abi_names_the_entries():
 
 
 # ---- the argument checks of the front end (no device needed: every refusal comes before the first launch)
-def _fake_level(c_in, widths):
-    from svnet_amd import sa_fused as SF
-    level = object.__new__(SF.FoldedLevel)
-    level.c_in, level.widths, level.device = c_in, tuple(widths), torch.device("cpu")
-    return level
-
-
 def test_group_mlp_max_refuses_bad_arguments():
     from svnet_amd import sa_fused as SF
     B, N, S, K, D = 2, 16, 4, 4, 2
     xyz, new_xyz, pts = torch.zeros(B, N, 3), torch.zeros(B, S, 3), torch.zeros(B, N, D)
-    idx, count, level = torch.zeros(B, S, K, dtype=torch.int64), torch.ones(B, S, dtype=torch.int32), _fake_level(3 + D, (8,))
+    idx, count, level = torch.zeros(B, S, K, dtype=torch.int64), torch.ones(B, S, dtype=torch.int32), FL.fake_level(3 + D, (8,))
     with pytest.raises(TypeError, match="FoldedLevel"):
         SF.group_mlp_max(xyz, new_xyz, idx, pts, object())
     with pytest.raises(TypeError, match="idx must be torch.int64"):

@@ -10,6 +10,7 @@ import pytest
 import torch
 
 from svnet_amd import _lib, synth
+from tests import fused_level_cases as FL
 from tests import sa_fused_ref as R
 from tests import sa_global_ref as SG
 from tests.common import compare_case
@@ -19,22 +20,11 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 GOLDEN = np.load(os.path.join(HERE, "golden", "sa_global.npz"))
 
 
-def _random_level(seed, C0, widths):
-    layers, last = [], C0
-    for i, w in enumerate(widths):
-        W = (synth.normal(seed, 10 + 8 * i, (w, last)) / np.sqrt(F32(last))).astype(F32)
-        gamma = (synth.normal(seed, 11 + 8 * i, (w,)) + F32(0.25)).astype(F32)                 # both signs
-        layers.append(R.fold(W, synth.normal(seed, 12 + 8 * i, (w,)) * F32(0.1), gamma, synth.normal(seed, 13 + 8 * i, (w,)) * F32(0.2),
-                             synth.normal(seed, 14 + 8 * i, (w,)) * F32(0.1), (np.abs(synth.normal(seed, 15 + 8 * i, (w,))) + F32(0.5)).astype(F32), 1e-5))
-        last = w
-    return layers
-
-
 @pytest.mark.parametrize("N,D,widths", [(1, 0, (5,)), (17, 4, (12, 20)), (40, 64, (33, 8, 300)), (9, 131, (16, 16, 16, 7))])
 def test_fp32_chain_lies_within_the_running_bound_of_the_float64_chain(N, D, widths):
     x = (synth.normal(18, 1, (3, N)) * F32(0.5)).astype(F32)
     pts = synth.normal(18, 2, (D, N)) if D else None
-    layers = _random_level(18 + D, 3 + D, widths)
+    layers = FL.random_level(18 + D, 3 + D, widths)
     got = SG.level(x, pts, layers)
     value, bound = SG.level_f64(x, pts, layers)
     assert got.dtype == F32 and got.shape == value.shape == bound.shape == (widths[-1],)
@@ -109,17 +99,10 @@ def test_supported_is_the_stated_envelope_and_the_abi_names_the_entries():
 
 
 # ---- the argument checks of the front end (no device needed: every refusal comes before the first launch)
-def _fake_level(c_in, widths):
-    from svnet_amd import sa_fused as SF
-    level = object.__new__(SF.FoldedLevel)
-    level.c_in, level.widths, level.device = c_in, tuple(widths), torch.device("cpu")
-    return level
-
-
 def test_global_mlp_max_refuses_bad_arguments():
     from svnet_amd import sa_global as SGL
     B, N, D = 2, 16, 2
-    xyz, pts, level = torch.zeros(B, 3, N), torch.zeros(B, D, N), _fake_level(3 + D, (8,))
+    xyz, pts, level = torch.zeros(B, 3, N), torch.zeros(B, D, N), FL.fake_level(3 + D, (8,))
     with pytest.raises(TypeError, match="FoldedLevel"):
         SGL.global_mlp_max(xyz, pts, object())
     with pytest.raises(TypeError, match="xyz must be torch.float32"):
