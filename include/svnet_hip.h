@@ -45,9 +45,9 @@ int svnet_slices_sum_f64(double* buf, int64_t L, void* stream);
 
 /* ABI version = 100 * round-of-change + serial.  It changes whenever an entry point gains / loses an argument or a caller-owned buffer
  * changes its required length (200: sliced accumulators, SVNET_SLICED_LEN; 400: this header; 401: the totals of a sliced accumulator are
- * written by its consumer, svnet_slices_sum_*; 402: GX of svnet_v2s_bwd_*, gw of svnet_xyzblock_bwd_f32 and col_sum of svnet_gemm_f32 are sliced accumulators; 403: svnet_binweight_grad_f32 takes sliced inputs; 421: svnet_three_nn_f32, svnet_three_interpolate_f32; 422: svnet_ball_query_f32, svnet_group_points_f32; 423: svnet_vlinear_stats_f32 is gone; 424: svnet_edgeblock_fwd_tier, svnet_edgeblock_bwd_tier, svnet_edgeblock_wgrad_tier, svnet_xyzblock_tier; 425: svnet_pointset_reverse_i32, svnet_three_interpolate_bwd_f32, svnet_group_points_bwd_f32; 426: wbt of svnet_edgeblock_wbt_bf16 is 512 values longer, the all-zero fragment; 427: svnet_ball_query_msg_f32, svnet_group_points_msg_f32, svnet_group_points_msg_bwd_f32; 428: svnet_sa_fold_f32, svnet_sa_fused_f32; 429: svnet_fp_fused_f32, svnet_fp_fused_supported, svnet_fp_fused_rows_tile; 430: svnet_sa_global_f32, svnet_sa_global_supported, svnet_sa_global_rows_tile).  svnet_version() returns the value the
+ * written by its consumer, svnet_slices_sum_*; 402: GX of svnet_v2s_bwd_*, gw of svnet_xyzblock_bwd_f32 and col_sum of svnet_gemm_f32 are sliced accumulators; 403: svnet_binweight_grad_f32 takes sliced inputs; 421: svnet_three_nn_f32, svnet_three_interpolate_f32; 422: svnet_ball_query_f32, svnet_group_points_f32; 423: svnet_vlinear_stats_f32 is gone; 424: svnet_edgeblock_fwd_tier, svnet_edgeblock_bwd_tier, svnet_edgeblock_wgrad_tier, svnet_xyzblock_tier; 425: svnet_pointset_reverse_i32, svnet_three_interpolate_bwd_f32, svnet_group_points_bwd_f32; 426: wbt of svnet_edgeblock_wbt_bf16 is 512 values longer, the all-zero fragment; 427: svnet_ball_query_msg_f32, svnet_group_points_msg_f32, svnet_group_points_msg_bwd_f32; 428: svnet_sa_fold_f32, svnet_sa_fused_f32; 429: svnet_fp_fused_f32, svnet_fp_fused_supported, svnet_fp_fused_rows_tile; 430: svnet_sa_global_f32, svnet_sa_global_supported, svnet_sa_global_rows_tile; 431: svnet_pool_gather_attr_f32, the attribute fields attr, A, attr_vectors, attr_out at the end of svnet_batch_desc).  svnet_version() returns the value the
  * library was BUILT with: a caller compiled against another header must refuse to run (svnet_amd/_lib.py does).                   */
-#define SVNET_ABI_VERSION 430
+#define SVNET_ABI_VERSION 431
 int svnet_version(void);
 const char* svnet_last_error(void);
 
@@ -720,7 +720,15 @@ int svnet_sgd_step_dev_f32(float* p, const float* g, float* buf, int64_t n, cons
  * (:179) as ONE launch, one workgroup per cloud, into fixed caller-owned buffers.  Everything slot b receives is a pure function of
  * (seed, epoch, g = first + b) - counter-based splitmix64, the derivation is fixed in svnet_amd/data.py's docstring - so batch size,
  * rank count, graph replay and a resume cannot change a sample.  Slots count .. B-1 repeat slot 0 (a short final batch stays finite).
- * The sorted modes put 8 bytes per key into LDS (keys: N for FIRST_SHUFFLED, P for SUBSET; at most 8192 = 64 KiB, no opt-in). */
+ * The sorted modes put 8 bytes per key into LDS (keys: N for FIRST_SHUFFLED, P for SUBSET; at most 8192 = 64 KiB, no opt-in).
+ * Attributes: attr_out[b,:,n] is the attr row of the pool point x[b,:,n] came from (slots past count repeat slot 0, a poisoned order
+ * entry gives NaN), filled by the same launch and with no further random numbers.  Scalar channels are the pool's bits.  A direction
+ * group (q_0, q_1, q_2) transforms as a normal under x' = R (S x) + shift, i.e. with R S^-1 followed by a renormalisation - the
+ * definition, operation by operation, stands in svnet_amd/data.py's docstring ("attributes"): with scale_shift q_c = fl(n_c / scale_c),
+ * l = fl(sqrt(fl(fl(fl(q_0 q_0) + fl(q_1 q_1)) + fl(q_2 q_2)))), q_c = fl(q_c / l) if l > 0; with a rotation out = R q in the coordinates' operation order;
+ * with neither, the pool's bits.  Non-finite attributes: unspecified values, never an out-of-range access.  Attributes take no LDS:
+ * svnet_batch_supported does not ask about them.                                                                                 */
+#define SVNET_BATCH_MAX_ATTR 32      /* the most attribute channels per point */
 #define SVNET_BATCH_FIRST_SHUFFLED 0 /* the first N points of the cloud, in random order */
 #define SVNET_BATCH_SUBSET 1         /* N of all P points, in random order */
 #define SVNET_BATCH_FIRST_ORDERED 2  /* the first N points as stored */
@@ -745,6 +753,11 @@ typedef struct svnet_batch_desc {
     int64_t* seg_out;     /* [B,N] in x's point order, or NULL */
     float* onehot;        /* [B,num_cat] one-hot of the label, or NULL */
     float* params;        /* [B,16]: 3 scales, 3 shifts, 9 rotation entries (row-major), 0 */
+    /* per-point attributes (normals, colours); all zero = none, which is what a descriptor written before ABI 431 says */
+    const float* attr;    /* [M,P,A] pool attributes, point-major, or NULL */
+    int64_t A;            /* 1 .. SVNET_BATCH_MAX_ATTR when attr is given */
+    int64_t attr_vectors; /* the first attr_vectors groups of three channels are direction vectors; 0 <= 3 attr_vectors <= A */
+    float* attr_out;      /* [B,A,N] channel-first in x's point order, or NULL (then attr is not read) */
 } svnet_batch_desc;
 /* 1 when svnet_batch_assemble_f32 takes the shape, else 0: a pure host function. */
 int svnet_batch_supported(int64_t P, int64_t N, int select_mode);
@@ -768,6 +781,11 @@ int svnet_fps_tier(int64_t P);
 int svnet_fps_f32(const float* xyz, int64_t M, int64_t P, int64_t npoint, const int64_t* start, int64_t* idx, void* stream);
 int svnet_pool_gather_f32(const float* data, const int64_t* seg, const int64_t* idx, int64_t M, int64_t P, int64_t N, int normalize,
                           float* out, int64_t* seg_out, void* stream);
+/* out[m,n,:] = attr[m, idx[m,n], :] for rows of A floats (attr [M,P,A], idx [M,N], out [M,N,A]; 1 <= A <= SVNET_BATCH_MAX_ATTR): the
+ * attributes of a resampled pool, bit for bit, one launch.  An index outside 0 .. P-1 reads nothing: a NaN row.  N * A <= 2^31 - 1 and
+ * M * ceil(N A / 256) <= 2^31 - 1, past that SVNET_E_UNSUPPORTED.                                                                 */
+int svnet_pool_gather_attr_f32(const float* attr, const int64_t* idx, int64_t M, int64_t P, int64_t N, int64_t A, float* out,
+                               void* stream);
 
 /* ------------------------------------------------------------------ feature propagation: sampled points -> dense cloud
  * (models/utils/pointnet_util.py:281-308 PointNetFeaturePropagation.forward without its MLP: three nearest sampled points,

@@ -14,6 +14,12 @@
 // Shape of the kernel: one workgroup per cloud.  The S keys (8 B each, padded with ~0 to a power of two) are written to LDS, sorted
 // there by a bitonic network (one workgroup barrier per compare-exchange step), then the same workgroup gathers the first N rows of
 // the order: 12-byte rows of the pool in, three coalesced channel planes out.
+//
+// Per-point attributes (normals, colours: `attr` [M,P,A] -> `attr_out` [B,A,N]) ride in the same launch, as a second instantiation of the
+// same body (batch_assemble_kernel<true>): the thread that gathered pool point p into slot n reads p's row of A floats and writes one
+// float into each of the A channel planes.  The first `attr_vectors` groups of three channels are direction vectors and follow the
+// normal's rule of svnet_amd/data.py's docstring (divide by the scales, renormalise, rotate); the rest are copied bit for bit.  A pool
+// without attributes launches batch_assemble_kernel<false>, in which none of this exists.
 #include "pointset.h"
 
 namespace {
@@ -50,7 +56,14 @@ struct BatchArgs {
     float* x; int64_t* y; int64_t* seg_out; float* onehot; float* params;
 };
 
-__global__ __launch_bounds__(BATCH_THREADS) void batch_assemble_kernel(const BatchArgs a) {
+struct BatchAttr {
+    const float* attr; float* out;      // [M,P,A] -> [B,A,N]
+    int A, vec3;                        // channels; 3 * attr_vectors: channels 0 .. vec3-1 are direction vectors
+};
+
+// ATTR = false never looks at `at` (the launch passes an empty one)
+template <bool ATTR>
+__global__ __launch_bounds__(BATCH_THREADS) void batch_assemble_kernel(const BatchArgs a, const BatchAttr at) {
     extern __shared__ __align__(16) unsigned char batch_lds[];
     uint64_t* keys = reinterpret_cast<uint64_t*>(batch_lds);
     const int b = blockIdx.x, t = threadIdx.x, T = blockDim.x;
@@ -143,8 +156,38 @@ __global__ __launch_bounds__(BATCH_THREADS) void batch_assemble_kernel(const Bat
         xb[N + n] = v1;
         xb[2 * N + n] = v2;
         if (a.seg_out) a.seg_out[(int64_t)b * N + n] = sg;
+        if (ATTR) {
+            // the row of the same pool point: A floats in, one float into each of the A planes (each plane coalesced over n)
+            const float* arow = at.attr + ((int64_t)m * a.P + p) * at.A;        // (followed only when valid)
+            float* ob = at.out + (int64_t)b * at.A * N + n;
+            int c = 0;
+            for (; c < at.vec3; c += 3) {
+                float q0 = SVNET_QNAN, q1 = SVNET_QNAN, q2 = SVNET_QNAN;
+                if (valid) {
+                    q0 = arow[c]; q1 = arow[c + 1]; q2 = arow[c + 2];
+                    if (a.scale_shift) {
+                        // a normal takes the inverse transpose of the linear part: S^-1, then back to unit length
+                        q0 = q0 / sc[0]; q1 = q1 / sc[1]; q2 = q2 / sc[2];
+                        const float l = sqrtf(sq_len(q0, q1, q2));
+                        if (l > 0.f) { q0 = q0 / l; q1 = q1 / l; q2 = q2 / l; }
+                    }
+                    if (a.rotate != SVNET_BATCH_ROTATE_NONE) {
+                        const float r0 = (R[0] * q0 + R[1] * q1) + R[2] * q2;
+                        const float r1 = (R[3] * q0 + R[4] * q1) + R[5] * q2;
+                        const float r2 = (R[6] * q0 + R[7] * q1) + R[8] * q2;
+                        q0 = r0; q1 = r1; q2 = r2;
+                    }
+                }
+                ob[(int64_t)c * N] = q0;
+                ob[(int64_t)(c + 1) * N] = q1;
+                ob[(int64_t)(c + 2) * N] = q2;
+            }
+#pragma unroll 4
+            for (; c < at.A; ++c) ob[(int64_t)c * N] = valid ? arow[c] : SVNET_QNAN;
+        }
     }
 }
+
 
 }  // namespace
 
@@ -163,6 +206,11 @@ extern "C" int svnet_batch_assemble_f32(const svnet_batch_desc* d, void* stream)
     SVNET_REQUIRE((d->seg_out == nullptr) || d->seg, SVNET_E_ARG, "svnet_batch_assemble_f32: seg_out without a pool seg (null)");
     SVNET_REQUIRE((d->onehot == nullptr) || d->num_cat >= 1, SVNET_E_ARG, "svnet_batch_assemble_f32: onehot with num_cat %lld < 1",
                   (long long)d->num_cat);
+    SVNET_REQUIRE((d->attr_out == nullptr) || d->attr, SVNET_E_ARG, "svnet_batch_assemble_f32: attr_out without a pool attr (null)");
+    SVNET_REQUIRE((d->attr == nullptr) || (d->A >= 1 && d->A <= SVNET_BATCH_MAX_ATTR), SVNET_E_ARG,
+                  "svnet_batch_assemble_f32: attr with A %lld outside 1 .. %d", (long long)d->A, SVNET_BATCH_MAX_ATTR);
+    SVNET_REQUIRE((d->attr == nullptr) || (d->attr_vectors >= 0 && d->attr_vectors <= d->A / 3), SVNET_E_ARG,
+                  "svnet_batch_assemble_f32: attr_vectors %lld: 3 x it outside 0 .. A = %lld", (long long)d->attr_vectors, (long long)d->A);
     SVNET_REQUIRE(d->M >= 1 && d->P >= 1 && d->N >= 1 && d->B >= 1 && d->L >= 1, SVNET_E_ARG,
                   "svnet_batch_assemble_f32: M, P, N, B, L must be positive");
     SVNET_REQUIRE(d->N <= d->P, SVNET_E_ARG, "svnet_batch_assemble_f32: N %lld > P %lld", (long long)d->N, (long long)d->P);
@@ -194,7 +242,12 @@ extern "C" int svnet_batch_assemble_f32(const svnet_batch_desc* d, void* stream)
     threads = svnet_cdiv(threads, SVNET_WAVE) * SVNET_WAVE;
     if (threads > BATCH_THREADS) threads = BATCH_THREADS;
     const size_t lds = (size_t)a.Spad * sizeof(uint64_t);
-    hipLaunchKernelGGL(batch_assemble_kernel, dim3((unsigned)d->B), dim3((unsigned)threads), lds, (hipStream_t)stream, a);
+    if (d->attr_out) {
+        const BatchAttr at{d->attr, d->attr_out, (int)d->A, 3 * (int)d->attr_vectors};
+        hipLaunchKernelGGL(batch_assemble_kernel<true>, dim3((unsigned)d->B), dim3((unsigned)threads), lds, (hipStream_t)stream, a, at);
+    } else {
+        hipLaunchKernelGGL(batch_assemble_kernel<false>, dim3((unsigned)d->B), dim3((unsigned)threads), lds, (hipStream_t)stream, a, BatchAttr{});
+    }
     SVNET_CHECK_LAUNCH("batch_assemble_kernel");
     return SVNET_OK;
 }

@@ -182,6 +182,20 @@ __global__ __launch_bounds__(GATHER_THREADS) void pool_gather_kernel(const float
     }
 }
 
+// out[m,n,:] = attr[m, idx[m,n], :] for rows of A floats: one thread per output float, GATHER_THREADS consecutive floats of a cloud's
+// [N,A] block per workgroup (cloud_grid: cloud-major), so the stores are coalesced and the A threads of a row read A consecutive
+// floats through one index.  A pure copy: the bits of the pool.  An index outside 0 .. P-1 reads nothing and gives NaN.
+__global__ __launch_bounds__(GATHER_THREADS) void pool_gather_attr_kernel(const float* __restrict__ attr, const int64_t* __restrict__ idx,
+                                                                          int64_t P, int64_t N, uint32_t A, uint32_t chunks,
+                                                                          float* __restrict__ out) {
+    const int64_t m = blockIdx.x / chunks;
+    const uint32_t e = (blockIdx.x % chunks) * (uint32_t)GATHER_THREADS + threadIdx.x;         // element of the cloud's [N,A] block
+    if (e >= (uint32_t)N * A) return;
+    const uint32_t n = e / A, c = e - n * A;
+    const int64_t p = idx[m * N + n];
+    out[m * N * A + e] = p >= 0 && p < P ? attr[(m * P + p) * A + c] : SVNET_QNAN;
+}
+
 static size_t fps_lds_bytes(int tier, int64_t P) {
     const size_t slots = 2 * (size_t)(FPS_THREADS[tier] / SVNET_WAVE) * sizeof(FpsSlot);
     return slots + (tier < 4 ? (size_t)P * 3 * sizeof(float) : 0);
@@ -246,5 +260,23 @@ extern "C" int svnet_pool_gather_f32(const float* data, const int64_t* seg, cons
     hipLaunchKernelGGL(pool_gather_kernel, dim3((unsigned)M), dim3(GATHER_THREADS), 0, (hipStream_t)stream, data, seg, idx, P, N,
                        normalize ? 1 : 0, out, seg_out);
     SVNET_CHECK_LAUNCH("pool_gather_kernel");
+    return SVNET_OK;
+}
+
+extern "C" int svnet_pool_gather_attr_f32(const float* attr, const int64_t* idx, int64_t M, int64_t P, int64_t N, int64_t A, float* out,
+                                          void* stream) {
+    SVNET_REQUIRE(attr && idx && out, SVNET_E_ARG, "svnet_pool_gather_attr_f32: null attr / idx / out");
+    SVNET_REQUIRE(M >= 1 && P >= 1 && N >= 1, SVNET_E_ARG, "svnet_pool_gather_attr_f32: M %lld, P %lld, N %lld must be positive",
+                  (long long)M, (long long)P, (long long)N);
+    SVNET_REQUIRE(A >= 1 && A <= SVNET_BATCH_MAX_ATTR, SVNET_E_ARG, "svnet_pool_gather_attr_f32: A %lld outside 1 .. %d", (long long)A,
+                  SVNET_BATCH_MAX_ATTR);
+    SVNET_REQUIRE(N <= 0x7fffffffll / A, SVNET_E_UNSUPPORTED, "svnet_pool_gather_attr_f32: N %lld x A %lld > 2^31 - 1", (long long)N,
+                  (long long)A);
+    const CloudGrid grid = cloud_grid(M, N * A, GATHER_THREADS);
+    SVNET_REQUIRE(grid.blocks > 0, SVNET_E_UNSUPPORTED, "svnet_pool_gather_attr_f32: M %lld x ceil(N A / %d) workgroups > 2^31 - 1",
+                  (long long)M, GATHER_THREADS);
+    hipLaunchKernelGGL(pool_gather_attr_kernel, dim3((unsigned)grid.blocks), dim3(GATHER_THREADS), 0, (hipStream_t)stream, attr, idx, P, N,
+                       (uint32_t)A, (uint32_t)grid.chunks, out);
+    SVNET_CHECK_LAUNCH("pool_gather_attr_kernel");
     return SVNET_OK;
 }

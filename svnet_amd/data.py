@@ -38,6 +38,31 @@ host can restate a batch exactly (tests/loader_ref.py does).  The derivation:
     9 rotation entries it used into `params` [B,16] (no augmentation: 1, 0, identity; those operations are then skipped, not
     multiplied through).
 
+Attributes.  A pool may carry A more floats per point, `attr` [M,P,A] (the reference's ModelNet40_v2(normal_channel=True), data.py:203-256,
+keeps six columns per point, its S3DIS set nine).  They arrive in `loader.points` [B,A,N], channel-first as the set-abstraction levels
+take `points`, filled by the same launch as `loader.x`: slot n of cloud b holds the attributes of the pool point x[b,:,n] came from.
+
+    pool = DevicePool(data, label, attr=normals_and_colours, attr_vectors=1, device="cuda:0")       # attr [M,P,6]: a normal, then r g b
+    loader = BatchLoader(pool, 32, 1024, select="first_shuffled", scale_shift=True, rotate="so3", seed=1)
+    step = TrainStep(model, inputs=(loader.x, loader.points), target=loader.y)
+
+    The first `attr_vectors` groups of three channels are direction vectors (unit normals), the other channels scalars.
+    scalar channels: the pool's bits (-0 stays -0), whatever the augmentation.
+    direction group (n_0, n_1, n_2): the coordinates undergo x' = R (S x) + shift with S = diag(scale); a normal transforms with the
+        inverse transpose of the linear part, R S^-1, the shift does nothing, and its length is restored:
+        scale_shift on:   q_c = fl(n_c / scale_c);  l2 = fl(fl(fl(q_0 q_0) + fl(q_1 q_1)) + fl(q_2 q_2));  l = fl(sqrt(l2));
+                          if l > 0: q_c = fl(q_c / l)  (a zero or underflowing vector stays as the first division left it)
+        scale_shift off:  q = n, bit for bit
+        rotate "z" / "so3": out_r = fl(fl(fl(R_r0 q_0) + fl(R_r1 q_1)) + fl(R_r2 q_2)), R the nine entries written to `params`;
+        rotate "none":      out = q
+    Single-rounded fp32 operations as above, division and square root correctly rounded.  With scale_shift on a direction group
+    therefore comes out at UNIT length whatever length it had in the pool - which is what a normal is; with it off, lengths are kept
+    (a rotation changes them by rounding only).  No further random numbers are drawn and `params` keeps its layout.  The reference
+    never augments a six-column cloud, so this rule is the project's own; tests/loader_attr_ref.py restates it, and checks that the
+    result stays perpendicular to the transformed surface.  Non-finite attributes give unspecified values.
+    resample_fps carries the attributes: sampling and pc_normalize look at the coordinates only (data.py:241-248 normalises
+    point_set[:, 0:3]; a translation and an isotropic scale leave a normal as it is), the new attr[m,n,:] = attr[m, fps_index[m,n], :].
+
 Uniformly resampled pools (the reference's ModelNet40_v2(uniform=True), data.py:203-256: ~10 000-point clouds reduced to num_points
 by `farthest_point_sample`, models/utils/pointnet_util.py:63-84, then `pc_normalize`, data.py:15-20) are made once, on the device
 (svnet_amd/csrc/fps.hip), and the result is an ordinary pool:
@@ -66,6 +91,7 @@ import torch
 from . import _lib, _ops, _pointset, synth
 
 SELECT_MODES = {m: _lib.DEFINES["SVNET_BATCH_" + m.upper()] for m in ("first_shuffled", "subset", "first_ordered")}
+MAX_ATTR = _lib.DEFINES["SVNET_BATCH_MAX_ATTR"]
 ROTATE_MODES = {m: _lib.DEFINES["SVNET_BATCH_ROTATE_" + (m or "none").upper()] for m in ("none", None, "z", "so3")}
 
 _U64 = np.uint64
@@ -137,9 +163,11 @@ def _as_tensor(a, dtype, name):
 
 class DevicePool:
     """A whole data set on the device: data [M,P,3] float32 (point-major, as the HDF5 files hold it: `np.asarray(h5['data'])` is what
-    goes in), label [M] or [M,1] int64, optional seg [M,P] int64.  numpy arrays or tensors; moved to `device` once."""
+    goes in), label [M] or [M,1] int64, optional seg [M,P] int64, optional attr [M,P,A] float32 with 1 <= A <= 32 whose first
+    `attr_vectors` groups of three channels are direction vectors (module docstring, "Attributes"); .A is 0 without attributes.
+    numpy arrays or tensors; moved to `device` once."""
 
-    def __init__(self, data, label, seg=None, device="cuda:0"):
+    def __init__(self, data, label, seg=None, attr=None, attr_vectors=0, device="cuda:0"):
         data = _as_tensor(data, torch.float32, "data")
         label = _as_tensor(label, torch.int64, "label")
         if data.dim() != 3 or data.shape[2] != 3 or data.shape[0] < 1 or data.shape[1] < 1:
@@ -151,8 +179,18 @@ class DevicePool:
             seg = _as_tensor(seg, torch.int64, "seg")
             if tuple(seg.shape) != (M, P):
                 raise ValueError("DevicePool: seg must be [M,P] = %s, got %s" % ((M, P), tuple(seg.shape)))
+        A, attr_vectors = 0, int(attr_vectors)
+        if attr is not None:
+            attr = _as_tensor(attr, torch.float32, "attr")
+            if attr.dim() != 3 or tuple(attr.shape[:2]) != (M, P) or not 1 <= attr.shape[2] <= MAX_ATTR:
+                raise ValueError("DevicePool: attr must be [M,P,A] = [%d,%d,1 .. %d], got %s" % (M, P, MAX_ATTR, tuple(attr.shape)))
+            A = int(attr.shape[2])
+        if not 0 <= 3 * attr_vectors <= A:
+            raise ValueError("DevicePool: attr_vectors = %d: 3 x it must lie in 0 .. A = %d" % (attr_vectors, A))
         device = _pointset.hip_device("DevicePool", device)
         self.M, self.P, self.device = M, P, device
+        self.A, self.attr_vectors = A, attr_vectors
+        self.attr = None if attr is None else attr.to(device).contiguous()
         self.data = data.to(device).contiguous()
         self.label = label.reshape(M).to(device).contiguous()
         self.seg = None if seg is None else seg.to(device).contiguous()
@@ -161,7 +199,8 @@ class DevicePool:
         """A new pool [M,num_points,3] on the same device: every cloud reduced to `num_points` by farthest point sampling, optionally
         followed by pc_normalize (module docstring) - how a pool of more than 8192 points per cloud gets under the BatchLoader's limit.
         `start` [M] int64 (numpy or tensor) is the first centroid of every cloud; None: fps_start(seed, M, P).  `label` is shared,
-        `seg` is gathered, and `.fps_index` [M,num_points] keeps which point of the source every point is."""
+        `seg` and `attr` are gathered (attr[m,n,:] = attr[m, fps_index[m,n], :] bit for bit; sampling and normalisation look at the
+        coordinates only), and `.fps_index` [M,num_points] keeps which point of the source every point is."""
         N = int(num_points)
         if start is None:
             start = fps_start(seed, self.M, self.P)
@@ -172,10 +211,15 @@ class DevicePool:
         new.data = torch.empty(self.M, N, 3, dtype=torch.float32, device=self.device)
         new.label = self.label
         new.seg = None if self.seg is None else torch.empty(self.M, N, dtype=torch.int64, device=self.device)
+        new.A, new.attr_vectors = self.A, self.attr_vectors
+        new.attr = None if self.attr is None else torch.empty(self.M, N, self.A, dtype=torch.float32, device=self.device)
         new.fps_index = idx
         with torch.cuda.device(self.device):
             _lib.call("svnet_pool_gather_f32", _ops._p(self.data), _ops._p(self.seg), _ops._p(idx), self.M, self.P, N,
                       int(bool(normalize)), _ops._p(new.data), _ops._p(new.seg), _ops._stream())
+            if self.attr is not None:
+                _lib.call("svnet_pool_gather_attr_f32", _ops._p(self.attr), _ops._p(idx), self.M, self.P, N, self.A, _ops._p(new.attr),
+                          _ops._stream())
         return new
 
     def source_points(self, source_pool):
@@ -214,7 +258,9 @@ class BatchLoader:
     """Fills fixed device buffers with one batch per `load(step)`, one launch each (see the module docstring).
 
     .x [B,3,N] float32 (the models' input), .y [B] int64, .seg [B,N] int64 (pools with seg), .onehot [B,num_cat] float32 (when
-    num_cat is given: the one-hot of the label, the part-seg models' second input), .params [B,16] float32 (the augmentation used).
+    num_cat is given: the one-hot of the label, the part-seg models' second input), .params [B,16] float32 (the augmentation used),
+    .points [B,A,N] float32 (pools with attr, else None: the per-point attributes in .x's point order, direction vectors transformed
+    with the coordinates - with scale_shift on they come out at unit length; module docstring, "Attributes").
     select: "first_shuffled" (ModelNet40 / ShapeNetPart training), "subset" (ScanObjectNN), "first_ordered" (every test partition).
     """
 
@@ -222,7 +268,7 @@ class BatchLoader:
                  rank=0, world=1, num_cat=None):
         if not isinstance(pool, DevicePool):
             raise TypeError("BatchLoader: pool must be a DevicePool")
-        _ops._hip(pool.data, pool.label, pool.seg)
+        _ops._hip(pool.data, pool.label, pool.seg, pool.attr)
         if select not in SELECT_MODES:
             raise ValueError("BatchLoader: select must be one of %r" % sorted(SELECT_MODES))
         if rotate not in ROTATE_MODES:
@@ -249,6 +295,7 @@ class BatchLoader:
         self.num_cat = None if num_cat is None else int(num_cat)
         self.onehot = None if num_cat is None else torch.zeros(B, self.num_cat, dtype=torch.float32, device=dev)
         self.params = torch.zeros(B, 16, dtype=torch.float32, device=dev)
+        self.points = None if pool.attr is None else torch.zeros(B, pool.A, N, dtype=torch.float32, device=dev)
         self.order = torch.empty(pool.M, dtype=torch.int64, device=dev)
         self.epoch = None
         self._desc = _lib.BatchDesc()
@@ -259,6 +306,7 @@ class BatchLoader:
         d.select_mode, d.scale_shift, d.rotate = self.select_mode, self.scale_shift, self.rotate
         d.num_cat = self.num_cat or 0
         d.x, d.y, d.seg_out, d.onehot, d.params = _ops._p(self.x), _ops._p(self.y), _ops._p(self.seg), _ops._p(self.onehot), _ops._p(self.params)
+        d.attr, d.A, d.attr_vectors, d.attr_out = _ops._p(pool.attr), pool.A, pool.attr_vectors, _ops._p(self.points)
         self.set_epoch(0)
 
     def set_epoch(self, epoch):
