@@ -45,9 +45,9 @@ int svnet_slices_sum_f64(double* buf, int64_t L, void* stream);
 
 /* ABI version = 100 * round-of-change + serial.  It changes whenever an entry point gains / loses an argument or a caller-owned buffer
  * changes its required length (200: sliced accumulators, SVNET_SLICED_LEN; 400: this header; 401: the totals of a sliced accumulator are
- * written by its consumer, svnet_slices_sum_*; 402: GX of svnet_v2s_bwd_*, gw of svnet_xyzblock_bwd_f32 and col_sum of svnet_gemm_f32 are sliced accumulators; 403: svnet_binweight_grad_f32 takes sliced inputs; 421: svnet_three_nn_f32, svnet_three_interpolate_f32; 422: svnet_ball_query_f32, svnet_group_points_f32; 423: svnet_vlinear_stats_f32 is gone; 424: svnet_edgeblock_fwd_tier, svnet_edgeblock_bwd_tier, svnet_edgeblock_wgrad_tier, svnet_xyzblock_tier; 425: svnet_pointset_reverse_i32, svnet_three_interpolate_bwd_f32, svnet_group_points_bwd_f32; 426: wbt of svnet_edgeblock_wbt_bf16 is 512 values longer, the all-zero fragment; 427: svnet_ball_query_msg_f32, svnet_group_points_msg_f32, svnet_group_points_msg_bwd_f32; 428: svnet_sa_fold_f32, svnet_sa_fused_f32; 429: svnet_fp_fused_f32, svnet_fp_fused_supported, svnet_fp_fused_rows_tile; 430: svnet_sa_global_f32, svnet_sa_global_supported, svnet_sa_global_rows_tile; 431: svnet_pool_gather_attr_f32, the attribute fields attr, A, attr_vectors, attr_out at the end of svnet_batch_desc).  svnet_version() returns the value the
+ * written by its consumer, svnet_slices_sum_*; 402: GX of svnet_v2s_bwd_*, gw of svnet_xyzblock_bwd_f32 and col_sum of svnet_gemm_f32 are sliced accumulators; 403: svnet_binweight_grad_f32 takes sliced inputs; 421: svnet_three_nn_f32, svnet_three_interpolate_f32; 422: svnet_ball_query_f32, svnet_group_points_f32; 423: svnet_vlinear_stats_f32 is gone; 424: svnet_edgeblock_fwd_tier, svnet_edgeblock_bwd_tier, svnet_edgeblock_wgrad_tier, svnet_xyzblock_tier; 425: svnet_pointset_reverse_i32, svnet_three_interpolate_bwd_f32, svnet_group_points_bwd_f32; 426: wbt of svnet_edgeblock_wbt_bf16 is 512 values longer, the all-zero fragment; 427: svnet_ball_query_msg_f32, svnet_group_points_msg_f32, svnet_group_points_msg_bwd_f32; 428: svnet_sa_fold_f32, svnet_sa_fused_f32; 429: svnet_fp_fused_f32, svnet_fp_fused_supported, svnet_fp_fused_rows_tile; 430: svnet_sa_global_f32, svnet_sa_global_supported, svnet_sa_global_rows_tile; 431: svnet_pool_gather_attr_f32, the attribute fields attr, A, attr_vectors, attr_out at the end of svnet_batch_desc; 432: svnet_vn_fold_f32, svnet_vn_tables_f32, svnet_vn_edge_mean_f32, svnet_vn_supported, svnet_vn_workspace_bytes).  svnet_version() returns the value the
  * library was BUILT with: a caller compiled against another header must refuse to run (svnet_amd/_lib.py does).                   */
-#define SVNET_ABI_VERSION 431
+#define SVNET_ABI_VERSION 432
 int svnet_version(void);
 const char* svnet_last_error(void);
 
@@ -982,6 +982,41 @@ int svnet_sa_global_supported(int64_t N, int64_t D, int64_t L, const int64_t* wi
 int svnet_sa_global_rows_tile(int64_t D, int64_t L, const int64_t* widths);
 int svnet_sa_global_f32(const float* xyz, const float* points, int64_t B, int64_t N, int64_t D, int64_t L, const int64_t* widths,
                         const void* wf, const void* bf, float* out, int64_t C_total, int64_t c_off, void* stream);
+
+/* ------------------------------------------------------------------ fused vector-neuron edge level for inference: tables, leaky rule, mean
+ * (models/vn_layers.py:50-78, the eval-mode forward of VNLinearLeakyReLU over 2C -> O vector channels, on the edge feature
+ * [x_j - x_i | x_i] of models/utils/vn_util.py:23-49 get_graph_feature, followed by mean_pool over the k neighbours: one edge level of
+ * models/vn_dgcnn_cls.py with pooling = 'mean').  The level is linear in the edge feature in front of its non-linearity,
+ * W [x_j - x_i | x_i] = W_a x_j + (W_b - W_a) x_i, so the products are taken once per point and an edge adds two table rows.
+ * fl() is rounding to fp32; every operation is rounded once, nothing is contracted but the stated fmaf.  EPS = fl(1e-6).
+ * Od is the number of direction rows: O, or 1 (share_nonlinearity: every o uses row 0).  R = 2 (O + Od).
+ * svnet_vn_fold_f32: w_feat [O,2C] (map_to_feat.weight), w_dir [Od,2C] (map_to_dir.weight), BatchNorm gamma, beta, running_mean,
+ *     running_var [O] -> folded, C R + 2 O floats, caller-owned: WT [C][R] | s [O] | t [O].  One launch, no host read.
+ *         A_f = w_feat[:, :C], D_f = fl(w_feat[:, C:] - w_feat[:, :C]); A_d, D_d likewise from w_dir; column r of WT is row r of
+ *         [A_f | A_d | D_f | D_d];  invstd = fl(1 / fl(sqrt(fl(var + eps)))), s = fl(gamma invstd), t = fl(beta - fl(mean s)).
+ * svnet_vn_tables_f32: x [B,C,3,N] -> workspace [TN | TC], each [B][N][3 (O + Od)] floats.  Per point n, component a and row:
+ *     a c-ascending chain acc = +0; acc = fmaf(x[c,a,n], M[row,c], acc) - Pn with M = A_f, Qn with A_d (into TN), Pc with D_f, Qc with
+ *     D_d (into TC).  A table row is [P: a O + o | Q: 3 O + a Od + od].  K is never split: no value depends on tiling.  One launch.
+ * svnet_vn_edge_mean_f32: the tables, idx [B,N,k] int64 and folded -> out [B,O,3,N].  Per edge (n, j), m = idx[n,j] clamped into
+ *     0 .. N-1, per o (od = o, or 0 with Od = 1):
+ *         p[a] = fl(Pn[m,o,a] + Pc[n,o,a]);  d[a] = fl(Qn[m,od,a] + Qc[n,od,a])
+ *         q = fmaf(p2, p2, fmaf(p1, p1, fl(p0 p0)));  r = fl(fl(sqrt(q)) + EPS);  nb = fmaf(r, s[o], t[o]);  g = fl(nb / r);  p'[a] = fl(p[a] g)
+ *         dot = fmaf(p'2, d2, fmaf(p'1, d1, fl(p'0 d0)));  dd = fmaf(d2, d2, fmaf(d1, d1, fl(d0 d0)))
+ *         w = p' if dot >= 0, else c = fl(dot / fl(dd + EPS)) and w[a] = fmaf(-c, d[a], p'[a])
+ *         y[a] = fmaf(slope, p'[a], fl(fl(1 - slope) w[a]))
+ *     out[o,a,n] = fl((sum over j ascending from +0 of y_j[o,a]) / fl(k)).  One launch, no host read, no atomics: capturable,
+ *     reproducible.  Inputs are assumed finite.
+ * svnet_vn_supported (1 / 0, a pure host function): 1 <= k <= 64, k <= N <= 32768, 1 <= C <= 128, 1 <= O <= 128, Od = O or 1.
+ * svnet_vn_workspace_bytes (a pure host function): 2 B N 3 (O + Od) floats in bytes; 0 outside the limits.  B > 65535 is refused by
+ *     the tables call with SVNET_E_ARG, B * ceil(N / 16) > 2^31 - 1 by the edge call with SVNET_E_UNSUPPORTED.                       */
+int svnet_vn_supported(int64_t N, int64_t k, int64_t C, int64_t O, int64_t Od);
+size_t svnet_vn_workspace_bytes(int64_t B, int64_t N, int64_t O, int64_t Od);
+int svnet_vn_fold_f32(const float* w_feat, const float* w_dir, const float* gamma, const float* beta, const float* running_mean,
+                      const float* running_var, int64_t C, int64_t O, int64_t Od, float eps, float* folded, void* stream);
+int svnet_vn_tables_f32(const float* x, const float* folded, int64_t B, int64_t N, int64_t C, int64_t O, int64_t Od, float* workspace,
+                        size_t workspace_bytes, void* stream);
+int svnet_vn_edge_mean_f32(const float* workspace, size_t workspace_bytes, const int64_t* idx, const float* folded, int64_t B, int64_t N,
+                           int64_t k, int64_t C, int64_t O, int64_t Od, float slope, float* out, void* stream);
 
 /* ------------------------------------------------------------------ epoch metrics (main_cls_dgcnn.py:187-251, main_partseg_dgcnn.py:185-279,
  * utils.py:68-91 calculate_shape_IoU; the accuracy scores of sklearn.metrics are functions of the confusion matrix)

@@ -1,0 +1,240 @@
+"""Fused vector-neuron edge level for inference: the point tables, the leaky rule and the mean over the neighbours as two launches
+(svnet_amd/csrc/vn_edge.hip), and the eval-mode forward of VN_DGCNN_CLS on top of it.
+
+An edge level of the vector-neuron DGCNN is get_graph_feature -> VNLinearLeakyReLU -> mean over k (svnet_amd/models/vn_layers.py,
+models/utils/vn_util.py).  In torch operations it works on [B, 2C, 3, N, k] and [B, O, 3, N, k] tensors and writes and re-reads more
+than ten of them; the mean then keeps 1/k.  The level is linear in the edge feature in front of its non-linearity,
+
+    W [x_j - x_i | x_i] = W_a x_j + (W_b - W_a) x_i,
+
+so the products are taken once per point (the tables: k times fewer multiply-adds) and the edge pass is a gather of two table rows,
+the non-linearity and a running sum that writes 3 O floats per point and nothing else.  Training is out of scope, as in
+svnet_amd/sa_fused.py: the modules stay as they are, this is an entry beside them, for pooling = 'mean'.
+
+    folded = fold_vn_layer(layer)                      # a VNLinearLeakyReLU over 2C -> O; buffers allocated once, refresh()
+    out = vn_edge_mean(x, idx, folded, out=None)       # x [B,C,3,N] f32, idx [B,N,k] int64 -> [B,O,3,N]
+    fused = FusedVNDGCNN(model)                        # an nn.Module: the eval-mode forward of a VN_DGCNN_CLS
+    logits = fused(x)                                  # x [B,3,N]; fused.last_idx: the four neighbour lists of this call
+
+The contract, for one cloud (fl() is rounding to fp32, every operation rounded once, nothing contracted but the stated fmaf;
+EPS = fl(1e-6), vn_layers.EPS):
+
+    fold        A_f = W_feat[:, :C], D_f = fl(W_feat[:, C:] - W_feat[:, :C]); A_d, D_d likewise from map_to_dir (O rows, or 1 row
+                under share_nonlinearity: Od = 1 and every o uses direction row 0).  From BatchNorm's running statistics, as
+                fold_level does: invstd = fl(1 / fl(sqrt(fl(var + eps)))), s = fl(gamma invstd), t = fl(beta - fl(mean s)).
+    tables      per point n, component a and row o: four c-ascending chains acc = +0; acc = fmaf(x[c,a,n], M[o,c], acc):
+                Pn with M = A_f, Pc with D_f, Qn with A_d, Qc with D_d.  K is never split, so no value depends on tiling.
+    edge        (n, j), m = idx[n,j] clamped into 0 .. N-1:  p[o,a] = fl(Pn[m,o,a] + Pc[n,o,a]),  d likewise from Qn, Qc.
+    norm        q = fl(p0 p0), then fmaf in p1 and p2;  r = fl(fl(sqrt(q)) + EPS);  nb = fmaf(r, s[o], t[o]);  g = fl(nb / r);
+                p'[a] = fl(p[a] g).
+    leaky       dot and dd are 3-term chains like q, of p' d and d d.  If dot >= 0 then w = p'; otherwise c = fl(dot / fl(dd + EPS))
+                and w[a] = fmaf(-c, d[a], p'[a]).  y[a] = fmaf(slope, p'[a], fl(fl(1 - slope) w[a])).  The function is continuous
+                across dot = 0: the mask selects between branches that agree there.
+    mean        out[o,a,n] = fl((sum over j ascending from +0 of y_j[o,a]) / fl(k)).
+    limits      1 <= k <= 64, k <= N <= 32768, 1 <= C <= 128, 1 <= O <= 128, Od is O or 1 (`supported`).  Inputs are assumed finite.
+
+The module divides by the norm and multiplies by BatchNorm's output, p / r * nb, in batched torch operations; the contract's order
+differs from it in rounding only.  tests/vn_ref.py restates the contract in numpy; the kernel's results are compared with it as bit
+patterns (a -0 counted as +0).  No argument may require grad.  There is no CPU fallback: tensors that are not on a HIP device raise.
+"""
+import torch
+
+from . import _lib, _ops, _pointset
+
+__all__ = ["fold_vn_layer", "vn_edge_mean", "supported", "FoldedVNLayer", "FusedVNDGCNN", "MAX_K", "MAX_C", "MAX_O"]
+
+_WHAT = "the fused vector-neuron edge level"   # in the messages of _pointset.check_tensors
+MAX_K, MAX_C, MAX_O = 64, 128, 128
+_F32 = torch.float32
+
+
+def supported(N, k, C, O, Od):
+    """Whether the fused kernels take this level (module docstring, limits)."""
+    return bool(_lib.lib().svnet_vn_supported(int(N), int(k), int(C), int(O), int(Od)))
+
+
+class FoldedVNLayer:
+    """The folded form of one VNLinearLeakyReLU over 2C -> O vector channels: WT [C, 2 (O + Od)] | s [O] | t [O] in one buffer on the
+    layer's device, allocated once, and the table workspace, which grows to the largest (B, N) seen and is then reused.  refresh()
+    runs the fold again - after the parameters or the running statistics changed - on the current stream, one launch.
+    A workspace that was outgrown stays allocated, because a graph captured with it goes on replaying into it: a caller that sweeps
+    growing (B, N) holds one buffer per growth step (134 MB at B 32, N 1024 for the classifier's widest level) until release()."""
+
+    def __init__(self, layer):
+        from .models.vn_layers import VNLinearLeakyReLU
+        if not isinstance(layer, VNLinearLeakyReLU):
+            raise TypeError("fold_vn_layer: needs a VNLinearLeakyReLU, got %s" % type(layer).__name__)
+        bn = layer.batchnorm.bn
+        wf, wd = layer.map_to_feat.weight, layer.map_to_dir.weight
+        if wf.shape[1] % 2 or wf.shape[1] != wd.shape[1] or wd.shape[0] not in (wf.shape[0], 1) or int(bn.num_features) != wf.shape[0]:
+            raise ValueError("fold_vn_layer: map_to_feat %s, map_to_dir %s, BatchNorm over %d: needs an even input width 2C, O or 1 direction rows"
+                             % (tuple(wf.shape), tuple(wd.shape), bn.num_features))
+        if bn.running_mean is None or bn.running_var is None or bn.weight is None or bn.bias is None:
+            raise ValueError("fold_vn_layer: the BatchNorm must be affine and track running statistics")
+        for k, t in {"map_to_feat.weight": wf, "map_to_dir.weight": wd, "bn.weight": bn.weight, "bn.bias": bn.bias,
+                     "running_mean": bn.running_mean, "running_var": bn.running_var}.items():
+            if t.dtype != _F32 or not t.is_contiguous() or t.device != wf.device:
+                raise ValueError("fold_vn_layer: %s must be contiguous float32 on %s" % (k, wf.device))
+        self.device = _pointset.hip_device("fold_vn_layer", wf.device)
+        self.layer = layer
+        self.C, self.O, self.Od = int(wf.shape[1]) // 2, int(wf.shape[0]), int(wd.shape[0])
+        if not supported(1, 1, self.C, self.O, self.Od):
+            raise _lib.SvnetHipError("fold_vn_layer: C = %d, O = %d is not supported (1 <= C <= %d, 1 <= O <= %d)" % (self.C, self.O, MAX_C, MAX_O))
+        self.folded = torch.empty(self.C * 2 * (self.O + self.Od) + 2 * self.O, dtype=_F32, device=self.device)
+        self.workspace, self._retired = None, []
+        self.refresh()
+
+    @property
+    def slope(self):
+        return float(self.layer.negative_slope)
+
+    def refresh(self):
+        layer, bn = self.layer, self.layer.batchnorm.bn
+        if layer.map_to_feat.weight.device != self.device:
+            raise ValueError("fold_vn_layer: the layer moved from %s to %s - fold it again" % (self.device, layer.map_to_feat.weight.device))
+        with torch.cuda.device(self.device):
+            _lib.call("svnet_vn_fold_f32", _ops._p(layer.map_to_feat.weight.detach()), _ops._p(layer.map_to_dir.weight.detach()),
+                      _ops._p(bn.weight.detach()), _ops._p(bn.bias.detach()), _ops._p(bn.running_mean), _ops._p(bn.running_var), self.C, self.O,
+                      self.Od, float(bn.eps), _ops._p(self.folded), _ops._stream())
+        return self
+
+    def tables(self, B, N):
+        """The workspace for B clouds of N points (uint8): the one kept if it is large enough, else a new one that replaces it.  A
+        replaced one stays allocated: a graph captured with it goes on replaying into memory nothing else was given."""
+        need = int(_lib.lib().svnet_vn_workspace_bytes(B, N, self.O, self.Od))
+        if self.workspace is None or self.workspace.numel() < need:
+            if self.workspace is not None:
+                self._retired.append(self.workspace)
+            self.workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return self.workspace
+
+    def release(self):
+        """Frees the outgrown workspaces (the current one stays).  Only when no captured graph that was recorded with one of them
+        will be replayed again: such a graph would write into memory that may by then belong to another tensor."""
+        self._retired.clear()
+        return self
+
+
+def fold_vn_layer(layer):
+    """A VNLinearLeakyReLU over 2C -> O vector channels (an edge level's), on a HIP device -> FoldedVNLayer."""
+    return FoldedVNLayer(layer)
+
+
+def _launch(x, idx, folded, out, B, N, k, edge=True, tables=True):
+    ws = folded.tables(B, N)
+    with torch.cuda.device(x.device):
+        if tables:
+            _lib.call("svnet_vn_tables_f32", _ops._p(x), _ops._p(folded.folded), B, N, folded.C, folded.O, folded.Od, _ops._p(ws), ws.numel(),
+                      _ops._stream())
+        if edge:
+            _lib.call("svnet_vn_edge_mean_f32", _ops._p(ws), ws.numel(), _ops._p(idx), _ops._p(folded.folded), B, N, k, folded.C, folded.O,
+                      folded.Od, folded.slope, _ops._p(out), _ops._stream())
+
+
+def vn_edge_mean(x, idx, folded, out=None):
+    """x [B,C,3,N] float32, idx [B,N,k] int64 and folded a FoldedVNLayer over 2C -> O -> out [B,O,3,N]: the mean over the k edges of
+    the layer's eval-mode forward on [x_j - x_i | x_i] (module docstring).  Two launches on the current stream, no host read.  Entries
+    of idx outside 0 .. N-1 are clamped into the cloud.  No argument may require grad."""
+    name = "vn_edge_mean"
+    if not isinstance(folded, FoldedVNLayer):
+        raise TypeError("%s: folded must be a FoldedVNLayer (vn_fused.fold_vn_layer), got %s" % (name, type(folded).__name__))
+    args = {"x": x, "idx": idx}
+    dtypes = [_F32, torch.int64]
+    if out is not None:
+        args["out"] = out
+        dtypes.append(_F32)
+    _pointset.check_tensors(name, args, dtypes, _WHAT)
+    if x.dim() != 4 or x.shape[2] != 3 or x.shape[0] < 1:
+        raise ValueError("%s: x must be [B,C,3,N], got %s" % (name, tuple(x.shape)))
+    B, C, _, N = (int(v) for v in x.shape)
+    if idx.dim() != 3 or idx.shape[0] != B or idx.shape[1] != N:
+        raise ValueError("%s: idx must be [B,N,k] with B = %d, N = %d, got %s" % (name, B, N, tuple(idx.shape)))
+    k = int(idx.shape[2])
+    if C != folded.C:
+        raise ValueError("%s: the layer takes %d vector channels, x has %d" % (name, folded.C, C))
+    if out is not None and tuple(out.shape) != (B, folded.O, 3, N):
+        raise ValueError("%s: out must be [B,O,3,N] = %s, got %s" % (name, (B, folded.O, 3, N), tuple(out.shape)))
+    _ops._hip(x, idx, out)
+    if folded.device != x.device:
+        raise ValueError("%s: the layer is on %s, x on %s" % (name, folded.device, x.device))
+    if not supported(N, k, C, folded.O, folded.Od):
+        raise _lib.SvnetHipError("%s: N = %d, k = %d, C = %d, O = %d is not supported (1 <= k <= %d, k <= N <= %d, C <= %d, O <= %d)"
+                                 % (name, N, k, C, folded.O, MAX_K, _pointset.MAX_N, MAX_C, MAX_O))
+    if out is None:
+        out = torch.empty(B, folded.O, 3, N, dtype=_F32, device=x.device)
+    _launch(x, idx, folded, out, B, N, k)
+    return out
+
+
+class FusedVNDGCNN(torch.nn.Module):
+    """The eval-mode forward of a VN_DGCNN_CLS on a HIP device with the module's signature, forward(x [B,3,N], idx=None) -> logits:
+    the four edge levels run as knn then vn_edge_mean (or on the four given lists), the rest of the network - conv5, VNStdFeature, the
+    pools, the head - through the model's own layers, under no_grad.  It holds the model, so ForwardStep and Distiller take it as
+    they take the model.  The levels are folded at construction; refresh() folds them again after the parameters or the running
+    statistics changed.  Train mode is refused: batch statistics are not what this computes.  A model with pooling = 'max', or a
+    call with a level outside the kernels' limits (`supported`), goes through the model's own forward.  `last_idx`: the four
+    neighbour lists of the last fused call, so that a comparison can replay them into the model.  The wrapper's own `training` flag
+    is the model's at construction and follows train() / eval() called on the wrapper; forward reads the model's flag, so a mode
+    set on the model directly is honoured as well.  release() frees the levels' outgrown table workspaces (FoldedVNLayer)."""
+
+    def __init__(self, model):
+        from .models.vn_dgcnn_cls import VN_DGCNN_CLS
+        from .models.vn_layers import mean_pool
+        super().__init__()
+        if not isinstance(model, VN_DGCNN_CLS):
+            raise TypeError("FusedVNDGCNN: needs a VN_DGCNN_CLS, got %s" % type(model).__name__)
+        self.model = model
+        self.training = model.training                      # (a new nn.Module starts in train mode: this one is in its model's)
+        self.mean = all(pool is mean_pool for _, pool in model.edge_levels())
+        self.levels = [fold_vn_layer(conv) for conv, _ in model.edge_levels()] if self.mean else []
+        self.last_idx = None
+
+    def refresh(self):
+        for level in self.levels:
+            level.refresh()
+        return self
+
+    def release(self):
+        for level in self.levels:
+            level.release()
+        return self
+
+    def supported(self, N, k):
+        """Whether clouds of N points with k neighbours take the fused path here; else forward runs the model."""
+        return bool(self.mean and all(supported(N, k, f.C, f.O, f.Od) for f in self.levels))
+
+    @torch.no_grad()
+    def forward(self, x, idx=None):
+        name = "FusedVNDGCNN"
+        if self.model.training:
+            raise RuntimeError("%s: the model is in train mode - this is the eval-mode forward (model.eval())" % name)
+        if isinstance(x, torch.Tensor) and x.requires_grad:      # (asked of the argument itself: under no_grad a contiguous copy takes no gradient)
+            raise ValueError("%s: x requires grad - %s is forward only in x" % (name, _WHAT))
+        _pointset.check_tensors(name, {"x": x.contiguous() if isinstance(x, torch.Tensor) else x}, [_F32], _WHAT)      # (a view is taken, as the model takes it)
+        if x.dim() != 3 or x.shape[1] != 3 or x.shape[0] < 1:
+            raise ValueError("%s: x must be [B,3,N], got %s" % (name, tuple(x.shape)))
+        if idx is not None and (len(idx) != 4 or any(not isinstance(i, torch.Tensor) or i.dtype != torch.int64 or i.dim() != 3
+                                                     or i.shape[:2] != (x.shape[0], x.shape[2]) for i in idx)):
+            raise ValueError("%s: idx must hold the four levels' neighbour lists [B,N,k] int64" % name)
+        for n, i in enumerate(idx or ()):
+            if i.device != x.device:
+                raise ValueError("%s: x on %s, idx[%d] on %s" % (name, x.device, n, i.device))
+        _ops._hip(x, *(idx or ()))
+        B, _, N = (int(v) for v in x.shape)
+        ks = [self.model.k] * 4 if idx is None else [int(i.shape[2]) for i in idx]
+        if not all(self.supported(N, k) for k in ks):
+            return self.model(x, idx=idx)
+        if self.levels[0].device != x.device:
+            raise ValueError("%s: the model is on %s, x on %s" % (name, self.levels[0].device, x.device))
+        from .models.utils.vn_util import knn
+        h = x.contiguous().view(B, 1, 3, N)
+        feats, used = [], []
+        for i, level in enumerate(self.levels):
+            nbr = knn(h.view(B, -1, N), ks[i]) if idx is None else idx[i].contiguous()
+            out = torch.empty(B, level.O, 3, N, dtype=_F32, device=x.device)
+            _launch(h, nbr, level, out, B, N, ks[i])
+            used.append(nbr)
+            feats.append(out)
+            h = out
+        self.last_idx = used
+        return self.model.tail(feats)
