@@ -4,12 +4,12 @@ fold_level and MAX_LAYERS in sa_fused.  The device side of the same - the layer 
 svnet_amd/csrc/mlp_tile.h.
 
 Here: the folded layers of a level, and the argument checks in the order every entry applies them - the level's type, the tensors,
-the shapes, the level's input columns, the window of `out`, then (by _ops._hip) the HIP device, the level's device and, in the
+the shapes, the level's input columns, the window of `out`, then (by _call.hip) the HIP device, the level's device and, in the
 entry itself, the kernel's limits.  Which kernel runs, its launch and its limits stay in the three modules.
 """
 import torch
 
-from . import _lib, _ops, _pointset
+from . import _call, _lib, _pointset
 
 MAX_LAYERS = _lib.DEFINES["SVNET_SA_MAX_LAYERS"]
 
@@ -61,9 +61,9 @@ class FoldedLevel:
             for conv, bn, wf, bf in zip(self.convs, self.bns, self.wf, self.bf):
                 if conv.weight.device != self.device:
                     raise ValueError("fold_level: the layers moved from %s to %s - fold them again" % (self.device, conv.weight.device))
-                _lib.call("svnet_sa_fold_f32", _ops._p(conv.weight.detach()), _ops._p(conv.bias.detach()), _ops._p(bn.weight.detach()),
-                          _ops._p(bn.bias.detach()), _ops._p(bn.running_mean), _ops._p(bn.running_var), wf.shape[0], wf.shape[1],
-                          float(bn.eps), _ops._p(wf), _ops._p(bf), _ops._stream())
+                _lib.call("svnet_sa_fold_f32", _call.p(conv.weight.detach()), _call.p(conv.bias.detach()), _call.p(bn.weight.detach()),
+                          _call.p(bn.bias.detach()), _call.p(bn.running_mean), _call.p(bn.running_var), wf.shape[0], wf.shape[1],
+                          float(bn.eps), _call.p(wf), _call.p(bf), _call.stream())
         return self
 
 

@@ -1,4 +1,4 @@
-"""torch.autograd.Function wrappers over the C ABI (include/svnet_hip.h).
+"""The torch.autograd.Function wrappers and the functional ops over the C ABI (include/svnet_hip.h).
 
 PyTorch is plumbing here: it owns device memory (every output / workspace is a torch tensor), the
 current HIP stream and the autograd graph.  All arithmetic happens in libsvnet_hip.so.  Every entry
@@ -8,8 +8,13 @@ import ctypes
 
 import torch
 
-from . import _lib, config
-from ._lib import BinHeadDesc, GemmDesc, call
+from . import _call, _lib, config
+from ._lib import BinHeadDesc, GemmDesc
+# (none of these is ever rebound, so the names here cannot go stale; what is rebound during a step is read as STEP.<name>)
+from ._step import (DEFERRED, PLANES, STEP, UNIT_GRAD, _Deferred, _PlaneCache, _ZeroArena, _side_stream, _zeros,      # noqa: F401
+                    _zeros_pool, begin_step, end_step)
+
+_p, _stream, _hip, _f32c, call = _call.p, _call.stream, _call.hip, _call.f32c, _call.call       # the op layer's short names
 
 BN_EPS = 1e-5
 RED_SLICES = _lib.DEFINES["SVNET_RED_SLICES"]          # slices of the fused backward preludes' batch sums
@@ -24,26 +29,6 @@ TAP = None
 
 
 # ----------------------------------------------------------------------------- helpers
-
-def _p(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _hip(*tensors):
-    for t in tensors:
-        if t is not None and not t.is_cuda:
-            raise RuntimeError("svnet_amd: expected a HIP (cuda) tensor, got %s — the product path has no CPU fallback" % t.device)
-
-
-def _f32c(t):
-    if t.dtype != torch.float32:
-        raise TypeError("svnet_amd: expected float32, got %s" % t.dtype)
-    return t if t.is_contiguous() else t.contiguous()
-
 
 def gemm(M, N, K, B, b_rs, b_cs, C, ldc, A=None, a_rs=0, a_cs=0, a_scale=None, a_planes=None, b_exact=False, c_cs=1,
          alpha=1.0, col_scale=None, bias=None, mask=None, col_sum=None, split_k=0, accumulate=False, tern_tile_mask=0):
@@ -121,7 +106,7 @@ def _block_post(block, B, N, k, Os, Ov, gate_sum, Wg0, Wg0c, Wg2c, hi, lo, slot_
                 g2, b2, rm2, rv2, training, nbt1, nbt2):
     """Everything behind the edge pass of a fused level (block: "edgeblock" / "xyzblock"; csrc/block_post.h): BatchNorm coefficients of
     both sets with the gate MLP beside them (sv_layers.py:156-161,179-183: one workgroup per cloud, on the mean edge scalar gate_sum),
-    the apply pass on the pooled extrema hi / lo and mv / mvn, its concatenation slices (_SINK) and, inside knn_table_ahead, the table
+    the apply pass on the pooled extrema hi / lo and mv / mvn, its concatenation slices (STEP.sink) and, inside knn_table_ahead, the table
     of the next k-NN - ONE launch (svnet_*_tail_f32) where the switch and the shape allow it, else coefficients + apply.
     sc1: the pre-BN scale of the edge block's integer scalars (None for xyz).  Returns coef, gate, h, gin, s_out, v_out, s_view, v_view."""
     P, E = B * N, B * N * k
@@ -138,7 +123,7 @@ def _block_post(block, B, N, k, Os, Ov, gate_sum, Wg0, Wg0c, Wg2c, hi, lo, slot_
     coef = torch.empty((4 * Os + 4 * Ov,), **f32)
     s_out = torch.empty((B, N, Os), **f32)
     v_out = torch.empty((B, N, 3, Ov), **f32)
-    slot = _SINK.slot(B, N, Os, Ov, dev) if _SINK is not None else None
+    slot = STEP.sink.slot(B, N, Os, Ov, dev) if STEP.sink is not None else None
     kws = knn_table_ahead.workspace(B, N, Os, Ov, dev)
     cat = slot if slot is not None else (None, 0, None, 0)
     if config.FUSE_BLOCK_TAIL and _lib.lib().svnet_block_tail_supported(P, N, Os, Ov, 1 if kws is not None else 0):
@@ -165,9 +150,9 @@ def _block_post(block, B, N, k, Os, Ov, gate_sum, Wg0, Wg0c, Wg2c, hi, lo, slot_
         else:
             call("svnet_%s_apply_f32" % block, *apply, _stream())
     if kws is not None:
-        knn_table_ahead.table = (s_out.data_ptr(), v_out.data_ptr(), kws, B, N, Os + 3 * Ov)
+        STEP.knn_table = (s_out.data_ptr(), v_out.data_ptr(), kws, B, N, Os + 3 * Ov)
     _tap_act(Wg0, 2, h)
-    s_view, v_view = _SINK.wrote(s_out, v_out) if slot is not None else (None, None)
+    s_view, v_view = STEP.sink.wrote(s_out, v_out) if slot is not None else (None, None)
     if TAP is not None:      # the pooled slot: BatchNorm + LeakyReLU is increasing (slope coef[o] >= 0: max_k) or decreasing (min_k)
         TAP["pools"].append(torch.where(coef[:Os].view(1, Os) >= 0, slot_max, slot_min))
     return coef, gate, h, gin, s_out, v_out, s_view, v_view
@@ -179,7 +164,6 @@ class knn_table_ahead:
     critical path and its first kernel only re-read, squared and transposed those rows), and knn_sv on exactly those tensors skips
     its preparation.  Anything else - other tensors, a shape the fused producer does not take - runs the plain path."""
     active = 0
-    table = None                            # (s.data_ptr(), v.data_ptr(), workspace, B, N, C) of the last prepared level
 
     def __enter__(self):
         knn_table_ahead.active += 1
@@ -201,7 +185,7 @@ class knn_table_ahead:
 
     @staticmethod
     def take(s, v):
-        t, knn_table_ahead.table = knn_table_ahead.table, None
+        t, STEP.knn_table = STEP.knn_table, None
         if t is None or t[0] != s.data_ptr() or t[1] != v.data_ptr() or t[3:] != (s.shape[0], s.shape[1], s.shape[2] + 3 * v.shape[-1]):
             return None
         return t[2]
@@ -323,248 +307,10 @@ def _binweight_grad(GX, W, sc, O, K, training, gx_sliced=False, sum_buf=None, su
     return dW, dsc
 
 
-class _ZeroArena:
-    """Zero-filled scratch of ONE training / inference step from a single fill: every accumulator of the step (BatchNorm sums,
-    atomically accumulated gradients, ...) is a slice of one persistent buffer that `begin()` clears with one launch.  The slices
-    are handed out in call order (a bump allocator), so a step that repeats asks for the same slices; what lies beyond the extent
-    cleared at `begin()` (first step, a larger shape) falls back to torch.zeros and enlarges the extent for the next step.
-    Slices stay valid until the next begin() - long enough for gradients, which the bucket copies before that.
-    Every TrainStep / ForwardStep owns ITS arena (svnet_amd.train), and a step captured into a HIP graph pins it: the graph has
-    the buffer's addresses baked in (the fill and every accumulator slice), so the buffer is never replaced afterwards and lives
-    as long as the step object - another step, model or batch size cannot free or outgrow it under the graph's feet.
-    Outside begin()/end() (tests calling single ops, ...) nothing is pooled."""
-
-    def __init__(self):
-        self.buf, self.zeroed, self.off, self.active, self.pinned = None, 0, 0, False, False
-
-    def begin(self, dev, pin=False):
-        need = (self.off + 4095) // 4096 * 4096
-        if need and not self.pinned and (self.buf is None or self.buf.numel() < need or self.buf.device != torch.device(dev)):
-            self.buf = torch.empty((need + need // 4 + (1 << 20),), dtype=torch.uint8, device=dev)
-        self.zeroed = min(need, self.buf.numel()) if self.buf is not None else 0      # (pinned and outgrown: the rest comes from torch.zeros)
-        if self.zeroed:
-            self.buf[:self.zeroed].zero_()
-        self.off, self.active = 0, True
-        self.pinned = self.pinned or pin
-
-    def end(self):
-        self.active = False
-
-    def take(self, nbytes, dev):
-        if not self.active:
-            return None
-        o = self.off
-        self.off += (nbytes + 255) // 256 * 256
-        if self.buf is not None and self.off <= self.zeroed and self.buf.device == torch.device(dev):
-            return self.buf[o:o + nbytes]
-        return None
-
-
-_DEFAULT_ARENA = _ZeroArena()
-ARENA = _DEFAULT_ARENA          # the arena of the step that is running (begin_step / end_step)
-
-
-def _zeros(shape, dtype, dev):
-    n = 1
-    for d in shape:
-        n *= int(d)
-    nbytes = n * torch.empty((), dtype=dtype).element_size()
-    buf = ARENA.take(nbytes, dev) if nbytes else None
-    if buf is None:
-        return torch.zeros(tuple(shape), dtype=dtype, device=dev)
-    return buf.view(dtype).view(tuple(shape))
-
-
-def _zeros_pool(dev, *specs):
-    """One zero-filled allocation (one fill launch, none inside a step: _ZeroArena) carved into tensors: specs are (shape, dtype) pairs."""
-    offs, total = [], 0
-    for shape, dtype in specs:
-        n = 1
-        for d in shape:
-            n *= int(d)
-        nbytes = n * torch.empty((), dtype=dtype).element_size()
-        offs.append((total, nbytes))
-        total += (nbytes + 255) // 256 * 256
-    buf = ARENA.take(max(total, 1), dev)
-    if buf is None:
-        buf = torch.zeros((max(total, 1),), dtype=torch.uint8, device=dev)
-    return [buf[o:o + nb].view(dtype).view(shape) for (o, nb), (shape, dtype) in zip(offs, specs)]
-
-
 def _sliced_len(L):
     """SVNET_SLICED_LEN(L) (include/svnet_hip.h): [L result | RED_SLICES x L slices | arrival counter] - the zero-filled accumulator the
     grid-wide reductions add to; consumers read the first L elements."""
     return (RED_SLICES + 1) * L + 2
-
-
-class _PlaneCache:
-    """Packed forms of the binarized weights (sign / non-zero bit planes, +-1 values, scale*sign, the fused edge kernels' permuted
-    planes and MFMA-fragment sign weights): sv_layers.py:44-48 re-derives sign(W) inside every forward; here a packed form is
-    rebuilt only when its parameters CHANGED since it was packed - autograd's version counter (torch.optim steps, load_state_dict,
-    in-place ops under no_grad) or the data address (re-homing into a flat buffer); writers that bypass both (the flat optimizer
-    kernels of svnet_amd.train, anything going through .data or a raw pointer) call invalidate().  An eager step rebuilds the
-    stale forms for all layers together on the side stream at its start (begin()), off the forward's critical path; a step
-    replayed as a captured graph keeps the packing OUTSIDE the graph (begin(external=True) while capturing, refresh() before
-    every replay).  Entries are created lazily the first time a layer asks (built inline that once).  Keys are the Parameter
-    objects; the rebuild closures read their CURRENT data.  Outside begin()/end() every layer packs on the fly."""
-
-    def __init__(self):
-        self.entries, self.active, self.event, self.waited = {}, False, None, None      # waited: ids of the streams that have joined
-        self.sig, self.dirty = {}, False        # (version counter, address) of every entry's parameters at its last (re)build
-
-    @staticmethod
-    def _signature(params):
-        return tuple((p._version, p.data_ptr()) for p in params)
-
-    def invalidate(self):
-        """The weights were changed behind autograd's back (a raw kernel on a flat parameter buffer: svnet_amd.train's optimizers call
-        this; so must anything else that writes through .data or a raw pointer): rebuild everything at the next step."""
-        self.dirty = True
-
-    def _stale(self):
-        """Entries whose parameters changed since they were packed (autograd version counter or address), or all after invalidate()."""
-        out = []
-        for key in list(self.entries):
-            refs, _, rebuild = self.entries[key]
-            ps = [r() for r in refs]
-            if any(p is None for p in ps):
-                del self.entries[key]                 # the parameters are gone (another model was built)
-                self.sig.pop(key, None)
-            elif self.dirty or self.sig.get(key) != self._signature(ps):
-                out.append((key, ps, rebuild))
-        return out
-
-    def refresh(self, dev):
-        """Re-pack what is stale, on the CURRENT stream.  For a step that is replayed as a captured graph (the packing launches are
-        not part of the graph: they depend on whether an optimizer ran in between) - svnet_amd.train calls it before every replay."""
-        for key, ps, rebuild in self._stale():
-            rebuild()
-            self.sig[key] = self._signature(ps)
-        self.dirty = False
-
-    def rebuild_all(self, run=None):
-        """Every live entry re-packed now, whatever its state (run(rebuild) issues one; default: on the current stream) - what a
-        captured optimizer step records behind its update kernel (svnet_amd.train).  Returns the entries' keys."""
-        keys = []
-        for key in list(self.entries):
-            refs, _, rebuild = self.entries[key]
-            if any(r() is None for r in refs):
-                continue
-            (run or (lambda f: f()))(rebuild)
-            keys.append(key)
-        return keys
-
-    def mark_fresh(self, keys):
-        """The given entries have just been re-packed from the parameters' current values by someone else (a replayed graph)."""
-        for key in keys:
-            e = self.entries.get(key)
-            if e is not None:
-                ps = [r() for r in e[0]]
-                if all(p is not None for p in ps):
-                    self.sig[key] = self._signature(ps)
-
-    def _join(self):
-        if self.waited is not None:
-            st = torch.cuda.current_stream()
-            if st.cuda_stream not in self.waited:
-                st.wait_event(self.event)
-                self.waited.add(st.cuda_stream)
-
-    def begin(self, dev, external=False):
-        """external: the step is being captured into a graph - its packed forms are kept fresh by refresh() before every replay."""
-        self.active, self.waited = True, None
-        if external:
-            return
-        stale = self._stale()
-        if stale:
-            main, side = torch.cuda.current_stream(dev), _side_stream(dev)
-            side.wait_stream(main)
-            with torch.cuda.stream(side):
-                for key, ps, rebuild in stale:
-                    rebuild()
-                    self.sig[key] = self._signature(ps)
-                self.event = side.record_event()
-            self.waited = {side.cuda_stream}
-        self.dirty = False
-
-    def end(self):
-        if self.active:                          # (also when nothing looked anything up: graph capture needs the side stream joined)
-            self._join()
-        self.active = False
-
-    def get(self, kind, params, build):
-        """build() -> (outputs, rebuild): packs now; rebuild() re-packs into the same output tensors."""
-        if not self.active:
-            return build()[0]
-        key = (kind,) + tuple(id(p) for p in params)
-        e = self.entries.get(key)
-        if e is not None and all(r() is p for r, p in zip(e[0], params)):
-            self._join()
-            return e[1]
-        import weakref
-        out, rebuild = build()
-        self.entries[key] = (tuple(weakref.ref(p) for p in params), out, rebuild)
-        self.sig[key] = self._signature(params)
-        return out
-
-
-PLANES = _PlaneCache()
-
-
-def begin_step(dev, planes_external=False, arena=None):
-    """Start of a train / inference step (svnet_amd.train): one fill for the step's zero-initialised scratch (`arena`: the step
-    object's own _ZeroArena; `planes_external` = the step is being captured into a HIP graph, which also pins the arena), and the
-    packed weight forms of the layers whose weights changed since they were last packed rebuilt on the side stream."""
-    global ARENA
-    ARENA = arena if arena is not None else _DEFAULT_ARENA
-    ARENA.begin(dev, pin=planes_external)
-    PLANES.begin(dev, planes_external)
-
-
-def end_step():
-    global ARENA, _FUSED_COLSUMS
-    knn_table_ahead.table = None                          # (a prepared k-NN table nobody asked for is not held across steps)
-    _FUSED_COLSUMS = None                                 # (the producer's [M, O] output and its arena slice are not held across steps)
-    ARENA.end()
-    ARENA = _DEFAULT_ARENA
-    PLANES.end()
-    DEFERRED.active = False
-    DEFERRED.keep.clear()
-    DEFERRED.seen.clear()
-
-
-class _Deferred:
-    """Weight-gradient work that nothing in the backward pass waits for (svnet_amd.train.TrainStep only: it gathers the parameter
-    gradients ONCE, after the backward).  While `active`, a fused edge layer's backward leaves its weight-gradient chain (linear1's
-    product, linear2's, the parameter epilogue) on the side stream WITHOUT joining it into the main stream, which goes on with the next
-    layer's backward; `join()` (called before the gradients are packed) is the one join.  `keep` holds every tensor those kernels
-    touch until then: the caching allocator would otherwise hand their blocks - freed when the backward function returns - to the
-    main stream's next allocation while the side stream still reads them.  Off (plain autograd use of the layers): every backward
-    joins before it returns, as before."""
-
-    def __init__(self):
-        self.active = False
-        self.keep = []
-        self.seen = set()
-
-    def first_use(self, *params):
-        """True while none of `params` (a layer's weights) has been handed an unwritten gradient in this backward.  A module applied
-        twice in one forward - or one parameter read by two Functions - gets two gradients, which autograd ADDS on the main stream:
-        the second backward must therefore take the joined schedule (its final join also covers the first, deferred chain).  This is
-        the run-time half of TrainStep._deferral_is_safe(), which can only see parameters registered under two names."""
-        keys = [p.data_ptr() for p in params if p is not None]
-        dup = any(k in self.seen for k in keys)
-        self.seen.update(keys)
-        return not dup
-
-    def join(self, dev):
-        if self.keep:
-            torch.cuda.current_stream(dev).wait_stream(_side_stream(dev))
-            self.keep.clear()
-        self.seen.clear()
-
-
-DEFERRED = _Deferred()
 
 
 class defer_rows_wgrad:
@@ -656,7 +402,6 @@ class BinLinear(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, W, beta, scale, bias, training=True):
-        global _FUSED_COLSUMS
         _hip(x, W, beta, scale, bias)
         ctx.training = bool(training)
         x2 = _f32c(x).reshape(-1, x.shape[-1])
@@ -681,9 +426,9 @@ class BinLinear(torch.autograd.Function):
             sums = _zeros((_sliced_len(2 * O),), torch.float64, dev) if (training and config.FUSE_BN_STATS and K <= 46340) else None
             call("svnet_binlinear_i8_fwd_f32", _p(x2), K, _p(bt), _p(packed["w_i8"]), _p(sc), _p(bias), M, K, O, _p(y),
                  _p(planes[0]), _p(planes[1]), _p(planes[2]), _p(sums), _stream())
-            _FUSED_COLSUMS = (y, y._version, sums) if sums is not None else None
+            STEP.fused_colsums = (y, y._version, sums) if sums is not None else None
         else:
-            _FUSED_COLSUMS = None                         # (a stale record would keep the previous producer's output alive)
+            STEP.fused_colsums = None                     # (a stale record would keep the previous producer's output alive)
             call("svnet_binlinear_fwd_f32", _p(x2), K, _p(bt), _p(w_sign), _p(w_nz), _p(sc), _p(bias), M, K, O, _p(y),
                  _p(planes[0]), _p(planes[1]), _p(planes[2]), _stream())
         if TAP is not None:
@@ -806,7 +551,6 @@ class BinLinearCloud(torch.autograd.Function):
     def forward(ctx, x_cloud, x_point, W, beta, scale, training=True, cloud_at=0):
         """cloud_at: first column of the per-cloud block in the layer's row (0: sv_dgcnn_partseg's conv8, whose per-cloud features come first;
         512: conv_fuse.linear1 of sv_pointnet_cls, cat[s, expand(pooled s), Vector2Scalar(v)]); the per-point columns keep their order."""
-        global _FUSED_COLSUMS
         _hip(x_cloud, x_point, W, beta, scale)
         ctx.training = bool(training)
         B, N, Kp = x_point.shape
@@ -838,7 +582,7 @@ class BinLinearCloud(torch.autograd.Function):
         sums = _zeros((_sliced_len(2 * O),), torch.float64, dev) if (training and config.FUSE_BN_STATS and K <= 46340) else None
         call("svnet_binlinear_i8_cloud_fwd_f32", _p(xp), Kp, _p(bt_p), _p(pk_p["w_i8"]), _p(sc), None, M, Kp, O, _p(y),
              _p(pl_p[0]), _p(pl_p[1]), _p(pl_p[2]), _p(sums), _p(n_cloud), N, _stream())
-        _FUSED_COLSUMS = (y, y._version, sums) if sums is not None else None
+        STEP.fused_colsums = (y, y._version, sums) if sums is not None else None
         if TAP is not None:      # the planes of the full [M, K] rows, as the layer over the materialised concatenation would have recorded them
             full = [torch.cat([b[:, :k0], a, b[:, k0:]], dim=1).contiguous() for a, b in zip(_cloud_planes_as_rows(pl_c, B, N, Kc), pl_p)]
             TAP["signs"].append(("rows", M, K, full))
@@ -1151,19 +895,13 @@ class VProject(torch.autograd.Function):
 
 # ----------------------------------------------------------------------------- normalisation
 
-# Column sums a producer left for the BatchNorm over its output: (the [M, C] tensor itself - held, so that its memory cannot be handed to
-# another tensor while the record lives -, its version at the time, sums [2C] double).  Consumed once; any later producer replaces it.
-_FUSED_COLSUMS = None
-
-
 def _batch_stats(x, M, C, kind, running_mean, running_var, training, momentum, eps, nbt=None):
-    global _FUSED_COLSUMS
     L = _lib.lib()
     dev = x.device
     mean = torch.empty((C,), dtype=torch.float32, device=dev)
     invstd = torch.empty((C,), dtype=torch.float32, device=dev)
     if training:
-        rec, _FUSED_COLSUMS = _FUSED_COLSUMS, None
+        rec, STEP.fused_colsums = STEP.fused_colsums, None
         if (kind == 0 and rec is not None and rec[0].data_ptr() == x.data_ptr() and tuple(rec[0].shape) == (M, C)
                 and rec[0]._version == rec[1] and x.is_contiguous()):
             sums = rec[2]                                       # the producing kernel's sums (exact integer counts, svnet_binlinear_i8_fwd_f32)
@@ -1770,25 +1508,6 @@ class GateMLPRows(torch.autograd.Function):
         return ds, dW0, dW2
 
 
-class _UnitGrad:
-    """One cached scalar 1.0 per device: a train step seeds its backward with it (`torch.autograd.backward(loss, UNIT_GRAD.get(dev))`)
-    instead of `loss.backward()`'s fresh ones_like, and SmoothCE.backward recognises it BY IDENTITY - the fill kernel and the
-    multiplication by one were two launches (~10 us) on the critical path between the forward and the backward."""
-
-    def __init__(self):
-        self.t = {}
-
-    def get(self, dev):
-        dev = torch.device(dev)
-        key = (dev.type, dev.index if dev.index is not None else (torch.cuda.current_device() if dev.type == "cuda" else 0))
-        if key not in self.t:
-            self.t[key] = torch.ones((), dtype=torch.float32, device=dev)
-        return self.t[key]
-
-
-UNIT_GRAD = _UnitGrad()
-
-
 def _scale_saved_grad(dlog, g):
     """A loss's saved gradient times the upstream `g`; the step's own seed (train.TrainStep: the cached 1.0, known by identity) hands
     `dlog` back untouched."""
@@ -1903,13 +1622,11 @@ class CatSink:
         self.prev = None
 
     def __enter__(self):
-        global _SINK
-        self.prev, _SINK = _SINK, self
+        self.prev, STEP.sink = STEP.sink, self
         return self
 
     def __exit__(self, *exc):
-        global _SINK
-        _SINK = self.prev
+        STEP.sink = self.prev
 
     def slot(self, B, N, Os, Ov, dev):
         """(s_ptr, s_ld, v_ptr, v_ld) of the next slice if it is (Os, Ov) wide, else None (and the sink is abandoned)."""
@@ -1952,9 +1669,6 @@ class CatSink:
         # source next to the gradient of the pooled output the next layer consumed - no strided add / copy kernels in between
         flat = [t for vw in self.views for t in vw]
         return _CatFilled.apply(self.s, self.v, len(levels), *flat)
-
-
-_SINK = None
 
 
 class _CatFilled(torch.autograd.Function):
@@ -2342,19 +2056,6 @@ class XyzBlock(torch.autograd.Function):
         dWz = gw[o + Ov * NC + NG:o + Ov * NC + 2 * NG].view(3, NC)
         # forward args: x, idx, k, training, W0, Wz, W1, g1, b1, rm1, rv1, W2, g2, b2, rm2, rv2, Wg0, Wg2
         return (None, None, None, None, dW0, dWz, dW1, dg1, db1, None, None, dW2, dg2, db2, None, None, dWg0, dWg2, None, None)
-
-
-_SIDE_STREAMS = {}
-
-
-def _side_stream(dev):
-    """One extra HIP stream per device for independent kernels of a fused backward (forked / joined with events, so the
-    pattern is also valid inside a hipGraph capture)."""
-    key = torch.device(dev).index if torch.device(dev).index is not None else torch.cuda.current_device()
-    if key not in _SIDE_STREAMS:
-        # (a high-priority side stream was measured: 10.7 ms per step against 6.4 - the tile kernel on the main stream starves)
-        _SIDE_STREAMS[key] = torch.cuda.Stream(device=key, priority=0)
-    return _SIDE_STREAMS[key]
 
 
 _PERM_CACHE = {}

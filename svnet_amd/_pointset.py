@@ -2,20 +2,20 @@
 propagation (svnet_amd/propagate.py), ball query and grouping (svnet_amd/group.py).  Private: the public names live in those modules.
 The device side of the same contract - the distance all three use, the LDS tile, the launch geometry - is svnet_amd/csrc/pointset.h.
 
-Here: the argument checks in the order every entry point applies them (tensors, then shapes, then - by _ops._hip - the HIP device,
+Here: the argument checks in the order every entry point applies them (tensors, then shapes, then - by _call.hip - the HIP device,
 then the kernels' limits), the device refusal of the classes that allocate, the row gather, the one launch of the sampler, and the
 reverse lists both backwards sum over (svnet_amd/csrc/pointset_grad.hip).
 """
 import torch
 
-from . import _lib, _ops
+from . import _call, _lib
 
 MAX_N = 32768       # SVNET_KNN_MAX_N (svnet_amd/csrc/common.h), for the messages: the library's *_supported queries are the check
 
 
 def check_tensors(name, tensors, dtypes, what, grad=()):
     """tensors: {argument name: tensor}; the type, dtype, device-match, contiguity and gradient checks shared by the entry points
-    (the HIP device itself is checked after the shapes, by _ops._hip).  `what` names the operation: "the grouping".  `grad` names
+    (the HIP device itself is checked after the shapes, by _call.hip).  `what` names the operation: "the grouping".  `grad` names
     the arguments that may require grad - the data tensors whose backward exists, on a HIP device; coordinates, weights and indices
     never may.  Returns whether one of them does."""
     for k, t in tensors.items():
@@ -88,7 +88,7 @@ def fps_launch(xyz, B, P, npoint, start, idx):
     """The sampler on the current stream: xyz [B,P,3], start [B] int64 -> idx [B,npoint] int64 (given).  No host read: capturable.
     A start outside 0 .. P-1 is clamped into the cloud by the kernel; callers that refuse it check before."""
     with torch.cuda.device(xyz.device):
-        _lib.call("svnet_fps_f32", _ops._p(xyz), B, P, npoint, _ops._p(start), _ops._p(idx), _ops._stream())
+        _lib.call("svnet_fps_f32", _call.p(xyz), B, P, npoint, _call.p(start), _call.p(idx), _call.stream())
 
 
 def reverse_supported(name, R, K, N):
@@ -118,5 +118,5 @@ def reverse_lists(idx, N):
     rev_start = torch.empty(B, N + 1, dtype=torch.int32, device=idx.device)
     rev_edge = torch.empty(B, R * K, dtype=torch.int32, device=idx.device)
     with torch.cuda.device(idx.device):
-        _lib.call("svnet_pointset_reverse_i32", _ops._p(idx), B, R, K, N, _ops._p(rev_start), _ops._p(rev_edge), _ops._stream())
+        _lib.call("svnet_pointset_reverse_i32", _call.p(idx), B, R, K, N, _call.p(rev_start), _call.p(rev_edge), _call.stream())
     return rev_start, rev_edge

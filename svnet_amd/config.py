@@ -52,7 +52,7 @@ SPLIT_BROADCAST = True
 # (csrc/head.hip) instead of ~12 launch-bound kernels per layer.
 FUSE_HEAD = True
 # TrainStep: the fused edge layers' weight-gradient chains stay on the side stream until the one join before the gradients are packed
-# (svnet_amd._ops._Deferred); False = every backward joins before it returns
+# (svnet_amd._step._Deferred); False = every backward joins before it returns
 DEFER_WGRAD = True
 # ... and so do the weight-gradient chains of the big rows layers (conv5.linear1 of the classifier: 111 + 11 us at the tail of the side
 # stream instead of in front of the launch-bound end of conv5's backward): 4.29 -> 4.23 ms (profiles/r05_ab_defer_rows.log).  Opt-in per

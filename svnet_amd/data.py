@@ -88,7 +88,7 @@ import ctypes
 import numpy as np
 import torch
 
-from . import _lib, _ops, _pointset, synth
+from . import _call, _lib, _pointset, synth
 
 SELECT_MODES = {m: _lib.DEFINES["SVNET_BATCH_" + m.upper()] for m in ("first_shuffled", "subset", "first_ordered")}
 MAX_ATTR = _lib.DEFINES["SVNET_BATCH_MAX_ATTR"]
@@ -134,7 +134,7 @@ def farthest_point_sample(xyz, npoint, start):
     range is checked with one device reduction and one synchronisation before the launch."""
     if not isinstance(xyz, torch.Tensor) or not isinstance(start, torch.Tensor):
         raise TypeError("farthest_point_sample: xyz and start must be tensors")
-    _ops._hip(xyz, start)
+    _call.hip(xyz, start)
     if xyz.dtype != torch.float32 or start.dtype != torch.int64:
         raise TypeError("farthest_point_sample: xyz must be float32 and start int64, got %s and %s" % (xyz.dtype, start.dtype))
     B, P = _pointset.check_cloud("farthest_point_sample", "xyz", xyz, "P")
@@ -215,11 +215,11 @@ class DevicePool:
         new.attr = None if self.attr is None else torch.empty(self.M, N, self.A, dtype=torch.float32, device=self.device)
         new.fps_index = idx
         with torch.cuda.device(self.device):
-            _lib.call("svnet_pool_gather_f32", _ops._p(self.data), _ops._p(self.seg), _ops._p(idx), self.M, self.P, N,
-                      int(bool(normalize)), _ops._p(new.data), _ops._p(new.seg), _ops._stream())
+            _lib.call("svnet_pool_gather_f32", _call.p(self.data), _call.p(self.seg), _call.p(idx), self.M, self.P, N,
+                      int(bool(normalize)), _call.p(new.data), _call.p(new.seg), _call.stream())
             if self.attr is not None:
-                _lib.call("svnet_pool_gather_attr_f32", _ops._p(self.attr), _ops._p(idx), self.M, self.P, N, self.A, _ops._p(new.attr),
-                          _ops._stream())
+                _lib.call("svnet_pool_gather_attr_f32", _call.p(self.attr), _call.p(idx), self.M, self.P, N, self.A, _call.p(new.attr),
+                          _call.stream())
         return new
 
     def source_points(self, source_pool):
@@ -268,7 +268,7 @@ class BatchLoader:
                  rank=0, world=1, num_cat=None):
         if not isinstance(pool, DevicePool):
             raise TypeError("BatchLoader: pool must be a DevicePool")
-        _ops._hip(pool.data, pool.label, pool.seg, pool.attr)
+        _call.hip(pool.data, pool.label, pool.seg, pool.attr)
         if select not in SELECT_MODES:
             raise ValueError("BatchLoader: select must be one of %r" % sorted(SELECT_MODES))
         if rotate not in ROTATE_MODES:
@@ -300,13 +300,13 @@ class BatchLoader:
         self.epoch = None
         self._desc = _lib.BatchDesc()
         d = self._desc
-        d.data, d.label, d.seg, d.order = _ops._p(pool.data), _ops._p(pool.label), _ops._p(pool.seg), _ops._p(self.order)
+        d.data, d.label, d.seg, d.order = _call.p(pool.data), _call.p(pool.label), _call.p(pool.seg), _call.p(self.order)
         d.M, d.P, d.L, d.B, d.N = pool.M, pool.P, pool.M, B, N
         d.seed = self.seed
         d.select_mode, d.scale_shift, d.rotate = self.select_mode, self.scale_shift, self.rotate
         d.num_cat = self.num_cat or 0
-        d.x, d.y, d.seg_out, d.onehot, d.params = _ops._p(self.x), _ops._p(self.y), _ops._p(self.seg), _ops._p(self.onehot), _ops._p(self.params)
-        d.attr, d.A, d.attr_vectors, d.attr_out = _ops._p(pool.attr), pool.A, pool.attr_vectors, _ops._p(self.points)
+        d.x, d.y, d.seg_out, d.onehot, d.params = _call.p(self.x), _call.p(self.y), _call.p(self.seg), _call.p(self.onehot), _call.p(self.params)
+        d.attr, d.A, d.attr_vectors, d.attr_out = _call.p(pool.attr), pool.A, pool.attr_vectors, _call.p(self.points)
         self.set_epoch(0)
 
     def set_epoch(self, epoch):
@@ -333,5 +333,5 @@ class BatchLoader:
         if count == 0:
             return 0
         self._desc.first, self._desc.count = first, count
-        _lib.call("svnet_batch_assemble_f32", ctypes.byref(self._desc), _ops._stream())
+        _lib.call("svnet_batch_assemble_f32", ctypes.byref(self._desc), _call.stream())
         return count

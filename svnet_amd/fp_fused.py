@@ -32,7 +32,7 @@ require grad.  There is no CPU fallback: tensors that are not on a HIP device ra
 """
 import torch
 
-from . import _level, _lib, _ops, _pointset
+from . import _call, _level, _lib, _pointset
 from ._level import MAX_LAYERS, fold_level
 from .propagate import _nn_launch
 
@@ -55,8 +55,8 @@ def supported(N, S, D1, D2, widths):
 
 def _launch(idx, weight, points2, points1, level, out, c_off, B, N, S, D1, D2):
     with torch.cuda.device(points2.device):
-        _lib.call("svnet_fp_fused_f32", _ops._p(idx), _ops._p(weight), _ops._p(points2), _ops._p(points1 if D1 else None), B, N, S, D1, D2,
-                  len(level.widths), level._c_widths, level._c_wf, level._c_bf, _ops._p(out), int(out.shape[1]), c_off, _ops._stream())
+        _lib.call("svnet_fp_fused_f32", _call.p(idx), _call.p(weight), _call.p(points2), _call.p(points1 if D1 else None), B, N, S, D1, D2,
+                  len(level.widths), level._c_widths, level._c_wf, level._c_bf, _call.p(out), int(out.shape[1]), c_off, _call.stream())
 
 
 def interp_mlp(idx, weight, points2, points1, level, out=None, c_off=0):
@@ -79,7 +79,7 @@ def interp_mlp(idx, weight, points2, points1, level, out=None, c_off=0):
         D1 = int(points1.shape[1])
     _level.check_c_in(name, level, D1 + D2, "points1 and points2 give %d + %d" % (D1, D2))
     c_off = _level.check_window(name, out, c_off, level, B, N, "N")
-    _ops._hip(points2, idx, weight, points1, out)
+    _call.hip(points2, idx, weight, points1, out)
     _level.check_device(name, level, "points2", points2)
     if not supported(N, S, D1, D2, level.widths):
         raise _lib.SvnetHipError("%s: N = %d, S = %d, D1 = %d, D2 = %d, widths %s is not supported (N >= 1, 1 <= S <= %d, D2 >= 1, D1 + D2 <= %d, "
@@ -115,7 +115,7 @@ class FusedFeaturePropagation(_level.FusedWrapper):
     def __call__(self, xyz1, xyz2, points1, points2):
         name = self._begin(_WHAT, {"xyz1": (xyz1, _F32), "xyz2": (xyz2, _F32), "points2": (points2, _F32)}, {"points1": (points1, _F32)})
         B, N, S, D1, D2 = _level.cloud_pair_shapes(name, xyz1, xyz2, points1, points2)
-        _ops._hip(xyz1, xyz2, points1, points2)
+        _call.hip(xyz1, xyz2, points1, points2)
         if not self.supported(N, S, D1, D2):
             return self.module(xyz1, xyz2, points1, points2)
         dev = xyz1.device

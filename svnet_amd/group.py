@@ -77,7 +77,7 @@ Multi-scale grouping (the reference's PointNetSetAbstractionMsg.forward, lines 2
 import numpy as np
 import torch
 
-from . import _lib, _ops, _pointset
+from . import _call, _lib, _pointset
 from .data import fps_start
 
 _WHAT = "the grouping"          # in the messages of _pointset.check_tensors
@@ -118,13 +118,13 @@ def _points_shape(name, points, B, N):
 
 def _query_launch(xyz, new_xyz, B, N, S, r2, nsample, idx, count):
     with torch.cuda.device(xyz.device):
-        _lib.call("svnet_ball_query_f32", _ops._p(xyz), _ops._p(new_xyz), B, N, S, r2, nsample, _ops._p(idx), _ops._p(count), _ops._stream())
+        _lib.call("svnet_ball_query_f32", _call.p(xyz), _call.p(new_xyz), B, N, S, r2, nsample, _call.p(idx), _call.p(count), _call.stream())
 
 
 def _group_launch(xyz, new_xyz, points, idx, B, N, S, nsample, D, out):
     with torch.cuda.device(xyz.device):
-        _lib.call("svnet_group_points_f32", _ops._p(xyz), _ops._p(new_xyz), _ops._p(points if D else None), _ops._p(idx), B, N, S, nsample, D,
-                  _ops._p(out), _ops._stream())
+        _lib.call("svnet_group_points_f32", _call.p(xyz), _call.p(new_xyz), _call.p(points if D else None), _call.p(idx), B, N, S, nsample, D,
+                  _call.p(out), _call.stream())
 
 
 def _sample_centres(name, xyz, B, N, S, start, seed=0):
@@ -159,7 +159,7 @@ def query_ball_point(radius, nsample, xyz, new_xyz, return_count=False):
     _pointset.check_tensors("query_ball_point", {"xyz": xyz, "new_xyz": new_xyz}, (torch.float32, torch.float32), _WHAT)
     B, N, S = _cloud_shapes("query_ball_point", xyz, new_xyz)
     nsample = int(nsample)
-    _ops._hip(xyz, new_xyz)
+    _call.hip(xyz, new_xyz)
     _supported("query_ball_point", N, S, nsample, 0)
     idx = torch.empty(B, S, nsample, dtype=torch.int64, device=xyz.device)
     count = torch.empty(B, S, dtype=torch.int32, device=xyz.device)
@@ -202,7 +202,7 @@ def group_points(xyz, new_xyz, idx, points=None, out=None):
     of every group's points followed by their attributes (module docstring).  An index outside [0, N) is clamped into it.  One
     launch, no host read; `out` lets a caller keep a fixed buffer.  points may require grad (module docstring); the rest may not."""
     B, N, S, nsample, D = _group_args("group_points", xyz, new_xyz, idx, points)
-    _ops._hip(xyz, new_xyz, idx, points)
+    _call.hip(xyz, new_xyz, idx, points)
     _supported("group_points", N, S, nsample, D)
     if D and points.requires_grad:
         if out is not None:
@@ -225,7 +225,7 @@ def group_points_backward(dgrouped, idx, N, out=None):
         raise ValueError("group_points_backward: dgrouped must be [B,S,nsample,3+D] with D >= 1 and idx [B,S,nsample], got %s and %s"
                          % (tuple(dgrouped.shape), tuple(idx.shape)))
     B, S, nsample, D, N = int(idx.shape[0]), int(idx.shape[1]), int(idx.shape[2]), int(dgrouped.shape[3]) - 3, int(N)
-    _ops._hip(dgrouped, idx)
+    _call.hip(dgrouped, idx)
     _pointset.reverse_supported("group_points_backward", S, nsample, N)
     if out is None:
         out = torch.empty(B, N, D, dtype=torch.float32, device=dgrouped.device)
@@ -233,8 +233,8 @@ def group_points_backward(dgrouped, idx, N, out=None):
         _pointset.check_out("group_points_backward", {"dgrouped": dgrouped}, out, "[B,N,D]", (B, N, D), _WHAT)
     rev_start, rev_edge = _pointset.reverse_lists(idx, N)
     with torch.cuda.device(dgrouped.device):
-        _lib.call("svnet_group_points_bwd_f32", _ops._p(dgrouped), _ops._p(rev_start), _ops._p(rev_edge), B, N, S, nsample, D, _ops._p(out),
-                  _ops._stream())
+        _lib.call("svnet_group_points_bwd_f32", _call.p(dgrouped), _call.p(rev_start), _call.p(rev_edge), B, N, S, nsample, D, _call.p(out),
+                  _call.stream())
     return out
 
 
@@ -253,7 +253,7 @@ def sample_and_group(npoint, radius, nsample, xyz, points, returnfps=False, star
     B, N = _pointset.check_cloud("sample_and_group", "xyz", xyz, "N")
     S, nsample = int(npoint), int(nsample)
     D = 0 if points is None else _points_shape("sample_and_group", points, B, N)
-    _ops._hip(xyz, points)
+    _call.hip(xyz, points)
     _pointset.fps_supported("sample_and_group", "N", N, S)
     _supported("sample_and_group", N, S, nsample, D)
     new_xyz, fps_idx = _sample_centres("sample_and_group", xyz, B, N, S, start, seed)
@@ -297,13 +297,13 @@ def _supported_msg(name, N, S, R, c_nsample, nsamples, D):
 
 def _four(tensors):
     """The pointers of up to four tensors, None past them: the out0 .. out3 / dg0 .. dg3 arguments of the C entry points."""
-    return [_ops._p(t) for t in tensors] + [None] * (MAX_SCALES - len(tensors))
+    return [_call.p(t) for t in tensors] + [None] * (MAX_SCALES - len(tensors))
 
 
 def _query_msg_launch(xyz, new_xyz, B, N, S, R, c_r2, c_nsample, idx, count):
     with torch.cuda.device(xyz.device):
-        _lib.call("svnet_ball_query_msg_f32", _ops._p(xyz), _ops._p(new_xyz), B, N, S, R, c_r2, c_nsample, _ops._p(idx), _ops._p(count),
-                  _ops._stream())
+        _lib.call("svnet_ball_query_msg_f32", _call.p(xyz), _call.p(new_xyz), B, N, S, R, c_r2, c_nsample, _call.p(idx), _call.p(count),
+                  _call.stream())
 
 
 def _group_msg_launch(xyz, new_xyz, points, idx_cat, B, N, S, R, c_nsample, nsamples, D, outs=None):
@@ -311,8 +311,8 @@ def _group_msg_launch(xyz, new_xyz, points, idx_cat, B, N, S, R, c_nsample, nsam
     if outs is None:
         outs = [torch.empty(B, S, k, D + 3, dtype=torch.float32, device=xyz.device) for k in nsamples]
     with torch.cuda.device(xyz.device):
-        _lib.call("svnet_group_points_msg_f32", _ops._p(xyz), _ops._p(new_xyz), _ops._p(points if D else None), _ops._p(idx_cat), B, N, S, R,
-                  c_nsample, D, *_four(outs), _ops._stream())
+        _lib.call("svnet_group_points_msg_f32", _call.p(xyz), _call.p(new_xyz), _call.p(points if D else None), _call.p(idx_cat), B, N, S, R,
+                  c_nsample, D, *_four(outs), _call.stream())
     return tuple(outs)
 
 
@@ -323,7 +323,7 @@ def query_ball_point_msg(radius_list, nsample_list, xyz, new_xyz, return_count=F
     _pointset.check_tensors("query_ball_point_msg", {"xyz": xyz, "new_xyz": new_xyz}, (torch.float32, torch.float32), _WHAT)
     B, N, S = _cloud_shapes("query_ball_point_msg", xyz, new_xyz)
     R, c_r2, c_nsample, nsamples = _scales("query_ball_point_msg", radius_list, nsample_list)
-    _ops._hip(xyz, new_xyz)
+    _call.hip(xyz, new_xyz)
     _supported_msg("query_ball_point_msg", N, S, R, c_nsample, nsamples, 0)
     idx = torch.empty(B, S, sum(nsamples), dtype=torch.int64, device=xyz.device)
     count = torch.empty(B, S, R, dtype=torch.int32, device=xyz.device)
@@ -374,7 +374,7 @@ def group_points_msg(xyz, new_xyz, idx_cat, nsample_list, points=None):
     per scale the attributes of every group's points FOLLOWED BY their centred coordinates (module docstring).  An index outside
     [0, N) is clamped into it.  One launch for all scales, no host read.  points may require grad; the rest may not."""
     B, N, S, R, c_nsample, nsamples, D = _group_msg_args("group_points_msg", xyz, new_xyz, idx_cat, nsample_list, points)
-    _ops._hip(xyz, new_xyz, idx_cat, points)
+    _call.hip(xyz, new_xyz, idx_cat, points)
     _supported_msg("group_points_msg", N, S, R, c_nsample, nsamples, D)
     if D and points.requires_grad:
         return _GroupMsg.apply(points, xyz, new_xyz, idx_cat, nsamples)
@@ -397,7 +397,7 @@ def group_points_msg_backward(dgrouped_list, idx_cat, nsample_list, N, out=None)
         raise ValueError("group_points_msg_backward: dgrouped_list must be [B,S,nsample_i,D+3] with D >= 1 for nsample %s and idx_cat "
                          "[B,S,%d], got %s and %s" % (list(nsamples), sum(nsamples), [tuple(g.shape) for g in dgrouped_list], tuple(idx_cat.shape)))
     B, S, D, N = int(idx_cat.shape[0]), int(idx_cat.shape[1]), W - 3, int(N)
-    _ops._hip(idx_cat, *dgrouped_list)
+    _call.hip(idx_cat, *dgrouped_list)
     _supported_msg("group_points_msg_backward", N, S, R, c_nsample, nsamples, D)
     _pointset.reverse_supported("group_points_msg_backward", S, sum(nsamples), N)
     if out is None:
@@ -406,8 +406,8 @@ def group_points_msg_backward(dgrouped_list, idx_cat, nsample_list, N, out=None)
         _pointset.check_out("group_points_msg_backward", {"dgrouped_0": dgrouped_list[0]}, out, "[B,N,D]", (B, N, D), _WHAT)
     rev_start, rev_edge = _pointset.reverse_lists(idx_cat, N)
     with torch.cuda.device(idx_cat.device):
-        _lib.call("svnet_group_points_msg_bwd_f32", *_four(dgrouped_list), _ops._p(rev_start), _ops._p(rev_edge), B, N, S, R, c_nsample, D,
-                  _ops._p(out), _ops._stream())
+        _lib.call("svnet_group_points_msg_bwd_f32", *_four(dgrouped_list), _call.p(rev_start), _call.p(rev_edge), B, N, S, R, c_nsample, D,
+                  _call.p(out), _call.stream())
     return out
 
 
@@ -425,7 +425,7 @@ def sample_and_group_msg(npoint, radius_list, nsample_list, xyz, points, start=N
     S = int(npoint)
     R, c_r2, c_nsample, nsamples = _scales("sample_and_group_msg", radius_list, nsample_list)
     D = 0 if points is None else _points_shape("sample_and_group_msg", points, B, N)
-    _ops._hip(xyz, points)
+    _call.hip(xyz, points)
     _pointset.fps_supported("sample_and_group_msg", "N", N, S)
     _supported_msg("sample_and_group_msg", N, S, R, c_nsample, nsamples, D)
     new_xyz, _ = _sample_centres("sample_and_group_msg", xyz, B, N, S, start, seed)
@@ -446,7 +446,7 @@ def sample_and_group_all(xyz, points):
     B, N = _pointset.check_cloud("sample_and_group_all", "xyz", xyz, "N")
     if points is not None:
         _points_shape("sample_and_group_all", points, B, N)
-    _ops._hip(xyz, points)
+    _call.hip(xyz, points)
     new_xyz = torch.zeros(B, 1, 3, dtype=torch.float32, device=xyz.device)
     grouped = xyz.view(B, 1, N, 3)
     return new_xyz, (grouped if points is None else torch.cat([grouped, points.view(B, 1, N, -1)], dim=-1))
@@ -471,7 +471,7 @@ class Grouper:
         _pointset.check_tensors("Grouper.run", *_with_points({"xyz": xyz, "new_xyz": new_xyz}, [torch.float32, torch.float32], points), _WHAT)
         count, N, S = _cloud_shapes("Grouper.run", xyz, new_xyz)
         D = 0 if points is None else _points_shape("Grouper.run", points, count, N)
-        _ops._hip(xyz, new_xyz, points)
+        _call.hip(xyz, new_xyz, points)
         if count > self.B or (N, S, D) != (self.N, self.S, self.D) or xyz.device != self.out.device:
             raise ValueError("Grouper.run: xyz %s, new_xyz %s, points %s do not fit B <= %d, N %d, S %d, D %d on %s"
                              % (tuple(xyz.shape), tuple(new_xyz.shape), None if points is None else tuple(points.shape), self.B, self.N,

@@ -18,7 +18,7 @@ There is no CPU fallback: `update` on anything but HIP tensors raises.
 import numpy as np
 import torch
 
-from . import _lib, _ops
+from . import _call, _lib
 
 # ShapeNetPart: first part id and number of parts of its 16 categories (the 50 part ids are numbered category by category)
 SHAPENET_PARTS = ((0, 4, 6, 8, 12, 16, 19, 22, 24, 28, 30, 36, 38, 41, 44, 47),
@@ -62,8 +62,8 @@ class EpochMetrics:
 
     def reset(self):
         """Empty state, every shape slot unfilled: one launch on the current stream."""
-        _lib.call("svnet_metrics_reset", _ops._p(self._buf), self.C, _ops._p(self._iou) if self.seg else None,
-                  _ops._p(self._cat) if self.seg else None, self.capacity, _ops._stream())
+        _lib.call("svnet_metrics_reset", _call.p(self._buf), self.C, _call.p(self._iou) if self.seg else None,
+                  _call.p(self._cat) if self.seg else None, self.capacity, _call.stream())
 
     def _workspace(self, B, N):
         need = _lib.lib().svnet_metrics_workspace_bytes(B, self.C, N)
@@ -74,7 +74,7 @@ class EpochMetrics:
     def update(self, logits, target, count=None, label=None, first=0):
         """Add one batch: one C call on the current stream, no sync, no host read.  count: the valid leading rows (clouds in the
         part-segmentation form), first: the epoch position of slot 0 (where the clouds' shape IoUs go)."""
-        _ops._hip(logits, target, label)
+        _call.hip(logits, target, label)
         if logits.dtype != torch.float32 or target.dtype != torch.int64 or not logits.is_contiguous() or not target.is_contiguous():
             raise TypeError("EpochMetrics.update: logits must be contiguous float32, target contiguous int64")
         if self.seg:
@@ -85,17 +85,17 @@ class EpochMetrics:
             if label is None or label.dtype != torch.int64 or label.numel() != B or not label.is_contiguous():
                 raise ValueError("EpochMetrics.update: the part-segmentation form needs label [B] int64")
             ws = self._workspace(B, N)
-            _lib.call("svnet_metrics_seg_f32", _ops._p(logits), _ops._p(target), _ops._p(label), B, self.C, N, _ops._p(self._parts[0]),
-                      _ops._p(self._parts[1]), self.num_cat, B if count is None else int(count), int(first), self.eps, _ops._p(self._buf),
-                      _ops._p(self._iou), _ops._p(self._cat), self.capacity, _ops._p(ws), ws.numel(), _ops._stream())
+            _lib.call("svnet_metrics_seg_f32", _call.p(logits), _call.p(target), _call.p(label), B, self.C, N, _call.p(self._parts[0]),
+                      _call.p(self._parts[1]), self.num_cat, B if count is None else int(count), int(first), self.eps, _call.p(self._buf),
+                      _call.p(self._iou), _call.p(self._cat), self.capacity, _call.p(ws), ws.numel(), _call.stream())
         else:
             if logits.dim() != 2 or logits.shape[1] != self.C or target.numel() != logits.shape[0]:
                 raise ValueError("EpochMetrics.update: logits [R,%d] and target [R] expected, got %s and %s"
                                  % (self.C, tuple(logits.shape), tuple(target.shape)))
             R = int(logits.shape[0])
             ws = self._workspace(R, 0)
-            _lib.call("svnet_metrics_cls_f32", _ops._p(logits), _ops._p(target), R, self.C, R if count is None else int(count), self.eps,
-                      _ops._p(self._buf), _ops._p(ws), ws.numel(), _ops._stream())
+            _lib.call("svnet_metrics_cls_f32", _call.p(logits), _call.p(target), R, self.C, R if count is None else int(count), self.eps,
+                      _call.p(self._buf), _call.p(ws), ws.numel(), _call.stream())
 
     def state(self):
         """The state as host numpy arrays - the one device-to-host copy (and sync) of an epoch."""

@@ -18,7 +18,7 @@ import torch.nn as nn
 import torch.nn.init as init
 import torch.nn.functional as F
 
-from .. import _ops
+from .. import _ops, _step
 from .. import config
 from .utils.sv_util import svpool, EdgeFeatures, XyzEdges
 
@@ -198,7 +198,7 @@ class PendingXyzBlock:
             bn1.bias, bn1.running_mean, bn1.running_var, b.linear2.weight, bn2.weight, bn2.bias, bn2.running_mean, bn2.running_var,
             b.gate[0].weight, b.gate[2].weight, bn1.num_batches_tracked, bn2.num_batches_tracked)
         if s_view is not None:
-            _ops._SINK.tracked(s_view, v_view)          # (its slice of a pyramid's concatenation: _ops.CatSink)
+            _step.STEP.sink.tracked(s_view, v_view)     # (its slice of a pyramid's concatenation: _ops.CatSink)
         return (s.unsqueeze(2), v.unsqueeze(2)) if keepdim else (s, v)
 
     def materialize(self):
@@ -238,7 +238,7 @@ class PendingEdgeBlock:
             bn2.weight, bn2.bias, bn2.running_mean, bn2.running_var, b.gate[0].weight, b.gate[2].weight,
             bn1.num_batches_tracked, bn2.num_batches_tracked)
         if s_view is not None:
-            _ops._SINK.tracked(s_view, v_view)
+            _step.STEP.sink.tracked(s_view, v_view)
         return (s.unsqueeze(2), v.unsqueeze(2)) if keepdim else (s, v)
 
     def materialize(self):

@@ -43,7 +43,7 @@ HIP device raise.  Limits: 1 <= N <= 32768 (the k-NN's limit), P >= 1, D >= 1, B
 """
 import torch
 
-from . import _lib, _ops, _pointset
+from . import _call, _lib, _pointset
 
 _WHAT = "the propagation"        # in the messages of _pointset.check_tensors
 
@@ -64,12 +64,12 @@ def _nn_shapes(name, query, ref):
 
 def _nn_launch(query, ref, B, P, N, idx, dist3, weight):
     with torch.cuda.device(query.device):
-        _lib.call("svnet_three_nn_f32", _ops._p(query), _ops._p(ref), B, P, N, _ops._p(idx), _ops._p(dist3), _ops._p(weight), _ops._stream())
+        _lib.call("svnet_three_nn_f32", _call.p(query), _call.p(ref), B, P, N, _call.p(idx), _call.p(dist3), _call.p(weight), _call.stream())
 
 
 def _interp_launch(feat, idx, weight, B, D, N, P, out):
     with torch.cuda.device(feat.device):
-        _lib.call("svnet_three_interpolate_f32", _ops._p(feat), _ops._p(idx), _ops._p(weight), B, D, N, P, _ops._p(out), _ops._stream())
+        _lib.call("svnet_three_interpolate_f32", _call.p(feat), _call.p(idx), _call.p(weight), B, D, N, P, _call.p(out), _call.stream())
 
 
 def three_nn(query, ref):
@@ -77,7 +77,7 @@ def three_nn(query, ref):
     `ref` points of every query point and their interpolation weights (module docstring).  One launch, no host read; no gradient."""
     _pointset.check_tensors("three_nn", {"query": query, "ref": ref}, (torch.float32, torch.float32), _WHAT)
     B, P, N = _nn_shapes("three_nn", query, ref)
-    _ops._hip(query, ref)
+    _call.hip(query, ref)
     _supported("three_nn", P, N, 1)
     idx = torch.empty(B, P, 3, dtype=torch.int64, device=query.device)
     dist3 = torch.empty(B, P, 3, dtype=torch.float32, device=query.device)
@@ -134,7 +134,7 @@ def three_interpolate(feat, idx, weight, out=None):
     grad = _pointset.check_tensors("three_interpolate", {"feat": feat, "idx": idx, "weight": weight},
                                    (torch.float32, torch.int64, torch.float32), _WHAT, grad=("feat",))
     B, D, N, P = _interp_shapes("three_interpolate", feat, idx, weight)
-    _ops._hip(feat, idx, weight)
+    _call.hip(feat, idx, weight)
     _supported("three_interpolate", P, N, D)
     if grad:
         _no_out_with_grad("three_interpolate", "feat", out)
@@ -154,7 +154,7 @@ def three_interpolate_backward(dout, idx, weight, N, out=None):
     N = int(N)
     if idx.shape[1] != P:
         raise ValueError("three_interpolate_backward: dout must be [B,D,P] with P = %d, got %s" % (idx.shape[1], tuple(dout.shape)))
-    _ops._hip(dout, idx, weight)
+    _call.hip(dout, idx, weight)
     _supported("three_interpolate_backward", P, N, D)
     _pointset.reverse_supported("three_interpolate_backward", P, 3, N)
     if out is None:
@@ -163,8 +163,8 @@ def three_interpolate_backward(dout, idx, weight, N, out=None):
         _pointset.check_out("three_interpolate_backward", {"dout": dout}, out, "[B,D,N]", (B, D, N), _WHAT)
     rev_start, rev_edge = _pointset.reverse_lists(idx, N)
     with torch.cuda.device(dout.device):
-        _lib.call("svnet_three_interpolate_bwd_f32", _ops._p(dout), _ops._p(weight), _ops._p(rev_start), _ops._p(rev_edge), B, D, N, P,
-                  _ops._p(out), _ops._stream())
+        _lib.call("svnet_three_interpolate_bwd_f32", _call.p(dout), _call.p(weight), _call.p(rev_start), _call.p(rev_edge), B, D, N, P,
+                  _call.p(out), _call.stream())
     return out
 
 
@@ -177,7 +177,7 @@ def propagate(query, ref, feat, out=None):
     if feat.dim() != 3 or feat.shape[0] != B or feat.shape[2] != N:
         raise ValueError("propagate: feat must be [B,D,N] with B = %d, N = %d, got %s" % (B, N, tuple(feat.shape)))
     D = int(feat.shape[1])
-    _ops._hip(query, ref, feat)
+    _call.hip(query, ref, feat)
     _supported("propagate", P, N, D)
     if grad:
         _no_out_with_grad("propagate", "feat", out)
@@ -211,7 +211,7 @@ class Propagator:
     def run(self, query, ref, feat):
         _pointset.check_tensors("Propagator.run", {"query": query, "ref": ref, "feat": feat}, (torch.float32,) * 3, _WHAT)
         count, P, N = _nn_shapes("Propagator.run", query, ref)
-        _ops._hip(query, ref, feat)
+        _call.hip(query, ref, feat)
         if count > self.B or (P, N) != (self.P, self.N) or tuple(feat.shape) != (count, self.D, N) or query.device != self.out.device:
             raise ValueError("Propagator.run: query %s, ref %s, feat %s do not fit B <= %d, D %d, N %d, P %d on %s"
                              % (tuple(query.shape), tuple(ref.shape), tuple(feat.shape), self.B, self.D, self.N, self.P, self.out.device))

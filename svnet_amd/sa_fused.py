@@ -33,7 +33,7 @@ require grad.  There is no CPU fallback: tensors that are not on a HIP device ra
 """
 import torch
 
-from . import _level, _lib, _ops, _pointset
+from . import _call, _level, _lib, _pointset
 from ._level import MAX_LAYERS, FoldedLevel, fold_level
 from .group import _query_msg_launch, _sample_centres, _scales
 
@@ -55,9 +55,9 @@ def supported(N, S, K, D, widths):
 
 def _launch(xyz, new_xyz, idx, idx_ld, points, level, count, count_ld, xyz_last, out, c_off, B, N, S, K, D):
     with torch.cuda.device(xyz.device):
-        _lib.call("svnet_sa_fused_f32", _ops._p(xyz), _ops._p(new_xyz), _ops._p(points if D else None), _ops._p(idx), idx_ld, _ops._p(count),
-                  count_ld, B, N, S, K, D, len(level.widths), level._c_widths, level._c_wf, level._c_bf, int(bool(xyz_last)), _ops._p(out),
-                  int(out.shape[1]), c_off, _ops._stream())
+        _lib.call("svnet_sa_fused_f32", _call.p(xyz), _call.p(new_xyz), _call.p(points if D else None), _call.p(idx), idx_ld, _call.p(count),
+                  count_ld, B, N, S, K, D, len(level.widths), level._c_widths, level._c_wf, level._c_bf, int(bool(xyz_last)), _call.p(out),
+                  int(out.shape[1]), c_off, _call.stream())
 
 
 def _row_stride(name, arg, t, inner):
@@ -103,7 +103,7 @@ def group_mlp_max(xyz, new_xyz, idx, points, level, count=None, xyz_last=False, 
         D = int(points.shape[2])
     _level.check_c_in(name, level, 3 + D, "xyz and points give 3 + %d" % D)
     c_off = _level.check_window(name, out, c_off, level, B, S, "S")
-    _ops._hip(xyz, new_xyz, idx, points, count, out)
+    _call.hip(xyz, new_xyz, idx, points, count, out)
     _level.check_device(name, level, "xyz", xyz)
     if not supported(N, S, K, D, level.widths):
         raise _lib.SvnetHipError("%s: N = %d, S = %d, K = %d, D = %d, widths %s is not supported (1 <= K <= N <= %d, S >= 1, D <= 321, 1 .. %d "
@@ -153,7 +153,7 @@ class FusedSetAbstraction(_level.FusedWrapper):
     def __call__(self, xyz, points, start=None):
         name = self._begin(_WHAT, {"xyz": (xyz, _F32)}, {"points": (points, _F32), "start": (start, torch.int64)})
         B, N, D = _level.cloud_shapes(name, xyz, points)
-        _ops._hip(xyz, points, start)
+        _call.hip(xyz, points, start)
         if not self.supported(N, D):
             return self.module(xyz, points, start=start)
         if start is None:

@@ -34,7 +34,7 @@ require grad.  There is no CPU fallback: tensors that are not on a HIP device ra
 """
 import torch
 
-from . import _level, _lib, _ops, _pointset
+from . import _call, _level, _lib, _pointset
 from ._level import MAX_LAYERS, fold_level
 
 __all__ = ["global_mlp_max", "supported", "rows_tile", "FusedGlobalAbstraction"]
@@ -56,8 +56,8 @@ def supported(N, D, widths):
 
 def _launch(xyz, points, level, out, c_off, B, N, D):
     with torch.cuda.device(xyz.device):
-        _lib.call("svnet_sa_global_f32", _ops._p(xyz), _ops._p(points if D else None), B, N, D, len(level.widths), level._c_widths, level._c_wf,
-                  level._c_bf, _ops._p(out), int(out.shape[1]), c_off, _ops._stream())
+        _lib.call("svnet_sa_global_f32", _call.p(xyz), _call.p(points if D else None), B, N, D, len(level.widths), level._c_widths, level._c_wf,
+                  level._c_bf, _call.p(out), int(out.shape[1]), c_off, _call.stream())
 
 
 def global_mlp_max(xyz, points, level, out=None, c_off=0):
@@ -70,7 +70,7 @@ def global_mlp_max(xyz, points, level, out=None, c_off=0):
     B, N, D = _level.cloud_shapes(name, xyz, points)
     _level.check_c_in(name, level, 3 + D, "xyz and points give 3 + %d" % D)
     c_off = _level.check_window(name, out, c_off, level, B, 1)
-    _ops._hip(xyz, points, out)
+    _call.hip(xyz, points, out)
     _level.check_device(name, level, "xyz", xyz)
     if not supported(N, D, level.widths):
         raise _lib.SvnetHipError("%s: N = %d, D = %d, widths %s is not supported (1 <= N <= %d, D <= %d, 1 .. %d layers of width 1 .. %d)"
@@ -109,7 +109,7 @@ class FusedGlobalAbstraction(_level.FusedWrapper):
     def __call__(self, xyz, points, start=None):
         name = self._begin(_WHAT, {"xyz": (xyz, _F32)}, {"points": (points, _F32)})
         B, N, D = _level.cloud_shapes(name, xyz, points)
-        _ops._hip(xyz, points)
+        _call.hip(xyz, points)
         if not self.supported(N, D):
             return self.module(xyz, points, start=start)
         dev = xyz.device

@@ -22,7 +22,7 @@ import math
 
 import torch
 
-from . import _lib, _ops, config
+from . import _call, _lib, _ops, _step, config
 from .dist import GradBucket
 
 
@@ -103,14 +103,14 @@ class TrainStep:
         self.graph = None
         self.loss = None
         self._stream = None
-        self._arena = _ops._ZeroArena()       # this step's zero-filled scratch: a captured graph has its addresses baked in
+        self._arena = _step._ZeroArena()       # this step's zero-filled scratch: a captured graph has its addresses baked in
 
     def _deferral_is_safe(self):
         """config.DEFER_WGRAD hands autograd parameter gradients that the side stream has not written yet; that is sound only while
         autograd merely ADOPTS them as .grad (never reads them on the main stream): every parameter used by ONE module only (a shared
         one gets two gradients, added on the main stream), .grad None at backward (bucket.begin()), no tensor / post-accumulate hooks
         (they run on the main stream).  Anything else falls back to the per-layer join.  What this static check cannot see - one
-        module applied twice in a forward, a parameter read by two Functions - is counted at run time: _ops.DEFERRED.first_use() sends the
+        module applied twice in a forward, a parameter read by two Functions - is counted at run time: _step.DEFERRED.first_use() sends the
         second backward of the same weights down the joined schedule."""
         seen = set()
         for _, p in self.model.named_parameters(remove_duplicate=False):
@@ -123,7 +123,7 @@ class TrainStep:
 
     def fwd_bwd(self, planes_external=False):
         """zero_grad -> forward -> loss -> backward, gradients packed into the flat bucket (no optimizer step)."""
-        _ops.begin_step(self.bucket.flat.device, planes_external, self._arena)   # one zero fill for the step's accumulators; stale packed weights rebuilt on the side stream
+        _step.begin_step(self.bucket.flat.device, planes_external, self._arena)   # one zero fill for the step's accumulators; stale packed weights rebuilt on the side stream
         try:
             self.bucket.begin()
             out = self.model(*self.inputs)
@@ -131,16 +131,16 @@ class TrainStep:
                 self.out = out.detach()
             loss = self.loss_fn(out, self.target)
             del out
-            # nothing reads a parameter gradient before pack() (checked: _deferral_is_safe): see _ops._Deferred
-            _ops.DEFERRED.active = bool(config.DEFER_WGRAD) and self._deferral_is_safe()
+            # nothing reads a parameter gradient before pack() (checked: _deferral_is_safe): see _step._Deferred
+            _step.DEFERRED.active = bool(config.DEFER_WGRAD) and self._deferral_is_safe()
             if loss.dim() == 0 and loss.is_cuda and loss.dtype == torch.float32:
-                torch.autograd.backward(loss, _ops.UNIT_GRAD.get(loss.device))      # (a cached 1.0: no fill, no multiplication by one)
+                torch.autograd.backward(loss, _step.UNIT_GRAD.get(loss.device))      # (a cached 1.0: no fill, no multiplication by one)
             else:
                 loss.backward()
-            _ops.DEFERRED.join(self.bucket.flat.device)
+            _step.DEFERRED.join(self.bucket.flat.device)
             self.bucket.pack()                              # one batched copy of all gradients into the flat bucket
         finally:
-            _ops.end_step()
+            _step.end_step()
         return loss.detach()
 
     def capture(self, warmup=2, before_capture=None):
@@ -167,7 +167,7 @@ class TrainStep:
 
     def run(self, all_reduce=True):
         if self.graph is not None:
-            _ops.PLANES.refresh(self.bucket.flat.device)      # packed weight forms: only what an optimizer step (or a load) changed
+            _step.PLANES.refresh(self.bucket.flat.device)      # packed weight forms: only what an optimizer step (or a load) changed
             self.graph.replay()
             loss = self.loss
         else:
@@ -185,17 +185,17 @@ class ForwardStep:
         self.model, self.inputs = model, tuple(inputs)
         self.graph = None
         self.out = None
-        self._arena = _ops._ZeroArena()
+        self._arena = _step._ZeroArena()
 
     def forward(self, planes_external=False):
         was_training = self.model.training
         self.model.eval()
-        _ops.begin_step(self.inputs[0].device, planes_external, self._arena)
+        _step.begin_step(self.inputs[0].device, planes_external, self._arena)
         try:
             with torch.no_grad():
                 return self.model(*self.inputs)
         finally:
-            _ops.end_step()
+            _step.end_step()
             self.model.train(was_training)        # (a TrainStep on the same model must not silently train in eval mode)
 
     def capture(self, warmup=2):
@@ -215,7 +215,7 @@ class ForwardStep:
 
     def run(self):
         if self.graph is not None:
-            _ops.PLANES.refresh(self.inputs[0].device)
+            _step.PLANES.refresh(self.inputs[0].device)
             self.graph.replay()
         else:
             self.out = self.forward()
@@ -395,10 +395,10 @@ def rotate_clouds(x, mode, generator=None):
 # ----------------------------------------------------------------------------- optimizers on flat buffers
 
 def invalidate_packed_weights():
-    """Tell the packed-weight cache (_ops._PlaneCache) that weights were changed in a way autograd's version counters do not see
+    """Tell the packed-weight cache (_step._PlaneCache) that weights were changed in a way autograd's version counters do not see
     (a write through `.data`, a raw pointer, a custom kernel): everything is re-packed at the next step.  torch.optim steps,
     load_state_dict and in-place ops under no_grad ARE seen; the flat optimizers below call this themselves."""
-    _ops.PLANES.invalidate()
+    _step.PLANES.invalidate()
 
 
 class FlatParams:
@@ -452,7 +452,7 @@ class _FlatOptimizer:
 
 
     # ---- the step as a captured graph.  An eager step is the update kernel plus, before the next forward, ~25 small launches that re-pack
-    # the binarized weights it changed (_ops.PLANES.refresh): 0.18 ms per step of latency-bound launches behind a 4.4 ms replay.  capture()
+    # the binarized weights it changed (_step.PLANES.refresh): 0.18 ms per step of latency-bound launches behind a 4.4 ms replay.  capture()
     # records [update kernel -> every re-pack, spread over four streams] once; step() then costs one 32-byte copy of the step's scalars
     # (learning rate, bias corrections) and one graph launch.  The update kernel reads those scalars from device memory.
     def _hyper_values(self):
@@ -491,7 +491,7 @@ class _FlatOptimizer:
                 issued[0] += 1
                 with torch.cuda.stream(h):
                     rebuild()
-            keys = _ops.PLANES.rebuild_all(run)
+            keys = _step.PLANES.rebuild_all(run)
             for h in self._helpers[:issued[0]]:
                 main.wait_stream(h)                           # join
             return keys
@@ -528,10 +528,10 @@ class _FlatOptimizer:
                                "re-allocated state): the captured graph would update the old memory - call capture() again")
         self._put_hyper(self._hyper_values())
         self._graph.replay()
-        if set(_ops.PLANES.entries) <= set(self._keys):
-            _ops.PLANES.mark_fresh(self._keys)                # everything that exists was re-packed inside the graph
+        if set(_step.PLANES.entries) <= set(self._keys):
+            _step.PLANES.mark_fresh(self._keys)                # everything that exists was re-packed inside the graph
         else:
-            _ops.PLANES.invalidate()                          # a packed form created after capture(): the eager refresh takes over
+            _step.PLANES.invalidate()                          # a packed form created after capture(): the eager refresh takes over
 
 
 class FlatAdam(_FlatOptimizer):
@@ -581,16 +581,16 @@ class FlatAdam(_FlatOptimizer):
         return [self.lr, self.b1, self.b2, self.eps, self.wd, bc1, 1.0 / math.sqrt(bc2)]
 
     def _launch_dev(self):
-        _ops.call("svnet_adam_step_dev_f32", _ops._p(self.p), _ops._p(self.g), _ops._p(self.m), _ops._p(self.v), self.p.numel(),
-                  _ops._p(self._hyper), _ops._stream())
+        _call.call("svnet_adam_step_dev_f32", _call.p(self.p), _call.p(self.g), _call.p(self.m), _call.p(self.v), self.p.numel(),
+                  _call.p(self._hyper), _call.stream())
 
     def step(self):
         self.steps += 1
         if getattr(self, "_graph", None) is not None:
             return self._step_captured()
-        _ops.PLANES.invalidate()                              # (the kernel writes the flat buffer behind autograd's version counters)
-        _ops.call("svnet_adam_step_f32", _ops._p(self.p), _ops._p(self.g), _ops._p(self.m), _ops._p(self.v), self.p.numel(),
-                  self.lr, self.b1, self.b2, self.eps, self.wd, self.steps, _ops._stream())
+        _step.PLANES.invalidate()                              # (the kernel writes the flat buffer behind autograd's version counters)
+        _call.call("svnet_adam_step_f32", _call.p(self.p), _call.p(self.g), _call.p(self.m), _call.p(self.v), self.p.numel(),
+                  self.lr, self.b1, self.b2, self.eps, self.wd, self.steps, _call.stream())
 
 
 class FlatSGD(_FlatOptimizer):
@@ -632,16 +632,16 @@ class FlatSGD(_FlatOptimizer):
         return [self.lr, self.momentum, self.wd, 1.0 if self.steps == 1 else 0.0]
 
     def _launch_dev(self):
-        _ops.call("svnet_sgd_step_dev_f32", _ops._p(self.p), _ops._p(self.g), _ops._p(self.buf), self.p.numel(), _ops._p(self._hyper),
-                  _ops._stream())
+        _call.call("svnet_sgd_step_dev_f32", _call.p(self.p), _call.p(self.g), _call.p(self.buf), self.p.numel(), _call.p(self._hyper),
+                  _call.stream())
 
     def step(self):
         self.steps += 1
         if getattr(self, "_graph", None) is not None:
             return self._step_captured()
-        _ops.PLANES.invalidate()
-        _ops.call("svnet_sgd_step_f32", _ops._p(self.p), _ops._p(self.g), _ops._p(self.buf), self.p.numel(), self.lr, self.momentum,
-                  self.wd, int(self.steps == 1), _ops._stream())
+        _step.PLANES.invalidate()
+        _call.call("svnet_sgd_step_f32", _call.p(self.p), _call.p(self.g), _call.p(self.buf), self.p.numel(), self.lr, self.momentum,
+                  self.wd, int(self.steps == 1), _call.stream())
 
 
 class CosineLR:

@@ -39,7 +39,7 @@ patterns (a -0 counted as +0).  No argument may require grad.  There is no CPU f
 """
 import torch
 
-from . import _lib, _ops, _pointset
+from . import _call, _lib, _pointset
 
 __all__ = ["fold_vn_layer", "vn_edge_mean", "supported", "FoldedVNLayer", "FusedVNDGCNN", "MAX_K", "MAX_C", "MAX_O"]
 
@@ -93,9 +93,9 @@ class FoldedVNLayer:
         if layer.map_to_feat.weight.device != self.device:
             raise ValueError("fold_vn_layer: the layer moved from %s to %s - fold it again" % (self.device, layer.map_to_feat.weight.device))
         with torch.cuda.device(self.device):
-            _lib.call("svnet_vn_fold_f32", _ops._p(layer.map_to_feat.weight.detach()), _ops._p(layer.map_to_dir.weight.detach()),
-                      _ops._p(bn.weight.detach()), _ops._p(bn.bias.detach()), _ops._p(bn.running_mean), _ops._p(bn.running_var), self.C, self.O,
-                      self.Od, float(bn.eps), _ops._p(self.folded), _ops._stream())
+            _lib.call("svnet_vn_fold_f32", _call.p(layer.map_to_feat.weight.detach()), _call.p(layer.map_to_dir.weight.detach()),
+                      _call.p(bn.weight.detach()), _call.p(bn.bias.detach()), _call.p(bn.running_mean), _call.p(bn.running_var), self.C, self.O,
+                      self.Od, float(bn.eps), _call.p(self.folded), _call.stream())
         return self
 
     def tables(self, B, N):
@@ -124,11 +124,11 @@ def _launch(x, idx, folded, out, B, N, k, edge=True, tables=True):
     ws = folded.tables(B, N)
     with torch.cuda.device(x.device):
         if tables:
-            _lib.call("svnet_vn_tables_f32", _ops._p(x), _ops._p(folded.folded), B, N, folded.C, folded.O, folded.Od, _ops._p(ws), ws.numel(),
-                      _ops._stream())
+            _lib.call("svnet_vn_tables_f32", _call.p(x), _call.p(folded.folded), B, N, folded.C, folded.O, folded.Od, _call.p(ws), ws.numel(),
+                      _call.stream())
         if edge:
-            _lib.call("svnet_vn_edge_mean_f32", _ops._p(ws), ws.numel(), _ops._p(idx), _ops._p(folded.folded), B, N, k, folded.C, folded.O,
-                      folded.Od, folded.slope, _ops._p(out), _ops._stream())
+            _lib.call("svnet_vn_edge_mean_f32", _call.p(ws), ws.numel(), _call.p(idx), _call.p(folded.folded), B, N, k, folded.C, folded.O,
+                      folded.Od, folded.slope, _call.p(out), _call.stream())
 
 
 def vn_edge_mean(x, idx, folded, out=None):
@@ -154,7 +154,7 @@ def vn_edge_mean(x, idx, folded, out=None):
         raise ValueError("%s: the layer takes %d vector channels, x has %d" % (name, folded.C, C))
     if out is not None and tuple(out.shape) != (B, folded.O, 3, N):
         raise ValueError("%s: out must be [B,O,3,N] = %s, got %s" % (name, (B, folded.O, 3, N), tuple(out.shape)))
-    _ops._hip(x, idx, out)
+    _call.hip(x, idx, out)
     if folded.device != x.device:
         raise ValueError("%s: the layer is on %s, x on %s" % (name, folded.device, x.device))
     if not supported(N, k, C, folded.O, folded.Od):
@@ -219,7 +219,7 @@ class FusedVNDGCNN(torch.nn.Module):
         for n, i in enumerate(idx or ()):
             if i.device != x.device:
                 raise ValueError("%s: x on %s, idx[%d] on %s" % (name, x.device, n, i.device))
-        _ops._hip(x, *(idx or ()))
+        _call.hip(x, *(idx or ()))
         B, _, N = (int(v) for v in x.shape)
         ks = [self.model.k] * 4 if idx is None else [int(i.shape[2]) for i in idx]
         if not all(self.supported(N, k) for k in ks):

@@ -336,3 +336,54 @@ def test_a_second_backward_of_the_same_weights_is_not_deferred():
     assert not d.first_use(c, torch.zeros(2))
     d.join(torch.device("cpu"))            # (nothing kept: no stream is touched) - the next backward starts counting afresh
     assert d.first_use(a, b, c)
+
+
+_FRONT_ENDS = ["_pointset", "_level", "group", "propagate", "data", "metrics", "sa_fused", "fp_fused", "sa_global", "vn_fused"]
+
+
+def _ops_loaded_after_importing(names):
+    """In a fresh child process: import svnet_amd.<name> one after the other; is svnet_amd._ops in sys.modules after each?"""
+    code = ("import importlib, sys\n"
+            "for n in %r:\n"
+            "    importlib.import_module('svnet_amd.' + n)\n"
+            "    print(n, 'svnet_amd._ops' in sys.modules)\n" % (list(names),))
+    p = subprocess.run([sys.executable, "-c", code], cwd=ROOT, env=dict(os.environ, PYTHONPATH=ROOT), stdout=subprocess.PIPE,
+                       stderr=subprocess.PIPE, timeout=300)
+    assert p.returncode == 0, p.stderr.decode()[-2000:]
+    return [tuple(line.split()) for line in p.stdout.decode().splitlines()]
+
+
+def test_front_ends_and_step_state_do_not_import_the_op_layer():
+    """The point-set and fused-level front ends, data and metrics take their call helpers from the leaf svnet_amd._call; the step
+    state (svnet_amd._step) sits under the op layer, not above it."""
+    assert _ops_loaded_after_importing(_FRONT_ENDS) == [(n, "False") for n in _FRONT_ENDS]
+    assert _ops_loaded_after_importing(["_step", "_call"]) == [("_step", "False"), ("_call", "False")]
+
+
+def test_op_layer_names_are_the_call_helpers_and_the_step_objects_themselves():
+    from svnet_amd import _call, _ops, _step
+    for old, new in (("_p", "p"), ("_stream", "stream"), ("_hip", "hip"), ("_f32c", "f32c"), ("call", "call")):
+        assert getattr(_ops, old) is getattr(_call, new), old
+    for name in ("PLANES", "DEFERRED", "UNIT_GRAD", "begin_step", "end_step", "_ZeroArena", "_PlaneCache", "_Deferred", "_side_stream"):
+        assert getattr(_ops, name) is getattr(_step, name), name
+    for name in ("ARENA", "_SINK", "_FUSED_COLSUMS"):        # what is rebound lives on _step.STEP only: a copy here would go stale
+        assert not hasattr(_ops, name), name
+    assert not hasattr(_ops.knn_table_ahead, "table")
+
+
+def test_end_step_restores_every_record_of_the_step():
+    from svnet_amd import _step
+    STEP, DEFERRED, PLANES = _step.STEP, _step.DEFERRED, _step.PLANES
+    STEP.fused_colsums, STEP.sink, STEP.knn_table = object(), object(), object()
+    DEFERRED.keep.append(object())
+    DEFERRED.seen.add(1)
+    DEFERRED.active = True
+    arena = _step._ZeroArena()
+    _step.begin_step("cpu", arena=arena)
+    assert STEP.arena is arena and arena.active and PLANES.active
+    _step.end_step()
+    assert STEP.fused_colsums is None and STEP.sink is None and STEP.knn_table is None
+    assert STEP.arena is STEP.default_arena and not STEP.arena.active and not arena.active
+    assert not DEFERRED.active and not DEFERRED.keep and not DEFERRED.seen
+    assert not PLANES.active
+    assert _step.STEP is STEP

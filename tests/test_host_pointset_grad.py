@@ -163,7 +163,7 @@ def test_out_beside_a_grad_is_refused(monkeypatch):
     """`out=` together with an input that requires grad raises a ValueError before anything is launched.  Without a GPU the two
     device checks in front of that refusal are patched to let CPU tensors through (tests/test_hip_pointset_grad.py sees the same
     refusal unpatched)."""
-    from svnet_amd import _ops, _pointset, group as Gr, propagate as Pr
+    from svnet_amd import _call, _pointset, group as Gr, propagate as Pr
     real = _pointset.check_tensors
 
     def lenient(name, tensors, dtypes, what, grad=()):
@@ -171,7 +171,7 @@ def test_out_beside_a_grad_is_refused(monkeypatch):
         return any(tensors[k].requires_grad for k in grad if k in tensors)
 
     monkeypatch.setattr(_pointset, "check_tensors", lenient)
-    monkeypatch.setattr(_ops, "_hip", lambda *t: None)
+    monkeypatch.setattr(_call, "hip", lambda *t: None)
     q, r, f = (torch.from_numpy(a) for a in R.lattice_case(43, 2, 10, 5, 4))
     x, c, pts = (torch.from_numpy(a) for a in G.lattice_case(43, 2, 10, 5, 4))
     idx3, w3, gidx = torch.zeros(2, 10, 3, dtype=torch.int64), torch.zeros(2, 10, 3), torch.zeros(2, 5, 3, dtype=torch.int64)
