@@ -45,9 +45,9 @@ int svnet_slices_sum_f64(double* buf, int64_t L, void* stream);
 
 /* ABI version = 100 * round-of-change + serial.  It changes whenever an entry point gains / loses an argument or a caller-owned buffer
  * changes its required length (200: sliced accumulators, SVNET_SLICED_LEN; 400: this header; 401: the totals of a sliced accumulator are
- * written by its consumer, svnet_slices_sum_*; 402: GX of svnet_v2s_bwd_*, gw of svnet_xyzblock_bwd_f32 and col_sum of svnet_gemm_f32 are sliced accumulators; 403: svnet_binweight_grad_f32 takes sliced inputs; 421: svnet_three_nn_f32, svnet_three_interpolate_f32; 422: svnet_ball_query_f32, svnet_group_points_f32; 423: svnet_vlinear_stats_f32 is gone; 424: svnet_edgeblock_fwd_tier, svnet_edgeblock_bwd_tier, svnet_edgeblock_wgrad_tier, svnet_xyzblock_tier; 425: svnet_pointset_reverse_i32, svnet_three_interpolate_bwd_f32, svnet_group_points_bwd_f32; 426: wbt of svnet_edgeblock_wbt_bf16 is 512 values longer, the all-zero fragment; 427: svnet_ball_query_msg_f32, svnet_group_points_msg_f32, svnet_group_points_msg_bwd_f32; 428: svnet_sa_fold_f32, svnet_sa_fused_f32; 429: svnet_fp_fused_f32, svnet_fp_fused_supported, svnet_fp_fused_rows_tile; 430: svnet_sa_global_f32, svnet_sa_global_supported, svnet_sa_global_rows_tile; 431: svnet_pool_gather_attr_f32, the attribute fields attr, A, attr_vectors, attr_out at the end of svnet_batch_desc; 432: svnet_vn_fold_f32, svnet_vn_tables_f32, svnet_vn_edge_mean_f32, svnet_vn_supported, svnet_vn_workspace_bytes).  svnet_version() returns the value the
+ * written by its consumer, svnet_slices_sum_*; 402: GX of svnet_v2s_bwd_*, gw of svnet_xyzblock_bwd_f32 and col_sum of svnet_gemm_f32 are sliced accumulators; 403: svnet_binweight_grad_f32 takes sliced inputs; 421: svnet_three_nn_f32, svnet_three_interpolate_f32; 422: svnet_ball_query_f32, svnet_group_points_f32; 423: svnet_vlinear_stats_f32 is gone; 424: svnet_edgeblock_fwd_tier, svnet_edgeblock_bwd_tier, svnet_edgeblock_wgrad_tier, svnet_xyzblock_tier; 425: svnet_pointset_reverse_i32, svnet_three_interpolate_bwd_f32, svnet_group_points_bwd_f32; 426: wbt of svnet_edgeblock_wbt_bf16 is 512 values longer, the all-zero fragment; 427: svnet_ball_query_msg_f32, svnet_group_points_msg_f32, svnet_group_points_msg_bwd_f32; 428: svnet_sa_fold_f32, svnet_sa_fused_f32; 429: svnet_fp_fused_f32, svnet_fp_fused_supported, svnet_fp_fused_rows_tile; 430: svnet_sa_global_f32, svnet_sa_global_supported, svnet_sa_global_rows_tile; 431: svnet_pool_gather_attr_f32, the attribute fields attr, A, attr_vectors, attr_out at the end of svnet_batch_desc; 432: svnet_vn_fold_f32, svnet_vn_tables_f32, svnet_vn_edge_mean_f32, svnet_vn_supported, svnet_vn_workspace_bytes; 433: svnet_vn_point_supported, svnet_vn_point_workspace_bytes, svnet_vn_point_fold_f32, svnet_vn_point_f32, svnet_vn_cloud_mean_f32, svnet_vn_std_pool_supported, svnet_vn_std_pool_workspace_bytes, svnet_vn_std_pool_f32).  svnet_version() returns the value the
  * library was BUILT with: a caller compiled against another header must refuse to run (svnet_amd/_lib.py does).                   */
-#define SVNET_ABI_VERSION 432
+#define SVNET_ABI_VERSION 433
 int svnet_version(void);
 const char* svnet_last_error(void);
 
@@ -1017,6 +1017,55 @@ int svnet_vn_tables_f32(const float* x, const float* folded, int64_t B, int64_t 
                         size_t workspace_bytes, void* stream);
 int svnet_vn_edge_mean_f32(const float* workspace, size_t workspace_bytes, const int64_t* idx, const float* folded, int64_t B, int64_t N,
                            int64_t k, int64_t C, int64_t O, int64_t Od, float slope, float* out, void* stream);
+
+/* ------------------------------------------------------------------ fused vector-neuron tail for inference: point level, cloud mean, standardise and pool
+ * (models/vn_dgcnn_cls.py tail: conv5, the mean over the points, VNStdFeature (models/vn_layers.py) with normalize_frame = False and
+ * the [amax | mean] pool, in eval mode).  fl() is rounding to fp32; every operation is rounded once, nothing is contracted but the
+ * stated fmaf.  EPS = fl(1e-6).  Inputs are assumed finite.  Every call launches on `stream`, reads nothing back and uses no atomics:
+ * capturable, reproducible.
+ * POINT LEVEL: the eval forward of a VNLinearLeakyReLU on [B, C + Cg, 3, N] whose last Cg input channels are constant over each cloud
+ * and are given as g [B,Cg,3] (Cg may be 0: g and workspace may then be null).  K = C + Cg, Od = O or 1 (share_nonlinearity: every o uses
+ * direction row 0), R = O + Od.
+ * svnet_vn_point_fold_f32: w_feat [O,K] (map_to_feat.weight), w_dir [Od,K] (map_to_dir.weight), BatchNorm gamma, beta, running_mean,
+ *     running_var [O] -> folded, K R + 2 O floats, caller-owned: WT [K][R] | s [O] | t [O]; column r of WT is row r of W = [w_feat | w_dir]
+ *     stacked; invstd = fl(1 / fl(sqrt(fl(var + eps)))), s = fl(gamma invstd), t = fl(beta - fl(mean s)), as svnet_vn_fold_f32.  One launch.
+ * svnet_vn_point_f32: x [B,C,3,N], g [B,Cg,3], folded -> out [B,O,3,N].  One launch, and one small launch in front of it with Cg > 0.
+ *         cloud term   per cloud b, row r of W and component a: u = +0; for c ascending over Cg: u = fmaf(g[b,c,a], W[r, C + c], u).
+ *                      It lies in the workspace, [B][3][R] floats.
+ *         point term   per (b, n, a) and row r: acc = u[b,r,a] (+0 with Cg = 0); for c ascending over C: acc = fmaf(x[b,c,a,n], W[r,c], acc).
+ *                      K is never split: no value depends on tiling.  p[o,a] are the w_feat rows, d[od,a] the w_dir rows (od = o, or 0).
+ *         norm, leaky  the edge level's arithmetic (svnet_vn_edge_mean_f32 above) on p and d:
+ *                      q = fmaf(p2, p2, fmaf(p1, p1, fl(p0 p0)));  r = fl(fl(sqrt(q)) + EPS);  nb = fmaf(r, s[o], t[o]);  g = fl(nb / r);  p'[a] = fl(p[a] g)
+ *                      dot = fmaf(p'2, d2, fmaf(p'1, d1, fl(p'0 d0)));  dd = fmaf(d2, d2, fmaf(d1, d1, fl(d0 d0)))
+ *                      w = p' if dot >= 0, else c = fl(dot / fl(dd + EPS)) and w[a] = fmaf(-c, d[a], p'[a])
+ *                      out[b,o,a,n] = fmaf(slope, p'[a], fl(fl(1 - slope) w[a])).
+ * svnet_vn_point_supported (1 / 0, a pure host function): 1 <= N <= 32768, 1 <= C <= 512, 0 <= Cg <= 512, 1 <= O <= 512, Od = O or 1.
+ * svnet_vn_point_workspace_bytes (a pure host function): 3 B R floats in bytes with Cg > 0, else 0; 0 outside the limits or 1 <= B <= 65535.
+ * CLOUD MEAN: svnet_vn_cloud_mean_f32: x [B,C,3,N] -> m [B,C,3].  The order is the contract's, not the tiling's: run j holds n in
+ *     [64 j, min(N, 64 j + 64)); a run's sum is n-ascending plain additions from +0; m = fl((the runs' sums added j-ascending from +0) / fl(N)).
+ *     1 <= N <= 32768, 1 <= C <= 512.  One launch.
+ * STANDARDISE AND POOL: svnet_vn_std_pool_f32: x [B,C,3,N], g [B,Cg,3] (constant channels; null with Cg = 0), y [B,Cy,3,N] (vn2's output),
+ *     w_lin [3,Cy] (vn_lin.weight) -> h [B, 6 I], I = C + Cg.
+ *         frame rows   z[k][a](n) = +0; for c ascending over Cy: z = fmaf(y[b,c,a,n], w_lin[k,c], z).
+ *         coordinates  v_i = x[b,i,:,n] for i < C, g[b,i-C,:] otherwise: e[i,k](n) = fmaf(v_i[2], z[k][2], fmaf(v_i[1], z[k][1], fl(v_i[0] z[k][0]))).
+ *         pool         h[b, 3 i + k] = max over n of e (a -0 counts as +0); h[b, 3 I + 3 i + k] = the mean of e under the cloud-mean rule.
+ *     The workgroups of a cloud meet through per-run maxima and sums in the workspace, [2][runs][B][3 I] floats with runs = ceil(N / 64), and
+ *     a finishing launch that adds the runs' sums in order.  Two launches.
+ * svnet_vn_std_pool_supported (1 / 0, a pure host function): 1 <= N <= 32768, 1 <= C <= 512, 0 <= Cg <= 512, 1 <= Cy <= 512.
+ * svnet_vn_std_pool_workspace_bytes (a pure host function): 2 ceil(N / 64) B 3 (C + Cg) floats in bytes; 0 outside the limits or 1 <= B <= 65535.
+ * Errors: a null pointer or B outside 1 .. 65535 is SVNET_E_ARG, a shape outside the limits SVNET_E_UNSUPPORTED, a short workspace
+ * SVNET_E_WORKSPACE; svnet_last_error names the entry.                                                                               */
+int svnet_vn_point_supported(int64_t N, int64_t C, int64_t Cg, int64_t O, int64_t Od);
+size_t svnet_vn_point_workspace_bytes(int64_t B, int64_t Cg, int64_t O, int64_t Od);
+int svnet_vn_point_fold_f32(const float* w_feat, const float* w_dir, const float* gamma, const float* beta, const float* running_mean,
+                            const float* running_var, int64_t C, int64_t Cg, int64_t O, int64_t Od, float eps, float* folded, void* stream);
+int svnet_vn_point_f32(const float* x, const float* g, const float* folded, int64_t B, int64_t N, int64_t C, int64_t Cg, int64_t O, int64_t Od,
+                       float slope, void* workspace, size_t workspace_bytes, float* out, void* stream);
+int svnet_vn_cloud_mean_f32(const float* x, int64_t B, int64_t C, int64_t N, float* m, void* stream);
+int svnet_vn_std_pool_supported(int64_t N, int64_t C, int64_t Cg, int64_t Cy);
+size_t svnet_vn_std_pool_workspace_bytes(int64_t B, int64_t N, int64_t C, int64_t Cg);
+int svnet_vn_std_pool_f32(const float* x, const float* g, const float* y, const float* w_lin, int64_t B, int64_t N, int64_t C, int64_t Cg,
+                          int64_t Cy, void* workspace, size_t workspace_bytes, float* h, void* stream);
 
 /* ------------------------------------------------------------------ epoch metrics (main_cls_dgcnn.py:187-251, main_partseg_dgcnn.py:185-279,
  * utils.py:68-91 calculate_shape_IoU; the accuracy scores of sklearn.metrics are functions of the confusion matrix)

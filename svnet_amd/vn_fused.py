@@ -13,7 +13,8 @@ svnet_amd/sa_fused.py: the modules stay as they are, this is an entry beside the
 
     folded = fold_vn_layer(layer)                      # a VNLinearLeakyReLU over 2C -> O; buffers allocated once, refresh()
     out = vn_edge_mean(x, idx, folded, out=None)       # x [B,C,3,N] f32, idx [B,N,k] int64 -> [B,O,3,N]
-    fused = FusedVNDGCNN(model)                        # an nn.Module: the eval-mode forward of a VN_DGCNN_CLS
+    fused = FusedVNDGCNN(model, tail=False)            # an nn.Module: the eval-mode forward of a VN_DGCNN_CLS; tail=True: the rest of
+                                                       # the network through svnet_amd.vn_tail.FusedVNTail as well
     logits = fused(x)                                  # x [B,3,N]; fused.last_idx: the four neighbour lists of this call
 
 The contract, for one cloud (fl() is rounding to fp32, every operation rounded once, nothing contracted but the stated fmaf;
@@ -175,9 +176,11 @@ class FusedVNDGCNN(torch.nn.Module):
     call with a level outside the kernels' limits (`supported`), goes through the model's own forward.  `last_idx`: the four
     neighbour lists of the last fused call, so that a comparison can replay them into the model.  The wrapper's own `training` flag
     is the model's at construction and follows train() / eval() called on the wrapper; forward reads the model's flag, so a mode
-    set on the model directly is honoured as well.  release() frees the levels' outgrown table workspaces (FoldedVNLayer)."""
+    set on the model directly is honoured as well.  release() frees the levels' outgrown table workspaces (FoldedVNLayer).
+    tail=True: what follows the levels runs through svnet_amd.vn_tail.FusedVNTail (conv5, the cloud mean, VNStdFeature and the pools
+    on kernels, the head through the model's layers) instead of model.tail; refresh() and release() reach it."""
 
-    def __init__(self, model):
+    def __init__(self, model, tail=False):
         from .models.vn_dgcnn_cls import VN_DGCNN_CLS
         from .models.vn_layers import mean_pool
         super().__init__()
@@ -188,15 +191,23 @@ class FusedVNDGCNN(torch.nn.Module):
         self.mean = all(pool is mean_pool for _, pool in model.edge_levels())
         self.levels = [fold_vn_layer(conv) for conv, _ in model.edge_levels()] if self.mean else []
         self.last_idx = None
+        self.__dict__["tail"] = None                        # (kept out of the module registry: it holds the same model)
+        if tail and self.mean:
+            from .vn_tail import FusedVNTail
+            self.__dict__["tail"] = FusedVNTail(model)
 
     def refresh(self):
         for level in self.levels:
             level.refresh()
+        if self.tail is not None:
+            self.tail.refresh()
         return self
 
     def release(self):
         for level in self.levels:
             level.release()
+        if self.tail is not None:
+            self.tail.release()
         return self
 
     def supported(self, N, k):
@@ -237,4 +248,4 @@ class FusedVNDGCNN(torch.nn.Module):
             feats.append(out)
             h = out
         self.last_idx = used
-        return self.model.tail(feats)
+        return self.model.tail(feats) if self.tail is None else self.tail(feats)

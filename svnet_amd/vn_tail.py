@@ -1,0 +1,343 @@
+"""Fused vector-neuron tail for inference: conv5, the cloud mean, VNStdFeature and the [amax | mean] pool of VN_DGCNN_CLS.tail as
+per-point kernels (svnet_amd/csrc/vn_tail.hip), and the eval-mode tail of the classifier on top of them.
+
+In torch operations the tail works on [B, 341, 3, N] and [B, 682, 3, N] tensors and writes and re-reads more than twenty of them.
+Here a VNLinearLeakyReLU is one launch that writes its 3 O floats per point and nothing else, the mean over the points is one launch,
+and VNStdFeature's frame, its einsum and the two pools are one launch and a small finish that never write the [B, 2046, N] tensor.
+`both = [local | mean_N(local) expanded]` is never built: half of vn1's K axis is constant over a cloud,
+
+    W both = W[:, :341] local + W[:, 341:] m,
+
+so the second term is one small product per cloud (the cloud term) and the chain of a point starts from it.  Training is out of
+scope, as in svnet_amd/vn_fused.py: the modules stay as they are, this is an entry beside them.
+
+    folded = fold_vn_point(layer, cloud_channels=0)    # a VNLinearLeakyReLU over C + Cg -> O; buffers allocated once, refresh()
+    out = vn_point(x, folded, cloud=None, out=None)    # x [B,C,3,N], cloud [B,Cg,3] -> [B,O,3,N]
+    m = vn_cloud_mean(x, out=None)                     # x [B,C,3,N] -> [B,C,3]
+    h = vn_std_pool(x, y, w_lin, cloud=None, out=None) # x [B,C,3,N], y [B,Cy,3,N], w_lin [3,Cy], cloud [B,Cg,3] -> [B, 6 (C + Cg)]
+    tail = FusedVNTail(model)                          # the four levels' outputs -> logits; vn_fused.FusedVNDGCNN(model, tail=True)
+
+The contract, for one cloud (fl() is rounding to fp32, every operation rounded once, nothing contracted but the stated fmaf;
+EPS = fl(1e-6); inputs are assumed finite):
+
+    fold        W_f = map_to_feat.weight [O, C + Cg], W_d = map_to_dir.weight [Od, C + Cg], Od = O or 1 (share_nonlinearity: every o
+                uses direction row 0); W = [W_f | W_d] stacked.  s, t from BatchNorm's running statistics as vn_fused has them:
+                invstd = fl(1 / fl(sqrt(fl(var + eps)))), s = fl(gamma invstd), t = fl(beta - fl(mean s)).
+    cloud term  per row r of W and component a: u = +0; for c ascending over Cg: u = fmaf(g[c,a], W[r, C + c], u).
+    point term  per (n, a) and row r: acc = u[r,a]; for c ascending over C: acc = fmaf(x[c,a,n], W[r,c], acc).  K is never split.
+                p[o,a] are the W_f rows, d[od,a] the W_d rows.
+    norm        q = fl(p0 p0), then fmaf in p1 and p2;  r = fl(fl(sqrt(q)) + EPS);  nb = fmaf(r, s[o], t[o]);  g = fl(nb / r);
+                p'[a] = fl(p[a] g).
+    leaky       dot and dd are 3-term chains like q, of p' d and d d.  If dot >= 0 then w = p'; otherwise c = fl(dot / fl(dd + EPS))
+                and w[a] = fmaf(-c, d[a], p'[a]).  out[o,a,n] = fmaf(slope, p'[a], fl(fl(1 - slope) w[a])).
+    cloud mean  run j holds n in [64 j, min(N, 64 j + 64)); a run's sum is n-ascending plain additions from +0;
+                m = fl((the runs' sums added j-ascending from +0) / fl(N)).  The order is the contract's, not the tiling's.
+    std-pool    frame rows z[k][a](n) = +0, then fmaf(y[c,a,n], w_lin[k,c], z) for c ascending over Cy; with v_i = x[i,:,n] for i < C
+                and g[i-C,:] otherwise, e[i,k](n) = fmaf(v_i[2], z[k][2], fmaf(v_i[1], z[k][1], fl(v_i[0] z[k][0])));  with I = C + Cg,
+                h[3 i + k] = max over n of e, h[3 I + 3 i + k] = the mean of e under the cloud-mean rule.
+    limits      1 <= N <= 32768, 1 <= C <= 512, 0 <= Cg <= 512, 1 <= O <= 512, Od is O or 1, 1 <= Cy <= 512, B <= 65535
+                (`supported_point`, `supported_std`).
+
+The norm and leaky arithmetic is the edge level's (vn_fused.py), and the module's order differs from it in rounding only.
+tests/vn_tail_ref.py restates the contract in numpy; the kernels' results are compared with it as bit patterns (a -0 counted as +0).
+No argument may require grad.  There is no CPU fallback: tensors that are not on a HIP device raise.
+"""
+import torch
+
+from . import _call, _lib, _pointset
+
+__all__ = ["fold_vn_point", "vn_point", "vn_cloud_mean", "vn_std_pool", "supported_point", "supported_std", "FoldedVNPoint", "FusedVNTail",
+           "MAX_C", "MAX_O", "MAX_B"]
+
+_WHAT = "the fused vector-neuron tail"   # in the messages of _pointset.check_tensors
+MAX_C, MAX_O, MAX_B = 512, 512, 65535
+_F32 = torch.float32
+
+
+def supported_point(N, C, Cg, O, Od):
+    """Whether the point-level kernel takes this layer (module docstring, limits)."""
+    return bool(_lib.lib().svnet_vn_point_supported(int(N), int(C), int(Cg), int(O), int(Od)))
+
+
+def supported_std(N, C, Cg, Cy):
+    """Whether the standardise-and-pool kernel takes these widths (module docstring, limits)."""
+    return bool(_lib.lib().svnet_vn_std_pool_supported(int(N), int(C), int(Cg), int(Cy)))
+
+
+class _Workspace:
+    """A byte buffer that grows to the largest need seen and is then reused.  One that was outgrown stays allocated, because a graph
+    captured with it goes on replaying into it, until release()."""
+
+    def __init__(self, device):
+        self.device, self.buffer, self._retired = device, None, []
+
+    def take(self, need):
+        if self.buffer is None or self.buffer.numel() < need:
+            if self.buffer is not None:
+                self._retired.append(self.buffer)
+            self.buffer = torch.empty(max(int(need), 1), dtype=torch.uint8, device=self.device)
+        return self.buffer
+
+    def release(self):
+        self._retired.clear()
+
+
+class FoldedVNPoint:
+    """The folded form of one VNLinearLeakyReLU over C + Cg -> O vector channels whose last Cg input channels are constant over a
+    cloud: WT [C + Cg, O + Od] | s [O] | t [O] in one buffer on the layer's device, allocated once, and the workspace of the cloud
+    term, which grows to the largest B seen and is then reused.  refresh() runs the fold again - after the parameters or the running
+    statistics changed - on the current stream, one launch.  release() frees outgrown workspaces: only when no captured graph that
+    was recorded with one of them will be replayed again."""
+
+    def __init__(self, layer, cloud_channels=0):
+        from .models.vn_layers import VNLinearLeakyReLU
+        if not isinstance(layer, VNLinearLeakyReLU):
+            raise TypeError("fold_vn_point: needs a VNLinearLeakyReLU, got %s" % type(layer).__name__)
+        bn = layer.batchnorm.bn
+        wf, wd = layer.map_to_feat.weight, layer.map_to_dir.weight
+        Cg = int(cloud_channels)
+        if wf.shape[1] != wd.shape[1] or wd.shape[0] not in (wf.shape[0], 1) or int(bn.num_features) != wf.shape[0]:
+            raise ValueError("fold_vn_point: map_to_feat %s, map_to_dir %s, BatchNorm over %d: needs one input width, O or 1 direction rows"
+                             % (tuple(wf.shape), tuple(wd.shape), bn.num_features))
+        if Cg < 0 or Cg >= wf.shape[1]:
+            raise ValueError("fold_vn_point: cloud_channels = %d of %d input channels: needs 0 <= cloud_channels < the input width" % (Cg, wf.shape[1]))
+        if bn.running_mean is None or bn.running_var is None or bn.weight is None or bn.bias is None:
+            raise ValueError("fold_vn_point: the BatchNorm must be affine and track running statistics")
+        for k, t in {"map_to_feat.weight": wf, "map_to_dir.weight": wd, "bn.weight": bn.weight, "bn.bias": bn.bias,
+                     "running_mean": bn.running_mean, "running_var": bn.running_var}.items():
+            if t.dtype != _F32 or not t.is_contiguous() or t.device != wf.device:
+                raise ValueError("fold_vn_point: %s must be contiguous float32 on %s" % (k, wf.device))
+        self.device = _pointset.hip_device("fold_vn_point", wf.device)
+        self.layer = layer
+        self.C, self.Cg, self.O, self.Od = int(wf.shape[1]) - Cg, Cg, int(wf.shape[0]), int(wd.shape[0])
+        if not supported_point(1, self.C, self.Cg, self.O, self.Od):
+            raise _lib.SvnetHipError("fold_vn_point: C = %d, Cg = %d, O = %d is not supported (1 <= C <= %d, Cg <= %d, 1 <= O <= %d)"
+                                     % (self.C, self.Cg, self.O, MAX_C, MAX_C, MAX_O))
+        self.folded = torch.empty((self.C + self.Cg) * (self.O + self.Od) + 2 * self.O, dtype=_F32, device=self.device)
+        self._ws = _Workspace(self.device)
+        self.refresh()
+
+    @property
+    def slope(self):
+        return float(self.layer.negative_slope)
+
+    @property
+    def workspace(self):
+        return self._ws.buffer
+
+    def refresh(self):
+        layer, bn = self.layer, self.layer.batchnorm.bn
+        if layer.map_to_feat.weight.device != self.device:
+            raise ValueError("fold_vn_point: the layer moved from %s to %s - fold it again" % (self.device, layer.map_to_feat.weight.device))
+        with torch.cuda.device(self.device):
+            _lib.call("svnet_vn_point_fold_f32", _call.p(layer.map_to_feat.weight.detach()), _call.p(layer.map_to_dir.weight.detach()),
+                      _call.p(bn.weight.detach()), _call.p(bn.bias.detach()), _call.p(bn.running_mean), _call.p(bn.running_var), self.C, self.Cg,
+                      self.O, self.Od, float(bn.eps), _call.p(self.folded), _call.stream())
+        return self
+
+    def cloud_terms(self, B):
+        """The workspace of the cloud term for B clouds (uint8; one byte when Cg = 0)."""
+        return self._ws.take(int(_lib.lib().svnet_vn_point_workspace_bytes(B, self.Cg, self.O, self.Od)))
+
+    def release(self):
+        self._ws.release()
+        return self
+
+
+def fold_vn_point(layer, cloud_channels=0):
+    """A VNLinearLeakyReLU on a HIP device whose last `cloud_channels` input channels are constant over a cloud -> FoldedVNPoint."""
+    return FoldedVNPoint(layer, cloud_channels)
+
+
+def _check(name, args):
+    """The established order: tensors and dtypes, device match, contiguity, gradients (check_tensors); shapes are the caller's next."""
+    _pointset.check_tensors(name, {k: t for k, t in args.items() if t is not None}, [_F32] * len([t for t in args.values() if t is not None]), _WHAT)
+
+
+def _cloud_shape(name, cloud, B, Cg):
+    if Cg == 0 and cloud is None:
+        return
+    if cloud is None or cloud.dim() != 3 or tuple(cloud.shape) != (B, Cg, 3) or Cg == 0:
+        raise ValueError("%s: cloud must be [B,Cg,3] = %s%s, got %s" % (name, (B, Cg, 3), " (None with no constant channels)" if Cg == 0 else "",
+                                                                        None if cloud is None else tuple(cloud.shape)))
+
+
+def _launch_point(x, cloud, folded, out, B, N):
+    ws = folded.cloud_terms(B)
+    with torch.cuda.device(x.device):
+        _lib.call("svnet_vn_point_f32", _call.p(x), _call.p(cloud), _call.p(folded.folded), B, N, folded.C, folded.Cg, folded.O, folded.Od, folded.slope,
+                  _call.p(ws), ws.numel() if folded.Cg else 0, _call.p(out), _call.stream())
+
+
+def vn_point(x, folded, cloud=None, out=None):
+    """x [B,C,3,N] float32, folded a FoldedVNPoint over C + Cg -> O, cloud [B,Cg,3] (the channels that are constant over a cloud; None
+    with Cg = 0) -> out [B,O,3,N]: the layer's eval-mode forward on [x | cloud expanded over the points] (module docstring).  One
+    launch on the current stream, and a small one in front of it with Cg > 0; no host read.  No argument may require grad."""
+    name = "vn_point"
+    if not isinstance(folded, FoldedVNPoint):
+        raise TypeError("%s: folded must be a FoldedVNPoint (vn_tail.fold_vn_point), got %s" % (name, type(folded).__name__))
+    _check(name, {"x": x, "cloud": cloud, "out": out})
+    if x.dim() != 4 or x.shape[2] != 3 or x.shape[0] < 1:
+        raise ValueError("%s: x must be [B,C,3,N], got %s" % (name, tuple(x.shape)))
+    B, C, _, N = (int(v) for v in x.shape)
+    if C != folded.C:
+        raise ValueError("%s: the layer takes %d vector channels per point, x has %d" % (name, folded.C, C))
+    _cloud_shape(name, cloud, B, folded.Cg)
+    if out is not None and tuple(out.shape) != (B, folded.O, 3, N):
+        raise ValueError("%s: out must be [B,O,3,N] = %s, got %s" % (name, (B, folded.O, 3, N), tuple(out.shape)))
+    _call.hip(x, cloud, out)
+    if folded.device != x.device:
+        raise ValueError("%s: the layer is on %s, x on %s" % (name, folded.device, x.device))
+    if B > MAX_B or not supported_point(N, C, folded.Cg, folded.O, folded.Od):
+        raise _lib.SvnetHipError("%s: B = %d, N = %d, C = %d, O = %d is not supported (B <= %d, 1 <= N <= %d, C <= %d, O <= %d)"
+                                 % (name, B, N, C, folded.O, MAX_B, _pointset.MAX_N, MAX_C, MAX_O))
+    if out is None:
+        out = torch.empty(B, folded.O, 3, N, dtype=_F32, device=x.device)
+    _launch_point(x, cloud, folded, out, B, N)
+    return out
+
+
+def vn_cloud_mean(x, out=None):
+    """x [B,C,3,N] float32 -> out [B,C,3]: the mean over the points in the contract's order (module docstring).  One launch on the
+    current stream, no host read.  No argument may require grad."""
+    name = "vn_cloud_mean"
+    _check(name, {"x": x, "out": out})
+    if x.dim() != 4 or x.shape[2] != 3 or x.shape[0] < 1:
+        raise ValueError("%s: x must be [B,C,3,N], got %s" % (name, tuple(x.shape)))
+    B, C, _, N = (int(v) for v in x.shape)
+    if out is not None and tuple(out.shape) != (B, C, 3):
+        raise ValueError("%s: out must be [B,C,3] = %s, got %s" % (name, (B, C, 3), tuple(out.shape)))
+    _call.hip(x, out)
+    if B > MAX_B or not supported_point(N, C, 0, 1, 1):
+        raise _lib.SvnetHipError("%s: B = %d, N = %d, C = %d is not supported (B <= %d, 1 <= N <= %d, 1 <= C <= %d)" % (name, B, N, C, MAX_B, _pointset.MAX_N, MAX_C))
+    if out is None:
+        out = torch.empty(B, C, 3, dtype=_F32, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.call("svnet_vn_cloud_mean_f32", _call.p(x), B, C, N, _call.p(out), _call.stream())
+    return out
+
+
+_std_workspaces = {}     # device -> _Workspace of vn_std_pool calls that bring none
+
+
+def vn_std_pool(x, y, w_lin, cloud=None, out=None, workspace=None):
+    """x [B,C,3,N], y [B,Cy,3,N] (vn2's output), w_lin [3,Cy] (vn_lin.weight as it lies), cloud [B,Cg,3] or None -> out [B, 6 I],
+    I = C + Cg: the coordinates of [x | cloud expanded] in the frame w_lin y, pooled [amax | mean] over the points (module docstring).
+    Two launches on the current stream, no host read.  workspace: a _Workspace to take the per-run partials from (FusedVNTail's);
+    without one the calls of a device share a buffer that grows.  No argument may require grad."""
+    name = "vn_std_pool"
+    _check(name, {"x": x, "y": y, "w_lin": w_lin, "cloud": cloud, "out": out})
+    if x.dim() != 4 or x.shape[2] != 3 or x.shape[0] < 1:
+        raise ValueError("%s: x must be [B,C,3,N], got %s" % (name, tuple(x.shape)))
+    B, C, _, N = (int(v) for v in x.shape)
+    if y.dim() != 4 or y.shape[0] != B or y.shape[2] != 3 or y.shape[3] != N or y.shape[1] < 1:
+        raise ValueError("%s: y must be [B,Cy,3,N] with B = %d, N = %d, got %s" % (name, B, N, tuple(y.shape)))
+    Cy = int(y.shape[1])
+    if tuple(w_lin.shape) != (3, Cy):
+        raise ValueError("%s: w_lin must be [3,Cy] = %s (normalize_frame = False), got %s" % (name, (3, Cy), tuple(w_lin.shape)))
+    Cg = 0 if cloud is None else int(cloud.shape[1]) if cloud.dim() == 3 else -1
+    if cloud is not None and (Cg < 1 or tuple(cloud.shape) != (B, Cg, 3)):
+        raise ValueError("%s: cloud must be [B,Cg,3] with B = %d, got %s" % (name, B, tuple(cloud.shape)))
+    cols = 6 * (C + Cg)
+    if out is not None and tuple(out.shape) != (B, cols):
+        raise ValueError("%s: out must be [B, 6 (C + Cg)] = %s, got %s" % (name, (B, cols), tuple(out.shape)))
+    _call.hip(x, y, w_lin, cloud, out)
+    if B > MAX_B or not supported_std(N, C, Cg, Cy):
+        raise _lib.SvnetHipError("%s: B = %d, N = %d, C = %d, Cg = %d, Cy = %d is not supported (B <= %d, 1 <= N <= %d, C, Cg, Cy <= %d)"
+                                 % (name, B, N, C, Cg, Cy, MAX_B, _pointset.MAX_N, MAX_C))
+    if out is None:
+        out = torch.empty(B, cols, dtype=_F32, device=x.device)
+    if workspace is None:
+        workspace = _std_workspaces.setdefault(x.device, _Workspace(x.device))
+    ws = workspace.take(int(_lib.lib().svnet_vn_std_pool_workspace_bytes(B, N, C, Cg)))
+    with torch.cuda.device(x.device):
+        _lib.call("svnet_vn_std_pool_f32", _call.p(x), _call.p(cloud), _call.p(y), _call.p(w_lin), B, N, C, Cg, Cy, _call.p(ws), ws.numel(), _call.p(out),
+                  _call.stream())
+    return out
+
+
+class FusedVNTail(torch.nn.Module):
+    """The eval-mode tail of a VN_DGCNN_CLS on a HIP device: forward(feats) maps the four levels' outputs [B,C_i,3,N] to logits, as
+    model.tail does.  The steps: torch.cat of the feats (one copy of 3 x 169 N floats per cloud: 2 % of the tail's traffic - the edge
+    levels' entry has no channel window to write into one buffer), conv5, the cloud mean, vn1 with cloud = m, vn2, the
+    standardise-and-pool stage, then the head through the model's own linear*, bn* and dp* modules.  `pooled(feats)` is everything in
+    front of the head: h [B, 4092].  The three layers are folded at construction; refresh() folds them again after the parameters or
+    the running statistics changed; release() frees outgrown workspaces.  Train mode is refused.  A model whose std_feature has
+    normalize_frame set, or widths or a call outside the kernels' limits (`supported`), goes through model.tail."""
+
+    def __init__(self, model):
+        from .models.vn_dgcnn_cls import VN_DGCNN_CLS
+        super().__init__()
+        if not isinstance(model, VN_DGCNN_CLS):
+            raise TypeError("FusedVNTail: needs a VN_DGCNN_CLS, got %s" % type(model).__name__)
+        self.model = model
+        self.training = model.training
+        std = model.std_feature
+        wide = model.conv5.map_to_feat.weight.shape[0]
+        self.widths = [(int(l.map_to_feat.weight.shape[1]) - cg, cg, int(l.map_to_feat.weight.shape[0]), int(l.map_to_dir.weight.shape[0]))
+                       for l, cg in ((model.conv5, 0), (std.vn1, int(wide)), (std.vn2, 0))]
+        self.Cy = int(std.vn_lin.weight.shape[1])
+        self.fused = bool(not std.normalize_frame and all(c >= 1 and supported_point(1, c, cg, o, od) for c, cg, o, od in self.widths)
+                          and supported_std(1, wide, wide, self.Cy))
+        self.layers = [fold_vn_point(l, cg) for l, cg in ((model.conv5, 0), (std.vn1, int(wide)), (std.vn2, 0))] if self.fused else []
+        self._std_ws = _Workspace(self.layers[0].device) if self.fused else None
+
+    def refresh(self):
+        for layer in self.layers:
+            layer.refresh()
+        return self
+
+    def release(self):
+        for layer in self.layers:
+            layer.release()
+        if self._std_ws is not None:
+            self._std_ws.release()
+        return self
+
+    def supported(self, B, N):
+        """Whether B clouds of N points take the fused path here; else forward runs model.tail."""
+        return bool(self.fused and 1 <= B <= MAX_B and all(supported_point(N, c, cg, o, od) for c, cg, o, od in self.widths)
+                    and supported_std(N, self.widths[0][2], self.widths[0][2], self.Cy))
+
+    def _feats(self, feats):
+        name = "FusedVNTail"
+        if self.model.training:
+            raise RuntimeError("%s: the model is in train mode - this is the eval-mode forward (model.eval())" % name)
+        feats = list(feats)
+        if not feats:
+            raise ValueError("%s: feats must hold the levels' outputs [B,C_i,3,N]" % name)
+        _pointset.check_tensors(name, {"feats[%d]" % i: f for i, f in enumerate(feats)}, [_F32] * len(feats), _WHAT)
+        first = feats[0]
+        if any(f.dim() != 4 or f.shape[2] != 3 or f.shape[0] != first.shape[0] or f.shape[3] != first.shape[3] or f.shape[0] < 1 for f in feats):
+            raise ValueError("%s: feats must be [B,C_i,3,N] with one B and N, got %s" % (name, [tuple(f.shape) for f in feats]))
+        _call.hip(*feats)
+        return feats
+
+    @torch.no_grad()
+    def pooled(self, feats):
+        """The tail in front of the head on the kernels: feats -> h [B, 6 x 682]; raises outside `supported`."""
+        feats = self._feats(feats)
+        B, N = int(feats[0].shape[0]), int(feats[0].shape[3])
+        x = feats[0] if len(feats) == 1 else torch.cat(feats, dim=1)
+        if not self.supported(B, N) or int(x.shape[1]) != self.widths[0][0]:
+            raise _lib.SvnetHipError("FusedVNTail: B = %d, N = %d, %d channels is outside the fused tail (`supported`)" % (B, N, x.shape[1]))
+        if self.layers[0].device != x.device:
+            raise ValueError("FusedVNTail: the model is on %s, feats on %s" % (self.layers[0].device, x.device))
+        conv5, vn1, vn2 = self.layers
+        local = vn_point(x, conv5)
+        m = vn_cloud_mean(local)
+        y = vn_point(vn_point(local, vn1, cloud=m), vn2)
+        return vn_std_pool(local, y, self.model.std_feature.vn_lin.weight.detach(), cloud=m, workspace=self._std_ws)
+
+    @torch.no_grad()
+    def forward(self, feats):
+        feats = self._feats(feats)
+        B, N = int(feats[0].shape[0]), int(feats[0].shape[3])
+        if not self.supported(B, N) or sum(int(f.shape[1]) for f in feats) != self.widths[0][0]:
+            return self.model.tail(feats)
+        h = self.pooled(feats)
+        model = self.model
+        for layer in (1, 2):
+            linear, bn, drop = (getattr(model, "%s%d" % (n, layer)) for n in ("linear", "bn", "dp"))
+            h = drop(torch.nn.functional.leaky_relu(bn(linear(h)), negative_slope=0.2))
+        return model.linear3(h)
