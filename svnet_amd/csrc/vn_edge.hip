@@ -18,20 +18,20 @@
 //                     the classifier's widest level, stays in that XCD's L2.
 // Table rows: [P: a O + o | Q: 3 O + a Od + od] for component a; TN (gathered by neighbour) holds Pn | Qn, TC (the centre's) Pc | Qc;
 // the workspace is [TN | TC], each [B][N][3 (O + Od)].  Built with -ffp-contract=off (Makefile, NO_CONTRACT): every product, sum,
-// quotient and square root is its own correctly rounded fp32 operation; fmaf is written where the contract has one.
-#include "pointset.h"
+// quotient and square root is its own correctly rounded fp32 operation.  The fold of the statistics and the norm / leaky rule are
+// vn_math.h's, shared with vn_tail.hip.
+#include "vn_math.h"
 
 namespace {
 
 constexpr int VN_THREADS = 256;
-constexpr int VN_MAX_N = SVNET_KNN_MAX_N, VN_MAX_K = 64, VN_MAX_C = 128, VN_MAX_O = 128;      // the envelope (svnet_vn_supported)
+constexpr int VN_MAX_K = 64, VN_MAX_C = 128, VN_MAX_O = 128;      // the envelope (svnet_vn_supported)
 constexpr int VN_QT = 16;           // (component, point) pairs per wave of the tables kernel
 constexpr int VN_P = 16;            // points per workgroup of the edge kernel
 constexpr int VN_PP = VN_P + 1;     // row stride of the LDS image of the means: odd, so that o-adjacent lanes fall on distinct banks
-constexpr float VN_EPS = 1e-6f;     // EPS of models/vn_layers.py:14
 
 inline bool vn_ok(int64_t N, int64_t k, int64_t C, int64_t O, int64_t Od) {
-    return k >= 1 && k <= VN_MAX_K && N >= k && N <= VN_MAX_N && C >= 1 && C <= VN_MAX_C && O >= 1 && O <= VN_MAX_O && (Od == O || Od == 1);
+    return k >= 1 && k <= VN_MAX_K && N >= k && N <= VN_MAX_N && C >= 1 && C <= VN_MAX_C && O >= 1 && O <= VN_MAX_O && vn_dir_rows_ok(O, Od);
 }
 inline int64_t vn_row(int64_t O, int64_t Od) { return 3 * (O + Od); }
 inline int64_t vn_cols(int64_t O, int64_t Od) { return 2 * (O + Od); }
@@ -52,10 +52,7 @@ __global__ __launch_bounds__(VN_THREADS) void vn_fold_kernel(const float* __rest
         folded[e] = diff ? row[C + c] - row[c] : row[c];
     } else if (e < CR + O) {
         const int o = e - CR;
-        const float invstd = 1.f / sqrtf(rvar[o] + eps);             // sa_fold_kernel's (sa_fused.hip)
-        const float s = gamma[o] * invstd;
-        folded[CR + o] = s;
-        folded[CR + O + o] = beta[o] - rmean[o] * s;
+        vn_bn_fold(gamma[o], beta[o], rmean[o], rvar[o], eps, folded[CR + o], folded[CR + O + o]);
     }
 }
 
@@ -149,24 +146,11 @@ __global__ __launch_bounds__(VN_THREADS) void vn_edge_kernel(const float* __rest
             const float* tn = tnb + nb[j] * ROW;
             const float p0 = tn[po] + pc0, p1 = tn[po + O] + pc1, p2 = tn[po + 2 * O] + pc2;
             const float d0 = tn[qo] + qc0, d1 = tn[qo + Od] + qc1, d2 = tn[qo + 2 * Od] + qc2;
-            // the norm through BatchNorm's folded affine
-            const float q = fmaf(p2, p2, fmaf(p1, p1, p0 * p0));
-            const float r = sqrtf(q) + VN_EPS;
-            const float g = fmaf(r, so, to) / r;
-            const float u0 = p0 * g, u1 = p1 * g, u2 = p2 * g;
-            // the leaky rule
-            const float dot = fmaf(u2, d2, fmaf(u1, d1, u0 * d0));
-            const float dd = fmaf(d2, d2, fmaf(d1, d1, d0 * d0));
-            float w0 = u0, w1 = u1, w2 = u2;
-            if (!(dot >= 0.f)) {
-                const float c = -(dot / (dd + VN_EPS));
-                w0 = fmaf(c, d0, u0);
-                w1 = fmaf(c, d1, u1);
-                w2 = fmaf(c, d2, u2);
-            }
-            y0 += fmaf(slope, u0, one_minus * w0);
-            y1 += fmaf(slope, u1, one_minus * w1);
-            y2 += fmaf(slope, u2, one_minus * w2);
+            float y[3];
+            vn_norm_leaky(p0, p1, p2, d0, d1, d2, so, to, slope, one_minus, y);
+            y0 += y[0];
+            y1 += y[1];
+            y2 += y[2];
         }
         float* sy = s_y + (o * 3) * VN_PP + p;
         sy[0] = y0 / kf;

@@ -3,7 +3,7 @@
 // include/svnet_hip.h ("fused vector-neuron tail for inference") and svnet_amd/vn_tail.py; tests/vn_tail_ref.py restates it.
 //
 //   vn_point_fold_kernel   [W_f | W_d] transposed into WT [C + Cg][R], R = O + Od, so that a wave reads consecutive columns of one c;
-//                          BatchNorm's running statistics folded into s, t [O] (vn_fold_kernel's arithmetic, vn_edge.hip).
+//                          BatchNorm's running statistics folded into s, t [O].
 //   vn_cloud_term_kernel   u [B][3][R]: per cloud the chain over the Cg channels that are constant over it (Cg > 0 only).
 //   vn_point_kernel        the eval forward of a VNLinearLeakyReLU per point.  A workgroup takes TP = 16 NPT consecutive points of a
 //                          cloud and stages their x, all K channels x 3 components, in LDS once; NPT is the largest of 4, 2, 1 whose
@@ -18,9 +18,9 @@
 //                          slabs of 64 through LDS; a thread owns a column (i, k) and walks the run's points n-ascending, keeping the
 //                          maximum and the sum, which go to the workspace as per-run partials.
 //   vn_std_finish_kernel   per column the maximum of the runs' maxima and the runs' sums added in order (split_reduce.h), over fl(N).
-// The norm / BatchNorm / leaky arithmetic is vn_edge_kernel's, restated here (vt_leaky) and not shared through a header: vn_edge.hip
-// stays byte for byte what it was.  Built with -ffp-contract=off (Makefile, NO_CONTRACT).  No atomics.
-#include "pointset.h"
+// The fold of the statistics and the norm / BatchNorm / leaky arithmetic are vn_math.h's, shared with vn_edge.hip.  Built with
+// -ffp-contract=off (Makefile, NO_CONTRACT).  No atomics.
+#include "vn_math.h"
 #include "split_reduce.h"
 #include <type_traits>
 
@@ -29,20 +29,19 @@ namespace {
 typedef __attribute__((ext_vector_type(4))) float vt_f32x4;
 
 constexpr int VT_THREADS = 256, VT_WAVES = VT_THREADS / SVNET_WAVE;
-constexpr int VT_MAX_N = SVNET_KNN_MAX_N, VT_MAX_C = 512, VT_MAX_O = 512, VT_MAX_B = 65535;      // the envelope
+constexpr int VT_MAX_C = 512, VT_MAX_O = 512, VT_MAX_B = 65535;      // the envelope
 constexpr int VT_RUN = 64;              // points per run of the ordered sums: part of the contract
 constexpr int VT_LDS_MAX = 160 * 1024;
 constexpr int VT_SLAB = 64;             // channels per LDS slab of the std-pool kernel
 constexpr int VT_VS = 3 * VT_RUN + 1;   // floats per channel of a slab: odd, so that channel-adjacent lanes fall on distinct banks
 constexpr int VT_SU = 8;                // loads of a thread in flight while x is staged
 constexpr int VT_U = 8;                 // k-steps whose weights a lane holds at a time: 32 channels
-constexpr float VT_EPS = 1e-6f;         // EPS of models/vn_layers.py
 
 inline bool vt_point_ok(int64_t N, int64_t C, int64_t Cg, int64_t O, int64_t Od) {
-    return N >= 1 && N <= VT_MAX_N && C >= 1 && C <= VT_MAX_C && Cg >= 0 && Cg <= VT_MAX_C && O >= 1 && O <= VT_MAX_O && (Od == O || Od == 1);
+    return N >= 1 && N <= VN_MAX_N && C >= 1 && C <= VT_MAX_C && Cg >= 0 && Cg <= VT_MAX_C && O >= 1 && O <= VT_MAX_O && vn_dir_rows_ok(O, Od);
 }
 inline bool vt_std_ok(int64_t N, int64_t C, int64_t Cg, int64_t Cy) {
-    return N >= 1 && N <= VT_MAX_N && C >= 1 && C <= VT_MAX_C && Cg >= 0 && Cg <= VT_MAX_C && Cy >= 1 && Cy <= VT_MAX_C;
+    return N >= 1 && N <= VN_MAX_N && C >= 1 && C <= VT_MAX_C && Cg >= 0 && Cg <= VT_MAX_C && Cy >= 1 && Cy <= VT_MAX_C;
 }
 inline bool vt_batch_ok(int64_t B) { return B >= 1 && B <= VT_MAX_B; }
 
@@ -68,10 +67,7 @@ __global__ __launch_bounds__(VT_THREADS) void vn_point_fold_kernel(const float* 
         folded[e] = r < O ? wf[(int64_t)r * K + c] : wd[(int64_t)(r - O) * K + c];
     } else if (e < KR + O) {
         const int o = e - KR;
-        const float invstd = 1.f / sqrtf(rvar[o] + eps);             // vn_fold_kernel's (vn_edge.hip)
-        const float s = gamma[o] * invstd;
-        folded[KR + o] = s;
-        folded[KR + O + o] = beta[o] - rmean[o] * s;
+        vn_bn_fold(gamma[o], beta[o], rmean[o], rvar[o], eps, folded[KR + o], folded[KR + O + o]);
     }
 }
 
@@ -87,27 +83,6 @@ __global__ __launch_bounds__(VT_THREADS) void vn_cloud_term_kernel(const float* 
     float acc = 0.f;
     for (int c = 0; c < Cg; ++c) acc = fmaf(gb[3 * c], w[(int64_t)c * R], acc);
     u[e] = acc;
-}
-
-// The norm through BatchNorm's folded affine and the leaky rule: vn_edge_kernel's arithmetic (vn_edge.hip), restated.
-__device__ __forceinline__ void vt_leaky(float p0, float p1, float p2, float d0, float d1, float d2, float so, float to, float slope, float one_minus,
-                                         float (&y)[3]) {
-    const float q = fmaf(p2, p2, fmaf(p1, p1, p0 * p0));
-    const float r = sqrtf(q) + VT_EPS;
-    const float g = fmaf(r, so, to) / r;
-    const float u0 = p0 * g, u1 = p1 * g, u2 = p2 * g;
-    const float dot = fmaf(u2, d2, fmaf(u1, d1, u0 * d0));
-    const float dd = fmaf(d2, d2, fmaf(d1, d1, d0 * d0));
-    float w0 = u0, w1 = u1, w2 = u2;
-    if (!(dot >= 0.f)) {
-        const float c = -(dot / (dd + VT_EPS));
-        w0 = fmaf(c, d0, u0);
-        w1 = fmaf(c, d1, u1);
-        w2 = fmaf(c, d2, u2);
-    }
-    y[0] = fmaf(slope, u0, one_minus * w0);
-    y[1] = fmaf(slope, u1, one_minus * w1);
-    y[2] = fmaf(slope, u2, one_minus * w2);
 }
 
 // grid (ceil(N / TP), B), TP = 16 NPT.  A = the inputs from LDS (lane = point l & 15 at k = l >> 4), B = the weights from global memory
@@ -255,7 +230,7 @@ __global__ __launch_bounds__(VT_THREADS) void vn_point_kernel(const float* __res
                     d1 = accd[tt][1][i];
                     d2 = accd[tt][2][i];
                 }
-                vt_leaky(accp[tt][0][i], accp[tt][1][i], accp[tt][2][i], d0, d1, d2, so, to, slope, one_minus, y);
+                vn_norm_leaky(accp[tt][0][i], accp[tt][1][i], accp[tt][2][i], d0, d1, d2, so, to, slope, one_minus, y);
                 if (ov && n < N) {
                     ob[n] = y[0];
                     ob[(int64_t)N + n] = y[1];
@@ -410,7 +385,7 @@ extern "C" int svnet_vn_point_f32(const float* x, const float* g, const float* f
     SVNET_REQUIRE(vt_batch_ok(B), SVNET_E_ARG, "svnet_vn_point_f32: B %lld must lie in 1 .. %d", (long long)B, VT_MAX_B);
     SVNET_REQUIRE(vt_point_ok(N, C, Cg, O, Od), SVNET_E_UNSUPPORTED,
                   "svnet_vn_point_f32: N %lld, C %lld, Cg %lld, O %lld, Od %lld: needs 1 <= N <= %d, 1 <= C <= %d, 0 <= Cg <= %d, 1 <= O <= %d, Od = O or 1",
-                  (long long)N, (long long)C, (long long)Cg, (long long)O, (long long)Od, VT_MAX_N, VT_MAX_C, VT_MAX_C, VT_MAX_O);
+                  (long long)N, (long long)C, (long long)Cg, (long long)O, (long long)Od, VN_MAX_N, VT_MAX_C, VT_MAX_C, VT_MAX_O);
     SVNET_REQUIRE(workspace_bytes >= svnet_vn_point_workspace_bytes(B, Cg, O, Od), SVNET_E_WORKSPACE, "svnet_vn_point_f32: workspace of %zu bytes, needs %zu",
                   workspace_bytes, svnet_vn_point_workspace_bytes(B, Cg, O, Od));
     const int R = (int)(O + Od);
@@ -454,8 +429,8 @@ extern "C" int svnet_vn_point_f32(const float* x, const float* g, const float* f
 extern "C" int svnet_vn_cloud_mean_f32(const float* x, int64_t B, int64_t C, int64_t N, float* m, void* stream) {
     SVNET_REQUIRE(x && m, SVNET_E_ARG, "svnet_vn_cloud_mean_f32: null x / m");
     SVNET_REQUIRE(vt_batch_ok(B), SVNET_E_ARG, "svnet_vn_cloud_mean_f32: B %lld must lie in 1 .. %d", (long long)B, VT_MAX_B);
-    SVNET_REQUIRE(N >= 1 && N <= VT_MAX_N && C >= 1 && C <= VT_MAX_C, SVNET_E_UNSUPPORTED, "svnet_vn_cloud_mean_f32: N %lld, C %lld: needs 1 <= N <= %d, 1 <= C <= %d",
-                  (long long)N, (long long)C, VT_MAX_N, VT_MAX_C);
+    SVNET_REQUIRE(N >= 1 && N <= VN_MAX_N && C >= 1 && C <= VT_MAX_C, SVNET_E_UNSUPPORTED, "svnet_vn_cloud_mean_f32: N %lld, C %lld: needs 1 <= N <= %d, 1 <= C <= %d",
+                  (long long)N, (long long)C, VN_MAX_N, VT_MAX_C);
     const int64_t rows = B * C * 3;
     const int runs = (int)svnet_cdiv(N, VT_RUN), rpb = runs >= VT_THREADS ? 1 : VT_THREADS / runs;
     hipLaunchKernelGGL(vn_cloud_mean_kernel, dim3((unsigned)svnet_cdiv(rows, rpb)), dim3(VT_THREADS), 0, (hipStream_t)stream, x, rows, (int)N, runs, rpb, m);
@@ -476,7 +451,7 @@ extern "C" int svnet_vn_std_pool_f32(const float* x, const float* g, const float
     SVNET_REQUIRE(vt_batch_ok(B), SVNET_E_ARG, "svnet_vn_std_pool_f32: B %lld must lie in 1 .. %d", (long long)B, VT_MAX_B);
     SVNET_REQUIRE(vt_std_ok(N, C, Cg, Cy), SVNET_E_UNSUPPORTED,
                   "svnet_vn_std_pool_f32: N %lld, C %lld, Cg %lld, Cy %lld: needs 1 <= N <= %d, 1 <= C <= %d, 0 <= Cg <= %d, 1 <= Cy <= %d", (long long)N,
-                  (long long)C, (long long)Cg, (long long)Cy, VT_MAX_N, VT_MAX_C, VT_MAX_C, VT_MAX_C);
+                  (long long)C, (long long)Cg, (long long)Cy, VN_MAX_N, VT_MAX_C, VT_MAX_C, VT_MAX_C);
     SVNET_REQUIRE(workspace_bytes >= svnet_vn_std_pool_workspace_bytes(B, N, C, Cg), SVNET_E_WORKSPACE, "svnet_vn_std_pool_f32: workspace of %zu bytes, needs %zu",
                   workspace_bytes, svnet_vn_std_pool_workspace_bytes(B, N, C, Cg));
     const int64_t runs = svnet_cdiv(N, VT_RUN), cols = 3 * (C + Cg), total = B * cols;

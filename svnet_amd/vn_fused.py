@@ -40,7 +40,7 @@ patterns (a -0 counted as +0).  No argument may require grad.  There is no CPU f
 """
 import torch
 
-from . import _call, _lib, _pointset
+from . import _call, _lib, _pointset, _vn
 
 __all__ = ["fold_vn_layer", "vn_edge_mean", "supported", "FoldedVNLayer", "FusedVNDGCNN", "MAX_K", "MAX_C", "MAX_O"]
 
@@ -54,66 +54,24 @@ def supported(N, k, C, O, Od):
     return bool(_lib.lib().svnet_vn_supported(int(N), int(k), int(C), int(O), int(Od)))
 
 
-class FoldedVNLayer:
+class FoldedVNLayer(_vn.Folded):
     """The folded form of one VNLinearLeakyReLU over 2C -> O vector channels: WT [C, 2 (O + Od)] | s [O] | t [O] in one buffer on the
-    layer's device, allocated once, and the table workspace, which grows to the largest (B, N) seen and is then reused.  refresh()
-    runs the fold again - after the parameters or the running statistics changed - on the current stream, one launch.
-    A workspace that was outgrown stays allocated, because a graph captured with it goes on replaying into it: a caller that sweeps
-    growing (B, N) holds one buffer per growth step (134 MB at B 32, N 1024 for the classifier's widest level) until release()."""
+    layer's device, allocated once, and the table workspace, which grows to the largest (B, N) seen and is then reused (`workspace`:
+    the current one).  refresh() and release() are _vn.Folded's: a workspace that was outgrown stays allocated, so a caller that
+    sweeps growing (B, N) holds one buffer per growth step (134 MB at B 32, N 1024 for the classifier's widest level) until release()."""
+    NAME, ENTRY = "fold_vn_layer", "svnet_vn_fold_f32"
 
     def __init__(self, layer):
-        from .models.vn_layers import VNLinearLeakyReLU
-        if not isinstance(layer, VNLinearLeakyReLU):
-            raise TypeError("fold_vn_layer: needs a VNLinearLeakyReLU, got %s" % type(layer).__name__)
-        bn = layer.batchnorm.bn
-        wf, wd = layer.map_to_feat.weight, layer.map_to_dir.weight
-        if wf.shape[1] % 2 or wf.shape[1] != wd.shape[1] or wd.shape[0] not in (wf.shape[0], 1) or int(bn.num_features) != wf.shape[0]:
-            raise ValueError("fold_vn_layer: map_to_feat %s, map_to_dir %s, BatchNorm over %d: needs an even input width 2C, O or 1 direction rows"
-                             % (tuple(wf.shape), tuple(wd.shape), bn.num_features))
-        if bn.running_mean is None or bn.running_var is None or bn.weight is None or bn.bias is None:
-            raise ValueError("fold_vn_layer: the BatchNorm must be affine and track running statistics")
-        for k, t in {"map_to_feat.weight": wf, "map_to_dir.weight": wd, "bn.weight": bn.weight, "bn.bias": bn.bias,
-                     "running_mean": bn.running_mean, "running_var": bn.running_var}.items():
-            if t.dtype != _F32 or not t.is_contiguous() or t.device != wf.device:
-                raise ValueError("fold_vn_layer: %s must be contiguous float32 on %s" % (k, wf.device))
-        self.device = _pointset.hip_device("fold_vn_layer", wf.device)
-        self.layer = layer
-        self.C, self.O, self.Od = int(wf.shape[1]) // 2, int(wf.shape[0]), int(wd.shape[0])
+        wf, wd, _ = _vn.check_layer(self.NAME, layer, even=True)
+        self.place(layer)
+        self.dims = self.C, self.O, self.Od = int(wf.shape[1]) // 2, int(wf.shape[0]), int(wd.shape[0])
         if not supported(1, 1, self.C, self.O, self.Od):
             raise _lib.SvnetHipError("fold_vn_layer: C = %d, O = %d is not supported (1 <= C <= %d, 1 <= O <= %d)" % (self.C, self.O, MAX_C, MAX_O))
-        self.folded = torch.empty(self.C * 2 * (self.O + self.Od) + 2 * self.O, dtype=_F32, device=self.device)
-        self.workspace, self._retired = None, []
-        self.refresh()
-
-    @property
-    def slope(self):
-        return float(self.layer.negative_slope)
-
-    def refresh(self):
-        layer, bn = self.layer, self.layer.batchnorm.bn
-        if layer.map_to_feat.weight.device != self.device:
-            raise ValueError("fold_vn_layer: the layer moved from %s to %s - fold it again" % (self.device, layer.map_to_feat.weight.device))
-        with torch.cuda.device(self.device):
-            _lib.call("svnet_vn_fold_f32", _call.p(layer.map_to_feat.weight.detach()), _call.p(layer.map_to_dir.weight.detach()),
-                      _call.p(bn.weight.detach()), _call.p(bn.bias.detach()), _call.p(bn.running_mean), _call.p(bn.running_var), self.C, self.O,
-                      self.Od, float(bn.eps), _call.p(self.folded), _call.stream())
-        return self
+        self.allocate(self.C * 2 * (self.O + self.Od) + 2 * self.O)
 
     def tables(self, B, N):
-        """The workspace for B clouds of N points (uint8): the one kept if it is large enough, else a new one that replaces it.  A
-        replaced one stays allocated: a graph captured with it goes on replaying into memory nothing else was given."""
-        need = int(_lib.lib().svnet_vn_workspace_bytes(B, N, self.O, self.Od))
-        if self.workspace is None or self.workspace.numel() < need:
-            if self.workspace is not None:
-                self._retired.append(self.workspace)
-            self.workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
-        return self.workspace
-
-    def release(self):
-        """Frees the outgrown workspaces (the current one stays).  Only when no captured graph that was recorded with one of them
-        will be replayed again: such a graph would write into memory that may by then belong to another tensor."""
-        self._retired.clear()
-        return self
+        """The workspace for B clouds of N points (uint8): the one kept if it is large enough, else a new one that replaces it."""
+        return self._ws.take(int(_lib.lib().svnet_vn_workspace_bytes(B, N, self.O, self.Od)))
 
 
 def fold_vn_layer(layer):
@@ -167,27 +125,21 @@ def vn_edge_mean(x, idx, folded, out=None):
     return out
 
 
-class FusedVNDGCNN(torch.nn.Module):
+class FusedVNDGCNN(_vn.EvalOnly):
     """The eval-mode forward of a VN_DGCNN_CLS on a HIP device with the module's signature, forward(x [B,3,N], idx=None) -> logits:
     the four edge levels run as knn then vn_edge_mean (or on the four given lists), the rest of the network - conv5, VNStdFeature, the
     pools, the head - through the model's own layers, under no_grad.  It holds the model, so ForwardStep and Distiller take it as
     they take the model.  The levels are folded at construction; refresh() folds them again after the parameters or the running
-    statistics changed.  Train mode is refused: batch statistics are not what this computes.  A model with pooling = 'max', or a
-    call with a level outside the kernels' limits (`supported`), goes through the model's own forward.  `last_idx`: the four
-    neighbour lists of the last fused call, so that a comparison can replay them into the model.  The wrapper's own `training` flag
-    is the model's at construction and follows train() / eval() called on the wrapper; forward reads the model's flag, so a mode
-    set on the model directly is honoured as well.  release() frees the levels' outgrown table workspaces (FoldedVNLayer).
+    statistics changed.  Train mode is refused, and the `training` flag is the model's (_vn.EvalOnly).  A model with pooling = 'max',
+    or a call with a level outside the kernels' limits (`supported`), goes through the model's own forward.  `last_idx`: the four
+    neighbour lists of the last fused call, so that a comparison can replay them into the model.  release() frees the levels'
+    outgrown table workspaces (FoldedVNLayer).
     tail=True: what follows the levels runs through svnet_amd.vn_tail.FusedVNTail (conv5, the cloud mean, VNStdFeature and the pools
     on kernels, the head through the model's layers) instead of model.tail; refresh() and release() reach it."""
 
     def __init__(self, model, tail=False):
-        from .models.vn_dgcnn_cls import VN_DGCNN_CLS
         from .models.vn_layers import mean_pool
-        super().__init__()
-        if not isinstance(model, VN_DGCNN_CLS):
-            raise TypeError("FusedVNDGCNN: needs a VN_DGCNN_CLS, got %s" % type(model).__name__)
-        self.model = model
-        self.training = model.training                      # (a new nn.Module starts in train mode: this one is in its model's)
+        super().__init__(model)
         self.mean = all(pool is mean_pool for _, pool in model.edge_levels())
         self.levels = [fold_vn_layer(conv) for conv, _ in model.edge_levels()] if self.mean else []
         self.last_idx = None
@@ -217,8 +169,7 @@ class FusedVNDGCNN(torch.nn.Module):
     @torch.no_grad()
     def forward(self, x, idx=None):
         name = "FusedVNDGCNN"
-        if self.model.training:
-            raise RuntimeError("%s: the model is in train mode - this is the eval-mode forward (model.eval())" % name)
+        self.eval_only()
         if isinstance(x, torch.Tensor) and x.requires_grad:      # (asked of the argument itself: under no_grad a contiguous copy takes no gradient)
             raise ValueError("%s: x requires grad - %s is forward only in x" % (name, _WHAT))
         _pointset.check_tensors(name, {"x": x.contiguous() if isinstance(x, torch.Tensor) else x}, [_F32], _WHAT)      # (a view is taken, as the model takes it)

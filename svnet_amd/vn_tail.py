@@ -26,10 +26,7 @@ EPS = fl(1e-6); inputs are assumed finite):
     cloud term  per row r of W and component a: u = +0; for c ascending over Cg: u = fmaf(g[c,a], W[r, C + c], u).
     point term  per (n, a) and row r: acc = u[r,a]; for c ascending over C: acc = fmaf(x[c,a,n], W[r,c], acc).  K is never split.
                 p[o,a] are the W_f rows, d[od,a] the W_d rows.
-    norm        q = fl(p0 p0), then fmaf in p1 and p2;  r = fl(fl(sqrt(q)) + EPS);  nb = fmaf(r, s[o], t[o]);  g = fl(nb / r);
-                p'[a] = fl(p[a] g).
-    leaky       dot and dd are 3-term chains like q, of p' d and d d.  If dot >= 0 then w = p'; otherwise c = fl(dot / fl(dd + EPS))
-                and w[a] = fmaf(-c, d[a], p'[a]).  out[o,a,n] = fmaf(slope, p'[a], fl(fl(1 - slope) w[a])).
+    norm, leaky the edge level's two rules, stated in svnet_amd/vn_fused.py, on p[o,:], d[o,:], s[o] and t[o]: out[o,a,n] = y[a].
     cloud mean  run j holds n in [64 j, min(N, 64 j + 64)); a run's sum is n-ascending plain additions from +0;
                 m = fl((the runs' sums added j-ascending from +0) / fl(N)).  The order is the contract's, not the tiling's.
     std-pool    frame rows z[k][a](n) = +0, then fmaf(y[c,a,n], w_lin[k,c], z) for c ascending over Cy; with v_i = x[i,:,n] for i < C
@@ -38,13 +35,13 @@ EPS = fl(1e-6); inputs are assumed finite):
     limits      1 <= N <= 32768, 1 <= C <= 512, 0 <= Cg <= 512, 1 <= O <= 512, Od is O or 1, 1 <= Cy <= 512, B <= 65535
                 (`supported_point`, `supported_std`).
 
-The norm and leaky arithmetic is the edge level's (vn_fused.py), and the module's order differs from it in rounding only.
+The module's order of the norm and leaky arithmetic differs from the contract's in rounding only.
 tests/vn_tail_ref.py restates the contract in numpy; the kernels' results are compared with it as bit patterns (a -0 counted as +0).
 No argument may require grad.  There is no CPU fallback: tensors that are not on a HIP device raise.
 """
 import torch
 
-from . import _call, _lib, _pointset
+from . import _call, _lib, _pointset, _vn
 
 __all__ = ["fold_vn_point", "vn_point", "vn_cloud_mean", "vn_std_pool", "supported_point", "supported_std", "FoldedVNPoint", "FusedVNTail",
            "MAX_C", "MAX_O", "MAX_B"]
@@ -64,84 +61,31 @@ def supported_std(N, C, Cg, Cy):
     return bool(_lib.lib().svnet_vn_std_pool_supported(int(N), int(C), int(Cg), int(Cy)))
 
 
-class _Workspace:
-    """A byte buffer that grows to the largest need seen and is then reused.  One that was outgrown stays allocated, because a graph
-    captured with it goes on replaying into it, until release()."""
-
-    def __init__(self, device):
-        self.device, self.buffer, self._retired = device, None, []
-
-    def take(self, need):
-        if self.buffer is None or self.buffer.numel() < need:
-            if self.buffer is not None:
-                self._retired.append(self.buffer)
-            self.buffer = torch.empty(max(int(need), 1), dtype=torch.uint8, device=self.device)
-        return self.buffer
-
-    def release(self):
-        self._retired.clear()
+_Workspace = _vn.Workspace     # (vn_std_pool takes one as its `workspace`)
 
 
-class FoldedVNPoint:
+class FoldedVNPoint(_vn.Folded):
     """The folded form of one VNLinearLeakyReLU over C + Cg -> O vector channels whose last Cg input channels are constant over a
     cloud: WT [C + Cg, O + Od] | s [O] | t [O] in one buffer on the layer's device, allocated once, and the workspace of the cloud
-    term, which grows to the largest B seen and is then reused.  refresh() runs the fold again - after the parameters or the running
-    statistics changed - on the current stream, one launch.  release() frees outgrown workspaces: only when no captured graph that
-    was recorded with one of them will be replayed again."""
+    term, which grows to the largest B seen and is then reused (`workspace`: the current one).  refresh() and release() are
+    _vn.Folded's."""
+    NAME, ENTRY = "fold_vn_point", "svnet_vn_point_fold_f32"
 
     def __init__(self, layer, cloud_channels=0):
-        from .models.vn_layers import VNLinearLeakyReLU
-        if not isinstance(layer, VNLinearLeakyReLU):
-            raise TypeError("fold_vn_point: needs a VNLinearLeakyReLU, got %s" % type(layer).__name__)
-        bn = layer.batchnorm.bn
-        wf, wd = layer.map_to_feat.weight, layer.map_to_dir.weight
+        wf, wd, _ = _vn.check_layer(self.NAME, layer, even=False)
         Cg = int(cloud_channels)
-        if wf.shape[1] != wd.shape[1] or wd.shape[0] not in (wf.shape[0], 1) or int(bn.num_features) != wf.shape[0]:
-            raise ValueError("fold_vn_point: map_to_feat %s, map_to_dir %s, BatchNorm over %d: needs one input width, O or 1 direction rows"
-                             % (tuple(wf.shape), tuple(wd.shape), bn.num_features))
         if Cg < 0 or Cg >= wf.shape[1]:
             raise ValueError("fold_vn_point: cloud_channels = %d of %d input channels: needs 0 <= cloud_channels < the input width" % (Cg, wf.shape[1]))
-        if bn.running_mean is None or bn.running_var is None or bn.weight is None or bn.bias is None:
-            raise ValueError("fold_vn_point: the BatchNorm must be affine and track running statistics")
-        for k, t in {"map_to_feat.weight": wf, "map_to_dir.weight": wd, "bn.weight": bn.weight, "bn.bias": bn.bias,
-                     "running_mean": bn.running_mean, "running_var": bn.running_var}.items():
-            if t.dtype != _F32 or not t.is_contiguous() or t.device != wf.device:
-                raise ValueError("fold_vn_point: %s must be contiguous float32 on %s" % (k, wf.device))
-        self.device = _pointset.hip_device("fold_vn_point", wf.device)
-        self.layer = layer
-        self.C, self.Cg, self.O, self.Od = int(wf.shape[1]) - Cg, Cg, int(wf.shape[0]), int(wd.shape[0])
+        self.place(layer)
+        self.dims = self.C, self.Cg, self.O, self.Od = int(wf.shape[1]) - Cg, Cg, int(wf.shape[0]), int(wd.shape[0])
         if not supported_point(1, self.C, self.Cg, self.O, self.Od):
             raise _lib.SvnetHipError("fold_vn_point: C = %d, Cg = %d, O = %d is not supported (1 <= C <= %d, Cg <= %d, 1 <= O <= %d)"
                                      % (self.C, self.Cg, self.O, MAX_C, MAX_C, MAX_O))
-        self.folded = torch.empty((self.C + self.Cg) * (self.O + self.Od) + 2 * self.O, dtype=_F32, device=self.device)
-        self._ws = _Workspace(self.device)
-        self.refresh()
-
-    @property
-    def slope(self):
-        return float(self.layer.negative_slope)
-
-    @property
-    def workspace(self):
-        return self._ws.buffer
-
-    def refresh(self):
-        layer, bn = self.layer, self.layer.batchnorm.bn
-        if layer.map_to_feat.weight.device != self.device:
-            raise ValueError("fold_vn_point: the layer moved from %s to %s - fold it again" % (self.device, layer.map_to_feat.weight.device))
-        with torch.cuda.device(self.device):
-            _lib.call("svnet_vn_point_fold_f32", _call.p(layer.map_to_feat.weight.detach()), _call.p(layer.map_to_dir.weight.detach()),
-                      _call.p(bn.weight.detach()), _call.p(bn.bias.detach()), _call.p(bn.running_mean), _call.p(bn.running_var), self.C, self.Cg,
-                      self.O, self.Od, float(bn.eps), _call.p(self.folded), _call.stream())
-        return self
+        self.allocate((self.C + self.Cg) * (self.O + self.Od) + 2 * self.O)
 
     def cloud_terms(self, B):
         """The workspace of the cloud term for B clouds (uint8; one byte when Cg = 0)."""
         return self._ws.take(int(_lib.lib().svnet_vn_point_workspace_bytes(B, self.Cg, self.O, self.Od)))
-
-    def release(self):
-        self._ws.release()
-        return self
 
 
 def fold_vn_point(layer, cloud_channels=0):
@@ -256,7 +200,7 @@ def vn_std_pool(x, y, w_lin, cloud=None, out=None, workspace=None):
     return out
 
 
-class FusedVNTail(torch.nn.Module):
+class FusedVNTail(_vn.EvalOnly):
     """The eval-mode tail of a VN_DGCNN_CLS on a HIP device: forward(feats) maps the four levels' outputs [B,C_i,3,N] to logits, as
     model.tail does.  The steps: torch.cat of the feats (one copy of 3 x 169 N floats per cloud: 2 % of the tail's traffic - the edge
     levels' entry has no channel window to write into one buffer), conv5, the cloud mean, vn1 with cloud = m, vn2, the
@@ -266,12 +210,7 @@ class FusedVNTail(torch.nn.Module):
     normalize_frame set, or widths or a call outside the kernels' limits (`supported`), goes through model.tail."""
 
     def __init__(self, model):
-        from .models.vn_dgcnn_cls import VN_DGCNN_CLS
-        super().__init__()
-        if not isinstance(model, VN_DGCNN_CLS):
-            raise TypeError("FusedVNTail: needs a VN_DGCNN_CLS, got %s" % type(model).__name__)
-        self.model = model
-        self.training = model.training
+        super().__init__(model)
         std = model.std_feature
         wide = model.conv5.map_to_feat.weight.shape[0]
         self.widths = [(int(l.map_to_feat.weight.shape[1]) - cg, cg, int(l.map_to_feat.weight.shape[0]), int(l.map_to_dir.weight.shape[0]))
@@ -301,8 +240,7 @@ class FusedVNTail(torch.nn.Module):
 
     def _feats(self, feats):
         name = "FusedVNTail"
-        if self.model.training:
-            raise RuntimeError("%s: the model is in train mode - this is the eval-mode forward (model.eval())" % name)
+        self.eval_only()
         feats = list(feats)
         if not feats:
             raise ValueError("%s: feats must hold the levels' outputs [B,C_i,3,N]" % name)

@@ -3,21 +3,20 @@
 and the reference's recorded run (tests/golden/vn.npz).  The contract is a fixed sequence of single-rounded operations, so the
 kernels' results are compared as BIT PATTERNS (a -0 counted as +0); the wrapper against the module, which rounds differently, within
 the project's activation tolerance tests.common.compare_case(..., 1e-3).  Every reference is computed once per process and shared."""
-import argparse
-
 import numpy as np
 import pytest
 import torch
 
 from svnet_amd import synth
 from tests import fused_level_cases as FL
+from tests import vn_cases as VC
 from tests import vn_ref as V
-from tests.common import compare_case, load_npz
+from tests.common import compare_case
 
 pytestmark = pytest.mark.gpu
 
 F32 = np.float32
-GOLDEN = load_npz("vn.npz")
+GOLDEN, _state, _golden_model = VC.GOLDEN, VC.state, VC.golden_model
 _once = FL.cache()
 
 # (C, O, N, k, B, share, slope): the first level (K of one); the second; the widest level at an N that is no multiple of the 16 points
@@ -46,13 +45,7 @@ def _arrays(C, O, N, k, B, share, lists="random"):
         elif lists == "outside":
             idx = synth.integers(seed, 9, (B, N, k), 3 * N) - N
             assert (idx < 0).any() and (idx >= N).any()
-        Od = 1 if share else O
-        arrays = dict(w_feat=(synth.normal(seed, 3, (O, 2 * C)) / np.sqrt(F32(2 * C))).astype(F32),
-                      w_dir=(synth.normal(seed, 4, (Od, 2 * C)) / np.sqrt(F32(2 * C))).astype(F32),
-                      gamma=(synth.normal(seed, 5, (O,)) + F32(0.25)).astype(F32), beta=synth.normal(seed, 6, (O,)) * F32(0.2),
-                      mean=synth.normal(seed, 7, (O,)) * F32(0.25), var=synth.uniform(seed, 8, (O,), 0.5, 1.5))
-        assert O < 4 or ((arrays["gamma"] > 0).any() and (arrays["gamma"] < 0).any())
-        return x, idx, arrays
+        return x, idx, VC.layer_arrays(seed, 2 * C, O, 1 if share else O, signs=4)
     return _once(("arrays", C, O, N, k, B, share, lists), make)
 
 
@@ -64,23 +57,10 @@ def _want(C, O, N, k, B, share, slope, lists="random"):
     return _once(("want", C, O, N, k, B, share, slope, lists), make)
 
 
-def _layer(dev, C, O, share, slope, a):
-    from svnet_amd.models.vn_layers import VNLinearLeakyReLU
-    layer = VNLinearLeakyReLU(2 * C, O, share_nonlinearity=share, negative_slope=slope)
-    with torch.no_grad():
-        layer.map_to_feat.weight.copy_(torch.from_numpy(a["w_feat"]))
-        layer.map_to_dir.weight.copy_(torch.from_numpy(a["w_dir"]))
-        layer.batchnorm.bn.weight.copy_(torch.from_numpy(a["gamma"]))
-        layer.batchnorm.bn.bias.copy_(torch.from_numpy(a["beta"]))
-        layer.batchnorm.bn.running_mean.copy_(torch.from_numpy(a["mean"]))
-        layer.batchnorm.bn.running_var.copy_(torch.from_numpy(a["var"]))
-    return layer.to(dev).eval()
-
-
 def _folded(dev, C, O, share, slope, a, f):
     """The FoldedVNLayer on the device; the fold's results are checked as bit patterns on the way."""
     from svnet_amd import vn_fused as VF
-    folded = VF.fold_vn_layer(_layer(dev, C, O, share, slope, a))
+    folded = VF.fold_vn_layer(VC.layer(dev, 2 * C, O, share, slope, a))
     Od, R = (1 if share else O), 2 * (O + (1 if share else O))
     got = folded.folded.cpu().numpy()
     WT = np.concatenate([f["Af"], f["Ad"], f["Df"], f["Dd"]], axis=0).T            # [C][A_f | A_d | D_f | D_d]
@@ -189,19 +169,6 @@ def test_level_in_a_captured_graph(hip_device):
 
 
 # ---- the model
-def _state():
-    return _once("state", lambda: V.synthetic_state(GOLDEN["keys"], GOLDEN["shapes"], V.GOLDEN_CASE[0]))
-
-
-def _golden_model(dev, pooling="mean"):
-    import svnet_amd.models as M
-    seed, B, N, k, num_class = V.GOLDEN_CASE
-    model = M.VN_DGCNN_CLS(argparse.Namespace(k=k, pooling=pooling), num_class)
-    if pooling == "mean":
-        model.load_state_dict({key: torch.from_numpy(v.copy()) for key, v in _state().items()}, strict=True)
-    return model.to(dev).eval()
-
-
 def test_knn_list_of_the_first_level_equals_the_recorded_one(hip_device):
     from svnet_amd.models.utils import vn_util as U
     seed, B, N, k, num_class = V.GOLDEN_CASE

@@ -11,14 +11,15 @@ import torch
 
 from svnet_amd import synth
 from tests import fused_level_cases as FL
+from tests import vn_cases as VC
 from tests import vn_ref as V
 from tests import vn_tail_ref as T
-from tests.common import compare_case, load_npz
+from tests.common import compare_case
 
 pytestmark = pytest.mark.gpu
 
 F32 = np.float32
-GOLDEN = load_npz("vn.npz")
+GOLDEN, _state, _golden_model, _levels = VC.GOLDEN, VC.state, VC.golden_model, VC.levels
 _once = FL.cache()
 
 # (C, Cg, O, Od, N, B): the smallest case; K and N off the tile multiples; more than 64 columns with one direction row and a cloud
@@ -34,12 +35,8 @@ STD_B = 2
 def _point_arrays(C, Cg, O, Od, N, B):
     """(x [B,C,3,N], g [B,Cg,3], the layer's arrays): weights ~ N(0, 1/K), BatchNorm weights of both signs, statistics away from identity."""
     def make():
-        seed, K = 9100 + 13 * C + 7 * Cg + O, C + Cg
-        arrays = dict(w_feat=(synth.normal(seed, 3, (O, K)) / np.sqrt(F32(K))).astype(F32), w_dir=(synth.normal(seed, 4, (Od, K)) / np.sqrt(F32(K))).astype(F32),
-                      gamma=(synth.normal(seed, 5, (O,)) + F32(0.25)).astype(F32), beta=synth.normal(seed, 6, (O,)) * F32(0.2),
-                      mean=synth.normal(seed, 7, (O,)) * F32(0.25), var=synth.uniform(seed, 8, (O,), 0.5, 1.5))
-        assert O < 7 or ((arrays["gamma"] > 0).any() and (arrays["gamma"] < 0).any())
-        return synth.normal(seed, 1, (B, C, 3, N)), synth.normal(seed, 2, (B, Cg, 3)), arrays
+        seed = 9100 + 13 * C + 7 * Cg + O
+        return synth.normal(seed, 1, (B, C, 3, N)), synth.normal(seed, 2, (B, Cg, 3)), VC.layer_arrays(seed, C + Cg, O, Od, signs=7)
     return _once(("point arrays", C, Cg, O, Od, N, B), make)
 
 
@@ -51,23 +48,10 @@ def _point_want(C, Cg, O, Od, N, B, slope):
     return _once(("point want", C, Cg, O, Od, N, B, slope), make)
 
 
-def _point_layer(dev, C, Cg, O, Od, slope, a):
-    from svnet_amd.models.vn_layers import VNLinearLeakyReLU
-    layer = VNLinearLeakyReLU(C + Cg, O, dim=4, share_nonlinearity=Od == 1 and O != 1, negative_slope=slope)
-    with torch.no_grad():
-        layer.map_to_feat.weight.copy_(torch.from_numpy(a["w_feat"]))
-        layer.map_to_dir.weight.copy_(torch.from_numpy(a["w_dir"]))
-        layer.batchnorm.bn.weight.copy_(torch.from_numpy(a["gamma"]))
-        layer.batchnorm.bn.bias.copy_(torch.from_numpy(a["beta"]))
-        layer.batchnorm.bn.running_mean.copy_(torch.from_numpy(a["mean"]))
-        layer.batchnorm.bn.running_var.copy_(torch.from_numpy(a["var"]))
-    return layer.to(dev).eval()
-
-
 def _folded(dev, C, Cg, O, Od, slope, a, f):
     """The FoldedVNPoint on the device; the fold's results are checked as bit patterns on the way."""
     from svnet_amd import vn_tail as VT
-    folded = VT.fold_vn_point(_point_layer(dev, C, Cg, O, Od, slope, a), Cg)
+    folded = VT.fold_vn_point(VC.layer(dev, C + Cg, O, Od == 1 and O != 1, slope, a, dim=4), Cg)
     K, R = C + Cg, O + Od
     got = folded.folded.cpu().numpy()
     WT = np.ascontiguousarray(np.concatenate([f["Wf"], f["Wd"]], axis=0).T)          # [K][W_f | W_d]
@@ -146,23 +130,6 @@ def test_cloud_mean_and_std_pool_equal_the_restatement_bit_for_bit(C, Cg, Cy, N,
 
 
 # ---- the model
-def _state():
-    return _once("state", lambda: V.synthetic_state(GOLDEN["keys"], GOLDEN["shapes"], V.GOLDEN_CASE[0]))
-
-
-def _golden_model(dev, pooling="mean"):
-    import svnet_amd.models as M
-    seed, B, N, k, num_class = V.GOLDEN_CASE
-    model = M.VN_DGCNN_CLS(argparse.Namespace(k=k, pooling=pooling), num_class)
-    if pooling == "mean":
-        model.load_state_dict({key: torch.from_numpy(v.copy()) for key, v in _state().items()}, strict=True)
-    return model.to(dev).eval()
-
-
-def _levels():
-    return [GOLDEN["lvl%d" % i] for i in range(4)]
-
-
 def _golden_pooled():
     return _once("golden pooled", lambda: T.pooled(_levels(), _state()))
 

@@ -360,6 +360,23 @@ def test_front_ends_and_step_state_do_not_import_the_op_layer():
     assert _ops_loaded_after_importing(["_step", "_call"]) == [("_step", "False"), ("_call", "False")]
 
 
+def test_vector_neuron_leaf_sits_under_its_two_front_ends():
+    """svnet_amd._vn imports neither front end, the op layer nor the step state, anywhere; vn_fused and vn_tail import it and not
+    each other at module level - FusedVNDGCNN imports vn_tail inside its constructor, when a tail is asked for."""
+    import ast
+
+    def imported(name, top_only):
+        tree = ast.parse(open(os.path.join(ROOT, "svnet_amd", name + ".py")).read())
+        nodes = tree.body if top_only else ast.walk(tree)
+        froms = [n for n in nodes if isinstance(n, ast.ImportFrom) and n.level == 1]
+        return {(n.module or a.name).split(".")[0] for n in froms for a in n.names}
+
+    assert imported("_vn", False) == {"_call", "_lib", "_pointset", "models"}
+    assert "_vn" in imported("vn_fused", True) and "_vn" in imported("vn_tail", True)
+    assert not {"vn_tail", "_ops", "_step"} & imported("vn_fused", True) and not {"vn_fused", "_ops", "_step"} & imported("vn_tail", True)
+    assert "vn_tail" in imported("vn_fused", False)
+
+
 def test_op_layer_names_are_the_call_helpers_and_the_step_objects_themselves():
     from svnet_amd import _call, _ops, _step
     for old, new in (("_p", "p"), ("_stream", "stream"), ("_hip", "hip"), ("_f32c", "f32c"), ("call", "call")):

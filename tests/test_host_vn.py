@@ -2,7 +2,7 @@
 models/vn_dgcnn_cls.py and the numpy restatement tests/vn_ref.py against the reference's recorded run (tests/golden/vn.npz, neighbour
 lists replayed), the header's new entry points, and the refusals of svnet_amd/vn_fused.py that need no device.  The kernels
 themselves: tests/test_hip_vn.py."""
-import argparse
+import functools
 import re
 
 import numpy as np
@@ -10,26 +10,13 @@ import pytest
 import torch
 
 from svnet_amd import _lib
-from tests import fused_level_cases as FL
+from tests import vn_cases as VC
 from tests import vn_ref as V
-from tests.common import compare_case, load_npz
+from tests.common import compare_case
 
 F32 = np.float32
-GOLDEN = load_npz("vn.npz")
-_once = FL.cache()
-
-
-def golden_state():
-    return _once("state", lambda: V.synthetic_state(GOLDEN["keys"], GOLDEN["shapes"], V.GOLDEN_CASE[0]))
-
-
-def golden_model(pooling="mean"):
-    import svnet_amd.models as M
-    seed, B, N, k, num_class = V.GOLDEN_CASE
-    model = M.VN_DGCNN_CLS(argparse.Namespace(k=k, pooling=pooling), num_class)
-    if pooling == "mean":
-        model.load_state_dict({key: torch.from_numpy(a.copy()) for key, a in golden_state().items()}, strict=True)
-    return model.eval()
+GOLDEN = VC.GOLDEN
+golden_state, golden_model = VC.state, functools.partial(VC.golden_model, None)
 
 
 def golden_lists():
@@ -101,12 +88,9 @@ def test_restatement_lies_at_fp32_noise_from_the_float64_definition(C, O, Od, N,
     from svnet_amd import synth
     x = synth.normal(60 + C, 1, (C, 3, N))
     idx = synth.integers(60 + C, 2, (N, k), N)
-    w_feat = (synth.normal(60 + C, 3, (O, 2 * C)) / np.sqrt(F32(2 * C))).astype(F32)
-    w_dir = (synth.normal(60 + C, 4, (Od, 2 * C)) / np.sqrt(F32(2 * C))).astype(F32)
-    gamma, beta = synth.normal(60 + C, 5, (O,)) + F32(0.25), synth.normal(60 + C, 6, (O,)) * F32(0.2)
-    mean, var = synth.normal(60 + C, 7, (O,)) * F32(0.25), synth.uniform(60 + C, 8, (O,), 0.5, 1.5)
-    got = V.level(x, idx, V.fold(w_feat, w_dir, gamma, beta, mean, var), slope)
-    want = V.level_f64(x, idx, w_feat, w_dir, gamma, beta, mean, var, slope=slope)
+    a = VC.layer_arrays(60 + C, 2 * C, O, Od)
+    got = V.level(x, idx, V.fold(**a), slope)
+    want = V.level_f64(x, idx, **a, slope=slope)
     assert got.dtype == F32 and got.shape == want.shape == (O, 3, N)
     # a few dozen fp32 roundings per value, some of them amplified by the division by the norm: 2e-5 of the largest output is two
     # hundred ulps of room, a fiftieth of the project's 1e-3
@@ -266,8 +250,9 @@ def test_fold_and_wrapper_refuse_what_they_cannot_take():
         fused(torch.zeros(2, 3, 64), idx=[i.to("meta") if n == 1 else i for n, i in enumerate(golden_lists())])
     assert fused.release() is fused
     f = _fake_folded(3, 5)
-    f._retired = [torch.zeros(4)]
-    assert f.release() is f and f._retired == []
+    f._ws = VF._vn.Workspace(f.device)
+    f._ws._retired = [torch.zeros(4)]
+    assert f.release() is f and f._ws._retired == []
     with pytest.raises(ValueError, match="pooling must be"):
         golden_model("median")
     with pytest.raises(ValueError, match="dim must be 3, 4 or 5"):

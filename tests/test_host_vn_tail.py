@@ -1,7 +1,7 @@
 """CPU tests of the fused vector-neuron tail: the numpy restatement tests/vn_tail_ref.py against the reference's recorded run
 (tests/golden/vn.npz), the module's own tail and float64 direct forms; the algebra of the cloud term; the header's new entry points;
 and the refusals of svnet_amd/vn_tail.py that need no device.  The kernels themselves: tests/test_hip_vn_tail.py."""
-import argparse
+import functools
 import re
 
 import numpy as np
@@ -9,27 +9,14 @@ import pytest
 import torch
 
 from svnet_amd import _lib, synth
-from tests import fused_level_cases as FL
+from tests import vn_cases as VC
 from tests import vn_ref as V
 from tests import vn_tail_ref as T
-from tests.common import compare_case, load_npz
+from tests.common import compare_case
 
 F32 = np.float32
-GOLDEN = load_npz("vn.npz")
-_once = FL.cache()
-
-
-def golden_state():
-    return _once("state", lambda: V.synthetic_state(GOLDEN["keys"], GOLDEN["shapes"], V.GOLDEN_CASE[0]))
-
-
-def golden_model(pooling="mean"):
-    import svnet_amd.models as M
-    seed, B, N, k, num_class = V.GOLDEN_CASE
-    model = M.VN_DGCNN_CLS(argparse.Namespace(k=k, pooling=pooling), num_class)
-    if pooling == "mean":
-        model.load_state_dict({key: torch.from_numpy(a.copy()) for key, a in golden_state().items()}, strict=True)
-    return model.eval()
+GOLDEN = VC.GOLDEN
+golden_state, golden_model = VC.state, functools.partial(VC.golden_model, None)
 
 
 def head(model, h):
@@ -57,11 +44,7 @@ def test_restatement_of_the_tail_equals_the_recorded_logits_and_the_module():
 
 
 def _arrays(C, Cg, O, Od, N, seed):
-    K = C + Cg
-    return dict(x=synth.normal(seed, 1, (C, 3, N)), g=synth.normal(seed, 2, (Cg, 3)),
-                w_feat=(synth.normal(seed, 3, (O, K)) / np.sqrt(F32(K))).astype(F32), w_dir=(synth.normal(seed, 4, (Od, K)) / np.sqrt(F32(K))).astype(F32),
-                gamma=(synth.normal(seed, 5, (O,)) + F32(0.25)).astype(F32), beta=synth.normal(seed, 6, (O,)) * F32(0.2),
-                mean=synth.normal(seed, 7, (O,)) * F32(0.25), var=synth.uniform(seed, 8, (O,), 0.5, 1.5))
+    return dict(VC.layer_arrays(seed, C + Cg, O, Od), x=synth.normal(seed, 1, (C, 3, N)), g=synth.normal(seed, 2, (Cg, 3)))
 
 
 @pytest.mark.parametrize("C,Cg,O,Od,N,slope", [(5, 0, 7, 7, 9, 0.2), (3, 2, 70, 1, 20, 0.0), (6, 5, 20, 20, 33, 0.2), (40, 40, 12, 12, 70, 0.2)])

@@ -1,0 +1,55 @@
+"""What the tests of the fused vector-neuron kernels share (tests/test_{hip,host}_{vn,vn_tail}.py): the arrays of a synthetic
+VNLinearLeakyReLU, the module built from them, and the golden case of tests/golden/vn.npz - its state, model and recorded levels.
+Every draw is a function of (seed, shape) alone, so a file's references stay what they were whichever test asks first."""
+import argparse
+
+import numpy as np
+import torch
+
+from svnet_amd import synth
+from tests import fused_level_cases as FL
+from tests import vn_ref as V
+from tests.common import load_npz
+
+F32 = np.float32
+GOLDEN = load_npz("vn.npz")
+_once = FL.cache()
+
+
+def layer_arrays(seed, K, O, Od, signs=None):
+    """The arrays of a layer over K -> O vector channels with Od direction rows: weights ~ N(0, 1/K), BatchNorm weights of both signs
+    (asserted from O = signs on), statistics away from identity."""
+    arrays = dict(w_feat=(synth.normal(seed, 3, (O, K)) / np.sqrt(F32(K))).astype(F32), w_dir=(synth.normal(seed, 4, (Od, K)) / np.sqrt(F32(K))).astype(F32),
+                  gamma=(synth.normal(seed, 5, (O,)) + F32(0.25)).astype(F32), beta=synth.normal(seed, 6, (O,)) * F32(0.2),
+                  mean=synth.normal(seed, 7, (O,)) * F32(0.25), var=synth.uniform(seed, 8, (O,), 0.5, 1.5))
+    assert signs is None or O < signs or ((arrays["gamma"] > 0).any() and (arrays["gamma"] < 0).any())
+    return arrays
+
+
+def layer(dev, K, O, share, slope, a, **kw):
+    """The VNLinearLeakyReLU over K -> O that holds the arrays a, on dev in eval mode."""
+    from svnet_amd.models.vn_layers import VNLinearLeakyReLU
+    layer = VNLinearLeakyReLU(K, O, share_nonlinearity=share, negative_slope=slope, **kw)
+    bn = layer.batchnorm.bn
+    with torch.no_grad():
+        for t, key in ((layer.map_to_feat.weight, "w_feat"), (layer.map_to_dir.weight, "w_dir"), (bn.weight, "gamma"), (bn.bias, "beta"),
+                       (bn.running_mean, "mean"), (bn.running_var, "var")):
+            t.copy_(torch.from_numpy(a[key]))
+    return layer.to(dev).eval()
+
+
+def state():
+    return _once("state", lambda: V.synthetic_state(GOLDEN["keys"], GOLDEN["shapes"], V.GOLDEN_CASE[0]))
+
+
+def golden_model(dev=None, pooling="mean"):
+    import svnet_amd.models as M
+    seed, B, N, k, num_class = V.GOLDEN_CASE
+    model = M.VN_DGCNN_CLS(argparse.Namespace(k=k, pooling=pooling), num_class)
+    if pooling == "mean":
+        model.load_state_dict({key: torch.from_numpy(v.copy()) for key, v in state().items()}, strict=True)
+    return model.to(dev).eval()
+
+
+def levels():
+    return [GOLDEN["lvl%d" % i] for i in range(4)]

@@ -2,8 +2,10 @@
 svnet_amd/vn_fused.py's docstring and include/svnet_hip.h and independent of the kernels.
 
     fold(w_feat, w_dir, gamma, beta, mean, var, eps)     {Af, Df [O,C], Ad, Dd [Od,C], s, t [O]} in fp32, every operation rounded once
-    fold_state(state, prefix, eps)                       the same from a state_dict's arrays: prefix "conv1." ...
+    fold_bn(gamma, beta, mean, var, eps)                 (s, t): the ONE restatement of BatchNorm's fold, the tail's too
+    fold_state(state, prefix, eps, fold=fold)            a fold from a state_dict's arrays: prefix "conv1." ...
     tables(x, f)                                         (Pn, Pc [N,O,3], Qn, Qc [N,Od,3]): the c-ascending fmaf chains from +0
+    norm_leaky(p, d, s, t, slope)                        (y, dot): the ONE restatement of the norm and the leaky rule, the tail's too
     level(x, idx, f, slope, taken=None)                  [O,3,N] float32: edge, norm, leaky and mean of the contract, indices clamped
     level_batch(x, idx, f, slope)                        the same over a leading batch axis
     level_f64(x, idx, w_feat, w_dir, ...)                the module's own definition in float64 on the unfolded arrays
@@ -30,26 +32,31 @@ SLOPE = 0.2
 GRAPH_CASE = (5, 2, 2, 6, 3)
 
 
-def fold(w_feat, w_dir, gamma, beta, mean, var, eps=1e-5):
-    w_feat, w_dir, gamma, beta, mean, var = (np.ascontiguousarray(a, dtype=F32) for a in (w_feat, w_dir, gamma, beta, mean, var))
-    C = w_feat.shape[1] // 2
-    assert w_feat.shape[1] == 2 * C == w_dir.shape[1] and w_dir.shape[0] in (w_feat.shape[0], 1)
+def fold_bn(gamma, beta, mean, var, eps):
+    gamma, beta, mean, var = (np.ascontiguousarray(a, dtype=F32) for a in (gamma, beta, mean, var))
     invstd = (F32(1) / np.sqrt((var + F32(eps)).astype(F32)).astype(F32)).astype(F32)
     s = (gamma * invstd).astype(F32)
-    t = (beta - (mean * s).astype(F32)).astype(F32)
+    return s, (beta - (mean * s).astype(F32)).astype(F32)
+
+
+def fold(w_feat, w_dir, gamma, beta, mean, var, eps=1e-5):
+    w_feat, w_dir = (np.ascontiguousarray(a, dtype=F32) for a in (w_feat, w_dir))
+    C = w_feat.shape[1] // 2
+    assert w_feat.shape[1] == 2 * C == w_dir.shape[1] and w_dir.shape[0] in (w_feat.shape[0], 1)
+    s, t = fold_bn(gamma, beta, mean, var, eps)
     return dict(Af=np.ascontiguousarray(w_feat[:, :C]), Df=(w_feat[:, C:] - w_feat[:, :C]).astype(F32),
                 Ad=np.ascontiguousarray(w_dir[:, :C]), Dd=(w_dir[:, C:] - w_dir[:, :C]).astype(F32), s=s, t=t)
 
 
-def fold_state(state, prefix, eps=1e-5):
+def fold_state(state, prefix, eps=1e-5, fold=fold):
     return fold(state[prefix + "map_to_feat.weight"], state[prefix + "map_to_dir.weight"], state[prefix + "batchnorm.bn.weight"],
                 state[prefix + "batchnorm.bn.bias"], state[prefix + "batchnorm.bn.running_mean"], state[prefix + "batchnorm.bn.running_var"], eps)
 
 
-def _chain(x, M):
-    """x [C,3,N], M [R,C] -> [N,R,3]: acc = +0, then acc = fmaf(x[c,a,n], M[r,c], acc) for c ascending."""
+def _chain(x, M, u=None):
+    """x [C,3,N], M [R,K], u [R,3] or None for +0 -> [N,R,3]: acc = u, then acc = fmaf(x[c,a,n], M[r,c], acc) for c ascending over C."""
     C, _, N = x.shape
-    acc = np.zeros((N, M.shape[0], 3), dtype=F32)
+    acc = np.zeros((N, M.shape[0], 3), dtype=F32) if u is None else np.ascontiguousarray(np.broadcast_to(u[None], (N, M.shape[0], 3)), dtype=F32)
     for c in range(C):
         acc = fmaf(x[c].T[:, None, :], M[None, :, c, None], acc)
     return acc
@@ -64,27 +71,31 @@ def _dot3(a, b):
     return fmaf(a[..., 2], b[..., 2], fmaf(a[..., 1], b[..., 1], (a[..., 0] * b[..., 0]).astype(F32)))
 
 
+def norm_leaky(p, d, s, t, slope):
+    """p, d [N,O,3], s, t [O] -> (y [N,O,3], dot [N,O]): the norm through BatchNorm's folded affine, then the leaky rule."""
+    slope = F32(slope)
+    one_minus = F32(F32(1) - slope)
+    q = _dot3(p, p)
+    r = (np.sqrt(q).astype(F32) + EPS).astype(F32)
+    g = (fmaf(r, s[None, :], t[None, :]) / r).astype(F32)
+    u = (p * g[..., None]).astype(F32)
+    dot, dd = _dot3(u, d), _dot3(d, d)
+    c = (dot / (dd + EPS).astype(F32)).astype(F32)
+    w = np.where((dot >= 0)[..., None], u, fmaf(-c[..., None], d, u))
+    return fmaf(slope, u, (one_minus * w).astype(F32)), dot
+
+
 def level(x, idx, f, slope=SLOPE, taken=None):
     """x [C,3,N] float32, idx [N,k] -> [O,3,N] float32.  taken: a list that receives the share of (edge, o) pairs on the dot < 0 branch."""
     Pn, Pc, Qn, Qc = tables(x, f)
     N, k = idx.shape
     m = np.clip(np.asarray(idx, dtype=np.int64), 0, N - 1)
-    slope = F32(slope)
-    one_minus = F32(F32(1) - slope)
-    s, t = f["s"][None, :], f["t"][None, :]
     acc = np.zeros(Pn.shape, dtype=F32)                                           # [N,O,3]
     neg = 0
     for j in range(k):
         p = (Pn[m[:, j]] + Pc).astype(F32)                                        # [N,O,3]
         d = np.broadcast_to((Qn[m[:, j]] + Qc).astype(F32), p.shape)              # (one direction row serves every o)
-        q = _dot3(p, p)
-        r = (np.sqrt(q).astype(F32) + EPS).astype(F32)
-        g = (fmaf(r, s, t) / r).astype(F32)
-        u = (p * g[..., None]).astype(F32)
-        dot, dd = _dot3(u, d), _dot3(d, d)
-        c = (dot / (dd + EPS).astype(F32)).astype(F32)
-        w = np.where((dot >= 0)[..., None], u, fmaf(-c[..., None], d, u))
-        y = fmaf(slope, u, (one_minus * w).astype(F32))
+        y, dot = norm_leaky(p, d, f["s"], f["t"], slope)
         acc = (acc + y).astype(F32)
         neg += int((dot < 0).sum())
     if taken is not None:

@@ -1,10 +1,10 @@
 """numpy restatement of the fused vector-neuron tail (svnet_amd/csrc/vn_tail.hip), written from the contract in svnet_amd/vn_tail.py's
 docstring and include/svnet_hip.h and independent of the kernels.
 
-    fold_point(w_feat, w_dir, gamma, beta, mean, var, eps)   {Wf [O,K], Wd [Od,K], s, t [O]}: s and t as tests/vn_ref.fold has them
+    fold_point(w_feat, w_dir, gamma, beta, mean, var, eps)   {Wf [O,K], Wd [Od,K], s, t [O]}: s and t are tests/vn_ref.fold_bn's
     fold_point_state(state, prefix, eps)                     the same from a state_dict's arrays: prefix "conv5." ...
     cloud_term(g, W, C)                                      [R,3]: u = +0, then fmaf over the Cg constant channels, c ascending
-    point_level(x, f, slope, g=None)                         [O,3,N]: the chain from the cloud term, the norm and the leaky rule
+    point_level(x, f, slope, g=None)                         [O,3,N]: the chain from the cloud term, then tests/vn_ref.norm_leaky
     ordered_mean(e)                                          over the last axis: runs of 64 n-ascending, the runs j-ascending, / fl(N)
     std_pool(x, y, w_lin, g=None)                            [6 I]: frame rows, coordinates, [max | ordered mean]
     pooled(feats, state, slope)                              the whole tail in front of the head: the four levels' outputs -> [B, 6 I]
@@ -15,7 +15,7 @@ correctly rounded single operations.
 import numpy as np
 
 from tests.sa_fused_ref import fmaf
-from tests.vn_ref import EPS, SLOPE, _dot3
+from tests.vn_ref import SLOPE, _chain, fold_bn, fold_state, norm_leaky
 
 F32, F64 = np.float32, np.float64
 RUN = 64
@@ -26,17 +26,14 @@ TAIL_PREFIXES = ("conv5.", "std_feature.vn1.", "std_feature.vn2.")
 
 
 def fold_point(w_feat, w_dir, gamma, beta, mean, var, eps=1e-5):
-    w_feat, w_dir, gamma, beta, mean, var = (np.ascontiguousarray(a, dtype=F32) for a in (w_feat, w_dir, gamma, beta, mean, var))
+    w_feat, w_dir = (np.ascontiguousarray(a, dtype=F32) for a in (w_feat, w_dir))
     assert w_feat.shape[1] == w_dir.shape[1] and w_dir.shape[0] in (w_feat.shape[0], 1)
-    invstd = (F32(1) / np.sqrt((var + F32(eps)).astype(F32)).astype(F32)).astype(F32)
-    s = (gamma * invstd).astype(F32)
-    t = (beta - (mean * s).astype(F32)).astype(F32)
+    s, t = fold_bn(gamma, beta, mean, var, eps)
     return dict(Wf=w_feat, Wd=w_dir, s=s, t=t)
 
 
 def fold_point_state(state, prefix, eps=1e-5):
-    return fold_point(state[prefix + "map_to_feat.weight"], state[prefix + "map_to_dir.weight"], state[prefix + "batchnorm.bn.weight"],
-                      state[prefix + "batchnorm.bn.bias"], state[prefix + "batchnorm.bn.running_mean"], state[prefix + "batchnorm.bn.running_var"], eps)
+    return fold_state(state, prefix, eps, fold_point)
 
 
 def cloud_term(g, W, C):
@@ -47,15 +44,6 @@ def cloud_term(g, W, C):
     return u
 
 
-def _chain(x, W, u):
-    """x [C,3,N], W [R,K], u [R,3] -> [N,R,3]: acc = u, then acc = fmaf(x[c,a,n], W[r,c], acc) for c ascending over C."""
-    C, _, N = x.shape
-    acc = np.ascontiguousarray(np.broadcast_to(u[None], (N, W.shape[0], 3)), dtype=F32)
-    for c in range(C):
-        acc = fmaf(x[c].T[:, None, :], W[None, :, c, None], acc)
-    return acc
-
-
 def point_level(x, f, slope=SLOPE, g=None):
     """x [C,3,N] float32, g [Cg,3] or None -> [O,3,N] float32."""
     x = np.ascontiguousarray(x, dtype=F32)
@@ -63,20 +51,9 @@ def point_level(x, f, slope=SLOPE, g=None):
     W = np.concatenate([f["Wf"], f["Wd"]], axis=0)
     O = f["Wf"].shape[0]
     assert W.shape[1] == C + (0 if g is None else g.shape[0])
-    u = np.zeros((W.shape[0], 3), dtype=F32) if g is None or g.shape[0] == 0 else cloud_term(np.ascontiguousarray(g, dtype=F32), W, C)
-    acc = _chain(x, W, u)
+    acc = _chain(x, W, None if g is None or g.shape[0] == 0 else cloud_term(np.ascontiguousarray(g, dtype=F32), W, C))
     p, d = acc[:, :O], np.broadcast_to(acc[:, O:], (acc.shape[0], O, 3)) if W.shape[0] == O + 1 else acc[:, O:]
-    slope = F32(slope)
-    one_minus = F32(F32(1) - slope)
-    q = _dot3(p, p)
-    r = (np.sqrt(q).astype(F32) + EPS).astype(F32)
-    gain = (fmaf(r, f["s"][None, :], f["t"][None, :]) / r).astype(F32)
-    v = (p * gain[..., None]).astype(F32)
-    dot, dd = _dot3(v, d), _dot3(d, d)
-    c = (dot / (dd + EPS).astype(F32)).astype(F32)
-    w = np.where((dot >= 0)[..., None], v, fmaf(-c[..., None], d, v))
-    y = fmaf(slope, v, (one_minus * w).astype(F32))
-    return np.ascontiguousarray(y.transpose(1, 2, 0))
+    return np.ascontiguousarray(norm_leaky(p, d, f["s"], f["t"], slope)[0].transpose(1, 2, 0))
 
 
 def ordered_sum(e):
