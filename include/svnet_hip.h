@@ -45,9 +45,9 @@ int svnet_slices_sum_f64(double* buf, int64_t L, void* stream);
 
 /* ABI version = 100 * round-of-change + serial.  It changes whenever an entry point gains / loses an argument or a caller-owned buffer
  * changes its required length (200: sliced accumulators, SVNET_SLICED_LEN; 400: this header; 401: the totals of a sliced accumulator are
- * written by its consumer, svnet_slices_sum_*; 402: GX of svnet_v2s_bwd_*, gw of svnet_xyzblock_bwd_f32 and col_sum of svnet_gemm_f32 are sliced accumulators; 403: svnet_binweight_grad_f32 takes sliced inputs; 421: svnet_three_nn_f32, svnet_three_interpolate_f32; 422: svnet_ball_query_f32, svnet_group_points_f32; 423: svnet_vlinear_stats_f32 is gone; 424: svnet_edgeblock_fwd_tier, svnet_edgeblock_bwd_tier, svnet_edgeblock_wgrad_tier, svnet_xyzblock_tier; 425: svnet_pointset_reverse_i32, svnet_three_interpolate_bwd_f32, svnet_group_points_bwd_f32; 426: wbt of svnet_edgeblock_wbt_bf16 is 512 values longer, the all-zero fragment; 427: svnet_ball_query_msg_f32, svnet_group_points_msg_f32, svnet_group_points_msg_bwd_f32; 428: svnet_sa_fold_f32, svnet_sa_fused_f32; 429: svnet_fp_fused_f32, svnet_fp_fused_supported, svnet_fp_fused_rows_tile; 430: svnet_sa_global_f32, svnet_sa_global_supported, svnet_sa_global_rows_tile; 431: svnet_pool_gather_attr_f32, the attribute fields attr, A, attr_vectors, attr_out at the end of svnet_batch_desc; 432: svnet_vn_fold_f32, svnet_vn_tables_f32, svnet_vn_edge_mean_f32, svnet_vn_supported, svnet_vn_workspace_bytes; 433: svnet_vn_point_supported, svnet_vn_point_workspace_bytes, svnet_vn_point_fold_f32, svnet_vn_point_f32, svnet_vn_cloud_mean_f32, svnet_vn_std_pool_supported, svnet_vn_std_pool_workspace_bytes, svnet_vn_std_pool_f32).  svnet_version() returns the value the
+ * written by its consumer, svnet_slices_sum_*; 402: GX of svnet_v2s_bwd_*, gw of svnet_xyzblock_bwd_f32 and col_sum of svnet_gemm_f32 are sliced accumulators; 403: svnet_binweight_grad_f32 takes sliced inputs; 421: svnet_three_nn_f32, svnet_three_interpolate_f32; 422: svnet_ball_query_f32, svnet_group_points_f32; 423: svnet_vlinear_stats_f32 is gone; 424: svnet_edgeblock_fwd_tier, svnet_edgeblock_bwd_tier, svnet_edgeblock_wgrad_tier, svnet_xyzblock_tier; 425: svnet_pointset_reverse_i32, svnet_three_interpolate_bwd_f32, svnet_group_points_bwd_f32; 426: wbt of svnet_edgeblock_wbt_bf16 is 512 values longer, the all-zero fragment; 427: svnet_ball_query_msg_f32, svnet_group_points_msg_f32, svnet_group_points_msg_bwd_f32; 428: svnet_sa_fold_f32, svnet_sa_fused_f32; 429: svnet_fp_fused_f32, svnet_fp_fused_supported, svnet_fp_fused_rows_tile; 430: svnet_sa_global_f32, svnet_sa_global_supported, svnet_sa_global_rows_tile; 431: svnet_pool_gather_attr_f32, the attribute fields attr, A, attr_vectors, attr_out at the end of svnet_batch_desc; 432: svnet_vn_fold_f32, svnet_vn_tables_f32, svnet_vn_edge_mean_f32, svnet_vn_supported, svnet_vn_workspace_bytes; 433: svnet_vn_point_supported, svnet_vn_point_workspace_bytes, svnet_vn_point_fold_f32, svnet_vn_point_f32, svnet_vn_cloud_mean_f32, svnet_vn_std_pool_supported, svnet_vn_std_pool_workspace_bytes, svnet_vn_std_pool_f32; 434: svnet_vn_edge2_supported, svnet_vn_edge2_mean_f32, svnet_vn_std_coords_supported, svnet_vn_std_coords_f32).  svnet_version() returns the value the
  * library was BUILT with: a caller compiled against another header must refuse to run (svnet_amd/_lib.py does).                   */
-#define SVNET_ABI_VERSION 433
+#define SVNET_ABI_VERSION 434
 int svnet_version(void);
 const char* svnet_last_error(void);
 
@@ -1066,6 +1066,39 @@ int svnet_vn_std_pool_supported(int64_t N, int64_t C, int64_t Cg, int64_t Cy);
 size_t svnet_vn_std_pool_workspace_bytes(int64_t B, int64_t N, int64_t C, int64_t Cg);
 int svnet_vn_std_pool_f32(const float* x, const float* g, const float* y, const float* w_lin, int64_t B, int64_t N, int64_t C, int64_t Cg,
                           int64_t Cy, void* workspace, size_t workspace_bytes, float* h, void* stream);
+
+/* ------------------------------------------------------------------ fused two-layer vector-neuron edge level for inference: two layers per edge, mean
+ * (models/vn_dgcnn_partseg.py: get_graph_feature -> conv1 -> conv2 -> pool1 and conv3 -> conv4 -> pool2 with pooling = 'mean', in eval
+ * mode: two VNLinearLeakyReLU layers per edge in front of the mean over the k neighbours).  Layer 1 (C -> O1, Od1 direction rows) is the
+ * edge level above: its tables come from svnet_vn_tables_f32 with svnet_vn_fold_f32's folded1.  Layer 2 (O1 -> O2, Od2 direction rows)
+ * acts on layer 1's non-linear output, a dense product per edge; it is folded by svnet_vn_point_fold_f32 with Cg = 0:
+ * folded2 = WT [O1][O2 + Od2] | s2 [O2] | t2 [O2].  The conventions (fl(), fmaf, EPS, Od) are the edge level's.
+ * svnet_vn_edge2_mean_f32: layer 1's tables (workspace), idx [B,N,k] int64, folded1, folded2 -> out [B,O2,3,N].  Per edge (n, j),
+ *     m = idx[n,j] clamped into 0 .. N-1:
+ *         layer 1   y1[c,a], c < O1: svnet_vn_edge_mean_f32's per-edge y (edge, norm, leaky on folded1 with slope1), before its sum.
+ *         layer 2   per row r of W2 = [w_feat2 | w_dir2] stacked and component a: acc = +0; for c ascending over O1:
+ *                   acc = fmaf(y1[c,a], W2[r,c], acc).  K is never split: no value depends on tiling.  p[o,a] are the w_feat2 rows,
+ *                   d[od,a] the w_dir2 rows (od = o, or 0 with Od2 = 1);  y2 = the norm / leaky rule on p, d, s2[o], t2[o] with slope2.
+ *     out[b,o,a,n] = fl((sum over j ascending from +0 of y2_j[o,a]) / fl(k)).  One launch that writes 3 O2 floats per point and nothing
+ *     else: layer 1's outputs stay on the chip.  No host read, no atomics: capturable, reproducible.  Inputs are assumed finite.
+ * svnet_vn_edge2_supported (1 / 0, a pure host function): 1 <= k <= 64, k <= N <= 32768, 1 <= C, O1, O2 <= 128, Od1 = O1 or 1, Od2 = O2 or 1.
+ * Errors as svnet_vn_edge_mean_f32: a null pointer or B < 1 is SVNET_E_ARG, a shape outside the limits SVNET_E_UNSUPPORTED (as is
+ * B * ceil(N / P) > 2^31 - 1 workgroups, P >= 1 the points of one), a workspace below svnet_vn_workspace_bytes(B, N, O1, Od1)
+ * SVNET_E_WORKSPACE; svnet_last_error names the entry.                                                                              */
+int svnet_vn_edge2_supported(int64_t N, int64_t k, int64_t C, int64_t O1, int64_t Od1, int64_t O2, int64_t Od2);
+int svnet_vn_edge2_mean_f32(const float* workspace, size_t workspace_bytes, const int64_t* idx, const float* folded1, const float* folded2,
+                            int64_t B, int64_t N, int64_t k, int64_t C, int64_t O1, int64_t Od1, int64_t O2, int64_t Od2,
+                            float slope1, float slope2, float* out, void* stream);
+
+/* ------------------------------------------------------------------ frame coordinates per point (models/vn_dgcnn_partseg.py: the einsum of the
+ * levels' features with VNStdFeature's frame, unpooled).  svnet_vn_std_coords_f32: x [B,C,3,N], y [B,Cy,3,N] (vn2's output), w_lin [3,Cy]
+ * (vn_lin.weight) -> e [B,3C,N]: e[b, 3 i + k, n] = the coordinates rule of svnet_vn_std_pool_f32 on v_i = x[b,i,:,n] and its frame rows
+ * z[k] - the same device functions, so max over n of e is that entry's h[b, 3 i + k] bit for bit.  One launch, stores along n, no host
+ * read, no atomics.  svnet_vn_std_coords_supported (1 / 0, a pure host function): 1 <= N <= 32768, 1 <= C <= 512, 1 <= Cy <= 512.
+ * Errors: a null pointer or B outside 1 .. 65535 is SVNET_E_ARG, a shape outside the limits SVNET_E_UNSUPPORTED.                       */
+int svnet_vn_std_coords_supported(int64_t N, int64_t C, int64_t Cy);
+int svnet_vn_std_coords_f32(const float* x, const float* y, const float* w_lin, int64_t B, int64_t N, int64_t C, int64_t Cy, float* e,
+                            void* stream);
 
 /* ------------------------------------------------------------------ epoch metrics (main_cls_dgcnn.py:187-251, main_partseg_dgcnn.py:185-279,
  * utils.py:68-91 calculate_shape_IoU; the accuracy scores of sklearn.metrics are functions of the confusion matrix)

@@ -1,6 +1,6 @@
 """What the front ends of the fused vector-neuron kernels share, the edge level (svnet_amd/vn_fused.py) and the tail
 (svnet_amd/vn_tail.py): the checks on a VNLinearLeakyReLU that is to be folded, the workspace that grows and retires, the folded layer
-- its buffer, refresh() and release() - and the eval-only wrapper of a VN_DGCNN_CLS.  Private: the public names, what a level's buffer
+- its buffer, refresh() and release() - and the eval-only wrapper of a vector-neuron model.  Private: the public names, what a level's buffer
 holds, which kernels run and their limits stay in those two modules.  The device side of the same is svnet_amd/csrc/vn_math.h.
 """
 import torch
@@ -89,15 +89,21 @@ class Folded:
 
 
 class EvalOnly(torch.nn.Module):
-    """A wrapper that holds a VN_DGCNN_CLS and computes its eval-mode forward.  Its own `training` flag is the model's at construction
+    """A wrapper that holds a vector-neuron model - a VN_DGCNN_CLS, or what a subclass names in model_class() - and computes its
+    eval-mode forward.  Its own `training` flag is the model's at construction
     (a new nn.Module starts in train mode) and follows train() / eval() called on the wrapper; eval_only() reads the model's flag, so
     a mode set on the model directly is honoured as well.  Train mode is refused: batch statistics are not what the kernels compute."""
 
-    def __init__(self, model):
+    @staticmethod
+    def model_class():
         from .models.vn_dgcnn_cls import VN_DGCNN_CLS
+        return VN_DGCNN_CLS
+
+    def __init__(self, model):
         super().__init__()
-        if not isinstance(model, VN_DGCNN_CLS):
-            raise TypeError("%s: needs a VN_DGCNN_CLS, got %s" % (type(self).__name__, type(model).__name__))
+        cls = self.model_class()
+        if not isinstance(model, cls):
+            raise TypeError("%s: needs a %s, got %s" % (type(self).__name__, cls.__name__, type(model).__name__))
         self.model = model
         self.training = model.training
 

@@ -18,6 +18,9 @@
 //                          slabs of 64 through LDS; a thread owns a column (i, k) and walks the run's points n-ascending, keeping the
 //                          maximum and the sum, which go to the workspace as per-run partials.
 //   vn_std_finish_kernel   per column the maximum of the runs' maxima and the runs' sums added in order (split_reduce.h), over fl(N).
+//   vn_std_coords_kernel   grid (runs, B): the same frame rows, then the coordinates of every channel of x per point, unpooled, stored
+//                          along n: what VN_DGCNN_PSEG's head reads of the levels' features.  The frame rows and the coordinates are
+//                          stated once (vt_stage_frame, vt_coordinate) and both kernels call them.
 // The fold of the statistics and the norm / BatchNorm / leaky arithmetic are vn_math.h's, shared with vn_edge.hip.  Built with
 // -ffp-contract=off (Makefile, NO_CONTRACT).  No atomics.
 #include "vn_math.h"
@@ -269,15 +272,12 @@ __global__ __launch_bounds__(VT_THREADS) void vn_cloud_mean_kernel(const float* 
     }
 }
 
-// grid (runs, B).  pmax, psum: [runs][B][3 I], I = C + Cg.
-__global__ __launch_bounds__(VT_THREADS) void vn_std_pool_kernel(const float* __restrict__ x, const float* __restrict__ g, const float* __restrict__ y,
-                                                                 const float* __restrict__ wlin, int N, int C, int Cg, int Cy, float* __restrict__ pmax,
-                                                                 float* __restrict__ psum) {
-    __shared__ __align__(16) float zs[VT_RUN * 12];      // [p][k][a | pad]: the frame rows of the run's points
-    __shared__ float vs[VT_SLAB * VT_VS];                // [channel of the slab][a][p]
-    const int tid = threadIdx.x, j = blockIdx.x;
-    const int64_t b = blockIdx.y, B = gridDim.y;
-    const int n0 = VT_RUN * j, np = N - n0 < VT_RUN ? N - n0 : VT_RUN;
+// ---- the two rules of the learnt frame, stated once: the standardise-and-pool kernel and the per-point coordinates kernel call them
+// frame rows: z[k][a](n) = +0, then fmaf(y[c,a,n], w_lin[k,c], z) for c ascending over Cy.  The first 3 VT_RUN threads of a workgroup take
+// an (a, point) pair of the run at n0 each and leave zs [p][k][a | pad]; a point past the run's end reads the cloud's last one.
+__device__ __forceinline__ void vt_stage_frame(const float* __restrict__ y, const float* __restrict__ wlin, int64_t b, int n0, int np, int N, int Cy,
+                                               float* __restrict__ zs) {
+    const int tid = threadIdx.x;
     if (tid < 3 * VT_RUN) {
         const int a = tid / VT_RUN, p = tid - a * VT_RUN;
         const int n = p < np ? n0 + p : N - 1;
@@ -295,6 +295,20 @@ __global__ __launch_bounds__(VT_THREADS) void vn_std_pool_kernel(const float* __
         zs[p * 12 + 8 + a] = z2;
         if (a == 0) zs[p * 12 + 3] = zs[p * 12 + 7] = zs[p * 12 + 11] = 0.f;
     }
+}
+// coordinates: e[i,k](n) = fmaf(v[2], z[k][2], fmaf(v[1], z[k][1], fl(v[0] z[k][0]))), z = the frame row k of the point
+__device__ __forceinline__ float vt_coordinate(float v0, float v1, float v2, const float4& z) { return fmaf(v2, z.z, fmaf(v1, z.y, v0 * z.x)); }
+
+// grid (runs, B).  pmax, psum: [runs][B][3 I], I = C + Cg.
+__global__ __launch_bounds__(VT_THREADS) void vn_std_pool_kernel(const float* __restrict__ x, const float* __restrict__ g, const float* __restrict__ y,
+                                                                 const float* __restrict__ wlin, int N, int C, int Cg, int Cy, float* __restrict__ pmax,
+                                                                 float* __restrict__ psum) {
+    __shared__ __align__(16) float zs[VT_RUN * 12];      // [p][k][a | pad]: the frame rows of the run's points
+    __shared__ float vs[VT_SLAB * VT_VS];                // [channel of the slab][a][p]
+    const int tid = threadIdx.x, j = blockIdx.x;
+    const int64_t b = blockIdx.y, B = gridDim.y;
+    const int n0 = VT_RUN * j, np = N - n0 < VT_RUN ? N - n0 : VT_RUN;
+    vt_stage_frame(y, wlin, b, n0, np, N, Cy, zs);
     const int I = C + Cg;
     const int64_t total = B * 3 * I;
     const int ci = tid / 3, k = tid - ci * 3;
@@ -313,7 +327,7 @@ __global__ __launch_bounds__(VT_THREADS) void vn_std_pool_kernel(const float* __
                 const float* v = vs + ci * VT_VS;
                 for (int p = 0; p < np; ++p) {
                     const float4 z = *reinterpret_cast<const float4*>(zs + p * 12 + 4 * k);
-                    const float e = fmaf(v[2 * VT_RUN + p], z.z, fmaf(v[VT_RUN + p], z.y, v[p] * z.x));
+                    const float e = vt_coordinate(v[p], v[VT_RUN + p], v[2 * VT_RUN + p], z);
                     sum += e;
                     best = p == 0 || e > best ? e : best;
                 }
@@ -322,7 +336,7 @@ __global__ __launch_bounds__(VT_THREADS) void vn_std_pool_kernel(const float* __
                 const float g0 = gv[0], g1 = gv[1], g2 = gv[2];
                 for (int p = 0; p < np; ++p) {
                     const float4 z = *reinterpret_cast<const float4*>(zs + p * 12 + 4 * k);
-                    const float e = fmaf(g2, z.z, fmaf(g1, z.y, g0 * z.x));
+                    const float e = vt_coordinate(g0, g1, g2, z);
                     sum += e;
                     best = p == 0 || e > best ? e : best;
                 }
@@ -347,6 +361,29 @@ __global__ __launch_bounds__(VT_THREADS) void vn_std_finish_kernel(const float* 
     const int64_t b = e / cols, col = e - b * cols;
     h[b * 2 * cols + col] = best;
     h[b * 2 * cols + cols + col] = ordered_chunk_sum(psum, runs, total, e) / (float)N;
+}
+
+// grid (runs, B): the frame rows of the run's 64 points into LDS, then a thread takes a (channel, point) pair - point fastest, so the loads
+// and the stores of a wave run along n - and writes the channel's three coordinates.  e [B][3 C][N].
+__global__ __launch_bounds__(VT_THREADS) void vn_std_coords_kernel(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ wlin,
+                                                                   int N, int C, int Cy, float* __restrict__ e) {
+    __shared__ __align__(16) float zs[VT_RUN * 12];      // [p][k][a | pad]
+    const int tid = threadIdx.x;
+    const int64_t b = blockIdx.y;
+    const int n0 = VT_RUN * blockIdx.x, np = N - n0 < VT_RUN ? N - n0 : VT_RUN;
+    vt_stage_frame(y, wlin, b, n0, np, N, Cy, zs);
+    __syncthreads();
+    const float* xb = x + b * C * 3 * N + n0;
+    float* eb = e + b * 3 * C * N + n0;
+    for (int w = tid; w < C * VT_RUN; w += VT_THREADS) {
+        const int i = w / VT_RUN, p = w - i * VT_RUN;
+        if (p >= np) continue;
+        const float* xv = xb + (int64_t)i * 3 * N + p;
+        const float v0 = xv[0], v1 = xv[N], v2 = xv[2 * (int64_t)N];
+        float* ev = eb + (int64_t)i * 3 * N + p;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) ev[(int64_t)k * N] = vt_coordinate(v0, v1, v2, *reinterpret_cast<const float4*>(zs + p * 12 + 4 * k));
+    }
 }
 
 template <int NPT, bool SHARE>
@@ -463,5 +500,19 @@ extern "C" int svnet_vn_std_pool_f32(const float* x, const float* g, const float
     hipLaunchKernelGGL(vn_std_finish_kernel, dim3((unsigned)svnet_cdiv(total, VT_THREADS)), dim3(VT_THREADS), 0, (hipStream_t)stream, pmax, psum, runs, total,
                        (int)cols, (int)N, h);
     SVNET_CHECK_LAUNCH("vn_std_finish_kernel");
+    return SVNET_OK;
+}
+
+extern "C" int svnet_vn_std_coords_supported(int64_t N, int64_t C, int64_t Cy) { return vt_std_ok(N, C, 0, Cy) ? 1 : 0; }
+
+extern "C" int svnet_vn_std_coords_f32(const float* x, const float* y, const float* w_lin, int64_t B, int64_t N, int64_t C, int64_t Cy, float* e,
+                                       void* stream) {
+    SVNET_REQUIRE(x && y && w_lin && e, SVNET_E_ARG, "svnet_vn_std_coords_f32: null x / y / w_lin / e");
+    SVNET_REQUIRE(vt_batch_ok(B), SVNET_E_ARG, "svnet_vn_std_coords_f32: B %lld must lie in 1 .. %d", (long long)B, VT_MAX_B);
+    SVNET_REQUIRE(vt_std_ok(N, C, 0, Cy), SVNET_E_UNSUPPORTED, "svnet_vn_std_coords_f32: N %lld, C %lld, Cy %lld: needs 1 <= N <= %d, 1 <= C <= %d, 1 <= Cy <= %d",
+                  (long long)N, (long long)C, (long long)Cy, VN_MAX_N, VT_MAX_C, VT_MAX_C);
+    hipLaunchKernelGGL(vn_std_coords_kernel, dim3((unsigned)svnet_cdiv(N, VT_RUN), (unsigned)B), dim3(VT_THREADS), 0, (hipStream_t)stream, x, y, w_lin, (int)N,
+                       (int)C, (int)Cy, e);
+    SVNET_CHECK_LAUNCH("vn_std_coords_kernel");
     return SVNET_OK;
 }

@@ -13,6 +13,7 @@ svnet_amd/sa_fused.py: the modules stay as they are, this is an entry beside the
 
     folded = fold_vn_layer(layer)                      # a VNLinearLeakyReLU over 2C -> O; buffers allocated once, refresh()
     out = vn_edge_mean(x, idx, folded, out=None)       # x [B,C,3,N] f32, idx [B,N,k] int64 -> [B,O,3,N]
+    out = vn_edge2_mean(x, idx, folded1, folded2)      # two layers per edge in front of the mean (VN_DGCNN_PSEG's levels): its docstring
     fused = FusedVNDGCNN(model, tail=False)            # an nn.Module: the eval-mode forward of a VN_DGCNN_CLS; tail=True: the rest of
                                                        # the network through svnet_amd.vn_tail.FusedVNTail as well
     logits = fused(x)                                  # x [B,3,N]; fused.last_idx: the four neighbour lists of this call
@@ -42,7 +43,7 @@ import torch
 
 from . import _call, _lib, _pointset, _vn
 
-__all__ = ["fold_vn_layer", "vn_edge_mean", "supported", "FoldedVNLayer", "FusedVNDGCNN", "MAX_K", "MAX_C", "MAX_O"]
+__all__ = ["fold_vn_layer", "vn_edge_mean", "vn_edge2_mean", "supported", "supported2", "FoldedVNLayer", "FusedVNDGCNN", "MAX_K", "MAX_C", "MAX_O"]
 
 _WHAT = "the fused vector-neuron edge level"   # in the messages of _pointset.check_tensors
 MAX_K, MAX_C, MAX_O = 64, 128, 128
@@ -122,6 +123,73 @@ def vn_edge_mean(x, idx, folded, out=None):
     if out is None:
         out = torch.empty(B, folded.O, 3, N, dtype=_F32, device=x.device)
     _launch(x, idx, folded, out, B, N, k)
+    return out
+
+
+def supported2(N, k, C, O1, Od1, O2, Od2):
+    """Whether the two-layer kernel takes this level (vn_edge2_mean, limits)."""
+    return bool(_lib.lib().svnet_vn_edge2_supported(int(N), int(k), int(C), int(O1), int(Od1), int(O2), int(Od2)))
+
+
+def _launch2(x, idx, folded1, folded2, out, B, N, k):
+    ws = folded1.tables(B, N)
+    with torch.cuda.device(x.device):
+        _lib.call("svnet_vn_tables_f32", _call.p(x), _call.p(folded1.folded), B, N, folded1.C, folded1.O, folded1.Od, _call.p(ws), ws.numel(),
+                  _call.stream())
+        _lib.call("svnet_vn_edge2_mean_f32", _call.p(ws), ws.numel(), _call.p(idx), _call.p(folded1.folded), _call.p(folded2.folded), B, N, k,
+                  folded1.C, folded1.O, folded1.Od, folded2.O, folded2.Od, folded1.slope, folded2.slope, _call.p(out), _call.stream())
+
+
+def vn_edge2_mean(x, idx, folded1, folded2, out=None):
+    """x [B,C,3,N] float32, idx [B,N,k] int64, folded1 a FoldedVNLayer over 2C -> O1 and folded2 a vn_tail.FoldedVNPoint over O1 -> O2
+    without constant channels -> out [B,O2,3,N]: the mean over the k edges of the two layers' eval-mode forward on [x_j - x_i | x_i]
+    (svnet_amd/csrc/vn_edge2.hip), one edge level of VN_DGCNN_PSEG.  The contract, in the words of the module docstring:
+
+        layer 1   per edge (n, j), m = idx[n,j] clamped: y1[c,a], c < O1 - exactly vn_edge_mean's per-edge y (edge, norm, leaky on
+                  folded1 with its slope), before its sum.
+        layer 2   per row r of W2 = [W_feat2 | W_dir2] stacked and component a: acc = +0; for c ascending over O1:
+                  acc = fmaf(y1[c,a], W2[r,c], acc).  K is never split.  p[o,a] are the feat rows, d[od,a] the dir rows (od = o, or 0
+                  with Od2 = 1); y2 = norm, leaky on p, d, s2[o], t2[o] with folded2's slope.
+        mean      out[o,a,n] = fl((sum over j ascending from +0 of y2_j[o,a]) / fl(k)).
+        limits    1 <= k <= 64, k <= N <= 32768, 1 <= C, O1, O2 <= 128, Od1 is O1 or 1, Od2 is O2 or 1 (`supported2`).
+
+    Two launches on the current stream - the tables of layer 1, then the edge pass, which writes 3 O2 floats per point and nothing
+    else: layer 1's outputs stay on the chip - and no host read.  Entries of idx outside 0 .. N-1 are clamped into the cloud.  No
+    argument may require grad.  tests/vn_pseg_ref.py restates the contract; results are compared with it as bit patterns."""
+    from .vn_tail import FoldedVNPoint
+    name = "vn_edge2_mean"
+    if not isinstance(folded1, FoldedVNLayer):
+        raise TypeError("%s: folded1 must be a FoldedVNLayer (vn_fused.fold_vn_layer), got %s" % (name, type(folded1).__name__))
+    if not isinstance(folded2, FoldedVNPoint):
+        raise TypeError("%s: folded2 must be a FoldedVNPoint (vn_tail.fold_vn_point), got %s" % (name, type(folded2).__name__))
+    args = {"x": x, "idx": idx}
+    dtypes = [_F32, torch.int64]
+    if out is not None:
+        args["out"] = out
+        dtypes.append(_F32)
+    _pointset.check_tensors(name, args, dtypes, _WHAT)
+    if x.dim() != 4 or x.shape[2] != 3 or x.shape[0] < 1:
+        raise ValueError("%s: x must be [B,C,3,N], got %s" % (name, tuple(x.shape)))
+    B, C, _, N = (int(v) for v in x.shape)
+    if idx.dim() != 3 or idx.shape[0] != B or idx.shape[1] != N:
+        raise ValueError("%s: idx must be [B,N,k] with B = %d, N = %d, got %s" % (name, B, N, tuple(idx.shape)))
+    k = int(idx.shape[2])
+    if C != folded1.C:
+        raise ValueError("%s: the first layer takes %d vector channels, x has %d" % (name, folded1.C, C))
+    if folded2.Cg != 0 or folded2.C != folded1.O:
+        raise ValueError("%s: the second layer must take the first one's %d channels and no constant ones, it takes %d + %d"
+                         % (name, folded1.O, folded2.C, folded2.Cg))
+    if out is not None and tuple(out.shape) != (B, folded2.O, 3, N):
+        raise ValueError("%s: out must be [B,O2,3,N] = %s, got %s" % (name, (B, folded2.O, 3, N), tuple(out.shape)))
+    _call.hip(x, idx, out)
+    if folded1.device != x.device or folded2.device != x.device:
+        raise ValueError("%s: the layers are on %s and %s, x on %s" % (name, folded1.device, folded2.device, x.device))
+    if not supported2(N, k, C, folded1.O, folded1.Od, folded2.O, folded2.Od):
+        raise _lib.SvnetHipError("%s: N = %d, k = %d, C = %d, O1 = %d, O2 = %d is not supported (1 <= k <= %d, k <= N <= %d, C <= %d, O1, O2 <= %d)"
+                                 % (name, N, k, C, folded1.O, folded2.O, MAX_K, _pointset.MAX_N, MAX_C, MAX_O))
+    if out is None:
+        out = torch.empty(B, folded2.O, 3, N, dtype=_F32, device=x.device)
+    _launch2(x, idx, folded1, folded2, out, B, N, k)
     return out
 
 

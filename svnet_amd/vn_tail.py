@@ -15,6 +15,7 @@ scope, as in svnet_amd/vn_fused.py: the modules stay as they are, this is an ent
     out = vn_point(x, folded, cloud=None, out=None)    # x [B,C,3,N], cloud [B,Cg,3] -> [B,O,3,N]
     m = vn_cloud_mean(x, out=None)                     # x [B,C,3,N] -> [B,C,3]
     h = vn_std_pool(x, y, w_lin, cloud=None, out=None) # x [B,C,3,N], y [B,Cy,3,N], w_lin [3,Cy], cloud [B,Cg,3] -> [B, 6 (C + Cg)]
+    e = vn_std_coords(x, y, w_lin, out=None)           # the same coordinates per point, unpooled -> [B, 3 C, N] (VN_DGCNN_PSEG's head)
     tail = FusedVNTail(model)                          # the four levels' outputs -> logits; vn_fused.FusedVNDGCNN(model, tail=True)
 
 The contract, for one cloud (fl() is rounding to fp32, every operation rounded once, nothing contracted but the stated fmaf;
@@ -43,7 +44,8 @@ import torch
 
 from . import _call, _lib, _pointset, _vn
 
-__all__ = ["fold_vn_point", "vn_point", "vn_cloud_mean", "vn_std_pool", "supported_point", "supported_std", "FoldedVNPoint", "FusedVNTail",
+__all__ = ["fold_vn_point", "vn_point", "vn_cloud_mean", "vn_std_pool", "vn_std_coords", "supported_point", "supported_std", "supported_coords",
+           "FoldedVNPoint", "FusedVNTail",
            "MAX_C", "MAX_O", "MAX_B"]
 
 _WHAT = "the fused vector-neuron tail"   # in the messages of _pointset.check_tensors
@@ -197,6 +199,40 @@ def vn_std_pool(x, y, w_lin, cloud=None, out=None, workspace=None):
     with torch.cuda.device(x.device):
         _lib.call("svnet_vn_std_pool_f32", _call.p(x), _call.p(cloud), _call.p(y), _call.p(w_lin), B, N, C, Cg, Cy, _call.p(ws), ws.numel(), _call.p(out),
                   _call.stream())
+    return out
+
+
+def supported_coords(N, C, Cy):
+    """Whether the per-point coordinates kernel takes these widths (vn_std_coords, limits)."""
+    return bool(_lib.lib().svnet_vn_std_coords_supported(int(N), int(C), int(Cy)))
+
+
+def vn_std_coords(x, y, w_lin, out=None):
+    """x [B,C,3,N], y [B,Cy,3,N] (vn2's output), w_lin [3,Cy] (vn_lin.weight as it lies) -> out [B,3C,N]: out[b, 3 i + k, n] is the
+    coordinate e[i,k](n) of x[b,i,:,n] in the frame w_lin y, by the frame rows and coordinates rules of the std-pool stage (module
+    docstring) - the same device functions, so out.amax(-1) is vn_std_pool's h[:, :3C] bit for bit.  What VN_DGCNN_PSEG's head reads of
+    the levels' features.  One launch on the current stream, stores along n, no host read.  1 <= N <= 32768, 1 <= C, Cy <= 512,
+    B <= 65535 (`supported_coords`).  No argument may require grad."""
+    name = "vn_std_coords"
+    _check(name, {"x": x, "y": y, "w_lin": w_lin, "out": out})
+    if x.dim() != 4 or x.shape[2] != 3 or x.shape[0] < 1:
+        raise ValueError("%s: x must be [B,C,3,N], got %s" % (name, tuple(x.shape)))
+    B, C, _, N = (int(v) for v in x.shape)
+    if y.dim() != 4 or y.shape[0] != B or y.shape[2] != 3 or y.shape[3] != N or y.shape[1] < 1:
+        raise ValueError("%s: y must be [B,Cy,3,N] with B = %d, N = %d, got %s" % (name, B, N, tuple(y.shape)))
+    Cy = int(y.shape[1])
+    if tuple(w_lin.shape) != (3, Cy):
+        raise ValueError("%s: w_lin must be [3,Cy] = %s (normalize_frame = False), got %s" % (name, (3, Cy), tuple(w_lin.shape)))
+    if out is not None and tuple(out.shape) != (B, 3 * C, N):
+        raise ValueError("%s: out must be [B,3C,N] = %s, got %s" % (name, (B, 3 * C, N), tuple(out.shape)))
+    _call.hip(x, y, w_lin, out)
+    if B > MAX_B or not supported_coords(N, C, Cy):
+        raise _lib.SvnetHipError("%s: B = %d, N = %d, C = %d, Cy = %d is not supported (B <= %d, 1 <= N <= %d, 1 <= C, Cy <= %d)"
+                                 % (name, B, N, C, Cy, MAX_B, _pointset.MAX_N, MAX_C))
+    if out is None:
+        out = torch.empty(B, 3 * C, N, dtype=_F32, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.call("svnet_vn_std_coords_f32", _call.p(x), _call.p(y), _call.p(w_lin), B, N, C, Cy, _call.p(out), _call.stream())
     return out
 
 
