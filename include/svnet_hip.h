@@ -45,9 +45,9 @@ int svnet_slices_sum_f64(double* buf, int64_t L, void* stream);
 
 /* ABI version = 100 * round-of-change + serial.  It changes whenever an entry point gains / loses an argument or a caller-owned buffer
  * changes its required length (200: sliced accumulators, SVNET_SLICED_LEN; 400: this header; 401: the totals of a sliced accumulator are
- * written by its consumer, svnet_slices_sum_*; 402: GX of svnet_v2s_bwd_*, gw of svnet_xyzblock_bwd_f32 and col_sum of svnet_gemm_f32 are sliced accumulators; 403: svnet_binweight_grad_f32 takes sliced inputs; 421: svnet_three_nn_f32, svnet_three_interpolate_f32; 422: svnet_ball_query_f32, svnet_group_points_f32; 423: svnet_vlinear_stats_f32 is gone; 424: svnet_edgeblock_fwd_tier, svnet_edgeblock_bwd_tier, svnet_edgeblock_wgrad_tier, svnet_xyzblock_tier; 425: svnet_pointset_reverse_i32, svnet_three_interpolate_bwd_f32, svnet_group_points_bwd_f32; 426: wbt of svnet_edgeblock_wbt_bf16 is 512 values longer, the all-zero fragment; 427: svnet_ball_query_msg_f32, svnet_group_points_msg_f32, svnet_group_points_msg_bwd_f32; 428: svnet_sa_fold_f32, svnet_sa_fused_f32; 429: svnet_fp_fused_f32, svnet_fp_fused_supported, svnet_fp_fused_rows_tile; 430: svnet_sa_global_f32, svnet_sa_global_supported, svnet_sa_global_rows_tile; 431: svnet_pool_gather_attr_f32, the attribute fields attr, A, attr_vectors, attr_out at the end of svnet_batch_desc; 432: svnet_vn_fold_f32, svnet_vn_tables_f32, svnet_vn_edge_mean_f32, svnet_vn_supported, svnet_vn_workspace_bytes; 433: svnet_vn_point_supported, svnet_vn_point_workspace_bytes, svnet_vn_point_fold_f32, svnet_vn_point_f32, svnet_vn_cloud_mean_f32, svnet_vn_std_pool_supported, svnet_vn_std_pool_workspace_bytes, svnet_vn_std_pool_f32; 434: svnet_vn_edge2_supported, svnet_vn_edge2_mean_f32, svnet_vn_std_coords_supported, svnet_vn_std_coords_f32).  svnet_version() returns the value the
+ * written by its consumer, svnet_slices_sum_*; 402: GX of svnet_v2s_bwd_*, gw of svnet_xyzblock_bwd_f32 and col_sum of svnet_gemm_f32 are sliced accumulators; 403: svnet_binweight_grad_f32 takes sliced inputs; 421: svnet_three_nn_f32, svnet_three_interpolate_f32; 422: svnet_ball_query_f32, svnet_group_points_f32; 423: svnet_vlinear_stats_f32 is gone; 424: svnet_edgeblock_fwd_tier, svnet_edgeblock_bwd_tier, svnet_edgeblock_wgrad_tier, svnet_xyzblock_tier; 425: svnet_pointset_reverse_i32, svnet_three_interpolate_bwd_f32, svnet_group_points_bwd_f32; 426: wbt of svnet_edgeblock_wbt_bf16 is 512 values longer, the all-zero fragment; 427: svnet_ball_query_msg_f32, svnet_group_points_msg_f32, svnet_group_points_msg_bwd_f32; 428: svnet_sa_fold_f32, svnet_sa_fused_f32; 429: svnet_fp_fused_f32, svnet_fp_fused_supported, svnet_fp_fused_rows_tile; 430: svnet_sa_global_f32, svnet_sa_global_supported, svnet_sa_global_rows_tile; 431: svnet_pool_gather_attr_f32, the attribute fields attr, A, attr_vectors, attr_out at the end of svnet_batch_desc; 432: svnet_vn_fold_f32, svnet_vn_tables_f32, svnet_vn_edge_mean_f32, svnet_vn_supported, svnet_vn_workspace_bytes; 433: svnet_vn_point_supported, svnet_vn_point_workspace_bytes, svnet_vn_point_fold_f32, svnet_vn_point_f32, svnet_vn_cloud_mean_f32, svnet_vn_std_pool_supported, svnet_vn_std_pool_workspace_bytes, svnet_vn_std_pool_f32; 434: svnet_vn_edge2_supported, svnet_vn_edge2_mean_f32, svnet_vn_std_coords_supported, svnet_vn_std_coords_f32; 435: svnet_vn_cross_supported, svnet_vn_cross_fold_f32, svnet_vn_edge_cross_mean_f32, svnet_vn_point_norm_supported, svnet_vn_point_norm_fold_f32, svnet_vn_point_norm_f32).  svnet_version() returns the value the
  * library was BUILT with: a caller compiled against another header must refuse to run (svnet_amd/_lib.py does).                   */
-#define SVNET_ABI_VERSION 434
+#define SVNET_ABI_VERSION 435
 int svnet_version(void);
 const char* svnet_last_error(void);
 
@@ -1099,6 +1099,43 @@ int svnet_vn_edge2_mean_f32(const float* workspace, size_t workspace_bytes, cons
 int svnet_vn_std_coords_supported(int64_t N, int64_t C, int64_t Cy);
 int svnet_vn_std_coords_f32(const float* x, const float* y, const float* w_lin, int64_t B, int64_t N, int64_t C, int64_t Cy, float* e,
                             void* stream);
+
+/* ------------------------------------------------------------------ fused vector-neuron cross edge level for inference
+ * (models/vn_pointnet_cls.py: get_graph_feature_cross -> conv_pos -> mean over k with pooling = 'mean', in eval mode: a VNLinearLeakyReLU
+ * over 3 -> O vector channels on the edge feature [x_j - x_i | x_i | x_j x x_i] of models/utils/vn_util.py:52-76, the cloud being ONE
+ * vector channel).  The cross product depends on the pair, so there are no point tables: one launch computes the feature per edge.
+ * svnet_vn_cross_fold_f32: w_feat [O,3] (map_to_feat.weight), w_dir [Od,3] (map_to_dir.weight), BatchNorm gamma, beta, running_mean,
+ *     running_var [O] -> folded, 3 (O + Od) + 2 O floats: W [O + Od][3] = [W_f | W_d] stacked | s [O] | t [O], s and t as svnet_vn_fold_f32.
+ *     One launch.
+ * svnet_vn_edge_cross_mean_f32: x [B,1,3,N], idx [B,N,k] int64, folded -> out [B,O,3,N].  Per edge (n, j), m = idx[n,j] clamped into
+ *     0 .. N-1 before any address is formed, xi = x[:,n], xj = x[:,m], every operation rounded once to fp32:
+ *         edge     e0[a] = xj[a] - xi[a];  e1[a] = xi[a];  e2 = xj x xi: e2[0] = fl(xj[1] xi[2]) - fl(xj[2] xi[1]),
+ *                  e2[1] = fl(xj[2] xi[0]) - fl(xj[0] xi[2]),  e2[2] = fl(xj[0] xi[1]) - fl(xj[1] xi[0]).
+ *         product  per row r of W and component a: acc = +0; for c = 0, 1, 2: acc = fmaf(e_c[a], W[r,c], acc).  p = the W_f rows, d the
+ *                  W_d rows (row 0 for every o with Od = 1).
+ *         norm, leaky, mean   as svnet_vn_edge_mean_f32 above, on p, d, s[o], t[o] and slope.
+ *     One launch that writes 3 O floats per point and nothing else; no workspace, no atomics, no host read; capturable.
+ * svnet_vn_cross_supported (1 / 0, a pure host function): 1 <= k <= 64, k <= N <= 32768, 1 <= O <= 128, Od = O or 1.
+ * Errors: a null pointer or B outside 1 .. 65535 is SVNET_E_ARG, a shape outside the limits SVNET_E_UNSUPPORTED.                       */
+int svnet_vn_cross_supported(int64_t N, int64_t k, int64_t O, int64_t Od);
+int svnet_vn_cross_fold_f32(const float* w_feat, const float* w_dir, const float* gamma, const float* beta, const float* running_mean,
+                            const float* running_var, int64_t O, int64_t Od, float eps, float* folded, void* stream);
+int svnet_vn_edge_cross_mean_f32(const float* x, const int64_t* idx, const float* folded, int64_t B, int64_t N, int64_t k, int64_t O, int64_t Od,
+                                 float slope, float* out, void* stream);
+
+/* ------------------------------------------------------------------ norm-only vector-neuron point layer (models/vn_pointnet_cls.py: bn3(conv3(x)),
+ * a VNLinear followed by a VNBatchNorm with no leaky rule, in eval mode).  The point kernel of svnet_vn_point_f32 with its epilogue
+ * exchanged: no direction rows, no constant channels.
+ * svnet_vn_point_norm_fold_f32: w_feat [O,C], BatchNorm gamma, beta, running_mean, running_var [O] -> folded, C O + 2 O floats:
+ *     WT [C][O] | s [O] | t [O].  One launch.
+ * svnet_vn_point_norm_f32: x [B,C,3,N], folded -> out [B,O,3,N]: the point term of svnet_vn_point_f32 with u = +0 (the c-ascending fmaf
+ *     chain over C, K never split), then q, r, g of the norm rule and out[o,a,n] = fl(p[a] g).  One launch.
+ * svnet_vn_point_norm_supported (1 / 0, a pure host function): 1 <= N <= 32768, 1 <= C <= 512, 1 <= O <= 512.
+ * Errors: a null pointer or B outside 1 .. 65535 is SVNET_E_ARG, a shape outside the limits SVNET_E_UNSUPPORTED.                       */
+int svnet_vn_point_norm_supported(int64_t N, int64_t C, int64_t O);
+int svnet_vn_point_norm_fold_f32(const float* w_feat, const float* gamma, const float* beta, const float* running_mean, const float* running_var,
+                                 int64_t C, int64_t O, float eps, float* folded, void* stream);
+int svnet_vn_point_norm_f32(const float* x, const float* folded, int64_t B, int64_t N, int64_t C, int64_t O, float* out, void* stream);
 
 /* ------------------------------------------------------------------ epoch metrics (main_cls_dgcnn.py:187-251, main_partseg_dgcnn.py:185-279,
  * utils.py:68-91 calculate_shape_IoU; the accuracy scores of sklearn.metrics are functions of the confusion matrix)

@@ -1,7 +1,7 @@
 // The arithmetic of a vector-neuron level (VNLinearLeakyReLU in eval mode, models/vn_layers.py:50-78), element by element: the ONE
-// statement of its fp32 sequence.  vn_edge.hip and vn_tail.hip walk their own layouts and call these, so the edge levels and the tail
+// statement of its fp32 sequence.  vn_edge.hip, vn_edge2.hip, vn_cross.hip and vn_tail.hip walk their own layouts and call these, so the levels and the tail
 // agree bit for bit by construction; nothing here knows a layout, a tiling or a launch geometry.  The contract in prose is in
-// svnet_amd/vn_fused.py; tests/vn_ref.py restates it.  Both files that include this (Makefile, NO_CONTRACT) are
+// svnet_amd/vn_fused.py; tests/vn_ref.py restates it.  Every file that includes this (Makefile, NO_CONTRACT) is
 // built with -ffp-contract=off; every operation its own rounding, fmaf where the contract has one.  Internal: not part of the C interface.
 #pragma once
 #include "pointset.h"
@@ -17,15 +17,19 @@ __device__ __forceinline__ void vn_bn_fold(float gamma, float beta, float rmean,
     t = beta - rmean * s;
 }
 
-// ---- p, d [3] of one (point or edge, channel) -> y [3]
-__device__ __forceinline__ void vn_norm_leaky(float p0, float p1, float p2, float d0, float d1, float d2, float so, float to, float slope,
-                                              float one_minus, float (&y)[3]) {
-    // the norm through BatchNorm's folded affine
+// ---- p [3] of one (point or edge, channel) -> u [3]: the norm through BatchNorm's folded affine.  A VNLinear followed by a VNBatchNorm
+// (the norm-only point layer of vn_tail.hip) ends here.
+__device__ __forceinline__ void vn_norm(float p0, float p1, float p2, float so, float to, float (&u)[3]) {
     const float q = fmaf(p2, p2, fmaf(p1, p1, p0 * p0));
     const float r = sqrtf(q) + VN_EPS;
     const float g = fmaf(r, so, to) / r;
-    const float u0 = p0 * g, u1 = p1 * g, u2 = p2 * g;
-    // the leaky rule
+    u[0] = p0 * g;
+    u[1] = p1 * g;
+    u[2] = p2 * g;
+}
+
+// ---- u (the normed p), d [3] -> y [3]: the leaky rule
+__device__ __forceinline__ void vn_leaky(float u0, float u1, float u2, float d0, float d1, float d2, float slope, float one_minus, float (&y)[3]) {
     const float dot = fmaf(u2, d2, fmaf(u1, d1, u0 * d0));
     const float dd = fmaf(d2, d2, fmaf(d1, d1, d0 * d0));
     float w0 = u0, w1 = u1, w2 = u2;
@@ -38,4 +42,12 @@ __device__ __forceinline__ void vn_norm_leaky(float p0, float p1, float p2, floa
     y[0] = fmaf(slope, u0, one_minus * w0);
     y[1] = fmaf(slope, u1, one_minus * w1);
     y[2] = fmaf(slope, u2, one_minus * w2);
+}
+
+// ---- p, d [3] of one (point or edge, channel) -> y [3]: the two halves in order
+__device__ __forceinline__ void vn_norm_leaky(float p0, float p1, float p2, float d0, float d1, float d2, float so, float to, float slope,
+                                              float one_minus, float (&y)[3]) {
+    float u[3];
+    vn_norm(p0, p1, p2, so, to, u);
+    vn_leaky(u[0], u[1], u[2], d0, d1, d2, slope, one_minus, y);
 }

@@ -13,6 +13,8 @@
 //                          d[o,0..2] of one point in one lane and the norm, BatchNorm and leaky epilogue runs in registers: neither p
 //                          nor d goes to memory.  The chain starts at the cloud term and K is never split.  With one direction row
 //                          (Od = 1) the row is computed once per point, by plain fmaf chains into LDS, and shared by every wave.
+//                          The epilogue is a policy: VtLeaky is the layer above; VtNormOnly is a VNLinear followed by a VNBatchNorm
+//                          (svnet_vn_point_norm_f32) - no direction rows, R = O, and the norm half of the rule alone.
 //   vn_cloud_mean_kernel   m [B,C,3]: per row of N floats the sums of runs of 64, n-ascending, then the runs' sums in order.
 //   vn_std_pool_kernel     grid (runs, B): the three frame rows z of the run's 64 points (chains over Cy) into LDS, then the channels in
 //                          slabs of 64 through LDS; a thread owns a column (i, k) and walks the run's points n-ascending, keeping the
@@ -58,7 +60,22 @@ inline int vt_point_tiles(int64_t N, int64_t C, bool share) {
     return 1;
 }
 
-// e over [K R | O]: WT[c][r] = row r of [W_f | W_d] at channel c; then s and t
+// ---- the epilogue of the point kernel on p, d [3] of one (point, channel); DIR: whether the layer has direction rows at all
+struct VtLeaky {
+    static constexpr bool DIR = true;
+    static __device__ __forceinline__ void apply(float p0, float p1, float p2, float d0, float d1, float d2, float so, float to, float slope,
+                                                 float one_minus, float (&y)[3]) {
+        vn_norm_leaky(p0, p1, p2, d0, d1, d2, so, to, slope, one_minus, y);
+    }
+};
+struct VtNormOnly {
+    static constexpr bool DIR = false;
+    static __device__ __forceinline__ void apply(float p0, float p1, float p2, float, float, float, float so, float to, float, float, float (&y)[3]) {
+        vn_norm(p0, p1, p2, so, to, y);
+    }
+};
+
+// e over [K R | O]: WT[c][r] = row r of [W_f | W_d] at channel c; then s and t.  Od = 0 (a layer without direction rows): w_d is not read.
 __global__ __launch_bounds__(VT_THREADS) void vn_point_fold_kernel(const float* __restrict__ wf, const float* __restrict__ wd, const float* __restrict__ gamma,
                                                                    const float* __restrict__ beta, const float* __restrict__ rmean,
                                                                    const float* __restrict__ rvar, int K, int O, int Od, float eps,
@@ -91,13 +108,13 @@ __global__ __launch_bounds__(VT_THREADS) void vn_cloud_term_kernel(const float* 
 // grid (ceil(N / TP), B), TP = 16 NPT.  A = the inputs from LDS (lane = point l & 15 at k = l >> 4), B = the weights from global memory
 // (lane = column l & 15 at k = l >> 4), D[i] = point 4 (l >> 4) + i, column l & 15.  K is padded to a multiple of 4 with zeros in both
 // operands; points past N are zeros in LDS and are not stored; columns past O are computed on a clamped address and not stored.
-template <int NPT, bool SHARE>
+template <int NPT, bool SHARE, class EPI>
 __global__ __launch_bounds__(VT_THREADS) void vn_point_kernel(const float* __restrict__ x, const float* __restrict__ WT, const float* __restrict__ s,
                                                               const float* __restrict__ t, const float* __restrict__ u, int N, int C, int O, float slope,
                                                               int vec, float* __restrict__ out) {
     extern __shared__ __align__(16) float vt_lds[];
     constexpr int TP = 16 * NPT, XS = vt_xs(NPT);
-    const int Od = SHARE ? 1 : O, R = O + Od, Kp = (C + 3) & ~3;
+    const int Od = !EPI::DIR ? 0 : SHARE ? 1 : O, R = O + Od, Kp = (C + 3) & ~3;
     float* xs = vt_lds;                                  // [Kp][XS]: x[c][a][p] at c XS + a TP + p
     float* ds = vt_lds + Kp * XS;                        // [3][TP]: the one direction row (SHARE)
     const int tid = threadIdx.x;
@@ -163,7 +180,7 @@ __global__ __launch_bounds__(VT_THREADS) void vn_point_kernel(const float* __res
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
             const float up = ub ? ub[a * R + oc] : 0.f;
-            const float ud = (!SHARE && ub) ? ub[a * R + O + oc] : 0.f;
+            const float ud = (EPI::DIR && !SHARE && ub) ? ub[a * R + O + oc] : 0.f;
 #pragma unroll
             for (int tt = 0; tt < NPT; ++tt) {
                 accp[tt][a] = vt_f32x4{up, up, up, up};
@@ -180,7 +197,7 @@ __global__ __launch_bounds__(VT_THREADS) void vn_point_kernel(const float* __res
             for (int uu = 0; uu < VT_U; ++uu) {
                 const int c = c0 + 4 * uu + kq, at = (c < C ? c : C - 1) * R;
                 wf[uu] = wcol[at];
-                wd[uu] = SHARE ? 0.f : wcol[at + O];
+                wd[uu] = SHARE || !EPI::DIR ? 0.f : wcol[at + O];
             }
         };
         // VT_U k-steps on the weights in wfc / wdc.  Whole blocks carry no branch, so their LDS reads are scheduled ahead of the
@@ -199,7 +216,7 @@ __global__ __launch_bounds__(VT_THREADS) void vn_point_kernel(const float* __res
                     for (int a = 0; a < 3; ++a) {
                         const float av = ap[a * TP + tt * 16];
                         accp[tt][a] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bf, accp[tt][a], 0, 0, 0);
-                        if (!SHARE) accd[tt][a] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bd, accd[tt][a], 0, 0, 0);
+                        if (EPI::DIR && !SHARE) accd[tt][a] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bd, accd[tt][a], 0, 0, 0);
                     }
                 }
             }
@@ -233,7 +250,7 @@ __global__ __launch_bounds__(VT_THREADS) void vn_point_kernel(const float* __res
                     d1 = accd[tt][1][i];
                     d2 = accd[tt][2][i];
                 }
-                vn_norm_leaky(accp[tt][0][i], accp[tt][1][i], accp[tt][2][i], d0, d1, d2, so, to, slope, one_minus, y);
+                EPI::apply(accp[tt][0][i], accp[tt][1][i], accp[tt][2][i], d0, d1, d2, so, to, slope, one_minus, y);
                 if (ov && n < N) {
                     ob[n] = y[0];
                     ob[(int64_t)N + n] = y[1];
@@ -386,11 +403,11 @@ __global__ __launch_bounds__(VT_THREADS) void vn_std_coords_kernel(const float* 
     }
 }
 
-template <int NPT, bool SHARE>
+template <int NPT, bool SHARE, class EPI>
 void vt_launch_point(dim3 grid, size_t lds, hipStream_t stream, const float* x, const float* WT, const float* s, const float* t, const float* u, int N, int C,
                      int O, float slope, float* out) {
     const int vec = (N & 3) == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0;      // whole, aligned float4s along n
-    hipLaunchKernelGGL((vn_point_kernel<NPT, SHARE>), grid, dim3(VT_THREADS), lds, stream, x, WT, s, t, u, N, C, O, slope, vec, out);
+    hipLaunchKernelGGL((vn_point_kernel<NPT, SHARE, EPI>), grid, dim3(VT_THREADS), lds, stream, x, WT, s, t, u, N, C, O, slope, vec, out);
 }
 
 }  // namespace
@@ -440,15 +457,15 @@ extern "C" int svnet_vn_point_f32(const float* x, const float* g, const float* f
     const size_t lds = (size_t)vt_point_lds(npt, C, share);
     if (lds > 64 * 1024) {
         bool ok = true;
-        SVNET_LDS_OPTIN(ok, VT_LDS_MAX, "svnet_vn_point_f32", reinterpret_cast<const void*>(vn_point_kernel<1, false>),
-                        reinterpret_cast<const void*>(vn_point_kernel<1, true>), reinterpret_cast<const void*>(vn_point_kernel<2, false>),
-                        reinterpret_cast<const void*>(vn_point_kernel<2, true>), reinterpret_cast<const void*>(vn_point_kernel<4, false>),
-                        reinterpret_cast<const void*>(vn_point_kernel<4, true>));
+        SVNET_LDS_OPTIN(ok, VT_LDS_MAX, "svnet_vn_point_f32", reinterpret_cast<const void*>(vn_point_kernel<1, false, VtLeaky>),
+                        reinterpret_cast<const void*>(vn_point_kernel<1, true, VtLeaky>), reinterpret_cast<const void*>(vn_point_kernel<2, false, VtLeaky>),
+                        reinterpret_cast<const void*>(vn_point_kernel<2, true, VtLeaky>), reinterpret_cast<const void*>(vn_point_kernel<4, false, VtLeaky>),
+                        reinterpret_cast<const void*>(vn_point_kernel<4, true, VtLeaky>));
         if (!ok) return SVNET_E_LAUNCH;
     }
     const dim3 grid((unsigned)svnet_cdiv(N, 16 * npt), (unsigned)B);
     const hipStream_t st = (hipStream_t)stream;
-#define VT_POINT(NPT, SHARE) vt_launch_point<NPT, SHARE>(grid, lds, st, x, folded, s, s + O, u, (int)N, (int)C, (int)O, slope, out)
+#define VT_POINT(NPT, SHARE) vt_launch_point<NPT, SHARE, VtLeaky>(grid, lds, st, x, folded, s, s + O, u, (int)N, (int)C, (int)O, slope, out)
     if (share) {
         if (npt == 4) VT_POINT(4, true);
         else if (npt == 2) VT_POINT(2, true);
@@ -459,6 +476,46 @@ extern "C" int svnet_vn_point_f32(const float* x, const float* g, const float* f
         else VT_POINT(1, false);
     }
 #undef VT_POINT
+    SVNET_CHECK_LAUNCH("vn_point_kernel");
+    return SVNET_OK;
+}
+
+extern "C" int svnet_vn_point_norm_supported(int64_t N, int64_t C, int64_t O) { return vt_point_ok(N, C, 0, O, O) ? 1 : 0; }
+
+extern "C" int svnet_vn_point_norm_fold_f32(const float* w_feat, const float* gamma, const float* beta, const float* running_mean, const float* running_var,
+                                            int64_t C, int64_t O, float eps, float* folded, void* stream) {
+    SVNET_REQUIRE(w_feat && gamma && beta && running_mean && running_var && folded, SVNET_E_ARG,
+                  "svnet_vn_point_norm_fold_f32: null w_feat / gamma / beta / running_mean / running_var / folded");
+    SVNET_REQUIRE(vt_point_ok(1, C, 0, O, O), SVNET_E_UNSUPPORTED, "svnet_vn_point_norm_fold_f32: C %lld, O %lld: needs 1 <= C <= %d, 1 <= O <= %d", (long long)C,
+                  (long long)O, VT_MAX_C, VT_MAX_O);
+    const int64_t total = C * O + O;
+    hipLaunchKernelGGL(vn_point_fold_kernel, dim3((unsigned)svnet_cdiv(total, VT_THREADS)), dim3(VT_THREADS), 0, (hipStream_t)stream, w_feat, w_feat, gamma,
+                       beta, running_mean, running_var, (int)C, (int)O, 0, eps, folded);
+    SVNET_CHECK_LAUNCH("vn_point_fold_kernel");
+    return SVNET_OK;
+}
+
+extern "C" int svnet_vn_point_norm_f32(const float* x, const float* folded, int64_t B, int64_t N, int64_t C, int64_t O, float* out, void* stream) {
+    SVNET_REQUIRE(x && folded && out, SVNET_E_ARG, "svnet_vn_point_norm_f32: null x / folded / out");
+    SVNET_REQUIRE(vt_batch_ok(B), SVNET_E_ARG, "svnet_vn_point_norm_f32: B %lld must lie in 1 .. %d", (long long)B, VT_MAX_B);
+    SVNET_REQUIRE(vt_point_ok(N, C, 0, O, O), SVNET_E_UNSUPPORTED, "svnet_vn_point_norm_f32: N %lld, C %lld, O %lld: needs 1 <= N <= %d, 1 <= C <= %d, 1 <= O <= %d",
+                  (long long)N, (long long)C, (long long)O, VN_MAX_N, VT_MAX_C, VT_MAX_O);
+    const float* s = folded + C * O;
+    const int npt = vt_point_tiles(N, C, false);
+    const size_t lds = (size_t)vt_point_lds(npt, C, false);
+    if (lds > 64 * 1024) {
+        bool ok = true;
+        SVNET_LDS_OPTIN(ok, VT_LDS_MAX, "svnet_vn_point_norm_f32", reinterpret_cast<const void*>(vn_point_kernel<1, false, VtNormOnly>),
+                        reinterpret_cast<const void*>(vn_point_kernel<2, false, VtNormOnly>), reinterpret_cast<const void*>(vn_point_kernel<4, false, VtNormOnly>));
+        if (!ok) return SVNET_E_LAUNCH;
+    }
+    const dim3 grid((unsigned)svnet_cdiv(N, 16 * npt), (unsigned)B);
+    const hipStream_t st = (hipStream_t)stream;
+#define VT_NORM(NPT) vt_launch_point<NPT, false, VtNormOnly>(grid, lds, st, x, folded, s, s + O, nullptr, (int)N, (int)C, (int)O, 0.f, out)
+    if (npt == 4) VT_NORM(4);
+    else if (npt == 2) VT_NORM(2);
+    else VT_NORM(1);
+#undef VT_NORM
     SVNET_CHECK_LAUNCH("vn_point_kernel");
     return SVNET_OK;
 }

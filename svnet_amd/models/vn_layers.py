@@ -2,19 +2,18 @@
 
 Drop-in for the reference module `models/vn_layers.py` (same class names, constructor arguments, defaults and state_dict keys, so a
 reference checkpoint loads with strict=True): EPS :14, VNLinear :16, VNLeakyReLU :29, VNLinearLeakyReLU :50, VNBatchNorm :111,
-VNMaxPool :134, mean_pool :151, VNStdFeature :155.  Features are channel-first, [B, C, 3, N] or [B, C, 3, N, k]: C vector channels
+VNMaxPool :134, mean_pool :151, VNStdFeature :155, STNkd :204.  Features are channel-first, [B, C, 3, N] or [B, C, 3, N, k]: C vector channels
 of three components each.  Everything here is plain torch, train and eval, on any device; the fused eval-mode form of an edge
 level (VNLinearLeakyReLU on an edge feature, then the mean over k) is svnet_amd/vn_fused.py.
 
-Not here: VNLinearAndLeakyReLU (the reference's cannot be constructed: its __init__ names another class in super()) and STNkd (the
-PointNet VN models are not part of this package).
+Not here: VNLinearAndLeakyReLU (the reference's cannot be constructed: its __init__ names another class in super()).
 """
 import torch
 import torch.nn as nn
 
 EPS = 1e-6
 
-__all__ = ["EPS", "VNLinear", "VNLeakyReLU", "VNLinearLeakyReLU", "VNBatchNorm", "VNMaxPool", "mean_pool", "VNStdFeature"]
+__all__ = ["EPS", "VNLinear", "VNLeakyReLU", "VNLinearLeakyReLU", "VNBatchNorm", "VNMaxPool", "mean_pool", "VNStdFeature", "STNkd"]
 
 
 def _channels_last(linear, x):
@@ -128,3 +127,34 @@ class VNStdFeature(nn.Module):
         frame = rows.transpose(1, 2)                                                   # [B, 3 components, 3 vectors, N, ...]
         # per point, every channel's vector in the frame's coordinates; the ellipsis stands for the N (, k) axes of any `dim`
         return torch.einsum('bij...,bjk...->bik...', x, frame), frame
+
+
+class STNkd(nn.Module):
+    """The transform net of the vector-neuron PointNet: x [B, d, 3, N] -> [B, d, 3], one equivariant vector per input channel.  Three
+    point layers, the pool over the points, two layers on the pooled feature and a VNLinear; every leaky rule with slope 0."""
+
+    def __init__(self, args, d=64):
+        super().__init__()
+        if args.pooling not in ("max", "mean"):
+            raise ValueError("STNkd: pooling must be 'max' or 'mean', got %r" % (args.pooling,))
+        self.args, self.d = args, d
+        self.conv1 = VNLinearLeakyReLU(d, 64 // 3, dim=4, negative_slope=0.0)
+        self.conv2 = VNLinearLeakyReLU(64 // 3, 128 // 3, dim=4, negative_slope=0.0)
+        self.conv3 = VNLinearLeakyReLU(128 // 3, 1024 // 3, dim=4, negative_slope=0.0)
+        self.fc1 = VNLinearLeakyReLU(1024 // 3, 512 // 3, dim=3, negative_slope=0.0)
+        self.fc2 = VNLinearLeakyReLU(512 // 3, 256 // 3, dim=3, negative_slope=0.0)
+        self.pool = VNMaxPool(1024 // 3) if args.pooling == "max" else mean_pool
+        self.fc3 = VNLinear(256 // 3, d)
+
+    def point_layers(self):
+        """The three VNLinearLeakyReLU in front of the pool, in order."""
+        return [self.conv1, self.conv2, self.conv3]
+
+    def head(self, pooled):
+        """What follows the pool: pooled [B, 341, 3] -> [B, d, 3]."""
+        return self.fc3(self.fc2(self.fc1(pooled)))
+
+    def forward(self, x):
+        for conv in self.point_layers():
+            x = conv(x)
+        return self.head(self.pool(x))

@@ -13,6 +13,8 @@ scope, as in svnet_amd/vn_fused.py: the modules stay as they are, this is an ent
 
     folded = fold_vn_point(layer, cloud_channels=0)    # a VNLinearLeakyReLU over C + Cg -> O; buffers allocated once, refresh()
     out = vn_point(x, folded, cloud=None, out=None)    # x [B,C,3,N], cloud [B,Cg,3] -> [B,O,3,N]
+    folded = fold_vn_linear_norm(linear, batchnorm)    # a VNLinear then a VNBatchNorm, no leaky rule, C -> O
+    out = vn_point_norm(x, folded, out=None)           # x [B,C,3,N] -> [B,O,3,N]
     m = vn_cloud_mean(x, out=None)                     # x [B,C,3,N] -> [B,C,3]
     h = vn_std_pool(x, y, w_lin, cloud=None, out=None) # x [B,C,3,N], y [B,Cy,3,N], w_lin [3,Cy], cloud [B,Cg,3] -> [B, 6 (C + Cg)]
     e = vn_std_coords(x, y, w_lin, out=None)           # the same coordinates per point, unpooled -> [B, 3 C, N] (VN_DGCNN_PSEG's head)
@@ -28,6 +30,8 @@ EPS = fl(1e-6); inputs are assumed finite):
     point term  per (n, a) and row r: acc = u[r,a]; for c ascending over C: acc = fmaf(x[c,a,n], W[r,c], acc).  K is never split.
                 p[o,a] are the W_f rows, d[od,a] the W_d rows.
     norm, leaky the edge level's two rules, stated in svnet_amd/vn_fused.py, on p[o,:], d[o,:], s[o] and t[o]: out[o,a,n] = y[a].
+    norm only   (vn_point_norm) the point term with u = +0 and no direction rows, then the norm rule alone: q, r, g as stated there,
+                out[o,a,n] = fl(p[a] g).  The same kernel with its epilogue exchanged; 1 <= C, O <= 512 (`supported_point_norm`).
     cloud mean  run j holds n in [64 j, min(N, 64 j + 64)); a run's sum is n-ascending plain additions from +0;
                 m = fl((the runs' sums added j-ascending from +0) / fl(N)).  The order is the contract's, not the tiling's.
     std-pool    frame rows z[k][a](n) = +0, then fmaf(y[c,a,n], w_lin[k,c], z) for c ascending over Cy; with v_i = x[i,:,n] for i < C
@@ -45,7 +49,7 @@ import torch
 from . import _call, _lib, _pointset, _vn
 
 __all__ = ["fold_vn_point", "vn_point", "vn_cloud_mean", "vn_std_pool", "vn_std_coords", "supported_point", "supported_std", "supported_coords",
-           "FoldedVNPoint", "FusedVNTail",
+           "FoldedVNPoint", "FusedVNTail", "fold_vn_linear_norm", "vn_point_norm", "supported_point_norm", "FoldedVNPointNorm",
            "MAX_C", "MAX_O", "MAX_B"]
 
 _WHAT = "the fused vector-neuron tail"   # in the messages of _pointset.check_tensors
@@ -140,6 +144,78 @@ def vn_point(x, folded, cloud=None, out=None):
     if out is None:
         out = torch.empty(B, folded.O, 3, N, dtype=_F32, device=x.device)
     _launch_point(x, cloud, folded, out, B, N)
+    return out
+
+
+def supported_point_norm(N, C, O):
+    """Whether the norm-only point kernel takes this layer (module docstring, limits)."""
+    return bool(_lib.lib().svnet_vn_point_norm_supported(int(N), int(C), int(O)))
+
+
+class FoldedVNPointNorm(_vn.Folded):
+    """The folded form of a VNLinear over C -> O vector channels followed by a VNBatchNorm, with no leaky rule: WT [C, O] | s [O] | t [O]
+    in one buffer on the layer's device, allocated once.  refresh() and release() as _vn.Folded's; there is no workspace."""
+    NAME, ENTRY = "fold_vn_linear_norm", "svnet_vn_point_norm_fold_f32"
+
+    def __init__(self, linear, batchnorm):
+        from .models.vn_layers import VNBatchNorm, VNLinear
+        if not isinstance(linear, VNLinear) or not isinstance(batchnorm, VNBatchNorm):
+            raise TypeError("%s: needs a VNLinear and a VNBatchNorm, got %s and %s" % (self.NAME, type(linear).__name__, type(batchnorm).__name__))
+        w, bn = linear.map_to_feat.weight, batchnorm.bn
+        if int(bn.num_features) != w.shape[0]:
+            raise ValueError("%s: map_to_feat %s, BatchNorm over %d: the widths differ" % (self.NAME, tuple(w.shape), bn.num_features))
+        if bn.running_mean is None or bn.running_var is None or bn.weight is None or bn.bias is None:
+            raise ValueError("%s: the BatchNorm must be affine and track running statistics" % self.NAME)
+        for k, t in {"map_to_feat.weight": w, "bn.weight": bn.weight, "bn.bias": bn.bias, "running_mean": bn.running_mean,
+                     "running_var": bn.running_var}.items():
+            if t.dtype != _F32 or not t.is_contiguous() or t.device != w.device:
+                raise ValueError("%s: %s must be contiguous float32 on %s" % (self.NAME, k, w.device))
+        self.place(linear)
+        self.batchnorm = batchnorm
+        self.dims = self.C, self.O = int(w.shape[1]), int(w.shape[0])
+        if not supported_point_norm(1, self.C, self.O):
+            raise _lib.SvnetHipError("%s: C = %d, O = %d is not supported (1 <= C <= %d, 1 <= O <= %d)" % (self.NAME, self.C, self.O, MAX_C, MAX_O))
+        self.allocate(self.C * self.O + 2 * self.O)
+
+    def refresh(self):
+        w, bn = self.layer.map_to_feat.weight, self.batchnorm.bn
+        if w.device != self.device:
+            raise ValueError("%s: the layer moved from %s to %s - fold it again" % (self.NAME, self.device, w.device))
+        with torch.cuda.device(self.device):
+            _lib.call(self.ENTRY, _call.p(w.detach()), _call.p(bn.weight.detach()), _call.p(bn.bias.detach()), _call.p(bn.running_mean),
+                      _call.p(bn.running_var), *self.dims, float(bn.eps), _call.p(self.folded), _call.stream())
+        return self
+
+
+def fold_vn_linear_norm(linear, batchnorm):
+    """A VNLinear and the VNBatchNorm that follows it, on a HIP device -> FoldedVNPointNorm."""
+    return FoldedVNPointNorm(linear, batchnorm)
+
+
+def vn_point_norm(x, folded, out=None):
+    """x [B,C,3,N] float32, folded a FoldedVNPointNorm over C -> O -> out [B,O,3,N]: the eval-mode forward of the VNBatchNorm on the
+    VNLinear's output (module docstring, norm only).  One launch on the current stream, no host read.  No argument may require grad."""
+    name = "vn_point_norm"
+    if not isinstance(folded, FoldedVNPointNorm):
+        raise TypeError("%s: folded must be a FoldedVNPointNorm (vn_tail.fold_vn_linear_norm), got %s" % (name, type(folded).__name__))
+    _check(name, {"x": x, "out": out})
+    if x.dim() != 4 or x.shape[2] != 3 or x.shape[0] < 1:
+        raise ValueError("%s: x must be [B,C,3,N], got %s" % (name, tuple(x.shape)))
+    B, C, _, N = (int(v) for v in x.shape)
+    if C != folded.C:
+        raise ValueError("%s: the layer takes %d vector channels per point, x has %d" % (name, folded.C, C))
+    if out is not None and tuple(out.shape) != (B, folded.O, 3, N):
+        raise ValueError("%s: out must be [B,O,3,N] = %s, got %s" % (name, (B, folded.O, 3, N), tuple(out.shape)))
+    _call.hip(x, out)
+    if folded.device != x.device:
+        raise ValueError("%s: the layer is on %s, x on %s" % (name, folded.device, x.device))
+    if B > MAX_B or not supported_point_norm(N, C, folded.O):
+        raise _lib.SvnetHipError("%s: B = %d, N = %d, C = %d, O = %d is not supported (B <= %d, 1 <= N <= %d, C <= %d, O <= %d)"
+                                 % (name, B, N, C, folded.O, MAX_B, _pointset.MAX_N, MAX_C, MAX_O))
+    if out is None:
+        out = torch.empty(B, folded.O, 3, N, dtype=_F32, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.call("svnet_vn_point_norm_f32", _call.p(x), _call.p(folded.folded), B, N, C, folded.O, _call.p(out), _call.stream())
     return out
 
 
