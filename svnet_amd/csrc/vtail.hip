@@ -119,10 +119,14 @@ __device__ __forceinline__ void vt_point(const float (&a)[3][CPL], const VtChan<
                                          float (&z)[3][J], int lane, float* nv_out = nullptr) {
 #pragma unroll
     for (int t = 0; t < CPL; ++t) {
-        const float nv = sqrtf(a[0][t] * a[0][t] + a[1][t] * a[1][t] + a[2][t] * a[2][t]);
+        // (the contraction spelled out: left to the compiler, the two inlined copies of a kernel's point body got DIFFERENT ones - the first
+        //  this chain, the second a packed multiply of two squares + one fma + a plain add - so one point's norm, and with it every scalar
+        //  of the point, depended by an ulp on which of a wave's two slots took it, and an exact tie between a row and its copy went to
+        //  whichever slot had rounded up instead of to the first row: tests/test_hip_kernel_tiers.py test_vtail_exact_ties_take_the_first_row)
+        const float nv = sqrtf(fmaf(a[2][t], a[2][t], fmaf(a[0][t], a[0][t], a[1][t] * a[1][t])));
         if (nv_out) nv_out[t] = nv;
         n[t] = nv + VT_VEPS;
-        rr[t] = (n[t] - ch.mu[t]) * ch.is[t] * ch.ga[t] + ch.be[t];
+        rr[t] = fmaf((n[t] - ch.mu[t]) * ch.is[t], ch.ga[t], ch.be[t]);
         const float q = rr[t] / n[t] * ch.gt[t];        // (no branch around the division: a dead channel reads channel 0, n > 0, gate 0)
 #pragma unroll
         for (int i = 0; i < 3; ++i) x[i][t] = a[i][t] * q;
@@ -174,7 +178,9 @@ __global__ __launch_bounds__(256) void vtail_fwd_kernel(const float* __restrict_
         for (int t = 0; t < CPL; ++t)
 #pragma unroll
             for (int j = 0; j < J; ++j) {
-                const float sv = x[0][t] * z[0][j] + x[1][t] * z[1][j] + x[2][t] * z[2][j];
+                // (spelled out like the norm in vt_point, and for the same reason: the second copy of this body held its x pair the other
+                //  way round in a packed register, and the compiler's contraction rounded x1 * z1 first in one copy, x0 * z0 in the other)
+                const float sv = fmaf(x[2][t], z[2][j], fmaf(x[1][t], z[1][j], x[0][t] * z[0][j]));
                 sum[t][j] += live ? sv : 0.f;
                 const bool up = live && sv > best[t][j];                  // strict '>': the first index keeps a tie
                 best[t][j] = up ? sv : best[t][j];

@@ -10,6 +10,9 @@ and parameter gradient - with the textbook operation written below in float64 on
 Bounds: values that do not depend on a summation order (max, copies, subtractions, arg-max) are bit-exact; everything else goes through
 tests/common.py:compare_case at OUT_RTOL (forward values, running statistics) and GRAD_RTOL (gradients) of the tensor's max.  Each family
 has a teeth check: one element of the HIP output off by one part in 1e4 (or one arg-max moved) must fail the same comparison.
+
+The classifier's fused vector tail (csrc/vtail.hip) has a section of the same kind; its reference is the oracle's own chain in float64 on
+the HIP run's replayed, certified arg-max (tests/vtail_cases.py), because near-ties between float32 results are not a rule to pin.
 """
 import numpy as np
 import pytest
@@ -639,6 +642,187 @@ def test_binhead_tiers(M, hip_device):
     check(*run_binhead(M, hip_device), name="binhead M=%d" % M)
 
 
+# ----------------------------------------------------------------------------- vector tail (csrc/vtail.hip, _ops.GlobalMaxMeanPoolBNV)
+# vtail_fwd_kernel<CPL> / vtail_bwd_kernel<CPL, APPLY>: C <= 64 -> 1, <= 128 -> 2, <= 192 -> 3 channels per lane; grid (chunks, B) from
+# vtail_plan = split_plan(B, N, 768, 32, 8); four waves take a chunk's rows two per trip.  The cases, their inputs and the float64
+# reference (the oracle's own chain) are tests/vtail_cases.py's; tests/test_host_vtail_cases.py holds the reference alone to a quarter
+# of these bounds.  The HIP arg-max is replayed into the reference and certified (tests/decisions.py), not waved through.
+
+VTAIL_REPORT = {}
+
+
+def _vtail_record(name, worst_by_key, forced):
+    """vtail_tier_errors.txt in the report directory of tests/test_hip_train_parity.py (OUT): worst relative error per key and case, forced arg-max decisions per case (rewritten as cases run)."""
+    import os
+    from tests.test_hip_train_parity import OUT
+    VTAIL_REPORT[name] = (worst_by_key, forced)
+    os.makedirs(OUT, exist_ok=True)
+    with open(os.path.join(OUT, "vtail_tier_errors.txt"), "w") as f:
+        f.write("# vector tail against float64 (tests/test_hip_kernel_tiers.py): relative error per key (tests/common.py compare_case scaling;\n"
+                "# bounds %.0e for out / buf:, %.0e for gradients) and arg-max decisions forced in the replay, per case\n" % (OUT_RTOL, GRAD_RTOL))
+        for n in sorted(VTAIL_REPORT):
+            errs, forced_n = VTAIL_REPORT[n]
+            f.write("%s  forced_argmax=%s\n" % (n, forced_n))
+            for k in sorted(errs):
+                f.write("    %-20s %.3e\n" % (k, errs[k]))
+
+
+def vtail_hip(inp, train, dev, gate=True, binary=True, backward=True):
+    """_ops.GlobalMaxMeanPoolBNV as sv_dgcnn_cls calls it -> ({key: numpy}, the recorded arg-max [B, Ca + 3C])."""
+    from svnet_amd import _ops
+    from tests import vtail_cases as T
+    from tests.decisions import tapped
+    leaves = {k: _leaf(inp[k], dev) for k in ("y", "v", "gamma1", "beta1", "gamma2", "beta2", "Wz")}
+    gt = _leaf(inp["gate"], dev) if gate else None
+    sc = _leaf(inp["scz"], dev) if binary else None
+    stats = {k: inp[k].clone().to(dev) for k in ("rm1", "rv1", "rm2", "rv2")}
+    nbt1, nbt2 = torch.full((), 3, dtype=torch.int64, device=dev), torch.full((), 5, dtype=torch.int64, device=dev)
+    with tapped() as tap:
+        out = _ops.GlobalMaxMeanPoolBNV.apply(leaves["y"], leaves["v"], gt, leaves["gamma1"], leaves["beta1"], stats["rm1"], stats["rv1"],
+                                              leaves["gamma2"], leaves["beta2"], stats["rm2"], stats["rv2"], leaves["Wz"], sc, train, 1,
+                                              T.SLOPE, nbt1 if train else None, nbt2 if train else None)
+        torch.cuda.synchronize()
+        assert len(tap["pools"]) == 1
+        pools = tap["pools"][0].cpu().long()
+    got = {"out": _np(out)}
+    if backward:
+        out.backward(inp["gout"].to(dev))
+        torch.cuda.synchronize()
+        got.update({"dy": _np(leaves["y"].grad), "dv": _np(leaves["v"].grad), "d:Wz": _np(leaves["Wz"].grad)})
+        if gate:
+            got["dgate"] = _np(gt.grad)
+        if binary:
+            got["d:scz"] = _np(sc.grad)
+        for i in (1, 2):
+            got["d:gamma%d" % i], got["d:beta%d" % i] = _np(leaves["gamma%d" % i].grad), _np(leaves["beta%d" % i].grad)
+    for i in (1, 2):
+        got["buf:running_mean%d" % i], got["buf:running_var%d" % i] = _np(stats["rm%d" % i]), _np(stats["rv%d" % i])
+    got["buf:nbt"] = np.array([int(nbt1), int(nbt2)])
+    return got, pools
+
+
+def run_vtail(tag, train, dev, variant=None, gate=True, binary=True):
+    """(got, ref, exact, info): the HIP tail and the float64 reference on the HIP run's replayed arg-max; info["dec"] certifies the replay."""
+    from tests import vtail_cases as T
+    inp = T.inputs(T.BY_TAG[tag], variant)
+    got, pools = vtail_hip(inp, train, dev, gate, binary)
+    ref, info = T.reference(inp, F64, train, pools=pools, gate=gate, binary=binary)
+    ref["buf:nbt"] = np.array([4, 6] if train else [3, 5])
+    info["inp"], info["pools"] = inp, pools
+    return got, ref, ("buf:nbt",), info
+
+
+def _vtail_errors(got, ref):
+    from tests.common import case_errors
+    return case_errors(got, {k: v for k, v in ref.items() if k != "buf:nbt"})
+
+
+VTAIL_TAGS = ["c1_dead_lanes", "c64_last_of_1", "c65_last_of_5", "c128_last_of_12", "c129_last_of_3", "c192_widest", "one_chunk",
+              "chunk_removed", "rows128"]
+
+
+def test_vtail_case_list_is_the_tables():
+    from tests import vtail_cases as T
+    assert VTAIL_TAGS == [c[0] for c in T.CASES]
+
+
+@pytest.mark.parametrize("recompute", [True, False], ids=["apply_recomputes", "apply_reads_g5"])
+@pytest.mark.parametrize("train", [True, False], ids=["train", "eval"])
+@pytest.mark.parametrize("tag", VTAIL_TAGS)
+def test_vtail_tiers(tag, train, recompute, hip_device, monkeypatch):
+    """Every case of tests/vtail_cases.py, both forms of the backward's second pass (svnet_vtail_bwd_apply_f32 recomputing dL/dv5, and
+    svnet_vbn_bwd_apply_f32 on the copy the first pass stores): outputs, every gradient and both norms' running statistics against float64
+    on the replayed, certified arg-max; num_batches_tracked exact; a second forward on the same inputs the same bits (ordered chunk sums)."""
+    from svnet_amd import config
+    from tests import vtail_cases as T
+    monkeypatch.setattr(config, "FUSE_VTAIL_APPLY", recompute)
+    name = "%s %s %s" % (tag, "train" if train else "eval", "recompute" if recompute else "g5")
+    got, ref, exact, info = run_vtail(tag, train, hip_device)
+    errs = _vtail_errors(got, ref)
+    print("vtail %s: %s" % (name, "  ".join("%s %.2e" % kv for kv in sorted(errs.items()))))
+    summary = info["dec"].check()
+    _vtail_record(name, errs, summary["forced"])
+    assert set(ref) == set(T.KEYS) | {"buf:nbt"}
+    check(got, ref, exact, "vtail " + name)
+    again, pools = vtail_hip(info["inp"], train, hip_device, backward=False)
+    assert np.array_equal(again["out"].view(np.uint32), got["out"].view(np.uint32)) and torch.equal(pools, info["pools"])
+
+
+@pytest.mark.parametrize("form", ["no_gate", "fp_weight"])
+@pytest.mark.parametrize("tag", ["c64_last_of_1", "c129_last_of_3"])
+def test_vtail_optional_operands(tag, form, hip_device):
+    """gate = None (no dgate: the backward's `dgate == nullptr` branch) and scz = None (fp32 Wz: the svnet_slices_sum_f32 finish)."""
+    gate, binary = form != "no_gate", form != "fp_weight"
+    got, ref, exact, info = run_vtail(tag, True, hip_device, gate=gate, binary=binary)
+    assert ("dgate" in ref) == gate and ("d:scz" in ref) == binary and set(got) == set(ref)
+    summary = info["dec"].check()
+    _vtail_record("%s train %s" % (tag, form), _vtail_errors(got, ref), summary["forced"])
+    check(got, ref, exact, "vtail %s %s" % (tag, form))
+
+
+@pytest.mark.parametrize("recompute", [True, False], ids=["apply_recomputes", "apply_reads_g5"])
+def test_vtail_zero_vectors(recompute, hip_device, monkeypatch):
+    """A handful of zero vectors: the norm's gradient at 0 is 0 (torch.linalg.vector_norm; the kernel's nvv > 0 ? dn / nvv : 0), what is
+    left there is g * BN(EPS) / EPS * gate, ~1e6 times an ordinary entry.  dv is compared in TWO parts, each against its own largest
+    reference element - one bound over the whole tensor would leave every ordinary entry unchecked."""
+    from svnet_amd import config
+    from tests import vtail_cases as T
+    monkeypatch.setattr(config, "FUSE_VTAIL_APPLY", recompute)
+    got, ref, exact, info = run_vtail("c65_last_of_5", True, hip_device, variant="zeros")
+    zero = T.zero_vectors(info["inp"]["v"]).numpy()
+    assert zero.any() and np.isfinite(got["dv"]).all()
+    info["dec"].check()
+    errs = _vtail_errors({k: v for k, v in got.items() if k != "dv"}, {k: v for k, v in ref.items() if k != "dv"})
+    (got_rest, got_zero), (ref_rest, ref_zero) = T.split_dv(got, zero), T.split_dv(ref, zero)
+    errs["dv (zero vectors)"], errs["dv (the rest)"] = _vtail_errors(got_zero, ref_zero)["dv"], _vtail_errors(got_rest, ref_rest)["dv"]
+    print("vtail zero vectors: |dv|max %.3e at the zero vectors, %.3e elsewhere; %s" % (
+        np.abs(ref_zero["dv"]).max(), np.abs(ref_rest["dv"]).max(), "  ".join("%s %.2e" % kv for kv in sorted(errs.items()))))
+    _vtail_record("c65_last_of_5 train zeros %s" % ("recompute" if recompute else "g5"), errs, info["dec"].check()["forced"])
+    check({k: v for k, v in got.items() if k != "dv"}, {k: v for k, v in ref.items() if k != "dv"}, exact, "vtail zeros")
+    check(got_zero, ref_zero, (), "vtail zeros, dv at the zero vectors")
+    check(got_rest, ref_rest, (), "vtail zeros, dv elsewhere")
+
+
+def test_vtail_exact_ties_take_the_first_row(hip_device):
+    """One point in rows 31, 32 (either side of the first chunk boundary) and 256 (the one-row last chunk) of every cloud, scaled by 4:
+    wherever the float64 maximum of a vector column is at one of the copies, the HIP arg-max is the FIRST of them - within a wave the
+    strict '>', across waves and chunks the key's lower row."""
+    from tests import vtail_cases as T
+    tag, B, N, C, _ = T.BY_TAG["c64_last_of_1"]
+    inp = T.inputs(T.BY_TAG[tag], "ties")
+    got, pools = vtail_hip(inp, True, hip_device, backward=False)
+    _, info = T.reference(inp, F64, True)
+    own = info["f"].argmax(dim=1)[:, T.CA:]
+    at_copy = sum(own == r for r in T.TIE_ROWS).bool()
+    assert int(at_copy.sum()) >= 3 * C // 4
+    hip = pools[:, T.CA:][at_copy]
+    assert bool((hip == T.TIE_ROWS[0]).all()), "arg-max rows at the tied columns: %r" % (sorted(set(hip.tolist())),)
+
+
+def test_vtail_refusals(hip_device):
+    from svnet_amd import _ops, _lib
+    from tests import vtail_cases as T
+    assert not _ops.GlobalMaxMeanPoolBNV.supported(2, 255, 5, 64) and not _ops.GlobalMaxMeanPoolBNV.supported(2, 256, 5, 193)
+    assert _ops.GlobalMaxMeanPoolBNV.supported(2, 256, 5, 192)
+    inp = T.inputs(("refused", 2, 256, 193, None))
+    with pytest.raises(_lib.SvnetHipError, match=r"C=193 > 192"):
+        vtail_hip(inp, True, hip_device, backward=False)
+    torch.cuda.synchronize()
+
+
+def test_vtail_replay_has_teeth(hip_device):
+    """One replayed arg-max moved to the row of its column's SMALLEST value: Decisions.check() must refuse the replay."""
+    from tests import vtail_cases as T
+    got, ref, exact, info = run_vtail("c65_last_of_5", True, hip_device)
+    info["dec"].check()
+    bad = info["pools"].clone()
+    col = T.CA + 7
+    bad[1, col] = int(info["f"][1, :, col].argmin())
+    _, bad_info = T.reference(info["inp"], F64, True, pools=bad)
+    with pytest.raises(AssertionError, match="decision replay"):
+        bad_info["dec"].check()
+
+
 # ----------------------------------------------------------------------------- teeth
 
 TEETH = {
@@ -659,6 +843,7 @@ TEETH = {
     "gate_rows": lambda dev: run_gate(33, 256, 1021, dev),
     "act": lambda dev: run_act(257, 2, dev),
     "binhead": lambda dev: run_binhead(33, dev),
+    "vtail": lambda dev: run_vtail("c129_last_of_3", True, dev)[:3],
 }
 
 
