@@ -47,7 +47,6 @@ __all__ = ["fold_vn_layer", "vn_edge_mean", "vn_edge2_mean", "supported", "suppo
 
 _WHAT = "the fused vector-neuron edge level"   # in the messages of _pointset.check_tensors
 MAX_K, MAX_C, MAX_O = 64, 128, 128
-_F32 = torch.float32
 
 
 def supported(N, k, C, O, Od):
@@ -96,32 +95,14 @@ def vn_edge_mean(x, idx, folded, out=None):
     the layer's eval-mode forward on [x_j - x_i | x_i] (module docstring).  Two launches on the current stream, no host read.  Entries
     of idx outside 0 .. N-1 are clamped into the cloud.  No argument may require grad."""
     name = "vn_edge_mean"
-    if not isinstance(folded, FoldedVNLayer):
-        raise TypeError("%s: folded must be a FoldedVNLayer (vn_fused.fold_vn_layer), got %s" % (name, type(folded).__name__))
-    args = {"x": x, "idx": idx}
-    dtypes = [_F32, torch.int64]
-    if out is not None:
-        args["out"] = out
-        dtypes.append(_F32)
-    _pointset.check_tensors(name, args, dtypes, _WHAT)
-    if x.dim() != 4 or x.shape[2] != 3 or x.shape[0] < 1:
-        raise ValueError("%s: x must be [B,C,3,N], got %s" % (name, tuple(x.shape)))
-    B, C, _, N = (int(v) for v in x.shape)
-    if idx.dim() != 3 or idx.shape[0] != B or idx.shape[1] != N:
-        raise ValueError("%s: idx must be [B,N,k] with B = %d, N = %d, got %s" % (name, B, N, tuple(idx.shape)))
-    k = int(idx.shape[2])
-    if C != folded.C:
-        raise ValueError("%s: the layer takes %d vector channels, x has %d" % (name, folded.C, C))
-    if out is not None and tuple(out.shape) != (B, folded.O, 3, N):
-        raise ValueError("%s: out must be [B,O,3,N] = %s, got %s" % (name, (B, folded.O, 3, N), tuple(out.shape)))
-    _call.hip(x, idx, out)
-    if folded.device != x.device:
-        raise ValueError("%s: the layer is on %s, x on %s" % (name, folded.device, x.device))
+    B, C, N, k = _vn.check_entry(name, _WHAT, {"x": x, "idx": idx, "out": out}, ("out",), folded, FoldedVNLayer, "vn_fused.fold_vn_layer")
+    shape = (B, folded.O, 3, N)
+    _vn.check_out(name, out, shape, "[B,O,3,N]", (x, idx, out), folded)
     if not supported(N, k, C, folded.O, folded.Od):
         raise _lib.SvnetHipError("%s: N = %d, k = %d, C = %d, O = %d is not supported (1 <= k <= %d, k <= N <= %d, C <= %d, O <= %d)"
                                  % (name, N, k, C, folded.O, MAX_K, _pointset.MAX_N, MAX_C, MAX_O))
     if out is None:
-        out = torch.empty(B, folded.O, 3, N, dtype=_F32, device=x.device)
+        out = torch.empty(*shape, dtype=torch.float32, device=x.device)
     _launch(x, idx, folded, out, B, N, k)
     return out
 
@@ -158,37 +139,21 @@ def vn_edge2_mean(x, idx, folded1, folded2, out=None):
     argument may require grad.  tests/vn_pseg_ref.py restates the contract; results are compared with it as bit patterns."""
     from .vn_tail import FoldedVNPoint
     name = "vn_edge2_mean"
-    if not isinstance(folded1, FoldedVNLayer):
-        raise TypeError("%s: folded1 must be a FoldedVNLayer (vn_fused.fold_vn_layer), got %s" % (name, type(folded1).__name__))
-    if not isinstance(folded2, FoldedVNPoint):
-        raise TypeError("%s: folded2 must be a FoldedVNPoint (vn_tail.fold_vn_point), got %s" % (name, type(folded2).__name__))
-    args = {"x": x, "idx": idx}
-    dtypes = [_F32, torch.int64]
-    if out is not None:
-        args["out"] = out
-        dtypes.append(_F32)
-    _pointset.check_tensors(name, args, dtypes, _WHAT)
-    if x.dim() != 4 or x.shape[2] != 3 or x.shape[0] < 1:
-        raise ValueError("%s: x must be [B,C,3,N], got %s" % (name, tuple(x.shape)))
-    B, C, _, N = (int(v) for v in x.shape)
-    if idx.dim() != 3 or idx.shape[0] != B or idx.shape[1] != N:
-        raise ValueError("%s: idx must be [B,N,k] with B = %d, N = %d, got %s" % (name, B, N, tuple(idx.shape)))
-    k = int(idx.shape[2])
-    if C != folded1.C:
-        raise ValueError("%s: the first layer takes %d vector channels, x has %d" % (name, folded1.C, C))
+    _vn.check_is(name, "folded1", folded1, FoldedVNLayer, "vn_fused.fold_vn_layer")
+    _vn.check_is(name, "folded2", folded2, FoldedVNPoint, "vn_tail.fold_vn_point")
+    B, C, N, k = _vn.check_entry(name, _WHAT, {"x": x, "idx": idx, "out": out}, folded=folded1, layer="the first layer")
     if folded2.Cg != 0 or folded2.C != folded1.O:
         raise ValueError("%s: the second layer must take the first one's %d channels and no constant ones, it takes %d + %d"
                          % (name, folded1.O, folded2.C, folded2.Cg))
-    if out is not None and tuple(out.shape) != (B, folded2.O, 3, N):
-        raise ValueError("%s: out must be [B,O2,3,N] = %s, got %s" % (name, (B, folded2.O, 3, N), tuple(out.shape)))
-    _call.hip(x, idx, out)
+    shape = (B, folded2.O, 3, N)
+    _vn.check_out(name, out, shape, "[B,O2,3,N]", (x, idx, out))
     if folded1.device != x.device or folded2.device != x.device:
         raise ValueError("%s: the layers are on %s and %s, x on %s" % (name, folded1.device, folded2.device, x.device))
     if not supported2(N, k, C, folded1.O, folded1.Od, folded2.O, folded2.Od):
         raise _lib.SvnetHipError("%s: N = %d, k = %d, C = %d, O1 = %d, O2 = %d is not supported (1 <= k <= %d, k <= N <= %d, C <= %d, O1, O2 <= %d)"
                                  % (name, N, k, C, folded1.O, folded2.O, MAX_K, _pointset.MAX_N, MAX_C, MAX_O))
     if out is None:
-        out = torch.empty(B, folded2.O, 3, N, dtype=_F32, device=x.device)
+        out = torch.empty(*shape, dtype=torch.float32, device=x.device)
     _launch2(x, idx, folded1, folded2, out, B, N, k)
     return out
 
@@ -216,19 +181,8 @@ class FusedVNDGCNN(_vn.EvalOnly):
             from .vn_tail import FusedVNTail
             self.__dict__["tail"] = FusedVNTail(model)
 
-    def refresh(self):
-        for level in self.levels:
-            level.refresh()
-        if self.tail is not None:
-            self.tail.refresh()
-        return self
-
-    def release(self):
-        for level in self.levels:
-            level.release()
-        if self.tail is not None:
-            self.tail.release()
-        return self
+    def _folded(self):
+        return self.levels + ([] if self.tail is None else [self.tail])
 
     def supported(self, N, k):
         """Whether clouds of N points with k neighbours take the fused path here; else forward runs the model."""
@@ -236,35 +190,10 @@ class FusedVNDGCNN(_vn.EvalOnly):
 
     @torch.no_grad()
     def forward(self, x, idx=None):
-        name = "FusedVNDGCNN"
-        self.eval_only()
-        if isinstance(x, torch.Tensor) and x.requires_grad:      # (asked of the argument itself: under no_grad a contiguous copy takes no gradient)
-            raise ValueError("%s: x requires grad - %s is forward only in x" % (name, _WHAT))
-        _pointset.check_tensors(name, {"x": x.contiguous() if isinstance(x, torch.Tensor) else x}, [_F32], _WHAT)      # (a view is taken, as the model takes it)
-        if x.dim() != 3 or x.shape[1] != 3 or x.shape[0] < 1:
-            raise ValueError("%s: x must be [B,3,N], got %s" % (name, tuple(x.shape)))
-        if idx is not None and (len(idx) != 4 or any(not isinstance(i, torch.Tensor) or i.dtype != torch.int64 or i.dim() != 3
-                                                     or i.shape[:2] != (x.shape[0], x.shape[2]) for i in idx)):
-            raise ValueError("%s: idx must hold the four levels' neighbour lists [B,N,k] int64" % name)
-        for n, i in enumerate(idx or ()):
-            if i.device != x.device:
-                raise ValueError("%s: x on %s, idx[%d] on %s" % (name, x.device, n, i.device))
-        _call.hip(x, *(idx or ()))
-        B, _, N = (int(v) for v in x.shape)
-        ks = [self.model.k] * 4 if idx is None else [int(i.shape[2]) for i in idx]
+        name = self._begin(_WHAT, x)
+        B, N, ks = self._lists(name, x, idx, 4)
         if not all(self.supported(N, k) for k in ks):
             return self.model(x, idx=idx)
-        if self.levels[0].device != x.device:
-            raise ValueError("%s: the model is on %s, x on %s" % (name, self.levels[0].device, x.device))
-        from .models.utils.vn_util import knn
-        h = x.contiguous().view(B, 1, 3, N)
-        feats, used = [], []
-        for i, level in enumerate(self.levels):
-            nbr = knn(h.view(B, -1, N), ks[i]) if idx is None else idx[i].contiguous()
-            out = torch.empty(B, level.O, 3, N, dtype=_F32, device=x.device)
-            _launch(h, nbr, level, out, B, N, ks[i])
-            used.append(nbr)
-            feats.append(out)
-            h = out
-        self.last_idx = used
+        _vn.check_model_device(name, self.levels[0], "x", x)
+        feats = self._edge_levels(x, idx, ks, [(level, level.O) for level in self.levels], _launch)
         return self.model.tail(feats) if self.tail is None else self.tail(feats)

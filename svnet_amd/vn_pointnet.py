@@ -38,7 +38,6 @@ __all__ = ["fold_vn_cross", "vn_edge_cross_mean", "supported_cross", "FoldedVNCr
 
 _WHAT = "the fused vector-neuron position level"   # in the messages of _pointset.check_tensors
 MAX_K, MAX_O, MAX_B = 64, 128, 65535
-_F32 = torch.float32
 
 
 def supported_cross(N, k, O, Od):
@@ -79,30 +78,15 @@ def vn_edge_cross_mean(x, idx, folded, out=None):
     layer's eval-mode forward on [x_j - x_i | x_i | x_j x x_i] (module docstring).  One launch on the current stream, no host read, no
     workspace.  Entries of idx outside 0 .. N-1 are clamped into the cloud.  No argument may require grad."""
     name = "vn_edge_cross_mean"
-    if not isinstance(folded, FoldedVNCross):
-        raise TypeError("%s: folded must be a FoldedVNCross (vn_pointnet.fold_vn_cross), got %s" % (name, type(folded).__name__))
-    args = {"x": x, "idx": idx}
-    dtypes = [_F32, torch.int64]
-    if out is not None:
-        args["out"] = out
-        dtypes.append(_F32)
-    _pointset.check_tensors(name, args, dtypes, _WHAT)
-    if x.dim() != 4 or x.shape[1] != 1 or x.shape[2] != 3 or x.shape[0] < 1:
-        raise ValueError("%s: x must be [B,1,3,N], got %s" % (name, tuple(x.shape)))
-    B, _, _, N = (int(v) for v in x.shape)
-    if idx.dim() != 3 or idx.shape[0] != B or idx.shape[1] != N:
-        raise ValueError("%s: idx must be [B,N,k] with B = %d, N = %d, got %s" % (name, B, N, tuple(idx.shape)))
-    k = int(idx.shape[2])
-    if out is not None and tuple(out.shape) != (B, folded.O, 3, N):
-        raise ValueError("%s: out must be [B,O,3,N] = %s, got %s" % (name, (B, folded.O, 3, N), tuple(out.shape)))
-    _call.hip(x, idx, out)
-    if folded.device != x.device:
-        raise ValueError("%s: the layer is on %s, x on %s" % (name, folded.device, x.device))
+    B, _, N, k = _vn.check_entry(name, _WHAT, {"x": x, "idx": idx, "out": out}, folded=folded, cls=FoldedVNCross, maker="vn_pointnet.fold_vn_cross",
+                                 channels=1)
+    shape = (B, folded.O, 3, N)
+    _vn.check_out(name, out, shape, "[B,O,3,N]", (x, idx, out), folded)
     if B > MAX_B or not supported_cross(N, k, folded.O, folded.Od):
         raise _lib.SvnetHipError("%s: B = %d, N = %d, k = %d, O = %d is not supported (B <= %d, 1 <= k <= %d, k <= N <= %d, O <= %d)"
                                  % (name, B, N, k, folded.O, MAX_B, MAX_K, _pointset.MAX_N, MAX_O))
     if out is None:
-        out = torch.empty(B, folded.O, 3, N, dtype=_F32, device=x.device)
+        out = torch.empty(*shape, dtype=torch.float32, device=x.device)
     _launch_cross(x, idx, folded, out, B, N, k)
     return out
 
@@ -119,9 +103,9 @@ class FusedVNPointNet(_vn.EvalOnly):
         5.    x2 = vn_point(x1, conv2, cloud=g): conv2 folded with its last 21 input channels constant over a cloud, so
               cat((x, x_global)) is never built;
         6.    local = vn_point_norm(x2, conv3 + bn3) [B,341,3,N];
-        7.    as FusedVNTail: m = vn_cloud_mean(local); y = vn_point(vn_point(local, vn1, cloud=m), vn2);
-              h = vn_std_pool(local, y, w_lin, cloud=m)[:, :2046], the amax half.  The entry also computes the mean half, which this
-              model does not read: known waste (DESIGN.md 4.30);
+        7.    vn_tail.std_tail(local, vn1, vn2, w_lin), as FusedVNTail runs it: the cloud mean m, vn1 with cloud = m, vn2, and
+              vn_std_pool in the frame of vn2's output.  Of its h [B,4092] the model reads [:, :2046], the amax half; the entry also
+              computes the mean half: known waste (DESIGN.md 4.30);
         8.    the head (fc1 / bn1, fc2 / dropout / bn2, fc3) through the model's layers.
 
     The layers are folded at construction; refresh() folds them again after the parameters or the running statistics changed;
@@ -155,18 +139,6 @@ class FusedVNPointNet(_vn.EvalOnly):
     def _folded(self):
         return ([self.cross, self.norm] if self.fused else []) + list(self.points.values())
 
-    def refresh(self):
-        for f in self._folded():
-            f.refresh()
-        return self
-
-    def release(self):
-        for f in self._folded():
-            f.release()
-        if self._std_ws is not None:
-            self._std_ws.release()
-        return self
-
     def supported(self, B, N, k):
         """Whether B clouds of N points with k neighbours take the fused path here; else forward runs the model."""
         if not self.fused or not 1 <= B <= MAX_B:
@@ -198,32 +170,22 @@ class FusedVNPointNet(_vn.EvalOnly):
         st["fstn"] = g = enc.fstn.head(_vt.vn_cloud_mean(t)).contiguous()
         st["conv2"] = _vt.vn_point(x1, P["conv2"], cloud=g)
         st["local"] = local = _vt.vn_point_norm(st["conv2"], self.norm)
-        m = _vt.vn_cloud_mean(local)
-        y = _vt.vn_point(_vt.vn_point(local, P["vn1"], cloud=m), P["vn2"])
-        h = _vt.vn_std_pool(local, y, enc.std_feature.vn_lin.weight.detach(), cloud=m, workspace=self._std_ws)
+        h = _vt.std_tail(local, P["vn1"], P["vn2"], enc.std_feature.vn_lin.weight.detach(), self._std_ws)[2]
         return h[:, :6 * self.norm.O], st
 
     @torch.no_grad()
     def forward(self, x, idx=None):
-        name = "FusedVNPointNet"
-        self.eval_only()
-        if isinstance(x, torch.Tensor) and x.requires_grad:      # (asked of the argument itself, as FusedVNDGCNN does)
-            raise ValueError("%s: x requires grad - %s is forward only in x" % (name, _WHAT))
-        _pointset.check_tensors(name, {"x": x.contiguous() if isinstance(x, torch.Tensor) else x}, [_F32], _WHAT)
-        if x.dim() != 3 or x.shape[1] != 3 or x.shape[0] < 1:
-            raise ValueError("%s: x must be [B,3,N], got %s" % (name, tuple(x.shape)))
-        if idx is not None and (not isinstance(idx, torch.Tensor) or idx.dtype != torch.int64 or idx.dim() != 3
-                                or tuple(idx.shape[:2]) != (x.shape[0], x.shape[2])):
+        name = self._begin(_WHAT, x)
+        B, N = int(x.shape[0]), int(x.shape[2])
+        if idx is not None and not self.is_list(idx, B, N):
             raise ValueError("%s: idx must be the position level's neighbour list [B,N,k] int64" % name)
         if idx is not None and idx.device != x.device:
             raise ValueError("%s: x on %s, idx on %s" % (name, x.device, idx.device))
         _call.hip(x, idx)
-        B, _, N = (int(v) for v in x.shape)
         k = self.model.k if idx is None else int(idx.shape[2])
         if not self.supported(B, N, k):
             return self.model(x, idx=idx)
-        if self.cross.device != x.device:
-            raise ValueError("%s: the model is on %s, x on %s" % (name, self.cross.device, x.device))
+        _vn.check_model_device(name, self.cross, "x", x)
         from .models.utils.vn_util import knn
         x = x.contiguous()
         nbr = knn(x, k) if idx is None else idx.contiguous()

@@ -17,14 +17,13 @@ pooling = 'max'.
 """
 import torch
 
-from . import _call, _lib, _pointset, _vn
+from . import _vn
 from . import vn_fused as _vf
 from . import vn_tail as _vt
 
 __all__ = ["FusedVNDGCNNPSeg"]
 
 _WHAT = "the fused vector-neuron part-segmentation forward"
-_F32 = torch.float32
 
 
 class FusedVNDGCNNPSeg(_vn.EvalOnly):
@@ -35,9 +34,10 @@ class FusedVNDGCNNPSeg(_vn.EvalOnly):
         1-3.  per level knn (or the given list), then the tables of its first layer and the edge pass: vn_edge2_mean for (conv1, conv2)
               and (conv3, conv4), vn_edge_mean for conv5 -> x1, x2, x3 [B,21,3,N];
         4.    x123 = cat(x1, x2, x3) (the edge entries have no channel window to write into one buffer);
-        5-7.  local = vn_point(x123, conv6); m = vn_cloud_mean(local); y = vn_point(vn_point(local, vn1, cloud=m), vn2);
-        8.    h = vn_std_pool(local, y, w_lin, cloud=m)[:, :3 * 682]: the amax half.  The entry also computes the mean half, which this
-              model does not read: a known small cost (the sums ride on the loop that finds the maxima);
+        5.    local = vn_point(x123, conv6);
+        6-8.  vn_tail.std_tail(local, vn1, vn2, w_lin): the cloud mean m, vn1 with cloud = m, vn2 -> y, and vn_std_pool in y's frame.
+              Of its h the model reads [:, :3 * 682], the amax half; the entry also computes the mean half: a known small cost (the
+              sums ride on the loop that finds the maxima);
         9.    e123 = vn_std_coords(x123, y, w_lin) [B,189,N];
         10.   the head in torch without the [B,2299,N] tensor (module docstring), then bn8, the leaky rule and conv9 .. conv11 through
               the model's own modules.
@@ -74,17 +74,9 @@ class FusedVNDGCNNPSeg(_vn.EvalOnly):
         self._w8 = (w[:, :const].contiguous(), w[:, const:].contiguous())
 
     def refresh(self):
-        for f in self._folded():
-            f.refresh()
+        super().refresh()
         if self.fused:
             self._split_head()
-        return self
-
-    def release(self):
-        for f in self._folded():
-            f.release()
-        if self._std_ws is not None:
-            self._std_ws.release()
         return self
 
     def _folded(self):
@@ -106,53 +98,30 @@ class FusedVNDGCNNPSeg(_vn.EvalOnly):
         return bool(conv6.C == x123 and all(_vt.supported_point(N, f.C, f.Cg, f.O, f.Od) for f in self.points)
                     and _vt.supported_std(N, conv6.O, conv6.O, vn2.O) and _vt.supported_coords(N, x123, vn2.O))
 
+    @staticmethod
+    def _launch_level(h, nbr, level, out, B, N, k):
+        """A level's launches: the tables of its first layer, then the two-layer edge pass or, for a single layer, vn_edge_mean's."""
+        if len(level) == 2:
+            _vf._launch2(h, nbr, level[0], level[1], out, B, N, k)
+        else:
+            _vf._launch(h, nbr, level[0], out, B, N, k)
+
     @torch.no_grad()
     def forward(self, x, l, idx=None):
-        name = "FusedVNDGCNNPSeg"
-        self.eval_only()
-        for key, t in (("x", x), ("l", l)):
-            if isinstance(t, torch.Tensor) and t.requires_grad:      # (asked of the arguments themselves, as FusedVNDGCNN does)
-                raise ValueError("%s: %s requires grad - %s is forward only" % (name, key, _WHAT))
-        _pointset.check_tensors(name, {key: t.contiguous() if isinstance(t, torch.Tensor) else t for key, t in (("x", x), ("l", l))}, [_F32, _F32], _WHAT)
-        if x.dim() != 3 or x.shape[1] != 3 or x.shape[0] < 1:
-            raise ValueError("%s: x must be [B,3,N], got %s" % (name, tuple(x.shape)))
-        if l.dim() != 2 or l.shape[0] != x.shape[0] or l.shape[1] != self.model.conv7[0].weight.shape[1]:
-            raise ValueError("%s: l must be [B,%d] with B = %d, got %s" % (name, self.model.conv7[0].weight.shape[1], x.shape[0], tuple(l.shape)))
-        if idx is not None and (len(idx) != 3 or any(not isinstance(i, torch.Tensor) or i.dtype != torch.int64 or i.dim() != 3
-                                                     or i.shape[:2] != (x.shape[0], x.shape[2]) for i in idx)):
-            raise ValueError("%s: idx must hold the three levels' neighbour lists [B,N,k] int64" % name)
-        for n, i in enumerate(idx or ()):
-            if i.device != x.device:
-                raise ValueError("%s: x on %s, idx[%d] on %s" % (name, x.device, n, i.device))
-        _call.hip(x, l, *(idx or ()))
-        B, _, N = (int(v) for v in x.shape)
-        ks = [self.model.k] * 3 if idx is None else [int(i.shape[2]) for i in idx]
-        if not all(self.supported(B, N, k) for k in ks):
-            return self.model(x, l, idx=idx)
-        if self.points[0].device != x.device:
-            raise ValueError("%s: the model is on %s, x on %s" % (name, self.points[0].device, x.device))
-        from .models.utils.vn_util import knn
+        name = self._begin(_WHAT, x, l=l)
         model = self.model
-        h = x.contiguous().view(B, 1, 3, N)
-        feats, used = [], []
-        for i, level in enumerate(self.levels):
-            nbr = knn(h.view(B, -1, N), ks[i]) if idx is None else idx[i].contiguous()
-            out = torch.empty(B, level[-1].O, 3, N, dtype=_F32, device=x.device)
-            if len(level) == 2:
-                _vf._launch2(h, nbr, level[0], level[1], out, B, N, ks[i])
-            else:
-                _vf._launch(h, nbr, level[0], out, B, N, ks[i])
-            used.append(nbr)
-            feats.append(out)
-            h = out
-        self.last_idx = used
+        if l.dim() != 2 or l.shape[0] != x.shape[0] or l.shape[1] != model.conv7[0].weight.shape[1]:
+            raise ValueError("%s: l must be [B,%d] with B = %d, got %s" % (name, model.conv7[0].weight.shape[1], x.shape[0], tuple(l.shape)))
+        B, N, ks = self._lists(name, x, idx, 3, others=(l,))
+        if not all(self.supported(B, N, k) for k in ks):
+            return model(x, l, idx=idx)
+        _vn.check_model_device(name, self.points[0], "x", x)
+        feats = self._edge_levels(x, idx, ks, [(level, level[-1].O) for level in self.levels], self._launch_level)
         conv6, vn1, vn2 = self.points
         w_lin = model.std_feature.vn_lin.weight.detach()
         x123 = torch.cat(feats, dim=1)
-        local = _vt.vn_point(x123, conv6)
-        m = _vt.vn_cloud_mean(local)
-        y = _vt.vn_point(_vt.vn_point(local, vn1, cloud=m), vn2)
-        pooled = _vt.vn_std_pool(local, y, w_lin, cloud=m, workspace=self._std_ws)[:, :6 * conv6.O]
+        _, y, pooled = _vt.std_tail(_vt.vn_point(x123, conv6), vn1, vn2, w_lin, self._std_ws)
+        pooled = pooled[:, :6 * conv6.O]
         e123 = _vt.vn_std_coords(x123, y, w_lin)
         # the head: conv8 on [pooled | conv7(l)] expanded over the points and e123, as two products
         w_const, w_point = self._w8

@@ -99,11 +99,6 @@ def fold_vn_point(layer, cloud_channels=0):
     return FoldedVNPoint(layer, cloud_channels)
 
 
-def _check(name, args):
-    """The established order: tensors and dtypes, device match, contiguity, gradients (check_tensors); shapes are the caller's next."""
-    _pointset.check_tensors(name, {k: t for k, t in args.items() if t is not None}, [_F32] * len([t for t in args.values() if t is not None]), _WHAT)
-
-
 def _cloud_shape(name, cloud, B, Cg):
     if Cg == 0 and cloud is None:
         return
@@ -124,25 +119,16 @@ def vn_point(x, folded, cloud=None, out=None):
     with Cg = 0) -> out [B,O,3,N]: the layer's eval-mode forward on [x | cloud expanded over the points] (module docstring).  One
     launch on the current stream, and a small one in front of it with Cg > 0; no host read.  No argument may require grad."""
     name = "vn_point"
-    if not isinstance(folded, FoldedVNPoint):
-        raise TypeError("%s: folded must be a FoldedVNPoint (vn_tail.fold_vn_point), got %s" % (name, type(folded).__name__))
-    _check(name, {"x": x, "cloud": cloud, "out": out})
-    if x.dim() != 4 or x.shape[2] != 3 or x.shape[0] < 1:
-        raise ValueError("%s: x must be [B,C,3,N], got %s" % (name, tuple(x.shape)))
-    B, C, _, N = (int(v) for v in x.shape)
-    if C != folded.C:
-        raise ValueError("%s: the layer takes %d vector channels per point, x has %d" % (name, folded.C, C))
+    B, C, N, _ = _vn.check_entry(name, _WHAT, {"x": x, "cloud": cloud, "out": out}, ("x", "cloud", "out"), folded, FoldedVNPoint, "vn_tail.fold_vn_point",
+                                  per=" per point")
     _cloud_shape(name, cloud, B, folded.Cg)
-    if out is not None and tuple(out.shape) != (B, folded.O, 3, N):
-        raise ValueError("%s: out must be [B,O,3,N] = %s, got %s" % (name, (B, folded.O, 3, N), tuple(out.shape)))
-    _call.hip(x, cloud, out)
-    if folded.device != x.device:
-        raise ValueError("%s: the layer is on %s, x on %s" % (name, folded.device, x.device))
+    shape = (B, folded.O, 3, N)
+    _vn.check_out(name, out, shape, "[B,O,3,N]", (x, cloud, out), folded)
     if B > MAX_B or not supported_point(N, C, folded.Cg, folded.O, folded.Od):
         raise _lib.SvnetHipError("%s: B = %d, N = %d, C = %d, O = %d is not supported (B <= %d, 1 <= N <= %d, C <= %d, O <= %d)"
                                  % (name, B, N, C, folded.O, MAX_B, _pointset.MAX_N, MAX_C, MAX_O))
     if out is None:
-        out = torch.empty(B, folded.O, 3, N, dtype=_F32, device=x.device)
+        out = torch.empty(*shape, dtype=_F32, device=x.device)
     _launch_point(x, cloud, folded, out, B, N)
     return out
 
@@ -164,12 +150,7 @@ class FoldedVNPointNorm(_vn.Folded):
         w, bn = linear.map_to_feat.weight, batchnorm.bn
         if int(bn.num_features) != w.shape[0]:
             raise ValueError("%s: map_to_feat %s, BatchNorm over %d: the widths differ" % (self.NAME, tuple(w.shape), bn.num_features))
-        if bn.running_mean is None or bn.running_var is None or bn.weight is None or bn.bias is None:
-            raise ValueError("%s: the BatchNorm must be affine and track running statistics" % self.NAME)
-        for k, t in {"map_to_feat.weight": w, "bn.weight": bn.weight, "bn.bias": bn.bias, "running_mean": bn.running_mean,
-                     "running_var": bn.running_var}.items():
-            if t.dtype != _F32 or not t.is_contiguous() or t.device != w.device:
-                raise ValueError("%s: %s must be contiguous float32 on %s" % (self.NAME, k, w.device))
+        _vn.check_batchnorm(self.NAME, bn, {"map_to_feat.weight": w})
         self.place(linear)
         self.batchnorm = batchnorm
         self.dims = self.C, self.O = int(w.shape[1]), int(w.shape[0])
@@ -177,14 +158,8 @@ class FoldedVNPointNorm(_vn.Folded):
             raise _lib.SvnetHipError("%s: C = %d, O = %d is not supported (1 <= C <= %d, 1 <= O <= %d)" % (self.NAME, self.C, self.O, MAX_C, MAX_O))
         self.allocate(self.C * self.O + 2 * self.O)
 
-    def refresh(self):
-        w, bn = self.layer.map_to_feat.weight, self.batchnorm.bn
-        if w.device != self.device:
-            raise ValueError("%s: the layer moved from %s to %s - fold it again" % (self.NAME, self.device, w.device))
-        with torch.cuda.device(self.device):
-            _lib.call(self.ENTRY, _call.p(w.detach()), _call.p(bn.weight.detach()), _call.p(bn.bias.detach()), _call.p(bn.running_mean),
-                      _call.p(bn.running_var), *self.dims, float(bn.eps), _call.p(self.folded), _call.stream())
-        return self
+    def sources(self):
+        return [self.layer.map_to_feat.weight], self.batchnorm.bn
 
 
 def fold_vn_linear_norm(linear, batchnorm):
@@ -196,24 +171,15 @@ def vn_point_norm(x, folded, out=None):
     """x [B,C,3,N] float32, folded a FoldedVNPointNorm over C -> O -> out [B,O,3,N]: the eval-mode forward of the VNBatchNorm on the
     VNLinear's output (module docstring, norm only).  One launch on the current stream, no host read.  No argument may require grad."""
     name = "vn_point_norm"
-    if not isinstance(folded, FoldedVNPointNorm):
-        raise TypeError("%s: folded must be a FoldedVNPointNorm (vn_tail.fold_vn_linear_norm), got %s" % (name, type(folded).__name__))
-    _check(name, {"x": x, "out": out})
-    if x.dim() != 4 or x.shape[2] != 3 or x.shape[0] < 1:
-        raise ValueError("%s: x must be [B,C,3,N], got %s" % (name, tuple(x.shape)))
-    B, C, _, N = (int(v) for v in x.shape)
-    if C != folded.C:
-        raise ValueError("%s: the layer takes %d vector channels per point, x has %d" % (name, folded.C, C))
-    if out is not None and tuple(out.shape) != (B, folded.O, 3, N):
-        raise ValueError("%s: out must be [B,O,3,N] = %s, got %s" % (name, (B, folded.O, 3, N), tuple(out.shape)))
-    _call.hip(x, out)
-    if folded.device != x.device:
-        raise ValueError("%s: the layer is on %s, x on %s" % (name, folded.device, x.device))
+    B, C, N, _ = _vn.check_entry(name, _WHAT, {"x": x, "out": out}, ("x", "out"), folded, FoldedVNPointNorm, "vn_tail.fold_vn_linear_norm",
+                                  per=" per point")
+    shape = (B, folded.O, 3, N)
+    _vn.check_out(name, out, shape, "[B,O,3,N]", (x, out), folded)
     if B > MAX_B or not supported_point_norm(N, C, folded.O):
         raise _lib.SvnetHipError("%s: B = %d, N = %d, C = %d, O = %d is not supported (B <= %d, 1 <= N <= %d, C <= %d, O <= %d)"
                                  % (name, B, N, C, folded.O, MAX_B, _pointset.MAX_N, MAX_C, MAX_O))
     if out is None:
-        out = torch.empty(B, folded.O, 3, N, dtype=_F32, device=x.device)
+        out = torch.empty(*shape, dtype=_F32, device=x.device)
     with torch.cuda.device(x.device):
         _lib.call("svnet_vn_point_norm_f32", _call.p(x), _call.p(folded.folded), B, N, C, folded.O, _call.p(out), _call.stream())
     return out
@@ -223,13 +189,8 @@ def vn_cloud_mean(x, out=None):
     """x [B,C,3,N] float32 -> out [B,C,3]: the mean over the points in the contract's order (module docstring).  One launch on the
     current stream, no host read.  No argument may require grad."""
     name = "vn_cloud_mean"
-    _check(name, {"x": x, "out": out})
-    if x.dim() != 4 or x.shape[2] != 3 or x.shape[0] < 1:
-        raise ValueError("%s: x must be [B,C,3,N], got %s" % (name, tuple(x.shape)))
-    B, C, _, N = (int(v) for v in x.shape)
-    if out is not None and tuple(out.shape) != (B, C, 3):
-        raise ValueError("%s: out must be [B,C,3] = %s, got %s" % (name, (B, C, 3), tuple(out.shape)))
-    _call.hip(x, out)
+    B, C, N, _ = _vn.check_entry(name, _WHAT, {"x": x, "out": out}, ("x", "out"))
+    _vn.check_out(name, out, (B, C, 3), "[B,C,3]", (x, out))
     if B > MAX_B or not supported_point(N, C, 0, 1, 1):
         raise _lib.SvnetHipError("%s: B = %d, N = %d, C = %d is not supported (B <= %d, 1 <= N <= %d, 1 <= C <= %d)" % (name, B, N, C, MAX_B, _pointset.MAX_N, MAX_C))
     if out is None:
@@ -248,27 +209,18 @@ def vn_std_pool(x, y, w_lin, cloud=None, out=None, workspace=None):
     Two launches on the current stream, no host read.  workspace: a _Workspace to take the per-run partials from (FusedVNTail's);
     without one the calls of a device share a buffer that grows.  No argument may require grad."""
     name = "vn_std_pool"
-    _check(name, {"x": x, "y": y, "w_lin": w_lin, "cloud": cloud, "out": out})
-    if x.dim() != 4 or x.shape[2] != 3 or x.shape[0] < 1:
-        raise ValueError("%s: x must be [B,C,3,N], got %s" % (name, tuple(x.shape)))
-    B, C, _, N = (int(v) for v in x.shape)
-    if y.dim() != 4 or y.shape[0] != B or y.shape[2] != 3 or y.shape[3] != N or y.shape[1] < 1:
-        raise ValueError("%s: y must be [B,Cy,3,N] with B = %d, N = %d, got %s" % (name, B, N, tuple(y.shape)))
-    Cy = int(y.shape[1])
-    if tuple(w_lin.shape) != (3, Cy):
-        raise ValueError("%s: w_lin must be [3,Cy] = %s (normalize_frame = False), got %s" % (name, (3, Cy), tuple(w_lin.shape)))
+    B, C, N, _ = _vn.check_entry(name, _WHAT, {"x": x, "y": y, "w_lin": w_lin, "cloud": cloud, "out": out}, ("x", "y", "w_lin", "cloud", "out"))
+    Cy = _vn.frame_shapes(name, y, w_lin, B, N)
     Cg = 0 if cloud is None else int(cloud.shape[1]) if cloud.dim() == 3 else -1
     if cloud is not None and (Cg < 1 or tuple(cloud.shape) != (B, Cg, 3)):
         raise ValueError("%s: cloud must be [B,Cg,3] with B = %d, got %s" % (name, B, tuple(cloud.shape)))
-    cols = 6 * (C + Cg)
-    if out is not None and tuple(out.shape) != (B, cols):
-        raise ValueError("%s: out must be [B, 6 (C + Cg)] = %s, got %s" % (name, (B, cols), tuple(out.shape)))
-    _call.hip(x, y, w_lin, cloud, out)
+    shape = (B, 6 * (C + Cg))
+    _vn.check_out(name, out, shape, "[B, 6 (C + Cg)]", (x, y, w_lin, cloud, out))
     if B > MAX_B or not supported_std(N, C, Cg, Cy):
         raise _lib.SvnetHipError("%s: B = %d, N = %d, C = %d, Cg = %d, Cy = %d is not supported (B <= %d, 1 <= N <= %d, C, Cg, Cy <= %d)"
                                  % (name, B, N, C, Cg, Cy, MAX_B, _pointset.MAX_N, MAX_C))
     if out is None:
-        out = torch.empty(B, cols, dtype=_F32, device=x.device)
+        out = torch.empty(*shape, dtype=_F32, device=x.device)
     if workspace is None:
         workspace = _std_workspaces.setdefault(x.device, _Workspace(x.device))
     ws = workspace.take(int(_lib.lib().svnet_vn_std_pool_workspace_bytes(B, N, C, Cg)))
@@ -290,26 +242,27 @@ def vn_std_coords(x, y, w_lin, out=None):
     the levels' features.  One launch on the current stream, stores along n, no host read.  1 <= N <= 32768, 1 <= C, Cy <= 512,
     B <= 65535 (`supported_coords`).  No argument may require grad."""
     name = "vn_std_coords"
-    _check(name, {"x": x, "y": y, "w_lin": w_lin, "out": out})
-    if x.dim() != 4 or x.shape[2] != 3 or x.shape[0] < 1:
-        raise ValueError("%s: x must be [B,C,3,N], got %s" % (name, tuple(x.shape)))
-    B, C, _, N = (int(v) for v in x.shape)
-    if y.dim() != 4 or y.shape[0] != B or y.shape[2] != 3 or y.shape[3] != N or y.shape[1] < 1:
-        raise ValueError("%s: y must be [B,Cy,3,N] with B = %d, N = %d, got %s" % (name, B, N, tuple(y.shape)))
-    Cy = int(y.shape[1])
-    if tuple(w_lin.shape) != (3, Cy):
-        raise ValueError("%s: w_lin must be [3,Cy] = %s (normalize_frame = False), got %s" % (name, (3, Cy), tuple(w_lin.shape)))
-    if out is not None and tuple(out.shape) != (B, 3 * C, N):
-        raise ValueError("%s: out must be [B,3C,N] = %s, got %s" % (name, (B, 3 * C, N), tuple(out.shape)))
-    _call.hip(x, y, w_lin, out)
+    B, C, N, _ = _vn.check_entry(name, _WHAT, {"x": x, "y": y, "w_lin": w_lin, "out": out}, ("x", "y", "w_lin", "out"))
+    Cy = _vn.frame_shapes(name, y, w_lin, B, N)
+    shape = (B, 3 * C, N)
+    _vn.check_out(name, out, shape, "[B,3C,N]", (x, y, w_lin, out))
     if B > MAX_B or not supported_coords(N, C, Cy):
         raise _lib.SvnetHipError("%s: B = %d, N = %d, C = %d, Cy = %d is not supported (B <= %d, 1 <= N <= %d, 1 <= C, Cy <= %d)"
                                  % (name, B, N, C, Cy, MAX_B, _pointset.MAX_N, MAX_C))
     if out is None:
-        out = torch.empty(B, 3 * C, N, dtype=_F32, device=x.device)
+        out = torch.empty(*shape, dtype=_F32, device=x.device)
     with torch.cuda.device(x.device):
         _lib.call("svnet_vn_std_coords_f32", _call.p(x), _call.p(y), _call.p(w_lin), B, N, C, Cy, _call.p(out), _call.stream())
     return out
+
+
+def std_tail(local, vn1, vn2, w_lin, workspace):
+    """What follows the local features [B,C,3,N] in every vector-neuron model: the cloud mean, vn1 on [local | mean] with the mean as
+    its constant channels, vn2, and the standardise-and-pool stage in the frame w_lin y -> (m [B,C,3], y [B,Cy,3,N], h [B, 12 C]).
+    Through the public entries, with their checks; workspace: the caller's _Workspace for the stage's partials."""
+    m = vn_cloud_mean(local)
+    y = vn_point(vn_point(local, vn1, cloud=m), vn2)
+    return m, y, vn_std_pool(local, y, w_lin, cloud=m, workspace=workspace)
 
 
 class FusedVNTail(_vn.EvalOnly):
@@ -324,26 +277,18 @@ class FusedVNTail(_vn.EvalOnly):
     def __init__(self, model):
         super().__init__(model)
         std = model.std_feature
-        wide = model.conv5.map_to_feat.weight.shape[0]
+        wide = int(model.conv5.map_to_feat.weight.shape[0])
+        layers = ((model.conv5, 0), (std.vn1, wide), (std.vn2, 0))
         self.widths = [(int(l.map_to_feat.weight.shape[1]) - cg, cg, int(l.map_to_feat.weight.shape[0]), int(l.map_to_dir.weight.shape[0]))
-                       for l, cg in ((model.conv5, 0), (std.vn1, int(wide)), (std.vn2, 0))]
+                       for l, cg in layers]
         self.Cy = int(std.vn_lin.weight.shape[1])
         self.fused = bool(not std.normalize_frame and all(c >= 1 and supported_point(1, c, cg, o, od) for c, cg, o, od in self.widths)
                           and supported_std(1, wide, wide, self.Cy))
-        self.layers = [fold_vn_point(l, cg) for l, cg in ((model.conv5, 0), (std.vn1, int(wide)), (std.vn2, 0))] if self.fused else []
+        self.layers = [fold_vn_point(l, cg) for l, cg in layers] if self.fused else []
         self._std_ws = _Workspace(self.layers[0].device) if self.fused else None
 
-    def refresh(self):
-        for layer in self.layers:
-            layer.refresh()
-        return self
-
-    def release(self):
-        for layer in self.layers:
-            layer.release()
-        if self._std_ws is not None:
-            self._std_ws.release()
-        return self
+    def _folded(self):
+        return self.layers
 
     def supported(self, B, N):
         """Whether B clouds of N points take the fused path here; else forward runs model.tail."""
@@ -371,13 +316,9 @@ class FusedVNTail(_vn.EvalOnly):
         x = feats[0] if len(feats) == 1 else torch.cat(feats, dim=1)
         if not self.supported(B, N) or int(x.shape[1]) != self.widths[0][0]:
             raise _lib.SvnetHipError("FusedVNTail: B = %d, N = %d, %d channels is outside the fused tail (`supported`)" % (B, N, x.shape[1]))
-        if self.layers[0].device != x.device:
-            raise ValueError("FusedVNTail: the model is on %s, feats on %s" % (self.layers[0].device, x.device))
+        _vn.check_model_device("FusedVNTail", self.layers[0], "feats", x)
         conv5, vn1, vn2 = self.layers
-        local = vn_point(x, conv5)
-        m = vn_cloud_mean(local)
-        y = vn_point(vn_point(local, vn1, cloud=m), vn2)
-        return vn_std_pool(local, y, self.model.std_feature.vn_lin.weight.detach(), cloud=m, workspace=self._std_ws)
+        return std_tail(vn_point(x, conv5), vn1, vn2, self.model.std_feature.vn_lin.weight.detach(), self._std_ws)[2]
 
     @torch.no_grad()
     def forward(self, feats):

@@ -362,7 +362,8 @@ def test_front_ends_and_step_state_do_not_import_the_op_layer():
 
 def test_vector_neuron_leaf_sits_under_its_two_front_ends():
     """svnet_amd._vn imports neither front end, the op layer nor the step state, anywhere; vn_fused and vn_tail import it and not
-    each other at module level - FusedVNDGCNN imports vn_tail inside its constructor, when a tail is asked for."""
+    each other at module level - FusedVNDGCNN imports vn_tail inside its constructor, when a tail is asked for.  The two model
+    fronts on top of them, vn_pseg and vn_pointnet, import it too, and neither vn_fused nor vn_tail imports one of those, anywhere."""
     import ast
 
     def imported(name, top_only):
@@ -375,6 +376,10 @@ def test_vector_neuron_leaf_sits_under_its_two_front_ends():
     assert "_vn" in imported("vn_fused", True) and "_vn" in imported("vn_tail", True)
     assert not {"vn_tail", "_ops", "_step"} & imported("vn_fused", True) and not {"vn_fused", "_ops", "_step"} & imported("vn_tail", True)
     assert "vn_tail" in imported("vn_fused", False)
+    assert "_vn" in imported("vn_pseg", True) and "_vn" in imported("vn_pointnet", True)
+    for front in ("vn_fused", "vn_tail"):
+        assert not {"vn_pseg", "vn_pointnet", "_ops", "_step"} & imported(front, False), front
+    assert not {"_ops", "_step"} & (imported("vn_pseg", False) | imported("vn_pointnet", False))
 
 
 def test_op_layer_names_are_the_call_helpers_and_the_step_objects_themselves():

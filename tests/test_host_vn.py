@@ -180,11 +180,8 @@ def test_header_names_the_new_entry_points_under_the_bumped_abi():
 
 
 def _fake_folded(C, O, Od=None):
-    """A FoldedVNLayer that was never folded, on the CPU: for the argument checks, which come before the first launch."""
     from svnet_amd import vn_fused as VF
-    f = object.__new__(VF.FoldedVNLayer)
-    f.C, f.O, f.Od, f.device = C, O, O if Od is None else Od, torch.device("cpu")
-    return f
+    return VC.fake(VF.FoldedVNLayer, C=C, O=O, Od=O if Od is None else Od)
 
 
 def test_vn_edge_mean_refuses_bad_arguments():
@@ -232,22 +229,15 @@ def test_fold_and_wrapper_refuse_what_they_cannot_take():
         VF.FusedVNDGCNN(golden_model())
     fused = VF.FusedVNDGCNN(golden_model("max"))                                 # nothing to fold: every call is the model's
     assert not fused.supported(64, 8) and isinstance(fused, torch.nn.Module) and fused.model.pool1.map_to_dir.weight.shape == (21, 21)
-    fused.train()
-    with pytest.raises(RuntimeError, match="train mode"):
-        fused(torch.zeros(2, 3, 64))
-    fused.eval()
-    with pytest.raises(TypeError, match="x must be torch.float32"):
-        fused(torch.zeros(2, 3, 64).double())
-    with pytest.raises(ValueError, match=r"x must be \[B,3,N\]"):
-        fused(torch.zeros(2, 64, 3))
-    with pytest.raises(ValueError, match="x requires grad"):                     # asked of the argument, a view included
-        fused(torch.zeros(2, 64, 3).transpose(1, 2).requires_grad_())
-    with pytest.raises(ValueError, match="x requires grad"):
-        fused(torch.zeros(2, 3, 64).requires_grad_())
-    with pytest.raises(ValueError, match="four levels"):
-        fused(torch.zeros(2, 3, 64), idx=golden_lists()[:2])
-    with pytest.raises(ValueError, match=r"idx\[1\] on meta"):                    # every list on x's device
-        fused(torch.zeros(2, 3, 64), idx=[i.to("meta") if n == 1 else i for n, i in enumerate(golden_lists())])
+    x, flat = torch.zeros(2, 3, 64), torch.zeros(2, 64, 3)
+    VC.cpu_wrapper_refuses(fused, (x,), [
+        (TypeError, "x must be torch.float32", (x.double(),), {}),
+        (ValueError, r"x must be \[B,3,N\]", (flat,), {}),
+        (ValueError, "x requires grad", (flat.transpose(1, 2).requires_grad_(),), {}),      # asked of the argument, a view included
+        (ValueError, "x requires grad", (x.clone().requires_grad_(),), {}),
+        (ValueError, "four levels", (x,), {"idx": golden_lists()[:2]}),
+        (ValueError, r"idx\[1\] on meta", (x,), {"idx": [i.to("meta") if n == 1 else i for n, i in enumerate(golden_lists())]}),      # every list on x's device
+        (RuntimeError, "no CPU fallback", (x,), {"idx": golden_lists()})], mode=fused)
     assert fused.release() is fused
     f = _fake_folded(3, 5)
     f._ws = VF._vn.Workspace(f.device)
@@ -257,5 +247,3 @@ def test_fold_and_wrapper_refuse_what_they_cannot_take():
         golden_model("median")
     with pytest.raises(ValueError, match="dim must be 3, 4 or 5"):
         L.VNBatchNorm(4, dim=2)
-    with pytest.raises(RuntimeError, match="no CPU fallback"):
-        fused(torch.zeros(2, 3, 64), idx=golden_lists())

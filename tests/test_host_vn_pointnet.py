@@ -181,13 +181,7 @@ def test_header_names_the_entries_under_abi_435():
     assert L.svnet_vn_point_norm_fold_f32(p, p, p, p, p, 4, 513, 1e-5, p, None) == E["SVNET_E_UNSUPPORTED"]
 
 
-def _fake(cls, **fields):
-    """A folded layer that was never folded, on the CPU: for the argument checks, which come before the first launch."""
-    f = object.__new__(cls)
-    f.device = torch.device("cpu")
-    for key, v in fields.items():
-        setattr(f, key, v)
-    return f
+_fake = VC.fake
 
 
 def test_fronts_refuse_bad_arguments_before_any_device_call():
@@ -259,19 +253,9 @@ def test_wrapper_refuses_what_it_cannot_take():
     for model in (PC.golden_model(pooling="max"), framed):
         fused = VP.FusedVNPointNet(model)
         assert not fused.fused and fused.cross is None and not fused.points and not fused.supported(2, 64, 8)
-        assert isinstance(fused, torch.nn.Module) and fused.refresh() is fused and fused.release() is fused and not fused.training
-        assert list(fused.state_dict()) == ["model." + key for key in model.state_dict()]
-        model.train()
-        with pytest.raises(RuntimeError, match="train mode"):
-            fused(x)
-        model.eval()
-        with pytest.raises(TypeError, match="x must be torch.float32"):
-            fused(x.double())
-        with pytest.raises(ValueError, match="x requires grad"):
-            fused(x.clone().requires_grad_())
-        with pytest.raises(ValueError, match=r"x must be \[B,3,N\]"):
-            fused(x[:, :2].contiguous())
-        with pytest.raises(ValueError, match="neighbour list"):
-            fused(x, idx=[idx])
-        with pytest.raises(RuntimeError, match="no CPU fallback"):
-            fused(x, idx=idx)
+        VC.cpu_wrapper_refuses(fused, (x,), [
+            (TypeError, "x must be torch.float32", (x.double(),), {}),
+            (ValueError, "x requires grad", (x.clone().requires_grad_(),), {}),
+            (ValueError, r"x must be \[B,3,N\]", (x[:, :2].contiguous(),), {}),
+            (ValueError, "neighbour list", (x,), {"idx": [idx]}),
+            (RuntimeError, "no CPU fallback", (x,), {"idx": idx})])

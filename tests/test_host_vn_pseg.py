@@ -178,13 +178,7 @@ def test_header_names_the_entries_under_abi_434():
     assert b"svnet_vn_std_coords_f32" in L.svnet_last_error()
 
 
-def _fake(cls, **fields):
-    """A folded layer that was never folded, on the CPU: for the argument checks, which come before the first launch."""
-    f = object.__new__(cls)
-    f.device = torch.device("cpu")
-    for key, v in fields.items():
-        setattr(f, key, v)
-    return f
+_fake = VC.fake
 
 
 def test_fronts_refuse_bad_arguments_before_any_device_call():
@@ -248,22 +242,11 @@ def test_wrapper_refuses_what_it_cannot_take():
         model.std_feature.normalize_frame = True
         fused = VP.FusedVNDGCNNPSeg(model)
         assert not fused.fused and not fused.levels and not fused.points and not fused.supported(2, 64, 8)
-        assert isinstance(fused, torch.nn.Module) and fused.refresh() is fused and fused.release() is fused and not fused.training
-        assert list(fused.state_dict()) == ["model." + key for key in model.state_dict()]
-        x, l = torch.from_numpy(GOLDEN["x"]), torch.from_numpy(GOLDEN["l"])
-        model.train()
-        with pytest.raises(RuntimeError, match="train mode"):
-            fused(x, l)
-        model.eval()
-        with pytest.raises(TypeError, match="x must be torch.float32"):
-            fused(x.double(), l)
-        with pytest.raises(ValueError, match="l requires grad"):
-            fused(x, l.clone().requires_grad_())
-        with pytest.raises(ValueError, match=r"x must be \[B,3,N\]"):
-            fused(x[:, :2].contiguous(), l)
-        with pytest.raises(ValueError, match=r"l must be \[B,16\]"):
-            fused(x, l[:1].contiguous())
-        with pytest.raises(ValueError, match="three levels"):
-            fused(x, l, idx=[torch.from_numpy(i) for i in PC.lists()[:2]])
-        with pytest.raises(RuntimeError, match="no CPU fallback"):
-            fused(x, l, idx=[torch.from_numpy(i) for i in PC.lists()])
+        x, l, lists = torch.from_numpy(GOLDEN["x"]), torch.from_numpy(GOLDEN["l"]), [torch.from_numpy(i) for i in PC.lists()]
+        VC.cpu_wrapper_refuses(fused, (x, l), [
+            (TypeError, "x must be torch.float32", (x.double(), l), {}),
+            (ValueError, "l requires grad", (x, l.clone().requires_grad_()), {}),
+            (ValueError, r"x must be \[B,3,N\]", (x[:, :2].contiguous(), l), {}),
+            (ValueError, r"l must be \[B,16\]", (x, l[:1].contiguous()), {}),
+            (ValueError, "three levels", (x, l), {"idx": lists[:2]}),
+            (RuntimeError, "no CPU fallback", (x, l), {"idx": lists})])

@@ -143,11 +143,8 @@ def test_header_names_the_tail_entries_under_abi_433():
 
 
 def _fake_folded(C, Cg, O, Od=None):
-    """A FoldedVNPoint that was never folded, on the CPU: for the argument checks, which come before the first launch."""
     from svnet_amd import vn_tail as VT
-    f = object.__new__(VT.FoldedVNPoint)
-    f.C, f.Cg, f.O, f.Od, f.device = C, Cg, O, O if Od is None else Od, torch.device("cpu")
-    return f
+    return VC.fake(VT.FoldedVNPoint, C=C, Cg=Cg, O=O, Od=O if Od is None else Od)
 
 
 def test_front_refuses_bad_arguments():
@@ -227,22 +224,14 @@ def test_fold_and_wrappers_refuse_what_they_cannot_take():
     model = golden_model()
     model.std_feature.normalize_frame = True
     tail = VT.FusedVNTail(model)
-    assert not tail.fused and not tail.supported(2, 64) and isinstance(tail, torch.nn.Module) and tail.release() is tail and tail.refresh() is tail
+    assert not tail.fused and not tail.supported(2, 64)
     feats = [torch.from_numpy(GOLDEN["lvl%d" % i]) for i in range(4)]
-    model.train()
-    with pytest.raises(RuntimeError, match="train mode"):
-        tail(feats)
-    model.eval()
-    with pytest.raises(TypeError, match=r"feats\[0\] must be torch.float32"):
-        tail([f.double() for f in feats])
-    with pytest.raises(ValueError, match=r"feats\[2\] requires grad"):
-        tail([f.clone().requires_grad_() if i == 2 else f for i, f in enumerate(feats)])
-    with pytest.raises(ValueError, match=r"feats must be \[B,C_i,3,N\]"):
-        tail([feats[0], feats[1][:, :, :, :8].contiguous()])
-    with pytest.raises(ValueError, match="feats must hold"):
-        tail([])
-    with pytest.raises(RuntimeError, match="no CPU fallback"):
-        tail(feats)
+    VC.cpu_wrapper_refuses(tail, (feats,), [
+        (TypeError, r"feats\[0\] must be torch.float32", ([f.double() for f in feats],), {}),
+        (ValueError, r"feats\[2\] requires grad", ([f.clone().requires_grad_() if i == 2 else f for i, f in enumerate(feats)],), {}),
+        (ValueError, r"feats must be \[B,C_i,3,N\]", ([feats[0], feats[1][:, :, :, :8].contiguous()],), {}),
+        (ValueError, "feats must hold", ([],), {}),
+        (RuntimeError, "no CPU fallback", (feats,), {})])
     # pooling = 'max' with tail=True: no tail is built, as no level is
     fused = VF.FusedVNDGCNN(golden_model("max"), tail=True)
     assert fused.tail is None and not fused.levels and fused.refresh() is fused and fused.release() is fused

@@ -1,9 +1,11 @@
-"""What the tests of the fused vector-neuron kernels share (tests/test_{hip,host}_{vn,vn_tail}.py): the arrays of a synthetic
-VNLinearLeakyReLU, the module built from them, and the golden case of tests/golden/vn.npz - its state, model and recorded levels.
+"""What the tests of the fused vector-neuron kernels share (tests/test_{hip,host}_vn*.py): the arrays of a synthetic
+VNLinearLeakyReLU, the module built from them, the folded layer that was never folded and the refusals of a wrapper that lives on the
+CPU (the host files'), and the golden case of tests/golden/vn.npz - its state, model and recorded levels.
 Every draw is a function of (seed, shape) alone, so a file's references stay what they were whichever test asks first."""
 import argparse
 
 import numpy as np
+import pytest
 import torch
 
 from svnet_amd import synth
@@ -36,6 +38,35 @@ def layer(dev, K, O, share, slope, a, **kw):
                        (bn.running_mean, "mean"), (bn.running_var, "var")):
             t.copy_(torch.from_numpy(a[key]))
     return layer.to(dev).eval()
+
+
+def fake(cls, **fields):
+    """A folded layer of class cls that was never folded, on the CPU, with the given fields: for the argument checks, which come
+    before the first launch."""
+    f = object.__new__(cls)
+    f.device = torch.device("cpu")
+    for key, v in fields.items():
+        setattr(f, key, v)
+    return f
+
+
+def cpu_wrapper_refuses(fused, good, refusals, mode=None):
+    """A wrapper that found nothing to fold, so that it lives on the CPU: it is a Module whose refresh() and release() return it,
+    it is in eval mode as its model is, its state_dict is the model's under `model.`; a call in train mode - set on `mode`, the model
+    or the wrapper - is refused, whatever the arguments `good`; then the calls of `refusals`, (exception, match, args, kwargs) in the
+    order of the checks they meet, the last of them the one with no fault but the device."""
+    model = fused.model
+    assert isinstance(fused, torch.nn.Module) and fused.refresh() is fused and fused.release() is fused and not fused.training
+    assert list(fused.state_dict()) == ["model." + key for key in model.state_dict()]
+    mode = model if mode is None else mode
+    mode.train()
+    with pytest.raises(RuntimeError, match="train mode"):
+        fused(*good)
+    mode.eval()
+    assert not fused.training and not model.training and refusals[-1][:2] == (RuntimeError, "no CPU fallback")
+    for exc, match, args, kw in refusals:
+        with pytest.raises(exc, match=match):
+            fused(*args, **kw)
 
 
 def state():
