@@ -585,11 +585,16 @@ __global__ __launch_bounds__(256, tile_waves(NKS, NC2)) void edgeblock_bwd_kerne
     // the gate path's per-cloud constants of phase C's scalar pass (lane = scalar channel): requested HERE.  Loaded where they are used
     // - first thing in pass 1, behind the ~20 gather requests of phase C that are still in flight (vmcnt retires in order) - they made
     // that pass wait out the whole gather: 19 % (conv4) to 42 % (conv2) of a workgroup's time (phase clocks, profiles/r04_tile_phases.txt)
-    float gc_pre0 = 0.f, gc_pre1 = 0.f;
+    // A tile's rows lie in its first cloud b0 or in the one behind it unless a cloud has fewer than 31 edge rows: the second cloud's
+    // constants are requested here as well (from the last cloud where there is none), and pass 1 picks per row with a uniform select.
+    float gc_pre0 = 0.f, gc_pre1 = 0.f, gc_nx0 = 0.f, gc_nx1 = 0.f;
     if constexpr (NC2 > 0) {
         const int sl_ = min(lane, Cs - 1);
+        const uint32_t b1_ = min(tp.b0 + 1u, (uint32_t)d.B - 1u);
         gc_pre0 = d.gconst[tp.b0 * 2u * (uint32_t)Cs + sl_];
         gc_pre1 = d.gconst[tp.b0 * 2u * (uint32_t)Cs + Cs + sl_];
+        gc_nx0 = d.gconst[b1_ * 2u * (uint32_t)Cs + sl_];
+        gc_nx1 = d.gconst[b1_ * 2u * (uint32_t)Cs + Cs + sl_];
     }
 
     // ================= phase A: dL/dy_pre of the tile's 32 x Os edge-channels from the saved integer sums =========
@@ -686,8 +691,10 @@ __global__ __launch_bounds__(256, tile_waves(NKS, NC2)) void edgeblock_bwd_kerne
     }
 
     PHASE_MARK(1);   // plane transposition
-    // phase C's global operands (NC2 > 0): requested between phase B's MFMAs and its epilogue (see there), consumed in phase C
+    // phase C's global operands (NC2 > 0): requested between phase B's MFMAs and its epilogue (see there) or at the start of phase C,
+    // consumed in phase C
     constexpr int PC_NCH = NC2 > 0 ? NC2 / 4 : 1;
+    constexpr bool PC_EARLY = NC2 > 0 && NC2 <= 44 && NKS >= 4;
     float pc_vst[8][2], pc_vi[PC_NCH], pc_zj[3], pc_zi[6];
     // ================= phase B: dx_b = dnl . sign(W1), masked by the STE plane =================
     {
@@ -726,8 +733,10 @@ __global__ __launch_bounds__(256, tile_waves(NKS, NC2)) void edgeblock_bwd_kerne
         // instructions, too short to cover an L2 round trip, while the epilogue below is 300 - 450 (and phase B's weight fragments are
         // dead by now: the registers are free).  conv4 531 -> 521 us, conv3 330 -> 320; at Os = 32 the epilogue is two column tiles per
         // wave and the early requests only lengthened live ranges (254 -> 276 us): there they stay at the start of phase C.
+        // So do those of the NC2 = 48 forms (no layer of the models): their sixteen row registers did not fit across the epilogue - four
+        // to six of the gathered values were waited for one by one right behind their loads and parked in scratch (24 - 28 bytes per lane).
         PHASE_MARK(5);   // phase B: MFMAs issued
-        if constexpr (NC2 > 0 && NKS >= 4) SVNET_PHASEC_REQUESTS();
+        if constexpr (PC_EARLY) SVNET_PHASEC_REQUESTS();
         __syncthreads();   // every wave has consumed dnb: dxl may now overwrite the same LDS bytes
         PHASE_MARK(6);   // phase B: barrier behind the MFMAs
         // Accumulator element i of a lane is row (i & 3) + 8 (i >> 2) + 4 h of the tile: the sixteen row offsets are wave-uniform values
@@ -793,12 +802,30 @@ __global__ __launch_bounds__(256, tile_waves(NKS, NC2)) void edgeblock_bwd_kerne
         const int row0 = RW * wave;
         const int n3 = 3 * Cv;
         float* zs = reinterpret_cast<float*>(pl);          // [TE][9] dL/dz of every row (the plane words are consumed: phase B is over)
-        EdgeCursor cur;                                    // position of row0 (uniform)
-        cursor_init(d, tp, e0, row0, cur);
-
+        const int nrows = (int)min((int64_t)RW, E - ew);   // this wave's rows below E (uniform)
+        if (nrows <= 0) return;                            // (a ragged last tile: no row, nothing to store or to sum; never wave 0)
         // ---- the neighbour rows v_j (lane = element of the [3][Cv] row) and the per-lane operands of pass 3: requested before phase
-        // B's epilogue (wide layers) or here
-        if constexpr (NKS < 4) SVNET_PHASEC_REQUESTS();
+        // B's epilogue (Os >= 64 with one load per row) or here.  Pass 1 does not wait for them: behind them it only stores.
+        if constexpr (!PC_EARLY) SVNET_PHASEC_REQUESTS();
+        // ---- the positions of the wave's rows, ONCE, as scalars: the point of every row, "last row of its point in this wave" (the row
+        // behind which the centre sums go out) and "in the cloud behind the tile's first".  Rows past E REPEAT the wave's last row in
+        // passes 1 and 4 - same LDS row, same address, same value stored again, no flush - so neither pass has a row-count branch.
+        // (Lane rr works out row rr - two small divisions, no cursor walk on the scalar unit - and ballots / lane reads make the answers
+        //  uniform.  pin = the row's point counted from the first point of cloud b0: N and more is the next cloud, 2 N and more a third.)
+        uint32_t rgp[RW], lastm, nxm;
+        bool far;                                          // rows in a third cloud (a cloud of fewer than 31 edge rows)
+        {
+            const int rl = lane & 7;
+            const uint32_t n_ = (uint32_t)(tp.t0 + row0 + min(rl, nrows - 1));
+            const uint32_t dq_ = small_div(n_, tp.kmagic), dq1_ = small_div(n_ + 1u, tp.kmagic);
+            const uint32_t pin_ = (uint32_t)tp.pin0 + dq_;
+            nxm = (uint32_t)__ballot(pin_ >= Nu) & 0xFFu;
+            far = __ballot(pin_ >= 2u * Nu) != 0ull;
+            lastm = (uint32_t)__ballot(rl == nrows - 1 || (rl < nrows - 1 && dq1_ != dq_)) & 0xFFu;
+            const int gpv = (int)(tp.gp0 + dq_);
+#pragma unroll
+            for (int rr = 0; rr < RW; ++rr) rgp[rr] = (uint32_t)__builtin_amdgcn_readlane(gpv, rr);
+        }
         float (&vst)[RW][2] = pc_vst;
         // ---- per-lane operands of pass 3 (requested there as well)
         const int el = lane >> 3, ch = (lane >> 2) & 1, q = lane & 3, qq = min(q, 2);
@@ -815,35 +842,51 @@ __global__ __launch_bounds__(256, tile_waves(NKS, NC2)) void edgeblock_bwd_kerne
         const float zj0 = pc_zj[0], zj1 = pc_zj[1], zj2 = pc_zj[2];
         const float zi0 = pc_zi[0], zi1 = pc_zi[1], zi2 = pc_zi[2], zi3 = pc_zi[3], zi4 = pc_zi[4], zi5 = pc_zi[5];
 
-        PHASE_MARK(10);   // phase C: set-up (cursor, requests of the narrow layers)
+        PHASE_MARK(10);   // phase C: set-up (row positions, requests of the narrow layers)
         // ---- pass 1: scalar part, lanes = scalar channels
         {
+            // Straight-line over the eight rows, no load and no branch but the flush in a row's body: the compiler's wait-count pass gives
+            // up counting at a back-edge or at a branch around a load or a store (it then drains vmcnt to 0 - the gathers of phase C that
+            // are still in flight, and every earlier row's store).  So every lane stores every row: lanes past Cs repeat lane Cs - 1 and
+            // rows past E the wave's last row (same address, same value).  The flush is a uniform branch around an atomic without a
+            // return value: nothing waits for it.
             const bool s_lane = lane < Cs;
             const int sl = min(lane, Cs - 1);
-            uint32_t cur_p = 0xFFFFFFFFu, cur_b = 0xFFFFFFFFu;
-            float g0c = 0.f, g1c = 0.f, cs_sum = 0.f;
-            EdgeCursor c2 = cur;
-            for (int rr = 0; rr < RW; ++rr) {
-                if (c2.e >= E) break;                              // (uniform)
-                if (c2.gp != cur_p) {
-                    if (cur_p != 0xFFFFFFFFu && s_lane) ATOMIC_ADD(&d.ds_acc[cur_p * (uint32_t)Cs + (uint32_t)lane], cs_sum);
-                    cur_p = c2.gp;
-                    cs_sum = 0.f;
-                    if (c2.b != cur_b) {
-                        cur_b = c2.b;
-                        if (cur_b == tp.b0) { g0c = gc_pre0; g1c = gc_pre1; }      // (the tile's first cloud: requested at the kernel's start)
-                        else { g0c = d.gconst[cur_b * 2u * (uint32_t)Cs + sl]; g1c = d.gconst[cur_b * 2u * (uint32_t)Cs + Cs + sl]; }
+            if (far) {
+                // More than two clouds under one tile (N k <= 30; no shape of the models): the early-requested constants do not cover
+                // the wave's rows.  Every row's constants are added to its two operands IN the tile, from the table, and the pass below
+                // adds -0.0f, which changes no value: the sums are the same single additions of the same operands.  Taken once per
+                // wave; its loads are consumed inside the branch.
+                EdgeCursor c2;
+                cursor_init(d, tp, e0, row0, c2);
+                for (int rr = 0; rr < nrows; ++rr) {
+                    float* row = dxl + (row0 + rr) * DXS;
+                    if (s_lane) {
+                        row[lane] += d.gconst[c2.b * 2u * (uint32_t)Cs + lane];
+                        row[Cs + lane] += d.gconst[c2.b * 2u * (uint32_t)Cs + Cs + lane];
                     }
+                    cursor_next(d, c2);
                 }
-                const float* row = dxl + (row0 + rr) * DXS;
-                const float d0 = row[sl] + g0c;
-                if (s_lane) {
-                    st_f32_sbase(d.msg + c2.e * R, 4u * (uint32_t)lane, d0);
-                    cs_sum += (row[Cs + sl] + g1c) - d0;
-                }
-                cursor_next(d, c2);
+                gc_pre0 = gc_pre1 = gc_nx0 = gc_nx1 = -0.f;
             }
-            if (cur_p != 0xFFFFFFFFu && s_lane) ATOMIC_ADD(&d.ds_acc[cur_p * (uint32_t)Cs + (uint32_t)lane], cs_sum);
+            float a0[RW], a1[RW];
+#pragma unroll
+            for (int rr = 0; rr < RW; ++rr) {
+                const float* row = dxl + (row0 + min(rr, nrows - 1)) * DXS;
+                a0[rr] = row[sl];
+                a1[rr] = row[Cs + sl];
+            }
+            float* const srow = d.msg + ew * R;
+            float cs_sum = 0.f;
+#pragma unroll
+            for (int rr = 0; rr < RW; ++rr) {
+                const bool nx = (nxm >> rr) & 1u, last = (lastm >> rr) & 1u;           // (uniform)
+                const float d0 = a0[rr] + (nx ? gc_nx0 : gc_pre0);
+                st_f32_sbase(srow + (uint32_t)min(rr, nrows - 1) * (uint32_t)R, 4u * (uint32_t)sl, d0);
+                cs_sum += (a1[rr] + (nx ? gc_nx1 : gc_pre1)) - d0;
+                if (last && s_lane) ATOMIC_ADD(&d.ds_acc[rgp[rr] * (uint32_t)Cs + (uint32_t)lane], cs_sum);
+                cs_sum = last ? 0.f : cs_sum;
+            }
         }
         PHASE_MARK(7);   // phase C pass 1
         // ---- pass 2: the neighbours' v rows into the (consumed) scalar columns of their tile rows: [3][Cv] at column 0 (3 Cv <= 2 Cs)
@@ -884,39 +927,45 @@ __global__ __launch_bounds__(256, tile_waves(NKS, NC2)) void edgeblock_bwd_kerne
         PHASE_MARK(9);   // phase C passes 2 + 3
         // ---- pass 4: lanes = elements L of the message row's Vector2Scalar part [dve (3 x Cv) | dz (9)]; centre sums [dv | dz] per point
         {
+            // Straight-line like pass 1, on the same row positions.  A lane's class (dve element or dz element, its group, its columns)
+            // is settled once per 64-lane column group: the lane then walks ONE LDS address per value with its own row stride (the dx
+            // tile's or the dz rows'), all sixteen reads of a group go out before the first use, and its centre sums go to one
+            // address of its own table.  Lanes past the row's end repeat its last element, rows past E the wave's last row.
             const int nout = n3 + 9;
-            for (int L0 = 0; L0 < nout; L0 += 64) {
-                const int L = L0 + lane;
+            constexpr int NG = NC2 > 24 ? 2 : 1;                  // column groups: nout <= 45 up to Cv = 12, <= 81 up to Cv = 24
+            float* const mrow = d.msg + ew * R + Cs;
+#pragma unroll
+            for (int g = 0; g < NG; ++g) {
+                if (g > 0 && nout <= 64 * g) break;               // (uniform)
+                const int L = 64 * g + lane;
                 const bool on = L < nout;
-                const int Ld = on ? L : 0;
+                const int Ld = min(L, nout - 1);
                 const bool isv = Ld < n3;
-                const int grp = isv ? Ld / Cv : 0;
-                const int colm = 2 * Cs + grp * 2 * Cv + (Ld - grp * Cv);     // column of dve element (grp, c); its centre twin is Cv further
-                EdgeCursor c2 = cur;
-                uint32_t cur_p = 0xFFFFFFFFu;
-                float acc = 0.f;
-#define SVNET_FLUSH_V(p)                                                                                           \
-    do {                                                                                                           \
-        if (on) {                                                                                                  \
-            if (isv) ATOMIC_ADD(&d.dv_acc[(p) * 3u * uCv + (uint32_t)L], acc);                                     \
-            else ATOMIC_ADD(&d.dzc[(p) * 9u + (uint32_t)(L - n3)], acc);                                           \
-        }                                                                                                          \
-    } while (0)
+                const int grp = (Ld >= Cv ? 1 : 0) + (Ld >= 2 * Cv ? 1 : 0);      // (of a dve element; Cv <= 24: no division)
+                // the message element: column of dve element (grp, c), or dz element Ld - n3 of the row; the centre sums add the dve
+                // element's centre twin Cv further, or the dz element itself
+                const float* const pm = isv ? dxl + row0 * DXS + 2 * Cs + grp * 2 * Cv + (Ld - grp * Cv) : zs + row0 * 9 + (Ld - n3);
+                const float* const pc = isv ? pm + Cv : pm;
+                const int rs = isv ? DXS : 9;
+                float* const pacc = isv ? d.dv_acc + Ld : d.dzc + (Ld - n3);
+                const uint32_t ps = isv ? 3u * uCv : 9u;
+                float mv_[RW], cv_[RW];
+#pragma unroll
                 for (int rr = 0; rr < RW; ++rr) {
-                    if (c2.e >= E) break;                          // (uniform)
-                    if (c2.gp != cur_p) {
-                        if (cur_p != 0xFFFFFFFFu) SVNET_FLUSH_V(cur_p);
-                        cur_p = c2.gp;
-                        acc = 0.f;
-                    }
-                    const float* row = dxl + (row0 + rr) * DXS;
-                    const float mv_ = isv ? row[colm] : zs[(row0 + rr) * 9 + (Ld - n3)];
-                    acc += isv ? row[colm + Cv] : mv_;
-                    if (on) st_f32_sbase(d.msg + c2.e * R + Cs, 4u * (uint32_t)L, mv_);
-                    cursor_next(d, c2);
+                    const int ro = __mul24(min(rr, nrows - 1), rs);
+                    mv_[rr] = pm[ro];
+                    cv_[rr] = pc[ro];
                 }
-                if (cur_p != 0xFFFFFFFFu) SVNET_FLUSH_V(cur_p);
-#undef SVNET_FLUSH_V
+                __builtin_amdgcn_sched_barrier(0);                // (every read of the group is out: one wait, not one per read)
+                float acc = 0.f;
+#pragma unroll
+                for (int rr = 0; rr < RW; ++rr) {
+                    acc += cv_[rr];
+                    st_f32_sbase(mrow + (uint32_t)min(rr, nrows - 1) * (uint32_t)R, 4u * (uint32_t)Ld, mv_[rr]);
+                    const bool last = (lastm >> rr) & 1u;                              // (uniform)
+                    if (last && on) ATOMIC_ADD(pacc + __umul24(rgp[rr], ps), acc);       // (point ids < 2^24: P * 384 < 2^32)
+                    acc = last ? 0.f : acc;
+                }
             }
         }
         PHASE_MARK(4);
