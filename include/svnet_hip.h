@@ -45,9 +45,9 @@ int svnet_slices_sum_f64(double* buf, int64_t L, void* stream);
 
 /* ABI version = 100 * round-of-change + serial.  It changes whenever an entry point gains / loses an argument or a caller-owned buffer
  * changes its required length (200: sliced accumulators, SVNET_SLICED_LEN; 400: this header; 401: the totals of a sliced accumulator are
- * written by its consumer, svnet_slices_sum_*; 402: GX of svnet_v2s_bwd_*, gw of svnet_xyzblock_bwd_f32 and col_sum of svnet_gemm_f32 are sliced accumulators; 403: svnet_binweight_grad_f32 takes sliced inputs; 421: svnet_three_nn_f32, svnet_three_interpolate_f32; 422: svnet_ball_query_f32, svnet_group_points_f32; 423: svnet_vlinear_stats_f32 is gone; 424: svnet_edgeblock_fwd_tier, svnet_edgeblock_bwd_tier, svnet_edgeblock_wgrad_tier, svnet_xyzblock_tier; 425: svnet_pointset_reverse_i32, svnet_three_interpolate_bwd_f32, svnet_group_points_bwd_f32; 426: wbt of svnet_edgeblock_wbt_bf16 is 512 values longer, the all-zero fragment; 427: svnet_ball_query_msg_f32, svnet_group_points_msg_f32, svnet_group_points_msg_bwd_f32; 428: svnet_sa_fold_f32, svnet_sa_fused_f32; 429: svnet_fp_fused_f32, svnet_fp_fused_supported, svnet_fp_fused_rows_tile; 430: svnet_sa_global_f32, svnet_sa_global_supported, svnet_sa_global_rows_tile; 431: svnet_pool_gather_attr_f32, the attribute fields attr, A, attr_vectors, attr_out at the end of svnet_batch_desc; 432: svnet_vn_fold_f32, svnet_vn_tables_f32, svnet_vn_edge_mean_f32, svnet_vn_supported, svnet_vn_workspace_bytes; 433: svnet_vn_point_supported, svnet_vn_point_workspace_bytes, svnet_vn_point_fold_f32, svnet_vn_point_f32, svnet_vn_cloud_mean_f32, svnet_vn_std_pool_supported, svnet_vn_std_pool_workspace_bytes, svnet_vn_std_pool_f32; 434: svnet_vn_edge2_supported, svnet_vn_edge2_mean_f32, svnet_vn_std_coords_supported, svnet_vn_std_coords_f32; 435: svnet_vn_cross_supported, svnet_vn_cross_fold_f32, svnet_vn_edge_cross_mean_f32, svnet_vn_point_norm_supported, svnet_vn_point_norm_fold_f32, svnet_vn_point_norm_f32).  svnet_version() returns the value the
+ * written by its consumer, svnet_slices_sum_*; 402: GX of svnet_v2s_bwd_*, gw of svnet_xyzblock_bwd_f32 and col_sum of svnet_gemm_f32 are sliced accumulators; 403: svnet_binweight_grad_f32 takes sliced inputs; 421: svnet_three_nn_f32, svnet_three_interpolate_f32; 422: svnet_ball_query_f32, svnet_group_points_f32; 423: svnet_vlinear_stats_f32 is gone; 424: svnet_edgeblock_fwd_tier, svnet_edgeblock_bwd_tier, svnet_edgeblock_wgrad_tier, svnet_xyzblock_tier; 425: svnet_pointset_reverse_i32, svnet_three_interpolate_bwd_f32, svnet_group_points_bwd_f32; 426: wbt of svnet_edgeblock_wbt_bf16 is 512 values longer, the all-zero fragment; 427: svnet_ball_query_msg_f32, svnet_group_points_msg_f32, svnet_group_points_msg_bwd_f32; 428: svnet_sa_fold_f32, svnet_sa_fused_f32; 429: svnet_fp_fused_f32, svnet_fp_fused_supported, svnet_fp_fused_rows_tile; 430: svnet_sa_global_f32, svnet_sa_global_supported, svnet_sa_global_rows_tile; 431: svnet_pool_gather_attr_f32, the attribute fields attr, A, attr_vectors, attr_out at the end of svnet_batch_desc; 432: svnet_vn_fold_f32, svnet_vn_tables_f32, svnet_vn_edge_mean_f32, svnet_vn_supported, svnet_vn_workspace_bytes; 433: svnet_vn_point_supported, svnet_vn_point_workspace_bytes, svnet_vn_point_fold_f32, svnet_vn_point_f32, svnet_vn_cloud_mean_f32, svnet_vn_std_pool_supported, svnet_vn_std_pool_workspace_bytes, svnet_vn_std_pool_f32; 434: svnet_vn_edge2_supported, svnet_vn_edge2_mean_f32, svnet_vn_std_coords_supported, svnet_vn_std_coords_f32; 435: svnet_vn_cross_supported, svnet_vn_cross_fold_f32, svnet_vn_edge_cross_mean_f32, svnet_vn_point_norm_supported, svnet_vn_point_norm_fold_f32, svnet_vn_point_norm_f32; 436: svnet_gemm_tier, svnet_gemm_variant).  svnet_version() returns the value the
  * library was BUILT with: a caller compiled against another header must refuse to run (svnet_amd/_lib.py does).                   */
-#define SVNET_ABI_VERSION 435
+#define SVNET_ABI_VERSION 436
 int svnet_version(void);
 const char* svnet_last_error(void);
 
@@ -151,12 +151,45 @@ typedef struct svnet_gemm_desc {
     int split_k;       /* 0 = choose automatically (vector-ALU kernel only) */
     int accumulate;    /* C += result */
     uint32_t tern_tile_mask; /* ternary A only: bit t set = rows [32t, 32t+32) of A^T (output rows i) may be non-zero; 0 = all.
-                                Cleared tiles are skipped: their outputs are left untouched (use with accumulate on zeros)       */
+                                Cleared tiles are skipped: their outputs are left untouched (use with accumulate on zeros).
+                                A partial mask (neither 0 nor all ones) needs M <= 1024.  When it has at most as many live tiles as one
+                                workgroup takes (NQ below) and every live tile has an index of at most 14, the launch is compacted
+                                to one column group over exactly the live tiles; a live tile 15 .. 31 keeps it uncompacted.       */
     void* workspace;   /* optional scratch; with b_exact, >= svnet_gemm_workspace_bytes(N, K) lets the MFMA path pack B once as */
     size_t workspace_bytes; /* bf16 [N][K] (k contiguous) so that its LDS staging is plain 16-byte copies                       */
 } svnet_gemm_desc;
 size_t svnet_gemm_workspace_bytes(int64_t N, int64_t K);
 int svnet_gemm_f32(const svnet_gemm_desc* desc, void* stream);
+/* Which kernel a descriptor runs on.  Both are pure host functions of the descriptor (sizes, strides, options, which pointers are null
+ * and how the non-null ones are aligned; nothing is dereferenced or launched), and svnet_gemm_f32 executes exactly what they report.
+ * A descriptor that svnet_gemm_f32 refuses gives its negative SVNET_E_* code (and the same svnet_last_error) from both.  An empty
+ * product (M == 0 or N == 0) launches nothing and reports SVNET_GEMM_TILE, variant 1.
+ * svnet_gemm_tier: the family.
+ *   SVNET_GEMM_TN_TERN    ternary A planes (weight gradients of the binarized layers): mfma_tn_tern_kernel
+ *   SVNET_GEMM_TN_FP32    a_rs == 1, b_cs == 1, K >= 1024, M, N <= 4096, plain epilogue: mfma_tn2_kernel
+ *   SVNET_GEMM_ROWS       b_exact, a_cs == 1, c_cs == 1, M >= 16, K >= 8: mfma_rows_kernel
+ *   SVNET_GEMM_ROWS_LDS   as ROWS with B packed into the workspace, M >= 4096, N > 128, K >= 64: mfma_rows2_kernel
+ *   SVNET_GEMM_ROWS_SPLIT general B, a_cs == 1, c_cs == 1, M >= 1024, K >= 8, N >= 8, alpha / bias / accumulate only, a workspace of
+ *                         3 x svnet_gemm_workspace_bytes: mfma_rows3_kernel
+ *   SVNET_GEMM_DOT        M * N <= 8192, K >= 128, no mask, no col_sum, split_k <= 1: gemm_dot_kernel
+ *   SVNET_GEMM_TILE       everything else: gemm_kernel on the vector ALUs
+ * svnet_gemm_variant: the template choice inside the family, packed as
+ *   TN_TERN     NQ (1, 2, 4, 5) | ptiles_per_block (1, 2, 4) << 4 | lds_reduce << 8 | compacted tile list << 9
+ *   TN_FP32     IP | JQ << 4                                        (mfma_tn2_kernel<IP, JQ>)
+ *   ROWS        NT (1, 2, 4, 8) | AVEC << 4 | DEEP << 5 | B packed << 6
+ *   ROWS_LDS    1 = aligned float4 A loads, 0 = per-element A loads
+ *   ROWS_SPLIT  NJ (1, 2, 4) | A load width (4, 2, 1) << 4
+ *   DOT         0
+ *   TILE        the number of K splits (1 = no split: plain stores, no zero-fill launch)                                          */
+#define SVNET_GEMM_TN_TERN 1
+#define SVNET_GEMM_TN_FP32 2
+#define SVNET_GEMM_ROWS 3
+#define SVNET_GEMM_ROWS_LDS 4
+#define SVNET_GEMM_ROWS_SPLIT 5
+#define SVNET_GEMM_DOT 6
+#define SVNET_GEMM_TILE 7
+int svnet_gemm_tier(const svnet_gemm_desc* desc);
+int svnet_gemm_variant(const svnet_gemm_desc* desc);
 
 /* ------------------------------------------------------------------ binarized layers (sv_layers.py:20-53 Linear, :55-78 Conv1d)
  * Weight preparation (sign(W) with sign(0)=0, clamp/STE mask |W|<=1.2):

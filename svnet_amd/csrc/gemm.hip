@@ -2,23 +2,23 @@
 //
 // Serves every dense contraction on the path: F.linear of sv_layers.py:31,49 (fp layers, the sign-weight
 // vector linear `linear2`, the gate, the classifier) and the autograd products of their backward.
-// Dispatch (all shapes are tall-and-skinny, i.e. HBM-bound):
+// Dispatch (stated once, in gemm_plan.h: svnet_gemm_tier / svnet_gemm_variant report it; all shapes are tall-and-skinny, i.e. HBM-bound):
 //   * B exact in bf16 (sign weights) and A row-major        -> mfma_rows_kernel   (gemm_mfma.hip)
 //   * reduction over the rows (weight gradients), K >= 1024 -> mfma_tn_kernel     (fp32 or ternary-plane operand)
 //   * everything else (small fp layers, K <= 12 ...)         -> gemm_kernel below: 64x64x16 LDS tiles, 4x4 register
 //     micro-tiles on the vector ALUs, strided operands, split-K with float atomics.
 #include "common.h"
+#include "gemm_plan.h"
 
-int svnet_mfma_rows(const svnet_gemm_desc& d, hipStream_t st);
-int svnet_mfma_rows_split(const svnet_gemm_desc& d, hipStream_t st);
-extern "C" size_t svnet_gemm_workspace_bytes(int64_t N, int64_t K);
+int svnet_mfma_rows(const svnet_gemm_desc& d, const GemmPlan& p, hipStream_t st);
+int svnet_mfma_rows_split(const svnet_gemm_desc& d, const GemmPlan& p, hipStream_t st);
 int svnet_mfma_tn(const float* A, int64_t lda, const float* B, int64_t ldb, const uint64_t* b_sign, const uint64_t* b_nz,
                   int64_t M, int64_t P, int64_t Q, float* C, int64_t c_ps, int64_t c_qs, float alpha, int accumulate,
-                  hipStream_t st, uint32_t q_tile_mask = 0);
+                  hipStream_t st, const GemmPlan& p, uint32_t q_tile_mask = 0);
 
 namespace {
 
-constexpr int BM = 64, BN = 64, BK = 16, PAD = 4;
+constexpr int BM = GEMM_BM, BN = GEMM_BN, BK = GEMM_BK, PAD = 4;
 
 struct GemmArgs {
     svnet_gemm_desc d;
@@ -165,66 +165,52 @@ __global__ void zero_strided_kernel(float* C, int64_t M, int64_t N, int64_t rs, 
 
 }  // namespace
 
+// The dispatch proper is gemm_plan() (gemm_plan.h); this entry executes the plan, the two queries report it.
+extern "C" int svnet_gemm_tier(const svnet_gemm_desc* desc) {
+    GemmPlan p;
+    const int rc = gemm_plan(desc, p);
+    return rc != SVNET_OK ? rc : p.tier;
+}
+extern "C" int svnet_gemm_variant(const svnet_gemm_desc* desc) {
+    GemmPlan p;
+    const int rc = gemm_plan(desc, p);
+    return rc != SVNET_OK ? rc : p.variant;
+}
+
 extern "C" int svnet_gemm_f32(const svnet_gemm_desc* desc, void* stream) {
-    SVNET_REQUIRE(desc, SVNET_E_ARG, "svnet_gemm_f32: null descriptor");
+    GemmPlan p;
+    const int rc = gemm_plan(desc, p);
+    if (rc != SVNET_OK) return rc;
+    if (p.empty) return SVNET_OK;
     const svnet_gemm_desc& d = *desc;
-    SVNET_REQUIRE(d.M >= 0 && d.N >= 0 && d.K >= 0, SVNET_E_ARG, "svnet_gemm_f32: negative size");
-    SVNET_REQUIRE(d.C && d.B && (d.A || d.a_sign), SVNET_E_ARG, "svnet_gemm_f32: null operand");
-    SVNET_REQUIRE(!d.a_sign || d.a_nz, SVNET_E_ARG, "svnet_gemm_f32: ternary A needs both planes");
-    SVNET_REQUIRE(d.c_cs != 0 && d.ldc != 0, SVNET_E_ARG, "svnet_gemm_f32: zero C stride");
-    if (d.M == 0 || d.N == 0) return SVNET_OK;
     hipStream_t st = (hipStream_t)stream;
-    const bool plain_epi = !d.col_scale && !d.bias && !d.mask && !d.col_sum && !d.a_scale;
-
-    // ---- ternary A (row-sliced planes over the reduction index): C(i,j) = sum_k tern(i,k) * B[k*b_rs + j]
-    if (d.a_sign) {
-        SVNET_REQUIRE(d.b_cs == 1 && plain_epi, SVNET_E_UNSUPPORTED, "svnet_gemm_f32: ternary A needs row-major B and a plain epilogue");
-        return svnet_mfma_tn(d.B, d.b_rs, nullptr, 0, d.a_sign, d.a_nz, d.K, /*P=*/d.N, /*Q=*/d.M, d.C, /*c_ps=*/d.c_cs,
-                             /*c_qs=*/d.ldc, d.alpha, d.accumulate, st, d.tern_tile_mask);
-    }
-    // ---- reduction over rows with both operands fp32 rows: A(i,k) = A[k*a_cs + i], B(k,j) = B[k*b_rs + j]
-    if (d.a_rs == 1 && d.b_cs == 1 && d.K >= 1024 && plain_epi && d.M <= 4096 && d.N <= 4096) {
-        return svnet_mfma_tn(d.A, d.a_cs, d.B, d.b_rs, nullptr, nullptr, d.K, /*P=*/d.M, /*Q=*/d.N, d.C, d.ldc, d.c_cs, d.alpha,
-                             d.accumulate, st);
-    }
-    // ---- rows x exact-bf16 weights
-    if (d.b_exact && d.a_cs == 1 && d.c_cs == 1 && d.M >= 16 && d.K >= 8) return svnet_mfma_rows(d, st);
-    // ---- many rows x general fp32 weights: A and B split into three bf16 pieces each, the six leading products on the matrix cores (mfma_rows3_kernel)
-    if (!d.b_exact && d.a_cs == 1 && d.c_cs == 1 && d.M >= 1024 && d.K >= 8 && d.N >= 8 && !d.col_scale && !d.mask && !d.col_sum && !d.a_scale &&
-        d.workspace && d.workspace_bytes >= 3 * svnet_gemm_workspace_bytes(d.N, d.K))
-        return svnet_mfma_rows_split(d, st);
-
-    if (d.M * d.N <= 8192 && d.K >= 128 && !d.mask && !d.col_sum && d.split_k <= 1) {
+    switch (p.tier) {
+    case SVNET_GEMM_TN_TERN:
+        return svnet_mfma_tn(d.B, d.b_rs, nullptr, 0, d.a_sign, d.a_nz, d.K, /*P=*/d.N, /*Q=*/d.M, d.C, /*c_ps=*/d.c_cs, /*c_qs=*/d.ldc, d.alpha,
+                             d.accumulate, st, p, d.tern_tile_mask);
+    case SVNET_GEMM_TN_FP32:
+        return svnet_mfma_tn(d.A, d.a_cs, d.B, d.b_rs, nullptr, nullptr, d.K, /*P=*/d.M, /*Q=*/d.N, d.C, d.ldc, d.c_cs, d.alpha, d.accumulate, st, p);
+    case SVNET_GEMM_ROWS:
+    case SVNET_GEMM_ROWS_LDS:
+        return svnet_mfma_rows(d, p, st);
+    case SVNET_GEMM_ROWS_SPLIT:
+        return svnet_mfma_rows_split(d, p, st);
+    case SVNET_GEMM_DOT:
         hipLaunchKernelGGL(gemm_dot_kernel, dim3((unsigned)svnet_cdiv(d.M * d.N, 4)), dim3(256), 0, st, d);
         SVNET_CHECK_LAUNCH("gemm_dot_kernel");
         return SVNET_OK;
+    default:
+        break;
     }
     GemmArgs ga;
     ga.d = d;
-    const int64_t tiles = svnet_cdiv(d.M, BM) * svnet_cdiv(d.N, BN);
-    int split = d.split_k;
-    if (split <= 0) {
-        split = 1;
-        // few output tiles and a long reduction (the fp classifier head: [32 x 1022] . [1022 x 512] is 8 tiles - as 8 workgroups walking
-        // K in 16-wide steps it took 210 us): K is cut into chunks of >= 64 until ~2048 / tiles workgroups exist
-        if (tiles < 512 && d.K >= 256) {
-            int64_t want = svnet_cdiv(2048, tiles);
-            int64_t maxs = svnet_cdiv(d.K, 64);
-            split = (int)(want < maxs ? want : maxs);
-            if (split < 1) split = 1;
-        }
-    }
-    int64_t chunk = svnet_cdiv(svnet_cdiv(d.K > 0 ? d.K : 1, split), BK) * BK;
-    split = (int)svnet_cdiv(d.K > 0 ? d.K : 1, chunk);
-    ga.k_chunk = chunk;
-    ga.atomic_out = split > 1;
+    ga.k_chunk = p.k_chunk;
+    ga.atomic_out = p.split > 1;
     if (ga.atomic_out && !d.accumulate) {
         hipLaunchKernelGGL(zero_strided_kernel, dim3(svnet_grid(d.M * d.N, 256)), dim3(256), 0, st, d.C, d.M, d.N, d.ldc, d.c_cs);
         SVNET_CHECK_LAUNCH("zero_strided_kernel");
     }
-    SVNET_REQUIRE(svnet_cdiv(d.M, BM) <= 2147483647ll && svnet_cdiv(d.N, BN) <= 65535 && split <= 65535, SVNET_E_UNSUPPORTED,
-                  "svnet_gemm_f32: grid too large");
-    dim3 grid((unsigned)svnet_cdiv(d.M, BM), (unsigned)svnet_cdiv(d.N, BN), (unsigned)split);
+    dim3 grid((unsigned)svnet_cdiv(d.M, BM), (unsigned)svnet_cdiv(d.N, BN), (unsigned)p.split);
     hipLaunchKernelGGL(gemm_kernel, grid, dim3(256), 0, st, ga);
     SVNET_CHECK_LAUNCH("gemm_kernel");
     return SVNET_OK;

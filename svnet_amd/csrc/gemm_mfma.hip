@@ -18,6 +18,7 @@
 // is exactly what the k(=m)-strided MFMA operand and the per-column epilogue mask need.
 #include "bf16_split.h"
 #include "common.h"
+#include "gemm_plan.h"
 
 namespace {
 
@@ -1201,56 +1202,41 @@ void launch_rows_v(const RowsArgs& a, hipStream_t st) {
     (void)ok;                      // (a failed opt-in is in svnet_last_error; the launch below then fails and is reported by the caller's check)
     hipLaunchKernelGGL((mfma_rows_kernel<NT, AVEC, DEEP>), dim3((unsigned)gx, (unsigned)ny), dim3(256), lds, st, a);
 }
-// the LDS-tiled kernel: many rows, aligned A rows with K % 4 == 0, pre-packed B whose padded column count covers whole 256-column groups
-bool rows2_eligible(const RowsArgs& a) {
-    static const bool off = getenv("SVNET_ROWS2_OFF") != nullptr;       // (diagnostic switch)
-    return !(off || !a.B16 || a.K < 64 || a.M < 4096 || a.N <= 128);
-}
-bool rows2_aligned(const RowsArgs& a) {
-    return a.a_vec && (a.K & 3) == 0 && !(a.a_scale && (reinterpret_cast<uintptr_t>(a.a_scale) & 15) != 0);
-}
-bool launch_rows2(const RowsArgs& a, hipStream_t st) {
-    if (!rows2_eligible(a)) return false;
+// the LDS-tiled kernel (SVNET_GEMM_ROWS_LDS): many rows, pre-packed B whose padded column count covers whole 256-column groups; aligned
+// A rows with K % 4 == 0 load as float4s, anything else per element
+void launch_rows2(const RowsArgs& a, bool aligned, hipStream_t st) {
     const size_t lds = (size_t)2 * R2_BUF_BYTES;
     bool ok = true;
     SVNET_LDS_OPTIN(ok, lds, "mfma_rows2_kernel", reinterpret_cast<const void*>(&mfma_rows2_kernel<1, true>),
                     reinterpret_cast<const void*>(&mfma_rows2_kernel<1, false>));
     (void)ok;
     const dim3 grid((unsigned)svnet_cdiv(a.M, R2_BM), (unsigned)svnet_cdiv(a.N, R2_BN));
-    const bool av = rows2_aligned(a);
-    if (av) hipLaunchKernelGGL((mfma_rows2_kernel<1, true>), grid, dim3(256), lds, st, a);
+    if (aligned) hipLaunchKernelGGL((mfma_rows2_kernel<1, true>), grid, dim3(256), lds, st, a);
     else hipLaunchKernelGGL((mfma_rows2_kernel<1, false>), grid, dim3(256), lds, st, a);
-    return true;
 }
 template <int NJ>
-void launch_rows3_nj(const RowsArgs& a, hipStream_t st) {
+void launch_rows3_nj(const RowsArgs& a, int w, hipStream_t st) {
     const size_t lds = (size_t)R3_A_BYTES + 2 * (size_t)(64 * NJ) * R2_LDB * 2;
     bool ok = true;
     SVNET_LDS_OPTIN(ok, lds, "mfma_rows3_kernel", reinterpret_cast<const void*>(&mfma_rows3_kernel<NJ, 4>), reinterpret_cast<const void*>(&mfma_rows3_kernel<NJ, 2>),
                     reinterpret_cast<const void*>(&mfma_rows3_kernel<NJ, 1>));
     (void)ok;
     const dim3 grid((unsigned)svnet_cdiv(a.M, R2_BM), (unsigned)svnet_cdiv(a.N, 64 * NJ));
-    const uintptr_t ap = reinterpret_cast<uintptr_t>(a.A);
-    if ((ap & 15) == 0 && (a.lda & 3) == 0 && (a.K & 3) == 0) hipLaunchKernelGGL((mfma_rows3_kernel<NJ, 4>), grid, dim3(256), lds, st, a);
-    else if ((ap & 7) == 0 && (a.lda & 1) == 0 && (a.K & 1) == 0) hipLaunchKernelGGL((mfma_rows3_kernel<NJ, 2>), grid, dim3(256), lds, st, a);
+    if (w == 4) hipLaunchKernelGGL((mfma_rows3_kernel<NJ, 4>), grid, dim3(256), lds, st, a);
+    else if (w == 2) hipLaunchKernelGGL((mfma_rows3_kernel<NJ, 2>), grid, dim3(256), lds, st, a);
     else hipLaunchKernelGGL((mfma_rows3_kernel<NJ, 1>), grid, dim3(256), lds, st, a);
 }
 // general fp32 B (three packed pieces, a.b_piece apart), any K >= 1 / N >= 1, plain / alpha / bias / accumulate epilogue
-void launch_rows3(const RowsArgs& a, hipStream_t st) {
-    if (a.N <= 64) launch_rows3_nj<1>(a, st);
-    else if (a.N <= 128) launch_rows3_nj<2>(a, st);
-    else launch_rows3_nj<4>(a, st);
+void launch_rows3(const RowsArgs& a, const GemmPlan& p, hipStream_t st) {
+    if (p.nj == 1) launch_rows3_nj<1>(a, p.w, st);
+    else if (p.nj == 2) launch_rows3_nj<2>(a, p.w, st);
+    else launch_rows3_nj<4>(a, p.w, st);
 }
 template <int NT>
-void launch_rows(const RowsArgs& a, hipStream_t st) {
-    if (NT == 8 && launch_rows2(a, st)) return;
-    const bool vec = a.a_vec && a.K >= 8 && (a.K & 7) == 0;
-    if (a.K > 64) { if (vec) launch_rows_v<NT, true, true>(a, st); else launch_rows_v<NT, false, true>(a, st); }
-    else { if (vec) launch_rows_v<NT, true, false>(a, st); else launch_rows_v<NT, false, false>(a, st); }
+void launch_rows(const RowsArgs& a, const GemmPlan& p, hipStream_t st) {
+    if (p.deep) { if (p.avec) launch_rows_v<NT, true, true>(a, st); else launch_rows_v<NT, false, true>(a, st); }
+    else { if (p.avec) launch_rows_v<NT, true, false>(a, st); else launch_rows_v<NT, false, false>(a, st); }
 }
-// columns per workgroup (NT * 32) of the rows kernels.  Few row blocks (the classifier head: M = batch): narrow column tiles so that the
-// grid still has tens of workgroups
-int rows_cpb(int64_t M, int64_t N) { return (N <= 32 || M <= 512) ? 32 : (N <= 64 ? 64 : (N <= 128 ? 128 : 256)); }
 
 template <int IP, int JQ>
 void launch_tn2(TnArgs a, hipStream_t st) {
@@ -1263,19 +1249,11 @@ void launch_tn2(TnArgs a, hipStream_t st) {
                        dim3(256), 0, st, a);
 }
 template <int NQ>
-void launch_tn_tern(TnArgs a, hipStream_t st) {
-    // (a partial tile mask names tiles 0..31 only: svnet_mfma_tn refuses one for Q > 1024)
+void launch_tn_tern(TnArgs a, const TernPlan& tp, hipStream_t st) {
     const int ptiles = (int)svnet_cdiv(a.P, 32);
-    a.ptiles_per_block = ptiles >= 3 ? 4 : ptiles;
-    int gz = (int)svnet_cdiv(a.Q, NQ * 32);
-    a.qlist = 0;
-    if (a.qmask != 0xFFFFFFFFu) {   // few tiles in use: one z group over exactly those (the A split is then shared)
-        int used = 0;
-        uint32_t list = 0;
-        for (int t = 0; t < 15 && t * 32 < a.Q; ++t)
-            if ((a.qmask >> t) & 1u) { if (used < 8) list |= (uint32_t)(t + 1) << (4 * used); ++used; }
-        if (used > 0 && used <= NQ) { a.qlist = list; gz = 1; }
-    }
+    a.ptiles_per_block = tp.ptiles_per_block;
+    a.qlist = tp.qlist;             // compacted: one z group over exactly the live tiles (tern_plan, gemm_plan.h)
+    const int gz = tp.qlist ? 1 : (int)svnet_cdiv(a.Q, NQ * 32);
     const int gy = (int)svnet_cdiv(ptiles, a.ptiles_per_block);
     // exactly one resident round (2 workgroups per CU): every row split ends in P*Q float atomics, which the memory side executes at
     // ~1 TB/s (conv5's 512 x 505 gradient spent half its time there with 128 splits)
@@ -1286,7 +1264,7 @@ void launch_tn_tern(TnArgs a, hipStream_t st) {
     const int64_t gx = svnet_cdiv(a.M, rpb);
     const int nsub = 4 / a.ptiles_per_block;
     const size_t lds = (size_t)(nsub - 1) * a.ptiles_per_block * NQ * 1024 * sizeof(float);
-    a.lds_reduce = (nsub > 1 && ptiles == a.ptiles_per_block && lds <= 64 * 1024) ? 1 : 0;
+    a.lds_reduce = tp.lds_reduce;
     bool ok = true;                     // 8 KiB of static tables + up to 64 KiB of dynamic LDS: above the 64 KiB default
     SVNET_LDS_OPTIN(ok, 64 * 1024, "mfma_tn_tern_kernel", reinterpret_cast<const void*>(&mfma_tn_tern_kernel<NQ, false>),
                     reinterpret_cast<const void*>(&mfma_tn_tern_kernel<NQ, true>));
@@ -1306,8 +1284,7 @@ extern "C" size_t svnet_gemm_workspace_bytes(int64_t N, int64_t K) {
 }
 
 // Internal entry points used by svnet_gemm_f32 (gemm.hip).
-int svnet_mfma_rows(const svnet_gemm_desc& d, hipStream_t st) {
-    SVNET_REQUIRE(d.a_rs < ((int64_t)1 << 24), SVNET_E_UNSUPPORTED, "svnet_mfma_rows: A row stride %lld >= 2^24 (32-bit tile offsets)", (long long)d.a_rs);
+int svnet_mfma_rows(const svnet_gemm_desc& d, const GemmPlan& p, hipStream_t st) {
     RowsArgs a;
     a.A = d.A; a.lda = d.a_rs; a.a_scale = d.a_scale;
     a.B = d.B; a.b_rs = d.b_rs; a.b_cs = d.b_cs;
@@ -1315,10 +1292,10 @@ int svnet_mfma_rows(const svnet_gemm_desc& d, hipStream_t st) {
     a.M = d.M; a.N = (int)d.N; a.K = (int)d.K;
     a.alpha = d.alpha; a.col_scale = d.col_scale; a.bias = d.bias;
     a.mask = d.mask; a.col_sum = d.col_sum; a.accumulate = d.accumulate;
-    a.a_vec = (d.a_rs % 4 == 0) && (reinterpret_cast<uintptr_t>(d.A) % 16 == 0);
+    a.a_vec = p.a_vec;
     a.B16 = nullptr; a.Kp = 0; a.b_piece = 0;
-    const int cpb = rows_cpb(d.M, d.N);
-    if (d.workspace && d.workspace_bytes >= svnet_gemm_workspace_bytes(d.N, d.K) && reinterpret_cast<uintptr_t>(d.workspace) % 16 == 0) {
+    const int cpb = p.cpb;
+    if (p.packed) {
         const int Kp = (int)((d.K + 15) / 16 * 16), Np = (int)((d.N + cpb - 1) / cpb * cpb);
         uint16_t* w = reinterpret_cast<uint16_t*>(d.workspace);
         hipLaunchKernelGGL(pack_b_bf16_kernel, dim3(svnet_grid((int64_t)Kp * Np, 256)), dim3(256), 0, st, d.B, d.b_rs, d.b_cs, (int)d.K,
@@ -1326,10 +1303,11 @@ int svnet_mfma_rows(const svnet_gemm_desc& d, hipStream_t st) {
         SVNET_CHECK_LAUNCH("pack_b_bf16_kernel");
         a.B16 = w; a.Kp = Kp;
     }
-    if (cpb == 32) launch_rows<1>(a, st);
-    else if (cpb == 64) launch_rows<2>(a, st);
-    else if (cpb == 128) launch_rows<4>(a, st);
-    else launch_rows<8>(a, st);
+    if (p.tier == SVNET_GEMM_ROWS_LDS) launch_rows2(a, p.lds_aligned, st);
+    else if (cpb == 32) launch_rows<1>(a, p, st);
+    else if (cpb == 64) launch_rows<2>(a, p, st);
+    else if (cpb == 128) launch_rows<4>(a, p, st);
+    else launch_rows<8>(a, p, st);
     SVNET_CHECK_LAUNCH("mfma_rows_kernel");
     return SVNET_OK;
 }
@@ -1340,13 +1318,9 @@ int svnet_mfma_rows(const svnet_gemm_desc& d, hipStream_t st) {
 // ones are below 2^-24 of the product), fp32 accumulation: fp32-GEMM accuracy (tests: 2e-6 of the largest output against float64).
 // On the bf16 matrix cores six passes cost 6/16 of ONE f32-input MFMA pass.
 // Epilogue terms that are not linear in B (column scale, mask, column sums, per-k scale) are not taken here (checked by the caller).
-int svnet_mfma_rows_split(const svnet_gemm_desc& d, hipStream_t st) {
+// (the plan has checked the workspace - 3 x svnet_gemm_workspace_bytes, 16-byte aligned - and the A row stride)
+int svnet_mfma_rows_split(const svnet_gemm_desc& d, const GemmPlan& p, hipStream_t st) {
     const size_t one = svnet_gemm_workspace_bytes(d.N, d.K);
-    SVNET_REQUIRE(d.workspace && d.workspace_bytes >= 3 * one && reinterpret_cast<uintptr_t>(d.workspace) % 16 == 0 && one % 16 == 0, SVNET_E_WORKSPACE,
-                  "svnet_mfma_rows_split: needs 3 x svnet_gemm_workspace_bytes of 16-byte aligned workspace");
-    SVNET_REQUIRE(!d.col_scale && !d.mask && !d.col_sum && !d.a_scale, SVNET_E_UNSUPPORTED, "svnet_mfma_rows_split: plain or bias epilogue only");
-    SVNET_REQUIRE(d.M >= 1024, SVNET_E_UNSUPPORTED, "svnet_mfma_rows_split: M = %lld < 1024", (long long)d.M);
-    SVNET_REQUIRE(d.a_rs < ((int64_t)1 << 24), SVNET_E_UNSUPPORTED, "svnet_mfma_rows_split: A row stride %lld >= 2^24", (long long)d.a_rs);
     RowsArgs a;
     a.A = d.A; a.lda = d.a_rs; a.a_scale = nullptr;
     a.B = d.B; a.b_rs = d.b_rs; a.b_cs = d.b_cs;
@@ -1354,8 +1328,8 @@ int svnet_mfma_rows_split(const svnet_gemm_desc& d, hipStream_t st) {
     a.M = d.M; a.N = (int)d.N; a.K = (int)d.K;
     a.alpha = d.alpha; a.col_scale = nullptr; a.bias = d.bias;
     a.mask = nullptr; a.col_sum = nullptr;
-    a.a_vec = (d.a_rs % 4 == 0) && (reinterpret_cast<uintptr_t>(d.A) % 16 == 0);
-    const int cpb = rows_cpb(d.M, d.N);
+    a.a_vec = p.a_vec;
+    const int cpb = p.cpb;
     const int Kp = (int)((d.K + 15) / 16 * 16), Np = (int)((d.N + cpb - 1) / cpb * cpb);
     a.Kp = Kp;
     hipLaunchKernelGGL(pack_b_bf16_kernel, dim3(svnet_grid((int64_t)Kp * Np, 256)), dim3(256), 0, st, d.B, d.b_rs, d.b_cs, (int)d.K, (int)d.N, Kp, Np,
@@ -1364,7 +1338,7 @@ int svnet_mfma_rows_split(const svnet_gemm_desc& d, hipStream_t st) {
     a.B16 = reinterpret_cast<uint16_t*>(d.workspace);
     a.accumulate = d.accumulate;
     a.b_piece = (int64_t)(one / 2);
-    launch_rows3(a, st);                                                  // A split once per element, one launch
+    launch_rows3(a, p, st);                                               // A split once per element, one launch
     SVNET_CHECK_LAUNCH("mfma_rows3_kernel");
     return SVNET_OK;
 }
@@ -1372,9 +1346,8 @@ int svnet_mfma_rows_split(const svnet_gemm_desc& d, hipStream_t st) {
 // out(p,q) = alpha * sum_m A[m*lda+p] * B(m,q); B fp32 rows (ldb) or row-sliced ternary planes.
 int svnet_mfma_tn(const float* A, int64_t lda, const float* B, int64_t ldb, const uint64_t* b_sign, const uint64_t* b_nz,
                   int64_t M, int64_t P, int64_t Q, float* C, int64_t c_ps, int64_t c_qs, float alpha, int accumulate,
-                  hipStream_t st, uint32_t q_tile_mask) {
-    SVNET_REQUIRE(q_tile_mask == 0 || q_tile_mask == 0xFFFFFFFFu || Q <= 1024, SVNET_E_UNSUPPORTED,
-                  "svnet_mfma_tn: a partial column-tile mask needs Q <= 1024 (got %lld)", (long long)Q);
+                  hipStream_t st, const GemmPlan& p, uint32_t q_tile_mask) {
+    // (a partial tile mask names tiles 0..31 only: the plan refuses one for Q > 1024)
     if (!accumulate) {
         hipLaunchKernelGGL(zero2d_kernel, dim3(svnet_grid(P * Q, 256)), dim3(256), 0, st, C, P, Q, c_ps, c_qs);
         SVNET_CHECK_LAUNCH("zero2d_kernel");
@@ -1386,23 +1359,19 @@ int svnet_mfma_tn(const float* A, int64_t lda, const float* B, int64_t ldb, cons
     a.qmask = q_tile_mask ? q_tile_mask : 0xFFFFFFFFu;
     a.n16 = nullptr; a.gy = nullptr; a.smax = a.smin = nullptr; a.chc = nullptr; a.kk = 1; a.kmagic = 0; a.npts = 0;
     if (!b_sign) {                                                      // fp32 x fp32: the LDS-tiled kernel
-        // the largest tile that still leaves >= 32 tiles: every row split adds one float atomic per output element, and with few tiles
-        // the grid is filled by row splits ([512 x 127] as four 128 x 128 tiles: 128 splits, 50 of its 82 us in the atomics)
-        auto tiles = [&](int ip, int jq) { return svnet_cdiv(P, 64 * ip) * svnet_cdiv(Q, 64 * jq); };
-        if (P > 64 && Q > 64 && tiles(2, 2) >= 32) launch_tn2<2, 2>(a, st);
-        else if (P > 64 && (Q <= 64 || P >= Q) && tiles(2, 1) >= 32) launch_tn2<2, 1>(a, st);
-        else if (Q > 64 && tiles(1, 2) >= 32) launch_tn2<1, 2>(a, st);
-        else if (P > 64 && tiles(2, 1) >= 32) launch_tn2<2, 1>(a, st);
+        if (p.ip == 2 && p.jq == 2) launch_tn2<2, 2>(a, st);
+        else if (p.ip == 2) launch_tn2<2, 1>(a, st);
+        else if (p.jq == 2) launch_tn2<1, 2>(a, st);
         else launch_tn2<1, 1>(a, st);
         SVNET_CHECK_LAUNCH("mfma_tn2_kernel");
         return SVNET_OK;
     }
     // ternary B.  Past 128 columns: 160-column groups - the 5-tile kernel keeps a whole block of A and the next plane words in flight
     // (8 tiles: 255 VGPRs, neither), worth more than the extra L2 reads of A (conv5: -60 us per step)
-    if (Q <= 32) launch_tn_tern<1>(a, st);
-    else if (Q <= 64) launch_tn_tern<2>(a, st);
-    else if (Q <= 128) launch_tn_tern<4>(a, st);
-    else launch_tn_tern<5>(a, st);
+    if (p.tern.nq == 1) launch_tn_tern<1>(a, p.tern, st);
+    else if (p.tern.nq == 2) launch_tn_tern<2>(a, p.tern, st);
+    else if (p.tern.nq == 4) launch_tn_tern<4>(a, p.tern, st);
+    else launch_tn_tern<5>(a, p.tern, st);
     SVNET_CHECK_LAUNCH("mfma_tn_tern_kernel");
     return SVNET_OK;
 }
@@ -1449,7 +1418,7 @@ extern "C" int svnet_edgeblock_wgrad_f32(const int16_t* n16, const uint8_t* slot
         SVNET_CHECK_LAUNCH("mfma_tn_aff2_kernel");
         return SVNET_OK;
     }
-    launch_tn_tern<5>(a, st);
+    launch_tn_tern<5>(a, tern_plan(a.P, a.Q, a.qmask), st);          // (Q = 320: five tiles per workgroup)
     SVNET_CHECK_LAUNCH("mfma_tn_tern_kernel (affine)");
     return SVNET_OK;
 }

@@ -120,6 +120,10 @@ def test_spot_pins_of_the_derived_tables():
     assert S["svnet_last_error"] == (ctypes.c_char_p, [])
     assert S["svnet_knn_workspace_bytes"][0] is ctypes.c_size_t
     assert S["svnet_gemm_f32"][1] == [ctypes.POINTER(_lib.GemmDesc), _lib.c_p]
+    for query in ("svnet_gemm_tier", "svnet_gemm_variant"):                          # the dispatch queries take the descriptor alone
+        assert S[query] == (_lib.c_int, [ctypes.POINTER(_lib.GemmDesc)])
+    assert [D["SVNET_GEMM_" + n] for n in ("TN_TERN", "TN_FP32", "ROWS", "ROWS_LDS", "ROWS_SPLIT", "DOT", "TILE")] == [1, 2, 3, 4, 5, 6, 7]
+    assert D["SVNET_ABI_VERSION"] >= 436
     assert dict(_lib.BlockTailDesc._fields_)["gate"] is _lib.GateFwdJob and isinstance(_lib.BlockTailDesc().gate, _lib.GateFwdJob)
     assert dict(_lib.BinHeadDesc._fields_)["nbt"] is _lib.c_p                        # `long long* nbt` is a pointer
     assert D["SVNET_E_UNSUPPORTED"] == -2

@@ -1,6 +1,6 @@
 """Which products of a workload's train step go through svnet_gemm_f32, on which path, and how long they take (diagnostic).
 usage: python tools/gemm_shapes.py pointnet_fp|pointnet_bin|dgcnn_cls|partseg"""
-import argparse, collections, contextlib, io, os, sys
+import argparse, collections, contextlib, ctypes, io, os, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench
@@ -23,20 +23,13 @@ else:
     inputs, y, loss_fn = (x,), torch.from_numpy(synth.class_labels(1234, 0, 0, B)).to(dev), cal_loss
 
 
+TIER_NAMES = {v: k[len("SVNET_GEMM_"):].lower() for k, v in _lib.DEFINES.items() if k.startswith("SVNET_GEMM_")}
+
+
 def path_of(d):
-    plain = not (d.col_scale or d.bias or d.mask or d.col_sum or d.a_scale)
-    if d.a_sign:
-        return "tn_tern"
-    if d.a_rs == 1 and d.b_cs == 1 and d.K >= 1024 and plain and d.M <= 4096 and d.N <= 4096:
-        return "tn"
-    if d.b_exact and d.a_cs == 1 and d.c_cs == 1 and d.M >= 16 and d.K >= 8:
-        return "rows"
-    if (not d.b_exact and d.a_cs == 1 and d.c_cs == 1 and d.M >= 1024 and d.K >= 8 and d.N >= 8 and not (d.col_scale or d.mask or d.col_sum or d.a_scale)
-            and d.workspace and d.workspace_bytes):
-        return "rows_split"
-    if d.M * d.N <= 8192 and d.K >= 128 and not d.mask and not d.col_sum and d.split_k <= 1:
-        return "dot"
-    return "gemm_kernel"
+    """family/variant as the library's own queries name them (svnet_gemm_tier, svnet_gemm_variant: the dispatch is stated once)."""
+    L = _lib.lib()
+    return "%s/%d" % (TIER_NAMES.get(L.svnet_gemm_tier(ctypes.byref(d)), "refused"), L.svnet_gemm_variant(ctypes.byref(d)))
 
 
 keys = []
