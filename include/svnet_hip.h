@@ -45,9 +45,9 @@ int svnet_slices_sum_f64(double* buf, int64_t L, void* stream);
 
 /* ABI version = 100 * round-of-change + serial.  It changes whenever an entry point gains / loses an argument or a caller-owned buffer
  * changes its required length (200: sliced accumulators, SVNET_SLICED_LEN; 400: this header; 401: the totals of a sliced accumulator are
- * written by its consumer, svnet_slices_sum_*; 402: GX of svnet_v2s_bwd_*, gw of svnet_xyzblock_bwd_f32 and col_sum of svnet_gemm_f32 are sliced accumulators; 403: svnet_binweight_grad_f32 takes sliced inputs; 421: svnet_three_nn_f32, svnet_three_interpolate_f32; 422: svnet_ball_query_f32, svnet_group_points_f32; 423: svnet_vlinear_stats_f32 is gone; 424: svnet_edgeblock_fwd_tier, svnet_edgeblock_bwd_tier, svnet_edgeblock_wgrad_tier, svnet_xyzblock_tier; 425: svnet_pointset_reverse_i32, svnet_three_interpolate_bwd_f32, svnet_group_points_bwd_f32; 426: wbt of svnet_edgeblock_wbt_bf16 is 512 values longer, the all-zero fragment; 427: svnet_ball_query_msg_f32, svnet_group_points_msg_f32, svnet_group_points_msg_bwd_f32; 428: svnet_sa_fold_f32, svnet_sa_fused_f32; 429: svnet_fp_fused_f32, svnet_fp_fused_supported, svnet_fp_fused_rows_tile; 430: svnet_sa_global_f32, svnet_sa_global_supported, svnet_sa_global_rows_tile; 431: svnet_pool_gather_attr_f32, the attribute fields attr, A, attr_vectors, attr_out at the end of svnet_batch_desc; 432: svnet_vn_fold_f32, svnet_vn_tables_f32, svnet_vn_edge_mean_f32, svnet_vn_supported, svnet_vn_workspace_bytes; 433: svnet_vn_point_supported, svnet_vn_point_workspace_bytes, svnet_vn_point_fold_f32, svnet_vn_point_f32, svnet_vn_cloud_mean_f32, svnet_vn_std_pool_supported, svnet_vn_std_pool_workspace_bytes, svnet_vn_std_pool_f32; 434: svnet_vn_edge2_supported, svnet_vn_edge2_mean_f32, svnet_vn_std_coords_supported, svnet_vn_std_coords_f32; 435: svnet_vn_cross_supported, svnet_vn_cross_fold_f32, svnet_vn_edge_cross_mean_f32, svnet_vn_point_norm_supported, svnet_vn_point_norm_fold_f32, svnet_vn_point_norm_f32; 436: svnet_gemm_tier, svnet_gemm_variant).  svnet_version() returns the value the
+ * written by its consumer, svnet_slices_sum_*; 402: GX of svnet_v2s_bwd_*, gw of svnet_xyzblock_bwd_f32 and col_sum of svnet_gemm_f32 are sliced accumulators; 403: svnet_binweight_grad_f32 takes sliced inputs; 421: svnet_three_nn_f32, svnet_three_interpolate_f32; 422: svnet_ball_query_f32, svnet_group_points_f32; 423: svnet_vlinear_stats_f32 is gone; 424: svnet_edgeblock_fwd_tier, svnet_edgeblock_bwd_tier, svnet_edgeblock_wgrad_tier, svnet_xyzblock_tier; 425: svnet_pointset_reverse_i32, svnet_three_interpolate_bwd_f32, svnet_group_points_bwd_f32; 426: wbt of svnet_edgeblock_wbt_bf16 is 512 values longer, the all-zero fragment; 427: svnet_ball_query_msg_f32, svnet_group_points_msg_f32, svnet_group_points_msg_bwd_f32; 428: svnet_sa_fold_f32, svnet_sa_fused_f32; 429: svnet_fp_fused_f32, svnet_fp_fused_supported, svnet_fp_fused_rows_tile; 430: svnet_sa_global_f32, svnet_sa_global_supported, svnet_sa_global_rows_tile; 431: svnet_pool_gather_attr_f32, the attribute fields attr, A, attr_vectors, attr_out at the end of svnet_batch_desc; 432: svnet_vn_fold_f32, svnet_vn_tables_f32, svnet_vn_edge_mean_f32, svnet_vn_supported, svnet_vn_workspace_bytes; 433: svnet_vn_point_supported, svnet_vn_point_workspace_bytes, svnet_vn_point_fold_f32, svnet_vn_point_f32, svnet_vn_cloud_mean_f32, svnet_vn_std_pool_supported, svnet_vn_std_pool_workspace_bytes, svnet_vn_std_pool_f32; 434: svnet_vn_edge2_supported, svnet_vn_edge2_mean_f32, svnet_vn_std_coords_supported, svnet_vn_std_coords_f32; 435: svnet_vn_cross_supported, svnet_vn_cross_fold_f32, svnet_vn_edge_cross_mean_f32, svnet_vn_point_norm_supported, svnet_vn_point_norm_fold_f32, svnet_vn_point_norm_f32; 436: svnet_gemm_tier, svnet_gemm_variant; 437: svnet_vn_point_wide_supported, svnet_vn_point_wide_workspace_bytes, svnet_vn_point_wide_fold_f32, svnet_vn_point_wide_f32, svnet_vn_point_norm_wide_supported, svnet_vn_point_norm_wide_fold_f32, svnet_vn_point_norm_wide_f32, svnet_vn_cloud_mean_wide_f32, svnet_vn_std_pool_wide_supported, svnet_vn_std_pool_wide_workspace_bytes, svnet_vn_std_pool_wide_f32, svnet_vn_std_coords_wide_supported, svnet_vn_std_coords_wide_f32).  svnet_version() returns the value the
  * library was BUILT with: a caller compiled against another header must refuse to run (svnet_amd/_lib.py does).                   */
-#define SVNET_ABI_VERSION 436
+#define SVNET_ABI_VERSION 437
 int svnet_version(void);
 const char* svnet_last_error(void);
 
@@ -1169,6 +1169,36 @@ int svnet_vn_point_norm_supported(int64_t N, int64_t C, int64_t O);
 int svnet_vn_point_norm_fold_f32(const float* w_feat, const float* gamma, const float* beta, const float* running_mean, const float* running_var,
                                  int64_t C, int64_t O, float eps, float* folded, void* stream);
 int svnet_vn_point_norm_f32(const float* x, const float* folded, int64_t B, int64_t N, int64_t C, int64_t O, float* out, void* stream);
+
+/* ------------------------------------------------------------------ the wide envelope of the vector-neuron tail (models/vn_pointnet_partseg.py:
+ * conv5 + bn5 170 -> 682, std_feature over 682 + 682 channels).  THE NAMING RULE: every entry of the three sections above that begins
+ * svnet_vn_point_, svnet_vn_point_norm_, svnet_vn_cloud_mean_, svnet_vn_std_pool_ or svnet_vn_std_coords_ has a twin whose name carries
+ * _wide behind that stem: svnet_vn_point_wide_f32, svnet_vn_point_norm_wide_fold_f32, svnet_vn_std_pool_wide_workspace_bytes ...  A twin has
+ * its entry's arguments, buffers, contract (cloud term first, c ascending, K never split, runs of 64, the norm and leaky rules), launches
+ * and errors, word for word, and one other envelope, shared by all of them:
+ *     1 <= C, O, Cy <= 768, 0 <= Cg <= 768, 1 <= N <= 32768, 1 <= B <= 65535, Od = O or 1.
+ * The workspace formulas are the entries' own: svnet_vn_point_wide_workspace_bytes = 3 B (O + Od) floats in bytes with Cg > 0, else 0;
+ * svnet_vn_std_pool_wide_workspace_bytes = 2 ceil(N / 64) B 3 (C + Cg) floats in bytes; 0 outside the wide limits.
+ * Inside the base envelope a twin runs the kernel its entry runs and returns its bits; the base entries keep refusing 513.  Above 512
+ * channels the point kernel holds one image of x at 16 points per workgroup (4 x 48 C bytes of LDS: 131 KB at 682, 144 KB at 768).      */
+int svnet_vn_point_wide_supported(int64_t N, int64_t C, int64_t Cg, int64_t O, int64_t Od);
+size_t svnet_vn_point_wide_workspace_bytes(int64_t B, int64_t Cg, int64_t O, int64_t Od);
+int svnet_vn_point_wide_fold_f32(const float* w_feat, const float* w_dir, const float* gamma, const float* beta, const float* running_mean,
+                                 const float* running_var, int64_t C, int64_t Cg, int64_t O, int64_t Od, float eps, float* folded, void* stream);
+int svnet_vn_point_wide_f32(const float* x, const float* g, const float* folded, int64_t B, int64_t N, int64_t C, int64_t Cg, int64_t O, int64_t Od,
+                            float slope, void* workspace, size_t workspace_bytes, float* out, void* stream);
+int svnet_vn_point_norm_wide_supported(int64_t N, int64_t C, int64_t O);
+int svnet_vn_point_norm_wide_fold_f32(const float* w_feat, const float* gamma, const float* beta, const float* running_mean, const float* running_var,
+                                      int64_t C, int64_t O, float eps, float* folded, void* stream);
+int svnet_vn_point_norm_wide_f32(const float* x, const float* folded, int64_t B, int64_t N, int64_t C, int64_t O, float* out, void* stream);
+int svnet_vn_cloud_mean_wide_f32(const float* x, int64_t B, int64_t C, int64_t N, float* m, void* stream);
+int svnet_vn_std_pool_wide_supported(int64_t N, int64_t C, int64_t Cg, int64_t Cy);
+size_t svnet_vn_std_pool_wide_workspace_bytes(int64_t B, int64_t N, int64_t C, int64_t Cg);
+int svnet_vn_std_pool_wide_f32(const float* x, const float* g, const float* y, const float* w_lin, int64_t B, int64_t N, int64_t C, int64_t Cg,
+                               int64_t Cy, void* workspace, size_t workspace_bytes, float* h, void* stream);
+int svnet_vn_std_coords_wide_supported(int64_t N, int64_t C, int64_t Cy);
+int svnet_vn_std_coords_wide_f32(const float* x, const float* y, const float* w_lin, int64_t B, int64_t N, int64_t C, int64_t Cy, float* e,
+                                 void* stream);
 
 /* ------------------------------------------------------------------ epoch metrics (main_cls_dgcnn.py:187-251, main_partseg_dgcnn.py:185-279,
  * utils.py:68-91 calculate_shape_IoU; the accuracy scores of sklearn.metrics are functions of the confusion matrix)

@@ -23,6 +23,9 @@
 //   vn_std_coords_kernel   grid (runs, B): the same frame rows, then the coordinates of every channel of x per point, unpooled, stored
 //                          along n: what VN_DGCNN_PSEG's head reads of the levels' features.  The frame rows and the coordinates are
 //                          stated once (vt_stage_frame, vt_coordinate) and both kernels call them.
+// Every entry exists twice: in the base envelope (widths to 512) and, named svnet_vn_*_wide_*, in the wide one (widths to 768:
+// VN_PointNet_PSEG's 682).  The kernels are the same and so is the plan: above 426 channels the image of x at NPT 1 is more than half of LDS, so one
+// workgroup has the CU to itself and staging does not overlap the products; at 768 it is 144 KiB (VtEnvelope).
 // The fold of the statistics and the norm / BatchNorm / leaky arithmetic are vn_math.h's, shared with vn_edge.hip.  Built with
 // -ffp-contract=off (Makefile, NO_CONTRACT).  No atomics.
 #include "vn_math.h"
@@ -34,7 +37,12 @@ namespace {
 typedef __attribute__((ext_vector_type(4))) float vt_f32x4;
 
 constexpr int VT_THREADS = 256, VT_WAVES = VT_THREADS / SVNET_WAVE;
-constexpr int VT_MAX_C = 512, VT_MAX_O = 512, VT_MAX_B = 65535;      // the envelope
+constexpr int VT_MAX_B = 65535;
+// The envelope of an entry: the widest C, Cg and Cy and the widest O it admits.  The kernels are written for any width whose image fits
+// LDS; what an entry admits is what its tests pin.  VT_BASE is the entries' of ABI 433 to 435, VT_WIDE the svnet_vn_*_wide_* entries':
+// at NPT 1 the image of 768 channels is 4 x 768 x 48 = 147456 bytes (+ 192 with one direction row), under VT_LDS_MAX.
+struct VtEnvelope { int max_c, max_o; };
+constexpr VtEnvelope VT_BASE{512, 512}, VT_WIDE{768, 768};
 constexpr int VT_RUN = 64;              // points per run of the ordered sums: part of the contract
 constexpr int VT_LDS_MAX = 160 * 1024;
 constexpr int VT_SLAB = 64;             // channels per LDS slab of the std-pool kernel
@@ -42,11 +50,11 @@ constexpr int VT_VS = 3 * VT_RUN + 1;   // floats per channel of a slab: odd, so
 constexpr int VT_SU = 8;                // loads of a thread in flight while x is staged
 constexpr int VT_U = 8;                 // k-steps whose weights a lane holds at a time: 32 channels
 
-inline bool vt_point_ok(int64_t N, int64_t C, int64_t Cg, int64_t O, int64_t Od) {
-    return N >= 1 && N <= VN_MAX_N && C >= 1 && C <= VT_MAX_C && Cg >= 0 && Cg <= VT_MAX_C && O >= 1 && O <= VT_MAX_O && vn_dir_rows_ok(O, Od);
+inline bool vt_point_ok(const VtEnvelope& v, int64_t N, int64_t C, int64_t Cg, int64_t O, int64_t Od) {
+    return N >= 1 && N <= VN_MAX_N && C >= 1 && C <= v.max_c && Cg >= 0 && Cg <= v.max_c && O >= 1 && O <= v.max_o && vn_dir_rows_ok(O, Od);
 }
-inline bool vt_std_ok(int64_t N, int64_t C, int64_t Cg, int64_t Cy) {
-    return N >= 1 && N <= VN_MAX_N && C >= 1 && C <= VT_MAX_C && Cg >= 0 && Cg <= VT_MAX_C && Cy >= 1 && Cy <= VT_MAX_C;
+inline bool vt_std_ok(const VtEnvelope& v, int64_t N, int64_t C, int64_t Cg, int64_t Cy) {
+    return N >= 1 && N <= VN_MAX_N && C >= 1 && C <= v.max_c && Cg >= 0 && Cg <= v.max_c && Cy >= 1 && Cy <= v.max_c;
 }
 inline bool vt_batch_ok(int64_t B) { return B >= 1 && B <= VT_MAX_B; }
 
@@ -412,20 +420,23 @@ void vt_launch_point(dim3 grid, size_t lds, hipStream_t stream, const float* x, 
 
 }  // namespace
 
-extern "C" int svnet_vn_point_supported(int64_t N, int64_t C, int64_t Cg, int64_t O, int64_t Od) { return vt_point_ok(N, C, Cg, O, Od) ? 1 : 0; }
+// ---- the host side, stated once: an entry of the base envelope and its _wide twin pass their envelope and their own name (for the
+// messages) to the same function, which checks, plans (vt_point_tiles) and launches.  Within the base envelope both therefore choose
+// the same kernel and return the same bits.
+namespace {
 
-extern "C" size_t svnet_vn_point_workspace_bytes(int64_t B, int64_t Cg, int64_t O, int64_t Od) {
-    if (!vt_batch_ok(B) || !vt_point_ok(1, 1, Cg, O, Od)) return 0;
+size_t vt_point_workspace(const VtEnvelope& v, int64_t B, int64_t Cg, int64_t O, int64_t Od) {
+    if (!vt_batch_ok(B) || !vt_point_ok(v, 1, 1, Cg, O, Od)) return 0;
     return Cg > 0 ? (size_t)B * 3 * (size_t)(O + Od) * sizeof(float) : 0;
 }
 
-extern "C" int svnet_vn_point_fold_f32(const float* w_feat, const float* w_dir, const float* gamma, const float* beta, const float* running_mean,
-                                       const float* running_var, int64_t C, int64_t Cg, int64_t O, int64_t Od, float eps, float* folded, void* stream) {
+int vt_point_fold(const VtEnvelope& v, const char* name, const float* w_feat, const float* w_dir, const float* gamma, const float* beta,
+                  const float* running_mean, const float* running_var, int64_t C, int64_t Cg, int64_t O, int64_t Od, float eps, float* folded, void* stream) {
     SVNET_REQUIRE(w_feat && w_dir && gamma && beta && running_mean && running_var && folded, SVNET_E_ARG,
-                  "svnet_vn_point_fold_f32: null w_feat / w_dir / gamma / beta / running_mean / running_var / folded");
-    SVNET_REQUIRE(vt_point_ok(1, C, Cg, O, Od), SVNET_E_UNSUPPORTED,
-                  "svnet_vn_point_fold_f32: C %lld, Cg %lld, O %lld, Od %lld: needs 1 <= C <= %d, 0 <= Cg <= %d, 1 <= O <= %d, Od = O or 1", (long long)C,
-                  (long long)Cg, (long long)O, (long long)Od, VT_MAX_C, VT_MAX_C, VT_MAX_O);
+                  "%s: null w_feat / w_dir / gamma / beta / running_mean / running_var / folded", name);
+    SVNET_REQUIRE(vt_point_ok(v, 1, C, Cg, O, Od), SVNET_E_UNSUPPORTED,
+                  "%s: C %lld, Cg %lld, O %lld, Od %lld: needs 1 <= C <= %d, 0 <= Cg <= %d, 1 <= O <= %d, Od = O or 1", name, (long long)C, (long long)Cg,
+                  (long long)O, (long long)Od, v.max_c, v.max_c, v.max_o);
     const int64_t total = (C + Cg) * (O + Od) + O;
     hipLaunchKernelGGL(vn_point_fold_kernel, dim3((unsigned)svnet_cdiv(total, VT_THREADS)), dim3(VT_THREADS), 0, (hipStream_t)stream, w_feat, w_dir, gamma,
                        beta, running_mean, running_var, (int)(C + Cg), (int)O, (int)Od, eps, folded);
@@ -433,15 +444,15 @@ extern "C" int svnet_vn_point_fold_f32(const float* w_feat, const float* w_dir, 
     return SVNET_OK;
 }
 
-extern "C" int svnet_vn_point_f32(const float* x, const float* g, const float* folded, int64_t B, int64_t N, int64_t C, int64_t Cg, int64_t O, int64_t Od,
-                                  float slope, void* workspace, size_t workspace_bytes, float* out, void* stream) {
-    SVNET_REQUIRE(x && folded && out && (Cg <= 0 || (g && workspace)), SVNET_E_ARG, "svnet_vn_point_f32: null x / folded / out, or g / workspace with Cg > 0");
-    SVNET_REQUIRE(vt_batch_ok(B), SVNET_E_ARG, "svnet_vn_point_f32: B %lld must lie in 1 .. %d", (long long)B, VT_MAX_B);
-    SVNET_REQUIRE(vt_point_ok(N, C, Cg, O, Od), SVNET_E_UNSUPPORTED,
-                  "svnet_vn_point_f32: N %lld, C %lld, Cg %lld, O %lld, Od %lld: needs 1 <= N <= %d, 1 <= C <= %d, 0 <= Cg <= %d, 1 <= O <= %d, Od = O or 1",
-                  (long long)N, (long long)C, (long long)Cg, (long long)O, (long long)Od, VN_MAX_N, VT_MAX_C, VT_MAX_C, VT_MAX_O);
-    SVNET_REQUIRE(workspace_bytes >= svnet_vn_point_workspace_bytes(B, Cg, O, Od), SVNET_E_WORKSPACE, "svnet_vn_point_f32: workspace of %zu bytes, needs %zu",
-                  workspace_bytes, svnet_vn_point_workspace_bytes(B, Cg, O, Od));
+int vt_point(const VtEnvelope& v, const char* name, const float* x, const float* g, const float* folded, int64_t B, int64_t N, int64_t C, int64_t Cg,
+             int64_t O, int64_t Od, float slope, void* workspace, size_t workspace_bytes, float* out, void* stream) {
+    SVNET_REQUIRE(x && folded && out && (Cg <= 0 || (g && workspace)), SVNET_E_ARG, "%s: null x / folded / out, or g / workspace with Cg > 0", name);
+    SVNET_REQUIRE(vt_batch_ok(B), SVNET_E_ARG, "%s: B %lld must lie in 1 .. %d", name, (long long)B, VT_MAX_B);
+    SVNET_REQUIRE(vt_point_ok(v, N, C, Cg, O, Od), SVNET_E_UNSUPPORTED,
+                  "%s: N %lld, C %lld, Cg %lld, O %lld, Od %lld: needs 1 <= N <= %d, 1 <= C <= %d, 0 <= Cg <= %d, 1 <= O <= %d, Od = O or 1", name,
+                  (long long)N, (long long)C, (long long)Cg, (long long)O, (long long)Od, VN_MAX_N, v.max_c, v.max_c, v.max_o);
+    SVNET_REQUIRE(workspace_bytes >= vt_point_workspace(v, B, Cg, O, Od), SVNET_E_WORKSPACE, "%s: workspace of %zu bytes, needs %zu", name, workspace_bytes,
+                  vt_point_workspace(v, B, Cg, O, Od));
     const int R = (int)(O + Od);
     const float* s = folded + (C + Cg) * R;
     float* u = nullptr;
@@ -455,9 +466,10 @@ extern "C" int svnet_vn_point_f32(const float* x, const float* g, const float* f
     const bool share = Od == 1 && O != 1;
     const int npt = vt_point_tiles(N, C, share);
     const size_t lds = (size_t)vt_point_lds(npt, C, share);
+    SVNET_REQUIRE(lds <= (size_t)VT_LDS_MAX, SVNET_E_UNSUPPORTED, "%s: an image of %zu bytes does not fit LDS", name, lds);
     if (lds > 64 * 1024) {
         bool ok = true;
-        SVNET_LDS_OPTIN(ok, VT_LDS_MAX, "svnet_vn_point_f32", reinterpret_cast<const void*>(vn_point_kernel<1, false, VtLeaky>),
+        SVNET_LDS_OPTIN(ok, VT_LDS_MAX, name, reinterpret_cast<const void*>(vn_point_kernel<1, false, VtLeaky>),
                         reinterpret_cast<const void*>(vn_point_kernel<1, true, VtLeaky>), reinterpret_cast<const void*>(vn_point_kernel<2, false, VtLeaky>),
                         reinterpret_cast<const void*>(vn_point_kernel<2, true, VtLeaky>), reinterpret_cast<const void*>(vn_point_kernel<4, false, VtLeaky>),
                         reinterpret_cast<const void*>(vn_point_kernel<4, true, VtLeaky>));
@@ -480,14 +492,12 @@ extern "C" int svnet_vn_point_f32(const float* x, const float* g, const float* f
     return SVNET_OK;
 }
 
-extern "C" int svnet_vn_point_norm_supported(int64_t N, int64_t C, int64_t O) { return vt_point_ok(N, C, 0, O, O) ? 1 : 0; }
-
-extern "C" int svnet_vn_point_norm_fold_f32(const float* w_feat, const float* gamma, const float* beta, const float* running_mean, const float* running_var,
-                                            int64_t C, int64_t O, float eps, float* folded, void* stream) {
+int vt_point_norm_fold(const VtEnvelope& v, const char* name, const float* w_feat, const float* gamma, const float* beta, const float* running_mean,
+                       const float* running_var, int64_t C, int64_t O, float eps, float* folded, void* stream) {
     SVNET_REQUIRE(w_feat && gamma && beta && running_mean && running_var && folded, SVNET_E_ARG,
-                  "svnet_vn_point_norm_fold_f32: null w_feat / gamma / beta / running_mean / running_var / folded");
-    SVNET_REQUIRE(vt_point_ok(1, C, 0, O, O), SVNET_E_UNSUPPORTED, "svnet_vn_point_norm_fold_f32: C %lld, O %lld: needs 1 <= C <= %d, 1 <= O <= %d", (long long)C,
-                  (long long)O, VT_MAX_C, VT_MAX_O);
+                  "%s: null w_feat / gamma / beta / running_mean / running_var / folded", name);
+    SVNET_REQUIRE(vt_point_ok(v, 1, C, 0, O, O), SVNET_E_UNSUPPORTED, "%s: C %lld, O %lld: needs 1 <= C <= %d, 1 <= O <= %d", name, (long long)C, (long long)O,
+                  v.max_c, v.max_o);
     const int64_t total = C * O + O;
     hipLaunchKernelGGL(vn_point_fold_kernel, dim3((unsigned)svnet_cdiv(total, VT_THREADS)), dim3(VT_THREADS), 0, (hipStream_t)stream, w_feat, w_feat, gamma,
                        beta, running_mean, running_var, (int)C, (int)O, 0, eps, folded);
@@ -495,17 +505,19 @@ extern "C" int svnet_vn_point_norm_fold_f32(const float* w_feat, const float* ga
     return SVNET_OK;
 }
 
-extern "C" int svnet_vn_point_norm_f32(const float* x, const float* folded, int64_t B, int64_t N, int64_t C, int64_t O, float* out, void* stream) {
-    SVNET_REQUIRE(x && folded && out, SVNET_E_ARG, "svnet_vn_point_norm_f32: null x / folded / out");
-    SVNET_REQUIRE(vt_batch_ok(B), SVNET_E_ARG, "svnet_vn_point_norm_f32: B %lld must lie in 1 .. %d", (long long)B, VT_MAX_B);
-    SVNET_REQUIRE(vt_point_ok(N, C, 0, O, O), SVNET_E_UNSUPPORTED, "svnet_vn_point_norm_f32: N %lld, C %lld, O %lld: needs 1 <= N <= %d, 1 <= C <= %d, 1 <= O <= %d",
-                  (long long)N, (long long)C, (long long)O, VN_MAX_N, VT_MAX_C, VT_MAX_O);
+int vt_point_norm(const VtEnvelope& v, const char* name, const float* x, const float* folded, int64_t B, int64_t N, int64_t C, int64_t O, float* out,
+                  void* stream) {
+    SVNET_REQUIRE(x && folded && out, SVNET_E_ARG, "%s: null x / folded / out", name);
+    SVNET_REQUIRE(vt_batch_ok(B), SVNET_E_ARG, "%s: B %lld must lie in 1 .. %d", name, (long long)B, VT_MAX_B);
+    SVNET_REQUIRE(vt_point_ok(v, N, C, 0, O, O), SVNET_E_UNSUPPORTED, "%s: N %lld, C %lld, O %lld: needs 1 <= N <= %d, 1 <= C <= %d, 1 <= O <= %d", name,
+                  (long long)N, (long long)C, (long long)O, VN_MAX_N, v.max_c, v.max_o);
     const float* s = folded + C * O;
     const int npt = vt_point_tiles(N, C, false);
     const size_t lds = (size_t)vt_point_lds(npt, C, false);
+    SVNET_REQUIRE(lds <= (size_t)VT_LDS_MAX, SVNET_E_UNSUPPORTED, "%s: an image of %zu bytes does not fit LDS", name, lds);
     if (lds > 64 * 1024) {
         bool ok = true;
-        SVNET_LDS_OPTIN(ok, VT_LDS_MAX, "svnet_vn_point_norm_f32", reinterpret_cast<const void*>(vn_point_kernel<1, false, VtNormOnly>),
+        SVNET_LDS_OPTIN(ok, VT_LDS_MAX, name, reinterpret_cast<const void*>(vn_point_kernel<1, false, VtNormOnly>),
                         reinterpret_cast<const void*>(vn_point_kernel<2, false, VtNormOnly>), reinterpret_cast<const void*>(vn_point_kernel<4, false, VtNormOnly>));
         if (!ok) return SVNET_E_LAUNCH;
     }
@@ -520,11 +532,11 @@ extern "C" int svnet_vn_point_norm_f32(const float* x, const float* folded, int6
     return SVNET_OK;
 }
 
-extern "C" int svnet_vn_cloud_mean_f32(const float* x, int64_t B, int64_t C, int64_t N, float* m, void* stream) {
-    SVNET_REQUIRE(x && m, SVNET_E_ARG, "svnet_vn_cloud_mean_f32: null x / m");
-    SVNET_REQUIRE(vt_batch_ok(B), SVNET_E_ARG, "svnet_vn_cloud_mean_f32: B %lld must lie in 1 .. %d", (long long)B, VT_MAX_B);
-    SVNET_REQUIRE(N >= 1 && N <= VN_MAX_N && C >= 1 && C <= VT_MAX_C, SVNET_E_UNSUPPORTED, "svnet_vn_cloud_mean_f32: N %lld, C %lld: needs 1 <= N <= %d, 1 <= C <= %d",
-                  (long long)N, (long long)C, VN_MAX_N, VT_MAX_C);
+int vt_cloud_mean(const VtEnvelope& v, const char* name, const float* x, int64_t B, int64_t C, int64_t N, float* m, void* stream) {
+    SVNET_REQUIRE(x && m, SVNET_E_ARG, "%s: null x / m", name);
+    SVNET_REQUIRE(vt_batch_ok(B), SVNET_E_ARG, "%s: B %lld must lie in 1 .. %d", name, (long long)B, VT_MAX_B);
+    SVNET_REQUIRE(N >= 1 && N <= VN_MAX_N && C >= 1 && C <= v.max_c, SVNET_E_UNSUPPORTED, "%s: N %lld, C %lld: needs 1 <= N <= %d, 1 <= C <= %d", name,
+                  (long long)N, (long long)C, VN_MAX_N, v.max_c);
     const int64_t rows = B * C * 3;
     const int runs = (int)svnet_cdiv(N, VT_RUN), rpb = runs >= VT_THREADS ? 1 : VT_THREADS / runs;
     hipLaunchKernelGGL(vn_cloud_mean_kernel, dim3((unsigned)svnet_cdiv(rows, rpb)), dim3(VT_THREADS), 0, (hipStream_t)stream, x, rows, (int)N, runs, rpb, m);
@@ -532,22 +544,20 @@ extern "C" int svnet_vn_cloud_mean_f32(const float* x, int64_t B, int64_t C, int
     return SVNET_OK;
 }
 
-extern "C" int svnet_vn_std_pool_supported(int64_t N, int64_t C, int64_t Cg, int64_t Cy) { return vt_std_ok(N, C, Cg, Cy) ? 1 : 0; }
-
-extern "C" size_t svnet_vn_std_pool_workspace_bytes(int64_t B, int64_t N, int64_t C, int64_t Cg) {
-    if (!vt_batch_ok(B) || !vt_std_ok(N, C, Cg, 1)) return 0;
+size_t vt_std_pool_workspace(const VtEnvelope& v, int64_t B, int64_t N, int64_t C, int64_t Cg) {
+    if (!vt_batch_ok(B) || !vt_std_ok(v, N, C, Cg, 1)) return 0;
     return (size_t)2 * (size_t)svnet_cdiv(N, VT_RUN) * (size_t)B * 3 * (size_t)(C + Cg) * sizeof(float);
 }
 
-extern "C" int svnet_vn_std_pool_f32(const float* x, const float* g, const float* y, const float* w_lin, int64_t B, int64_t N, int64_t C, int64_t Cg,
-                                     int64_t Cy, void* workspace, size_t workspace_bytes, float* h, void* stream) {
-    SVNET_REQUIRE(x && y && w_lin && workspace && h && (Cg <= 0 || g), SVNET_E_ARG, "svnet_vn_std_pool_f32: null x / y / w_lin / workspace / h, or g with Cg > 0");
-    SVNET_REQUIRE(vt_batch_ok(B), SVNET_E_ARG, "svnet_vn_std_pool_f32: B %lld must lie in 1 .. %d", (long long)B, VT_MAX_B);
-    SVNET_REQUIRE(vt_std_ok(N, C, Cg, Cy), SVNET_E_UNSUPPORTED,
-                  "svnet_vn_std_pool_f32: N %lld, C %lld, Cg %lld, Cy %lld: needs 1 <= N <= %d, 1 <= C <= %d, 0 <= Cg <= %d, 1 <= Cy <= %d", (long long)N,
-                  (long long)C, (long long)Cg, (long long)Cy, VN_MAX_N, VT_MAX_C, VT_MAX_C, VT_MAX_C);
-    SVNET_REQUIRE(workspace_bytes >= svnet_vn_std_pool_workspace_bytes(B, N, C, Cg), SVNET_E_WORKSPACE, "svnet_vn_std_pool_f32: workspace of %zu bytes, needs %zu",
-                  workspace_bytes, svnet_vn_std_pool_workspace_bytes(B, N, C, Cg));
+int vt_std_pool(const VtEnvelope& v, const char* name, const float* x, const float* g, const float* y, const float* w_lin, int64_t B, int64_t N, int64_t C,
+                int64_t Cg, int64_t Cy, void* workspace, size_t workspace_bytes, float* h, void* stream) {
+    SVNET_REQUIRE(x && y && w_lin && workspace && h && (Cg <= 0 || g), SVNET_E_ARG, "%s: null x / y / w_lin / workspace / h, or g with Cg > 0", name);
+    SVNET_REQUIRE(vt_batch_ok(B), SVNET_E_ARG, "%s: B %lld must lie in 1 .. %d", name, (long long)B, VT_MAX_B);
+    SVNET_REQUIRE(vt_std_ok(v, N, C, Cg, Cy), SVNET_E_UNSUPPORTED,
+                  "%s: N %lld, C %lld, Cg %lld, Cy %lld: needs 1 <= N <= %d, 1 <= C <= %d, 0 <= Cg <= %d, 1 <= Cy <= %d", name, (long long)N, (long long)C,
+                  (long long)Cg, (long long)Cy, VN_MAX_N, v.max_c, v.max_c, v.max_c);
+    SVNET_REQUIRE(workspace_bytes >= vt_std_pool_workspace(v, B, N, C, Cg), SVNET_E_WORKSPACE, "%s: workspace of %zu bytes, needs %zu", name, workspace_bytes,
+                  vt_std_pool_workspace(v, B, N, C, Cg));
     const int64_t runs = svnet_cdiv(N, VT_RUN), cols = 3 * (C + Cg), total = B * cols;
     float* pmax = static_cast<float*>(workspace);
     float* psum = pmax + runs * total;
@@ -560,16 +570,57 @@ extern "C" int svnet_vn_std_pool_f32(const float* x, const float* g, const float
     return SVNET_OK;
 }
 
-extern "C" int svnet_vn_std_coords_supported(int64_t N, int64_t C, int64_t Cy) { return vt_std_ok(N, C, 0, Cy) ? 1 : 0; }
-
-extern "C" int svnet_vn_std_coords_f32(const float* x, const float* y, const float* w_lin, int64_t B, int64_t N, int64_t C, int64_t Cy, float* e,
-                                       void* stream) {
-    SVNET_REQUIRE(x && y && w_lin && e, SVNET_E_ARG, "svnet_vn_std_coords_f32: null x / y / w_lin / e");
-    SVNET_REQUIRE(vt_batch_ok(B), SVNET_E_ARG, "svnet_vn_std_coords_f32: B %lld must lie in 1 .. %d", (long long)B, VT_MAX_B);
-    SVNET_REQUIRE(vt_std_ok(N, C, 0, Cy), SVNET_E_UNSUPPORTED, "svnet_vn_std_coords_f32: N %lld, C %lld, Cy %lld: needs 1 <= N <= %d, 1 <= C <= %d, 1 <= Cy <= %d",
-                  (long long)N, (long long)C, (long long)Cy, VN_MAX_N, VT_MAX_C, VT_MAX_C);
+int vt_std_coords(const VtEnvelope& v, const char* name, const float* x, const float* y, const float* w_lin, int64_t B, int64_t N, int64_t C, int64_t Cy,
+                  float* e, void* stream) {
+    SVNET_REQUIRE(x && y && w_lin && e, SVNET_E_ARG, "%s: null x / y / w_lin / e", name);
+    SVNET_REQUIRE(vt_batch_ok(B), SVNET_E_ARG, "%s: B %lld must lie in 1 .. %d", name, (long long)B, VT_MAX_B);
+    SVNET_REQUIRE(vt_std_ok(v, N, C, 0, Cy), SVNET_E_UNSUPPORTED, "%s: N %lld, C %lld, Cy %lld: needs 1 <= N <= %d, 1 <= C <= %d, 1 <= Cy <= %d", name,
+                  (long long)N, (long long)C, (long long)Cy, VN_MAX_N, v.max_c, v.max_c);
     hipLaunchKernelGGL(vn_std_coords_kernel, dim3((unsigned)svnet_cdiv(N, VT_RUN), (unsigned)B), dim3(VT_THREADS), 0, (hipStream_t)stream, x, y, w_lin, (int)N,
                        (int)C, (int)Cy, e);
     SVNET_CHECK_LAUNCH("vn_std_coords_kernel");
     return SVNET_OK;
 }
+
+}  // namespace
+
+// ---- the entries: V is the envelope, INFIX what the wide twin's name carries behind the stage's (include/svnet_hip.h states the rule)
+#define VT_ENTRIES(V, INFIX)                                                                                                                                   \
+    extern "C" int svnet_vn_point##INFIX##_supported(int64_t N, int64_t C, int64_t Cg, int64_t O, int64_t Od) { return vt_point_ok(V, N, C, Cg, O, Od) ? 1 : 0; } \
+    extern "C" size_t svnet_vn_point##INFIX##_workspace_bytes(int64_t B, int64_t Cg, int64_t O, int64_t Od) { return vt_point_workspace(V, B, Cg, O, Od); }    \
+    extern "C" int svnet_vn_point##INFIX##_fold_f32(const float* w_feat, const float* w_dir, const float* gamma, const float* beta, const float* running_mean, \
+                                                    const float* running_var, int64_t C, int64_t Cg, int64_t O, int64_t Od, float eps, float* folded,         \
+                                                    void* stream) {                                                                                            \
+        return vt_point_fold(V, "svnet_vn_point" #INFIX "_fold_f32", w_feat, w_dir, gamma, beta, running_mean, running_var, C, Cg, O, Od, eps, folded, stream); \
+    }                                                                                                                                                          \
+    extern "C" int svnet_vn_point##INFIX##_f32(const float* x, const float* g, const float* folded, int64_t B, int64_t N, int64_t C, int64_t Cg, int64_t O,    \
+                                               int64_t Od, float slope, void* workspace, size_t workspace_bytes, float* out, void* stream) {                   \
+        return vt_point(V, "svnet_vn_point" #INFIX "_f32", x, g, folded, B, N, C, Cg, O, Od, slope, workspace, workspace_bytes, out, stream);                 \
+    }                                                                                                                                                          \
+    extern "C" int svnet_vn_point_norm##INFIX##_supported(int64_t N, int64_t C, int64_t O) { return vt_point_ok(V, N, C, 0, O, O) ? 1 : 0; }                   \
+    extern "C" int svnet_vn_point_norm##INFIX##_fold_f32(const float* w_feat, const float* gamma, const float* beta, const float* running_mean,                \
+                                                         const float* running_var, int64_t C, int64_t O, float eps, float* folded, void* stream) {             \
+        return vt_point_norm_fold(V, "svnet_vn_point_norm" #INFIX "_fold_f32", w_feat, gamma, beta, running_mean, running_var, C, O, eps, folded, stream);     \
+    }                                                                                                                                                          \
+    extern "C" int svnet_vn_point_norm##INFIX##_f32(const float* x, const float* folded, int64_t B, int64_t N, int64_t C, int64_t O, float* out,               \
+                                                    void* stream) {                                                                                            \
+        return vt_point_norm(V, "svnet_vn_point_norm" #INFIX "_f32", x, folded, B, N, C, O, out, stream);                                                      \
+    }                                                                                                                                                          \
+    extern "C" int svnet_vn_cloud_mean##INFIX##_f32(const float* x, int64_t B, int64_t C, int64_t N, float* m, void* stream) {                                 \
+        return vt_cloud_mean(V, "svnet_vn_cloud_mean" #INFIX "_f32", x, B, C, N, m, stream);                                                                   \
+    }                                                                                                                                                          \
+    extern "C" int svnet_vn_std_pool##INFIX##_supported(int64_t N, int64_t C, int64_t Cg, int64_t Cy) { return vt_std_ok(V, N, C, Cg, Cy) ? 1 : 0; }           \
+    extern "C" size_t svnet_vn_std_pool##INFIX##_workspace_bytes(int64_t B, int64_t N, int64_t C, int64_t Cg) { return vt_std_pool_workspace(V, B, N, C, Cg); } \
+    extern "C" int svnet_vn_std_pool##INFIX##_f32(const float* x, const float* g, const float* y, const float* w_lin, int64_t B, int64_t N, int64_t C,         \
+                                                  int64_t Cg, int64_t Cy, void* workspace, size_t workspace_bytes, float* h, void* stream) {                   \
+        return vt_std_pool(V, "svnet_vn_std_pool" #INFIX "_f32", x, g, y, w_lin, B, N, C, Cg, Cy, workspace, workspace_bytes, h, stream);                      \
+    }                                                                                                                                                          \
+    extern "C" int svnet_vn_std_coords##INFIX##_supported(int64_t N, int64_t C, int64_t Cy) { return vt_std_ok(V, N, C, 0, Cy) ? 1 : 0; }                      \
+    extern "C" int svnet_vn_std_coords##INFIX##_f32(const float* x, const float* y, const float* w_lin, int64_t B, int64_t N, int64_t C, int64_t Cy, float* e, \
+                                                    void* stream) {                                                                                            \
+        return vt_std_coords(V, "svnet_vn_std_coords" #INFIX "_f32", x, y, w_lin, B, N, C, Cy, e, stream);                                                     \
+    }
+
+VT_ENTRIES(VT_BASE, )
+VT_ENTRIES(VT_WIDE, _wide)
+#undef VT_ENTRIES

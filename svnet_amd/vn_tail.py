@@ -38,7 +38,10 @@ EPS = fl(1e-6); inputs are assumed finite):
                 and g[i-C,:] otherwise, e[i,k](n) = fmaf(v_i[2], z[k][2], fmaf(v_i[1], z[k][1], fl(v_i[0] z[k][0])));  with I = C + Cg,
                 h[3 i + k] = max over n of e, h[3 I + 3 i + k] = the mean of e under the cloud-mean rule.
     limits      1 <= N <= 32768, 1 <= C <= 512, 0 <= Cg <= 512, 1 <= O <= 512, Od is O or 1, 1 <= Cy <= 512, B <= 65535
-                (`supported_point`, `supported_std`).
+                (`supported_point`, `supported_std`).  With wide=True - on the folds, which hand it to vn_point and vn_point_norm, and on
+                vn_cloud_mean, vn_std_pool, vn_std_coords and std_tail - 768 stands for 512 throughout (MAX_C_WIDE, MAX_O_WIDE; the
+                `supported_*_wide` forms): the svnet_vn_*_wide_* entries, the same kernels and the same contract.  VN_PointNet_PSEG's
+                682-wide std_feature needs it; nothing takes it unasked.
 
 The module's order of the norm and leaky arithmetic differs from the contract's in rounding only.
 tests/vn_tail_ref.py restates the contract in numpy; the kernels' results are compared with it as bit patterns (a -0 counted as +0).
@@ -50,21 +53,47 @@ from . import _call, _lib, _pointset, _vn
 
 __all__ = ["fold_vn_point", "vn_point", "vn_cloud_mean", "vn_std_pool", "vn_std_coords", "supported_point", "supported_std", "supported_coords",
            "FoldedVNPoint", "FusedVNTail", "fold_vn_linear_norm", "vn_point_norm", "supported_point_norm", "FoldedVNPointNorm",
-           "MAX_C", "MAX_O", "MAX_B"]
+           "MAX_C", "MAX_O", "MAX_B", "MAX_C_WIDE", "MAX_O_WIDE", "supported_point_wide", "supported_point_norm_wide", "supported_std_wide",
+           "supported_coords_wide"]
 
 _WHAT = "the fused vector-neuron tail"   # in the messages of _pointset.check_tensors
 MAX_C, MAX_O, MAX_B = 512, 512, 65535
+MAX_C_WIDE, MAX_O_WIDE = 768, 768
 _F32 = torch.float32
 
 
-def supported_point(N, C, Cg, O, Od):
+def _entry(stem, rest, wide):
+    """The C entry of a stage in the envelope asked for: svnet_vn_<stem>[_wide]_<rest> (include/svnet_hip.h, the naming rule)."""
+    return "svnet_vn_%s%s_%s" % (stem, "_wide" if wide else "", rest)
+
+
+def _widest(wide):
+    """(the widest C, the widest O) of the envelope in force, for the messages."""
+    return (MAX_C_WIDE, MAX_O_WIDE) if wide else (MAX_C, MAX_O)
+
+
+def _ask(stem, wide, *dims):
+    return bool(getattr(_lib.lib(), _entry(stem, "supported", wide))(*(int(d) for d in dims)))
+
+
+def supported_point(N, C, Cg, O, Od, wide=False):
     """Whether the point-level kernel takes this layer (module docstring, limits)."""
-    return bool(_lib.lib().svnet_vn_point_supported(int(N), int(C), int(Cg), int(O), int(Od)))
+    return _ask("point", wide, N, C, Cg, O, Od)
 
 
-def supported_std(N, C, Cg, Cy):
+def supported_std(N, C, Cg, Cy, wide=False):
     """Whether the standardise-and-pool kernel takes these widths (module docstring, limits)."""
-    return bool(_lib.lib().svnet_vn_std_pool_supported(int(N), int(C), int(Cg), int(Cy)))
+    return _ask("std_pool", wide, N, C, Cg, Cy)
+
+
+def supported_point_wide(N, C, Cg, O, Od):
+    """supported_point in the wide envelope."""
+    return supported_point(N, C, Cg, O, Od, wide=True)
+
+
+def supported_std_wide(N, C, Cg, Cy):
+    """supported_std in the wide envelope."""
+    return supported_std(N, C, Cg, Cy, wide=True)
 
 
 _Workspace = _vn.Workspace     # (vn_std_pool takes one as its `workspace`)
@@ -76,27 +105,32 @@ class FoldedVNPoint(_vn.Folded):
     term, which grows to the largest B seen and is then reused (`workspace`: the current one).  refresh() and release() are
     _vn.Folded's."""
     NAME, ENTRY = "fold_vn_point", "svnet_vn_point_fold_f32"
+    wide = False
 
-    def __init__(self, layer, cloud_channels=0):
+    def __init__(self, layer, cloud_channels=0, wide=False):
+        self.wide = bool(wide)                           # the envelope the layer was folded in: vn_point launches in the same
+        self.ENTRY = _entry("point", "fold_f32", self.wide)
         wf, wd, _ = _vn.check_layer(self.NAME, layer, even=False)
         Cg = int(cloud_channels)
         if Cg < 0 or Cg >= wf.shape[1]:
             raise ValueError("fold_vn_point: cloud_channels = %d of %d input channels: needs 0 <= cloud_channels < the input width" % (Cg, wf.shape[1]))
         self.place(layer)
         self.dims = self.C, self.Cg, self.O, self.Od = int(wf.shape[1]) - Cg, Cg, int(wf.shape[0]), int(wd.shape[0])
-        if not supported_point(1, self.C, self.Cg, self.O, self.Od):
+        if not supported_point(1, self.C, self.Cg, self.O, self.Od, self.wide):
+            max_c, max_o = _widest(self.wide)
             raise _lib.SvnetHipError("fold_vn_point: C = %d, Cg = %d, O = %d is not supported (1 <= C <= %d, Cg <= %d, 1 <= O <= %d)"
-                                     % (self.C, self.Cg, self.O, MAX_C, MAX_C, MAX_O))
+                                     % (self.C, self.Cg, self.O, max_c, max_c, max_o))
         self.allocate((self.C + self.Cg) * (self.O + self.Od) + 2 * self.O)
 
     def cloud_terms(self, B):
         """The workspace of the cloud term for B clouds (uint8; one byte when Cg = 0)."""
-        return self._ws.take(int(_lib.lib().svnet_vn_point_workspace_bytes(B, self.Cg, self.O, self.Od)))
+        return self._ws.take(int(getattr(_lib.lib(), _entry("point", "workspace_bytes", self.wide))(B, self.Cg, self.O, self.Od)))
 
 
-def fold_vn_point(layer, cloud_channels=0):
-    """A VNLinearLeakyReLU on a HIP device whose last `cloud_channels` input channels are constant over a cloud -> FoldedVNPoint."""
-    return FoldedVNPoint(layer, cloud_channels)
+def fold_vn_point(layer, cloud_channels=0, wide=False):
+    """A VNLinearLeakyReLU on a HIP device whose last `cloud_channels` input channels are constant over a cloud -> FoldedVNPoint.
+    wide: fold it in the wide envelope (module docstring, limits); the folded layer carries it."""
+    return FoldedVNPoint(layer, cloud_channels, wide)
 
 
 def _cloud_shape(name, cloud, B, Cg):
@@ -110,7 +144,7 @@ def _cloud_shape(name, cloud, B, Cg):
 def _launch_point(x, cloud, folded, out, B, N):
     ws = folded.cloud_terms(B)
     with torch.cuda.device(x.device):
-        _lib.call("svnet_vn_point_f32", _call.p(x), _call.p(cloud), _call.p(folded.folded), B, N, folded.C, folded.Cg, folded.O, folded.Od, folded.slope,
+        _lib.call(_entry("point", "f32", folded.wide), _call.p(x), _call.p(cloud), _call.p(folded.folded), B, N, folded.C, folded.Cg, folded.O, folded.Od, folded.slope,
                   _call.p(ws), ws.numel() if folded.Cg else 0, _call.p(out), _call.stream())
 
 
@@ -124,27 +158,35 @@ def vn_point(x, folded, cloud=None, out=None):
     _cloud_shape(name, cloud, B, folded.Cg)
     shape = (B, folded.O, 3, N)
     _vn.check_out(name, out, shape, "[B,O,3,N]", (x, cloud, out), folded)
-    if B > MAX_B or not supported_point(N, C, folded.Cg, folded.O, folded.Od):
+    if B > MAX_B or not supported_point(N, C, folded.Cg, folded.O, folded.Od, folded.wide):
         raise _lib.SvnetHipError("%s: B = %d, N = %d, C = %d, O = %d is not supported (B <= %d, 1 <= N <= %d, C <= %d, O <= %d)"
-                                 % (name, B, N, C, folded.O, MAX_B, _pointset.MAX_N, MAX_C, MAX_O))
+                                 % ((name, B, N, C, folded.O, MAX_B, _pointset.MAX_N) + _widest(folded.wide)))
     if out is None:
         out = torch.empty(*shape, dtype=_F32, device=x.device)
     _launch_point(x, cloud, folded, out, B, N)
     return out
 
 
-def supported_point_norm(N, C, O):
+def supported_point_norm(N, C, O, wide=False):
     """Whether the norm-only point kernel takes this layer (module docstring, limits)."""
-    return bool(_lib.lib().svnet_vn_point_norm_supported(int(N), int(C), int(O)))
+    return _ask("point_norm", wide, N, C, O)
+
+
+def supported_point_norm_wide(N, C, O):
+    """supported_point_norm in the wide envelope."""
+    return supported_point_norm(N, C, O, wide=True)
 
 
 class FoldedVNPointNorm(_vn.Folded):
     """The folded form of a VNLinear over C -> O vector channels followed by a VNBatchNorm, with no leaky rule: WT [C, O] | s [O] | t [O]
     in one buffer on the layer's device, allocated once.  refresh() and release() as _vn.Folded's; there is no workspace."""
     NAME, ENTRY = "fold_vn_linear_norm", "svnet_vn_point_norm_fold_f32"
+    wide = False
 
-    def __init__(self, linear, batchnorm):
+    def __init__(self, linear, batchnorm, wide=False):
         from .models.vn_layers import VNBatchNorm, VNLinear
+        self.wide = bool(wide)
+        self.ENTRY = _entry("point_norm", "fold_f32", self.wide)
         if not isinstance(linear, VNLinear) or not isinstance(batchnorm, VNBatchNorm):
             raise TypeError("%s: needs a VNLinear and a VNBatchNorm, got %s and %s" % (self.NAME, type(linear).__name__, type(batchnorm).__name__))
         w, bn = linear.map_to_feat.weight, batchnorm.bn
@@ -154,17 +196,17 @@ class FoldedVNPointNorm(_vn.Folded):
         self.place(linear)
         self.batchnorm = batchnorm
         self.dims = self.C, self.O = int(w.shape[1]), int(w.shape[0])
-        if not supported_point_norm(1, self.C, self.O):
-            raise _lib.SvnetHipError("%s: C = %d, O = %d is not supported (1 <= C <= %d, 1 <= O <= %d)" % (self.NAME, self.C, self.O, MAX_C, MAX_O))
+        if not supported_point_norm(1, self.C, self.O, self.wide):
+            raise _lib.SvnetHipError("%s: C = %d, O = %d is not supported (1 <= C <= %d, 1 <= O <= %d)" % ((self.NAME, self.C, self.O) + _widest(self.wide)))
         self.allocate(self.C * self.O + 2 * self.O)
 
     def sources(self):
         return [self.layer.map_to_feat.weight], self.batchnorm.bn
 
 
-def fold_vn_linear_norm(linear, batchnorm):
-    """A VNLinear and the VNBatchNorm that follows it, on a HIP device -> FoldedVNPointNorm."""
-    return FoldedVNPointNorm(linear, batchnorm)
+def fold_vn_linear_norm(linear, batchnorm, wide=False):
+    """A VNLinear and the VNBatchNorm that follows it, on a HIP device -> FoldedVNPointNorm.  wide: as fold_vn_point's."""
+    return FoldedVNPointNorm(linear, batchnorm, wide)
 
 
 def vn_point_norm(x, folded, out=None):
@@ -175,39 +217,41 @@ def vn_point_norm(x, folded, out=None):
                                   per=" per point")
     shape = (B, folded.O, 3, N)
     _vn.check_out(name, out, shape, "[B,O,3,N]", (x, out), folded)
-    if B > MAX_B or not supported_point_norm(N, C, folded.O):
+    if B > MAX_B or not supported_point_norm(N, C, folded.O, folded.wide):
         raise _lib.SvnetHipError("%s: B = %d, N = %d, C = %d, O = %d is not supported (B <= %d, 1 <= N <= %d, C <= %d, O <= %d)"
-                                 % (name, B, N, C, folded.O, MAX_B, _pointset.MAX_N, MAX_C, MAX_O))
+                                 % ((name, B, N, C, folded.O, MAX_B, _pointset.MAX_N) + _widest(folded.wide)))
     if out is None:
         out = torch.empty(*shape, dtype=_F32, device=x.device)
     with torch.cuda.device(x.device):
-        _lib.call("svnet_vn_point_norm_f32", _call.p(x), _call.p(folded.folded), B, N, C, folded.O, _call.p(out), _call.stream())
+        _lib.call(_entry("point_norm", "f32", folded.wide), _call.p(x), _call.p(folded.folded), B, N, C, folded.O, _call.p(out), _call.stream())
     return out
 
 
-def vn_cloud_mean(x, out=None):
+def vn_cloud_mean(x, out=None, wide=False):
     """x [B,C,3,N] float32 -> out [B,C,3]: the mean over the points in the contract's order (module docstring).  One launch on the
-    current stream, no host read.  No argument may require grad."""
+    current stream, no host read.  wide: admit C to MAX_C_WIDE.  No argument may require grad."""
     name = "vn_cloud_mean"
     B, C, N, _ = _vn.check_entry(name, _WHAT, {"x": x, "out": out}, ("x", "out"))
     _vn.check_out(name, out, (B, C, 3), "[B,C,3]", (x, out))
-    if B > MAX_B or not supported_point(N, C, 0, 1, 1):
-        raise _lib.SvnetHipError("%s: B = %d, N = %d, C = %d is not supported (B <= %d, 1 <= N <= %d, 1 <= C <= %d)" % (name, B, N, C, MAX_B, _pointset.MAX_N, MAX_C))
+    if B > MAX_B or not supported_point(N, C, 0, 1, 1, wide):
+        raise _lib.SvnetHipError("%s: B = %d, N = %d, C = %d is not supported (B <= %d, 1 <= N <= %d, 1 <= C <= %d)"
+                                 % (name, B, N, C, MAX_B, _pointset.MAX_N, _widest(wide)[0]))
     if out is None:
         out = torch.empty(B, C, 3, dtype=_F32, device=x.device)
     with torch.cuda.device(x.device):
-        _lib.call("svnet_vn_cloud_mean_f32", _call.p(x), B, C, N, _call.p(out), _call.stream())
+        _lib.call(_entry("cloud_mean", "f32", wide), _call.p(x), B, C, N, _call.p(out), _call.stream())
     return out
 
 
 _std_workspaces = {}     # device -> _Workspace of vn_std_pool calls that bring none
 
 
-def vn_std_pool(x, y, w_lin, cloud=None, out=None, workspace=None):
+def vn_std_pool(x, y, w_lin, cloud=None, out=None, workspace=None, wide=False):
     """x [B,C,3,N], y [B,Cy,3,N] (vn2's output), w_lin [3,Cy] (vn_lin.weight as it lies), cloud [B,Cg,3] or None -> out [B, 6 I],
     I = C + Cg: the coordinates of [x | cloud expanded] in the frame w_lin y, pooled [amax | mean] over the points (module docstring).
     Two launches on the current stream, no host read.  workspace: a _Workspace to take the per-run partials from (FusedVNTail's);
-    without one the calls of a device share a buffer that grows.  No argument may require grad."""
+    without one the calls of a device share a buffer that grows.  wide: admit C, Cg and Cy to MAX_C_WIDE.  No argument may require
+    grad."""
     name = "vn_std_pool"
     B, C, N, _ = _vn.check_entry(name, _WHAT, {"x": x, "y": y, "w_lin": w_lin, "cloud": cloud, "out": out}, ("x", "y", "w_lin", "cloud", "out"))
     Cy = _vn.frame_shapes(name, y, w_lin, B, N)
@@ -216,53 +260,59 @@ def vn_std_pool(x, y, w_lin, cloud=None, out=None, workspace=None):
         raise ValueError("%s: cloud must be [B,Cg,3] with B = %d, got %s" % (name, B, tuple(cloud.shape)))
     shape = (B, 6 * (C + Cg))
     _vn.check_out(name, out, shape, "[B, 6 (C + Cg)]", (x, y, w_lin, cloud, out))
-    if B > MAX_B or not supported_std(N, C, Cg, Cy):
+    if B > MAX_B or not supported_std(N, C, Cg, Cy, wide):
         raise _lib.SvnetHipError("%s: B = %d, N = %d, C = %d, Cg = %d, Cy = %d is not supported (B <= %d, 1 <= N <= %d, C, Cg, Cy <= %d)"
-                                 % (name, B, N, C, Cg, Cy, MAX_B, _pointset.MAX_N, MAX_C))
+                                 % (name, B, N, C, Cg, Cy, MAX_B, _pointset.MAX_N, _widest(wide)[0]))
     if out is None:
         out = torch.empty(*shape, dtype=_F32, device=x.device)
     if workspace is None:
         workspace = _std_workspaces.setdefault(x.device, _Workspace(x.device))
-    ws = workspace.take(int(_lib.lib().svnet_vn_std_pool_workspace_bytes(B, N, C, Cg)))
+    ws = workspace.take(int(getattr(_lib.lib(), _entry("std_pool", "workspace_bytes", wide))(B, N, C, Cg)))
     with torch.cuda.device(x.device):
-        _lib.call("svnet_vn_std_pool_f32", _call.p(x), _call.p(cloud), _call.p(y), _call.p(w_lin), B, N, C, Cg, Cy, _call.p(ws), ws.numel(), _call.p(out),
+        _lib.call(_entry("std_pool", "f32", wide), _call.p(x), _call.p(cloud), _call.p(y), _call.p(w_lin), B, N, C, Cg, Cy, _call.p(ws), ws.numel(), _call.p(out),
                   _call.stream())
     return out
 
 
-def supported_coords(N, C, Cy):
+def supported_coords(N, C, Cy, wide=False):
     """Whether the per-point coordinates kernel takes these widths (vn_std_coords, limits)."""
-    return bool(_lib.lib().svnet_vn_std_coords_supported(int(N), int(C), int(Cy)))
+    return _ask("std_coords", wide, N, C, Cy)
 
 
-def vn_std_coords(x, y, w_lin, out=None):
+def supported_coords_wide(N, C, Cy):
+    """supported_coords in the wide envelope."""
+    return supported_coords(N, C, Cy, wide=True)
+
+
+def vn_std_coords(x, y, w_lin, out=None, wide=False):
     """x [B,C,3,N], y [B,Cy,3,N] (vn2's output), w_lin [3,Cy] (vn_lin.weight as it lies) -> out [B,3C,N]: out[b, 3 i + k, n] is the
     coordinate e[i,k](n) of x[b,i,:,n] in the frame w_lin y, by the frame rows and coordinates rules of the std-pool stage (module
     docstring) - the same device functions, so out.amax(-1) is vn_std_pool's h[:, :3C] bit for bit.  What VN_DGCNN_PSEG's head reads of
     the levels' features.  One launch on the current stream, stores along n, no host read.  1 <= N <= 32768, 1 <= C, Cy <= 512,
-    B <= 65535 (`supported_coords`).  No argument may require grad."""
+    B <= 65535 (`supported_coords`); wide: C, Cy to MAX_C_WIDE.  No argument may require grad."""
     name = "vn_std_coords"
     B, C, N, _ = _vn.check_entry(name, _WHAT, {"x": x, "y": y, "w_lin": w_lin, "out": out}, ("x", "y", "w_lin", "out"))
     Cy = _vn.frame_shapes(name, y, w_lin, B, N)
     shape = (B, 3 * C, N)
     _vn.check_out(name, out, shape, "[B,3C,N]", (x, y, w_lin, out))
-    if B > MAX_B or not supported_coords(N, C, Cy):
+    if B > MAX_B or not supported_coords(N, C, Cy, wide):
         raise _lib.SvnetHipError("%s: B = %d, N = %d, C = %d, Cy = %d is not supported (B <= %d, 1 <= N <= %d, 1 <= C, Cy <= %d)"
-                                 % (name, B, N, C, Cy, MAX_B, _pointset.MAX_N, MAX_C))
+                                 % (name, B, N, C, Cy, MAX_B, _pointset.MAX_N, _widest(wide)[0]))
     if out is None:
         out = torch.empty(*shape, dtype=_F32, device=x.device)
     with torch.cuda.device(x.device):
-        _lib.call("svnet_vn_std_coords_f32", _call.p(x), _call.p(y), _call.p(w_lin), B, N, C, Cy, _call.p(out), _call.stream())
+        _lib.call(_entry("std_coords", "f32", wide), _call.p(x), _call.p(y), _call.p(w_lin), B, N, C, Cy, _call.p(out), _call.stream())
     return out
 
 
-def std_tail(local, vn1, vn2, w_lin, workspace):
+def std_tail(local, vn1, vn2, w_lin, workspace, wide=False):
     """What follows the local features [B,C,3,N] in every vector-neuron model: the cloud mean, vn1 on [local | mean] with the mean as
     its constant channels, vn2, and the standardise-and-pool stage in the frame w_lin y -> (m [B,C,3], y [B,Cy,3,N], h [B, 12 C]).
-    Through the public entries, with their checks; workspace: the caller's _Workspace for the stage's partials."""
-    m = vn_cloud_mean(local)
+    Through the public entries, with their checks; workspace: the caller's _Workspace for the stage's partials.  wide: the mean and
+    the pool in the wide envelope (vn1 and vn2 carry their own)."""
+    m = vn_cloud_mean(local, wide=wide)
     y = vn_point(vn_point(local, vn1, cloud=m), vn2)
-    return m, y, vn_std_pool(local, y, w_lin, cloud=m, workspace=workspace)
+    return m, y, vn_std_pool(local, y, w_lin, cloud=m, workspace=workspace, wide=wide)
 
 
 class FusedVNTail(_vn.EvalOnly):
