@@ -45,9 +45,9 @@ int svnet_slices_sum_f64(double* buf, int64_t L, void* stream);
 
 /* ABI version = 100 * round-of-change + serial.  It changes whenever an entry point gains / loses an argument or a caller-owned buffer
  * changes its required length (200: sliced accumulators, SVNET_SLICED_LEN; 400: this header; 401: the totals of a sliced accumulator are
- * written by its consumer, svnet_slices_sum_*; 402: GX of svnet_v2s_bwd_*, gw of svnet_xyzblock_bwd_f32 and col_sum of svnet_gemm_f32 are sliced accumulators; 403: svnet_binweight_grad_f32 takes sliced inputs; 421: svnet_three_nn_f32, svnet_three_interpolate_f32; 422: svnet_ball_query_f32, svnet_group_points_f32; 423: svnet_vlinear_stats_f32 is gone; 424: svnet_edgeblock_fwd_tier, svnet_edgeblock_bwd_tier, svnet_edgeblock_wgrad_tier, svnet_xyzblock_tier; 425: svnet_pointset_reverse_i32, svnet_three_interpolate_bwd_f32, svnet_group_points_bwd_f32; 426: wbt of svnet_edgeblock_wbt_bf16 is 512 values longer, the all-zero fragment; 427: svnet_ball_query_msg_f32, svnet_group_points_msg_f32, svnet_group_points_msg_bwd_f32; 428: svnet_sa_fold_f32, svnet_sa_fused_f32; 429: svnet_fp_fused_f32, svnet_fp_fused_supported, svnet_fp_fused_rows_tile; 430: svnet_sa_global_f32, svnet_sa_global_supported, svnet_sa_global_rows_tile; 431: svnet_pool_gather_attr_f32, the attribute fields attr, A, attr_vectors, attr_out at the end of svnet_batch_desc; 432: svnet_vn_fold_f32, svnet_vn_tables_f32, svnet_vn_edge_mean_f32, svnet_vn_supported, svnet_vn_workspace_bytes; 433: svnet_vn_point_supported, svnet_vn_point_workspace_bytes, svnet_vn_point_fold_f32, svnet_vn_point_f32, svnet_vn_cloud_mean_f32, svnet_vn_std_pool_supported, svnet_vn_std_pool_workspace_bytes, svnet_vn_std_pool_f32; 434: svnet_vn_edge2_supported, svnet_vn_edge2_mean_f32, svnet_vn_std_coords_supported, svnet_vn_std_coords_f32; 435: svnet_vn_cross_supported, svnet_vn_cross_fold_f32, svnet_vn_edge_cross_mean_f32, svnet_vn_point_norm_supported, svnet_vn_point_norm_fold_f32, svnet_vn_point_norm_f32; 436: svnet_gemm_tier, svnet_gemm_variant; 437: svnet_vn_point_wide_supported, svnet_vn_point_wide_workspace_bytes, svnet_vn_point_wide_fold_f32, svnet_vn_point_wide_f32, svnet_vn_point_norm_wide_supported, svnet_vn_point_norm_wide_fold_f32, svnet_vn_point_norm_wide_f32, svnet_vn_cloud_mean_wide_f32, svnet_vn_std_pool_wide_supported, svnet_vn_std_pool_wide_workspace_bytes, svnet_vn_std_pool_wide_f32, svnet_vn_std_coords_wide_supported, svnet_vn_std_coords_wide_f32).  svnet_version() returns the value the
+ * written by its consumer, svnet_slices_sum_*; 402: GX of svnet_v2s_bwd_*, gw of svnet_xyzblock_bwd_f32 and col_sum of svnet_gemm_f32 are sliced accumulators; 403: svnet_binweight_grad_f32 takes sliced inputs; 421: svnet_three_nn_f32, svnet_three_interpolate_f32; 422: svnet_ball_query_f32, svnet_group_points_f32; 423: svnet_vlinear_stats_f32 is gone; 424: svnet_edgeblock_fwd_tier, svnet_edgeblock_bwd_tier, svnet_edgeblock_wgrad_tier, svnet_xyzblock_tier; 425: svnet_pointset_reverse_i32, svnet_three_interpolate_bwd_f32, svnet_group_points_bwd_f32; 426: wbt of svnet_edgeblock_wbt_bf16 is 512 values longer, the all-zero fragment; 427: svnet_ball_query_msg_f32, svnet_group_points_msg_f32, svnet_group_points_msg_bwd_f32; 428: svnet_sa_fold_f32, svnet_sa_fused_f32; 429: svnet_fp_fused_f32, svnet_fp_fused_supported, svnet_fp_fused_rows_tile; 430: svnet_sa_global_f32, svnet_sa_global_supported, svnet_sa_global_rows_tile; 431: svnet_pool_gather_attr_f32, the attribute fields attr, A, attr_vectors, attr_out at the end of svnet_batch_desc; 432: svnet_vn_fold_f32, svnet_vn_tables_f32, svnet_vn_edge_mean_f32, svnet_vn_supported, svnet_vn_workspace_bytes; 433: svnet_vn_point_supported, svnet_vn_point_workspace_bytes, svnet_vn_point_fold_f32, svnet_vn_point_f32, svnet_vn_cloud_mean_f32, svnet_vn_std_pool_supported, svnet_vn_std_pool_workspace_bytes, svnet_vn_std_pool_f32; 434: svnet_vn_edge2_supported, svnet_vn_edge2_mean_f32, svnet_vn_std_coords_supported, svnet_vn_std_coords_f32; 435: svnet_vn_cross_supported, svnet_vn_cross_fold_f32, svnet_vn_edge_cross_mean_f32, svnet_vn_point_norm_supported, svnet_vn_point_norm_fold_f32, svnet_vn_point_norm_f32; 436: svnet_gemm_tier, svnet_gemm_variant; 437: svnet_vn_point_wide_supported, svnet_vn_point_wide_workspace_bytes, svnet_vn_point_wide_fold_f32, svnet_vn_point_wide_f32, svnet_vn_point_norm_wide_supported, svnet_vn_point_norm_wide_fold_f32, svnet_vn_point_norm_wide_f32, svnet_vn_cloud_mean_wide_f32, svnet_vn_std_pool_wide_supported, svnet_vn_std_pool_wide_workspace_bytes, svnet_vn_std_pool_wide_f32, svnet_vn_std_coords_wide_supported, svnet_vn_std_coords_wide_f32; 438: svnet_bi_packed_bytes, svnet_bi_fold_f32, svnet_bi_chain_supported, svnet_bi_chain_rows_tile, svnet_bi_chain_workspace_bytes, svnet_bi_chain_f32).  svnet_version() returns the value the
  * library was BUILT with: a caller compiled against another header must refuse to run (svnet_amd/_lib.py does).                   */
-#define SVNET_ABI_VERSION 437
+#define SVNET_ABI_VERSION 438
 int svnet_version(void);
 const char* svnet_last_error(void);
 
@@ -1199,6 +1199,46 @@ int svnet_vn_std_pool_wide_f32(const float* x, const float* g, const float* y, c
 int svnet_vn_std_coords_wide_supported(int64_t N, int64_t C, int64_t Cy);
 int svnet_vn_std_coords_wide_f32(const float* x, const float* y, const float* w_lin, int64_t B, int64_t N, int64_t C, int64_t Cy, float* e,
                                  void* stream);
+
+/* ------------------------------------------------------------------ fused binary chain for inference (models/bipointnet.py in eval mode:
+ * the shared binary MLP of BiSTN3d, BiSTNkd and BiPointNetEncoder - Conv1d(BiLinearLSR) + BatchNorm1d + hardtanh per layer - with its
+ * optional bmm(x^T, T) in front and its maximum over the cloud behind).  fl() is rounding to fp32; every operation is rounded once;
+ * nothing is contracted but the stated fmaf; inputs are assumed finite.  sgn(0) = 0: ternary, as everywhere in this library.
+ * svnet_bi_fold_f32: one BiLinearLSR W [O,K], its 0-dim scale (a device pointer) and BatchNorm gamma, beta, running_mean, running_var
+ *     [O] - or all four NULL - in one launch of one workgroup, no host read:
+ *         S = the float64 sum of W: lane t of 1024 adds W[t], W[t + 1024], .. in that order (row-major flat index), then the tree
+ *             sh[i] += sh[i + s] for s = 512, 256 .. 1;   m = fl(S / (O K)) (the float64 quotient, rounded once)
+ *         S[o,k] = sgn(fl(W[o,k] - m))
+ *         with BatchNorm: invstd and s = fl(gamma invstd) as svnet_sa_fold_f32; a[o] = fl(scale s[o]); b[o] = fl(beta[o] - fl(mean[o] s[o]))
+ *         without: a[o] = scale, b[o] = +0
+ *     -> w_i8 (NULL to skip; svnet_bi_packed_bytes(O, K) bytes, K <= 512, the signs as int8 [32 ceil(O/32)][32 ceil(K/32)], zero filled,
+ *        O <= 2048), the form svnet_bi_chain_f32 reads; s_f32 (NULL to skip): the signs as floats [O,K], for svnet_binweight_prepare_f32
+ *        and the existing binary linear entries (the fully connected layers behind a maximum); ab: a [O] | b [O].  O K <= 2^24.
+ * svnet_bi_chain_f32: x [B,C0,N] channel-first, trans [B,C0,C0] or NULL, L layers of widths[l] (a HOST array), w and ab HOST arrays of L
+ *     device pointers: a binary layer's w_i8 and a | b; with first_fp the first layer's Wf [O,C0] and bf [O] of svnet_sa_fold_f32 (the
+ *     Linear's bias is its b).  Per cloud and point n:
+ *         u[j] = x[j,n] bit for bit without trans; with it u[j] = +0, then for c ascending u[j] = fmaf(x[c,n], trans[c,j], u[j])
+ *         fp layer:      t[o] = bf[o]; for c ascending t[o] = fmaf(u[c], Wf[o,c], t[o])
+ *         binary layer:  d[o] = sum_c sgn(h[c]) S[o,c], an exact integer; t[o] = fmaf((float)d[o], a[o], b[o]); the next layer reads h = t
+ *         pool = 0:      out[b,o,n] = t[o], clamped into [-1,1] with clamp set, out [B,O,N]
+ *         pool = 1:      out[b,o] = fl(max over n < N of t_n[o] + offset), out [B,O]; order-free, no float atomics: the kernel keeps
+ *                        the integer extreme of d per channel and tile (max where a >= 0, min where a < 0: t is monotone in d), a
+ *                        cloud of more than svnet_bi_chain_rows_tile points combines its tiles' partial maxima in a finishing launch
+ *                        of the same call, through `workspace` (svnet_bi_chain_workspace_bytes(B, N, O): 0 for one tile).
+ *     No host read, no atomics; capturable; two runs give the same bits.
+ * svnet_bi_chain_supported (1 / 0, a pure host function): 1 <= N <= 32768, 1 <= L <= 4, C0 <= 64 with trans or first_fp, the fp layer's
+ *     width <= 512, every binary layer's input width <= 512, the last width <= 2048.
+ * Errors: a null pointer, B outside 1 .. 65535 or a workspace that is too small is SVNET_E_ARG, a shape outside the limits
+ * SVNET_E_UNSUPPORTED.                                                                                                             */
+size_t svnet_bi_packed_bytes(int64_t O, int64_t K);
+int svnet_bi_fold_f32(const float* W, const float* scale, const float* gamma, const float* beta, const float* running_mean,
+                      const float* running_var, int64_t O, int64_t K, float eps, int8_t* w_i8, float* s_f32, float* ab, void* stream);
+int svnet_bi_chain_supported(int64_t C0, int64_t N, int64_t L, const int64_t* widths, int first_fp, int has_trans);
+int svnet_bi_chain_rows_tile(void);
+size_t svnet_bi_chain_workspace_bytes(int64_t B, int64_t N, int64_t O);
+int svnet_bi_chain_f32(const float* x, const float* trans, int64_t B, int64_t C0, int64_t N, int64_t L, const int64_t* widths, int first_fp,
+                       const void* w, const void* ab, int pool, int clamp, float offset, void* workspace, size_t workspace_bytes, float* out,
+                       void* stream);
 
 /* ------------------------------------------------------------------ epoch metrics (main_cls_dgcnn.py:187-251, main_partseg_dgcnn.py:185-279,
  * utils.py:68-91 calculate_shape_IoU; the accuracy scores of sklearn.metrics are functions of the confusion matrix)
