@@ -45,9 +45,9 @@ int svnet_slices_sum_f64(double* buf, int64_t L, void* stream);
 
 /* ABI version = 100 * round-of-change + serial.  It changes whenever an entry point gains / loses an argument or a caller-owned buffer
  * changes its required length (200: sliced accumulators, SVNET_SLICED_LEN; 400: this header; 401: the totals of a sliced accumulator are
- * written by its consumer, svnet_slices_sum_*; 402: GX of svnet_v2s_bwd_*, gw of svnet_xyzblock_bwd_f32 and col_sum of svnet_gemm_f32 are sliced accumulators; 403: svnet_binweight_grad_f32 takes sliced inputs; 421: svnet_three_nn_f32, svnet_three_interpolate_f32; 422: svnet_ball_query_f32, svnet_group_points_f32; 423: svnet_vlinear_stats_f32 is gone; 424: svnet_edgeblock_fwd_tier, svnet_edgeblock_bwd_tier, svnet_edgeblock_wgrad_tier, svnet_xyzblock_tier; 425: svnet_pointset_reverse_i32, svnet_three_interpolate_bwd_f32, svnet_group_points_bwd_f32; 426: wbt of svnet_edgeblock_wbt_bf16 is 512 values longer, the all-zero fragment; 427: svnet_ball_query_msg_f32, svnet_group_points_msg_f32, svnet_group_points_msg_bwd_f32; 428: svnet_sa_fold_f32, svnet_sa_fused_f32; 429: svnet_fp_fused_f32, svnet_fp_fused_supported, svnet_fp_fused_rows_tile; 430: svnet_sa_global_f32, svnet_sa_global_supported, svnet_sa_global_rows_tile; 431: svnet_pool_gather_attr_f32, the attribute fields attr, A, attr_vectors, attr_out at the end of svnet_batch_desc; 432: svnet_vn_fold_f32, svnet_vn_tables_f32, svnet_vn_edge_mean_f32, svnet_vn_supported, svnet_vn_workspace_bytes; 433: svnet_vn_point_supported, svnet_vn_point_workspace_bytes, svnet_vn_point_fold_f32, svnet_vn_point_f32, svnet_vn_cloud_mean_f32, svnet_vn_std_pool_supported, svnet_vn_std_pool_workspace_bytes, svnet_vn_std_pool_f32; 434: svnet_vn_edge2_supported, svnet_vn_edge2_mean_f32, svnet_vn_std_coords_supported, svnet_vn_std_coords_f32; 435: svnet_vn_cross_supported, svnet_vn_cross_fold_f32, svnet_vn_edge_cross_mean_f32, svnet_vn_point_norm_supported, svnet_vn_point_norm_fold_f32, svnet_vn_point_norm_f32; 436: svnet_gemm_tier, svnet_gemm_variant; 437: svnet_vn_point_wide_supported, svnet_vn_point_wide_workspace_bytes, svnet_vn_point_wide_fold_f32, svnet_vn_point_wide_f32, svnet_vn_point_norm_wide_supported, svnet_vn_point_norm_wide_fold_f32, svnet_vn_point_norm_wide_f32, svnet_vn_cloud_mean_wide_f32, svnet_vn_std_pool_wide_supported, svnet_vn_std_pool_wide_workspace_bytes, svnet_vn_std_pool_wide_f32, svnet_vn_std_coords_wide_supported, svnet_vn_std_coords_wide_f32; 438: svnet_bi_packed_bytes, svnet_bi_fold_f32, svnet_bi_chain_supported, svnet_bi_chain_rows_tile, svnet_bi_chain_workspace_bytes, svnet_bi_chain_f32).  svnet_version() returns the value the
+ * written by its consumer, svnet_slices_sum_*; 402: GX of svnet_v2s_bwd_*, gw of svnet_xyzblock_bwd_f32 and col_sum of svnet_gemm_f32 are sliced accumulators; 403: svnet_binweight_grad_f32 takes sliced inputs; 421: svnet_three_nn_f32, svnet_three_interpolate_f32; 422: svnet_ball_query_f32, svnet_group_points_f32; 423: svnet_vlinear_stats_f32 is gone; 424: svnet_edgeblock_fwd_tier, svnet_edgeblock_bwd_tier, svnet_edgeblock_wgrad_tier, svnet_xyzblock_tier; 425: svnet_pointset_reverse_i32, svnet_three_interpolate_bwd_f32, svnet_group_points_bwd_f32; 426: wbt of svnet_edgeblock_wbt_bf16 is 512 values longer, the all-zero fragment; 427: svnet_ball_query_msg_f32, svnet_group_points_msg_f32, svnet_group_points_msg_bwd_f32; 428: svnet_sa_fold_f32, svnet_sa_fused_f32; 429: svnet_fp_fused_f32, svnet_fp_fused_supported, svnet_fp_fused_rows_tile; 430: svnet_sa_global_f32, svnet_sa_global_supported, svnet_sa_global_rows_tile; 431: svnet_pool_gather_attr_f32, the attribute fields attr, A, attr_vectors, attr_out at the end of svnet_batch_desc; 432: svnet_vn_fold_f32, svnet_vn_tables_f32, svnet_vn_edge_mean_f32, svnet_vn_supported, svnet_vn_workspace_bytes; 433: svnet_vn_point_supported, svnet_vn_point_workspace_bytes, svnet_vn_point_fold_f32, svnet_vn_point_f32, svnet_vn_cloud_mean_f32, svnet_vn_std_pool_supported, svnet_vn_std_pool_workspace_bytes, svnet_vn_std_pool_f32; 434: svnet_vn_edge2_supported, svnet_vn_edge2_mean_f32, svnet_vn_std_coords_supported, svnet_vn_std_coords_f32; 435: svnet_vn_cross_supported, svnet_vn_cross_fold_f32, svnet_vn_edge_cross_mean_f32, svnet_vn_point_norm_supported, svnet_vn_point_norm_fold_f32, svnet_vn_point_norm_f32; 436: svnet_gemm_tier, svnet_gemm_variant; 437: svnet_vn_point_wide_supported, svnet_vn_point_wide_workspace_bytes, svnet_vn_point_wide_fold_f32, svnet_vn_point_wide_f32, svnet_vn_point_norm_wide_supported, svnet_vn_point_norm_wide_fold_f32, svnet_vn_point_norm_wide_f32, svnet_vn_cloud_mean_wide_f32, svnet_vn_std_pool_wide_supported, svnet_vn_std_pool_wide_workspace_bytes, svnet_vn_std_pool_wide_f32, svnet_vn_std_coords_wide_supported, svnet_vn_std_coords_wide_f32; 438: svnet_bi_packed_bytes, svnet_bi_fold_f32, svnet_bi_chain_supported, svnet_bi_chain_rows_tile, svnet_bi_chain_workspace_bytes, svnet_bi_chain_f32; 439: svnet_binlinear_tier, svnet_binlinear_i8_tier).  svnet_version() returns the value the
  * library was BUILT with: a caller compiled against another header must refuse to run (svnet_amd/_lib.py does).                   */
-#define SVNET_ABI_VERSION 438
+#define SVNET_ABI_VERSION 439
 int svnet_version(void);
 const char* svnet_last_error(void);
 
@@ -204,6 +204,32 @@ int svnet_binweight_prepare_f32(const float* W, const float* scale, int64_t O, i
 int svnet_binlinear_fwd_f32(const float* x, int64_t ldx, const float* beta, const uint64_t* w_sign,
                             const uint64_t* w_nz, const float* scale, const float* bias, int64_t M, int64_t K,
                             int64_t O, float* y, uint64_t* x_sign, uint64_t* x_nz, uint64_t* x_ste, void* stream);
+/* Which kernel svnet_binlinear_fwd_f32 runs a shape on.  A pure host function of the sizes: nothing is dereferenced or launched, `plan` is
+ * a HOST pointer, and svnet_binlinear_fwd_f32 executes exactly what it reports.  Sizes that svnet_binlinear_fwd_f32 refuses give its
+ * negative SVNET_E_* code (and the same svnet_last_error).  K > 2176 (34 words of 64 columns: what a row tile's planes may take in LDS)
+ * is processed in `nchunk` column chunks of `wpc` words, the last one possibly shorter; the integer count of the earlier chunks
+ * travels in y as int32.  `chunk` (0 .. nchunk - 1) selects the chunk that the fields from `chunk` on describe.                      */
+#define SVNET_BINLINEAR_TILE_SPLIT 1 /* at most 8 row tiles, O > 32: one launch, ceil(O / 32) workgroups of 32 channels per row tile        */
+#define SVNET_BINLINEAR_GROUPS 2     /* O > 256, tiles * ceil(O / 256) <= 4096: one launch, one workgroup per (tile, 256 channels)            */
+#define SVNET_BINLINEAR_LOOP 3       /* everything else: one launch per 256 * ppm channels (o_base), the grid capped at 2048 row tiles      */
+typedef struct svnet_binlinear_plan {
+    int nchunk;            /* column chunks: ceil(ceil(K / 64) / 34)                                            */
+    int wpc;               /* 64-bit words per chunk: ceil(ceil(K / 64) / nchunk)                               */
+    int chunk;             /* the chunk described from here on                                                  */
+    int64_t col0;          /* its first column: chunk * wpc * 64                                                */
+    int kc;                /* its columns                                                                       */
+    int kw;                /* its words: ceil(kc / 64)                                                          */
+    int kwm;               /* the kernel template's word bound: 2, 4, 8, 16 or 34 (34: the WIDE form, kw > 16)  */
+    int ppm;               /* output channels per thread: 2 when kw <= 8, O > 256 and tiles * ceil(O / 256) > 4096, else 1 */
+    int form;              /* SVNET_BINLINEAR_TILE_SPLIT / _GROUPS / _LOOP                                      */
+    int og_shift;          /* log2 of the threads that share one row: 5 (TILE_SPLIT), 8 (GROUPS), 5 .. 8 by O (LOOP) */
+    int o_blocks;          /* workgroups per row tile                                                           */
+    int launches;          /* kernel launches of this chunk (0 when M == 0)                                     */
+    int64_t grid_tiles;    /* row tiles the grid takes at once (grid = grid_tiles * o_blocks workgroups)        */
+    int ymode;             /* bit 0: add the int32 count kept in y, bit 1: keep the count instead of scaling it */
+    size_t lds_bytes;      /* dynamic LDS per workgroup: 3 planes x 64 rows x kw words                          */
+} svnet_binlinear_plan;
+int svnet_binlinear_tier(int64_t M, int64_t K, int64_t O, int64_t chunk, svnet_binlinear_plan* plan);
 /* The same layer on the matrix cores, for many rows (v_mfma_i32_32x32x32_i8 on int8 ternary operands, exact int32 counts: outputs
  * and saved planes identical to svnet_binlinear_fwd_f32).  w_i8 = svnet_binweight_pack_i8(W): sign(W) as int8 [O][128*ceil(K/128)],
  * every 128-column chunk in the kernel's reduction order, zero padded (svnet_binweight_i8_bytes bytes).                           */
@@ -214,6 +240,17 @@ int svnet_binweight_pack_i8(const float* W, int64_t O, int64_t K, int8_t* w_i8, 
 int svnet_binlinear_i8_fwd_f32(const float* x, int64_t ldx, const float* beta, const int8_t* w_i8, const float* scale,
                                const float* bias, int64_t M, int64_t K, int64_t O, float* y, uint64_t* x_sign, uint64_t* x_nz,
                                uint64_t* x_ste, double* col_sums, void* stream);
+/* Which template and grid svnet_binlinear_i8_fwd_f32 / svnet_binlinear_i8_cloud_fwd_f32 run a shape on (col_sums != 0: with column
+ * sums): a pure host function like svnet_binlinear_tier, `plan` a HOST pointer; refused sizes give their SVNET_E_* code.            */
+typedef struct svnet_binlinear_i8_plan {
+    int ntw;               /* 32-column tiles per wave: 1 (O <= 128), 2 (O <= 256), 4; a workgroup takes 128 * ntw channels */
+    int64_t grid_x;        /* row blocks of 128                                                                 */
+    int grid_y;            /* column groups of 128 * ntw channels                                               */
+    int nchunks;           /* 128-column chunks of K                                                            */
+    int kp;                /* 128 * nchunks: the row length of w_i8                                             */
+    size_t lds_bytes;      /* dynamic LDS per workgroup                                                         */
+} svnet_binlinear_i8_plan;
+int svnet_binlinear_i8_tier(int64_t M, int64_t K, int64_t O, int col_sums, svnet_binlinear_i8_plan* plan);
 /* The same layer when part of its input is CONSTANT over the rows of a cloud (the broadcast half of a concatenation:
  * sv_dgcnn_partseg.py:115-118 `repeat` + `cat`, sv_pointnet_cls.py:43-52 `expand_as` + `svcat`): x [M, K] holds only the per-point
  * columns, cloud_n [M / rows_per_cloud, O] the integer counts (as floats) of the per-cloud columns - svnet_binlinear_fwd_f32 over the

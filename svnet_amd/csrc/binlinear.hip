@@ -11,11 +11,11 @@
 // channel live in registers for the whole kernel, and row bit-planes are staged in LDS so that all
 // four waves of a workgroup share one packing pass.  HBM traffic = read x once + write y once
 // (+ 3 bits per input element of saved planes in training, instead of keeping the fp32 input).
-#include "common.h"
+#include "binlinear_plan.h"
 
 namespace {
 
-constexpr int ROWS = 64;  // rows per workgroup tile
+constexpr int ROWS = BL_ROWS;  // rows per workgroup tile
 
 __global__ __launch_bounds__(256) void binweight_values_kernel(const float* __restrict__ W, const float* __restrict__ scale,
                                                                int64_t O, int64_t K, float* __restrict__ w_b,
@@ -273,33 +273,15 @@ __global__ __launch_bounds__(256) void binweight_grad_kernel(const float* __rest
     }
 }
 
+// every launch of one K chunk, as binlinear_plan() (binlinear_plan.h) laid it out
 template <int KWM, int PPM>
-void launch_fwd(const float* x, int64_t ldx, const float* beta, const uint64_t* w_sign, const uint64_t* w_nz, const float* scale,
-                const float* bias, int64_t M, int K, int O, int KW, float* y, uint64_t* xs, uint64_t* xz, uint64_t* xt,
-                int wld, int64_t pld, int ymode, hipStream_t st) {
-    int og_shift = 5;
-    while ((1 << og_shift) < O && og_shift < 8) ++og_shift;
-    const int64_t tiles = svnet_cdiv(M, ROWS);
-    const size_t lds_bytes = (size_t)3 * ROWS * KW * sizeof(uint64_t);
-    if (PPM == 1 && tiles <= 8 && O > 32) {
-        // small M: one launch, ceil(O/32) workgroups per row tile (each repeats the cheap packing pass of its tile)
-        const int o_blocks = (O + 31) / 32;
-        hipLaunchKernelGGL((binlinear_fwd_kernel<KWM, PPM>), dim3((unsigned)(tiles * o_blocks)), dim3(256), lds_bytes, st, x, ldx, beta,
-                           w_sign, w_nz, scale, bias, M, K, O, 0, o_blocks, KW, 5, y, xs, xz, xt, wld, pld, ymode);
-        return;
-    }
-    if (PPM == 1 && O > 256 && tiles * ((O + 255) / 256) <= 256 * 16) {
-        // a few hundred row tiles (conv5: 512 tiles x 512 channels): one workgroup per (tile, 256 channels) in ONE launch, so that the
-        // grid has >= 4 workgroups per CU (2 per CU - 2 waves per SIMD - left every load latency of the packing pass exposed)
-        const int o_blocks = (O + 255) / 256;
-        hipLaunchKernelGGL((binlinear_fwd_kernel<KWM, PPM>), dim3((unsigned)(tiles * o_blocks)), dim3(256), lds_bytes, st, x, ldx, beta,
-                           w_sign, w_nz, scale, bias, M, K, O, 0, o_blocks, KW, 8, y, xs, xz, xt, wld, pld, ymode);
-        return;
-    }
-    const unsigned grid = (unsigned)(tiles < 256 * 8 ? tiles : 256 * 8);
-    for (int o_base = 0; o_base < O; o_base += 256 * PPM)
-        hipLaunchKernelGGL((binlinear_fwd_kernel<KWM, PPM>), dim3(grid), dim3(256), lds_bytes, st, x, ldx, beta, w_sign, w_nz, scale,
-                           bias, M, K, O, o_base, 1, KW, og_shift, y, xs, xz, xt, wld, pld, ymode);
+void launch_fwd(const svnet_binlinear_plan& p, const float* x, int64_t ldx, const float* beta, const uint64_t* w_sign, const uint64_t* w_nz,
+                const float* scale, const float* bias, int64_t M, int O, float* y, uint64_t* xs, uint64_t* xz, uint64_t* xt, int wld,
+                int64_t pld, hipStream_t st) {
+    for (int l = 0; l < p.launches; ++l)
+        hipLaunchKernelGGL((binlinear_fwd_kernel<KWM, PPM>), dim3((unsigned)(p.grid_tiles * p.o_blocks)), dim3(256), p.lds_bytes, st, x, ldx,
+                           beta, w_sign, w_nz, scale, bias, M, p.kc, O, l * 256 * PPM, p.o_blocks, p.kw, p.og_shift, y, xs, xz, xt, wld, pld,
+                           p.ymode);
 }
 
 }  // namespace
@@ -326,40 +308,41 @@ extern "C" int svnet_binlinear_fwd_f32(const float* x, int64_t ldx, const float*
                                        const uint64_t* w_nz, const float* scale, const float* bias, int64_t M, int64_t K,
                                        int64_t O, float* y, uint64_t* x_sign, uint64_t* x_nz, uint64_t* x_ste, void* stream) {
     SVNET_REQUIRE(x && beta && w_sign && w_nz && scale && y, SVNET_E_ARG, "svnet_binlinear_fwd_f32: null pointer");
-    SVNET_REQUIRE(M >= 0 && K > 0 && O > 0 && ldx >= K, SVNET_E_ARG, "svnet_binlinear_fwd_f32: bad sizes");
+    svnet_binlinear_plan p;
+    int rc = binlinear_plan(M, K, O, 0, p);                   // (sizes and limits)
+    if (rc != SVNET_OK) return rc;
+    SVNET_REQUIRE(ldx >= K, SVNET_E_ARG, "svnet_binlinear_fwd_f32: bad sizes");
     const bool any = x_sign || x_nz || x_ste, all = x_sign && x_nz && x_ste;
     SVNET_REQUIRE(!any || all, SVNET_E_ARG, "svnet_binlinear_fwd_f32: pass all three saved planes or none");
-    SVNET_REQUIRE(K <= (1 << 20) && O <= (1 << 20), SVNET_E_UNSUPPORTED, "svnet_binlinear_fwd_f32: K=%lld, O=%lld too large", (long long)K,
-                  (long long)O);
-    const int64_t KWF = svnet_cdiv(K, 64);                    // words per full row (= weight plane row stride)
     if (M == 0) return SVNET_OK;
+    const int64_t KWF = svnet_cdiv(K, 64);                    // words per full row (= weight plane row stride)
     hipStream_t st = (hipStream_t)stream;
-    // K > 2176 (34 words: what the row tile's planes may take in LDS) is processed in chunks of whole words; the integer count of
-    // the earlier chunks travels in y (int32), the last chunk applies scale and bias.  O > 256 (512 with two channels per thread)
-    // takes several launches over the output channels, each of which repeats the (cheap) packing pass.
-    const int64_t nchunk = svnet_cdiv(KWF, 34);
-    const int64_t wpc = svnet_cdiv(KWF, nchunk);              // words per chunk (<= 34)
-    for (int64_t c = 0; c < nchunk; ++c) {
-        const int64_t w0 = c * wpc, col0 = w0 * 64;
-        const int64_t Kc = (c + 1 == nchunk) ? K - col0 : wpc * 64;
-        const int64_t KW = svnet_cdiv(Kc, 64);
-        const int ymode = (c > 0 ? 1 : 0) | (c + 1 < nchunk ? 2 : 0);
-#define SVNET_BL(KWM, PPM)                                                                                                          \
-    launch_fwd<KWM, PPM>(x + col0, ldx, beta + col0, w_sign + w0, w_nz + w0, scale, bias, M, (int)Kc, (int)O, (int)KW, y,          \
-                         x_sign ? x_sign + col0 : nullptr, x_nz ? x_nz + col0 : nullptr, x_ste ? x_ste + col0 : nullptr, (int)KWF, K, \
-                         ymode, st)
-        // two output channels per thread only when there are row tiles in plenty; fewer tiles take a one-launch split over the
-        // output channels (PPM = 1) so that the grid still fills the chip
-        const bool two = O > 256 && svnet_cdiv(M, ROWS) * ((O + 255) / 256) > 256 * 16;
-        if (KW <= 2) { if (two) SVNET_BL(2, 2); else SVNET_BL(2, 1); }
-        else if (KW <= 4) { if (two) SVNET_BL(4, 2); else SVNET_BL(4, 1); }
-        else if (KW <= 8) { if (two) SVNET_BL(8, 2); else SVNET_BL(8, 1); }
-        else if (KW <= 16) SVNET_BL(16, 1);
-        else SVNET_BL(34, 1);
+    for (int c = 0; c < p.nchunk; ++c) {
+        if (c > 0 && (rc = binlinear_plan(M, K, O, c, p)) != SVNET_OK) return rc;
+        const int64_t w0 = p.col0 / 64, col0 = p.col0;
+#define SVNET_BL(KWM, PPM)                                                                                                       \
+    launch_fwd<KWM, PPM>(p, x + col0, ldx, beta + col0, w_sign + w0, w_nz + w0, scale, bias, M, (int)O, y,                        \
+                         x_sign ? x_sign + col0 : nullptr, x_nz ? x_nz + col0 : nullptr, x_ste ? x_ste + col0 : nullptr, (int)KWF, K, st)
+        switch (p.kwm * 4 + p.ppm) {
+            case 2 * 4 + 1: SVNET_BL(2, 1); break;
+            case 2 * 4 + 2: SVNET_BL(2, 2); break;
+            case 4 * 4 + 1: SVNET_BL(4, 1); break;
+            case 4 * 4 + 2: SVNET_BL(4, 2); break;
+            case 8 * 4 + 1: SVNET_BL(8, 1); break;
+            case 8 * 4 + 2: SVNET_BL(8, 2); break;
+            case 16 * 4 + 1: SVNET_BL(16, 1); break;
+            case BL_MAX_WORDS * 4 + 1: SVNET_BL(BL_MAX_WORDS, 1); break;
+            default: SVNET_REQUIRE(false, SVNET_E_UNSUPPORTED, "svnet_binlinear_fwd_f32: no kernel for KWM=%d, PPM=%d", p.kwm, p.ppm);
+        }
 #undef SVNET_BL
         SVNET_CHECK_LAUNCH("binlinear_fwd_kernel");
     }
     return SVNET_OK;
+}
+
+extern "C" int svnet_binlinear_tier(int64_t M, int64_t K, int64_t O, int64_t chunk, svnet_binlinear_plan* plan) {
+    SVNET_REQUIRE(plan, SVNET_E_ARG, "svnet_binlinear_tier: null plan");
+    return binlinear_plan(M, K, O, chunk, *plan);
 }
 
 extern "C" int svnet_binweight_grad_f32(const float* GX, const float* W, const float* scale, int64_t O, int64_t K,

@@ -12,16 +12,16 @@
 //            planes the backward GEMMs read, written as 32-bit halves;
 //   stage B: 16-byte copies of the pre-packed int8 weights (svnet_binweight_pack_i8);
 //   MFMA   : A and B fragments are 16-byte LDS reads (lane (r, h): row / column r, positions 16h .. 16h+15 of the k-step).
-#include "common.h"
+#include "binlinear_plan.h"
 
 namespace {
 
 typedef __attribute__((ext_vector_type(4))) int i32x4;
 typedef __attribute__((ext_vector_type(16))) int i32x16;
 
-constexpr int BM = 128;            // rows per workgroup
-constexpr int KC = 128;            // columns per chunk
-constexpr int LDA = KC + 16;       // bytes per LDS row (36 dwords: 16-byte reads of 16 consecutive rows hit 64 distinct banks)
+constexpr int BM = BL8_BM;         // rows per workgroup
+constexpr int KC = BL8_KC;         // columns per chunk
+constexpr int LDA = BL8_LDA;       // bytes per LDS row
 
 // (position of column k = 32 j + q of a 128-column chunk in the permuted reduction order: 4 q + j)
 // w_i8p [O][Kp] (Kp = 128 * ceil(K / 128)): sign(W) as int8, every 128-column chunk in the permuted order, zero padded
@@ -258,21 +258,20 @@ static int binlinear_i8_launch(const float* x, int64_t ldx, const float* beta, c
     SVNET_REQUIRE(x && beta && w_i8 && scale && y, SVNET_E_ARG, "svnet_binlinear_i8_fwd_f32: null pointer");
     SVNET_REQUIRE(!cloud_n || (rows_per_cloud > 0 && M % rows_per_cloud == 0), SVNET_E_ARG,
                   "svnet_binlinear_i8_cloud_fwd_f32: rows_per_cloud must divide M");
-    SVNET_REQUIRE(M >= 0 && K > 0 && O > 0 && ldx >= K, SVNET_E_ARG, "svnet_binlinear_i8_fwd_f32: bad sizes");
+    svnet_binlinear_i8_plan p;
+    const int rc = binlinear_i8_plan(M, K, O, col_sums != nullptr, p);       // (sizes and limits; binlinear_plan.h)
+    if (rc != SVNET_OK) return rc;
+    SVNET_REQUIRE(ldx >= K, SVNET_E_ARG, "svnet_binlinear_i8_fwd_f32: bad sizes");
     const bool any = x_sign || x_nz || x_ste, all = x_sign && x_nz && x_ste;
     SVNET_REQUIRE(!any || all, SVNET_E_ARG, "svnet_binlinear_i8_fwd_f32: pass all three saved planes or none");
-    SVNET_REQUIRE(K < (1 << 24) && O < (1 << 24), SVNET_E_UNSUPPORTED, "svnet_binlinear_i8_fwd_f32: K=%lld, O=%lld too large", (long long)K, (long long)O);
-    SVNET_REQUIRE(!col_sums || K <= 46340, SVNET_E_UNSUPPORTED, "svnet_binlinear_i8_fwd_f32: column sums need K <= 46340 (got %lld)", (long long)K);
     if (M == 0) return SVNET_OK;
-    const int Kp = (int)((K + KC - 1) / KC * KC);
-    // 128, 256 or 512 output channels per workgroup (16 waves: one, two or four 32-column tiles per wave)
-    const int ntw = O <= 128 ? 1 : (O <= 256 ? 2 : 4);
-    const dim3 grid((unsigned)svnet_cdiv(M, BM), (unsigned)svnet_cdiv(O, 128 * ntw));
-    const size_t lds = (size_t)BM * LDA + (size_t)128 * ntw * LDA + 3 * BM * 2 * sizeof(uint64_t);
+    const int Kp = p.kp, ntw = p.ntw;
+    const dim3 grid((unsigned)p.grid_x, (unsigned)p.grid_y);
+    const size_t lds = p.lds_bytes;
     bool ok = true;                                      // more than 64 KiB of dynamic LDS needs an explicit opt-in (NTW = 4: 96 KiB), per device
-    if (ntw == 1) SVNET_LDS_OPTIN(ok, BM * LDA + 128 * LDA + 6144, "binlinear_i8_fwd_kernel<1>", reinterpret_cast<const void*>(&binlinear_i8_fwd_kernel<1>));
-    else if (ntw == 2) SVNET_LDS_OPTIN(ok, BM * LDA + 256 * LDA + 6144, "binlinear_i8_fwd_kernel<2>", reinterpret_cast<const void*>(&binlinear_i8_fwd_kernel<2>));
-    else SVNET_LDS_OPTIN(ok, BM * LDA + 512 * LDA + 6144, "binlinear_i8_fwd_kernel<4>", reinterpret_cast<const void*>(&binlinear_i8_fwd_kernel<4>));
+    if (ntw == 1) SVNET_LDS_OPTIN(ok, lds, "binlinear_i8_fwd_kernel<1>", reinterpret_cast<const void*>(&binlinear_i8_fwd_kernel<1>));
+    else if (ntw == 2) SVNET_LDS_OPTIN(ok, lds, "binlinear_i8_fwd_kernel<2>", reinterpret_cast<const void*>(&binlinear_i8_fwd_kernel<2>));
+    else SVNET_LDS_OPTIN(ok, lds, "binlinear_i8_fwd_kernel<4>", reinterpret_cast<const void*>(&binlinear_i8_fwd_kernel<4>));
     if (!ok) return SVNET_E_LAUNCH;
 #define SVNET_BL_LAUNCH(NTW_)                                                                                                          \
     hipLaunchKernelGGL((binlinear_i8_fwd_kernel<NTW_>), grid, dim3(1024), lds, (hipStream_t)stream, x, ldx, beta, w_i8, scale, bias, M, (int)K, \
@@ -284,6 +283,11 @@ static int binlinear_i8_launch(const float* x, int64_t ldx, const float* beta, c
 #undef SVNET_BL_LAUNCH
     SVNET_CHECK_LAUNCH("binlinear_i8_fwd_kernel");
     return SVNET_OK;
+}
+
+extern "C" int svnet_binlinear_i8_tier(int64_t M, int64_t K, int64_t O, int col_sums, svnet_binlinear_i8_plan* plan) {
+    SVNET_REQUIRE(plan, SVNET_E_ARG, "svnet_binlinear_i8_tier: null plan");
+    return binlinear_i8_plan(M, K, O, col_sums, *plan);
 }
 
 extern "C" int svnet_binlinear_i8_fwd_f32(const float* x, int64_t ldx, const float* beta, const int8_t* w_i8, const float* scale,
